@@ -114,6 +114,35 @@ def cpu_baseline(pkg, weights_path, seconds_all, seconds_one):
     return head
 
 
+DUMP_BYTES = 60 * 2 ** 20  # --dump-outputs: at most this much stem data in all
+
+
+def dump_positions(n, tracks):
+    """Sample positions of a stem of n stereo samples that --dump-outputs keeps: all of them (None), or, when the stems of
+    `tracks` tracks would exceed DUMP_BYTES, a fixed seeded sample of them (sorted), the same for every stem."""
+    k = min(n, DUMP_BYTES // (tracks * 4 * 2 * 4))
+    return None if k == n else np.sort(np.random.default_rng(1234).choice(n, size=k, replace=False))
+
+
+def dump_stems(out_dir, stems, n):
+    """--dump-outputs: stems[b][t] = stem t of track b, 2n float32 interleaved (a torch tensor or a numpy array) ->
+    out_dir/stems.npy, float32 (tracks, 4, K, 2) at dump_positions(n, tracks)."""
+    pos = dump_positions(n, len(stems))
+    rows = []
+    for per_track in stems:
+        for s in per_track:
+            if isinstance(s, np.ndarray):
+                v = s.reshape(n, 2)
+                rows.append(v if pos is None else v[pos])
+            else:
+                import torch
+                v = s.view(n, 2)
+                rows.append((v if pos is None else v.index_select(0, torch.from_numpy(pos).to(v.device))).cpu().numpy())
+    os.makedirs(out_dir, exist_ok=True)
+    arr = np.stack(rows).reshape(len(stems), 4, -1, 2).astype(np.float32, copy=False)
+    np.save(os.path.join(out_dir, "stems.npy"), arr)
+
+
 def read_traffic(path):
     """profiles/*pmc_fetch_write_per_kernel.csv -> {kernel name: HBM bytes per launch} (2 x FETCH + WRITE, raw KB)."""
     out = {}
@@ -165,7 +194,12 @@ def main():
     ap.add_argument("--u8-dequant", action="store_true", help="u8 weights dequantised per element (UMX_CREATE_U8_DEQUANT)")
     ap.add_argument("--traffic-csv", default=None, help="rocprofv3 PMC summary to take roofline.traffic from "
                                                         "(default: the newest profiles/r*_pmc_fetch_write_per_kernel.csv)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the stems of the last timed step (rank 0) to DIR/stems.npy: float32 "
+                         "(tracks, 4, K, 2), every sample, or K seeded sample positions of each stem when that exceeds 60 MiB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -226,6 +260,9 @@ def main():
     dd = dist if world > 1 else None
     # W untimed warm-up steps, barrier + synchronize on both sides of exactly K steps, MAX over ranks
     dt = mg.timed_region(step, fence, args.steps, args.warmup, dist=dd, world=world, device=dev)
+    if args.dump_outputs and rank == 0:  # the last timed step's output set, before any further step reuses it
+        last = out_sets[(nstep[0] - 1) % depth]
+        dump_stems(args.dump_outputs, [last[4 * b:4 * b + 4] for b in range(B)], N)
     # per-stage device time from hipEvents on the engine's own streams.  (a) the last two steps of the timed region
     # (one per pipeline slot; consecutive steps overlap there, so a span includes the other slot's kernels -- this is
     # the duration rocprofv3 reports for the same command); (b) extra steps run one at a time afterwards (each kernel
@@ -330,7 +367,7 @@ def main():
         def fence1():
             e1.sync()
             torch.cuda.synchronize()
-        d1 = mg.timed_region(step1, fence1, 16, 4)
+        d1 = mg.timed_region(step1, fence1, args.steps, args.warmup)
         s1 = [d for d in (e1.stage_times(slot=i) for i in range(d1n)) if d]
         lstm1 = sum(sum(d[f"lstm_rec{l}"] for l in range(3)) for d in s1) / (3 * len(s1))
         step1()
@@ -343,7 +380,7 @@ def main():
             step1()
             e1.sync()
             lone.append((time.perf_counter() - t1) * 1e3)
-        # the same 16 back-to-back segments with pinned host buffers in and out
+        # the same back-to-back segments with pinned host buffers in and out
         d1p = None
         try:
             h1 = torch.from_numpy(waves[0]).pin_memory()
@@ -353,7 +390,7 @@ def main():
             def step1p():
                 e1.infer_batch_ptrs([h1.data_ptr()], [N], [o.data_ptr() for o in ho1[kp[0] % d1n]], flags, where="host_async")
                 kp[0] += 1
-            d1p = mg.timed_region(step1p, fence1, 16, 4)
+            d1p = mg.timed_region(step1p, fence1, args.steps, args.warmup)
         except Exception as e:  # noqa: BLE001
             d1p = repr(e)
         # value check: the batched engine's lanes against this engine, both from a reset state on the same audio
@@ -367,10 +404,10 @@ def main():
                 e1.sync()
                 for t in range(4):
                     checked = max(checked, float(np.abs(o1[0][t].cpu().numpy() - check_stems[b][t]).max()))
-        single = {"value": round(16 * (N / 44100.0) / d1, 2), "unit": "x realtime", "ms_per_step": round(d1 / 16 * 1e3, 3),
+        single = {"value": round(args.steps * (N / 44100.0) / d1, 2), "unit": "x realtime", "ms_per_step": round(d1 / args.steps * 1e3, 3),
                   "lone_segment_ms": round(float(np.median(lone)), 3),
-                  "value_pcie": round(16 * (N / 44100.0) / d1p, 2) if isinstance(d1p, float) else None,
-                  "ms_per_step_pcie": round(d1p / 16 * 1e3, 3) if isinstance(d1p, float) else d1p,
+                  "value_pcie": round(args.steps * (N / 44100.0) / d1p, 2) if isinstance(d1p, float) else None,
+                  "ms_per_step_pcie": round(d1p / args.steps * 1e3, 3) if isinstance(d1p, float) else d1p,
                   "tracks_per_gpu": 1, "lstm_kernel": "single-track (VALU, lstm_persistent_kernel)",
                   "lstm_launch_ms": round(lstm1, 4), "lstm_launch_ms_alone": round(sum(alone1[f"lstm_rec{l}"] for l in range(3)) / 3, 4),
                   "checked_max_abs": checked, "checked_lanes": check_lanes if check_stems else None}
@@ -661,8 +698,10 @@ def bench_track_mode(args, pkg, mg, dist, world, rank, local_rank, dev, wpath):
     def fence():
         eng.sync()
         torch.cuda.synchronize()
-    steps, warmup = max(1, min(args.steps, 4)), max(1, min(args.warmup, 1))
+    steps, warmup = args.steps, max(1, min(args.warmup, 1))
     dt = mg.timed_region(step, fence, steps, warmup, dist=dd, world=world, device=dev)
+    if args.dump_outputs and rank == 0:
+        dump_stems(args.dump_outputs, [touts], L)
     if rank == 0:
         nseg = -(-(L + 22050 - 4033) // int(0.75 * N))
         line = {"metric": "realtime-factor (audio-sec/wall-sec) UMX-L 4-stem, 60 s seg", "value": round(steps * secs / dt, 2),

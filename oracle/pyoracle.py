@@ -22,12 +22,10 @@ _fp = C.POINTER(C.c_float)
 
 
 def build(force=False):
-    """make -C oracle (g++ only; seconds).  Libraries that exist are rebuilt when stale only in the build container
-    (where /root/reference exists); on the GPU box the prebuilt files that travelled with the snapshot are used as
-    they are -- importing the checker never compiles anything there unless a library is missing altogether."""
+    """make -C oracle (g++ only; seconds): when a library is missing, or older than the oracle's sources."""
     missing = not (HERE / "liboracle.so").exists() or not (HERE / "liboracle_fast.so").exists()
-    stale = not missing and Path("/root/reference").exists() and \
-        max((HERE / f).stat().st_mtime for f in ("umx_oracle.cpp", "umx_oracle.h")) > (HERE / "liboracle.so").stat().st_mtime
+    stale = not missing and max((HERE / f).stat().st_mtime for f in ("umx_oracle.cpp", "umx_oracle.h")) > \
+        min((HERE / f).stat().st_mtime for f in ("liboracle.so", "liboracle_fast.so"))
     if force or missing or stale:
         subprocess.check_call(["make", "-C", str(HERE)], stdout=subprocess.DEVNULL)
 
