@@ -38,6 +38,12 @@ extern "C" {
 
 /* flags of umx_hip_infer_segment* */
 #define UMX_FLAG_NO_WIENER 0x1      /* BASELINE config 2: mix-phase estimate only (wiener.cpp:96-109) */
+/* Wiener EM iterations per call (flag bits 16-19): the reference's `for (int it = 0; it < WIENER_ITERATIONS; ++it)` of
+ * wiener.cpp:175, with WIENER_ITERATIONS = 1 at wiener.hpp:17; Open-Unmix's `niter`.  A field of 0 means 1 iteration, allowed are
+ * 1 .. 15.  Iteration k >= 2 forms the PSD and the spatial covariances from iteration k - 1's filtered spectrograms and filters the
+ * mixture again.  UMX_FLAG_NO_WIENER ignores it. */
+#define UMX_FLAG_WIENER_ITERS_MASK 0xF0000u
+#define UMX_FLAG_WIENER_ITERS(n) ((((unsigned)(n)) & 0xFu) << 16)
 #define UMX_FLAG_SKIP_TARGET(t) (0x100 << (t)) /* BASELINE config 1 (vocals only = skip 0,1,2) */
 #define UMX_FLAG_LSTM_STEPWISE 0x10 /* one launch per timestep instead of the persistent kernel */
 #define UMX_FLAG_DEBUG_TAPS 0x20    /* keep what only the taps read: the filtered spectrograms for umx_hip_read_tap("y") (the fused kernel does not

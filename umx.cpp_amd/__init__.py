@@ -36,6 +36,16 @@ def FLAG_SKIP_TARGET(t):
     return 0x100 << t
 
 
+FLAG_WIENER_ITERS_MASK = 0xF0000
+
+
+def FLAG_WIENER_ITERS(n):
+    """Wiener EM iterations per call (wiener.cpp:175; Open-Unmix's niter): 1 .. 15, flag bits 16-19."""
+    if not 1 <= int(n) <= 15:
+        raise ValueError(f"Wiener EM iterations must be 1 .. 15, not {n}")
+    return int(n) << 16
+
+
 _fp = C.POINTER(C.c_float)
 
 

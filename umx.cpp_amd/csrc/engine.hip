@@ -35,6 +35,7 @@
 #include "stft_kernels.h"
 #include "wiener_kernels.h"
 #include "wiener_istft.h"
+#include "wiener_em.h"
 
 using namespace umx;
 
@@ -183,6 +184,7 @@ struct Slot
     hipStream_t stream = nullptr;
     Lane lane[LSTMB_MAX_TRACKS];
     float *hbuf = nullptr;
+    float *wv = nullptr; // Wiener EM state v [T][2049][4] of every lane (wiener_em.h): allocated by the first call that asks for 2+ iterations
     bool lstm_wrote_planes[3] = {false, false, false}; // this call's recurrence of layer l wrote the next GEMM's A planes (run_lstm_layer_batched)
     bool lstm_rows_f32[3] = {true, true, true};        // ... and its fp32 output rows as well (else only the launch's last row: the taps of that layer are unavailable)
     unsigned *status = nullptr, *lsync = nullptr;
@@ -511,6 +513,7 @@ struct umx_hip_ctx
         ls.rc = (size_t)4 * NBINS * 4;
         ls.frames = (size_t)4 * T * NFFT;
         ls.y = (size_t)4 * 2 * T * NBINS;
+        ls.v = (size_t)4 * T * NBINS;
         return ls;
     }
     static LaneSet lane_set(int nb, const float *const *audio_dev) // the active lanes of a call

@@ -826,6 +826,7 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
             const int wi_lds = (int)WI_LDS_BYTES; // 155,648: four transforms + the window
             UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(wiener_istft_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, wi_lds));
             UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(wiener_istft_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, wi_lds));
+            UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(wiener_istft_v_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wi_lds));
         }
 #define UMX_GP_ATTR(MODE)                                                                                              \
     UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_planes_kernel<MODE, 1, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, gp_lds_bytes(2, 2, 1))); \

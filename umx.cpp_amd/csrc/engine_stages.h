@@ -346,6 +346,19 @@ int umx_hip_ctx::stage_finish(Slot &sl, hipStream_t st, int nb, const float *con
     for (int s = 0; s < 4; ++s)
         wm0.m[s] = L0.ta[s].mag;
     const int nchunk = (T + WIENER_CHUNK - 1) / WIENER_CHUNK;
+    // EM iterations (UMX_FLAG_WIENER_ITERS; 0 = 1): the ones after the first carry only the PSD v (wiener_em.h)
+    const int iters = (flags & UMX_FLAG_NO_WIENER) ? 1 : std::max(1, (int)((flags & UMX_FLAG_WIENER_ITERS_MASK) >> 16));
+    if (iters > 1 && !sl.wv)
+    {
+        // the kernels that read v address one lane of it through a buffer resource with 32-bit offsets (wiener_istft.h)
+        if ((unsigned long long)ls.v * sizeof(float) >= (1ull << 31))
+        {
+            set_error("Wiener EM iterations: the segment's PSD state exceeds the 32-bit addressing of the filter kernel: a shorter segment");
+            return UMX_ERR_ARG;
+        }
+        if (int rc = dalloc(&sl.wv, (size_t)B * ls.v, false)) // written in full by the first EM step before anything reads it
+            return rc;
+    }
     if (flags & UMX_FLAG_NO_WIENER)
     {
         if (!wiener_fused)
@@ -365,14 +378,28 @@ int umx_hip_ctx::stage_finish(Slot &sl, hipStream_t st, int nb, const float *con
         // 2 per thread 2.10 ms, 4 per thread 1.56 ms; lane-by-lane launches of rounds 1-2 had measured 4 per thread slower)
         hipLaunchKernelGGL(wiener_stats4_kernel<WIENER_STATS_NS>, dim3((NBINS + 63) / 64, nchunk * lanes.count, 4 / WIENER_STATS_NS), dim3(64), 0, st, L0.spec, wm0, T, L0.maxabs, L0.wpart, lanes, ls);
         hipLaunchKernelGGL(wiener_finish4_kernel, dim3(bt, 4, lanes.count), dim3(256), 0, st, L0.wpart, T, L0.Rc, lanes, ls);
+        // iterations 2 .. n: filter with v_k, R_k -> v_{k+1} (in place) and the partial sums of R_{k+1}
+        for (int it = 1; it < iters; ++it)
+        {
+            if (it == 1)
+                hipLaunchKernelGGL(wiener_em_step_kernel<true>, dim3((NBINS + 63) / 64, nchunk * lanes.count), dim3(64), 0, st, L0.spec, wm0, sl.wv, T, L0.maxabs, L0.Rc, L0.wpart, lanes, ls);
+            else
+                hipLaunchKernelGGL(wiener_em_step_kernel<false>, dim3((NBINS + 63) / 64, nchunk * lanes.count), dim3(64), 0, st, L0.spec, wm0, sl.wv, T, L0.maxabs, L0.Rc, L0.wpart, lanes, ls);
+            hipLaunchKernelGGL(wiener_finish4_kernel, dim3(bt, 4, lanes.count), dim3(256), 0, st, L0.wpart, T, L0.Rc, lanes, ls);
+        }
         if (!wiener_fused)
             for (int i = 0; i < lanes.count; ++i)
             {
-                Lane &L = sl.lane[lanes.id[i]];
+                const int ln = lanes.id[i];
+                Lane &L = sl.lane[ln];
                 WienerMags wm;
                 for (int s = 0; s < 4; ++s)
                     wm.m[s] = L.ta[s].mag;
-                hipLaunchKernelGGL(wiener_apply_kernel, dim3(bt, T), dim3(256), 0, st, L.spec, wm, T, L.maxabs, L.Rc, L.y);
+                if (iters > 1)
+                    hipLaunchKernelGGL(wiener_apply_kernel<true>, dim3(bt, T), dim3(256), 0, st, L.spec, wm,
+                                       reinterpret_cast<const float4 *>(sl.wv + (size_t)ln * ls.v), T, L.maxabs, L.Rc, L.y);
+                else
+                    hipLaunchKernelGGL(wiener_apply_kernel<false>, dim3(bt, T), dim3(256), 0, st, L.spec, wm, (const float4 *)nullptr, T, L.maxabs, L.Rc, L.y);
             }
     }
     OlaOut oo;
@@ -410,6 +437,9 @@ int umx_hip_ctx::stage_finish(Slot &sl, hipStream_t st, int nb, const float *con
         // each repeat the source-independent part, measured 1.7x / 2.7x slower in round 2)
         if (flags & UMX_FLAG_NO_WIENER)
             hipLaunchKernelGGL((wiener_istft_kernel<false>), dim3(nruns, 1, lanes.count), dim3(1024), WI_LDS_BYTES, st, L0.spec, wm0,
+                               T, L0.maxabs, L0.Rc, window, nw, tw1, tw2, L0.frames, ydbg, ls, run_len, oo);
+        else if (iters > 1) // the last of several EM iterations: the PSDs from v
+            hipLaunchKernelGGL(wiener_istft_v_kernel, dim3(nruns, 1, lanes.count), dim3(1024), WI_LDS_BYTES, st, (const float *)sl.wv, L0.spec, wm0,
                                T, L0.maxabs, L0.Rc, window, nw, tw1, tw2, L0.frames, ydbg, ls, run_len, oo);
         else
             hipLaunchKernelGGL((wiener_istft_kernel<true>), dim3(nruns, 1, lanes.count), dim3(1024), WI_LDS_BYTES, st, L0.spec, wm0,

@@ -20,6 +20,8 @@
 // LDS, the last pass's requested in front of the barrier.  Per frame: 98 KB of spectrogram / magnitudes and 131 KB of R (L2-resident) in,
 // 32 KB of stems out.
 // WIENER = false is BASELINE config 2: y_s = mag_s * exp(i arg X) (wiener.cpp:96-109 only).
+// VIN = true is the last of several EM iterations (wiener_em.h): the four PSDs of a bin are read from v [T][2049][4] (16 B) instead of
+// being formed from the eight masks (32 B).
 #pragma once
 #include "stft_kernels.h"
 #include "wiener_kernels.h"
@@ -67,14 +69,16 @@ __device__ __forceinline__ void bst2(__amdgpu_buffer_rsrc_t rs, int voff, int so
     __builtin_amdgcn_raw_buffer_store_b64(t, rs, voff, soff, 0);
 }
 
-template <bool WIENER>
-__global__ __launch_bounds__(1024) void wiener_istft_kernel(const float2 *__restrict__ spec, WienerMags mags, int T,
+// the body of wiener_istft_kernel (masks) and wiener_istft_v_kernel (v) below
+template <bool WIENER, bool VIN>
+__device__ __forceinline__ void wiener_istft_run(const float2 *__restrict__ spec, WienerMags mags, const float *__restrict__ v, int T,
                                                                   const unsigned *__restrict__ maxabs_bits,
                                                                   const float *__restrict__ Rc, const float *__restrict__ window,
                                                                   const float *__restrict__ nw, const float2 *__restrict__ tw1,
                                                                   const float2 *__restrict__ tw2, float2 *__restrict__ frames,
                                                                   float2 *__restrict__ y_dbg, WienerStrides ls, int run_len, OlaOut out)
 {
+    static_assert(WIENER || !VIN, "the PSDs of the filter");
     extern __shared__ __attribute__((aligned(16))) float2 wi_buf[]; // [4 sources][FFT_LDS_ELEMS], then the window [NFFT], then nw of an interior hop block [HOP]
     float *const wi_win = reinterpret_cast<float *>(wi_buf + 4 * FFT_LDS_ELEMS);
     float *const wi_nwp = wi_win + NFFT;
@@ -89,6 +93,8 @@ __global__ __launch_bounds__(1024) void wiener_istft_kernel(const float2 *__rest
         maxabs_bits += ln;
         if (y_dbg)
             y_dbg += (size_t)ln * ls.y;
+        if (VIN)
+            v += (size_t)ln * ls.v;
 #pragma unroll
         for (int s = 0; s < 4; ++s)
             mags.m[s] += (size_t)ln * ls.mag;
@@ -112,6 +118,8 @@ __global__ __launch_bounds__(1024) void wiener_istft_kernel(const float2 *__rest
 #pragma unroll
     for (int s = 0; s < 4; ++s)
         rs_mag[s] = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(mags.m[s]), 0, (int)((size_t)2 * T * MAGP * 4), 0x00020000);
+    // (v: 16 B per bin-frame of the lane, as many bytes as its mixture spectrogram; nullptr and unused unless VIN)
+    const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(v), 0, (int)((size_t)T * NBINS * 16), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_rc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Rc), 0, (int)((size_t)4 * NBINS * 16), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_nw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(nw), 0, (int)(((size_t)(T - 1) * HOP + NFFT) * 4), 0x00020000);
     const float max_abs = WIENER ? wiener_max_abs(maxabs_bits) : 1.0f, rmax = 1.0f / max_abs;
@@ -133,11 +141,20 @@ __global__ __launch_bounds__(1024) void wiener_istft_kernel(const float2 *__rest
     {                                                                                                                                  \
         Xq[q_][0] = bld2<2>(rs_spec, (tl_) * 8, ((0 * T + (f_)) * NBINS + WI_THREADS * (q_)) * 8);                                      \
         Xq[q_][1] = bld2<2>(rs_spec, (tl_) * 8, ((1 * T + (f_)) * NBINS + WI_THREADS * (q_)) * 8);                                      \
-        _Pragma("unroll") for (int s = 0; s < 4; ++s)                                                                                  \
+        if (VIN)                                                                                                                       \
         {                                                                                                                              \
-            mq[q_][0][s] = bld1<2>(rs_mag[s], (tl_) * 4, ((0 * T + (f_)) * MAGP + WI_THREADS * (q_)) * 4); /* mask_index(c, T, f, b) */ \
-            mq[q_][1][s] = bld1<2>(rs_mag[s], (tl_) * 4, ((1 * T + (f_)) * MAGP + WI_THREADS * (q_)) * 4);                              \
+            const float4 vf_ = bld4<2>(rs_v, (tl_) * 16, ((f_) * NBINS + WI_THREADS * (q_)) * 16);                                      \
+            mq[q_][0][0] = vf_.x;                                                                                                      \
+            mq[q_][0][1] = vf_.y;                                                                                                      \
+            mq[q_][0][2] = vf_.z;                                                                                                      \
+            mq[q_][0][3] = vf_.w;                                                                                                      \
         }                                                                                                                              \
+        else                                                                                                                           \
+            _Pragma("unroll") for (int s = 0; s < 4; ++s)                                                                              \
+            {                                                                                                                          \
+                mq[q_][0][s] = bld1<2>(rs_mag[s], (tl_) * 4, ((0 * T + (f_)) * MAGP + WI_THREADS * (q_)) * 4); /* mask_index(c, T, f, b) */ \
+                mq[q_][1][s] = bld1<2>(rs_mag[s], (tl_) * 4, ((1 * T + (f_)) * MAGP + WI_THREADS * (q_)) * 4);                          \
+            }                                                                                                                          \
     }
     if (f0 < f1)
     {
@@ -186,26 +203,38 @@ __global__ __launch_bounds__(1024) void wiener_istft_kernel(const float2 *__rest
             for (int s = 0; s < 4; ++s)
             {
                 m0[s] = mq[q < 2 ? q : 0][0][s];
-                m1[s] = mq[q < 2 ? q : 0][1][s];
+                m1[s] = VIN ? 0.f : mq[q < 2 ? q : 0][1][s];
             }
         }
         else
         {
             X0 = bld2<2>(rs_spec, tl * 8, ((0 * T + f) * NBINS + WI_THREADS * q) * 8);
             X1 = bld2<2>(rs_spec, tl * 8, ((1 * T + f) * NBINS + WI_THREADS * q) * 8);
+            if (VIN)
+            {
+                const float4 vf = bld4<2>(rs_v, tl * 16, (f * NBINS + WI_THREADS * q) * 16);
+                m0[0] = vf.x;
+                m0[1] = vf.y;
+                m0[2] = vf.z;
+                m0[3] = vf.w;
+            }
+            else
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                {
+                    m0[s] = bld1<2>(rs_mag[s], tl * 4, ((0 * T + f) * MAGP + WI_THREADS * q) * 4);
+                    m1[s] = bld1<2>(rs_mag[s], tl * 4, ((1 * T + f) * MAGP + WI_THREADS * q) * 4);
+                }
+        }
+        if (!VIN)
+        {
+            const float h0 = mix_magnitude(X0), h1 = mix_magnitude(X1);
 #pragma unroll
             for (int s = 0; s < 4; ++s)
             {
-                m0[s] = bld1<2>(rs_mag[s], tl * 4, ((0 * T + f) * MAGP + WI_THREADS * q) * 4);
-                m1[s] = bld1<2>(rs_mag[s], tl * 4, ((1 * T + f) * MAGP + WI_THREADS * q) * 4);
+                m0[s] *= h0; // target magnitude = mask x |X| (inference.cpp:175-183)
+                m1[s] *= h1;
             }
-        }
-        const float h0 = mix_magnitude(X0), h1 = mix_magnitude(X1);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-        {
-            m0[s] *= h0; // target magnitude = mask x |X| (inference.cpp:175-183)
-            m1[s] *= h1;
         }
         WienerBin wb;
         float4 rc[4];
@@ -215,7 +244,10 @@ __global__ __launch_bounds__(1024) void wiener_istft_kernel(const float2 *__rest
 #pragma unroll
             for (int s = 0; s < 4; ++s)
                 rc[s] = q == 0 ? rc0[s] : bld4<0>(rs_rc, tl * 16, (s * NBINS + WI_THREADS * q) * 16);
-            wiener_bin_setup(X0, X1, m0, m1, rc, max_abs, rmax, wb);
+            if (VIN)
+                wiener_bin_setup_v(X0, X1, m0, rc, max_abs, rmax, wb); // m0 = v_n
+            else
+                wiener_bin_setup(X0, X1, m0, m1, rc, max_abs, rmax, wb);
         }
         else
         {
@@ -369,6 +401,21 @@ __global__ __launch_bounds__(1024) void wiener_istft_kernel(const float2 *__rest
         printf("# wiener_istft thread %d, %d frames: cycles per frame  loads+gains %lld  barrier %lld  transform %lld  weight+overlap-add+drain %lld\n", tid,
                f1 - f0, pf[0] / (f1 - f0), pf[1] / (f1 - f0), pf[2] / (f1 - f0), pf[3] / (f1 - f0));
 }
+
+#define WI_PARAMS                                                                                                                  \
+    const float2 *__restrict__ spec, WienerMags mags, int T, const unsigned *__restrict__ maxabs_bits, const float *__restrict__ Rc,         \
+        const float *__restrict__ window, const float *__restrict__ nw, const float2 *__restrict__ tw1, const float2 *__restrict__ tw2,     \
+        float2 *__restrict__ frames, float2 *__restrict__ y_dbg, WienerStrides ls, int run_len, OlaOut out
+template <bool WIENER> __global__ __launch_bounds__(1024) void wiener_istft_kernel(WI_PARAMS)
+{
+    wiener_istft_run<WIENER, false>(spec, mags, nullptr, T, maxabs_bits, Rc, window, nw, tw1, tw2, frames, y_dbg, ls, run_len, out);
+}
+// the last of several EM iterations: v = the PSDs of that iteration, [T][2049][4] per lane (wiener_em.h)
+__global__ __launch_bounds__(1024) void wiener_istft_v_kernel(const float *__restrict__ v, WI_PARAMS)
+{
+    wiener_istft_run<true, true>(spec, mags, v, T, maxabs_bits, Rc, window, nw, tw1, tw2, frames, y_dbg, ls, run_len, out);
+}
+#undef WI_PARAMS
 
 // The first three hop blocks of every run of wiener_istft_kernel: the terms of the run's own frames (kept in `frames`)
 // are added to what the previous run's last frames left in the stem, in ascending frame order -- or to zero where no

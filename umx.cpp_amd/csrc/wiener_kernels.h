@@ -1,4 +1,5 @@
-// wiener_kernels.h -- multichannel Wiener filter, one EM iteration (wiener.cpp:92-425).
+// wiener_kernels.h -- multichannel Wiener filter, the first EM iteration and the filter of the last (wiener.cpp:92-425); the EM
+// steps in between (UMX_FLAG_WIENER_ITERS >= 2) are wiener_em.h.
 //
 // Reproduces the reference including its load-bearing quirks: the PSD is mean_c (Re y + Im y)^2
 // (wiener.cpp:187-202) and sqrt(eps) I is added once per source (wiener.cpp:311-323,
@@ -78,8 +79,25 @@ __device__ __forceinline__ void wiener_frame_load(WienerFrame<NS> &w, const floa
 // Lanes: blockIdx.y = entry * nchunk + chunk; spec, mags, maxabs_bits and part are lane 0's (WienerStrides apart per lane).
 struct WienerStrides
 {
-    size_t spec, mag, part, rc, frames, y; // elements between consecutive track lanes
+    size_t spec, mag, part, rc, frames, y, v; // elements between consecutive track lanes
 };
+
+// What one filtered bin y = (y0, y1) of one source contributes to the statistics of the next iteration: v = 1/2 sum_c (Re + Im)^2
+// (wiener.cpp:187-202, F5) is returned, y y^H (calculateCovariance wiener.cpp:435-478: a * conj(b), only the independent entries) is
+// added to the running sums in the reference's frame order.
+__device__ __forceinline__ float wiener_psd_cov(float2 y0, float2 y1, float &r00, float &r01x, float &r01y, float &r11)
+{
+    const float ra = y0.x + y0.y, rb = y1.x + y1.y;
+    float sum = 0.f;
+    sum += (ra * ra) + (0.f * 0.f);
+    sum += (rb * rb) + (0.f * 0.f);
+    const float2 q00 = cmul(y0, cconj(y0)), q01 = cmul(y0, cconj(y1)), q11 = cmul(y1, cconj(y1));
+    r00 += (0.f + q00.x);
+    r01x += (0.f + q01.x);
+    r01y += (0.f + q01.y);
+    r11 += (0.f + q11.x);
+    return sum / 2;
+}
 template <int NS>
 __global__ __launch_bounds__(64) void wiener_stats4_kernel(const float2 *__restrict__ spec, WienerMags mags, int T,
                                                            const unsigned *__restrict__ maxabs_bits,
@@ -117,18 +135,7 @@ __global__ __launch_bounds__(64) void wiener_stats4_kernel(const float2 *__restr
             // y_j(c) = mag * phasor / max_abs (wiener.cpp:133-146), the division as an exact 3-instruction quotient (div_by, common.h)
             const float2 y0 = make_float2(div_by(t0 * p0.x, max_abs, rmax), div_by(t0 * p0.y, max_abs, rmax));
             const float2 y1 = make_float2(div_by(t1 * p1.x, max_abs, rmax), div_by(t1 * p1.y, max_abs, rmax));
-            // v = 1/2 sum_c (Re + Im)^2   wiener.cpp:187-202 (F5)
-            const float ra = y0.x + y0.y, rb = y1.x + y1.y;
-            float sum = 0.f;
-            sum += (ra * ra) + (0.f * 0.f);
-            sum += (rb * rb) + (0.f * 0.f);
-            wsum[s] += sum / 2;
-            // calculateCovariance wiener.cpp:435-478: a * conj(b); only the independent entries
-            const float2 q00 = cmul(y0, cconj(y0)), q01 = cmul(y0, cconj(y1)), q11 = cmul(y1, cconj(y1));
-            r00[s] += (0.f + q00.x);
-            r01x[s] += (0.f + q01.x);
-            r01y[s] += (0.f + q01.y);
-            r11[s] += (0.f + q11.x);
+            wsum[s] += wiener_psd_cov(y0, y1, r00[s], r01x[s], r01y[s], r11[s]);
         }
     };
     // a ring of PF frames in registers: a slot is refilled (frame + PF) as soon as its frame has been accumulated, so PF
@@ -215,14 +222,12 @@ struct WienerBin
 // R_j, Cxx and its inverse are Hermitian with exactly real diagonals (the statistics pass below; Cxx = sum_s (sqrt(eps) I + v_s R_s);
 // its determinant is exactly real): four floats {M00, Re M01, Im M01, M11} carry each, and products with the structural zeros are
 // not formed.
-__device__ __forceinline__ void wiener_bin_setup(float2 X0, float2 X1, const float (&m0)[4], const float (&m1)[4],
-                                                 const float4 (&rc)[4], float max_abs, float rmax, WienerBin &w)
+// The first iteration's PSDs, from the target magnitudes m (= mask x |X|): v = 1/2 sum_c (Re y + Im y)^2 of y = m X/|X| / max_abs
+// (wiener.cpp:96-146, 187-202; F5).
+__device__ __forceinline__ void wiener_bin_psd(float2 X0, float2 X1, const float (&m0)[4], const float (&m1)[4], float max_abs, float rmax,
+                                               float (&v)[4])
 {
-    const float reg = sqrtf(WIENER_EPS); // wiener.cpp:165
-    const float2 x0 = make_float2(div_by(X0.x, max_abs, rmax), div_by(X0.y, max_abs, rmax)); // wiener.cpp:118-130
-    const float2 x1 = make_float2(div_by(X1.x, max_abs, rmax), div_by(X1.y, max_abs, rmax));
     const float2 p0 = unit_phasor(X0), p1 = unit_phasor(X1);
-    float c00 = 0.f, c11 = 0.f, c01x = 0.f, c01y = 0.f; // Cxx = [[c00, c01], [conj(c01), c11]]
 #pragma unroll
     for (int s = 0; s < 4; ++s)
     {
@@ -232,13 +237,28 @@ __device__ __forceinline__ void wiener_bin_setup(float2 X0, float2 X1, const flo
         float sum = 0.f;
         sum += (ra * ra) + (0.f * 0.f);
         sum += (rb * rb) + (0.f * 0.f);
-        const float v = sum / 2;
-        w.v[s] = v;
+        v[s] = sum / 2;
+    }
+}
+
+// Everything the filter of one bin needs from the PSDs v, whichever iteration formed them: Cxx, its inverse, t = Cxx^-1 x.
+__device__ __forceinline__ void wiener_bin_setup_v(float2 X0, float2 X1, const float (&v)[4], const float4 (&rc)[4], float max_abs, float rmax,
+                                                   WienerBin &w)
+{
+    const float reg = sqrtf(WIENER_EPS); // wiener.cpp:165
+    const float2 x0 = make_float2(div_by(X0.x, max_abs, rmax), div_by(X0.y, max_abs, rmax)); // wiener.cpp:118-130
+    const float2 x1 = make_float2(div_by(X1.x, max_abs, rmax), div_by(X1.y, max_abs, rmax));
+    float c00 = 0.f, c11 = 0.f, c01x = 0.f, c01y = 0.f; // Cxx = [[c00, c01], [conj(c01), c11]]
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+    {
+        const float v_s = v[s];
+        w.v[s] = v_s;
         // wiener.cpp:307-325: Cxx += reg(c1,c2) + v * R   (F6: once per source)
-        c00 += reg + v * rc[s].x;
-        c01x += v * rc[s].y;
-        c01y += v * rc[s].z;
-        c11 += reg + v * rc[s].w;
+        c00 += reg + v_s * rc[s].x;
+        c01x += v_s * rc[s].y;
+        c01y += v_s * rc[s].z;
+        c11 += reg + v_s * rc[s].w;
     }
     // invert4D wiener.cpp:54-84: det = c00 c11 - c01 conj(c01) is real; 1/det is formed as det / |det|^2 like the reference's form
     const float det = c00 * c11 - (c01x * c01x + c01y * c01y);
@@ -249,7 +269,17 @@ __device__ __forceinline__ void wiener_bin_setup(float2 X0, float2 X1, const flo
     w.t1 = make_float2((qx * x0.x + qy * x0.y) + r * x1.x, (qx * x0.y - qy * x0.x) + r * x1.y);
 }
 
-// y_s = v_s R_s t * max_abs for one source: R = [[a, b], [conj(b), d]]
+// the first iteration's filter setup: PSDs from the masks, then the above
+__device__ __forceinline__ void wiener_bin_setup(float2 X0, float2 X1, const float (&m0)[4], const float (&m1)[4],
+                                                 const float4 (&rc)[4], float max_abs, float rmax, WienerBin &w)
+{
+    float v[4];
+    wiener_bin_psd(X0, X1, m0, m1, max_abs, rmax, v);
+    wiener_bin_setup_v(X0, X1, v, rc, max_abs, rmax, w);
+}
+
+// y_s = v_s R_s t * max_abs for one source: R = [[a, b], [conj(b), d]].  (max_abs = 1: the scaled-down y of an intermediate EM
+// iteration, wiener_em.h -- v_s * 1 is v_s exactly.)
 __device__ __forceinline__ void wiener_bin_apply(const WienerBin &w, int s, float4 rc, float max_abs, float2 (&o)[2])
 {
     const float vs = s == 0 ? w.v[0] : s == 1 ? w.v[1] : s == 2 ? w.v[2] : w.v[3]; // selects: w stays in registers
@@ -263,8 +293,10 @@ __device__ __forceinline__ void wiener_bin_apply(const WienerBin &w, int s, floa
 }
 
 // The separate filter pass of single-track contexts (track-batched contexts: wiener_istft.h).  R: the four-float form.
-// grid (ceil(B/256), T).  y: [4][2][T][2049] complex
-__global__ __launch_bounds__(256) void wiener_apply_kernel(const float2 *__restrict__ spec, WienerMags mags,
+// grid (ceil(B/256), T).  y: [4][2][T][2049] complex.  VIN: the PSDs come from v [T][2049][4] (the last of several EM iterations,
+// wiener_em.h) instead of the masks.
+template <bool VIN>
+__global__ __launch_bounds__(256) void wiener_apply_kernel(const float2 *__restrict__ spec, WienerMags mags, const float4 *__restrict__ v,
                                                            int T, const unsigned *__restrict__ maxabs_bits,
                                                            const float *__restrict__ R, float2 *__restrict__ y)
 {
@@ -275,18 +307,29 @@ __global__ __launch_bounds__(256) void wiener_apply_kernel(const float2 *__restr
     const size_t i0 = ((size_t)0 * T + f) * NBINS + b, i1 = ((size_t)1 * T + f) * NBINS + b;
     const size_t j0 = mask_index(0, T, f, b), j1 = mask_index(1, T, f, b);
     const float2 X0 = spec[i0], X1 = spec[i1];
-    const float h0 = mix_magnitude(X0), h1 = mix_magnitude(X1);
-    float m0[4], m1[4];
     float4 rc[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s)
-    {
-        m0[s] = mags.m[s][j0] * h0; // inference.cpp:175-183: mask x |X|
-        m1[s] = mags.m[s][j1] * h1;
         rc[s] = *reinterpret_cast<const float4 *>(R + ((size_t)s * NBINS + b) * 4);
-    }
     WienerBin wb;
-    wiener_bin_setup(X0, X1, m0, m1, rc, max_abs, rmax, wb);
+    if (VIN)
+    {
+        const float4 vf = v[(size_t)f * NBINS + b];
+        const float vs[4] = {vf.x, vf.y, vf.z, vf.w};
+        wiener_bin_setup_v(X0, X1, vs, rc, max_abs, rmax, wb);
+    }
+    else
+    {
+        const float h0 = mix_magnitude(X0), h1 = mix_magnitude(X1);
+        float m0[4], m1[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+        {
+            m0[s] = mags.m[s][j0] * h0; // inference.cpp:175-183: mask x |X|
+            m1[s] = mags.m[s][j1] * h1;
+        }
+        wiener_bin_setup(X0, X1, m0, m1, rc, max_abs, rmax, wb);
+    }
 #pragma unroll
     for (int s = 0; s < 4; ++s)
     {

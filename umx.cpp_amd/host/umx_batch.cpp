@@ -3,7 +3,7 @@
 // bound by hand-off latency, not arithmetic, so the engine runs several tracks as track lanes of ONE context
 // (umx_hip_create_tracks / umx_hip_separate_tracks): per file the same shift_inference -> split_inference, the same
 // four stems, written to <out dir>/<wav stem>/target_{0..3}.wav.  More than 16 files are taken 16 at a time.
-// Environment: UMX_DEVICE, UMX_NO_WIENER, UMX_SHIFT_OFFSET (as umx-cli).
+// Environment: UMX_DEVICE, UMX_NO_WIENER, UMX_WIENER_ITERS, UMX_SHIFT_OFFSET (as umx-cli).
 #include "../../include/umx_host.h"
 
 #include <chrono>
@@ -52,7 +52,13 @@ int main(int argc, const char **argv)
         return 1;
     }
     umx_model_free(model);
-    const unsigned flags = env_int("UMX_NO_WIENER", 0) ? UMX_FLAG_NO_WIENER : 0;
+    const int wiener_iters = env_int("UMX_WIENER_ITERS", 1); // Wiener EM iterations (wiener.cpp:175; Open-Unmix's niter)
+    if (wiener_iters < 1 || wiener_iters > 15)
+    {
+        fprintf(stderr, "UMX_WIENER_ITERS: need 1 .. 15, got %d\n", wiener_iters);
+        return 1;
+    }
+    const unsigned flags = (env_int("UMX_NO_WIENER", 0) ? UMX_FLAG_NO_WIENER : 0) | (wiener_iters > 1 ? UMX_FLAG_WIENER_ITERS(wiener_iters) : 0u);
     double audio_secs = 0, wall = 0;
     const int first_rand_shift = UMX_REFERENCE_SHIFT; // glibc's first unseeded rand() % 22050 (not rand() here: umx_hip.h)
     std::set<std::string> used_names; // output directories are named after the file's stem: a/x.wav and b/x.wav must not collide

@@ -4,7 +4,7 @@
 // segments pipelined; UMX_CLI_PER_SEGMENT=1 selects the host drivers over umx_hip_infer_segment), writes
 // target_{0..3}.wav (0 = bass, 1 = drums, 2 = other, 3 = vocals).  Exit code 1 on any failure,
 // like the reference.  Extra knobs come from the environment only, so the 3 positionals stay:
-//   UMX_DEVICE=<n>   UMX_NO_WIENER=1   UMX_SHIFT_OFFSET=<n>   UMX_LSTM_STEPWISE=1   UMX_CLI_PER_SEGMENT=1
+//   UMX_DEVICE=<n>   UMX_NO_WIENER=1   UMX_WIENER_ITERS=<1..15>   UMX_SHIFT_OFFSET=<n>   UMX_LSTM_STEPWISE=1   UMX_CLI_PER_SEGMENT=1
 //   UMX_WEIGHTS_RESIDENT=expanded   UMX_GEMM=f32
 #include "../../include/umx_host.h"
 
@@ -82,6 +82,14 @@ int main(int argc, const char **argv)
     HipBackend hb{ctx, 0};
     if (env_int("UMX_NO_WIENER", 0))
         hb.flags |= UMX_FLAG_NO_WIENER;
+    const int wiener_iters = env_int("UMX_WIENER_ITERS", 1); // Wiener EM iterations (wiener.cpp:175; Open-Unmix's niter)
+    if (wiener_iters < 1 || wiener_iters > 15)
+    {
+        fprintf(stderr, "UMX_WIENER_ITERS: need 1 .. 15, got %d\n", wiener_iters);
+        return 1;
+    }
+    if (wiener_iters > 1)
+        hb.flags |= UMX_FLAG_WIENER_ITERS(wiener_iters);
     if (env_int("UMX_LSTM_STEPWISE", 0))
         hb.flags |= UMX_FLAG_LSTM_STEPWISE;
     umx_backend be{hip_segment, hip_reset, &hb};
