@@ -60,15 +60,16 @@ def _invert(C):
     return out
 
 
-def wiener_em(spec, target_mags, n_iter=1, precision="float64"):
+def wiener_em(spec, target_mags, n_iter=1, precision="float64", max_abs=None):
     """spec: complex [2, T, B] mixture; target_mags: 4 x [2, T, B] magnitudes -> 4 x complex [2, T, B] (complex128; complex64 at float32) (the reference's
     wiener_filter with WIENER_ITERATIONS = n_iter).  The caller's arrays are not changed (the reference divides its mixture in place:
-    here a copy is)."""
+    here a copy is).  max_abs: the scale of the whole spectrogram when `spec` holds only some of its bins (the filter is per bin but for
+    this scale)."""
     rt, ct = {"float64": (np.float64, np.complex128), "float32": (np.float32, np.complex64)}[precision]
     X = np.array(spec, dtype=ct)                                 # the copy the in-place division below works on
     phase = np.angle(X)
     y = [(np.asarray(m, rt) * np.cos(phase) + 1j * (np.asarray(m, rt) * np.sin(phase))).astype(ct) for m in target_mags]
-    max_abs = rt(find_max_abs(X))
+    max_abs = rt(find_max_abs(X) if max_abs is None else max_abs)
     X /= max_abs                                                 # :118-130, in place
     y = [yj / max_abs for yj in y]                               # :133-146
     T, B = X.shape[1], X.shape[2]

@@ -50,7 +50,7 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
     }
     if (segment_samples < NFFT || segment_samples / HOP + 2 > 4096)
     {
-        set_error("segment_samples must be in [4096, 4,190,000] (at most 4094 STFT frames per segment)");
+        set_error("segment_samples must be in [4096, 4,193,279] (at most 4095 STFT frames per segment)");
         return UMX_ERR_ARG;
     }
     int ndev = 0;
