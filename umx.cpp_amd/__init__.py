@@ -145,6 +145,14 @@ def hip_lib():
     lib.umx_hip_segment_begin.argtypes = [C.c_void_p, _fp, C.c_int, C.c_uint]
     lib.umx_hip_segment_lstm_layer.argtypes = [C.c_void_p, C.c_int]
     lib.umx_hip_segment_end.argtypes = [C.c_void_p, C.POINTER(_fp)]
+    lib.umx_hip_segment_begin_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint]
+    lib.umx_hip_segment_end_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.umx_hip_segment_masks_device.argtypes = [C.c_void_p]
+    lib.umx_hip_segment_finish_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.umx_hip_weight_stems_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
+    lib.umx_hip_track_accumulate_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p), C.c_int,
+                                                    C.c_int, C.c_void_p]
+    lib.umx_hip_track_normalise_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p]
     lib.umx_hip_debug_lds_guard.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint)]
     lib.umx_hip_split_inference.argtypes = [C.c_void_p, _fp, C.c_int, C.POINTER(_fp), C.c_uint, C.c_void_p, C.c_void_p]
     lib.umx_hip_shift_inference.argtypes = [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(_fp), C.c_uint, C.c_void_p,
@@ -323,6 +331,31 @@ class Engine:
         arr = (_fp * 4)(*[o.ctypes.data_as(_fp) for o in outs])
         self._check(self.lib.umx_hip_segment_end(self.h, arr))
         return [np.ascontiguousarray(o.reshape(n, 2).T) for o in outs]
+
+    # --- the same cut points on device pointers, all queued on one stream (host/mgpu.cpp); asynchronous, call sync() ---
+    def segment_begin_device(self, audio_ptr, n, flags=0):
+        self._check(self.lib.umx_hip_segment_begin_device(self.h, C.c_void_p(audio_ptr), n, flags))
+
+    def segment_end_device(self, out_ptrs):
+        self._check(self.lib.umx_hip_segment_end_device(self.h, (C.c_void_p * 4)(*out_ptrs)))
+
+    def segment_masks_device(self):
+        self._check(self.lib.umx_hip_segment_masks_device(self.h))
+
+    def segment_finish_device(self, out_ptrs):
+        self._check(self.lib.umx_hip_segment_finish_device(self.h, (C.c_void_p * 4)(*out_ptrs)))
+
+    # --- split_inference's overlap-add on device pointers (umx.cpp:197-273); hip_stream None = the null stream ---
+    def weight_stems_device(self, stem_ptrs, n, hip_stream=None):
+        self._check(self.lib.umx_hip_weight_stems_device(self.h, (C.c_void_p * 4)(*stem_ptrs), n, hip_stream))
+
+    def track_accumulate_device(self, track_ptrs, sum_weight_ptr, weighted_ptrs, offset, n, hip_stream=None):
+        self._check(self.lib.umx_hip_track_accumulate_device(self.h, (C.c_void_p * 4)(*track_ptrs), C.c_void_p(sum_weight_ptr),
+                                                             (C.c_void_p * 4)(*weighted_ptrs), offset, n, hip_stream))
+
+    def track_normalise_device(self, track_ptrs, sum_weight_ptr, length, hip_stream=None):
+        self._check(self.lib.umx_hip_track_normalise_device(self.h, (C.c_void_p * 4)(*track_ptrs), C.c_void_p(sum_weight_ptr), length,
+                                                            hip_stream))
 
     # --- whole track on the device (umx.cpp:99-295) ---
     def separate(self, wave, flags=0, shift_offset=None):

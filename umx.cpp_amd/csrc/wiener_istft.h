@@ -354,7 +354,9 @@ __device__ __forceinline__ void wiener_istft_run(const float2 *__restrict__ spec
             if (c == 0)
             {
                 // block f is complete
-                // (sample start + i - 2048 of the stem: negative or >= n_out = out of the resource's range, the store is dropped)
+                // (sample start + i - 2048 of the stem, >= 1024 here.  No `< n_out` predicate: past n_out the store is dropped by the
+                // resource's range check -- which on gfx950 covers soffset, where the part of the offset beyond j sits.  A lane with
+                // n_out < N stores blocks up to sample (T - 2) HOP - 1; tests/test_gpu_device_buffers.py pins that they stay dropped)
                 if (f >= f0 + 3)
                     bst2(rs_stem, j * 8, (start + 256 * r - NFFT / 2) * 8, sum);
             }
