@@ -55,34 +55,29 @@ namespace
 {
 std::string g_create_error = "";
 
-// A GEMM weight kept in HBM as stored in the ggml file (BASELINE config 5): u8 / u16 + (scale, offset);
-// two parameter pairs because W_ih of a layer is two file tensors (forward rows, then reverse rows).
-struct QMat
-{
-    void *q = nullptr;
-    int type = 0; // GemmBType
-    float s[2] = {1.f, 1.f}, o[2] = {0.f, 0.f};
-};
+// The weights of the dense stack, one per GEMM stage: fc1, W_ih of layers 0-2, fc2, fc3.
+enum { W_FC1 = 0, W_IH0, W_IH1, W_IH2, W_FC2, W_FC3, W_COUNT };
+inline int gemm_weight(int mode, int layer) { return mode == G_FC1 ? W_FC1 : mode == G_IH ? W_IH0 + layer : mode == G_FC2 ? W_FC2 : W_FC3; }
 
-// A GEMM weight as fp16 planes [nbp][N][K] (gemm_planes.h): u8 -> 1 exact plane of q - 128, u16 -> 2 planes whose sum is
-// exactly q - 32896: fp16(q - 32896) and the remainder (an integer of at most 16), fp32 -> 2 split terms of w / s with s a
-// power of two; (scale, offset + c scale) per file tensor (W_ih: two).
-struct PMat
+// One GEMM weight in HBM, [N][K] per plane.  Plane flavour (gemm_planes.h): `form` fp16 planes -- u8 as 1 exact plane of q - 128,
+// u16 as 2 planes whose sum is exactly q - 32896 (fp16(q - 32896) and the remainder, an integer of at most 16), fp32 as 2 split
+// terms of w / s with s a power of two; (s, o) = (scale, offset + c scale), or (s, 0).  Staged flavour (gemm_bf16x3.h): `form` is
+// the GemmBType -- BQ_U8 / BQ_U16 = the ggml file's bytes (BASELINE config 5) with (scale, offset), BQ_F32 = three bf16 planes
+// with (1, 0).  Two (s, o) pairs because W_ih of a layer is two file tensors (forward rows, then reverse rows).
+struct GemmWeight
 {
-    unsigned short *p = nullptr;
-    int nbp = 2;
-    float s[2] = {1.f, 1.f}, o2[2] = {0.f, 0.f};
+    const void *p = nullptr;
+    int form = 0;
+    float s[2] = {1.f, 1.f}, o[2] = {0.f, 0.f};
 };
 
 struct TargetBufs // weights of one target (shared by both pipeline slots)
 {
-    PMat fc1_p, ih_p[3], fc2_p, fc3_p; // gemm_planes.h (the default GEMM flavour)
-    QMat fc1_q, ih_q[3], fc2_q, fc3_q; // used instead of the fp32 matrix when .q != nullptr
-    unsigned short *fc1_bx = nullptr, *ih_bx[3] = {}, *fc2_bx = nullptr, *fc3_bx = nullptr; // bf16 planes [3][N][K] (gemm_bf16x3.h)
-    float *fc1_w = nullptr, *in_scale = nullptr, *in_mean = nullptr, *bn1[4] = {};
-    float *ih_w[3] = {}, *ih_b[3] = {};
-    float *fc2_w = nullptr, *bn2[4] = {};
-    float *fc3_w = nullptr, *bn3[4] = {}, *out_scale = nullptr, *out_mean = nullptr;
+    GemmWeight w[W_COUNT];
+    float *in_scale = nullptr, *in_mean = nullptr, *bn1[4] = {};
+    float *ih_b[3] = {};
+    float *bn2[4] = {};
+    float *bn3[4] = {}, *out_scale = nullptr, *out_mean = nullptr;
 };
 
 struct TargetAct // activations of one target in one pipeline slot
@@ -348,6 +343,76 @@ static const void *lstm_batch_fn(int Hl, bool wq, bool precise)
     }
 }
 
+// The GEMM kernel tables: (stage, form of the weight[, tile kind]) -> kernel and its dynamic LDS.  They hold the only
+// instantiations of the GEMM kernels; init raises the LDS limit of every entry and the launches take theirs from here.  The
+// u8 weights (fc1, W_ih) come in every form, the u16 ones (fc2, fc3) only as two planes (plane flavour) or as u16 / fp32 (staged).
+struct GemmKernel
+{
+    const void *fn = nullptr;
+    int lds = 0;
+};
+template <class K> static const void *kernel_ptr(K *k) { return reinterpret_cast<const void *>(k); }
+
+// gemm_bf16x3_kernel by GemmBType
+template <int MODE> static GemmKernel bx_kernel_m(int bq)
+{
+    if (bq == BQ_F32)
+        return {kernel_ptr(gemm_bf16x3_kernel<MODE, BQ_F32>), BX_LDS_BYTES};
+    if constexpr (MODE == G_FC1 || MODE == G_IH)
+    {
+        if (bq == BQ_U8X)
+            return {kernel_ptr(gemm_bf16x3_kernel<MODE, BQ_U8X>), BX_LDS_BYTES};
+        if (bq == BQ_U8)
+            return {kernel_ptr(gemm_bf16x3_kernel<MODE, BQ_U8>), BX_LDS_BYTES};
+    }
+    else if (bq == BQ_U16)
+        return {kernel_ptr(gemm_bf16x3_kernel<MODE, BQ_U16>), BX_LDS_BYTES};
+    return {};
+}
+static GemmKernel bx_kernel(int mode, int bq)
+{
+    switch (mode)
+    {
+    case G_FC1: return bx_kernel_m<G_FC1>(bq);
+    case G_IH: return bx_kernel_m<G_IH>(bq);
+    case G_FC2: return bx_kernel_m<G_FC2>(bq);
+    default: return bx_kernel_m<G_FC3>(bq);
+    }
+}
+
+// the plane GEMMs by planes of B and tile kind: lock step with 128 x 128 or 256 x 256 tiles (gemm_planes.h), 256 x 256 in
+// ping-pong (gemm_planes_pp.h) or persistent (gemm_planes_ps.h)
+enum { GP_128 = 0, GP_256, GP_PP, GP_PS, GP_KINDS };
+template <int MODE, int NBP> static GemmKernel gp_kernel_mn(int kind)
+{
+    switch (kind)
+    {
+    case GP_128: return {kernel_ptr(gemm_planes_kernel<MODE, NBP, 2, 2>), gp_lds_bytes(2, 2, NBP)};
+    case GP_256: return {kernel_ptr(gemm_planes_kernel<MODE, NBP, 4, 4>), gp_lds_bytes(4, 4, NBP)};
+    case GP_PP: return {kernel_ptr(gemm_planes_pp_kernel<MODE, NBP>), gp_lds_bytes(4, 4, NBP)};
+    default: return {kernel_ptr(gemm_planes_ps_kernel<MODE, NBP>), ps_lds_bytes(NBP)};
+    }
+}
+template <int MODE> static GemmKernel gp_kernel_m(int nbp, int kind)
+{
+    if constexpr (MODE == G_FC1 || MODE == G_IH)
+    {
+        if (nbp == 1)
+            return gp_kernel_mn<MODE, 1>(kind);
+    }
+    return nbp == 2 ? gp_kernel_mn<MODE, 2>(kind) : GemmKernel{};
+}
+static GemmKernel gp_kernel(int mode, int nbp, int kind)
+{
+    switch (mode)
+    {
+    case G_FC1: return gp_kernel_m<G_FC1>(nbp, kind);
+    case G_IH: return gp_kernel_m<G_IH>(nbp, kind);
+    case G_FC2: return gp_kernel_m<G_FC2>(nbp, kind);
+    default: return gp_kernel_m<G_FC3>(nbp, kind);
+    }
+}
+
 struct umx_hip_ctx
 {
     int device = 0, H = 0, Hl = 0, S = 0, N = 0, T = 0, Tp = 0, nbatch = 0;
@@ -422,7 +487,6 @@ struct umx_hip_ctx
     int env_gemm_pp = -1;            // UMX_GEMM_PP: bit mask of the GEMMs that take the ping-pong kernel; < 0: all.  Both are read ONCE, when the context is created: a test makes a context per mode
     const char *gemm_kernel_last[4] = {"none", "none", "none", "none"}; // per GemmMode (umx_hip_gemm_kernel_name)
     const char *lstm_kernel_last = "none"; // the recurrence kernel of the last layer launch (umx_hip_lstm_kernel_name)
-    int lstm_threads = LSTM_THREADS; // 512 (two workgroups per CU fit) or 576 (dedicated gate wave)
     int lstm_capacity = 0;           // workgroups of the persistent LSTM kernel that can be co-resident
     unsigned last_flags = 0;
     hipStream_t stream = nullptr; // = slot[0].stream (H2D/D2H of the host-pointer entry point)
@@ -450,9 +514,9 @@ struct umx_hip_ctx
     int init(int device_, int hidden, int segment_samples, const umx_tensor_view *tensors, int n_tensors,
              unsigned create_flags, int n_tracks);
     size_t weight_bytes = 0;      // HBM held by model tensors (the config-5 figure of merit)
-    bool gemm_bf16x3 = false;     // dense stack on the bf16 matrix cores, three-term split (gemm_bf16x3.h)
     bool wiener_fused = true;     // wiener_istft.h: gains + filter + inverse STFT frame in one kernel
-    bool gemm_planes = false;     // ... with both operands pre-split / re-encoded as bf16 planes and LDS-DMA staging (gemm_planes.h)
+    bool gemm_planes = false;     // dense stack with both operands pre-split as fp16 planes and LDS-DMA staging (gemm_planes.h);
+                                  // else the three-term bf16 split staged per tile (gemm_bf16x3.h)
     void launch_split(Lane &ln, int nl, hipStream_t st, int which, const int *active, int nact);
     void launch_gemm_planes(Lane &ln, int nl, hipStream_t st, int mode, int layer, const int *active, int nact, bool dbg);
     // one GEMM stage for the track lanes with audio: the plane GEMMs take every run of consecutive lanes in one launch

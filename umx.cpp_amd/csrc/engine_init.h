@@ -109,48 +109,19 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
         auto it = idx[tg].find(name);
         return it == idx[tg].end() ? nullptr : it->second;
     };
-    auto nelems = [](const umx_tensor_view *tv) {
-        size_t n = 1;
-        for (int i = 0; i < tv->n_dims; ++i)
-            n *= (size_t)tv->ne[i];
-        return n;
-    };
-    // Upload `rows` x `cols` of a u8/u16 tensor as stored, into a (rows_pad x cols_pad) device matrix; padding
-    // is q = 0 (any finite weight is fine there: padded K columns meet zero activations, padded N rows are
-    // never stored).  rowmap (optional) = source row of each destination row.
-    auto upload_q = [&](void **dst, const umx_tensor_view *tv, int rows, int cols, int rows_pad, int cols_pad,
-                        const std::vector<int> *rowmap, size_t dst_row0, size_t total_rows) -> int {
-        const size_t esz = tv->dtype == UMX_DTYPE_U8 ? 1 : 2;
-        if (!*dst)
-        {
-            void *q = nullptr;
-            UMX_HIP_CHECK(hipMalloc(&q, total_rows * cols_pad * esz));
-            UMX_HIP_CHECK(hipMemset(q, 0, total_rows * cols_pad * esz));
-            allocs.push_back(q);
-            *dst = q;
-            weight_bytes += total_rows * cols_pad * esz;
-        }
-        std::vector<unsigned char> host((size_t)rows_pad * cols_pad * esz, 0);
-        const unsigned char *src = static_cast<const unsigned char *>(tv->data);
-        for (int r = 0; r < rows; ++r)
-        {
-            const int sr = rowmap ? (*rowmap)[r] : r;
-            memcpy(&host[(size_t)r * cols_pad * esz], src + (size_t)sr * cols * esz, (size_t)cols * esz);
-        }
-        UMX_HIP_CHECK(hipMemcpy(static_cast<unsigned char *>(*dst) + dst_row0 * cols_pad * esz, host.data(), host.size(),
-                                hipMemcpyHostToDevice));
-        return UMX_OK;
-    };
-    auto is_q = [&](const umx_tensor_view *tv, int dtype, size_t expect) {
-        return keepq && tv && tv->dtype == dtype && nelems(tv) == expect;
-    };
     // A GEMM launch covers all four targets with ONE kernel instantiation (its B-operand type is a template
     // parameter), so a matrix stays quantised only if it is stored that way for EVERY target; otherwise it is expanded
     // for all of them.
     auto all_q = [&](const std::string &name, int dtype, size_t expect) {
         for (int tg = 0; tg < 4; ++tg)
-            if (!is_q(view(tg, name), dtype, expect))
+        {
+            const umx_tensor_view *tv = view(tg, name);
+            size_t n = 1;
+            for (int i = 0; tv && i < tv->n_dims; ++i)
+                n *= (size_t)tv->ne[i];
+            if (!keepq || !tv || tv->dtype != dtype || n != expect)
                 return false;
+        }
         return true;
     };
 
@@ -160,7 +131,6 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
                   "than the split-operand kernels: profiles/r02_accuracy_vs_float64.txt)");
         return UMX_ERR_ARG;
     }
-    gemm_bf16x3 = true; // 16-bit matrix cores with split operands: gemm_planes.h or gemm_bf16x3.h
     // Track-batched contexts fuse the Wiener filter with the inverse STFT (wiener_istft.h: one 1024-thread, 136 KB-LDS
     // workgroup per frame); the single-track context keeps the small kernels, which run beside the other slot's LSTM
     // grids (measured: fused 7.85 ms per segment in the pipeline, unfused 7.41).  UMX_WIENER = fused | stats4 | unfused.
@@ -182,89 +152,147 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
     // gemm_planes.h for track-batched contexts (large tiles over all lanes); gemm_bf16x3.h for the single-track,
     // latency-optimised context, whose pipeline overlaps small GEMM blocks with two co-resident LSTM grids (the register
     // and LDS budget of DESIGN 4.2 was tuned for exactly that kernel).  Either can be forced.
-    gemm_planes = gemm_bf16x3 && ((create_flags & UMX_CREATE_GEMM_PLANES) || (lstm_batched && !(create_flags & UMX_CREATE_GEMM_STAGED)));
-    const bool bx = gemm_bf16x3;
+    gemm_planes = (create_flags & UMX_CREATE_GEMM_PLANES) || (lstm_batched && !(create_flags & UMX_CREATE_GEMM_STAGED));
     Tp = gemm_planes ? std::max(T, 256) : round_up(T, 128); // (a tile must not hold rows of more than two lanes)
-    // A GEMM weight as fp16 planes (PMat): (rows x cols) of `tv` (u8 / u16 as stored: exact integers) or of `f32` (two
-    // split terms of w * 2^e, 2^e bringing the tensor's largest |w| into [2^14, 2^15); returns 2^-e), source row
-    // rowmap[r] -> destination row dst_row0 + r of a [nbp][total_rows][cols_pad] matrix built in `host`
-    auto fill_planes = [&](std::vector<unsigned short> &host, int nbp, size_t total_rows, int cols_pad, const umx_tensor_view *tv,
-                           const float *f32, int rows, int cols, const std::vector<int> *rowmap, size_t dst_row0) -> float {
-        const size_t plane = total_rows * (size_t)cols_pad;
-        if (host.empty())
-            host.assign((size_t)nbp * plane, 0);
-        float scale = 1.f, unscale = 1.f;
-        if (f32)
+
+    // ---- the GEMM weights
+    const int G = 4 * Hl; // gate rows per direction
+    // gate rows interleaved so that a workgroup's 64 columns (g,u) are contiguous: PyTorch gate row (i|f|g|o blocks) -> row
+    std::vector<int> gate_row(G);
+    for (int sl = 0; sl < S; ++sl)
+        for (int g = 0; g < 4; ++g)
+            for (int u = 0; u < 16; ++u)
+                gate_row[g * Hl + sl * 16 + u] = sl * 64 + u * 4 + g; // the 4 gates of a unit share a DPP quad
+    // fc3's output rows in the column layout of the mask planes: channel c's 2049 rows at [c * MAGP, ...), zero rows between
+    std::vector<int> fc3_row(NOUT);
+    for (int r = 0; r < NOUT; ++r)
+        fc3_row[r] = r / NBINS * MAGP + r % NBINS;
+    // Each weight: its source tensors (W_ih: forward, then reverse, stacked into one matrix), rows x cols of each, the
+    // dst_rows x cols_pad block each fills in the device matrix, the destination row of each source row (nullptr: the same
+    // row) and the integer type it may stay in.  Rows that none maps to and columns past cols are zero (q = 0 while integer:
+    // any finite weight is fine there, padded K columns meet zero activations and padded N rows are never stored).
+    struct WeightDesc
+    {
+        std::string name[2];
+        int nsrc, rows, cols, dst_rows, cols_pad;
+        const std::vector<int> *dst_row;
+        int dtype;
+    };
+    WeightDesc wd[W_COUNT];
+    wd[W_FC1] = {{"fc1.weight"}, 1, H, NIN, H, KX, nullptr, UMX_DTYPE_U8};
+    for (int l = 0; l < 3; ++l)
+        wd[W_IH0 + l] = {{"lstm.weight_ih_l" + std::to_string(l), "lstm.weight_ih_l" + std::to_string(l) + "_reverse"}, 2, G, H, G, H, &gate_row,
+                         UMX_DTYPE_U8};
+    wd[W_FC2] = {{"fc2.weight"}, 1, H, 2 * H, H, 2 * H, nullptr, UMX_DTYPE_U16};
+    wd[W_FC3] = {{"fc3.weight"}, 1, NOUT, H, NOUT_PAD, H, &fc3_row, UMX_DTYPE_U16};
+    auto upload_weight = [&](GemmWeight &w, const void *host, size_t bytes) -> int {
+        unsigned char *p = nullptr;
+        if (int rc = dalloc(&p, bytes, false))
+            return rc;
+        UMX_HIP_CHECK(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+        w.p = p;
+        weight_bytes += bytes;
+        return UMX_OK;
+    };
+    // element i of a matrix of fp16 planes `plane` elements apart: fp16(v) and, with two planes, fp16 of the remainder
+    auto fill_planes = [](std::vector<unsigned short> &host, size_t plane, size_t i, int nbp, float v) {
+        host[i] = f16_rne_bits(v);
+        if (nbp == 2)
+            host[plane + i] = f16_rne_bits(v - f16_bits_to_float(host[i]));
+    };
+    // Weight d of target tg in the form of the context's GEMM flavour (GemmWeight).  Integers as the file holds them if all
+    // four targets do: the file's bytes (staged), or exact planes of q - c (plane flavour, unless UMX_CREATE_U8_DEQUANT).
+    // Otherwise dequantised fp32: two split planes of w * 2^e, 2^e bringing the source tensor's largest finite |w| into
+    // [2^14, 2^15) (plane flavour), or three bf16 planes (staged).
+    const bool exact_ok = keepq && !u8_dequant;
+    auto load_weight = [&](int tg, const WeightDesc &d, GemmWeight &w) -> int {
+        const size_t n = (size_t)d.nsrc * d.dst_rows * d.cols_pad; // elements of one plane
+        auto dst = [&](int s, int r) { return ((size_t)s * d.dst_rows + (d.dst_row ? (*d.dst_row)[r] : r)) * d.cols_pad; };
+        bool q = true;
+        for (int s = 0; s < d.nsrc; ++s)
+            q = q && all_q(d.name[s], d.dtype, (size_t)d.rows * d.cols);
+        std::vector<unsigned short> planes;
+        if (q && (!gemm_planes || exact_ok))
         {
-            float mx = 0.f;
-            for (size_t i = 0; i < (size_t)rows * cols; ++i)
-                if (std::isfinite(f32[i]))
-                    mx = std::max(mx, std::fabs(f32[i]));
-            if (mx > 0.f)
+            const size_t esz = d.dtype == UMX_DTYPE_U8 ? 1 : 2;
+            std::vector<unsigned char> qh(n * esz, 0);
+            for (int s = 0; s < d.nsrc; ++s)
             {
-                int x;
-                (void)std::frexp(mx, &x);
-                const int e = std::min(std::max(GP_SPLIT_FIXED_EXP + 1 - x, -100), 100);
-                scale = std::ldexp(1.0f, e);
-                unscale = std::ldexp(1.0f, -e);
+                const umx_tensor_view *tv = view(tg, d.name[s]);
+                for (int r = 0; r < d.rows; ++r)
+                    memcpy(&qh[dst(s, r) * esz], static_cast<const unsigned char *>(tv->data) + (size_t)r * d.cols * esz, (size_t)d.cols * esz);
+                w.s[s] = tv->scale;
+                w.o[s] = tv->offset;
+            }
+            if (!gemm_planes)
+            {
+                w.form = esz == 1 ? BQ_U8 : BQ_U16;
+                return upload_weight(w, qh.data(), qh.size());
+            }
+            // u8: q - 128 in one plane.  u16: q - 32896 (= 256 (qh - 128) + (ql - 128)) as fp16 + exact remainder, |remainder|
+            // <= 16 = 2^-11 of the plane above it, so that a2 x remainder need not be formed (gemm_planes.h).  The constant
+            // goes into the offset: (scale, offset + c scale).
+            w.form = esz == 1 ? 1 : 2;
+            const float c = esz == 1 ? 128.0f : 32896.0f;
+            planes.assign(w.form * n, 0);
+            for (size_t i = 0; i < n; ++i)
+                if ((int)(i % d.cols_pad) < d.cols)
+                {
+                    uint16_t qv = qh[i * esz];
+                    if (esz == 2)
+                        memcpy(&qv, &qh[i * 2], 2);
+                    fill_planes(planes, n, i, w.form, (float)qv - c);
+                }
+            for (int s = 0; s < d.nsrc; ++s)
+                w.o[s] = w.o[s] + c * w.s[s];
+            return upload_weight(w, planes.data(), planes.size() * sizeof(unsigned short));
+        }
+        std::vector<float> f(n, 0.f), v;
+        if (gemm_planes)
+            planes.assign(2 * n, 0);
+        for (int s = 0; s < d.nsrc; ++s)
+        {
+            if (!get(tg, d.name[s], (size_t)d.rows * d.cols, v))
+                return UMX_ERR_MODEL;
+            for (int r = 0; r < d.rows; ++r)
+                memcpy(&f[dst(s, r)], &v[(size_t)r * d.cols], sizeof(float) * d.cols);
+            if (gemm_planes)
+            {
+                float mx = 0.f, scale = 1.f;
+                for (float x : v)
+                    if (std::isfinite(x))
+                        mx = std::max(mx, std::fabs(x));
+                if (mx > 0.f)
+                {
+                    int x;
+                    (void)std::frexp(mx, &x);
+                    const int e = std::min(std::max(GP_SPLIT_FIXED_EXP + 1 - x, -100), 100);
+                    scale = std::ldexp(1.0f, e);
+                    w.s[s] = std::ldexp(1.0f, -e);
+                }
+                const size_t b0 = (size_t)s * d.dst_rows * d.cols_pad;
+                for (size_t i = b0; i < b0 + (size_t)d.dst_rows * d.cols_pad; ++i)
+                    fill_planes(planes, n, i, 2, f[i] * scale);
             }
         }
-        for (int r = 0; r < rows; ++r)
+        if (gemm_planes)
+            w.form = 2;
+        else
         {
-            const int sr = rowmap ? (*rowmap)[r] : r;
-            unsigned short *d = &host[(dst_row0 + r) * cols_pad];
-            for (int k = 0; k < cols; ++k)
-            {
-                if (f32)
-                {
-                    const float w = f32[(size_t)sr * cols + k] * scale;
-                    d[k] = f16_rne_bits(w);
-                    d[plane + k] = f16_rne_bits(w - f16_bits_to_float(d[k]));
-                }
-                else if (nbp == 1)
-                    d[k] = f16_rne_bits((float)static_cast<const uint8_t *>(tv->data)[(size_t)sr * cols + k] - 128.0f);
-                else
-                {
-                    // q - 32896 (= 256 (qh - 128) + (ql - 128): the constant of the affine map below) as fp16 + exact remainder:
-                    // |remainder| <= 16 = 2^-11 of the plane above it, so that a2 x remainder need not be formed (gemm_planes.h)
-                    const float pq = (float)static_cast<const uint16_t *>(tv->data)[(size_t)sr * cols + k] - 32896.0f;
-                    d[k] = f16_rne_bits(pq);
-                    d[plane + k] = f16_rne_bits(pq - f16_bits_to_float(d[k]));
-                }
-            }
+            w.form = BQ_F32;
+            planes.resize(3 * n);
+            for (size_t i = 0; i < n; ++i)
+                split3_host(f[i], planes[i], planes[n + i], planes[2 * n + i]);
         }
-        return unscale;
-    };
-    auto upload_pmat = [&](PMat &pm, std::vector<unsigned short> &host, int nbp) -> int {
-        pm.nbp = nbp;
-        weight_bytes += host.size() * sizeof(unsigned short);
-        return upload(&pm.p, host);
-    };
-    // fp32 matrix (kernel layout, padded) -> device; as three bf16 planes when the bf16x3 GEMMs are selected
-    auto upload_matrix = [&](float **dst_f32, unsigned short **dst_bx, const std::vector<float> &w) -> int {
-        if (!bx)
-        {
-            weight_bytes += w.size() * sizeof(float);
-            return upload(dst_f32, w);
-        }
-        std::vector<unsigned short> planes(3 * w.size());
-        for (size_t i = 0; i < w.size(); ++i)
-            split3_host(w[i], planes[i], planes[w.size() + i], planes[2 * w.size() + i]);
-        weight_bytes += planes.size() * sizeof(unsigned short);
-        return upload(dst_bx, planes);
+        return upload_weight(w, planes.data(), planes.size() * sizeof(unsigned short));
     };
 
-    const int G = 4 * Hl; // gate rows per direction
     std::vector<float> whh_h[3], bhh_h[3];
     std::vector<unsigned char> whh_qh[3];
-    bool whh_all_u8 = keepq;
-    for (int tg = 0; tg < 4 && whh_all_u8; ++tg)
-        for (int l = 0; l < 3; ++l)
-            for (int dir = 0; dir < 2; ++dir)
-            {
-                const umx_tensor_view *tv = view(tg, "lstm.weight_hh_l" + std::to_string(l) + (dir ? "_reverse" : ""));
-                whh_all_u8 = whh_all_u8 && tv && tv->dtype == UMX_DTYPE_U8 && nelems(tv) == (size_t)G * Hl;
-            }
+    bool whh_all_u8 = true;
+    for (int l = 0; l < 3; ++l)
+        for (int dir = 0; dir < 2; ++dir)
+            whh_all_u8 = whh_all_u8 && all_q("lstm.weight_hh_l" + std::to_string(l) + (dir ? "_reverse" : ""), UMX_DTYPE_U8, (size_t)G * Hl);
     if (whh_all_u8)
         for (int l = 0; l < 3; ++l)
             whh_qh[l].assign((size_t)8 * S * Hl * 64, 0);
@@ -309,47 +337,8 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
                 w[c * MAGP + k] = v[k];
         if (int rc = upload(&b.out_mean, w))
             return rc;
-        // fc1 (H x 2974) -> (H x KX), zero K padding
-        const bool exact_ok = keepq && !(create_flags & UMX_CREATE_U8_DEQUANT); // integers as exact bf16 planes
-        if (gemm_planes)
-        {
-            std::vector<unsigned short> host;
-            const umx_tensor_view *tv = view(tg, "fc1.weight");
-            if (exact_ok && all_q("fc1.weight", UMX_DTYPE_U8, (size_t)H * NIN))
-            {
-                fill_planes(host, 1, H, KX, tv, nullptr, H, NIN, nullptr, 0);
-                b.fc1_p.s[0] = tv->scale;
-                b.fc1_p.o2[0] = tv->offset + 128.0f * tv->scale;
-                if (int rc = upload_pmat(b.fc1_p, host, 1))
-                    return rc;
-            }
-            else
-            {
-                if (!get(tg, "fc1.weight", (size_t)H * NIN, v))
-                    return UMX_ERR_MODEL;
-                b.fc1_p.s[0] = fill_planes(host, 2, H, KX, nullptr, v.data(), H, NIN, nullptr, 0);
-                if (int rc = upload_pmat(b.fc1_p, host, 2))
-                    return rc;
-            }
-        }
-        else if (const umx_tensor_view *tv = view(tg, "fc1.weight"); all_q("fc1.weight", UMX_DTYPE_U8, (size_t)H * NIN))
-        {
-            if (int rc = upload_q(&b.fc1_q.q, tv, H, NIN, H, KX, nullptr, 0, H))
-                return rc;
-            b.fc1_q.type = BQ_U8;
-            b.fc1_q.s[0] = tv->scale;
-            b.fc1_q.o[0] = tv->offset;
-        }
-        else
-        {
-            if (!get(tg, "fc1.weight", (size_t)H * NIN, v))
-                return UMX_ERR_MODEL;
-            w.assign((size_t)H * KX, 0.f);
-            for (int o = 0; o < H; ++o)
-                memcpy(&w[(size_t)o * KX], &v[(size_t)o * NIN], sizeof(float) * NIN);
-            if (int rc = upload_matrix(&b.fc1_w, &b.fc1_bx, w))
-                return rc;
-        }
+        if (int rc = load_weight(tg, wd[W_FC1], b.w[W_FC1]))
+            return rc;
         const char *bnn[4] = {"running_mean", "running_var", "weight", "bias"};
         for (int k = 0; k < 4; ++k)
         {
@@ -369,116 +358,21 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
             if (int rc = upload(&b.bn3[k], w))
                 return rc;
         }
-        if (gemm_planes)
-        {
-            std::vector<unsigned short> host;
-            const umx_tensor_view *tv = view(tg, "fc2.weight");
-            if (exact_ok && all_q("fc2.weight", UMX_DTYPE_U16, (size_t)H * 2 * H))
-            {
-                fill_planes(host, 2, H, 2 * H, tv, nullptr, H, 2 * H, nullptr, 0);
-                b.fc2_p.s[0] = tv->scale;
-                b.fc2_p.o2[0] = tv->offset + 32896.0f * tv->scale;
-                if (int rc = upload_pmat(b.fc2_p, host, 2))
-                    return rc;
-            }
-            else
-            {
-                if (!get(tg, "fc2.weight", (size_t)H * 2 * H, v))
-                    return UMX_ERR_MODEL;
-                b.fc2_p.s[0] = fill_planes(host, 2, H, 2 * H, nullptr, v.data(), H, 2 * H, nullptr, 0);
-                if (int rc = upload_pmat(b.fc2_p, host, 2))
-                    return rc;
-            }
-        }
-        else if (const umx_tensor_view *tv = view(tg, "fc2.weight"); all_q("fc2.weight", UMX_DTYPE_U16, (size_t)H * 2 * H))
-        {
-            if (int rc = upload_q(&b.fc2_q.q, tv, H, 2 * H, H, 2 * H, nullptr, 0, H))
-                return rc;
-            b.fc2_q.type = BQ_U16;
-            b.fc2_q.s[0] = tv->scale;
-            b.fc2_q.o[0] = tv->offset;
-        }
-        else
-        {
-            if (!get(tg, "fc2.weight", (size_t)H * 2 * H, v))
-                return UMX_ERR_MODEL;
-            if (int rc = upload_matrix(&b.fc2_w, &b.fc2_bx, v))
-                return rc;
-        }
-        // fc3's output rows in the column layout of the mask planes: channel c's 2049 rows at [c * MAGP, ...), zero rows between
-        std::vector<unsigned char> fc3_perm;
-        umx_tensor_view fc3_tv;
-        memset(&fc3_tv, 0, sizeof fc3_tv);
-        if (const umx_tensor_view *tv = view(tg, "fc3.weight"); tv && tv->dtype == UMX_DTYPE_U16 && nelems(tv) == (size_t)NOUT * H)
-        {
-            fc3_perm.assign((size_t)NOUT_PAD * H * 2, 0);
-            for (int c = 0; c < 2; ++c)
-                memcpy(&fc3_perm[(size_t)c * MAGP * H * 2], static_cast<const unsigned char *>(tv->data) + (size_t)c * NBINS * H * 2, (size_t)NBINS * H * 2);
-            fc3_tv = *tv;
-            fc3_tv.data = fc3_perm.data();
-        }
-        auto fc3_f32 = [&](std::vector<float> &dst) -> bool { // dequantised fp32, permuted, (NOUT_PAD x H)
-            std::vector<float> src;
-            if (!get(tg, "fc3.weight", (size_t)NOUT * H, src))
-                return false;
-            dst.assign((size_t)NOUT_PAD * H, 0.f);
-            for (int c = 0; c < 2; ++c)
-                memcpy(&dst[(size_t)c * MAGP * H], &src[(size_t)c * NBINS * H], sizeof(float) * (size_t)NBINS * H);
-            return true;
-        };
-        if (gemm_planes)
-        {
-            std::vector<unsigned short> host;
-            const umx_tensor_view *tv = fc3_tv.data ? &fc3_tv : nullptr;
-            if (exact_ok && all_q("fc3.weight", UMX_DTYPE_U16, (size_t)NOUT * H))
-            {
-                fill_planes(host, 2, NOUT_PAD, H, tv, nullptr, NOUT_PAD, H, nullptr, 0);
-                b.fc3_p.s[0] = tv->scale;
-                b.fc3_p.o2[0] = tv->offset + 32896.0f * tv->scale;
-                if (int rc = upload_pmat(b.fc3_p, host, 2))
-                    return rc;
-            }
-            else
-            {
-                if (!fc3_f32(v))
-                    return UMX_ERR_MODEL;
-                b.fc3_p.s[0] = fill_planes(host, 2, NOUT_PAD, H, nullptr, v.data(), NOUT_PAD, H, nullptr, 0);
-                if (int rc = upload_pmat(b.fc3_p, host, 2))
-                    return rc;
-            }
-        }
-        else if (const umx_tensor_view *tv = &fc3_tv; all_q("fc3.weight", UMX_DTYPE_U16, (size_t)NOUT * H))
-        {
-            if (int rc = upload_q(&b.fc3_q.q, tv, NOUT_PAD, H, NOUT_PAD, H, nullptr, 0, NOUT_PAD))
-                return rc;
-            b.fc3_q.type = BQ_U16;
-            b.fc3_q.s[0] = tv->scale;
-            b.fc3_q.o[0] = tv->offset;
-        }
-        else
-        {
-            if (!fc3_f32(w))
-                return UMX_ERR_MODEL;
-            if (int rc = upload_matrix(&b.fc3_w, &b.fc3_bx, w))
-                return rc;
-        }
-        // LSTM: permute gate rows so a workgroup's 64 columns (g,u) are contiguous
+        if (int rc = load_weight(tg, wd[W_FC2], b.w[W_FC2]))
+            return rc;
+        if (int rc = load_weight(tg, wd[W_FC3], b.w[W_FC3]))
+            return rc;
         for (int l = 0; l < 3; ++l)
         {
-            const umx_tensor_view *ihv[2] = {view(tg, "lstm.weight_ih_l" + std::to_string(l)),
-                                             view(tg, "lstm.weight_ih_l" + std::to_string(l) + "_reverse")};
-            const bool ih_q8 = all_q("lstm.weight_ih_l" + std::to_string(l), UMX_DTYPE_U8, (size_t)G * H) &&
-                               all_q("lstm.weight_ih_l" + std::to_string(l) + "_reverse", UMX_DTYPE_U8, (size_t)G * H);
-            const bool ih_exact = gemm_planes && exact_ok && ih_q8;
-            const bool ih_q = ih_q8 && (!gemm_planes || ih_exact); // the source stays u8 (no fp32 copy needed)
-            std::vector<unsigned short> ih_planes;
-            std::vector<float> ihw((ih_q || gemm_planes) ? 0 : (size_t)2 * G * H), ihb((size_t)2 * G);
+            if (int rc = load_weight(tg, wd[W_IH0 + l], b.w[W_IH0 + l]))
+                return rc;
+            // biases and W_hh: the gate rows of W_ih; W_hh per workgroup slice [chain][S][Hl][64]
+            std::vector<float> ihb((size_t)2 * G);
             for (int dir = 0; dir < 2; ++dir)
             {
                 const std::string sfx = "_l" + std::to_string(l) + (dir ? "_reverse" : "");
-                std::vector<float> wih, whhv, bih, bhhv;
-                if ((!ih_q && !get(tg, "lstm.weight_ih" + sfx, (size_t)G * H, wih)) ||
-                    (!whh_all_u8 && !get(tg, "lstm.weight_hh" + sfx, (size_t)G * Hl, whhv)) ||
+                std::vector<float> whhv, bih, bhhv;
+                if ((!whh_all_u8 && !get(tg, "lstm.weight_hh" + sfx, (size_t)G * Hl, whhv)) ||
                     !get(tg, "lstm.bias_ih" + sfx, G, bih) || !get(tg, "lstm.bias_hh" + sfx, G, bhhv))
                     return UMX_ERR_MODEL;
                 const int chain = tg * 2 + dir;
@@ -489,57 +383,20 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
                     whh_s[l][chain] = hhv->scale;
                     whh_o[l][chain] = hhv->offset;
                 }
-                std::vector<int> rowmap(G); // destination gate-interleaved row -> PyTorch gate row
-                for (int sl = 0; sl < S; ++sl)
-                    for (int g = 0; g < 4; ++g)
-                        for (int u = 0; u < 16; ++u)
-                        {
-                            const int row = g * Hl + sl * 16 + u; // PyTorch gate row (i|f|g|o blocks)
-                            const int col = u * 4 + g; // the 4 gates of a unit share a DPP quad
-                            const size_t n = (size_t)dir * G + (size_t)sl * 64 + col;
-                            rowmap[sl * 64 + col] = row;
-                            if (!ih_q && !gemm_planes)
-                                memcpy(&ihw[n * H], &wih[(size_t)row * H], sizeof(float) * H);
-                            ihb[n] = bih[row];
-                            bhh_h[l][((size_t)chain * S + sl) * 64 + col] = bhhv[row];
-                            for (int k = 0; k < Hl; ++k)
-                            {
-                                const size_t di = (((size_t)chain * S + sl) * Hl + k) * 64 + col;
-                                if (whh_all_u8)
-                                    whh_qh[l][di] = hhq[(size_t)row * Hl + k];
-                                else
-                                    whh_h[l][di] = whhv[(size_t)row * Hl + k];
-                            }
-                        }
-                if (gemm_planes)
+                for (int row = 0; row < G; ++row)
                 {
-                    if (ih_exact)
+                    const int sl = gate_row[row] / 64, col = gate_row[row] % 64;
+                    ihb[(size_t)dir * G + gate_row[row]] = bih[row];
+                    bhh_h[l][((size_t)chain * S + sl) * 64 + col] = bhhv[row];
+                    for (int k = 0; k < Hl; ++k)
                     {
-                        fill_planes(ih_planes, 1, (size_t)2 * G, H, ihv[dir], nullptr, G, H, &rowmap, (size_t)dir * G);
-                        b.ih_p[l].s[dir] = ihv[dir]->scale;
-                        b.ih_p[l].o2[dir] = ihv[dir]->offset + 128.0f * ihv[dir]->scale;
+                        const size_t di = (((size_t)chain * S + sl) * Hl + k) * 64 + col;
+                        if (whh_all_u8)
+                            whh_qh[l][di] = hhq[(size_t)row * Hl + k];
+                        else
+                            whh_h[l][di] = whhv[(size_t)row * Hl + k];
                     }
-                    else
-                        b.ih_p[l].s[dir] = fill_planes(ih_planes, 2, (size_t)2 * G, H, nullptr, wih.data(), G, H, &rowmap, (size_t)dir * G);
                 }
-                else if (ih_q)
-                {
-                    if (int rc = upload_q(&b.ih_q[l].q, ihv[dir], G, H, G, H, &rowmap, (size_t)dir * G, (size_t)2 * G))
-                        return rc;
-                    b.ih_q[l].type = BQ_U8;
-                    b.ih_q[l].s[dir] = ihv[dir]->scale;
-                    b.ih_q[l].o[dir] = ihv[dir]->offset;
-                }
-            }
-            if (gemm_planes)
-            {
-                if (int rc = upload_pmat(b.ih_p[l], ih_planes, ih_exact ? 1 : 2))
-                    return rc;
-            }
-            else if (!ih_q)
-            {
-                if (int rc = upload_matrix(&b.ih_w[l], &b.ih_bx[l], ihw))
-                    return rc;
             }
             if (int rc = upload(&b.ih_b[l], ihb))
                 return rc;
@@ -753,7 +610,7 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
         {
             const void *fn = lstm_persistent_fn(kpw, precise != 0);
             int v = 0;
-            UMX_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fn, lstm_threads, 0));
+            UMX_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fn, LSTM_THREADS, 0));
             per_cu = std::min(per_cu, v);
         }
         UMX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
@@ -808,40 +665,22 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
             lstm_writes_planes = lstm_rowsums;
         }
     }
-    // dynamic LDS > 64 KiB must be opted into
+    // dynamic LDS > 64 KiB must be opted into: the fused Wiener kernels (four transforms + the window) and every entry of the
+    // GEMM kernel tables
+    for (const void *fn : {reinterpret_cast<const void *>(wiener_istft_kernel<true>), reinterpret_cast<const void *>(wiener_istft_kernel<false>),
+                           reinterpret_cast<const void *>(wiener_istft_v_kernel)})
+        UMX_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WI_LDS_BYTES));
+    for (int mode = G_FC1; mode <= G_FC3; ++mode)
     {
-        const void *bxs[10] = {reinterpret_cast<const void *>(gemm_bf16x3_kernel<G_FC1, BQ_U8X>),
-                              reinterpret_cast<const void *>(gemm_bf16x3_kernel<G_IH, BQ_U8X>),
-                              reinterpret_cast<const void *>(gemm_bf16x3_kernel<G_FC1, BQ_F32>),
-                              reinterpret_cast<const void *>(gemm_bf16x3_kernel<G_FC1, BQ_U8>),
-                              reinterpret_cast<const void *>(gemm_bf16x3_kernel<G_IH, BQ_F32>),
-                              reinterpret_cast<const void *>(gemm_bf16x3_kernel<G_IH, BQ_U8>),
-                              reinterpret_cast<const void *>(gemm_bf16x3_kernel<G_FC2, BQ_F32>),
-                              reinterpret_cast<const void *>(gemm_bf16x3_kernel<G_FC2, BQ_U16>),
-                              reinterpret_cast<const void *>(gemm_bf16x3_kernel<G_FC3, BQ_F32>),
-                              reinterpret_cast<const void *>(gemm_bf16x3_kernel<G_FC3, BQ_U16>)};
-        for (const void *fn : bxs)
-            UMX_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, BX_LDS_BYTES));
-        {
-            const int wi_lds = (int)WI_LDS_BYTES; // 155,648: four transforms + the window
-            UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(wiener_istft_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, wi_lds));
-            UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(wiener_istft_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, wi_lds));
-            UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(wiener_istft_v_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wi_lds));
-        }
-#define UMX_GP_ATTR(MODE)                                                                                              \
-    UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_planes_kernel<MODE, 1, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, gp_lds_bytes(2, 2, 1))); \
-    UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_planes_kernel<MODE, 2, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, gp_lds_bytes(2, 2, 2))); \
-    UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_planes_kernel<MODE, 1, 4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, gp_lds_bytes(4, 4, 1))); \
-    UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_planes_kernel<MODE, 2, 4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, gp_lds_bytes(4, 4, 2))); \
-    UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_planes_pp_kernel<MODE, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, gp_lds_bytes(4, 4, 1))); \
-    UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_planes_pp_kernel<MODE, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, gp_lds_bytes(4, 4, 2))); \
-    UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_planes_ps_kernel<MODE, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, ps_lds_bytes(1))); \
-    UMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_planes_ps_kernel<MODE, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, ps_lds_bytes(2)));
-        UMX_GP_ATTR(G_FC1)
-        UMX_GP_ATTR(G_IH)
-        UMX_GP_ATTR(G_FC2)
-        UMX_GP_ATTR(G_FC3)
-#undef UMX_GP_ATTR
+        std::vector<GemmKernel> ks;
+        for (int bq : {BQ_F32, BQ_U8, BQ_U16, BQ_U8X})
+            ks.push_back(bx_kernel(mode, bq));
+        for (int nbp = 1; nbp <= 2; ++nbp)
+            for (int kind = 0; kind < GP_KINDS; ++kind)
+                ks.push_back(gp_kernel(mode, nbp, kind));
+        for (const GemmKernel &k : ks)
+            if (k.fn)
+                UMX_HIP_CHECK(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
     }
     UMX_HIP_CHECK(hipDeviceSynchronize());
     return UMX_OK;

@@ -73,8 +73,8 @@ int umx_hip_ctx::run_lstm_layer(Slot &sl, int layer, const int *active, int nact
         // UMX_ERR_TIMEOUT, not as a hang.
         // always 8*S workgroups: with round-robin dispatch every XCD then receives S of them and the
         // census can enable the intra-XCD protocol; surplus workgroups (skipped targets) exit at once
-        hipError_t e = lstm_gate_launch(device, st, 8 * S * (lstm_threads > 512 ? 2 : 1), 2 * n_cus,
-                                        [&] { return hipLaunchKernel(fn, dim3(8 * S), dim3(lstm_threads), kargs, 0, st); });
+        hipError_t e = lstm_gate_launch(device, st, 8 * S, 2 * n_cus,
+                                        [&] { return hipLaunchKernel(fn, dim3(8 * S), dim3(LSTM_THREADS), kargs, 0, st); });
         if (e != hipSuccess)
         {
             (void)hipGetLastError();

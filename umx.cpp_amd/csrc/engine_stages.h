@@ -7,85 +7,51 @@ void umx_hip_ctx::launch_gemm(Lane &sl, hipStream_t st, int mode, int layer, con
     memset(&g, 0, sizeof g);
     g.M = Tp;
     g.T = T;
+    int bq = BQ_F32;
     for (int i = 0; i < nact; ++i)
     {
         const TargetBufs &b = tb[active[i]];
         const TargetAct &c = sl.ta[active[i]];
+        const GemmWeight &w = b.w[gemm_weight(mode, layer)];
         GemmTarget &t = g.t[i];
         switch (mode)
         {
         case G_FC1:
-            t.A = sl.x; t.B = b.fc1_w; t.C = c.cat;
+            t.A = sl.x; t.C = c.cat;
             t.e0 = b.bn1[0]; t.e1 = b.bn1[1]; t.e2 = b.bn1[2]; t.e3 = b.bn1[3];
             t.q0 = b.in_scale; t.q1 = b.in_mean;
             g.N = H; g.K = KX; g.lda = KX; g.ldc = 2 * H;
             break;
         case G_IH:
             t.A = layer == 0 ? c.cat : layer == 1 ? c.la : c.lb;
-            t.B = b.ih_w[layer]; t.C = c.P; t.e0 = b.ih_b[layer];
+            t.C = c.P; t.e0 = b.ih_b[layer];
             g.N = 4 * H; g.K = H; g.lda = layer == 0 ? 2 * H : H; g.ldc = 4 * H;
             break;
         case G_FC2:
-            t.A = c.cat; t.B = b.fc2_w; t.C = c.a2;
+            t.A = c.cat; t.C = c.a2;
             t.e0 = b.bn2[0]; t.e1 = b.bn2[1]; t.e2 = b.bn2[2]; t.e3 = b.bn2[3];
             g.N = H; g.K = 2 * H; g.lda = 2 * H; g.ldc = H;
             break;
         default:
-            t.A = c.a2; t.B = b.fc3_w; t.C = c.mag;
+            t.A = c.a2; t.C = c.mag;
             t.e0 = b.bn3[0]; t.e1 = b.bn3[1]; t.e2 = b.bn3[2]; t.e3 = b.bn3[3];
             t.q0 = b.out_scale; t.q1 = b.out_mean;
             g.N = NOUT_PAD; g.K = H; g.lda = H; g.ldc = 0;
             break;
         }
-    }
-    // quantised-resident B (config 5): all active targets were loaded the same way
-    int bq = BQ_F32;
-    for (int i = 0; i < nact; ++i)
-    {
-        const TargetBufs &b = tb[active[i]];
-        const QMat &q = mode == G_FC1 ? b.fc1_q : mode == G_IH ? b.ih_q[layer] : mode == G_FC2 ? b.fc2_q : b.fc3_q;
-        GemmTarget &t = g.t[i];
+        t.Bq = w.p; // (t.B, the fp32 matrix of an earlier flavour, stays null)
+        t.bs[0] = w.s[0]; t.bs[1] = w.s[1];
+        t.bo[0] = w.o[0]; t.bo[1] = w.o[1];
         t.bsplit = mode == G_IH ? 2 * H : 0x7fffffff; // W_ih rows >= 4*Hl belong to the reverse direction's tensor
-        t.bs[0] = t.bs[1] = 1.f;
-        if (q.q)
-        {
-            t.Bq = q.q;
-            t.bs[0] = q.s[0]; t.bs[1] = q.s[1];
-            t.bo[0] = q.o[0]; t.bo[1] = q.o[1];
-            bq = q.type;
-        }
+        bq = w.form; // the same for every target (one loader decision for all four)
     }
-    if (gemm_bf16x3 && bq == BQ_F32) // weights resident as three bf16 planes
-        for (int i = 0; i < nact; ++i)
-        {
-            const TargetBufs &b = tb[active[i]];
-            g.t[i].Bq = mode == G_FC1 ? b.fc1_bx : mode == G_IH ? b.ih_bx[layer] : mode == G_FC2 ? b.fc2_bx : b.fc3_bx;
-        }
+    if (bq == BQ_U8 && !u8_dequant)
+        bq = BQ_U8X;
+    const GemmKernel k = bx_kernel(mode, bq);
     const dim3 grid((unsigned)round_up((g.N / GEMM_BN) * (g.M / GEMM_BM), 8), 1, nact), block(256);
     gemm_kernel_last[mode] = "gemm_bf16x3_kernel";
-#define UMX_LAUNCH(KERNEL, LDS) hipLaunchKernelGGL((KERNEL), grid, block, LDS, st, g)
-    switch (mode)
-        {
-        case G_FC1:
-            if (bq == BQ_U8 && !u8_dequant) UMX_LAUNCH((gemm_bf16x3_kernel<G_FC1, BQ_U8X>), BX_LDS_BYTES);
-            else if (bq == BQ_U8) UMX_LAUNCH((gemm_bf16x3_kernel<G_FC1, BQ_U8>), BX_LDS_BYTES);
-            else UMX_LAUNCH((gemm_bf16x3_kernel<G_FC1, BQ_F32>), BX_LDS_BYTES);
-            break;
-        case G_IH:
-            if (bq == BQ_U8 && !u8_dequant) UMX_LAUNCH((gemm_bf16x3_kernel<G_IH, BQ_U8X>), BX_LDS_BYTES);
-            else if (bq == BQ_U8) UMX_LAUNCH((gemm_bf16x3_kernel<G_IH, BQ_U8>), BX_LDS_BYTES);
-            else UMX_LAUNCH((gemm_bf16x3_kernel<G_IH, BQ_F32>), BX_LDS_BYTES);
-            break;
-        case G_FC2:
-            if (bq == BQ_U16) UMX_LAUNCH((gemm_bf16x3_kernel<G_FC2, BQ_U16>), BX_LDS_BYTES);
-            else UMX_LAUNCH((gemm_bf16x3_kernel<G_FC2, BQ_F32>), BX_LDS_BYTES);
-            break;
-        default:
-            if (bq == BQ_U16) UMX_LAUNCH((gemm_bf16x3_kernel<G_FC3, BQ_U16>), BX_LDS_BYTES);
-            else UMX_LAUNCH((gemm_bf16x3_kernel<G_FC3, BQ_F32>), BX_LDS_BYTES);
-            break;
-        }
-#undef UMX_LAUNCH
+    void *kargs[] = {&g};
+    (void)hipLaunchKernel(k.fn, grid, block, kargs, k.lds, st);
 }
 
 // gemm_planes.h: split one A operand of every active target into bf16 planes + row sums
@@ -160,19 +126,17 @@ void umx_hip_ctx::launch_gemm_planes(Lane &ln, int nl, hipStream_t st, int mode,
     {
         const TargetBufs &b = tb[active[i]];
         const TargetAct &c = ln.ta[active[i]];
+        const GemmWeight &w = b.w[gemm_weight(mode, layer)];
         GemmPTarget &t = g.t[i];
-        const PMat *pm = nullptr;
         t.bsplit = 0x7fffffff;
         switch (mode)
         {
         case G_FC1:
-            pm = &b.fc1_p;
             t.A = c.xs_p; t.C = c.cat; t.rs0 = c.rs_xs; t.rsc = c.rsc_xs;
             t.e0 = b.bn1[0]; t.e1 = b.bn1[1]; t.e2 = b.bn1[2]; t.e3 = b.bn1[3];
             g.N = H; g.K = KX; g.lda = KX; g.ldc = 2 * H; g.a_plane = rows_all * KX;
             break;
         case G_IH:
-            pm = &b.ih_p[layer];
             t.A = layer == 0 ? c.cat_p : layer == 1 ? c.la_p : c.lb_p;
             t.rs0 = layer == 0 ? c.rs_catL : layer == 1 ? c.rs_la : c.rs_lb;
             if (layer > 0 && lstm_rowsums) // one row-sum array per direction, from the recurrence itself
@@ -183,7 +147,6 @@ void umx_hip_ctx::launch_gemm_planes(Lane &ln, int nl, hipStream_t st, int mode,
             g.a_plane = layer == 0 ? rows_all * 2 * H : rows_all * H;
             break;
         case G_FC2:
-            pm = &b.fc2_p;
             t.A = c.cat_p; t.C = c.a2; t.rs0 = c.rs_catL; t.rs1 = c.rs_catR;
             if (lstm_rowsums)
                 t.rs2 = c.rs_catR + rows_all;
@@ -191,24 +154,21 @@ void umx_hip_ctx::launch_gemm_planes(Lane &ln, int nl, hipStream_t st, int mode,
             g.N = H; g.K = 2 * H; g.lda = 2 * H; g.ldc = H; g.a_plane = rows_all * 2 * H;
             break;
         default:
-            pm = &b.fc3_p;
             t.A = c.a2_p; t.C = c.mag; t.rs0 = c.rs_a2; t.rsc = c.rsc_a2;
             t.e0 = b.bn3[0]; t.e1 = b.bn3[1]; t.e2 = b.bn3[2]; t.e3 = b.bn3[3];
             t.q0 = b.out_scale; t.q1 = b.out_mean;
             g.N = NOUT_PAD; g.K = H; g.lda = H; g.ldc = 0; g.a_plane = rows_all * H;
             break;
         }
-        t.B = pm->p;
-        t.bs[0] = pm->s[0]; t.bs[1] = pm->s[1];
-        t.bo2[0] = pm->o2[0]; t.bo2[1] = pm->o2[1];
-        nbp = pm->nbp; // the same for every target (all_q at create)
+        t.B = static_cast<const unsigned short *>(w.p);
+        t.bs[0] = w.s[0]; t.bs[1] = w.s[1];
+        t.bo2[0] = w.o[0]; t.bo2[1] = w.o[1];
+        nbp = w.form; // the same for every target (one loader decision for all four)
     }
     // 256 x 256 tiles (half the L2 traffic per flop) when they fill the chip
     const int blocks_big = (g.N / 256) * (g.M / 256) * nact;
     const bool big = g.N % 256 == 0 && blocks_big >= 224;
     const int bm = big ? 256 : 128;
-    const dim3 grid((unsigned)round_up((g.N / bm) * (g.M / bm), 8), 1, nact), block(big ? 1024 : 256);
-    const size_t lds = big ? gp_lds_bytes(4, 4, nbp) : gp_lds_bytes(2, 2, nbp);
     // 256 x 256 blocks: eight waves of 128 x 64 in ping-pong (gemm_planes_pp.h), or sixteen waves of 64 x 64 in lock step
     // (gemm_planes.h: same bits; UMX_GEMM_PP=0, or a bit per GemmMode).  Measured alone, 32 lanes, ms per launch incl. the split
     // kernel, A/B on one box (round 3): fc1 5.70-5.98 -> 5.38-5.52, W_ih 5.69-6.14 -> 5.29-5.67, fc2 4.77 -> 4.62-4.66, fc3 9.21 -> 8.98-9.15.
@@ -219,23 +179,13 @@ void umx_hip_ctx::launch_gemm_planes(Lane &ln, int nl, hipStream_t st, int mode,
     const int ps_wgs = n_cus / 8 * 8;
     const bool ps = pp && (env_gemm_ps < 0 || ((env_gemm_ps >> mode) & 1)) && g.K / GP_BK >= 6 && ps_wgs >= 8 && blocks_big > ps_wgs && g.Tp_lane >= 256;
     gemm_kernel_last[mode] = ps ? "gemm_planes_ps_kernel" : pp ? "gemm_planes_pp_kernel" : "gemm_planes_kernel";
-#define UMX_GP(MODE)                                                                                                 \
-    if (ps && nbp == 1) hipLaunchKernelGGL((gemm_planes_ps_kernel<MODE, 1>), dim3(ps_wgs), dim3(512), ps_lds_bytes(1), st, g, nact); \
-    else if (ps) hipLaunchKernelGGL((gemm_planes_ps_kernel<MODE, 2>), dim3(ps_wgs), dim3(512), ps_lds_bytes(2), st, g, nact); \
-    else if (pp && nbp == 1) hipLaunchKernelGGL((gemm_planes_pp_kernel<MODE, 1>), grid, dim3(512), lds, st, g);           \
-    else if (pp) hipLaunchKernelGGL((gemm_planes_pp_kernel<MODE, 2>), grid, dim3(512), lds, st, g);                  \
-    else if (big && nbp == 1) hipLaunchKernelGGL((gemm_planes_kernel<MODE, 1, 4, 4>), grid, block, lds, st, g);      \
-    else if (big) hipLaunchKernelGGL((gemm_planes_kernel<MODE, 2, 4, 4>), grid, block, lds, st, g);                  \
-    else if (nbp == 1) hipLaunchKernelGGL((gemm_planes_kernel<MODE, 1, 2, 2>), grid, block, lds, st, g);             \
-    else hipLaunchKernelGGL((gemm_planes_kernel<MODE, 2, 2, 2>), grid, block, lds, st, g);
-    switch (mode)
-    {
-    case G_FC1: UMX_GP(G_FC1) break;
-    case G_IH: UMX_GP(G_IH) break;
-    case G_FC2: UMX_GP(G_FC2) break;
-    default: UMX_GP(G_FC3) break;
-    }
-#undef UMX_GP
+    const GemmKernel k = gp_kernel(mode, nbp, ps ? GP_PS : pp ? GP_PP : big ? GP_256 : GP_128);
+    void *kargs[] = {&g, &nact}; // (nact: the persistent kernel's second argument; the others take g alone)
+    if (ps)
+        (void)hipLaunchKernel(k.fn, dim3(ps_wgs), dim3(512), kargs, k.lds, st);
+    else
+        (void)hipLaunchKernel(k.fn, dim3((unsigned)round_up((g.N / bm) * (g.M / bm), 8), 1, nact), dim3(pp ? 512 : big ? 1024 : 256), kargs,
+                              k.lds, st);
 }
 
 void umx_hip_ctx::launch_gemm_lanes(Slot &sl, hipStream_t st, int nb, const float *const *audio_dev, int mode, int layer,

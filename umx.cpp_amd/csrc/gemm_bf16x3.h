@@ -1,5 +1,5 @@
-// gemm_bf16x3.h -- the dense stack's GEMMs on the bf16 matrix cores with fp32-class accuracy (the default;
-// UMX_CREATE_GEMM_F32 / UMX_GEMM=f32 selects the fp32-MFMA kernel of gemm_kernels.h instead).
+// gemm_bf16x3.h -- the dense stack's GEMMs on the bf16 matrix cores with fp32-class accuracy (the staged flavour: the
+// default of single-track contexts; track-batched ones run gemm_planes.h).
 //
 // Every fp32 operand is split into three bf16 terms, x = x1 + x2 + x3 with x1 = bf16(x), x2 = bf16(x - x1),
 // x3 = bf16(x - x1 - x2) (each subtraction is exact in fp32; the residual after three terms is < 2^-26 |x|),
