@@ -241,6 +241,37 @@ int umx_hip_separate_tracks(umx_hip_ctx *ctx, int n_tracks, const float *const *
                             const int *shift_offset, float *const *out_host, unsigned flags, void (*progress)(float, void *),
                             void *progress_user);
 
+/* Any sample rate: Open-Unmix's preprocess resamples its input to the model's 44.1 kHz with torchaudio's default
+ * windowed-sinc filter (sinc_interp_hann: 6 zero crossings, rolloff 0.99).  Here that filter runs on the device, into 44.1 kHz and
+ * back out.  For rates r_in -> r_out (8000 .. 192000 Hz) with g = gcd, M = r_in / g, L = r_out / g, b = 0.99 min(M, L), W = 6:
+ *     y[j] = sum_i x[i] (b / M) k(b (i / M - j / L)),  k(t) = sinc(t) cos^2(pi t / 2W) for |t| < W, else 0,
+ * each channel on its own, x zero outside [0, n_in), no delay, y defined for every j >= 0.  Each output is the fp32 sum of its
+ * taps (an fp32 table of L phases x K = 2D + 2 taps, D = ceil(W M / b), built in double) in a fixed order: launches of one or
+ * four buffers give the same bits. */
+#define UMX_RESAMPLE_MIN_RATE 8000
+#define UMX_RESAMPLE_MAX_RATE 192000
+/* the natural output length ceil(n L / M) (torchaudio's target_length); < 0 for a rate outside the range.  Host arithmetic. */
+long long umx_hip_resampled_length(long long n, int rate_in, int rate_out);
+/* n_buffers (1 .. 4) device buffers (2, n_in) -> (2, n_out), queued on hip_stream; writes exactly n_out frames of each output.
+ * n_out may differ from the natural length: beyond it the formula goes on (a decaying tail, then zeros). */
+int umx_hip_resample_device(umx_hip_ctx *ctx, int rate_in, int rate_out, int n_buffers, const float *const *in_dev, int n_in,
+                            float *const *out_dev, int n_out, void *hip_stream);
+/* umx_hip_shift_inference / umx_hip_separate_tracks for tracks at `rate`: the stems come back with the caller's length at the
+ * caller's rate, aligned sample for sample with the input.  The track is resampled to n44 = umx_hip_resampled_length(length,
+ * rate, 44100) frames, separated exactly as umx_hip_shift_inference / _separate_tracks separate n44 frames at 44.1 kHz
+ * (offset / shift_offset count 44.1 kHz samples, same meaning), and the four stems (those n44 frames, zero outside them) are
+ * resampled back: bit for bit that composition.  A track at 44100 is not resampled: bitwise today's entry points.  A rate outside
+ * 8000 .. 192000 is UMX_ERR_ARG.  Resampled tracks' stems are downloaded after the last segment, not region by region. */
+int umx_hip_shift_inference_rate(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int offset, float *const out_host[4],
+                                 unsigned flags, void (*progress)(float, void *), void *progress_user);
+int umx_hip_separate_tracks_rate(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *rate,
+                                 const int *shift_offset, float *const *out_host, unsigned flags, void (*progress)(float, void *),
+                                 void *progress_user);
+/* testing, host only: the fp32 tap table of a rate pair (taps[phase * K + d + D]; cap floats at most), its phase count L, taps
+ * per phase K and first offset -D.  UMX_ERR_ARG for a bad rate or a too small cap (the sizes are still reported). */
+int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase,
+                                int *first_offset);
+
 /* One segment phase by phase: front (STFT, fc1, W_ih layer 0) | LSTM layer 0 | 1 | 2 | back (fc2, fc3, Wiener,
  * iSTFT).  Same kernels and results as umx_hip_infer_segment; the cuts are where the reference's per-chain
  * (h, c) (lstm.cpp:116-161: read at the start of a layer, left behind at its end) crosses from the GPU that ran

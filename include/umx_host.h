@@ -49,6 +49,11 @@ int umx_wav_load(const char *path, float **audio_out, int *n_frames_out, int *ch
 void umx_wav_free(float *audio);
 /* write: stereo 32-bit IEEE float WAV, 44100 Hz (dsp.cpp:97-99 {channels, PCM_FLT, ...}) */
 int umx_wav_write_f32(const char *path, const float *audio, int n_frames, char *err);
+/* the same decoders for any rate in 8000 .. 192000 Hz (UMX_RESAMPLE_MIN_RATE .. _MAX_RATE): the rate is reported in *rate_out,
+ * not refused; for umx_hip_shift_inference_rate / _separate_tracks_rate */
+int umx_wav_load_rate(const char *path, float **audio_out, int *n_frames_out, int *channels_in_file, int *rate_out, char *err);
+/* stereo 32-bit IEEE float WAV at `rate` Hz */
+int umx_wav_write_f32_rate(const char *path, const float *audio, int n_frames, int rate, char *err);
 
 /* ---- segmented apply: replaces split_inference / shift_inference (umx.cpp:99-295).
  * The backend is the per-segment call (umx_inference, umx.cpp:226-227): audio (2,n) -> out[4] (2,n);

@@ -157,6 +157,16 @@ def hip_lib():
     lib.umx_hip_split_inference.argtypes = [C.c_void_p, _fp, C.c_int, C.POINTER(_fp), C.c_uint, C.c_void_p, C.c_void_p]
     lib.umx_hip_shift_inference.argtypes = [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(_fp), C.c_uint, C.c_void_p,
                                             C.c_void_p]
+    lib.umx_hip_resampled_length.restype = C.c_longlong
+    lib.umx_hip_resampled_length.argtypes = [C.c_longlong, C.c_int, C.c_int]
+    lib.umx_hip_resample_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int,
+                                            C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
+    lib.umx_hip_shift_inference_rate.argtypes = [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.c_uint, C.c_void_p,
+                                                 C.c_void_p]
+    lib.umx_hip_separate_tracks_rate.argtypes = [C.c_void_p, C.c_int, C.POINTER(_fp), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                 C.POINTER(C.c_int), C.POINTER(_fp), C.c_uint, C.c_void_p, C.c_void_p]
+    lib.umx_hip_debug_resample_taps.argtypes = [C.c_int, C.c_int, _fp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                C.POINTER(C.c_int)]
     _hip = lib
     return lib
 
@@ -169,6 +179,8 @@ CREATE_U8_DEQUANT = 0x20
 CREATE_GEMM_STAGED = 0x40
 CREATE_GEMM_PLANES = 0x80
 MAX_TRACKS = 64
+MODEL_RATE = 44100
+RESAMPLE_MIN_RATE, RESAMPLE_MAX_RATE = 8000, 192000
 
 HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "umx_hip_n_tracks", "umx_hip_lstm_is_batched",
                "umx_hip_track_stream_reset", "umx_hip_track_stream_get", "umx_hip_track_stream_set",
@@ -184,7 +196,29 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_stream_layer_floats", "umx_hip_stream_get_layer", "umx_hip_stream_set_layer",
                "umx_hip_segment_begin", "umx_hip_segment_lstm_layer", "umx_hip_segment_end",
                "umx_hip_split_inference", "umx_hip_shift_inference", "umx_hip_debug_lds_guard", "umx_hip_debug_f16_bits",
-               "umx_hip_segment_masks_device", "umx_hip_target_mag_device", "umx_hip_segment_finish_device", "umx_hip_gate_reserve", "umx_hip_segment_discard", "umx_hip_pipeline_depth"]
+               "umx_hip_segment_masks_device", "umx_hip_target_mag_device", "umx_hip_segment_finish_device", "umx_hip_gate_reserve", "umx_hip_segment_discard", "umx_hip_pipeline_depth",
+               "umx_hip_resampled_length", "umx_hip_resample_device", "umx_hip_shift_inference_rate", "umx_hip_separate_tracks_rate",
+               "umx_hip_debug_resample_taps"]
+
+
+def resampled_length(n, rate_in, rate_out):
+    """ceil(n L / M), the natural output length of the device resampler (host arithmetic; < 0 for a bad rate)."""
+    return int(hip_lib().umx_hip_resampled_length(int(n), int(rate_in), int(rate_out)))
+
+
+def resample_taps(rate_in, rate_out):
+    """The resampler's fp32 tap table of a rate pair: (taps [L][K], first offset -D).  Host only."""
+    lib = hip_lib()
+    L, K, d0 = C.c_int(), C.c_int(), C.c_int()
+    rc = lib.umx_hip_debug_resample_taps(int(rate_in), int(rate_out), None, 0, C.byref(L), C.byref(K), C.byref(d0))
+    if L.value < 1:
+        raise UmxError(rc, f"bad rate pair {rate_in} -> {rate_out}")
+    taps = np.empty((L.value, K.value), np.float32)
+    rc = lib.umx_hip_debug_resample_taps(int(rate_in), int(rate_out), taps.ctypes.data_as(_fp), taps.size, C.byref(L), C.byref(K),
+                                         C.byref(d0))
+    if rc:
+        raise UmxError(rc, "umx_hip_debug_resample_taps")
+    return taps, d0.value
 
 
 def views_from_file_tensors(targets, quantised=True):
@@ -358,18 +392,25 @@ class Engine:
                                                             hip_stream))
 
     # --- whole track on the device (umx.cpp:99-295) ---
-    def separate(self, wave, flags=0, shift_offset=None):
+    def separate(self, wave, flags=0, shift_offset=None, rate=MODEL_RATE):
         """(2,L) host array -> 4 x (2,L): split_inference with the track resident in HBM; shift_offset: None =
-        no shift buffer, n >= 0 = shift_inference with that offset."""
+        no shift buffer, n >= 0 = shift_inference with that offset.  rate != 44100: umx_hip_shift_inference_rate (the track is
+        resampled to 44.1 kHz and its stems back on the device; shift_offset None = the reference's 4033)."""
         wave = np.asarray(wave, np.float32)
         L = wave.shape[1]
         a = np.ascontiguousarray(wave.T).ravel()
         outs = [np.empty(2 * L, np.float32) for _ in range(4)]
-        self.separate_interleaved(a, L, outs, flags, shift_offset)
+        if rate == MODEL_RATE:
+            self.separate_interleaved(a, L, outs, flags, shift_offset)
+        else:
+            arr = (_fp * 4)(*[o.ctypes.data_as(_fp) for o in outs])
+            self._check(self.lib.umx_hip_shift_inference_rate(self.h, a.ctypes.data_as(_fp), L, int(rate),
+                                                              -1 if shift_offset is None else shift_offset, arr, flags, None, None))
         return [np.ascontiguousarray(o.reshape(L, 2).T) for o in outs]
 
-    def separate_many(self, waves, flags=0, shift_offsets=None):
-        """Several tracks at once, one per track lane (umx_hip_separate_tracks): list of (2,L_i) -> list of [4 x (2,L_i)]."""
+    def separate_many(self, waves, flags=0, shift_offsets=None, rates=None):
+        """Several tracks at once, one per track lane (umx_hip_separate_tracks): list of (2,L_i) -> list of [4 x (2,L_i)].
+        rates: one sample rate per track (umx_hip_separate_tracks_rate), None = all 44.1 kHz."""
         nt = len(waves)
         ins = [np.ascontiguousarray(np.asarray(w, np.float32).T).ravel() for w in waves]
         Ls = [np.asarray(w).shape[1] for w in waves]
@@ -377,8 +418,19 @@ class Engine:
         a = (_fp * nt)(*[x.ctypes.data_as(_fp) for x in ins])
         o = (_fp * (4 * nt))(*[x.ctypes.data_as(_fp) for t4 in outs for x in t4])
         sh = (C.c_int * nt)(*[(-1 if s is None else s) for s in (shift_offsets or [None] * nt)])
-        self._check(self.lib.umx_hip_separate_tracks(self.h, nt, a, (C.c_int * nt)(*Ls), sh, o, flags, None, None))
+        if rates is None:
+            self._check(self.lib.umx_hip_separate_tracks(self.h, nt, a, (C.c_int * nt)(*Ls), sh, o, flags, None, None))
+        else:
+            self._check(self.lib.umx_hip_separate_tracks_rate(self.h, nt, a, (C.c_int * nt)(*Ls), (C.c_int * nt)(*rates), sh, o, flags,
+                                                              None, None))
         return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t4] for t4, L in zip(outs, Ls)]
+
+    def resample_device(self, rate_in, rate_out, in_ptrs, n_in, out_ptrs, n_out, hip_stream=None):
+        """umx_hip_resample_device: 1 .. 4 device buffers (2,n_in) interleaved -> (2,n_out), queued on hip_stream."""
+        nb = len(in_ptrs)
+        assert len(out_ptrs) == nb
+        self._check(self.lib.umx_hip_resample_device(self.h, int(rate_in), int(rate_out), nb, (C.c_void_p * nb)(*in_ptrs), int(n_in),
+                                                     (C.c_void_p * nb)(*out_ptrs), int(n_out), hip_stream))
 
     def separate_interleaved(self, a, L, outs, flags=0, shift_offset=None):
         """The bare C call: a = (2,L) interleaved float32, outs = 4 preallocated float32[2L]; returns seconds."""
@@ -527,7 +579,7 @@ class Engine:
 # ------------------------------------------------------------------ C++17 host library (umx_host.h)
 HOST_SYMBOLS = ["umx_model_load", "umx_model_free", "umx_model_hidden", "umx_model_n_tensors", "umx_model_views",
                 "umx_model_data_bytes", "umx_model_load_progress", "umx_model_dequantize", "umx_wav_load",
-                "umx_wav_free", "umx_wav_write_f32", "umx_split_inference", "umx_shift_inference",
+                "umx_wav_free", "umx_wav_write_f32", "umx_wav_load_rate", "umx_wav_write_f32_rate", "umx_split_inference", "umx_shift_inference",
                 "umx_segment_plan", "umx_transition_weight", "umx_split_inference_carry", "umx_split_inference_targets"]
 
 SEGMENT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _fp, C.c_int, C.POINTER(_fp))
@@ -597,6 +649,8 @@ def host_lib():
     lib.umx_wav_load.argtypes = [C.c_char_p, C.POINTER(_fp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p]
     lib.umx_wav_free.argtypes = [_fp]
     lib.umx_wav_write_f32.argtypes = [C.c_char_p, _fp, C.c_int, C.c_char_p]
+    lib.umx_wav_load_rate.argtypes = [C.c_char_p, C.POINTER(_fp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p]
+    lib.umx_wav_write_f32_rate.argtypes = [C.c_char_p, _fp, C.c_int, C.c_int, C.c_char_p]
     lib.umx_split_inference.argtypes = [C.POINTER(Backend), _fp, C.c_int, C.c_int, C.POINTER(_fp), PROGRESS_FN,
                                         C.c_void_p, C.c_char_p]
     lib.umx_shift_inference.argtypes = [C.POINTER(Backend), _fp, C.c_int, C.c_int, C.c_int, C.POINTER(_fp),
@@ -685,11 +739,27 @@ def wav_load(path):
     return np.ascontiguousarray(a.T), ch.value
 
 
-def wav_write(path, wave):
-    """write_audio_file (dsp.cpp:80-101): (2,n) -> stereo float32 WAV."""
+def wav_load_rate(path):
+    """umx_wav_load_rate: -> ((2,n) float32, channels in file, sample rate); any rate of 8 .. 192 kHz."""
+    lib = host_lib()
+    p, n, ch, rate = _fp(), C.c_int(), C.c_int(), C.c_int()
+    err = C.create_string_buffer(256)
+    rc = lib.umx_wav_load_rate(str(path).encode(), C.byref(p), C.byref(n), C.byref(ch), C.byref(rate), err)
+    if rc:
+        raise HostError(rc, err.value.decode())
+    a = np.ctypeslib.as_array(p, shape=(n.value, 2)).copy()
+    lib.umx_wav_free(p)
+    return np.ascontiguousarray(a.T), ch.value, rate.value
+
+
+def wav_write(path, wave, rate=MODEL_RATE):
+    """write_audio_file (dsp.cpp:80-101): (2,n) -> stereo float32 WAV (at `rate` Hz: umx_wav_write_f32_rate)."""
     a = np.ascontiguousarray(np.asarray(wave, np.float32).T)
     err = C.create_string_buffer(256)
-    rc = host_lib().umx_wav_write_f32(str(path).encode(), a.ctypes.data_as(_fp), a.shape[0], err)
+    if rate == MODEL_RATE:
+        rc = host_lib().umx_wav_write_f32(str(path).encode(), a.ctypes.data_as(_fp), a.shape[0], err)
+    else:
+        rc = host_lib().umx_wav_write_f32_rate(str(path).encode(), a.ctypes.data_as(_fp), a.shape[0], int(rate), err)
     if rc:
         raise HostError(rc, err.value.decode())
 

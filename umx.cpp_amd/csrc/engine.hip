@@ -32,6 +32,7 @@
 #include "lstm_batch.h"
 #include "lstm_batch8.h"
 #include "track_kernels.h"
+#include "resample.h"
 #include "stft_kernels.h"
 #include "wiener_kernels.h"
 #include "wiener_istft.h"
@@ -541,10 +542,20 @@ struct umx_hip_ctx
     // whole track on the device (split_inference / shift_inference, umx.cpp:99-295)
     int track(const float *audio_host, int length, int shift_offset, float *const out_host[4], unsigned flags,
               void (*progress)(float, void *), void *progress_user);
+    // rate == nullptr: every track at 44.1 kHz; else track i is at rate[i] and is resampled to 44.1 kHz and back on the device
     int tracks(int nt, const float *const *audio_host, const int *length, const int *shift_offset, float *const *out_host, unsigned flags,
-               void (*progress)(float, void *), void *progress_user);
+               void (*progress)(float, void *), void *progress_user, const int *rate = nullptr);
     int tracks_once(int nt, const float *const *audio_host, const int *length, const int *shift_offset, float *const *out_host,
-                    unsigned flags, void (*progress)(float, void *), void *progress_user);
+                    unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate);
+    // resampling (resample.h): the tap table of each (rate_in, rate_out) pair, built once and kept in HBM
+    std::map<std::pair<int, int>, float *> rs_taps;
+    int resample_plan(int rate_in, int rate_out, ResampleGeom &g, const float **taps_dev);
+    struct RsStage // per track lane: the track and its four stems at the caller's rate (grow-only)
+    {
+        float *in = nullptr, *out[4] = {};
+        size_t cap = 0; // frames
+    };
+    std::vector<RsStage> rs_stage;
     struct TrackBufs // whole-track driver, per track lane: the (shifted) track, 4 stem accumulators, weight sum, 2 x 4 segment stems
     {
         float *in = nullptr, *out[4] = {}, *sumw = nullptr, *seg[kMaxSlots][4] = {};

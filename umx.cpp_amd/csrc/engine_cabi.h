@@ -208,6 +208,75 @@ int umx_hip_separate_tracks(umx_hip_ctx *ctx, int n_tracks, const float *const *
 {
     return ctx ? ctx->tracks(n_tracks, audio_host, length, shift_offset, out_host, flags, progress, progress_user) : UMX_ERR_ARG;
 }
+long long umx_hip_resampled_length(long long n, int rate_in, int rate_out) { return resampled_length(n, rate_in, rate_out); }
+
+int umx_hip_resample_device(umx_hip_ctx *ctx, int rate_in, int rate_out, int n_buffers, const float *const *in_dev, int n_in,
+                            float *const *out_dev, int n_out, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (n_buffers < 1 || n_buffers > 4 || !in_dev || !out_dev || n_in < 1 || n_out < 0)
+    {
+        ctx->set_error("resample: need 1 .. 4 buffers, n_in >= 1 and n_out >= 0");
+        return UMX_ERR_ARG;
+    }
+    for (int b = 0; b < n_buffers; ++b)
+        if (!in_dev[b] || !out_dev[b])
+        {
+            ctx->set_error("resample: null buffer");
+            return UMX_ERR_ARG;
+        }
+    ResampleGeom g;
+    const float *taps = nullptr;
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    if (int rc = ctx->resample_plan(rate_in, rate_out, g, &taps))
+        return rc;
+    UMX_HIP_CHECK_CTX(ctx, launch_resample(g, taps, n_buffers, in_dev, n_in, out_dev, n_out, (hipStream_t)hip_stream));
+    return UMX_OK;
+}
+
+int umx_hip_shift_inference_rate(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int offset, float *const out_host[4],
+                                 unsigned flags, void (*progress)(float, void *), void *progress_user)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!out_host)
+    {
+        ctx->set_error("track: need audio, outputs, length >= 1 and shift offset < 22050");
+        return UMX_ERR_ARG;
+    }
+    if (offset < 0)
+        offset = UMX_REFERENCE_SHIFT;
+    return ctx->tracks(1, &audio_host, &length, &offset, out_host, flags, progress, progress_user, &rate);
+}
+int umx_hip_separate_tracks_rate(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *rate,
+                                 const int *shift_offset, float *const *out_host, unsigned flags, void (*progress)(float, void *),
+                                 void *progress_user)
+{
+    if (!ctx || !rate)
+        return UMX_ERR_ARG;
+    return ctx->tracks(n_tracks, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate);
+}
+
+int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase, int *first_offset)
+{
+    ResampleGeom g;
+    if (!resample_geom(rate_in, rate_out, g))
+        return UMX_ERR_ARG;
+    if (phases)
+        *phases = g.L;
+    if (taps_per_phase)
+        *taps_per_phase = g.K;
+    if (first_offset)
+        *first_offset = -g.D;
+    if (!taps || cap < (size_t)g.L * g.K)
+        return UMX_ERR_ARG;
+    std::vector<float> t;
+    resample_taps(g, t);
+    std::copy(t.begin(), t.end(), taps);
+    return UMX_OK;
+}
+
 int umx_hip_shift_inference(umx_hip_ctx *ctx, const float *audio_host, int length, int offset, float *const out_host[4],
                             unsigned flags, void (*progress)(float, void *), void *progress_user)
 {

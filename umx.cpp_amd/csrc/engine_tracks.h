@@ -21,35 +21,59 @@ int umx_hip_ctx::track(const float *audio_host, int length, int shift_offset, fl
 // idle), the weighted overlap-add and the normalisation run per lane on the device, finished regions are downloaded
 // while later segments run.  nt == 1 is umx_hip_split_inference / umx_hip_shift_inference.
 int umx_hip_ctx::tracks(int nt, const float *const *audio_host, const int *length, const int *shift_offset, float *const *out_host,
-                        unsigned flags, void (*progress)(float, void *), void *progress_user)
+                        unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate)
 {
     // A persistent-kernel timeout inside a track cannot be repaired segment by segment (the overlap-add has consumed
     // the stems): everything is run again, once, with the per-step driver the timeout switches the context to.
     no_recovery = true;
-    int rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user);
-    if (rc == UMX_ERR_TIMEOUT)
-        rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user);
+    int rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate);
+    if (rc == UMX_ERR_TIMEOUT) // (a resampled track is resampled again from its host copy: tracks_once starts from scratch)
+        rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate);
     no_recovery = false;
     pending.clear();
     pending_lost = false;
     return rc;
 }
 
-int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *length, const int *shift_offset, float *const *out_host,
-                             unsigned flags, void (*progress)(float, void *), void *progress_user)
+int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *length_in, const int *shift_offset, float *const *out_host,
+                             unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate)
 {
-    if (nt < 1 || nt > B || !audio_host || !length || !shift_offset || !out_host)
+    if (nt < 1 || nt > B || !audio_host || !length_in || !shift_offset || !out_host)
     {
         set_error("tracks: need 1 <= n_tracks <= the context's track count and non-null argument arrays");
         return UMX_ERR_ARG;
     }
     for (int ln = 0; ln < nt; ++ln)
-        if (!audio_host[ln] || length[ln] < 1 || shift_offset[ln] >= UMX_MAX_SHIFT || !out_host[4 * ln] || !out_host[4 * ln + 1] ||
+        if (!audio_host[ln] || length_in[ln] < 1 || shift_offset[ln] >= UMX_MAX_SHIFT || !out_host[4 * ln] || !out_host[4 * ln + 1] ||
             !out_host[4 * ln + 2] || !out_host[4 * ln + 3])
         {
             set_error("track: need audio, outputs, length >= 1 and shift offset < 22050");
             return UMX_ERR_ARG;
         }
+    // A track at another rate runs as the n44 = ceil(length L / M) frames of its 44.1 kHz version: `length` below is
+    // that length, length_in the caller's.
+    int length[LSTMB_MAX_TRACKS];
+    bool resampled[LSTMB_MAX_TRACKS] = {};
+    ResampleGeom rs_fwd[LSTMB_MAX_TRACKS], rs_back[LSTMB_MAX_TRACKS];
+    const float *rs_fwd_taps[LSTMB_MAX_TRACKS] = {}, *rs_back_taps[LSTMB_MAX_TRACKS] = {};
+    for (int ln = 0; ln < nt; ++ln)
+    {
+        length[ln] = length_in[ln];
+        if (!rate || rate[ln] == RS_MODEL_RATE)
+            continue;
+        const long long n44 = resampled_length(length_in[ln], rate[ln], RS_MODEL_RATE);
+        if (n44 < 1 || n44 > 0x7fffffff / 2)
+        {
+            set_error(n44 < 1 ? "track: sample rate outside 8000 .. 192000 Hz" : "track: too long");
+            return UMX_ERR_ARG;
+        }
+        length[ln] = (int)n44;
+        resampled[ln] = true;
+        if (int rc = resample_plan(rate[ln], RS_MODEL_RATE, rs_fwd[ln], &rs_fwd_taps[ln]))
+            return rc;
+        if (int rc = resample_plan(RS_MODEL_RATE, rate[ln], rs_back[ln], &rs_back_taps[ln]))
+            return rc;
+    }
     if (ph_next != -1)
     {
         set_error("track: a phased segment is open (umx_hip_segment_end first)");
@@ -132,11 +156,44 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
             UMX_HIP_CHECK(hipMemset(tb_.out[t], 0, sizeof(float) * 2 * (size_t)L2[ln]));
         UMX_HIP_CHECK(hipMemset(tb_.sumw, 0, sizeof(float) * (size_t)L2[ln]));
     }
+    // a resampled track goes up whole at its own rate, into a grow-only staging buffer, and is resampled straight into the padded
+    // 44.1 kHz signal (upload_until below then has nothing left to do for it)
+    if (rs_stage.size() < (size_t)nt)
+        rs_stage.resize(nt);
+    for (int ln = 0; ln < nt; ++ln)
+    {
+        if (!resampled[ln])
+            continue;
+        RsStage &rs = rs_stage[ln];
+        if ((size_t)length_in[ln] > rs.cap)
+        {
+            for (float **p : {&rs.in, &rs.out[0], &rs.out[1], &rs.out[2], &rs.out[3]})
+                if (*p)
+                {
+                    allocs.erase(std::find(allocs.begin(), allocs.end(), (void *)*p));
+                    (void)hipFree(*p);
+                    *p = nullptr;
+                }
+            rs.cap = 0;
+            const size_t cap = (size_t)length_in[ln] + (size_t)length_in[ln] / 8;
+            for (float **p : {&rs.in, &rs.out[0], &rs.out[1], &rs.out[2], &rs.out[3]})
+                if (int rc = dalloc(p, 2 * cap, false))
+                    return rc;
+            rs.cap = cap;
+        }
+        UMX_HIP_CHECK(hipMemcpy(rs.in, audio_host[ln], sizeof(float) * 2 * (size_t)length_in[ln], hipMemcpyHostToDevice));
+        const float *src = rs.in;
+        float *dst = trk[ln].in + 2 * (size_t)lead[ln];
+        UMX_HIP_CHECK(launch_resample(rs_fwd[ln], rs_fwd_taps[ln], 1, &src, length_in[ln], &dst, length[ln], nullptr));
+    }
     UMX_HIP_CHECK(hipDeviceSynchronize());
     // The track goes up segment by segment (round 6): a call needs the samples up to the end of its last segment, and the rest of a
     // pageable upload (14 GB/s: 15 ms for ten minutes of stereo) runs while the device is busy with the segments before it -- the
     // slots' streams do not wait for the null stream, and launches are queued ahead of the copy.
     long long uploaded[LSTMB_MAX_TRACKS] = {}; // host samples of each track already on the device
+    for (int ln = 0; ln < nt; ++ln)
+        if (resampled[ln])
+            uploaded[ln] = length[ln];
     auto upload_until = [&](int ti, long long padded_end) -> hipError_t { // samples of the padded signal below `padded_end` must be there
         const long long want = std::min<long long>(length[ti], padded_end - lead[ti]);
         if (want <= uploaded[ti])
@@ -240,10 +297,23 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
         if (progress)
             progress(done, progress_user);
     }
+    // a resampled track's four stems: n44 frames from the shift on, back to the caller's rate in one launch behind the last
+    // segment's overlap-add (they are downloaded whole below, not region by region)
     hipError_t cerr = hipSuccess;
+    const hipStream_t last_st = slot[last_slot].stream;
+    for (int ln = 0; ln < nt && cerr == hipSuccess; ++ln)
+        if (resampled[ln])
+        {
+            const float *src[4];
+            for (int t = 0; t < 4; ++t)
+                src[t] = trk[ln].out[t] + 2 * (size_t)lead[ln];
+            cerr = launch_resample(rs_back[ln], rs_back_taps[ln], 4, src, length[ln], rs_stage[ln].out, length_in[ln], last_st);
+        }
     for (const Region &rg : regions) // umx.cpp:136-147: drop the shift
     {
         const int ln = rg.lane;
+        if (resampled[ln])
+            continue;
         const long long lo = std::max<long long>(rg.start, lead[ln]),
                         hi = std::min<long long>((long long)rg.start + rg.count, (long long)lead[ln] + length[ln]);
         if (hi <= lo)
@@ -255,6 +325,16 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
                              sizeof(float) * 2 * (size_t)(hi - lo), hipMemcpyDeviceToHost);
     }
     cleanup();
+    bool synced = false;
+    for (int ln = 0; ln < nt && cerr == hipSuccess; ++ln)
+        if (resampled[ln])
+        {
+            if (!synced)
+                cerr = hipStreamSynchronize(last_st);
+            synced = true;
+            for (int t = 0; t < 4 && cerr == hipSuccess; ++t)
+                cerr = hipMemcpy(out_host[4 * ln + t], rs_stage[ln].out[t], sizeof(float) * 2 * (size_t)length_in[ln], hipMemcpyDeviceToHost);
+        }
     if (cerr != hipSuccess)
     {
         set_error(hipGetErrorString(cerr));
@@ -263,5 +343,28 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
     UMX_HIP_CHECK(hipGetLastError());
     if (int rc = umx_hip_sync(this)) // surfaces a persistent-kernel timeout
         return rc;
+    return UMX_OK;
+}
+
+// the tap table of a rate pair, built on the host in double and kept in HBM for the context's lifetime
+int umx_hip_ctx::resample_plan(int rate_in, int rate_out, ResampleGeom &g, const float **taps_dev)
+{
+    if (!resample_geom(rate_in, rate_out, g))
+    {
+        set_error("resample: sample rates must be 8000 .. 192000 Hz");
+        return UMX_ERR_ARG;
+    }
+    auto it = rs_taps.find({rate_in, rate_out});
+    if (it == rs_taps.end())
+    {
+        UMX_HIP_CHECK(hipSetDevice(device));
+        std::vector<float> taps;
+        resample_taps(g, taps);
+        float *d = nullptr;
+        if (int rc = upload(&d, taps))
+            return rc;
+        it = rs_taps.emplace(std::make_pair(rate_in, rate_out), d).first;
+    }
+    *taps_dev = it->second;
     return UMX_OK;
 }

@@ -3,7 +3,8 @@
 // bound by hand-off latency, not arithmetic, so the engine runs several tracks as track lanes of ONE context
 // (umx_hip_create_tracks / umx_hip_separate_tracks): per file the same shift_inference -> split_inference, the same
 // four stems, written to <out dir>/<wav stem>/target_{0..3}.wav.  More than 16 files are taken 16 at a time.
-// Environment: UMX_DEVICE, UMX_NO_WIENER, UMX_WIENER_ITERS, UMX_SHIFT_OFFSET (as umx-cli).
+// Environment: UMX_DEVICE, UMX_NO_WIENER, UMX_WIENER_ITERS, UMX_SHIFT_OFFSET, UMX_RESAMPLE (as umx-cli: files of any rate of
+// 8 .. 192 kHz, mixed rates in one pass through umx_hip_separate_tracks_rate, stems written at each file's rate).
 #include "../../include/umx_host.h"
 
 #include <chrono>
@@ -61,6 +62,7 @@ int main(int argc, const char **argv)
     const unsigned flags = (env_int("UMX_NO_WIENER", 0) ? UMX_FLAG_NO_WIENER : 0) | (wiener_iters > 1 ? UMX_FLAG_WIENER_ITERS(wiener_iters) : 0u);
     double audio_secs = 0, wall = 0;
     const int first_rand_shift = UMX_REFERENCE_SHIFT; // glibc's first unseeded rand() % 22050 (not rand() here: umx_hip.h)
+    const bool resample = env_int("UMX_RESAMPLE", 0) != 0;
     std::set<std::string> used_names; // output directories are named after the file's stem: a/x.wav and b/x.wav must not collide
     for (int f0 = 0; f0 < nfiles; f0 += lanes)
     {
@@ -73,16 +75,18 @@ int main(int argc, const char **argv)
         std::vector<std::vector<float>> stems(4 * nb);
         std::vector<float *> out(4 * nb);
         std::vector<const float *> in(nb);
+        std::vector<int> rate(nb, UMX_SAMPLE_RATE);
         for (int i = 0; i < nb; ++i)
         {
             int ch = 0;
-            if (umx_wav_load(argv[3 + f0 + i], &audio[i], &n[i], &ch, err)) // umx.cpp:56
+            if (resample ? umx_wav_load_rate(argv[3 + f0 + i], &audio[i], &n[i], &ch, &rate[i], err)
+                         : umx_wav_load(argv[3 + f0 + i], &audio[i], &n[i], &ch, err)) // umx.cpp:56
             {
                 fprintf(stderr, "%s: %s\n", argv[3 + f0 + i], err);
                 return 1;
             }
             in[i] = audio[i];
-            audio_secs += n[i] / 44100.0;
+            audio_secs += n[i] / (double)rate[i];
             for (int t = 0; t < 4; ++t)
             {
                 stems[4 * i + t].resize((size_t)2 * n[i]);
@@ -90,7 +94,8 @@ int main(int argc, const char **argv)
             }
         }
         const auto t0 = std::chrono::steady_clock::now();
-        if (umx_hip_separate_tracks(ctx, nb, in.data(), n.data(), shift.data(), out.data(), flags, nullptr, nullptr))
+        if (resample ? umx_hip_separate_tracks_rate(ctx, nb, in.data(), n.data(), rate.data(), shift.data(), out.data(), flags, nullptr, nullptr)
+                     : umx_hip_separate_tracks(ctx, nb, in.data(), n.data(), shift.data(), out.data(), flags, nullptr, nullptr))
         {
             fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
             return 1;
@@ -107,7 +112,8 @@ int main(int argc, const char **argv)
             for (int t = 0; t < 4; ++t) // umx.cpp:75-96
             {
                 const std::string p = (dir / ("target_" + std::to_string(t) + ".wav")).string();
-                if (umx_wav_write_f32(p.c_str(), out[4 * i + t], n[i], err))
+                if (resample ? umx_wav_write_f32_rate(p.c_str(), out[4 * i + t], n[i], rate[i], err)
+                             : umx_wav_write_f32(p.c_str(), out[4 * i + t], n[i], err))
                 {
                     fprintf(stderr, "%s\n", err);
                     return 1;

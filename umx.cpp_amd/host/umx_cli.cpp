@@ -6,6 +6,8 @@
 // like the reference.  Extra knobs come from the environment only, so the 3 positionals stay:
 //   UMX_DEVICE=<n>   UMX_NO_WIENER=1   UMX_WIENER_ITERS=<1..15>   UMX_SHIFT_OFFSET=<n>   UMX_LSTM_STEPWISE=1   UMX_CLI_PER_SEGMENT=1
 //   UMX_WEIGHTS_RESIDENT=expanded   UMX_GEMM=f32
+//   UMX_RESAMPLE=1   any rate of 8 .. 192 kHz: resampled to 44.1 kHz and back on the device (umx_hip_shift_inference_rate,
+//                    DESIGN 13); the stems are written at the input's rate and length
 #include "../../include/umx_host.h"
 
 #include <chrono>
@@ -51,13 +53,16 @@ int main(int argc, const char **argv)
     printf("umx-cli (MI355X / gfx950) main driver program\n");
 
     float *audio = nullptr;
-    int n = 0, ch = 0;
-    if (umx_wav_load(wav_file.c_str(), &audio, &n, &ch, err)) // umx.cpp:56
+    int n = 0, ch = 0, rate = UMX_SAMPLE_RATE;
+    const bool resample = env_int("UMX_RESAMPLE", 0) != 0;
+    if (resample ? umx_wav_load_rate(wav_file.c_str(), &audio, &n, &ch, &rate, err) : umx_wav_load(wav_file.c_str(), &audio, &n, &ch, err)) // umx.cpp:56
     {
         fprintf(stderr, "%s\n", err);
         return 1;
     }
-    printf("Input Samples: %d\nLength in seconds: %f\nNumber of channels: %d\n", n * ch, n / 44100.0, ch);
+    printf("Input Samples: %d\nLength in seconds: %f\nNumber of channels: %d\n", n * ch, n / (double)rate, ch);
+    if (resample && rate != UMX_SAMPLE_RATE)
+        printf("Sample rate: %d Hz (resampled to 44100 Hz and back on the device)\n", rate);
 
     const auto t0 = std::chrono::steady_clock::now();
     umx_model *model = nullptr;
@@ -102,6 +107,11 @@ int main(int argc, const char **argv)
     }
     const auto t2 = std::chrono::steady_clock::now();
     const bool per_segment = env_int("UMX_CLI_PER_SEGMENT", 0) != 0;
+    if (per_segment && rate != UMX_SAMPLE_RATE)
+    {
+        fprintf(stderr, "UMX_CLI_PER_SEGMENT=1 takes 44100 Hz audio only (this file is %d Hz): unset it to resample on the device\n", rate);
+        return 1;
+    }
     if (per_segment)
     {
         if (umx_shift_inference(&be, audio, n, UMX_SEGMENT_SAMPLES, env_int("UMX_SHIFT_OFFSET", -1), out,
@@ -111,16 +121,17 @@ int main(int argc, const char **argv)
             return 1;
         }
     }
-    else if (umx_hip_shift_inference(ctx, audio, n, env_int("UMX_SHIFT_OFFSET", -1), out, hb.flags, print_progress,
-                                     nullptr)) // umx.cpp:72-73
+    else if (resample ? umx_hip_shift_inference_rate(ctx, audio, n, rate, env_int("UMX_SHIFT_OFFSET", -1), out, hb.flags, print_progress, nullptr)
+                      : umx_hip_shift_inference(ctx, audio, n, env_int("UMX_SHIFT_OFFSET", -1), out, hb.flags, print_progress,
+                                                nullptr)) // umx.cpp:72-73
     {
         fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
         return 1;
     }
     const auto t3 = std::chrono::steady_clock::now();
     const double secs = std::chrono::duration<double>(t3 - t2).count();
-    printf("Separated %.2f s of audio in %.3f s (%.1fx realtime, host buffers in/out, %s)\n", n / 44100.0, secs,
-           n / 44100.0 / secs, per_segment ? "one segment at a time" : "track resident in HBM");
+    printf("Separated %.2f s of audio in %.3f s (%.1fx realtime, host buffers in/out, %s)\n", n / (double)rate, secs,
+           n / (double)rate / secs, per_segment ? "one segment at a time" : "track resident in HBM");
 
     std::error_code ec;
     std::filesystem::create_directories(out_dir, ec); // umx.cpp:84-86
@@ -128,7 +139,7 @@ int main(int argc, const char **argv)
     {
         const std::string p = (std::filesystem::path(out_dir) / ("target_" + std::to_string(t) + ".wav")).string();
         printf("Writing wav file %s\n", p.c_str());
-        if (umx_wav_write_f32(p.c_str(), out[t], n, err))
+        if (resample ? umx_wav_write_f32_rate(p.c_str(), out[t], n, rate, err) : umx_wav_write_f32(p.c_str(), out[t], n, err))
         {
             fprintf(stderr, "%s\n", err);
             return 1;

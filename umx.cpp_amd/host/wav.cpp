@@ -1,7 +1,8 @@
 // wav.cpp -- minimal RIFF/WAVE reader + float32 writer (host side of include/umx_host.h).
 // Stands in for libnyquist as used by the reference's load_audio / write_audio_file
 // (src/dsp.cpp:18-101): decode to float, mono duplicated to both channels (dsp.cpp:52-60), only
-// 44.1 kHz (dsp.cpp:27-33) and 1 or 2 channels (dsp.cpp:39-44); write 2-channel IEEE-float WAV
+// 44.1 kHz (dsp.cpp:27-33; umx_wav_load_rate: any rate of 8 .. 192 kHz, reported, for the device resampler of DESIGN 13)
+// and 1 or 2 channels (dsp.cpp:39-44); write 2-channel IEEE-float WAV
 // (dsp.cpp:97-99 PCM_FLT).  libnyquist is an un-vendored submodule in the reference
 // (.gitmodules:4-6), so its integer->float scaling is restated from its published macros
 // (int16 / 32767.f, int24 / 8388608.f, int32 / 2147483648.f) and is not pinned by a test.
@@ -24,11 +25,12 @@ uint32_t u32(const unsigned char *p) { return p[0] | (p[1] << 8) | (p[2] << 16) 
 uint16_t u16(const unsigned char *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 } // namespace
 
-extern "C" int umx_wav_load(const char *path, float **audio_out, int *n_frames_out, int *channels_in_file, char *err)
+// any_rate: report the file's rate in *rate_out (8000 .. 192000 Hz) instead of refusing all but 44100
+static int wav_load(const char *path, float **audio_out, int *n_frames_out, int *channels_in_file, bool any_rate, int *rate_out, char *err)
 {
     if (!path || !audio_out || !n_frames_out)
     {
-        seterr(err, "umx_wav_load: null argument");
+        seterr(err, any_rate ? "umx_wav_load_rate: null argument" : "umx_wav_load: null argument");
         return UMX_ERR_ARG;
     }
     *audio_out = nullptr;
@@ -86,7 +88,17 @@ extern "C" int umx_wav_load(const char *path, float **audio_out, int *n_frames_o
     }
     if (channels_in_file)
         *channels_in_file = channels;
-    if (rate != UMX_SAMPLE_RATE) // dsp.cpp:27-33
+    if (any_rate)
+    {
+        if (rate < UMX_RESAMPLE_MIN_RATE || rate > UMX_RESAMPLE_MAX_RATE)
+        {
+            seterr(err, "sample rate " + std::to_string(rate) + " Hz is outside 8000 .. 192000 Hz");
+            return UMX_HOST_ERR_AUDIO;
+        }
+        if (rate_out)
+            *rate_out = rate;
+    }
+    else if (rate != UMX_SAMPLE_RATE) // dsp.cpp:27-33
     {
         seterr(err, "[ERROR] umx.cpp only supports the following sample rate (Hz): 44100");
         return UMX_HOST_ERR_AUDIO;
@@ -144,11 +156,26 @@ extern "C" int umx_wav_load(const char *path, float **audio_out, int *n_frames_o
     return UMX_OK;
 }
 
+extern "C" int umx_wav_load(const char *path, float **audio_out, int *n_frames_out, int *channels_in_file, char *err)
+{
+    return wav_load(path, audio_out, n_frames_out, channels_in_file, false, nullptr, err);
+}
+
+extern "C" int umx_wav_load_rate(const char *path, float **audio_out, int *n_frames_out, int *channels_in_file, int *rate_out, char *err)
+{
+    return wav_load(path, audio_out, n_frames_out, channels_in_file, true, rate_out, err);
+}
+
 extern "C" void umx_wav_free(float *audio) { free(audio); }
 
 extern "C" int umx_wav_write_f32(const char *path, const float *audio, int n_frames, char *err)
 {
-    if (!path || !audio || n_frames < 0)
+    return umx_wav_write_f32_rate(path, audio, n_frames, UMX_SAMPLE_RATE, err);
+}
+
+extern "C" int umx_wav_write_f32_rate(const char *path, const float *audio, int n_frames, int rate, char *err)
+{
+    if (!path || !audio || n_frames < 0 || rate < 1)
     {
         seterr(err, "umx_wav_write_f32: bad argument");
         return UMX_ERR_ARG;
@@ -169,8 +196,8 @@ extern "C" int umx_wav_write_f32(const char *path, const float *audio, int n_fra
     p32(16, 16);
     p16(20, 3); // WAVE_FORMAT_IEEE_FLOAT
     p16(22, 2);
-    p32(24, UMX_SAMPLE_RATE);
-    p32(28, UMX_SAMPLE_RATE * 2 * 4);
+    p32(24, (uint32_t)rate);
+    p32(28, (uint32_t)rate * 2 * 4);
     p16(32, 8);
     p16(34, 32);
     memcpy(h + 36, "data", 4);
