@@ -45,6 +45,14 @@ extern "C" {
 #define UMX_FLAG_WIENER_ITERS_MASK 0xF0000u
 #define UMX_FLAG_WIENER_ITERS(n) ((((unsigned)(n)) & 0xFu) << 16)
 #define UMX_FLAG_SKIP_TARGET(t) (0x100 << (t)) /* BASELINE config 1 (vocals only = skip 0,1,2) */
+/* Residual source: Open-Unmix's Separator(targets=[...], residual=True) -- no analogue in the reference, whose umx_inference
+ * always runs all four models.  Together with UMX_FLAG_SKIP_TARGET: the LOWEST skipped target's slot r (umx_hip_residual_slot) carries one more
+ * source, "everything else": its mask plane is rho = 1.0f - ((m_j1 + m_j2) + m_j3) over the active targets j1 < j2 < j3 (fp32, as many terms
+ * as there are; may be negative), so its magnitude is rho |X| and its first estimate X - sum_j y_j (Open-Unmix's `mix_stft - sum of targets`);
+ * from there on it is a source like any other in the EM, and out[4 * lane + r] receives its stem.  The other skipped targets stay silent.
+ * Needs at least one skipped and one active target, else UMX_ERR_ARG (four targets + residual would be five sources: not supported).
+ * "vocals + accompaniment" = UMX_FLAG_SKIP_TARGET(0) | (1) | (2) | UMX_FLAG_RESIDUAL: out[3] vocals, out[0] accompaniment, one network's cost. */
+#define UMX_FLAG_RESIDUAL 0x8000
 #define UMX_FLAG_LSTM_STEPWISE 0x10 /* one launch per timestep instead of the persistent kernel */
 #define UMX_FLAG_DEBUG_TAPS 0x20    /* keep what only the taps read: the filtered spectrograms for umx_hip_read_tap("y") (the fused kernel does not
                                      * write them otherwise) and, in track-batched contexts, the fp32 rows of the recurrence's layers ("lstm",
@@ -197,6 +205,9 @@ int umx_hip_infer_batch_async(umx_hip_ctx *ctx, int n_tracks, const float *const
                               float *const *out_host, unsigned flags);
 int umx_hip_infer_batch_device(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_dev, const int *n,
                                float *const *out_dev, unsigned flags);
+/* UMX_FLAG_RESIDUAL: the slot that carries the residual source = the lowest skipped target; -1 when the flag is not set, -2 for a
+ * combination the entry points refuse (no target skipped, or all four).  Host arithmetic. */
+int umx_hip_residual_slot(unsigned flags);
 /* Waits for everything queued.  A persistent LSTM launch needs its whole grid co-resident; inside a process that is
  * guaranteed (launches of all contexts on a device pass one admission gate), but another PROCESS on the same GPU can
  * still occupy the CUs, in which case the launch gives up after a bounded spin instead of hanging.  umx_hip_sync then
@@ -306,9 +317,13 @@ int umx_hip_segment_end(umx_hip_ctx *ctx, float *const out_host[4]);
  *                                  (inference.cpp:175-183), which _finish_device forms from its own spectrogram: read it
  *                                  after _masks_device, or write a peer's result there before _finish_device
  *   umx_hip_segment_finish_device  Wiener EM (or the mixture phase), inverse STFT, overlap-add from ALL four magnitude
- *                                  buffers as they are (a skipped target is NOT zero-filled here) into 4 device buffers
- * umx_hip_segment_end_device == _masks_device, zero-fill of the skipped targets, _finish_device. */
+ *                                  buffers as they are (a skipped target is NOT zero-filled here, and UMX_FLAG_RESIDUAL writes nothing
+ *                                  here) into 4 device buffers
+ *   umx_hip_segment_residual_device  UMX_FLAG_RESIDUAL of the open segment: writes the residual slot's mask planes from the active
+ *                                  targets' (after _masks_device, before _finish_device); UMX_ERR_ARG without the flag
+ * umx_hip_segment_end_device == _masks_device, zero-fill of the skipped targets (the residual slot: _residual_device), _finish_device. */
 int umx_hip_segment_masks_device(umx_hip_ctx *ctx);
+int umx_hip_segment_residual_device(umx_hip_ctx *ctx);
 float *umx_hip_target_mag_device(umx_hip_ctx *ctx, int target, size_t *floats);
 int umx_hip_segment_finish_device(umx_hip_ctx *ctx, float *const out_dev[4]);
 int umx_hip_segment_discard(umx_hip_ctx *ctx); /* closes the phased segment where it stands (a rank that only contributes magnitudes) */

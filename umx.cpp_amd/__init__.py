@@ -29,6 +29,7 @@ FLAG_LSTM_FORCE_SAFE = 0x40
 FLAG_LSTM_PROFILE = 0x80
 FLAG_PRECISE_ACT = 0x1000
 FLAG_DEBUG_LSTM_ABORT = 0x2000
+FLAG_RESIDUAL = 0x8000  # the lowest skipped target's slot carries "everything else" (Open-Unmix's residual=True)
 FLAG_RESET_SEGMENTS = 0x4000  # whole-track calls: every segment from a zero LSTM state, segments as lanes of one call (declared deviation)
 
 
@@ -37,6 +38,32 @@ def FLAG_SKIP_TARGET(t):
 
 
 FLAG_WIENER_ITERS_MASK = 0xF0000
+TARGET_NAMES = ("bass", "drums", "other", "vocals")  # convert-umx-pth-to-ggml.py:104
+
+
+def flags_for_targets(names, residual=False):
+    """The flag word of Open-Unmix's Separator(targets=names, residual=residual): every target not named is skipped; with
+    `residual` the lowest skipped slot (residual_slot) carries the rest of the mix.  ValueError for what the engine refuses."""
+    names = list(names)
+    for nm in names:
+        if nm not in TARGET_NAMES:
+            raise ValueError(f"unknown target {nm!r}: one of {', '.join(TARGET_NAMES)}")
+    if not names:
+        raise ValueError("no targets")
+    flags = 0
+    for t, nm in enumerate(TARGET_NAMES):
+        if nm not in names:
+            flags |= FLAG_SKIP_TARGET(t)
+    if residual:
+        flags |= FLAG_RESIDUAL
+        if residual_slot(flags) < 0:
+            raise ValueError("a residual needs one to three of the four targets: it takes the slot of a target that does not run")
+    return flags
+
+
+def residual_slot(flags):
+    """umx_hip_residual_slot: the slot that carries the residual source; -1 without FLAG_RESIDUAL, -2 for a refused combination."""
+    return int(hip_lib().umx_hip_residual_slot(int(flags)))
 
 
 def FLAG_WIENER_ITERS(n):
@@ -148,6 +175,8 @@ def hip_lib():
     lib.umx_hip_segment_begin_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint]
     lib.umx_hip_segment_end_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     lib.umx_hip_segment_masks_device.argtypes = [C.c_void_p]
+    lib.umx_hip_segment_residual_device.argtypes = [C.c_void_p]
+    lib.umx_hip_residual_slot.argtypes = [C.c_uint]
     lib.umx_hip_segment_finish_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     lib.umx_hip_weight_stems_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
     lib.umx_hip_track_accumulate_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p), C.c_int,
@@ -198,7 +227,7 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_split_inference", "umx_hip_shift_inference", "umx_hip_debug_lds_guard", "umx_hip_debug_f16_bits",
                "umx_hip_segment_masks_device", "umx_hip_target_mag_device", "umx_hip_segment_finish_device", "umx_hip_gate_reserve", "umx_hip_segment_discard", "umx_hip_pipeline_depth",
                "umx_hip_resampled_length", "umx_hip_resample_device", "umx_hip_shift_inference_rate", "umx_hip_separate_tracks_rate",
-               "umx_hip_debug_resample_taps"]
+               "umx_hip_debug_resample_taps", "umx_hip_residual_slot", "umx_hip_segment_residual_device"]
 
 
 def resampled_length(n, rate_in, rate_out):
@@ -375,6 +404,9 @@ class Engine:
 
     def segment_masks_device(self):
         self._check(self.lib.umx_hip_segment_masks_device(self.h))
+
+    def segment_residual_device(self):
+        self._check(self.lib.umx_hip_segment_residual_device(self.h))
 
     def segment_finish_device(self, out_ptrs):
         self._check(self.lib.umx_hip_segment_finish_device(self.h, (C.c_void_p * 4)(*out_ptrs)))

@@ -37,6 +37,7 @@
 #include "wiener_kernels.h"
 #include "wiener_istft.h"
 #include "wiener_em.h"
+#include "residual_mask.h"
 
 using namespace umx;
 
@@ -609,7 +610,19 @@ struct umx_hip_ctx
     int stage_finish(Slot &sl, hipStream_t st, int nb, const float *const *audio_dev, float *const *out, const int *n, unsigned flags,
                      bool zero_skipped);
     int phase_masks();
+    int phase_residual();
     int phase_finish_device(float *const out_dev_[4]);
+    // UMX_FLAG_RESIDUAL: the one check of the flag combination every entry point that takes flags goes through
+    int check_flags(unsigned flags)
+    {
+        if (residual_slot_of(flags) != -2)
+            return UMX_OK;
+        set_error("UMX_FLAG_RESIDUAL needs at least one skipped target (UMX_FLAG_SKIP_TARGET: its slot carries the residual; four targets "
+                  "plus a residual would be five sources) and at least one active target");
+        return UMX_ERR_ARG;
+    }
+    // rho of the residual slot from the active targets' masks, all lanes of the call in one launch (residual_mask.h)
+    int stage_residual(Slot &sl, hipStream_t st, int nb, const float *const *audio_dev, unsigned flags);
     static void active_list(unsigned flags, int *active, int &nact)
     {
         nact = 0;

@@ -378,6 +378,8 @@ int umx_hip_segment_begin_device(umx_hip_ctx *ctx, const float *audio_dev, int n
 }
 int umx_hip_segment_end_device(umx_hip_ctx *ctx, float *const out_dev[4]) { return ctx ? ctx->phase_end_device(out_dev) : UMX_ERR_ARG; }
 int umx_hip_segment_masks_device(umx_hip_ctx *ctx) { return ctx ? ctx->phase_masks() : UMX_ERR_ARG; }
+int umx_hip_segment_residual_device(umx_hip_ctx *ctx) { return ctx ? ctx->phase_residual() : UMX_ERR_ARG; }
+int umx_hip_residual_slot(unsigned flags) { return residual_slot_of(flags); }
 int umx_hip_segment_discard(umx_hip_ctx *ctx)
 {
     if (!ctx)
@@ -590,6 +592,8 @@ int umx_hip_infer_batch_async(umx_hip_ctx *ctx, int n_tracks, const float *const
             ctx->set_error("infer: bad arguments");
         return UMX_ERR_ARG;
     }
+    if (int rc = ctx->check_flags(flags)) // (before anything is uploaded)
+        return rc;
     const int si = ctx->next_slot();
     if (int rc = ctx->ensure_staging())
         return rc;

@@ -17,6 +17,8 @@ int umx_hip_ctx::phase_begin(const float *audio_host, int n, unsigned flags)
         set_error("segment_begin: a phased segment is already open");
         return UMX_ERR_ARG;
     }
+    if (int rc = check_flags(flags))
+        return rc;
     UMX_HIP_CHECK(hipSetDevice(device));
     if (int rc = sync_all())
         return rc;
@@ -49,6 +51,8 @@ int umx_hip_ctx::phase_begin_device(const float *audio_dev, int n, unsigned flag
         set_error("segment_begin: a phased segment is already open");
         return UMX_ERR_ARG;
     }
+    if (int rc = check_flags(flags))
+        return rc;
     UMX_HIP_CHECK(hipSetDevice(device));
     Slot &sl = slot[0];
     int active[4], nact;
@@ -102,6 +106,20 @@ int umx_hip_ctx::phase_masks()
         return rc;
     ph_next = 4;
     return UMX_OK;
+}
+
+// UMX_FLAG_RESIDUAL for a driver that zero-fills the skipped targets itself between phase_masks and phase_finish_device (host/mgpu.cpp):
+// the residual slot's planes, as stage_finish writes them for the entry points that zero-fill
+int umx_hip_ctx::phase_residual()
+{
+    if (ph_next != 4 || residual_slot_of(ph_flags) < 0)
+    {
+        set_error("segment_residual: umx_hip_segment_masks_device must have run on a segment begun with UMX_FLAG_RESIDUAL");
+        return UMX_ERR_ARG;
+    }
+    UMX_HIP_CHECK(hipSetDevice(device));
+    const float *ain = ph_audio ? ph_audio : audio_in;
+    return stage_residual(slot[0], slot[0].stream, 1, &ain, ph_flags);
 }
 
 // Wiener + inverse STFT from the magnitudes of all four targets, wherever they came from

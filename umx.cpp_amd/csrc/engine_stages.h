@@ -276,16 +276,47 @@ int umx_hip_ctx::stage_masks(Slot &sl, hipStream_t st, int nb, const float *cons
     return UMX_OK;
 }
 
+int umx_hip_ctx::stage_residual(Slot &sl, hipStream_t st, int nb, const float *const *audio_dev, unsigned flags)
+{
+    const int res = residual_slot_of(flags);
+    int active[4], nact;
+    active_list(flags, active, nact);
+    if (res < 0 || nact < 1 || nact > 3)
+    {
+        set_error("UMX_FLAG_RESIDUAL: no residual slot in these flags");
+        return UMX_ERR_ARG;
+    }
+    const LaneSet lanes = lane_set(nb, audio_dev);
+    Lane &L0 = sl.lane[0];
+    ResidualSrc src = {};
+    for (int i = 0; i < nact; ++i)
+        src.m[i] = L0.ta[active[i]].mag;
+    const dim3 grid((2 * T + RM_ROWS - 1) / RM_ROWS, 1, lanes.count), block(256);
+    if (nact == 1)
+        hipLaunchKernelGGL(residual_mask_kernel<1>, grid, block, 0, st, src, L0.ta[res].mag, T, lanes, lane_strides());
+    else if (nact == 2)
+        hipLaunchKernelGGL(residual_mask_kernel<2>, grid, block, 0, st, src, L0.ta[res].mag, T, lanes, lane_strides());
+    else
+        hipLaunchKernelGGL(residual_mask_kernel<3>, grid, block, 0, st, src, L0.ta[res].mag, T, lanes, lane_strides());
+    return UMX_OK;
+}
+
 int umx_hip_ctx::stage_finish(Slot &sl, hipStream_t st, int nb, const float *const *audio_dev, float *const *out, const int *n,
                               unsigned flags, bool zero_skipped)
 {
     const bool dbg = flags & UMX_FLAG_DEBUG_TAPS;
     if (zero_skipped)
+    {
+        const int res = residual_slot_of(flags); // < 0: none
         for (int ln = 0; ln < nb; ++ln)
             if (audio_dev[ln])
                 for (int tg = 0; tg < 4; ++tg) // a skipped target contributes an all-zero magnitude
-                    if (flags & UMX_FLAG_SKIP_TARGET(tg))
+                    if ((flags & UMX_FLAG_SKIP_TARGET(tg)) && tg != res)
                         UMX_HIP_CHECK(hipMemsetAsync(sl.lane[ln].ta[tg].mag, 0, sizeof(float) * 2 * T * MAGP, st));
+        if (res >= 0) // ... but the residual slot: the mixture minus the active targets
+            if (int rc = stage_residual(sl, st, nb, audio_dev, flags))
+                return rc;
+    }
     stage_range(ST_WIENER);
     UMX_HIP_CHECK(hipEventRecord(sl.ev[ST_WIENER], st));
     const int bt = (NBINS + 255) / 256;
@@ -432,6 +463,8 @@ int umx_hip_ctx::infer_batch(int nb, const float *const *audio_dev, const int *n
         set_error("infer: need 1 <= n_tracks <= the context's track count and non-null argument arrays");
         return UMX_ERR_ARG;
     }
+    if (int rc = check_flags(flags))
+        return rc;
     unsigned long long lane_mask = 0;
     for (int ln = 0; ln < nb; ++ln)
     {

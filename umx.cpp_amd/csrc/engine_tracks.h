@@ -43,6 +43,8 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
         set_error("tracks: need 1 <= n_tracks <= the context's track count and non-null argument arrays");
         return UMX_ERR_ARG;
     }
+    if (int rc = check_flags(flags))
+        return rc;
     for (int ln = 0; ln < nt; ++ln)
         if (!audio_host[ln] || length_in[ln] < 1 || shift_offset[ln] >= UMX_MAX_SHIFT || !out_host[4 * ln] || !out_host[4 * ln + 1] ||
             !out_host[4 * ln + 2] || !out_host[4 * ln + 3])

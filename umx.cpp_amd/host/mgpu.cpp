@@ -275,6 +275,7 @@ int separate_once(umx_mgpu *m, const float *audio_host, int length, int shift_of
     const umx_plan::Plan pl = umx_plan::make_plan(world, m->by_target);
     const int N = umx_hip_segment_samples(ctx), Hl = umx_hip_hidden(ctx) / 2;
     const int my_stage = pl.stage(rank);
+    const int res_slot = umx_hip_residual_slot(flags); // < 0: no residual source
     // shift_inference (umx.cpp:99-150): the track sits `lead` samples into a zero buffer of L2 samples
     const int lead = shift_offset < 0 ? 0 : shift_offset;
     const long long L2ll = shift_offset < 0 ? (long long)length : (long long)length + std::max(UMX_MAX_SHIFT - shift_offset, shift_offset);
@@ -453,8 +454,10 @@ int separate_once(umx_mgpu *m, const float *audio_host, int length, int shift_of
             MG_HIP(hipStreamWaitEvent(st, m->mags_sent, 0));
         MG_UMX(umx_hip_segment_masks_device(ctx));
         for (int k = 0; k < n_mine; ++k) // a target the CALLER skipped (BASELINE config 1) is silence, as in umx_hip_infer_segment
-            if (flags & UMX_FLAG_SKIP_TARGET(mine_t[k]))
+            if ((flags & UMX_FLAG_SKIP_TARGET(mine_t[k])) && mine_t[k] != res_slot)
                 MG_HIP(hipMemsetAsync(mag[mine_t[k]], 0, sizeof(float) * mag_floats, st));
+        if (res_slot >= 0) // ... but the residual slot (UMX_FLAG_RESIDUAL, by-segment mode only: this rank has every mask)
+            MG_UMX(umx_hip_segment_residual_device(ctx));
         const int wr = pl.wiener_rank(lc.seg);
         if (pl.G > 1 || loop)
         {
@@ -630,6 +633,12 @@ extern "C" int umx_mgpu_separate_track(umx_mgpu *m, const float *audio_host, int
 {
     if (!m || !audio_host || length < 1 || shift_offset >= UMX_MAX_SHIFT || (m->rank == 0 && !out_host))
         MG_FAIL(UMX_ERR_ARG, "umx_mgpu_separate_track: bad argument");
+    // the residual is the mixture minus the ACTIVE targets of the call; in by-target mode a rank's own skip flags (the other groups'
+    // targets) would be taken for the caller's, and no rank holds every mask before the filter
+    if ((flags & UMX_FLAG_RESIDUAL) && m->by_target)
+        MG_FAIL(UMX_ERR_ARG, "umx_mgpu_separate_track: UMX_FLAG_RESIDUAL is not supported in by-target mode (use by-segment mode)");
+    if (umx_hip_residual_slot(flags) == -2)
+        MG_FAIL(UMX_ERR_ARG, "umx_mgpu_separate_track: UMX_FLAG_RESIDUAL needs at least one skipped and one active target");
     if (m->dead)
         MG_FAIL(UMX_ERR_HIP, "umx_mgpu_separate_track: the communicators were aborted after an earlier error");
     m->stats[4] = 0;

@@ -4,8 +4,10 @@
 // (umx_hip_create_tracks / umx_hip_separate_tracks): per file the same shift_inference -> split_inference, the same
 // four stems, written to <out dir>/<wav stem>/target_{0..3}.wav.  More than 16 files are taken 16 at a time.
 // Environment: UMX_DEVICE, UMX_NO_WIENER, UMX_WIENER_ITERS, UMX_SHIFT_OFFSET, UMX_RESAMPLE (as umx-cli: files of any rate of
-// 8 .. 192 kHz, mixed rates in one pass through umx_hip_separate_tracks_rate, stems written at each file's rate).
+// 8 .. 192 kHz, mixed rates in one pass through umx_hip_separate_tracks_rate, stems written at each file's rate), UMX_TARGETS and
+// UMX_RESIDUAL (as umx-cli: target_<t>.wav of the chosen targets and residual.wav per file; host/targets_env.h).
 #include "../../include/umx_host.h"
+#include "targets_env.h"
 
 #include <chrono>
 #include <cstdio>
@@ -32,6 +34,9 @@ int main(int argc, const char **argv)
     const int nfiles = argc - 3;
     int lanes = std::min(nfiles, UMX_MAX_TRACKS);
     char err[UMX_ERRLEN] = "";
+    umx_target_choice choice;
+    if (!umx_targets_from_env(choice))
+        return 1;
     umx_model *model = nullptr;
     if (umx_model_load(model_file.c_str(), &model, err)) // umx.cpp:63-70
     {
@@ -59,7 +64,7 @@ int main(int argc, const char **argv)
         fprintf(stderr, "UMX_WIENER_ITERS: need 1 .. 15, got %d\n", wiener_iters);
         return 1;
     }
-    const unsigned flags = (env_int("UMX_NO_WIENER", 0) ? UMX_FLAG_NO_WIENER : 0) | (wiener_iters > 1 ? UMX_FLAG_WIENER_ITERS(wiener_iters) : 0u);
+    const unsigned flags = choice.flags | (env_int("UMX_NO_WIENER", 0) ? UMX_FLAG_NO_WIENER : 0) | (wiener_iters > 1 ? UMX_FLAG_WIENER_ITERS(wiener_iters) : 0u);
     double audio_secs = 0, wall = 0;
     const int first_rand_shift = UMX_REFERENCE_SHIFT; // glibc's first unseeded rand() % 22050 (not rand() here: umx_hip.h)
     const bool resample = env_int("UMX_RESAMPLE", 0) != 0;
@@ -111,7 +116,9 @@ int main(int argc, const char **argv)
             std::filesystem::create_directories(dir, ec);
             for (int t = 0; t < 4; ++t) // umx.cpp:75-96
             {
-                const std::string p = (dir / ("target_" + std::to_string(t) + ".wav")).string();
+                if (!choice.write[t]) // a target that did not run (UMX_TARGETS): a silent slot
+                    continue;
+                const std::string p = (dir / choice.file[t]).string();
                 if (resample ? umx_wav_write_f32_rate(p.c_str(), out[4 * i + t], n[i], rate[i], err)
                              : umx_wav_write_f32(p.c_str(), out[4 * i + t], n[i], err))
                 {

@@ -8,7 +8,10 @@
 //   UMX_WEIGHTS_RESIDENT=expanded   UMX_GEMM=f32
 //   UMX_RESAMPLE=1   any rate of 8 .. 192 kHz: resampled to 44.1 kHz and back on the device (umx_hip_shift_inference_rate,
 //                    DESIGN 13); the stems are written at the input's rate and length
+//   UMX_TARGETS=<comma list of bass,drums,other,vocals>   only these targets run and are written (target_<t>.wav)
+//   UMX_RESIDUAL=1   with UMX_TARGETS: residual.wav = everything else in the mix (UMX_FLAG_RESIDUAL; host/targets_env.h)
 #include "../../include/umx_host.h"
+#include "targets_env.h"
 
 #include <chrono>
 #include <cstdio>
@@ -50,6 +53,9 @@ int main(int argc, const char **argv)
     }
     const std::string model_file = argv[1], wav_file = argv[2], out_dir = argv[3];
     char err[UMX_ERRLEN] = "";
+    umx_target_choice choice;
+    if (!umx_targets_from_env(choice))
+        return 1;
     printf("umx-cli (MI355X / gfx950) main driver program\n");
 
     float *audio = nullptr;
@@ -84,7 +90,7 @@ int main(int argc, const char **argv)
     }
     umx_model_free(model); // weights now live in HBM
 
-    HipBackend hb{ctx, 0};
+    HipBackend hb{ctx, choice.flags};
     if (env_int("UMX_NO_WIENER", 0))
         hb.flags |= UMX_FLAG_NO_WIENER;
     const int wiener_iters = env_int("UMX_WIENER_ITERS", 1); // Wiener EM iterations (wiener.cpp:175; Open-Unmix's niter)
@@ -137,7 +143,9 @@ int main(int argc, const char **argv)
     std::filesystem::create_directories(out_dir, ec); // umx.cpp:84-86
     for (int t = 0; t < 4; ++t)                       // umx.cpp:75-96
     {
-        const std::string p = (std::filesystem::path(out_dir) / ("target_" + std::to_string(t) + ".wav")).string();
+        if (!choice.write[t]) // a target that did not run (UMX_TARGETS): a silent slot
+            continue;
+        const std::string p = (std::filesystem::path(out_dir) / choice.file[t]).string();
         printf("Writing wav file %s\n", p.c_str());
         if (resample ? umx_wav_write_f32_rate(p.c_str(), out[t], n, rate, err) : umx_wav_write_f32(p.c_str(), out[t], n, err))
         {
