@@ -160,6 +160,7 @@ def hip_lib():
     lib.umx_hip_lstm_mode.argtypes = [C.c_void_p]
     lib.umx_hip_debug_lstm_profile.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
     lib.umx_hip_debug_wiener_bins.argtypes = [C.c_int, _fp, _fp, _fp, C.c_float, _fp]
+    lib.umx_hip_debug_gate_math.argtypes = [C.c_int, _fp, _fp, C.c_int, _fp, _fp, _fp]
     lib.umx_hip_lstm_kernel_name.restype = C.c_char_p
     lib.umx_hip_lstm_kernel_name.argtypes = [C.c_void_p]
     lib.umx_hip_gemm_kernel_name.restype = C.c_char_p
@@ -221,7 +222,7 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_infer_segment_device", "umx_hip_sync", "umx_hip_stream_handle", "umx_hip_nb_frames",
                "umx_hip_segment_samples", "umx_hip_hidden", "umx_hip_read_tap", "umx_hip_stage_times",
                "umx_hip_stage_times_slot", "umx_hip_stage_kernel_times_slot",
-               "umx_hip_lstm_was_persistent", "umx_hip_lstm_mode", "umx_hip_lstm_kernel_name", "umx_hip_gemm_kernel_name", "umx_hip_debug_wiener_bins", "umx_hip_debug_lstm_profile", "umx_hip_debug_lstm_placement",
+               "umx_hip_lstm_was_persistent", "umx_hip_lstm_mode", "umx_hip_lstm_kernel_name", "umx_hip_gemm_kernel_name", "umx_hip_debug_wiener_bins", "umx_hip_debug_gate_math", "umx_hip_debug_lstm_profile", "umx_hip_debug_lstm_placement",
                "umx_hip_stream_layer_floats", "umx_hip_stream_get_layer", "umx_hip_stream_set_layer",
                "umx_hip_segment_begin", "umx_hip_segment_lstm_layer", "umx_hip_segment_end",
                "umx_hip_split_inference", "umx_hip_shift_inference", "umx_hip_debug_lds_guard", "umx_hip_debug_f16_bits",
@@ -233,6 +234,33 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
 def resampled_length(n, rate_in, rate_out):
     """ceil(n L / M), the natural output length of the device resampler (host arithmetic; < 0 for a bad rate)."""
     return int(hip_lib().umx_hip_resampled_length(int(n), int(rate_in), int(rate_out)))
+
+
+GATE_FUNCTIONS = ("tanh_epi", "tanh_hw", "sigmoid_hw", "tanhf", "sigmoid_ref")
+CELL_FORMS = ("lstm_cell<false>", "lstm_cell_flat", "lstm_cell<true>")
+
+
+def debug_gate_math(x=None, pre=None, c=None):
+    """umx_hip_debug_gate_math: x (n,) -> {name of GATE_FUNCTIONS: (n,)}; pre (waves, 64) in the quad layout lane = 4 * unit + gate and
+    c (waves, 16) -> {name of CELL_FORMS: (c, h), each (waves, 16)}.  Either half may be left out (None); returns (functions, cells)."""
+    lib = hip_lib()
+    n = nw = 0
+    fn = cell = None
+    if x is not None:
+        x = np.ascontiguousarray(x, np.float32).ravel()
+        n = x.size
+        fn = np.empty((5, n), np.float32)
+    if pre is not None:
+        pre, c = np.ascontiguousarray(pre, np.float32), np.ascontiguousarray(c, np.float32)
+        nw = pre.shape[0]
+        assert pre.shape == (nw, 64) and c.shape == (nw, 16), (pre.shape, c.shape)
+        cell = np.empty((3, nw, 2, 16), np.float32)
+    ptr = lambda a: a.ctypes.data_as(_fp) if a is not None and a.size else None  # noqa: E731
+    rc = lib.umx_hip_debug_gate_math(n, ptr(x), ptr(fn), nw, ptr(pre), ptr(c), ptr(cell))
+    if rc:
+        raise UmxError(rc, "umx_hip_debug_gate_math")
+    return ({k: fn[i] for i, k in enumerate(GATE_FUNCTIONS)} if n else {},
+            {k: (cell[i, :, 0], cell[i, :, 1]) for i, k in enumerate(CELL_FORMS)} if nw else {})
 
 
 def resample_taps(rate_in, rate_out):

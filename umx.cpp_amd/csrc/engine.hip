@@ -38,6 +38,7 @@
 #include "wiener_istft.h"
 #include "wiener_em.h"
 #include "residual_mask.h"
+#include "gate_debug.h"
 
 using namespace umx;
 

@@ -338,6 +338,44 @@ int umx_hip_debug_wiener_bins(int n, const float *X, const float *masks, const f
     return ok ? UMX_OK : UMX_ERR_HIP;
 }
 
+// testing: the gate functions and the cell step on caller-given values (gate_debug.h)
+int umx_hip_debug_gate_math(int n, const float *x, float *fn, int n_waves, const float *pre, const float *c, float *cell)
+{
+    if (n < 0 || n_waves < 0 || (n > 0 && (!x || !fn)) || (n_waves > 0 && (!pre || !c || !cell)) || n > (1 << 24) || n_waves > (1 << 16))
+        return UMX_ERR_ARG;
+    const size_t nx = (size_t)n, nf = (size_t)5 * n, np_ = (size_t)n_waves * 64, nc = (size_t)n_waves * 16, no = (size_t)n_waves * 96;
+    if (nx + np_ == 0)
+        return UMX_OK;
+    float *d = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&d), (nx + nf + np_ + nc + no) * sizeof(float)) != hipSuccess)
+        return UMX_ERR_HIP;
+    float *dx = d, *dfn = dx + nx, *dpre = dfn + nf, *dc = dpre + np_, *dcell = dc + nc;
+    bool ok = true;
+    if (n > 0)
+    {
+        ok = hipMemcpy(dx, x, nx * 4, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok)
+            hipLaunchKernelGGL(debug_gate_fn_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, n, dx, dfn);
+    }
+    if (ok && n_waves > 0)
+    {
+        ok = hipMemcpy(dpre, pre, np_ * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dc, c, nc * 4, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok)
+        {
+            hipLaunchKernelGGL(debug_gate_cell_kernel<0>, dim3(n_waves), dim3(64), 0, nullptr, dpre, dc, dcell);
+            hipLaunchKernelGGL(debug_gate_cell_kernel<1>, dim3(n_waves), dim3(64), 0, nullptr, dpre, dc, dcell + nc * 2);
+            hipLaunchKernelGGL(debug_gate_cell_kernel<2>, dim3(n_waves), dim3(64), 0, nullptr, dpre, dc, dcell + nc * 4);
+        }
+    }
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    if (ok && n > 0)
+        ok = hipMemcpy(fn, dfn, nf * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    if (ok && n_waves > 0)
+        ok = hipMemcpy(cell, dcell, no * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d);
+    return ok ? UMX_OK : UMX_ERR_HIP;
+}
+
 // debugging: queue `launches` LDS-guard kernels on a private stream (they run beside whatever the caller
 // queues next); read the counters back with launches == 0 (returns words corrupted, events in out2[0..1])
 int umx_hip_debug_lds_guard(umx_hip_ctx *ctx, int launches, int rounds, unsigned *out2)

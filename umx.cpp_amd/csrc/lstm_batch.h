@@ -523,10 +523,10 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
             }
             else
             {
-                i_t = __builtin_amdgcn_rcpf(1.0f + exp_hw(-pre_i));
-                f_t = __builtin_amdgcn_rcpf(1.0f + exp_hw(-pre_f));
+                i_t = sigmoid_hw(pre_i);
+                f_t = sigmoid_hw(pre_f);
                 g_t = tanh_hw(pre_g);
-                o_t = __builtin_amdgcn_rcpf(1.0f + exp_hw(-pre_o));
+                o_t = sigmoid_hw(pre_o);
             }
             const float c_t = f_t * c + i_t * g_t; // lstm.cpp:154-156
             const float h = o_t * (PRECISE ? tanhf(c_t) : tanh_hw(c_t)); // lstm.cpp:157

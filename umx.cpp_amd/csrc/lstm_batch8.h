@@ -406,10 +406,10 @@ __device__ __forceinline__ void lstm8_body(const LstmBArgs &a, int chain, int sh
                 }
                 else
                 {
-                    i_t = __builtin_amdgcn_rcpf(1.0f + exp_hw(-pre_i));
-                    f_t = __builtin_amdgcn_rcpf(1.0f + exp_hw(-pre_f));
+                    i_t = sigmoid_hw(pre_i);
+                    f_t = sigmoid_hw(pre_f);
                     g_t = tanh_hw(pre_g);
-                    o_t = __builtin_amdgcn_rcpf(1.0f + exp_hw(-pre_o));
+                    o_t = sigmoid_hw(pre_o);
                 }
                 const float c_t = f_t * c[o] + i_t * g_t;                     // lstm.cpp:154-156
                 const float h = o_t * (PRECISE ? tanhf(c_t) : tanh_hw(c_t)); // lstm.cpp:157

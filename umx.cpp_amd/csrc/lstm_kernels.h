@@ -128,6 +128,8 @@ __device__ __forceinline__ float tanh_hw(float x)
     const float e = exp_hw(-2.0f * fabsf(x));
     return tanh_from_e(x, e, __builtin_amdgcn_rcpf(1.0f + e));
 }
+// the sigmoid of the batched recurrences' gate lanes (lstm_batch.h, lstm_batch8.h): the r of lstm_cell<false> in the sigmoid lanes
+__device__ __forceinline__ float sigmoid_hw(float x) { return __builtin_amdgcn_rcpf(1.0f + exp_hw(-x)); }
 
 // pre-activation of gate column lane = 4*u + g (all 64 lanes) -> new (c, h), replicated in the quad
 template <bool PRECISE> __device__ __forceinline__ void lstm_cell(float pre, int lane, float &c, float &h)
