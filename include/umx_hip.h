@@ -391,8 +391,8 @@ int umx_hip_debug_wiener_bins(int n, const float *X, const float *masks, const f
 /* Testing: the gate functions of the recurrence kernels and of the fc1 epilogue on caller-given values, and one LSTM cell step per
  * wave.  x [n] -> fn [5][n]: tanh_epi (fc1 epilogue), tanh_hw, the fast sigmoid rcp(1 + exp(-x)), and the UMX_FLAG_PRECISE_ACT forms
  * tanhf and 1 / (1 + expf(-x)).  pre [n_waves][64]: a gate pre-activation per lane, lane = 4 * unit + gate (i, f, g, o); c [n_waves][16]
- * -> cell [3][n_waves][2][16]: the new (c, h) of every unit from the default cell of the per-step driver, from the branch-free cell
- * of the persistent kernel and from the PRECISE cell.  n == 0 or n_waves == 0 skips that half (n <= 2^24, n_waves <= 2^16).  Host
+ * -> cell [4][n_waves][2][16]: the new (c, h) of every unit from the default cell of the per-step driver, from the branch-free cell
+ * of the persistent kernel, from the PRECISE cell and from the one-lane cell of the batched recurrences.  n == 0 or n_waves == 0 skips that half (n <= 2^24, n_waves <= 2^16).  Host
  * pointers; needs a current HIP device, no context. */
 int umx_hip_debug_gate_math(int n, const float *x, float *fn, int n_waves, const float *pre, const float *c, float *cell);
 int umx_hip_debug_lstm_profile(umx_hip_ctx *ctx, unsigned long long *out48);

@@ -74,6 +74,17 @@ def cell_emu(pre, c, precise=False, leak=False):
         return c1, (o * th(c1)).astype(f32)
 
 
+def cell_lane_emu(pre, c, order=(0, 1, 2, 3)):
+    """The one-lane cell of the batched recurrences (lstm_cell_lane): the lane of a unit takes the quad's four pre-activations as
+    (i, f, g, o) arguments.  order: which pre-activation each argument gets ((0, 2, 1, 3): f and g handed over in each other's place)."""
+    p = np.asarray(pre, f32).reshape(-1, 16, 4)
+    c = np.asarray(c, f32)
+    i, f, g, o = (fn(p[..., k]) for fn, k in zip((sigmoid_hw_emu, sigmoid_hw_emu, tanh_hw_emu, sigmoid_hw_emu), order))
+    with np.errstate(invalid="ignore"):
+        c1 = (f * c + i * g).astype(f32)
+        return c1, (o * tanh_hw_emu(c1)).astype(f32)
+
+
 @pytest.fixture(scope="module")
 def mags():
     return sf.gate_magnitudes(seed=0, n_random=60_000)
@@ -163,6 +174,30 @@ def test_checks_fail_a_cell_that_lets_the_neighbouring_units_gate_through(cells)
     assert any(s.startswith("cell_emu h pre ~ N(0, 1), |c| <= 1:") for s in f), f  # the yardstick, naming cell and range
     assert any("changed unit(s)" in s and "NaN in unit" in s for s in f), f        # the NaN isolation
     assert any("bit for bit" in s for s in f), f
+
+
+def _lane_cell_failures(cells, order):
+    """The checks tests/test_gpu_gate_math.py runs on lstm_cell_lane<false>: the yardstick, the same bits as the quad cell, NaN isolation."""
+    pre, c, group, precise = cells
+    rep = sf.Report()
+    got = cell_lane_emu(pre, c, order)
+    sf.check_cell_yardstick(rep, "cell_lane_emu", pre, c, group, got, precise)
+    sf.check_cell_same_bits(rep, "cell_emu", cell_emu(pre, c), "cell_lane_emu", got, group)
+    pn, units = sf.nan_planted(pre)
+    sf.check_cell_nan_isolation(rep, "cell_lane_emu", (got[0][:len(pn)], got[1][:len(pn)]), cell_lane_emu(pn, c[:len(pn)], order), units)
+    return rep.failures()
+
+
+def test_unplanted_lane_cell_passes_and_has_the_quad_cells_bits(cells):
+    f = _lane_cell_failures(cells, (0, 1, 2, 3))
+    assert not f, "\n".join(f)
+
+
+def test_checks_fail_a_lane_cell_that_takes_f_and_g_in_each_others_place(cells):
+    f = _lane_cell_failures(cells, (0, 2, 1, 3))
+    assert any(s.startswith("cell_lane_emu ") and "N(0, 1), |c| <= 1:" in s for s in f), f  # the yardstick, naming cell and range
+    assert any("bit for bit" in s for s in f), f
+    assert not any("changed unit(s)" in s for s in f), f  # the fault stays inside its unit: the NaN isolation has nothing to report
 
 
 # ---------------------------------------------------------------- the recurrence on saturated gates

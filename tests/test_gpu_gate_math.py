@@ -4,12 +4,13 @@ Every other GPU test keeps the gate pre-activations within about +-2 (ggml.synth
 so a sigmoid near 0 or 1, tanh(c) at |c| > 2 and both polynomial seams went unchecked.  Here:
 
 * umx_hip_debug_gate_math evaluates the device functions the kernels call -- tanh_epi, tanh_hw, the fast sigmoid, lstm_cell<false>,
-  lstm_cell_flat -- and their PRECISE forms on a few million float32 values (every bit pattern around the seams 0.125 and 0.5 and
+  lstm_cell_flat, lstm_cell_lane<false> (the cell of both batched recurrences) -- and their PRECISE forms on a few million float32 values (every bit pattern around the seams 0.125 and 0.5 and
   around exp_hw's argument crossing -126, magnitudes from the smallest subnormal to FLT_MAX, +-0, +-inf, NaN, normals at scales 0.1
   to 100) against numpy float64.  A fast form may be C_DEFAULT times as far from float64 as its PRECISE form plus FLOOR, over all
   inputs and in every decade of |x|; tanh_epi meets the 3e-7 relative bound of its comment and tanh_hw a relative bound of C_DEFAULT
   times tanhf's plus FLOOR in each of its three ranges (no relative bound where float64's value is a float32 subnormal); oddness,
-  the limits, NaN, the range and monotonicity across the seams hold exactly.  lstm_cell_flat equals lstm_cell<false> bit for bit.
+  the limits, NaN, the range and monotonicity across the seams hold exactly.  lstm_cell_flat and lstm_cell_lane<false> equal
+  lstm_cell<false> bit for bit.
 * The recurrences run with tests/stage_f64.py's saturating weights (weight_ih x 32, forget bias + 3, weight_hh untouched) on audio
   at four times the usual level, twice per context so that the second call starts from a saturated carried state, and every stage
   of the network is held against float64 with the unchanged yardstick.  The float64 restatement must show, on the engine's own fc1
@@ -52,12 +53,14 @@ def test_cell_step_forms_agree_and_keep_a_nan_in_its_quad(pkg, device):
     W, Wn = len(pre), len(pn)
     _, cells = pkg.debug_gate_math(pre=np.concatenate([pre, pn]), c=np.concatenate([c, c[:Wn]]))
     rep = sf.Report()
-    fast, flat, precise = (cells[k] for k in pkg.CELL_FORMS)
-    sf.check_cell_same_bits(rep, "lstm_cell<false>", fast, "lstm_cell_flat", flat, np.concatenate([group, np.full(Wn, "one NaN")]))
-    for name, got in (("lstm_cell<false>", fast), ("lstm_cell_flat", flat)):
+    fast, flat, precise, lane = (cells[k] for k in pkg.CELL_FORMS)
+    groups = np.concatenate([group, np.full(Wn, "one NaN")])
+    sf.check_cell_same_bits(rep, "lstm_cell<false>", fast, "lstm_cell_flat", flat, groups)
+    sf.check_cell_same_bits(rep, "lstm_cell<false>", fast, "lstm_cell_lane<false>", lane, groups)
+    for name, got in (("lstm_cell<false>", fast), ("lstm_cell_flat", flat), ("lstm_cell_lane<false>", lane)):
         worst = sf.check_cell_yardstick(rep, name, pre, c, group, (got[0][:W], got[1][:W]), (precise[0][:W], precise[1][:W]))
         print(f"{name}: worst ratio to lstm_cell<true> {worst:.2f}")
-    for name, got in zip(pkg.CELL_FORMS, (fast, flat, precise)):
+    for name, got in zip(pkg.CELL_FORMS, (fast, flat, precise, lane)):
         sf.check_cell_nan_isolation(rep, name, (got[0][:Wn], got[1][:Wn]), (got[0][W:], got[1][W:]), units)
     geo._finish(rep, "cell_step")
 

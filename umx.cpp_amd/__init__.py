@@ -237,7 +237,7 @@ def resampled_length(n, rate_in, rate_out):
 
 
 GATE_FUNCTIONS = ("tanh_epi", "tanh_hw", "sigmoid_hw", "tanhf", "sigmoid_ref")
-CELL_FORMS = ("lstm_cell<false>", "lstm_cell_flat", "lstm_cell<true>")
+CELL_FORMS = ("lstm_cell<false>", "lstm_cell_flat", "lstm_cell<true>", "lstm_cell_lane<false>")
 
 
 def debug_gate_math(x=None, pre=None, c=None):
@@ -254,7 +254,7 @@ def debug_gate_math(x=None, pre=None, c=None):
         pre, c = np.ascontiguousarray(pre, np.float32), np.ascontiguousarray(c, np.float32)
         nw = pre.shape[0]
         assert pre.shape == (nw, 64) and c.shape == (nw, 16), (pre.shape, c.shape)
-        cell = np.empty((3, nw, 2, 16), np.float32)
+        cell = np.empty((len(CELL_FORMS), nw, 2, 16), np.float32)
     ptr = lambda a: a.ctypes.data_as(_fp) if a is not None and a.size else None  # noqa: E731
     rc = lib.umx_hip_debug_gate_math(n, ptr(x), ptr(fn), nw, ptr(pre), ptr(c), ptr(cell))
     if rc:

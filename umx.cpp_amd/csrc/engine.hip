@@ -301,49 +301,61 @@ template <class Launch> hipError_t lstm_gate_launch(int device, hipStream_t st, 
 }
 } // namespace
 
-// kernel instantiation pickers
-static const void *lstm_persistent_fn(int kpw, bool precise)
-{
-    return precise ? (kpw == 8    ? reinterpret_cast<const void *>(lstm_persistent_kernel<8, true>)
-                      : kpw == 16 ? reinterpret_cast<const void *>(lstm_persistent_kernel<16, true>)
-                      : kpw == 32 ? reinterpret_cast<const void *>(lstm_persistent_kernel<32, true>)
-                                  : reinterpret_cast<const void *>(lstm_persistent_kernel<64, true>))
-                   : (kpw == 8    ? reinterpret_cast<const void *>(lstm_persistent_kernel<8, false>)
-                      : kpw == 16 ? reinterpret_cast<const void *>(lstm_persistent_kernel<16, false>)
-                      : kpw == 32 ? reinterpret_cast<const void *>(lstm_persistent_kernel<32, false>)
-                                  : reinterpret_cast<const void *>(lstm_persistent_kernel<64, false>));
-}
-template <int HL> static const void *lstm_batch_fn_hl(bool wq, bool precise)
-{
-    return wq ? (precise ? reinterpret_cast<const void *>(lstm_batch_kernel<HL, true, true>)
-                         : reinterpret_cast<const void *>(lstm_batch_kernel<HL, true, false>))
-              : (precise ? reinterpret_cast<const void *>(lstm_batch_kernel<HL, false, true>)
-                         : reinterpret_cast<const void *>(lstm_batch_kernel<HL, false, false>));
-}
+template <class K> static const void *kernel_ptr(K *k) { return reinterpret_cast<const void *>(k); }
+
 #ifndef UMX_FUSE_LSTM_PLANES
 #define UMX_FUSE_LSTM_PLANES 1
 #endif
-// octets of 8 lanes x column shards of 64 units (lstm_batch8.h): LSTM hidden 512 (UMX-L) and 256 (umxhq), u8-resident W_hh
-template <int HL> static const void *lstm_batch8_fn_hl(bool precise, int no)
+// The LSTM kernel table: (family, LSTM hidden size Hl, W_hh u8-resident, PRECISE activations, octets per workgroup) -> kernel and
+// the dynamic LDS its limit is raised to.  It holds the only instantiations of the three recurrences; init walks it for the LDS
+// limits and the occupancy, the launches take their kernel from here.
+//   lstm_persistent_kernel  one track; fp32- and u8-resident W_hh in one kernel (u8 = -1)
+//   lstm_batch_kernel       a group of 16 lanes per launch; lds = the 16-lane worst case (a launch passes what its lanes need)
+//   lstm_batch8_kernel      octets of 8 lanes x column shards of 64 units (lstm_batch8.h): Hl 512 (UMX-L) and 256 (umxhq),
+//                           u8-resident W_hh only; two octets per workgroup in turn: hidden 1024, 33 .. 64 lanes in one launch
+enum { LSTM_PERSISTENT = 0, LSTM_BATCH, LSTM_BATCH8 };
+struct LstmKernel
 {
-    if (no == 2)
-        return precise ? reinterpret_cast<const void *>(lstm_batch8_kernel<HL, true, 2>) : reinterpret_cast<const void *>(lstm_batch8_kernel<HL, false, 2>);
-    return precise ? reinterpret_cast<const void *>(lstm_batch8_kernel<HL, true, 1>) : reinterpret_cast<const void *>(lstm_batch8_kernel<HL, false, 1>);
+    int family, hl, u8, precise, octets;
+    const void *fn;
+    size_t lds;
+};
+#define LSTM_ROW_P(HL, PR) {LSTM_PERSISTENT, HL, -1, PR, 1, kernel_ptr(lstm_persistent_kernel<HL / 8, PR>), 0}
+#define LSTM_ROW_B(HL, U8, PR) {LSTM_BATCH, HL, U8, PR, 1, kernel_ptr(lstm_batch_kernel<HL, U8, PR>), lstmb_lds_bytes(LSTMB_GROUP_TRACKS, lstmb_lanes(LSTMB_GROUP_TRACKS).bulk)}
+#define LSTM_ROW_8(HL, PR, NO) {LSTM_BATCH8, HL, 1, PR, NO, kernel_ptr(lstm_batch8_kernel<HL, PR, NO>), lstm8_lds_bytes(HL, NO)}
+#define LSTM_ROWS_P(HL) LSTM_ROW_P(HL, false), LSTM_ROW_P(HL, true)
+#define LSTM_ROWS_B(HL) LSTM_ROW_B(HL, false, false), LSTM_ROW_B(HL, false, true), LSTM_ROW_B(HL, true, false), LSTM_ROW_B(HL, true, true)
+#define LSTM_ROWS_8(HL) LSTM_ROW_8(HL, false, 1), LSTM_ROW_8(HL, true, 1), LSTM_ROW_8(HL, false, 2), LSTM_ROW_8(HL, true, 2)
+static const LstmKernel kLstmKernels[] = {
+    LSTM_ROWS_P(64), LSTM_ROWS_P(128), LSTM_ROWS_P(256), LSTM_ROWS_P(512), //
+    LSTM_ROWS_B(64), LSTM_ROWS_B(128), LSTM_ROWS_B(256), LSTM_ROWS_B(512), //
+    LSTM_ROWS_8(256), LSTM_ROWS_8(512),
+};
+#undef LSTM_ROWS_8
+#undef LSTM_ROWS_B
+#undef LSTM_ROWS_P
+#undef LSTM_ROW_8
+#undef LSTM_ROW_B
+#undef LSTM_ROW_P
+static const LstmKernel *lstm_kernel(int family, int hl, bool u8, bool precise, int octets = 1)
+{
+    for (const LstmKernel &k : kLstmKernels)
+        if (k.family == family && k.hl == hl && (k.u8 < 0 || k.u8 == (int)u8) && k.precise == (int)precise && k.octets == octets)
+            return &k;
+    return nullptr;
 }
-static const void *lstm_batch8_fn(int Hl, bool precise, int no = 1) // no = 2: two octets per workgroup in turn (hidden 1024: 33 .. 64 lanes in one launch)
+// "{128, 256, ...}": the hidden_size values (2 Hl) a family has kernels for
+static std::string lstm_hidden_sizes(int family)
 {
-    return Hl == 512 ? lstm_batch8_fn_hl<512>(precise, no) : Hl == 256 ? lstm_batch8_fn_hl<256>(precise, no) : nullptr;
-}
-static const void *lstm_batch_fn(int Hl, bool wq, bool precise)
-{
-    switch (Hl)
-    {
-    case 64: return lstm_batch_fn_hl<64>(wq, precise);
-    case 128: return lstm_batch_fn_hl<128>(wq, precise);
-    case 256: return lstm_batch_fn_hl<256>(wq, precise);
-    case 512: return lstm_batch_fn_hl<512>(wq, precise);
-    default: return nullptr;
-    }
+    std::string s;
+    int last = 0;
+    for (const LstmKernel &k : kLstmKernels)
+        if (k.family == family && k.hl != last)
+        {
+            s += (s.empty() ? "{" : ", ") + std::to_string(2 * k.hl);
+            last = k.hl;
+        }
+    return s + "}";
 }
 
 // The GEMM kernel tables: (stage, form of the weight[, tile kind]) -> kernel and its dynamic LDS.  They hold the only
@@ -354,7 +366,6 @@ struct GemmKernel
     const void *fn = nullptr;
     int lds = 0;
 };
-template <class K> static const void *kernel_ptr(K *k) { return reinterpret_cast<const void *>(k); }
 
 // gemm_bf16x3_kernel by GemmBType
 template <int MODE> static GemmKernel bx_kernel_m(int bq)
@@ -574,6 +585,7 @@ struct umx_hip_ctx
     int ph_next = -1; // -1: no phased segment open; 0..2: next LSTM layer; 3: back stage pending
     int ph_n = 0;
     unsigned ph_flags = 0;
+    template <class Args> void fill_lstm_args(Args &a, Slot &sl, int layer, const int *active, int nact);
     int run_lstm_layer(Slot &sl, int layer, const int *active, int nact, bool stepwise, unsigned long long lane_mask);
     int run_lstm_layer_batched(Slot &sl, int layer, const int *active, int nact, bool stepwise, unsigned long long lane_mask);
     int sync_all();

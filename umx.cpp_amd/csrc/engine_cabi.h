@@ -343,7 +343,7 @@ int umx_hip_debug_gate_math(int n, const float *x, float *fn, int n_waves, const
 {
     if (n < 0 || n_waves < 0 || (n > 0 && (!x || !fn)) || (n_waves > 0 && (!pre || !c || !cell)) || n > (1 << 24) || n_waves > (1 << 16))
         return UMX_ERR_ARG;
-    const size_t nx = (size_t)n, nf = (size_t)5 * n, np_ = (size_t)n_waves * 64, nc = (size_t)n_waves * 16, no = (size_t)n_waves * 96;
+    const size_t nx = (size_t)n, nf = (size_t)5 * n, np_ = (size_t)n_waves * 64, nc = (size_t)n_waves * 16, no = (size_t)n_waves * 128;
     if (nx + np_ == 0)
         return UMX_OK;
     float *d = nullptr;
@@ -365,6 +365,7 @@ int umx_hip_debug_gate_math(int n, const float *x, float *fn, int n_waves, const
             hipLaunchKernelGGL(debug_gate_cell_kernel<0>, dim3(n_waves), dim3(64), 0, nullptr, dpre, dc, dcell);
             hipLaunchKernelGGL(debug_gate_cell_kernel<1>, dim3(n_waves), dim3(64), 0, nullptr, dpre, dc, dcell + nc * 2);
             hipLaunchKernelGGL(debug_gate_cell_kernel<2>, dim3(n_waves), dim3(64), 0, nullptr, dpre, dc, dcell + nc * 4);
+            hipLaunchKernelGGL(debug_gate_cell_kernel<3>, dim3(n_waves), dim3(64), 0, nullptr, dpre, dc, dcell + nc * 6);
         }
     }
     ok = ok && hipDeviceSynchronize() == hipSuccess;

@@ -602,62 +602,42 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
     }
     stream = slot[0].stream;
     {
-        // residency of the persistent LSTM kernel: the smaller of the two activation flavours of the
-        // instantiation this hidden size uses (the two-grid co-residency of the pipeline rests on it)
-        const int kpw = Hl / 8;
-        int per_cu = 1 << 30, cus = 0;
-        for (int precise = 0; precise < 2; ++precise)
-        {
-            const void *fn = lstm_persistent_fn(kpw, precise != 0);
-            int v = 0;
-            UMX_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fn, LSTM_THREADS, 0));
-            per_cu = std::min(per_cu, v);
-        }
+        // Residency of the recurrences, from the LSTM kernel table: the smallest occupancy over the entries of a family at this
+        // hidden size (both activation flavours, fp32- and u8-resident W_hh, one and two octets per workgroup), each with its LDS
+        // limit raised.  The one-track persistent kernel: the two-grid co-residency of the pipeline rests on it.  lstm_batch_kernel:
+        // at the LDS a launch of all of this context's lanes (at most a group of 16) asks for.
+        // lstm_batch8_kernel (octets of 8 lanes x column shards of 64 units, lstm_batch8.h): LSTM hidden 512 / 256 with the u8-resident
+        // W_hh, chosen per CONTEXT and used for every launch of it -- its sums are not the bits of lstm_batch_kernel, and a lane's
+        // result must not depend on who rides along.  Everything else (hidden 256 / 128, fp32-resident W_hh, UMX_LSTM8_MIN_LANES=99)
+        // runs lstm_batch_kernel, a group of 16 lanes per launch, the groups one after the other.
+        int cus = 0;
         UMX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
         n_cus = cus;
-        lstm_capacity = per_cu * cus;
+        const bool want8 = lstm_batched && B >= env_lstm8_min && !u8_dequant && whh_q[0] && whh_q[1] && whh_q[2];
+        const LstmbLanes ll = lstmb_lanes(B);
+        constexpr int kNone = 1 << 30;
+        int per_cu[3] = {kNone, kNone, kNone}; // by family
+        for (const LstmKernel &k : kLstmKernels)
+        {
+            if (k.hl != Hl || (k.family == LSTM_BATCH && !lstm_batched) || (k.family == LSTM_BATCH8 && !want8))
+                continue;
+            if (k.lds)
+                UMX_HIP_CHECK(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds));
+            int v = 0;
+            UMX_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, k.fn, LSTM_THREADS, k.family == LSTM_BATCH ? lstmb_lds_bytes(ll.nbp, ll.bulk) : k.lds));
+            per_cu[k.family] = std::min(per_cu[k.family], v);
+        }
+        lstm_capacity = per_cu[LSTM_PERSISTENT] == kNone ? 0 : per_cu[LSTM_PERSISTENT] * cus; // (no kernel: the per-step driver)
         if (lstm_batched)
         {
-            // the batched kernel: worst-case dynamic LDS (16 lanes), both activation flavours
-            const size_t lds_max = lstmb_lds_bytes(LSTMB_GROUP_TRACKS, 8);
-            per_cu = 1 << 30;
-            for (int precise = 0; precise < 2; ++precise)
-                for (int wq = 0; wq < 2; ++wq)
-                {
-                    const void *fn = lstm_batch_fn(Hl, wq != 0, precise != 0);
-                    if (!fn)
-                    {
-                        set_error("track batching needs hidden_size in {128, 256, 512, 1024}");
-                        return UMX_ERR_ARG;
-                    }
-                    UMX_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-                    int v = 0;
-                    UMX_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fn, LSTM_THREADS, lstmb_lds_bytes(B > 8 ? 16 : B > 4 ? 8 : B > 2 ? 4 : B > 1 ? 2 : 1, B > 8 ? 8 : 16)));
-                    per_cu = std::min(per_cu, v);
-                }
-            // octets of 8 lanes x column shards of 64 units (lstm_batch8.h): LSTM hidden 512 / 256 with the u8-resident W_hh, chosen per
-            // CONTEXT and used for every launch of it -- its sums are not the bits of lstm_batch_kernel, and a lane's result must not depend on
-            // who rides along.  Everything else (hidden 256 / 128, fp32-resident W_hh, UMX_LSTM8_MIN_LANES=99) runs lstm_batch_kernel, a group
-            // of 16 lanes per launch, the groups one after the other.
-            lstm_batch8_ok = false;
-            if (B >= env_lstm8_min && lstm_batch8_fn(Hl, false) && !u8_dequant && whh_q[0] && whh_q[1] && whh_q[2])
+            if (per_cu[LSTM_BATCH] == kNone)
             {
-                lstm_batch8_ok = true;
-                int per_cu8 = 1 << 30;
-                for (int precise = 0; precise < 2; ++precise)
-                    for (int no = 1; no <= 2; ++no)
-                    {
-                        const void *fn = lstm_batch8_fn(Hl, precise != 0, no);
-                        UMX_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lstm8_lds_bytes(Hl, no)));
-                        int v = 0;
-                        UMX_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fn, LSTM_THREADS, lstm8_lds_bytes(Hl, no)));
-                        per_cu8 = std::min(per_cu8, v);
-                    }
-                lstm_batch8_ok = per_cu8 >= 1 && 8 * 32 <= per_cu8 * cus;
-                if (lstm_batch8_ok) // the persistent launches of this context are lstm_batch8_kernel's: its occupancy decides
-                    per_cu = per_cu8;
+                set_error("track batching needs hidden_size in " + lstm_hidden_sizes(LSTM_BATCH));
+                return UMX_ERR_ARG;
             }
-            lstm_batch_capacity = per_cu * cus;
+            lstm_batch8_ok = per_cu[LSTM_BATCH8] != kNone && per_cu[LSTM_BATCH8] >= 1 && 8 * 32 <= per_cu[LSTM_BATCH8] * cus;
+            // the persistent launches of a lstm_batch8 context are lstm_batch8_kernel's: its occupancy decides
+            lstm_batch_capacity = per_cu[lstm_batch8_ok ? LSTM_BATCH8 : LSTM_BATCH] * cus;
             // the recurrence writes the plane GEMMs' A operands (layers 1, 2 and fc2's right half) and their row sums itself where
             // it runs on the u8-resident W_hh (its gate lanes hold h as two fp16 planes, its all-ones tile the row sums): no
             // split_planes launches for them (lstm_batch.h, LstmBArgs::planes).  -DUMX_FUSE_LSTM_PLANES=0: A/B builds

@@ -1,14 +1,13 @@
 // engine_lstm.h -- part of engine.hip (one translation unit: the kernels inline into their launchers): one LSTM layer: the one-track persistent / per-step drivers and the track-batched kernels, through the admission gate.
 // Included by engine.hip behind the definition of umx_hip_ctx; not a stand-alone header.
 // ---------------------------------------------------------------- LSTM layer
-int umx_hip_ctx::run_lstm_layer(Slot &sl, int layer, const int *active, int nact, bool stepwise, unsigned long long lane_mask)
+// The fields LstmArgs and LstmBArgs share (the two stay separate structs: they are kernel arguments): this layer's weights, scales,
+// bias, the state, sync / status / profiler buffers, the geometry, and per target the W_ih rows in and the layer's output rows out
+// (layers 0 and 1 write la / lb; layer 2 the right half of cat, inference.cpp:118-123 skip concat).
+template <class Args> void umx_hip_ctx::fill_lstm_args(Args &a, Slot &sl, int layer, const int *active, int nact)
 {
-    if (lstm_batched)
-        return run_lstm_layer_batched(sl, layer, active, nact, stepwise, lane_mask);
-    hipStream_t st = sl.stream;
-    LstmArgs a;
     memset(&a, 0, sizeof a);
-    a.W = whh[layer];      // nullptr when W_hh is u8-resident
+    a.W = whh[layer]; // nullptr when W_hh is u8-resident
     a.Wq = whh_q[layer];
     for (int c = 0; c < 8; ++c)
     {
@@ -17,47 +16,40 @@ int umx_hip_ctx::run_lstm_layer(Slot &sl, int layer, const int *active, int nact
     }
     a.bhh = bhh[layer];
     a.state = state;
-    a.hbuf = sl.hbuf;
     a.sync = sl.lsync;
     a.status = sl.status;
     a.prof = (last_flags & UMX_FLAG_LSTM_PROFILE) ? sl.lprof : nullptr;
     a.force_safe = (last_flags & UMX_FLAG_LSTM_FORCE_SAFE) ? 1 : 0;
-    a.poll_delay = lstm_poll_delay;
     a.Hl = Hl;
     a.S = S;
     a.T = T;
     a.ldp = 4 * H;
     a.layer = layer;
+    a.ldo = layer == 2 ? 2 * H : H;
+    a.col0 = layer == 2 ? H : 0;
     for (int i = 0; i < 4; ++i)
     {
         const TargetAct &b = sl.lane[0].ta[i];
         a.P[i] = b.P;
-        if (layer == 0)
-        {
-            a.out[i] = b.la;
-            a.ldo = H;
-            a.col0 = 0;
-        }
-        else if (layer == 1)
-        {
-            a.out[i] = b.lb;
-            a.ldo = H;
-            a.col0 = 0;
-        }
-        else
-        {
-            a.out[i] = b.cat; // inference.cpp:118-123 skip concat: lstm output -> right half of cat
-            a.ldo = 2 * H;
-            a.col0 = H;
-        }
+        a.out[i] = layer == 0 ? b.la : layer == 1 ? b.lb : b.cat;
         a.tmap[i] = i < nact ? active[i] : 0;
     }
-    const int nchains = 2 * nact;
-    a.nchains = nchains;
+    a.nchains = 2 * nact;
+}
+
+int umx_hip_ctx::run_lstm_layer(Slot &sl, int layer, const int *active, int nact, bool stepwise, unsigned long long lane_mask)
+{
+    if (lstm_batched)
+        return run_lstm_layer_batched(sl, layer, active, nact, stepwise, lane_mask);
+    hipStream_t st = sl.stream;
+    LstmArgs a;
+    fill_lstm_args(a, sl, layer, active, nact);
+    a.hbuf = sl.hbuf;
+    a.poll_delay = lstm_poll_delay;
+    const int nchains = a.nchains;
     const dim3 grid(S, nchains), block(LSTM_THREADS);
-    const int kpw = Hl / 8;
-    bool persistent = !stepwise && persistent_ok && (kpw == 8 || kpw == 16 || kpw == 32 || kpw == 64) &&
-                      8 * S <= lstm_capacity;
+    const LstmKernel *k = lstm_kernel(LSTM_PERSISTENT, Hl, false, last_flags & UMX_FLAG_PRECISE_ACT);
+    bool persistent = !stepwise && persistent_ok && k && 8 * S <= lstm_capacity;
     if (persistent)
     {
         a.tag_base = next_tag_base();
@@ -65,7 +57,7 @@ int umx_hip_ctx::run_lstm_layer(Slot &sl, int layer, const int *active, int nact
         // census + arrival counter every launch; the granule area only when the tag epoch wraps
         UMX_HIP_CHECK(hipMemsetAsync(sl.lsync, 0, sizeof(unsigned) * (tag_epoch == 0 ? lsync_words : LSTM_SYNC_HEADER_WORDS), st));
         void *kargs[] = {&a};
-        const void *fn = lstm_persistent_fn(kpw, last_flags & UMX_FLAG_PRECISE_ACT);
+        const void *fn = k->fn;
         // The granule exchange needs the whole grid co-resident.  Residency was checked against the
         // occupancy of this kernel at create time (lstm_capacity); a plain launch is used because ROCm
         // serialises cooperative launches against other queues, which would defeat the two-slot overlap.
@@ -105,39 +97,11 @@ int umx_hip_ctx::run_lstm_layer_batched(Slot &sl, int layer, const int *active, 
 {
     hipStream_t st = sl.stream;
     LstmBArgs a;
-    memset(&a, 0, sizeof a);
-    a.W = whh[layer];
-    a.Wq = whh_q[layer];
-    for (int c = 0; c < 8; ++c)
-    {
-        a.wsc[c] = whh_s[layer][c];
-        a.wof[c] = whh_o[layer][c];
-    }
-    a.bhh = bhh[layer];
-    a.state = state;
+    fill_lstm_args(a, sl, layer, active, nact);
     a.state_out = state;
     a.state_stride = state_floats();
-    a.sync = sl.lsync;
-    a.status = sl.status;
-    a.prof = (last_flags & UMX_FLAG_LSTM_PROFILE) ? sl.lprof : nullptr;
-    a.force_safe = (last_flags & UMX_FLAG_LSTM_FORCE_SAFE) ? 1 : 0;
-    a.Hl = Hl;
-    a.S = S;
-    a.T = T;
-    a.ldp = 4 * H;
-    a.layer = layer;
     a.p_stride = (size_t)Tp * 4 * H;
-    a.out_stride = layer == 2 ? (size_t)Tp * 2 * H : (size_t)Tp * H;
-    a.ldo = layer == 2 ? 2 * H : H;
-    a.col0 = layer == 2 ? H : 0; // inference.cpp:118-123 skip concat: lstm output -> right half of cat
-    for (int i = 0; i < 4; ++i)
-    {
-        const TargetAct &b = sl.lane[0].ta[i];
-        a.P[i] = b.P;
-        a.out[i] = layer == 0 ? b.la : layer == 1 ? b.lb : b.cat;
-        a.tmap[i] = i < nact ? active[i] : 0;
-    }
-    a.nchains = 2 * nact;
+    a.out_stride = (size_t)Tp * a.ldo;
     a.lane_mask = lane_mask;
     a.poll_delay = lstm8_poll_delay;
     const bool wq_layer = whh_q[layer] != nullptr && !u8_dequant;
@@ -169,10 +133,13 @@ int umx_hip_ctx::run_lstm_layer_batched(Slot &sl, int layer, const int *active, 
     const int per = octets ? LSTM8_TRACKS * lstm8_octets(Hl) : LSTMB_GROUP_TRACKS;
     const int octs = octets && env_lstm8_paired && top > per ? 2 : 1; // octets per workgroup, in turn (UMX_LSTM8_PAIRED=0: two launches instead)
     const int span = per * octs, parts = (top + span - 1) / span;
-    a.nbp = octets ? 16 : std::min(top, span) > 8 ? 16 : std::min(top, span) > 4 ? 8 : std::min(top, span) > 2 ? 4 : std::min(top, span) > 1 ? 2 : 1;
-    a.bulk = a.nbp > 8 ? 8 : 16;
-    const size_t lds = octets ? lstm8_lds_bytes(Hl, octs) : lstmb_lds_bytes(a.nbp, a.bulk);
-    const void *fn = octets ? lstm_batch8_fn(Hl, last_flags & UMX_FLAG_PRECISE_ACT, octs) : lstm_batch_fn(Hl, wq, last_flags & UMX_FLAG_PRECISE_ACT);
+    const LstmbLanes ll = lstmb_lanes(octets ? LSTMB_GROUP_TRACKS : std::min(top, span));
+    a.nbp = ll.nbp;
+    a.bulk = ll.bulk;
+    const LstmKernel *k = octets ? lstm_kernel(LSTM_BATCH8, Hl, true, last_flags & UMX_FLAG_PRECISE_ACT, octs)
+                                 : lstm_kernel(LSTM_BATCH, Hl, wq, last_flags & UMX_FLAG_PRECISE_ACT);
+    const void *fn = k->fn; // (init refused the context if its hidden size has no batched kernel)
+    const size_t lds = octets ? k->lds : lstmb_lds_bytes(a.nbp, a.bulk);
     lstm_kernel_last = octets ? "lstm_batch8_kernel" : "lstm_batch_kernel";
     const int threads = LSTM_THREADS;
     const int Sw = octets ? 32 : S; // workgroups per chain of the launch's grid

@@ -117,13 +117,46 @@ template <bool FAST> __device__ __forceinline__ void granule_store16(__amdgpu_bu
 #define LSTMB_RING_PITCH_BYTES 272
 constexpr int LSTMB_RING_PITCH = LSTMB_RING_PITCH_BYTES;
 constexpr size_t LSTMB_HSW_BYTES = 2 * 8 * 16 * sizeof(float); // sum_k h'_k per k-range and lane, two steps (fused row sums): the last KiB
-__host__ __device__ inline size_t lstmb_lds_bytes(int nbp, int bulk, int sp = 1) // sp: slice span of the workgroup (lstmb_body)
+__host__ __device__ inline size_t lstmb_lds_bytes(int nbp, int bulk)
 {
-    return (size_t)2 * 8 * 16 * sp * nbp * 16 /* part */ + (sp > 1 ? (size_t)0 : (size_t)2 * bulk * nbp * LSTMB_RING_PITCH) /* ring (sp = 1) */ +
-           LSTMB_HSW_BYTES;
+    return (size_t)2 * 8 * 16 * nbp * 16 /* part */ + (size_t)2 * bulk * nbp * LSTMB_RING_PITCH /* ring */ + LSTMB_HSW_BYTES;
+}
+// The LDS arrays of lstm_batch_kernel for a launch of `lanes` track lanes: nbp = the power of two they are sized for (LstmBArgs::nbp),
+// bulk = rows per fetch of the W_ih-row ring (LstmBArgs::bulk: the ring of 16 lanes holds half as many rows).  The occupancy check at
+// create and every launch size them from here.
+struct LstmbLanes
+{
+    int nbp, bulk;
+};
+inline LstmbLanes lstmb_lanes(int lanes)
+{
+    const int nbp = lanes > 8 ? 16 : lanes > 4 ? 8 : lanes > 2 ? 4 : lanes > 1 ? 2 : 1;
+    return {nbp, nbp > 8 ? 8 : 16};
 }
 
 __device__ __forceinline__ bf16x8 as_bf16x8(const uint4 &v) { return __builtin_bit_cast(bf16x8, v); }
+
+// u8-resident W_hh: h travels as TWO fp16 planes of h * 2^14 (h1 = fp16(h'), h2 = fp16(h' - h1): 22 significand bits + the
+// residual's sign; |h| < 1 so h' < 2^14, and the second plane is a normal fp16 number down to residuals of 2^-28) -- the split of
+// the plane GEMMs' A operand (gemm_planes.h), whose rows the recurrence writes itself (LstmBArgs::planes).
+constexpr float LSTM_H_SCALE = 16384.0f;
+static_assert(LSTM_H_SCALE == (float)(1 << GP_SPLIT_FIXED_EXP), "the planes of h are the consuming GEMM's A operand");
+// the two plane words of one h: .x = bits of h1, .y = bits of h2.  split2_f16 (gemm_planes.h) for ONE value -- called on an array
+// of eight with one live element it does not compile to the same gate phase.  Returned by value: out-references keep a caller's
+// variables in memory until the call is inlined, and the register allocation of lstm_batch8_kernel then comes out differently.
+__device__ __forceinline__ uint2 h_planes(float h)
+{
+    const float hs14 = h * LSTM_H_SCALE; // power of two: exact
+    const _Float16 h1 = (_Float16)hs14, h2 = (_Float16)(hs14 - (float)h1);
+    return make_uint2(__builtin_bit_cast(unsigned short, h1), __builtin_bit_cast(unsigned short, h2));
+}
+// The 16-byte granule of a PAIR of units (2i, 2i+1) of one track: {tag, h1 pair, h2 pair, h3 pair}.  (b1, b2, b3) are the even
+// unit's terms -- its lane publishes --, other12 = b1 | b2 << 16 and other3 = b3 of the odd unit, 16 lanes up in the wave.
+__device__ __forceinline__ uint4 pair_granule(unsigned tag, unsigned b1, unsigned b2, unsigned b3, unsigned other12, unsigned other3)
+{
+    const unsigned mine12 = b1 | (b2 << 16);
+    return make_uint4(tag, b1 | (other12 << 16), (mine12 >> 16) | (other12 & 0xffff0000u), b3 | (other3 << 16));
+}
 
 // sum of the NDW k-range partials in a fixed tree
 template <int NDW> __device__ __forceinline__ float tree_sum(const float (&p)[8])
@@ -153,29 +186,27 @@ template <int NDW> __device__ __forceinline__ float2v tree_sum2(const float2v (&
 // the pair sums (h1 + h2) + (h1' + h2') travelling in the granules' free fourth dword, added by the consumer and folded over the
 // four 8-unit groups with two lane exchanges: 20 % fewer matrix-pipe cycles, 1.5 % SLOWER -- two dependent lane exchanges on the
 // turn's critical path cost more than four queued matrix instructions on an idle pipe.  Removed in round 4; the dword is zero.)
-// SP = slice span: the workgroup owns SP x 16 hidden units = SP x 64 gate columns (SP = 1: the form described above, the only one
-// instantiated since round 6; SP = 2 was round 4's side-by-side kernel -- eight M tiles, every wave also a gate wave).  group: the workgroup serves lanes
-// [16 group, 16 group + 16) of the launch, with a granule area of their own.
-template <int HL, bool WQ, bool FAST, bool PRECISE, int SP = 1>
-__device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int slice, unsigned char *smem, int *abort_flag, int group = 0)
+// The workgroup (chain, slice) for the lanes [16 group, 16 group + 16) of the context, which have a granule area of their own.
+// Waves 0 .. 3 are also the gate waves: wave w finishes M tile w, units 4w .. 4w + 3 of the slice.
+template <int HL, bool WQ, bool FAST, bool PRECISE>
+__device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int slice, unsigned char *smem, int *abort_flag, int group)
 {
     const int lane0 = LSTMB_GROUP_TRACKS * group;
     constexpr int NKS = HL / 32;                 // K steps (32 hidden units each) of the whole contraction
     constexpr int KSW = NKS >= 8 ? NKS / 8 : 1;  // K steps per dot wave
     constexpr int NDW = NKS >= 8 ? 8 : NKS;      // waves that multiply (all 8 for Hl >= 256)
-    constexpr int MT = 4 * SP;                   // M tiles (16 gate columns = 4 hidden units each) of the workgroup
-    static_assert(SP == 1 || (SP == 2 && NKS >= 8 && WQ), "slice span 2: u8-resident W_hh, eight multiply waves");
+    constexpr int MT = 4;                        // M tiles (16 gate columns = 4 hidden units each) of the workgroup
     constexpr int NPL = WQ ? 1 : 3;              // bf16 planes of W_hh held in registers
     const int target = a.tmap[chain >> 1], dir = chain & 1, wchain = target * 2 + dir;
     const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63, n = l & 15, q = l >> 4;
-    const int nbp = SP > 1 ? LSTMB_GROUP_TRACKS : a.nbp, bulk = a.bulk, ring_mask = 2 * bulk - 1, T = a.T, S = a.S;
+    const int nbp = a.nbp, bulk = a.bulk, ring_mask = 2 * bulk - 1, T = a.T, S = a.S;
     const unsigned lane_mask = (unsigned)(a.lane_mask >> lane0) & 0xffffu;
     const bool lane_on = (lane_mask >> n) & 1u;
     const bool dot_wave = w < NDW, gate_wave = w < MT; // gate wave w finishes M tile w (units 4w .. 4w+3 of the workgroup's)
     constexpr int RING_PITCH = LSTMB_RING_PITCH;
 
     float4 *part = reinterpret_cast<float4 *>(smem);                                   // [2][8 waves][MT tiles][4 q][nbp]
-    unsigned char *ring = smem + (size_t)2 * 8 * 4 * MT * nbp * 16;                   // [2*bulk rows][nbp] blocks of 64 SP floats, RING_PITCH apart
+    unsigned char *ring = smem + (size_t)2 * 8 * 4 * MT * nbp * 16;                   // [2*bulk rows][nbp] blocks of 64 floats, RING_PITCH apart
 
     // ---- W_hh fragments: lane (i = l & 15, q) of tile mt holds gate column 16 mt + i, units k = 32 ks' + 8 q + j
     bf16x8 Wf[MT][KSW][NPL];
@@ -187,8 +218,7 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
             for (int ks = 0; ks < KSW; ++ks)
             {
                 float wv[8];
-                // the weights stay in slices of 64 gate columns ([chain][S][Hl][64]): tile mt is tile mt & 3 of slice SP slice + mt / 4
-                const size_t base = (((size_t)wchain * S + slice * SP + (mt >> 2)) * HL + (size_t)(w * KSW + ks) * 32 + 8 * q) * 64 + 16 * (mt & 3) + n;
+                const size_t base = (((size_t)wchain * S + slice) * HL + (size_t)(w * KSW + ks) * 32 + 8 * q) * 64 + 16 * mt + n;
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
                     wv[j] = WQ ? (float)a.Wq[base + (size_t)j * 64] - 128.0f : whh_at(a.W, a.Wq, a.wsc[wchain], a.wof[wchain], base + (size_t)j * 64);
@@ -211,23 +241,21 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
                 }
             }
     }
-    // WQ: h travels as TWO fp16 planes of h * 2^14 (h1 = fp16(h'), h2 = fp16(h' - h1): 22 significand bits + the
-    // residual's sign; |h| < 1 so h' < 2^14, and the second plane is a normal fp16 number down to residuals of 2^-28)
-    // against ONE exact fp16 plane of q - 128: two products instead of the three of a bf16 split.  The power of two
-    // comes back out with the scale:  W h = (wsc 2^-14) * sum (q-128) h' + ((wof + 128 wsc) 2^-14) * sum h'
-    constexpr float HSCALE = 16384.0f;
-    const float wsc = a.wsc[wchain] * (WQ ? 1.0f / HSCALE : 1.0f),
-                wof2 = (a.wof[wchain] + 128.0f * a.wsc[wchain]) * (WQ ? 1.0f / HSCALE : 1.0f);
+    // WQ: the two fp16 planes of h * 2^14 (h_planes) against ONE exact fp16 plane of q - 128: two products instead of the three
+    // of a bf16 split.  The power of two comes back out with the scale:
+    //     W h = (wsc 2^-14) * sum (q-128) h' + ((wof + 128 wsc) 2^-14) * sum h'
+    const float wsc = a.wsc[wchain] * (WQ ? 1.0f / LSTM_H_SCALE : 1.0f),
+                wof2 = (a.wof[wchain] + 128.0f * a.wsc[wchain]) * (WQ ? 1.0f / LSTM_H_SCALE : 1.0f);
 
     // ---- per-(unit, track) cell state of the gate lanes, b_hh of the unit's four gates
-    const int unit = slice * 16 * SP + 4 * (w & (MT - 1)) + q;
+    const int unit = slice * 16 + 4 * (w & 3) + q;
     const size_t st_h = (size_t)(lane0 + n) * a.state_stride + state_off(target, a.layer, dir, 0, HL);
     const size_t st_c = (size_t)(lane0 + n) * a.state_stride + state_off(target, a.layer, dir, 1, HL);
     float c = 0.f, hlast = 0.f;
     float4 bh = make_float4(0.f, 0.f, 0.f, 0.f);
     if (gate_wave)
     {
-        bh = *reinterpret_cast<const float4 *>(a.bhh + ((size_t)wchain * S + slice * SP + (w >> 2)) * 64 + 4 * (4 * (w & 3) + q));
+        bh = *reinterpret_cast<const float4 *>(a.bhh + ((size_t)wchain * S + slice) * 64 + 4 * (4 * (w & 3) + q));
         if (lane_on)
         {
             c = a.state[st_c + unit];
@@ -245,7 +273,7 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
             hv[j] = (dot_wave && lane_on) ? a.state[st_h + (w * KSW + ks) * 32 + 8 * q + j] : 0.f;
         uint4 p1, p2, p3 = make_uint4(0u, 0u, 0u, 0u);
         if (WQ)
-            split2_f16(hv, HSCALE, p1, p2);
+            split2_f16(hv, LSTM_H_SCALE, p1, p2);
         else
             split3(hv, p1, p2, p3);
         hf[ks][0] = as_bf16x8(p1);
@@ -257,7 +285,7 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
     const __amdgpu_buffer_rsrc_t gran_rs =
         __builtin_amdgcn_make_buffer_rsrc(a.sync + LSTM_SYNC_HEADER_WORDS + (size_t)group * lstmb_granule_words(HL), 0, (int)(lstmb_granule_words(HL) * 4), 0x00020000);
     gu32 *status = (gu32 *)a.status;
-    const float *const Pp = a.P[target] + (size_t)lane0 * a.p_stride + ((size_t)dir * S + slice * SP) * 64 + l;
+    const float *const Pp = a.P[target] + (size_t)lane0 * a.p_stride + ((size_t)dir * S + slice) * 64 + l;
     float *const outp = a.out[target] + (size_t)(lane0 + n) * a.out_stride + a.col0 + dir * HL + unit;
     const size_t ldp = (size_t)a.ldp, ldo = (size_t)a.ldo, p_stride = a.p_stride;
     const unsigned tag_hi = a.tag_epoch << 12;
@@ -266,7 +294,7 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
     unsigned short *const plp = (WQ && a.planes[target]) ? a.planes[target] + (size_t)(lane0 + n) * a.Tp * a.ldpl + a.col0 + dir * HL + unit : nullptr;
     const size_t plane_elems = a.plane_elems, ldpl = (size_t)a.ldpl;
     float *const rsp = (WQ && a.rs_dir[target] && slice == 0) ? a.rs_dir[target] + (size_t)dir * a.rs_rows + (size_t)lane0 * a.Tp : nullptr;
-    float *const hsw = reinterpret_cast<float *>(smem + lstmb_lds_bytes(nbp, bulk, SP) - LSTMB_HSW_BYTES); // [2][8 waves][16]: sum_k h'_k per k-range and lane
+    float *const hsw = reinterpret_cast<float *>(smem + lstmb_lds_bytes(nbp, bulk) - LSTMB_HSW_BYTES); // [2][8 waves][16]: sum_k h'_k per k-range and lane
     unsigned plast = 0; // the fp16 planes of hlast (h1 | h2 << 16)
     // the row sum of the row that step `sm` multiplied with (h'_{sm-1}: frame sm - 1 forward, T - sm backward; at step 0 that is the
     // carried state, not a row): the eight k-ranges' sums in a fixed tree, by sixteen lanes of the last multiply wave of the chain's
@@ -280,7 +308,7 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
 #pragma unroll
             for (int ww = 0; ww < NDW; ++ww)
                 hp[ww] = hsw[((sm & 1) * 8 + ww) * 16 + l];
-            rsp[(size_t)l * a.Tp + (size_t)(dir == 0 ? sm - 1 : T - sm)] = tree_sum<NDW>(hp) * (1.0f / 16384.0f);
+            rsp[(size_t)l * a.Tp + (size_t)(dir == 0 ? sm - 1 : T - sm)] = tree_sum<NDW>(hp) * (1.0f / LSTM_H_SCALE);
         }
     };
 
@@ -299,17 +327,7 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
                                                  (lds_ptr)(size_t)(ring_lds + (unsigned)RING_PITCH * (unsigned)((r & ring_mask) * nbp + nn)), 4, 0, 0);
         }
     };
-    // SP > 1 (every wave multiplies AND finishes a tile): no ring -- a gate lane fetches the 16 bytes of its own (unit, track) of row
-    // step + 1 straight into registers right behind the polls of step `step`: a whole step ahead of its use, in front of the next
-    // step's polls in the memory queue (which return in order: the row is there when they are), no LDS and no other wave involved
-    const float *const Pg = a.P[target] + (size_t)(lane0 + n) * a.p_stride + ((size_t)dir * S + slice * SP + (w >> 2)) * 64 + 4 * (4 * (w & 3) + q);
-    float4 p4n = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (SP > 1)
-    {
-        if (gate_wave && lane_on && t_begin < t_end)
-            p4n = *reinterpret_cast<const float4 *>(Pg + (size_t)(dir == 0 ? t_begin : T - 1 - t_begin) * ldp);
-    }
-    else if (dot_wave)
+    if (dot_wave)
     {
         fetch_rows(t_begin);
         fetch_rows(t_begin + bulk);
@@ -328,7 +346,6 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
     for (int step = t_begin; step < t_end; ++step)
     {
         long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-        float4 p4s = make_float4(0.f, 0.f, 0.f, 0.f);
         if (prof)
             c0 = clock64();
         if (a.abort_at && step == a.abort_at && tid == 0)
@@ -386,14 +403,8 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
                     }
                     if (__all(ok))
                         break;
-                    if (++spins > LSTM_SPIN_LIMIT ||
-                        ((spins & 1023u) == 0 && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))
-                    {
-                        if (l == 0)
-                            __hip_atomic_store(status, 1u + (unsigned)step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        *abort_flag = 1;
+                    if (lstm_poll_gives_up(++spins, status, step, l, abort_flag))
                         break;
-                    }
                     __builtin_amdgcn_s_sleep(LSTMB_RETRY_SLEEP);
                 }
                 prof_spins = spins;
@@ -410,17 +421,11 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
                 // every gate wave of this workgroup is past iteration step - 2 (it has crossed the barrier of step - 1),
                 // so ring rows <= step - 2 may be replaced: rows [step-1+bulk, step-1+2 bulk) take the slots of
                 // [step-1-bulk, step-1); they are first read bulk - 1 barriers from now
-                if (SP == 1 && step - t_begin > bulk && ((step - t_begin) & (bulk - 1)) == (bulk > 1 ? 1 : 0))
+                if (step - t_begin > bulk && ((step - t_begin) & (bulk - 1)) == (bulk > 1 ? 1 : 0))
                     fetch_rows(step - 1 + bulk);
             }
             if (prof)
                 c1 = clock64();
-            if (SP > 1)
-            {
-                p4s = p4n; // row `step`, requested a step ago
-                if (gate_wave && lane_on && step + 1 < t_end)
-                    p4n = *reinterpret_cast<const float4 *>(Pg + (size_t)(dir == 0 ? step + 1 : T - 2 - step) * ldp);
-            }
             floatx4 acc[MT];
             floatx4 accH = {0.f, 0.f, 0.f, 0.f};
             const f16x8 ones16 = __builtin_bit_cast(f16x8, make_uint4(0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u));
@@ -487,8 +492,8 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
             }
         }
         // W_ih x + b_ih of this lane's unit and track (in the ring since at least one barrier ago)
-        float4 p4 = p4s;
-        if (SP == 1 && gate_wave && n < nbp)
+        float4 p4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (gate_wave && n < nbp)
             p4 = *reinterpret_cast<const float4 *>(ring + (size_t)((step & ring_mask) * nbp + n) * RING_PITCH + 16 * (4 * w + q));
         if (prof)
             c2 = clock64();
@@ -513,33 +518,16 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
             const float s0 = sa.x, s1 = sa.y, s2 = sb.x, s3 = sb.y;
             // ((W_ih x + b_ih) + W_hh h) + b_hh, lstm.cpp:132-140
             const float pre_i = (p4.x + s0) + bh.x, pre_f = (p4.y + s1) + bh.y, pre_g = (p4.z + s2) + bh.z, pre_o = (p4.w + s3) + bh.w;
-            float i_t, f_t, g_t, o_t;
-            if (PRECISE)
-            {
-                i_t = sigmoid_ref(pre_i);
-                f_t = sigmoid_ref(pre_f);
-                g_t = tanhf(pre_g);
-                o_t = sigmoid_ref(pre_o);
-            }
-            else
-            {
-                i_t = sigmoid_hw(pre_i);
-                f_t = sigmoid_hw(pre_f);
-                g_t = tanh_hw(pre_g);
-                o_t = sigmoid_hw(pre_o);
-            }
-            const float c_t = f_t * c + i_t * g_t; // lstm.cpp:154-156
-            const float h = o_t * (PRECISE ? tanhf(c_t) : tanh_hw(c_t)); // lstm.cpp:157
+            float c_t;
+            const float h = lstm_cell_lane<PRECISE>(pre_i, pre_f, pre_g, pre_o, c, c_t);
             // h split in three bf16 terms (WQ: two fp16 terms of h * 2^14); the odd unit of the pair sits 16 lanes up in
             // this wave
-            unsigned b1, b2, b3;
+            unsigned b1, b2, b3 = 0u;
             if (WQ)
             {
-                const float hs14 = h * HSCALE;
-                const _Float16 h1 = (_Float16)hs14, h2 = (_Float16)(hs14 - (float)h1);
-                b1 = __builtin_bit_cast(unsigned short, h1);
-                b2 = __builtin_bit_cast(unsigned short, h2);
-                b3 = 0u;
+                const uint2 hp = h_planes(h);
+                b1 = hp.x;
+                b2 = hp.y;
             }
             else
             {
@@ -561,8 +549,7 @@ __device__ __forceinline__ void lstmb_body(const LstmBArgs &a, int chain, int sl
                 plast = mine12;
                 if ((q & 1) == 0) // publish the pair (this unit, the next), tagged step + 1
                 {
-                    const uint4 gv = make_uint4(tag_hi | (unsigned)(step + 1), b1 | (other12 << 16), (mine12 >> 16) | (other12 & 0xffff0000u),
-                                                WQ ? 0u : (b3 | (other3 << 16)));
+                    const uint4 gv = pair_granule(tag_hi | (unsigned)(step + 1), b1, b2, b3, other12, other3);
                     granule_store16<FAST>(gran_rs, (int)(lstmb_granule_index(step & 1, chain, unit, n, HL, nbp) * 16), gv);
                 }
             }
@@ -652,15 +639,14 @@ __global__ __launch_bounds__(64) void lstm_last_row_sum_kernel(LstmBArgs a, int 
     float s = 0.f;
     for (int k = l; k < HL; k += 64) // lane l: units l, l + 64, ...; then the 64 lanes by xor-exchange
     {
-        const float hs14 = h[k] * 16384.0f;
-        const _Float16 h1 = (_Float16)hs14, h2 = (_Float16)(hs14 - (float)h1);
-        s += (float)h1 + (float)h2;
+        const uint2 hp = h_planes(h[k]);
+        s += (float)__builtin_bit_cast(_Float16, (unsigned short)hp.x) + (float)__builtin_bit_cast(_Float16, (unsigned short)hp.y);
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1)
         s += __shfl_xor(s, off, 64);
     if (l == 0)
-        a.rs_dir[target][(size_t)dir * a.rs_rows + row] = s * (1.0f / 16384.0f);
+        a.rs_dir[target][(size_t)dir * a.rs_rows + row] = s * (1.0f / LSTM_H_SCALE);
 }
 
 } // namespace umx

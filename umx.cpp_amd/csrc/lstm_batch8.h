@@ -58,12 +58,6 @@ __host__ __device__ inline size_t lstm8_lds_bytes(int Hl, int no = 1) { return (
 #ifndef LSTM8_EARLY_KS
 #define LSTM8_EARLY_KS 13 // the next turn's polls are issued behind this k-step of the matrix phase (-1: in front of it)
 #endif
-#ifndef LSTM8_EXPERIMENT
-#define LSTM8_EXPERIMENT 0 // timing builds only (wrong results): 1 = no request for the next row of W_ih x, 2 = no output stores inside the loop
-#endif
-#ifndef LSTM8_STAGE_PLANES
-#define LSTM8_STAGE_PLANES 1 // the row's fused A planes go through LDS and leave as two 16-byte store instructions per turn (0: two 2-byte stores per lane)
-#endif
 #ifndef LSTM8_PIN_ORDER
 #define LSTM8_PIN_ORDER 1 // the matrix phase in the order written (sched_barrier): two matrix instructions, then the fragment read LSTM8_FRAG_AHEAD k-steps ahead -- left to itself the scheduler sinks every read to its use (1,655 -> 1,540 cycles)
 #endif
@@ -118,8 +112,7 @@ __device__ __forceinline__ void lstm8_body(const LstmBArgs &a, int chain, int sh
             asm volatile("" ::: "memory"); // (sixteen byte loads in flight, not 256)
         }
     }
-    constexpr float HSCALE = 16384.0f;
-    const float wsc = a.wsc[wchain] * (1.0f / HSCALE), wof2 = (a.wof[wchain] + 128.0f * a.wsc[wchain]) * (1.0f / HSCALE);
+    const float wsc = a.wsc[wchain] * (1.0f / LSTM_H_SCALE), wof2 = (a.wof[wchain] + 128.0f * a.wsc[wchain]) * (1.0f / LSTM_H_SCALE);
     const float4 bh = *reinterpret_cast<const float4 *>(a.bhh + ((size_t)wchain * S + (U >> 4)) * 64 + 4 * (U & 15));
 
     // ---- what this thread polls: granule g = i 512 + tid of its (chain, octet): k-step g / 128, k-group (g / 32) % 4, pair (g / 8) % 4, track g % 8
@@ -177,7 +170,8 @@ __device__ __forceinline__ void lstm8_body(const LstmBArgs &a, int chain, int sh
             unsigned d1 = 0u, d2 = 0u;
             if (p_on[o])
             {
-                const float x0 = a.state[sh + k0] * HSCALE, x1 = a.state[sh + k0 + 1] * HSCALE;
+                // h_planes of the pair's two units, the two interleaved (through the helper the 512-unit instantiations allocate differently)
+                const float x0 = a.state[sh + k0] * LSTM_H_SCALE, x1 = a.state[sh + k0 + 1] * LSTM_H_SCALE;
                 const _Float16 a1 = (_Float16)x0, b1 = (_Float16)x1;
                 const _Float16 a2 = (_Float16)(x0 - (float)a1), b2 = (_Float16)(x1 - (float)b1);
                 d1 = (unsigned)__builtin_bit_cast(unsigned short, a1) | ((unsigned)__builtin_bit_cast(unsigned short, b1) << 16);
@@ -265,13 +259,8 @@ __device__ __forceinline__ void lstm8_body(const LstmBArgs &a, int chain, int sh
                 pending = false;
                 while (!__all(ok))
                 {
-                    if (++spins > LSTM_SPIN_LIMIT || ((spins & 1023u) == 0 && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))
-                    {
-                        if (l == 0)
-                            __hip_atomic_store(status, 1u + (unsigned)step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        *abort_flag = 1;
+                    if (lstm_poll_gives_up(++spins, status, step, l, abort_flag))
                         break;
-                    }
                     __builtin_amdgcn_s_sleep(LSTM8_RETRY_SLEEP);
                     if (p_on[o])
                     {
@@ -297,19 +286,14 @@ __device__ __forceinline__ void lstm8_body(const LstmBArgs &a, int chain, int sh
             // the CU's one address path then stall the wave's matrix instructions for longer -- 5.85 against 5.5 ms per 32-lane launch.)
             // (The row's two planes as ONE dword store per lane -- the even unit of a pair writing (h1, h1') into plane 0, the odd unit
             // (h2, h2') into plane 1 -- saves a store instruction and costs more in the gate phase: 9.7 against 9.4 ms per 64-lane launch.)
-            if (!(LSTM8_EXPERIMENT & 2) && lane_on[o] && step > t_begin)
+            if (lane_on[o] && step > t_begin)
             {
                 const size_t fr = (size_t)(dir == 0 ? step - 1 : T - step);
                 if (!plp[o] || a.write_f32)
                     outp[o][fr * ldo] = hlast[o]; // lstm.cpp:163-164,170-171
-                if (plp[o] && !LSTM8_STAGE_PLANES)
-                {
-                    plp[o][fr * ldpl] = (unsigned short)(plast[o] & 0xffffu);
-                    plp[o][plane_elems + fr * ldpl] = (unsigned short)(plast[o] >> 16);
-                }
             }
             const float4 p4 = p4n[o]; // row `step` of W_ih x + b_ih, requested a step ago
-            if (!(LSTM8_EXPERIMENT & 1) && lane_on[o] && step + 1 < t_end)
+            if (lane_on[o] && step + 1 < t_end)
                 p4n[o] = stream_load4(Pg[o] + (size_t)(dir == 0 ? step + 1 : T - 2 - step) * ldp); // (a row of W_ih x + b_ih is read once)
             if (prof)
                 c1 = clock64();
@@ -321,7 +305,7 @@ __device__ __forceinline__ void lstm8_body(const LstmBArgs &a, int chain, int sh
             // the PREVIOUS step's row of the fused A planes: staged in LDS by the gate lanes (two bytes each), it leaves as ONE 16-byte store
             // per lane of two waves -- a whole 128-byte line per (track, plane) -- instead of two 2-byte stores per lane of all eight:
             // 2 instead of 16 instructions per turn on the CU's one address path
-            if (LSTM8_STAGE_PLANES && !(LSTM8_EXPERIMENT & 2) && have_planes && step > t_begin && w < 2)
+            if (have_planes && step > t_begin && w < 2)
             {
                 const int strk = l >> 3, sgrp = l & 7;
                 if ((mask8s[o] >> strk) & 1u)
@@ -382,7 +366,7 @@ __device__ __forceinline__ void lstm8_body(const LstmBArgs &a, int chain, int sh
                 const float Hs = tree_sum<8>(hp8);
                 // the row that this step multiplied with (step 0 multiplies with the carried state, not a row)
                 if (rs_wave) // (wave-uniform: one wave of a chain)
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(Hs * (1.0f / 16384.0f)), rs_rs,
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(Hs * (1.0f / LSTM_H_SCALE)), rs_rs,
                                                           (rs_off[o] != LSTM8_OOR && step > 0) ? rs_off[o] + (dir == 0 ? step - 1 : T - step) * 4 : LSTM8_OOR, 0, 0);
                 const float hterm = wof2 * Hs;
                 float s[4];
@@ -396,26 +380,10 @@ __device__ __forceinline__ void lstm8_body(const LstmBArgs &a, int chain, int sh
                 }
                 // ((W_ih x + b_ih) + W_hh h) + b_hh, lstm.cpp:132-140
                 const float pre_i = (p4.x + s[0]) + bh.x, pre_f = (p4.y + s[1]) + bh.y, pre_g = (p4.z + s[2]) + bh.z, pre_o = (p4.w + s[3]) + bh.w;
-                float i_t, f_t, g_t, o_t;
-                if (PRECISE)
-                {
-                    i_t = sigmoid_ref(pre_i);
-                    f_t = sigmoid_ref(pre_f);
-                    g_t = tanhf(pre_g);
-                    o_t = sigmoid_ref(pre_o);
-                }
-                else
-                {
-                    i_t = sigmoid_hw(pre_i);
-                    f_t = sigmoid_hw(pre_f);
-                    g_t = tanh_hw(pre_g);
-                    o_t = sigmoid_hw(pre_o);
-                }
-                const float c_t = f_t * c[o] + i_t * g_t;                     // lstm.cpp:154-156
-                const float h = o_t * (PRECISE ? tanhf(c_t) : tanh_hw(c_t)); // lstm.cpp:157
-                const float hs14 = h * HSCALE;
-                const _Float16 h1 = (_Float16)hs14, h2 = (_Float16)(hs14 - (float)h1);
-                const unsigned b1 = __builtin_bit_cast(unsigned short, h1), b2 = __builtin_bit_cast(unsigned short, h2);
+                float c_t;
+                const float h = lstm_cell_lane<PRECISE>(pre_i, pre_f, pre_g, pre_o, c[o], c_t);
+                const uint2 hp = h_planes(h);
+                const unsigned b1 = hp.x, b2 = hp.y;
                 const unsigned mine12 = b1 | (b2 << 16);
                 // the odd unit of the pair sits 16 lanes up: row r + 1 into row r
                 const unsigned other12 = __builtin_amdgcn_permlane16_swap(mine12, mine12, false, false)[1];
@@ -425,7 +393,7 @@ __device__ __forceinline__ void lstm8_body(const LstmBArgs &a, int chain, int sh
                     hlast[o] = h;
                     plast[o] = mine12;
                 }
-                if (LSTM8_STAGE_PLANES && have_planes)
+                if (have_planes)
                 {
                     // two bytes per lane and plane, rows of LSTM8_STG_PITCH ushorts: the eight tracks of a wave on eight bank quads.  (One
                     // dword per pair of units from the even unit's lane -- half the lanes under an exec mask -- measured 2.5 % slower
@@ -436,7 +404,7 @@ __device__ __forceinline__ void lstm8_body(const LstmBArgs &a, int chain, int sh
                 }
                 // the even unit of a pair publishes it (this unit, the next), tagged step + 1
                 granule_store16<FAST>(gran_rs[o], (lane_on[o] && (q & 1) == 0) ? (step & 1) * gslot + pub_off : LSTM8_OOR,
-                                      make_uint4(tag_hi | (unsigned)(step + 1), b1 | (other12 << 16), (mine12 >> 16) | (other12 & 0xffff0000u), 0u));
+                                      pair_granule(tag_hi | (unsigned)(step + 1), b1, b2, 0u, other12, 0u));
             }
             if (prof)
             {

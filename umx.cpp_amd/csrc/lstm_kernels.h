@@ -130,6 +130,28 @@ __device__ __forceinline__ float tanh_hw(float x)
 }
 // the sigmoid of the batched recurrences' gate lanes (lstm_batch.h, lstm_batch8.h): the r of lstm_cell<false> in the sigmoid lanes
 __device__ __forceinline__ float sigmoid_hw(float x) { return __builtin_amdgcn_rcpf(1.0f + exp_hw(-x)); }
+// One cell in ONE lane, the gate phase of both batched recurrences: the four pre-activations of a unit -> c_t, returns h.  The
+// operations of lstm_cell<PRECISE> in its order (same bits), without the quad exchange.
+template <bool PRECISE> __device__ __forceinline__ float lstm_cell_lane(float pre_i, float pre_f, float pre_g, float pre_o, float c, float &c_t)
+{
+    float i_t, f_t, g_t, o_t;
+    if (PRECISE)
+    {
+        i_t = sigmoid_ref(pre_i);
+        f_t = sigmoid_ref(pre_f);
+        g_t = tanhf(pre_g);
+        o_t = sigmoid_ref(pre_o);
+    }
+    else
+    {
+        i_t = sigmoid_hw(pre_i);
+        f_t = sigmoid_hw(pre_f);
+        g_t = tanh_hw(pre_g);
+        o_t = sigmoid_hw(pre_o);
+    }
+    c_t = f_t * c + i_t * g_t;                          // lstm.cpp:154-156
+    return o_t * (PRECISE ? tanhf(c_t) : tanh_hw(c_t)); // lstm.cpp:157
+}
 
 // pre-activation of gate column lane = 4*u + g (all 64 lanes) -> new (c, h), replicated in the quad
 template <bool PRECISE> __device__ __forceinline__ void lstm_cell(float pre, int lane, float &c, float &h)
@@ -313,14 +335,11 @@ typedef __attribute__((address_space(1))) unsigned long long gu64;
 typedef __attribute__((address_space(1))) unsigned gu32;
 
 constexpr unsigned LSTM_SPIN_LIMIT = 1u << 22; // bounded spins: ~seconds, then abort the launch
-#define LSTM_POLLS_IN_FLIGHT 1 // measured best alone and with two grids on the chip (round 5, alone: 2: +3 %, 3: +10 %; round 1, pipelined: 2: +3 %, 3: +5 %)
 #define LSTM_TRACE_SLICE 5
 #define LSTM_TRACE_STEP0 1200
 #define LSTM_PROF_WAVE 1 // the dot wave the in-kernel profiler reports beside the gate wave
 #define LSTM_P_BULK 16 // W_ih x + b_ih rows fetched per bulk (multiple of 8, power of two)
 #define LSTM_P_RING (2 * LSTM_P_BULK)
-#define LSTM_GATE_POLL_DELAY 0 // x64 cycles the gate wave waits after publishing before its own first poll
-                               // (measured 0..4: 0 is best, its first poll already succeeds)
 #define LSTM_POLL_DELAY 5 // x64 shader cycles a dot wave sleeps after the barrier before its first poll (round 5: 8 -> 5 with the shorter gate phase; 6: +2 %, 4: +2 %, 3: +5 %)
 
 __device__ __forceinline__ unsigned xcc_id()
@@ -342,6 +361,20 @@ template <bool FAST> __device__ __forceinline__ void granule_store(gu64 *p, unsi
 __device__ __forceinline__ unsigned long long granule_load(gu64 *p)
 {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // global_load_dwordx2 ... sc1
+}
+// After the `spins`-th failed poll of a wave, in every recurrence.  True when the wave must give up -- its spins have run out, or
+// (looked at every 1024 spins) another wave of the launch has already given up: the status word then names the step, the workgroup's
+// abort flag is up, and the caller leaves its poll loop for the barrier behind which every wave of the workgroup returns.
+__device__ __forceinline__ bool lstm_poll_gives_up(unsigned spins, gu32 *status, int step, int l, int *abort_flag)
+{
+    if (spins > LSTM_SPIN_LIMIT || ((spins & 1023u) == 0 && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))
+    {
+        if (l == 0)
+            __hip_atomic_store(status, 1u + (unsigned)step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *abort_flag = 1;
+        return true;
+    }
+    return false;
 }
 
 // Census (thread 0 of every workgroup): register on the XCD this workgroup actually runs on, one bounded grid
@@ -589,48 +622,20 @@ __device__ __forceinline__ void lstm_persistent_body(const LstmArgs &a, int chai
                 // overwritten two steps later, so every lane reloads until one poll shows all tags.
                 gu64 *g = gran + granule_index((step - 1) & 1, chain, w * KPW + (l < KPW ? l : 0), S);
                 const unsigned want = tag_base + (unsigned)step;
-                // The gate wave needs ~600 cycles before anything can change: sleep through that, then keep
-                // three polls in flight so the poll period is a third of the L2 round trip (the step time is
-                // a maximum over ~2000 polling waves: the quantisation is paid almost in full every step).
-                if (FAST)
-                {
-                    if (!gate_wave)
-                        for (int i = 0; i < poll_delay; ++i)
-                            __builtin_amdgcn_s_sleep(1);
-                    else if (LSTM_GATE_POLL_DELAY > 0)
-                        __builtin_amdgcn_s_sleep(LSTM_GATE_POLL_DELAY);
-                }
-                unsigned long long x = granule_load(g), xb = 0, xc = 0;
-                if (LSTM_POLLS_IN_FLIGHT >= 2)
-                    xb = granule_load(g);
-                if (LSTM_POLLS_IN_FLIGHT >= 3)
-                    xc = granule_load(g);
+                // The gate wave needs ~600 cycles before anything can change: a dot wave sleeps through that (the gate wave's
+                // own first poll already succeeds), then one poll at a time (more polls in flight measured slower).
+                if (FAST && !gate_wave)
+                    for (int i = 0; i < poll_delay; ++i)
+                        __builtin_amdgcn_s_sleep(1);
+                unsigned long long x = granule_load(g);
                 unsigned spins = 0;
                 for (;;)
                 {
                     if (__all((unsigned)(x >> 32) == want))
                         break;
-                    if (LSTM_POLLS_IN_FLIGHT >= 3)
-                    {
-                        x = xb;
-                        xb = xc;
-                        xc = granule_load(g);
-                    }
-                    else if (LSTM_POLLS_IN_FLIGHT == 2)
-                    {
-                        x = xb;
-                        xb = granule_load(g);
-                    }
-                    else
-                        x = granule_load(g);
-                    if (++spins > LSTM_SPIN_LIMIT ||
-                        ((spins & 1023u) == 0 && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))
-                    {
-                        if (l == 0)
-                            __hip_atomic_store(status, 1u + (unsigned)step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        *abort_flag = 1;
+                    x = granule_load(g);
+                    if (lstm_poll_gives_up(++spins, status, step, l, abort_flag))
                         break;
-                    }
                     if (!FAST)
                         __builtin_amdgcn_s_sleep(1);
                 }
