@@ -53,6 +53,19 @@ extern "C" {
  * Needs at least one skipped and one active target, else UMX_ERR_ARG (four targets + residual would be five sources: not supported).
  * "vocals + accompaniment" = UMX_FLAG_SKIP_TARGET(0) | (1) | (2) | UMX_FLAG_RESIDUAL: out[3] vocals, out[0] accompaniment, one network's cost. */
 #define UMX_FLAG_RESIDUAL 0x8000
+/* Soft mask: Open-Unmix's Separator(softmask=True) -- no analogue in the reference.  The first estimate of a source is
+ * y_j = X g_j / (eps + sum_k g_k) with g_j = mask_j |X| instead of mask_j |X| X/|X|: the first estimates (and so the UMX_FLAG_NO_WIENER stems)
+ * add up to the mixture, and no target's initial PSD counts more energy than the mixture holds.  Right after fc3 the mask planes of the ACTIVE
+ * targets j1 < j2 < ... are rewritten in place, for every channel, frame and bin b <= 2048, in fp32:
+ *     a = |X| (the one mix_magnitude of csrc/common.h)    g_j = m_j * a
+ *     d = 1e-10f + (((g_j1 + g_j2) + g_j3) + g_j4)        (as many terms as there are; 1e-10 = WIENER_EPS = Open-Unmix's eps)
+ *     m'_j = g_j / d                                      (the correctly rounded quotient)
+ * and every consumer goes on forming m'_j a X/|X| = X g_j / (eps + sum g).  A silent bin (a = 0) gives m' = 0; a skipped target takes no part
+ * in the sum and stays what it is (zero planes, or the residual); the "mask" and "target_mag" taps show m' and m' a.  With UMX_FLAG_RESIDUAL the
+ * order is Open-Unmix's: normalise, then rho = 1 - sum m' from the normalised planes -- the residual's first estimate is then eps / (eps + sum g)
+ * of the mixture, i.e. almost nothing, and only the EM iterations give it energy (Open-Unmix behaves the same).  A call without the flag
+ * launches exactly what it launched before the flag existed.  Not supported by the multi-GPU driver in by-target mode (no rank holds every mask). */
+#define UMX_FLAG_SOFTMASK 0x2
 #define UMX_FLAG_LSTM_STEPWISE 0x10 /* one launch per timestep instead of the persistent kernel */
 #define UMX_FLAG_DEBUG_TAPS 0x20    /* keep what only the taps read: the filtered spectrograms for umx_hip_read_tap("y") (the fused kernel does not
                                      * write them otherwise) and, in track-batched contexts, the fp32 rows of the recurrence's layers ("lstm",

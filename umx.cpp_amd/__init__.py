@@ -23,6 +23,7 @@ SEGMENT_SAMPLES = 60 * 44100  # inference.hpp:13 x dsp.hpp:16
 UMX_OK, ERR_ARG, ERR_HIP, ERR_MODEL, ERR_TIMEOUT, ERR_NODEVICE = 0, 1, 2, 3, 4, 5
 DTYPE_F32, DTYPE_U8, DTYPE_U16 = 0, 1, 2
 FLAG_NO_WIENER = 0x1
+FLAG_SOFTMASK = 0x2  # first estimates X g_j / (eps + sum g), g = mask |X| (Open-Unmix's softmask=True)
 FLAG_LSTM_STEPWISE = 0x10
 FLAG_DEBUG_TAPS = 0x20
 FLAG_LSTM_FORCE_SAFE = 0x40
@@ -41,9 +42,10 @@ FLAG_WIENER_ITERS_MASK = 0xF0000
 TARGET_NAMES = ("bass", "drums", "other", "vocals")  # convert-umx-pth-to-ggml.py:104
 
 
-def flags_for_targets(names, residual=False):
-    """The flag word of Open-Unmix's Separator(targets=names, residual=residual): every target not named is skipped; with
-    `residual` the lowest skipped slot (residual_slot) carries the rest of the mix.  ValueError for what the engine refuses."""
+def flags_for_targets(names, residual=False, softmask=False):
+    """The flag word of Open-Unmix's Separator(targets=names, residual=residual, softmask=softmask): every target not named is
+    skipped; with `residual` the lowest skipped slot (residual_slot) carries the rest of the mix; with `softmask` the first estimates
+    are the soft-masked ones (FLAG_SOFTMASK).  ValueError for what the engine refuses."""
     names = list(names)
     for nm in names:
         if nm not in TARGET_NAMES:
@@ -58,6 +60,8 @@ def flags_for_targets(names, residual=False):
         flags |= FLAG_RESIDUAL
         if residual_slot(flags) < 0:
             raise ValueError("a residual needs one to three of the four targets: it takes the slot of a target that does not run")
+    if softmask:
+        flags |= FLAG_SOFTMASK
     return flags
 
 

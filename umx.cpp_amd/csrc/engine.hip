@@ -38,6 +38,7 @@
 #include "wiener_istft.h"
 #include "wiener_em.h"
 #include "residual_mask.h"
+#include "softmask.h"
 #include "gate_debug.h"
 
 using namespace umx;
@@ -625,7 +626,8 @@ struct umx_hip_ctx
     int phase_masks();
     int phase_residual();
     int phase_finish_device(float *const out_dev_[4]);
-    // UMX_FLAG_RESIDUAL: the one check of the flag combination every entry point that takes flags goes through
+    // UMX_FLAG_RESIDUAL: the one check of the flag combination every entry point that takes flags goes through.
+    // UMX_FLAG_SOFTMASK goes with every combination that passes: it normalises whatever targets are active (none: nothing to do).
     int check_flags(unsigned flags)
     {
         if (residual_slot_of(flags) != -2)
@@ -634,6 +636,8 @@ struct umx_hip_ctx
                   "plus a residual would be five sources) and at least one active target");
         return UMX_ERR_ARG;
     }
+    // UMX_FLAG_SOFTMASK: the active targets' masks normalised in place, all lanes of the call in one launch (softmask.h)
+    void stage_softmask(Slot &sl, hipStream_t st, int nb, const float *const *audio_dev, const int *active, int nact);
     // rho of the residual slot from the active targets' masks, all lanes of the call in one launch (residual_mask.h)
     int stage_residual(Slot &sl, hipStream_t st, int nb, const float *const *audio_dev, unsigned flags);
     static void active_list(unsigned flags, int *active, int &nact)

@@ -272,8 +272,28 @@ int umx_hip_ctx::stage_masks(Slot &sl, hipStream_t st, int nb, const float *cons
     stage_range(ST_FC3);
     UMX_HIP_CHECK(hipEventRecord(sl.ev[ST_FC3], st));
     launch_gemm_lanes(sl, st, nb, audio_dev, G_FC3, 0, active, nact, dbg);
+    if ((flags & UMX_FLAG_SOFTMASK) && nact > 0) // inside ST_FC3's interval: the masks are not complete before it
+        stage_softmask(sl, st, nb, audio_dev, active, nact);
     UMX_HIP_CHECK(hipGetLastError());
     return UMX_OK;
+}
+
+void umx_hip_ctx::stage_softmask(Slot &sl, hipStream_t st, int nb, const float *const *audio_dev, const int *active, int nact)
+{
+    const LaneSet lanes = lane_set(nb, audio_dev);
+    Lane &L0 = sl.lane[0];
+    SoftmaskPlanes pl = {};
+    for (int i = 0; i < nact; ++i)
+        pl.m[i] = L0.ta[active[i]].mag;
+    const dim3 grid((2 * T + SM_ROWS - 1) / SM_ROWS, 1, lanes.count), block(256);
+    if (nact == 1)
+        hipLaunchKernelGGL(softmask_kernel<1>, grid, block, 0, st, pl, L0.spec, T, lanes, lane_strides());
+    else if (nact == 2)
+        hipLaunchKernelGGL(softmask_kernel<2>, grid, block, 0, st, pl, L0.spec, T, lanes, lane_strides());
+    else if (nact == 3)
+        hipLaunchKernelGGL(softmask_kernel<3>, grid, block, 0, st, pl, L0.spec, T, lanes, lane_strides());
+    else
+        hipLaunchKernelGGL(softmask_kernel<4>, grid, block, 0, st, pl, L0.spec, T, lanes, lane_strides());
 }
 
 int umx_hip_ctx::stage_residual(Slot &sl, hipStream_t st, int nb, const float *const *audio_dev, unsigned flags)

@@ -637,6 +637,9 @@ extern "C" int umx_mgpu_separate_track(umx_mgpu *m, const float *audio_host, int
     // targets) would be taken for the caller's, and no rank holds every mask before the filter
     if ((flags & UMX_FLAG_RESIDUAL) && m->by_target)
         MG_FAIL(UMX_ERR_ARG, "umx_mgpu_separate_track: UMX_FLAG_RESIDUAL is not supported in by-target mode (use by-segment mode)");
+    // the soft mask divides by the sum over EVERY active target's mask x |X|: in by-target mode a rank holds only its own group's masks
+    if ((flags & UMX_FLAG_SOFTMASK) && m->by_target)
+        MG_FAIL(UMX_ERR_ARG, "umx_mgpu_separate_track: UMX_FLAG_SOFTMASK is not supported in by-target mode (use by-segment mode)");
     if (umx_hip_residual_slot(flags) == -2)
         MG_FAIL(UMX_ERR_ARG, "umx_mgpu_separate_track: UMX_FLAG_RESIDUAL needs at least one skipped and one active target");
     if (m->dead)

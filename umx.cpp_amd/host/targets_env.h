@@ -1,7 +1,9 @@
-// targets_env.h -- UMX_TARGETS / UMX_RESIDUAL of umx-cli and umx-batch (Open-Unmix's `--targets` and `--residual`; the reference's
-// CLI always writes all four stems, umx.cpp:75-96): which targets run, and whether one more stem holds the rest of the mix.
+// targets_env.h -- UMX_TARGETS / UMX_RESIDUAL / UMX_SOFTMASK of umx-cli and umx-batch (Open-Unmix's `--targets`, `--residual` and
+// `softmask`; the reference's CLI always writes all four stems, umx.cpp:75-96): which targets run, whether one more stem holds the
+// rest of the mix, and how the first estimates are formed.
 //   UMX_TARGETS=<comma list of bass,drums,other,vocals>   the active targets (default: all four)
 //   UMX_RESIDUAL=1                                        the residual source (UMX_FLAG_RESIDUAL) -> residual.wav
+//   UMX_SOFTMASK=1                                        first estimates X g_j / (eps + sum g) (UMX_FLAG_SOFTMASK); same files
 // Written: target_<t>.wav for every active target and residual.wav; nothing for a silent slot.
 #pragma once
 #include "../../include/umx_hip.h"
@@ -13,7 +15,7 @@
 
 struct umx_target_choice
 {
-    unsigned flags = 0;        // UMX_FLAG_SKIP_TARGET of the targets left out, UMX_FLAG_RESIDUAL
+    unsigned flags = 0;        // UMX_FLAG_SKIP_TARGET of the targets left out, UMX_FLAG_RESIDUAL, UMX_FLAG_SOFTMASK
     bool write[4] = {};        // the slot holds a stem to write ...
     std::string file[4];       // ... under this name
 };
@@ -69,5 +71,8 @@ inline bool umx_targets_from_env(umx_target_choice &c)
         c.write[r] = true;
         c.file[r] = "residual.wav";
     }
+    const char *sv = getenv("UMX_SOFTMASK");
+    if (sv && *sv && atoi(sv) != 0)
+        c.flags |= UMX_FLAG_SOFTMASK;
     return true;
 }

@@ -5,7 +5,7 @@
 // four stems, written to <out dir>/<wav stem>/target_{0..3}.wav.  More than 16 files are taken 16 at a time.
 // Environment: UMX_DEVICE, UMX_NO_WIENER, UMX_WIENER_ITERS, UMX_SHIFT_OFFSET, UMX_RESAMPLE (as umx-cli: files of any rate of
 // 8 .. 192 kHz, mixed rates in one pass through umx_hip_separate_tracks_rate, stems written at each file's rate), UMX_TARGETS and
-// UMX_RESIDUAL (as umx-cli: target_<t>.wav of the chosen targets and residual.wav per file; host/targets_env.h).
+// UMX_RESIDUAL (as umx-cli: target_<t>.wav of the chosen targets and residual.wav per file; host/targets_env.h), UMX_SOFTMASK (as umx-cli).
 #include "../../include/umx_host.h"
 #include "targets_env.h"
 

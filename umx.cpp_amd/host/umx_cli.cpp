@@ -10,6 +10,7 @@
 //                    DESIGN 13); the stems are written at the input's rate and length
 //   UMX_TARGETS=<comma list of bass,drums,other,vocals>   only these targets run and are written (target_<t>.wav)
 //   UMX_RESIDUAL=1   with UMX_TARGETS: residual.wav = everything else in the mix (UMX_FLAG_RESIDUAL; host/targets_env.h)
+//   UMX_SOFTMASK=1   Open-Unmix's softmask=True: first estimates that add up to the mixture (UMX_FLAG_SOFTMASK; host/targets_env.h)
 #include "../../include/umx_host.h"
 #include "targets_env.h"
 
