@@ -291,6 +291,27 @@ int umx_hip_shift_inference_rate(umx_hip_ctx *ctx, const float *audio_host, int 
 int umx_hip_separate_tracks_rate(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *rate,
                                  const int *shift_offset, float *const *out_host, unsigned flags, void (*progress)(float, void *),
                                  void *progress_user);
+/* Shift ensemble: the "shift trick" with K offsets instead of one (Demucs --shifts=K).  ONE track is separated at K
+ * shift offsets, shift k as track lane k of ONE pass over the segments, and the K results are averaged on the device.  With s_k[t] the
+ * `length` frames of stem t that umx_hip_separate_tracks returns for lane k when every lane is given this track, lane k at
+ * shift_offset[k] = offsets[k], with these flags, the result is, per channel and sample, in fp32
+ *     out[t] = (((s_0 + s_1) + s_2) + ... + s_{K-1}) / (float)K
+ * summed left to right in the order of `offsets`, one correctly rounded division.  K = 1 is umx_hip_shift_inference(_rate) with
+ * offsets[0], the same call, on any context; two equal offsets give that single-shift result bit for bit.  The track is uploaded
+ * once (and, at another rate, resampled once), placed into the other lanes device to device, nothing is downloaded before the mean
+ * (taken at 44.1 kHz; its four buffers are resampled back once), and the four stems come back in one download of exactly `length`
+ * frames each.  1 <= n_shifts <= umx_hip_n_tracks(ctx); offsets: n_shifts values in [0, UMX_MAX_SHIFT), duplicates allowed, NULL =
+ * umx_hip_ensemble_offsets(n_shifts, -1); rate: 44100, or 8000 .. 192000 as umx_hip_shift_inference_rate.  Every flag goes to every
+ * lane unchanged, except UMX_FLAG_RESET_SEGMENTS, which is refused (the lanes are taken).  UMX_ERR_ARG for arguments outside this. */
+#define UMX_MAX_SHIFTS UMX_MAX_TRACKS
+/* k-th default offset, host arithmetic, no context: (first + k * (UMX_MAX_SHIFT / n_shifts)) % UMX_MAX_SHIFT; first < 0 means
+ * UMX_REFERENCE_SHIFT.  n_shifts == 1 gives { first }.  UMX_ERR_ARG for n_shifts outside 1 .. UMX_MAX_SHIFTS or first >= UMX_MAX_SHIFT. */
+int umx_hip_ensemble_offsets(int n_shifts, int first, int *offsets_out);
+int umx_hip_shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets,
+                           float *const out_host[4], unsigned flags, void (*progress)(float, void *), void *progress_user);
+/* measuring: milliseconds shift_mean_kernel took in the context's last ensemble call with n_shifts > 1 (device events around its
+ * launch); < 0 when there has been none. */
+float umx_hip_debug_shift_mean_ms(umx_hip_ctx *ctx);
 /* testing, host only: the fp32 tap table of a rate pair (taps[phase * K + d + D]; cap floats at most), its phase count L, taps
  * per phase K and first offset -D.  UMX_ERR_ARG for a bad rate or a too small cap (the sizes are still reported). */
 int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase,

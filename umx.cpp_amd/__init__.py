@@ -201,6 +201,11 @@ def hip_lib():
                                                  C.POINTER(C.c_int), C.POINTER(_fp), C.c_uint, C.c_void_p, C.c_void_p]
     lib.umx_hip_debug_resample_taps.argtypes = [C.c_int, C.c_int, _fp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                 C.POINTER(C.c_int)]
+    lib.umx_hip_ensemble_offsets.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
+    lib.umx_hip_shift_ensemble.argtypes = [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(_fp), C.c_uint,
+                                           C.c_void_p, C.c_void_p]
+    lib.umx_hip_debug_shift_mean_ms.restype = C.c_float
+    lib.umx_hip_debug_shift_mean_ms.argtypes = [C.c_void_p]
     _hip = lib
     return lib
 
@@ -213,6 +218,7 @@ CREATE_U8_DEQUANT = 0x20
 CREATE_GEMM_STAGED = 0x40
 CREATE_GEMM_PLANES = 0x80
 MAX_TRACKS = 64
+MAX_SHIFTS = MAX_TRACKS  # umx_hip_shift_ensemble: one shift per track lane
 MODEL_RATE = 44100
 RESAMPLE_MIN_RATE, RESAMPLE_MAX_RATE = 8000, 192000
 
@@ -232,12 +238,25 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_split_inference", "umx_hip_shift_inference", "umx_hip_debug_lds_guard", "umx_hip_debug_f16_bits",
                "umx_hip_segment_masks_device", "umx_hip_target_mag_device", "umx_hip_segment_finish_device", "umx_hip_gate_reserve", "umx_hip_segment_discard", "umx_hip_pipeline_depth",
                "umx_hip_resampled_length", "umx_hip_resample_device", "umx_hip_shift_inference_rate", "umx_hip_separate_tracks_rate",
-               "umx_hip_debug_resample_taps", "umx_hip_residual_slot", "umx_hip_segment_residual_device"]
+               "umx_hip_debug_resample_taps", "umx_hip_residual_slot", "umx_hip_segment_residual_device",
+               "umx_hip_ensemble_offsets", "umx_hip_shift_ensemble", "umx_hip_debug_shift_mean_ms"]
 
 
 def resampled_length(n, rate_in, rate_out):
     """ceil(n L / M), the natural output length of the device resampler (host arithmetic; < 0 for a bad rate)."""
     return int(hip_lib().umx_hip_resampled_length(int(n), int(rate_in), int(rate_out)))
+
+
+def ensemble_offsets(n_shifts, first=None):
+    """The default offsets of an n_shifts ensemble (umx_hip_ensemble_offsets): (first + k (22050 // n_shifts)) % 22050; first None =
+    the reference's 4033.  Host arithmetic."""
+    if not 1 <= int(n_shifts) <= MAX_SHIFTS:
+        raise UmxError(ERR_ARG, f"ensemble_offsets: n_shifts must be 1 .. {MAX_SHIFTS}")
+    out = (C.c_int * int(n_shifts))()
+    rc = hip_lib().umx_hip_ensemble_offsets(int(n_shifts), -1 if first is None else int(first), out)
+    if rc != 0:
+        raise UmxError(rc, "ensemble_offsets: first must be below 22050")
+    return list(out)
 
 
 GATE_FUNCTIONS = ("tanh_epi", "tanh_hw", "sigmoid_hw", "tanhf", "sigmoid_ref")
@@ -488,6 +507,28 @@ class Engine:
             self._check(self.lib.umx_hip_separate_tracks_rate(self.h, nt, a, (C.c_int * nt)(*Ls), (C.c_int * nt)(*rates), sh, o, flags,
                                                               None, None))
         return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t4] for t4, L in zip(outs, Ls)]
+
+    def separate_ensemble(self, wave, shifts=None, offsets=None, flags=0, rate=MODEL_RATE):
+        """(2,L) host array -> 4 x (2,L): umx_hip_shift_ensemble, the fp32 mean of the track separated at len(offsets) shift offsets,
+        one per track lane of one pass.  offsets None: the default offsets of `shifts` shifts (None = 1: offset 4033)."""
+        wave = np.asarray(wave, np.float32)
+        L = wave.shape[1]
+        a = np.ascontiguousarray(wave.T).ravel()
+        outs = [np.empty(2 * L, np.float32) for _ in range(4)]
+        arr = (_fp * 4)(*[o.ctypes.data_as(_fp) for o in outs])
+        if offsets is None:
+            k, off = (1 if shifts is None else int(shifts)), None
+        else:
+            k, off = len(offsets), (C.c_int * len(offsets))(*[int(o) for o in offsets])
+            if shifts is not None and int(shifts) != k:
+                raise ValueError("separate_ensemble: shifts and len(offsets) disagree")
+        self._check(self.lib.umx_hip_shift_ensemble(self.h, a.ctypes.data_as(_fp), L, int(rate), k, off, arr, flags, None, None))
+        return [np.ascontiguousarray(o.reshape(L, 2).T) for o in outs]
+
+    def shift_mean_ms(self):
+        """shift_mean_kernel's milliseconds in the last separate_ensemble with more than one shift (None: there has been none)."""
+        ms = float(self.lib.umx_hip_debug_shift_mean_ms(self.h))
+        return None if ms < 0 else ms
 
     def resample_device(self, rate_in, rate_out, in_ptrs, n_in, out_ptrs, n_out, hip_stream=None):
         """umx_hip_resample_device: 1 .. 4 device buffers (2,n_in) interleaved -> (2,n_out), queued on hip_stream."""

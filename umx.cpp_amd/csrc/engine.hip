@@ -39,6 +39,7 @@
 #include "wiener_em.h"
 #include "residual_mask.h"
 #include "softmask.h"
+#include "shift_mean.h"
 #include "gate_debug.h"
 
 using namespace umx;
@@ -558,9 +559,9 @@ struct umx_hip_ctx
               void (*progress)(float, void *), void *progress_user);
     // rate == nullptr: every track at 44.1 kHz; else track i is at rate[i] and is resampled to 44.1 kHz and back on the device
     int tracks(int nt, const float *const *audio_host, const int *length, const int *shift_offset, float *const *out_host, unsigned flags,
-               void (*progress)(float, void *), void *progress_user, const int *rate = nullptr);
+               void (*progress)(float, void *), void *progress_user, const int *rate = nullptr, bool ensemble = false);
     int tracks_once(int nt, const float *const *audio_host, const int *length, const int *shift_offset, float *const *out_host,
-                    unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate);
+                    unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate, bool ensemble);
     // resampling (resample.h): the tap table of each (rate_in, rate_out) pair, built once and kept in HBM
     std::map<std::pair<int, int>, float *> rs_taps;
     int resample_plan(int rate_in, int rate_out, ResampleGeom &g, const float **taps_dev);
@@ -647,6 +648,13 @@ struct umx_hip_ctx
             if (!(flags & UMX_FLAG_SKIP_TARGET(tg)))
                 active[nact++] = tg;
     }
+    // shift ensemble (shift_mean.h): `ensemble` of tracks() = the nt lanes are ONE track (audio_host[0], length[0], rate[0])
+    // at nt shift offsets, out_host its 4 stems: one upload, the lanes' stems averaged on the device into ens_out (grow-only), one
+    // download.  Only umx_hip_shift_ensemble with more than one shift touches these.
+    float *ens_out[4] = {};
+    size_t ens_cap = 0;          // frames
+    hipEvent_t ens_ev[2] = {};   // around shift_mean_kernel of the last ensemble (umx_hip_debug_shift_mean_ms)
+    bool ens_timed = false;
 };
 
 #include "engine_init.h"

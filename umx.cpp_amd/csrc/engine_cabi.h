@@ -75,6 +75,9 @@ void umx_hip_destroy(umx_hip_ctx *ctx)
     for (hipEvent_t e : ctx->trk_acc_ev)
         if (e)
             (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->ens_ev)
+        if (e)
+            (void)hipEventDestroy(e);
     if (ctx->order_ev)
         (void)hipEventDestroy(ctx->order_ev);
     if (ctx->copy_stream)
@@ -285,6 +288,74 @@ int umx_hip_shift_inference(umx_hip_ctx *ctx, const float *audio_host, int lengt
     if (offset < 0)
         offset = UMX_REFERENCE_SHIFT; // umx.cpp:115: rand() % 22050, never seeded in the reference (see umx_hip.h)
     return ctx->track(audio_host, length, offset, out_host, flags, progress, progress_user);
+}
+
+// the default offsets of a K-shift ensemble: K steps of MAX_SHIFT / K from `first` on, wrapped into the shift buffer
+int umx_hip_ensemble_offsets(int n_shifts, int first, int *offsets_out)
+{
+    if (n_shifts < 1 || n_shifts > UMX_MAX_SHIFTS || first >= UMX_MAX_SHIFT || !offsets_out)
+        return UMX_ERR_ARG;
+    if (first < 0)
+        first = UMX_REFERENCE_SHIFT;
+    for (int k = 0; k < n_shifts; ++k)
+        offsets_out[k] = (first + k * (UMX_MAX_SHIFT / n_shifts)) % UMX_MAX_SHIFT;
+    return UMX_OK;
+}
+
+// the one track as lanes 0 .. K-1 of the whole-track driver, lane k at offsets[k]; K = 1 IS umx_hip_shift_inference_rate
+int umx_hip_shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets,
+                           float *const out_host[4], unsigned flags, void (*progress)(float, void *), void *progress_user)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!audio_host || !out_host || !out_host[0] || !out_host[1] || !out_host[2] || !out_host[3] || length < 1)
+    {
+        ctx->set_error("shift ensemble: need audio, four outputs and length >= 1");
+        return UMX_ERR_ARG;
+    }
+    if (n_shifts < 1 || n_shifts > UMX_MAX_SHIFTS || n_shifts > ctx->B)
+    {
+        ctx->set_error("shift ensemble: need 1 <= n_shifts <= the context's track count (umx_hip_create_tracks), at most " +
+                       std::to_string(UMX_MAX_SHIFTS));
+        return UMX_ERR_ARG;
+    }
+    if (flags & UMX_FLAG_RESET_SEGMENTS)
+    {
+        ctx->set_error("shift ensemble: UMX_FLAG_RESET_SEGMENTS does not go with it (the track lanes carry the shifts)");
+        return UMX_ERR_ARG;
+    }
+    int off[UMX_MAX_SHIFTS];
+    if (!offsets)
+        (void)umx_hip_ensemble_offsets(n_shifts, -1, off);
+    for (int k = 0; k < n_shifts && offsets; ++k)
+    {
+        if (offsets[k] < 0 || offsets[k] >= UMX_MAX_SHIFT)
+        {
+            ctx->set_error("shift ensemble: offsets must be 0 .. 22049");
+            return UMX_ERR_ARG;
+        }
+        off[k] = offsets[k];
+    }
+    if (n_shifts == 1)
+        return ctx->tracks(1, &audio_host, &length, off, out_host, flags, progress, progress_user, &rate);
+    const float *audio[UMX_MAX_SHIFTS];
+    int lengths[UMX_MAX_SHIFTS], rates[UMX_MAX_SHIFTS];
+    for (int k = 0; k < n_shifts; ++k)
+    {
+        audio[k] = audio_host;
+        lengths[k] = length;
+        rates[k] = rate;
+    }
+    return ctx->tracks(n_shifts, audio, lengths, off, out_host, flags, progress, progress_user, rates, true);
+}
+
+// measuring: shift_mean_kernel's time in the last umx_hip_shift_ensemble call with more than one shift (events around its launch)
+float umx_hip_debug_shift_mean_ms(umx_hip_ctx *ctx)
+{
+    float ms = -1.f;
+    if (!ctx || !ctx->ens_timed || ctx->sync_all() != UMX_OK || hipEventElapsedTime(&ms, ctx->ens_ev[0], ctx->ens_ev[1]) != hipSuccess)
+        return -1.f;
+    return ms;
 }
 
 // testing: the per-bin arithmetic of the Wiener filter -- mix_magnitude, wiener_bin_setup, wiener_bin_apply, the

@@ -21,14 +21,15 @@ int umx_hip_ctx::track(const float *audio_host, int length, int shift_offset, fl
 // idle), the weighted overlap-add and the normalisation run per lane on the device, finished regions are downloaded
 // while later segments run.  nt == 1 is umx_hip_split_inference / umx_hip_shift_inference.
 int umx_hip_ctx::tracks(int nt, const float *const *audio_host, const int *length, const int *shift_offset, float *const *out_host,
-                        unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate)
+                        unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate, bool ensemble)
 {
     // A persistent-kernel timeout inside a track cannot be repaired segment by segment (the overlap-add has consumed
     // the stems): everything is run again, once, with the per-step driver the timeout switches the context to.
     no_recovery = true;
-    int rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate);
-    if (rc == UMX_ERR_TIMEOUT) // (a resampled track is resampled again from its host copy: tracks_once starts from scratch)
-        rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate);
+    int rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate, ensemble);
+    if (rc == UMX_ERR_TIMEOUT) // (a resampled track is resampled again from its host copy, an ensemble placed in its lanes and averaged
+                               // again: tracks_once starts from scratch)
+        rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate, ensemble);
     no_recovery = false;
     pending.clear();
     pending_lost = false;
@@ -36,8 +37,10 @@ int umx_hip_ctx::tracks(int nt, const float *const *audio_host, const int *lengt
 }
 
 int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *length_in, const int *shift_offset, float *const *out_host,
-                             unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate)
+                             unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate, bool ensemble)
 {
+    // ensemble: the caller (umx_hip_shift_ensemble) has repeated the one track's audio pointer, length and rate per lane
+    // and checked the offsets; out_host holds that track's 4 stems
     if (nt < 1 || nt > B || !audio_host || !length_in || !shift_offset || !out_host)
     {
         set_error("tracks: need 1 <= n_tracks <= the context's track count and non-null argument arrays");
@@ -46,8 +49,8 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
     if (int rc = check_flags(flags))
         return rc;
     for (int ln = 0; ln < nt; ++ln)
-        if (!audio_host[ln] || length_in[ln] < 1 || shift_offset[ln] >= UMX_MAX_SHIFT || !out_host[4 * ln] || !out_host[4 * ln + 1] ||
-            !out_host[4 * ln + 2] || !out_host[4 * ln + 3])
+        if (!audio_host[ln] || length_in[ln] < 1 || shift_offset[ln] >= UMX_MAX_SHIFT || !out_host[ensemble ? 0 : 4 * ln] ||
+            !out_host[ensemble ? 1 : 4 * ln + 1] || !out_host[ensemble ? 2 : 4 * ln + 2] || !out_host[ensemble ? 3 : 4 * ln + 3])
         {
             set_error("track: need audio, outputs, length >= 1 and shift offset < 22050");
             return UMX_ERR_ARG;
@@ -86,7 +89,7 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
     // deviation, opt-in.  The segments of a track are then independent, and up to B of them ride as the track lanes of ONE call.
     const bool reset_lanes = (flags & UMX_FLAG_RESET_SEGMENTS) != 0;
     flags &= ~(unsigned)UMX_FLAG_RESET_SEGMENTS;
-    if (reset_lanes && (nt != 1 || !lstm_batched || B < 2))
+    if (reset_lanes && (nt != 1 || !lstm_batched || B < 2 || ensemble))
     {
         set_error("track: UMX_FLAG_RESET_SEGMENTS takes ONE track on a context made by umx_hip_create_tracks with at least 2 lanes");
         return UMX_ERR_ARG;
@@ -147,6 +150,22 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
     if (!trk_acc_ev[0])
         for (int s = 0; s < nslots; ++s)
             UMX_HIP_CHECK(hipEventCreateWithFlags(&trk_acc_ev[s], hipEventDisableTiming));
+    if (ensemble && (size_t)length[0] > ens_cap) // the mean of the lanes' stems: n44 frames, grow-only
+    {
+        for (float *&p : ens_out)
+            if (p)
+            {
+                allocs.erase(std::find(allocs.begin(), allocs.end(), (void *)p));
+                (void)hipFree(p);
+                p = nullptr;
+            }
+        ens_cap = 0;
+        const size_t cap = (size_t)length[0] + (size_t)length[0] / 8;
+        for (float *&p : ens_out)
+            if (int rc = dalloc(&p, 2 * cap, false))
+                return rc;
+        ens_cap = cap;
+    }
     // umx.cpp:167-171: a fresh, zeroed lstm_data per track; umx.cpp:186-195: zeroed accumulators (and F4)
     UMX_HIP_CHECK(hipMemset(state, 0, sizeof(float) * state_floats() * (reset_lanes ? B : nt)));
     clear_used();
@@ -162,7 +181,7 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
     // 44.1 kHz signal (upload_until below then has nothing left to do for it)
     if (rs_stage.size() < (size_t)nt)
         rs_stage.resize(nt);
-    for (int ln = 0; ln < nt; ++ln)
+    for (int ln = 0; ln < (ensemble ? 1 : nt); ++ln) // (an ensemble's one track: staged and resampled once, into lane 0)
     {
         if (!resampled[ln])
             continue;
@@ -188,13 +207,24 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
         float *dst = trk[ln].in + 2 * (size_t)lead[ln];
         UMX_HIP_CHECK(launch_resample(rs_fwd[ln], rs_fwd_taps[ln], 1, &src, length_in[ln], &dst, length[ln], nullptr));
     }
+    // an ensemble's track crosses PCIe once, whole, into lane 0 (unless the resampler has just written it there); the other lanes
+    // get it from lane 0, device to device, behind their own shift's zeros (the memsets above)
+    if (ensemble)
+    {
+        float *first = trk[0].in + 2 * (size_t)lead[0];
+        const size_t bytes = sizeof(float) * 2 * (size_t)length[0];
+        if (!resampled[0])
+            UMX_HIP_CHECK(hipMemcpy(first, audio_host[0], bytes, hipMemcpyHostToDevice));
+        for (int ln = 1; ln < nt; ++ln)
+            UMX_HIP_CHECK(hipMemcpy(trk[ln].in + 2 * (size_t)lead[ln], first, bytes, hipMemcpyDeviceToDevice));
+    }
     UMX_HIP_CHECK(hipDeviceSynchronize());
     // The track goes up segment by segment (round 6): a call needs the samples up to the end of its last segment, and the rest of a
     // pageable upload (14 GB/s: 15 ms for ten minutes of stereo) runs while the device is busy with the segments before it -- the
     // slots' streams do not wait for the null stream, and launches are queued ahead of the copy.
     long long uploaded[LSTMB_MAX_TRACKS] = {}; // host samples of each track already on the device
     for (int ln = 0; ln < nt; ++ln)
-        if (resampled[ln])
+        if (resampled[ln] || ensemble)
             uploaded[ln] = length[ln];
     auto upload_until = [&](int ti, long long padded_end) -> hipError_t { // samples of the padded signal below `padded_end` must be there
         const long long want = std::min<long long>(length[ti], padded_end - lead[ti]);
@@ -285,6 +315,8 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
             rg.start = offset;
             rg.count = (int)std::min<long long>((long long)offset + stride, L2[ti]) - offset;
             hipLaunchKernelGGL(track_normalise_kernel, dim3((rg.count + 255) / 256, 4), dim3(256), 0, st, tk, trk[ti].sumw, rg.start, rg.count);
+            if (ensemble) // nothing is downloaded region by region: the lanes' stems are averaged behind the last segment
+                continue;
             if (hipEventCreateWithFlags(&rg.ready, hipEventDisableTiming) != hipSuccess || hipEventRecord(rg.ready, st) != hipSuccess)
             {
                 cleanup();
@@ -303,7 +335,39 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
     // segment's overlap-add (they are downloaded whole below, not region by region)
     hipError_t cerr = hipSuccess;
     const hipStream_t last_st = slot[last_slot].stream;
-    for (int ln = 0; ln < nt && cerr == hipSuccess; ++ln)
+    if (ensemble)
+    {
+        // Every lane's last overlap-add is ordered before this stream's (trk_acc_ev chains the calls).  The mean of the lanes' `length`
+        // frames from their shifts on goes to ens_out; a resampled track's four means (n44 frames) then go back to the caller's rate
+        // in one launch, as a single resampled track's stems would.
+        ShiftMeanLanes lanes = {};
+        Stems4 mean;
+        for (int t = 0; t < 4; ++t)
+        {
+            for (int ln = 0; ln < nt; ++ln)
+                lanes.src[ln][t] = reinterpret_cast<const float2 *>(trk[ln].out[t]) + lead[ln];
+            mean.p[t] = reinterpret_cast<float2 *>(ens_out[t]);
+        }
+        for (hipEvent_t &e : ens_ev)
+            if (!e)
+                UMX_HIP_CHECK(hipEventCreate(&e));
+        (void)hipEventRecord(ens_ev[0], last_st);
+        launch_shift_mean(lanes, nt, mean, length[0], last_st);
+        (void)hipEventRecord(ens_ev[1], last_st);
+        ens_timed = true;
+        float *const *result = ens_out;
+        if (resampled[0])
+        {
+            const float *src[4] = {ens_out[0], ens_out[1], ens_out[2], ens_out[3]};
+            cerr = launch_resample(rs_back[0], rs_back_taps[0], 4, src, length[0], rs_stage[0].out, length_in[0], last_st);
+            result = rs_stage[0].out;
+        }
+        if (cerr == hipSuccess)
+            cerr = hipStreamSynchronize(last_st);
+        for (int t = 0; t < 4 && cerr == hipSuccess; ++t)
+            cerr = hipMemcpy(out_host[t], result[t], sizeof(float) * 2 * (size_t)length_in[0], hipMemcpyDeviceToHost);
+    }
+    for (int ln = 0; ln < nt && cerr == hipSuccess && !ensemble; ++ln)
         if (resampled[ln])
         {
             const float *src[4];
@@ -328,7 +392,7 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
     }
     cleanup();
     bool synced = false;
-    for (int ln = 0; ln < nt && cerr == hipSuccess; ++ln)
+    for (int ln = 0; ln < nt && cerr == hipSuccess && !ensemble; ++ln)
         if (resampled[ln])
         {
             if (!synced)

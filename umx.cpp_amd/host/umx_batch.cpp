@@ -7,6 +7,7 @@
 // 8 .. 192 kHz, mixed rates in one pass through umx_hip_separate_tracks_rate, stems written at each file's rate), UMX_TARGETS and
 // UMX_RESIDUAL (as umx-cli: target_<t>.wav of the chosen targets and residual.wav per file; host/targets_env.h), UMX_SOFTMASK (as umx-cli).
 #include "../../include/umx_host.h"
+#include "shifts_env.h"
 #include "targets_env.h"
 
 #include <chrono>
@@ -37,6 +38,14 @@ int main(int argc, const char **argv)
     umx_target_choice choice;
     if (!umx_targets_from_env(choice))
         return 1;
+    int shifts = 1;
+    if (!umx_shifts_from_env(shifts))
+        return 1;
+    if (shifts > 1) // (files x shifts in one pass is not offered)
+    {
+        fprintf(stderr, "UMX_SHIFTS=%d: umx-batch runs one FILE per track lane and has none left for shifts; use umx-cli per file\n", shifts);
+        return 1;
+    }
     umx_model *model = nullptr;
     if (umx_model_load(model_file.c_str(), &model, err)) // umx.cpp:63-70
     {

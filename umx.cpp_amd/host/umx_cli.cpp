@@ -11,7 +11,12 @@
 //   UMX_TARGETS=<comma list of bass,drums,other,vocals>   only these targets run and are written (target_<t>.wav)
 //   UMX_RESIDUAL=1   with UMX_TARGETS: residual.wav = everything else in the mix (UMX_FLAG_RESIDUAL; host/targets_env.h)
 //   UMX_SOFTMASK=1   Open-Unmix's softmask=True: first estimates that add up to the mixture (UMX_FLAG_SOFTMASK; host/targets_env.h)
+//   UMX_SHIFTS=<1..64>   Demucs' --shifts: the mean of that many separations at the offsets umx_hip_ensemble_offsets(K, UMX_SHIFT_OFFSET)
+//                    (umx_hip_shift_ensemble; host/shifts_env.h), as track lanes of a context made like umx-batch's (create
+//                    flags 0: UMX_WEIGHTS_RESIDENT and UMX_GEMM do not apply); goes with every knob above except UMX_CLI_PER_SEGMENT.
+//                    1 or unset: one shift, the path and the files of a run without it
 #include "../../include/umx_host.h"
+#include "shifts_env.h"
 #include "targets_env.h"
 
 #include <chrono>
@@ -57,6 +62,19 @@ int main(int argc, const char **argv)
     umx_target_choice choice;
     if (!umx_targets_from_env(choice))
         return 1;
+    int shifts = 1, shift_offsets[UMX_MAX_SHIFTS];
+    if (!umx_shifts_from_env(shifts))
+        return 1;
+    if (shifts > 1 && env_int("UMX_CLI_PER_SEGMENT", 0))
+    {
+        fprintf(stderr, "UMX_SHIFTS=%d: the shifts run as track lanes on the device, UMX_CLI_PER_SEGMENT=1 does not go with it\n", shifts);
+        return 1;
+    }
+    if (shifts > 1 && umx_hip_ensemble_offsets(shifts, env_int("UMX_SHIFT_OFFSET", -1), shift_offsets))
+    {
+        fprintf(stderr, "UMX_SHIFT_OFFSET: need an offset below %d\n", UMX_MAX_SHIFT);
+        return 1;
+    }
     printf("umx-cli (MI355X / gfx950) main driver program\n");
 
     float *audio = nullptr;
@@ -83,8 +101,10 @@ int main(int argc, const char **argv)
            umx_model_data_bytes(model) / 1024.0 / 1024.0, std::chrono::duration<double>(t1 - t0).count());
 
     umx_hip_ctx *ctx = nullptr;
-    if (umx_hip_create(&ctx, env_int("UMX_DEVICE", 0), umx_model_hidden(model), UMX_SEGMENT_SAMPLES,
-                       umx_model_views(model), umx_model_n_tensors(model)))
+    if (shifts > 1 ? umx_hip_create_tracks(&ctx, env_int("UMX_DEVICE", 0), umx_model_hidden(model), UMX_SEGMENT_SAMPLES,
+                                           umx_model_views(model), umx_model_n_tensors(model), 0, shifts) // one track lane per shift
+                   : umx_hip_create(&ctx, env_int("UMX_DEVICE", 0), umx_model_hidden(model), UMX_SEGMENT_SAMPLES,
+                                    umx_model_views(model), umx_model_n_tensors(model)))
     {
         fprintf(stderr, "umx_hip_create: %s\n", umx_hip_last_error(nullptr));
         return 1;
@@ -128,6 +148,14 @@ int main(int argc, const char **argv)
             return 1;
         }
     }
+    else if (shifts > 1)
+    {
+        if (umx_hip_shift_ensemble(ctx, audio, n, rate, shifts, shift_offsets, out, hb.flags, print_progress, nullptr))
+        {
+            fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
+            return 1;
+        }
+    }
     else if (resample ? umx_hip_shift_inference_rate(ctx, audio, n, rate, env_int("UMX_SHIFT_OFFSET", -1), out, hb.flags, print_progress, nullptr)
                       : umx_hip_shift_inference(ctx, audio, n, env_int("UMX_SHIFT_OFFSET", -1), out, hb.flags, print_progress,
                                                 nullptr)) // umx.cpp:72-73
@@ -139,6 +167,8 @@ int main(int argc, const char **argv)
     const double secs = std::chrono::duration<double>(t3 - t2).count();
     printf("Separated %.2f s of audio in %.3f s (%.1fx realtime, host buffers in/out, %s)\n", n / (double)rate, secs,
            n / (double)rate / secs, per_segment ? "one segment at a time" : "track resident in HBM");
+    if (shifts > 1)
+        printf("Mean of %d shifts (offsets %d, %d, ...)\n", shifts, shift_offsets[0], shift_offsets[1]);
 
     std::error_code ec;
     std::filesystem::create_directories(out_dir, ec); // umx.cpp:84-86
