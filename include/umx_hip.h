@@ -312,6 +312,45 @@ int umx_hip_shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length
 /* measuring: milliseconds shift_mean_kernel took in the context's last ensemble call with n_shifts > 1 (device events around its
  * launch); < 0 when there has been none. */
 float umx_hip_debug_shift_mean_ms(umx_hip_ctx *ctx);
+/* Stem mix matrix: weighted sums of the stems and of the input mixture, formed on the device, so that only the outputs
+ * a caller wants cross PCIe -- Open-Unmix's aggregate_dict ("accompaniment" = drums + bass + other), Demucs' --two-stems, karaoke
+ * ("mixture minus vocals", which is NOT the sum of the other three: Wiener stems do not add up to the mix), rebalancing ("vocals -6 dB").
+ * A mix is n_out rows (1 .. UMX_MAX_MIX_OUTPUTS) of five fp32 gains, gains[m * 5 + c]:
+ *     c = 0 .. 3   the four output slots exactly as the unmixed call with the same flags returns them (a residual slot and a skipped
+ *                  target's slot of zeros included)
+ *     c = 4        the input mixture; for a track at another sample rate its 44.1 kHz version (the mix is formed at 44.1 kHz, then
+ *                  the n_out buffers are resampled back)
+ * Per output m, channel and sample, in fp32: the terms are the columns with gains[m][c] != 0.0f in ascending c; each term is the
+ * correctly rounded product g * s_c; the terms are added left to right, one rounding per addition; the first term is the product
+ * itself (not 0 + product); there is no fused multiply-add; a row without a nonzero gain gives +0.0f.  A zero gain (+0 or -0) means
+ * the column is not read: an inf or NaN there does not reach the output.  Gains must be finite, else UMX_ERR_ARG.  The identity
+ * matrix returns the unmixed call's four stems bit for bit; a 0/1 row equals ((s_a + s_b) + s_c) of the downloaded stems in fp32.
+ * Not offered by the multi-GPU driver (umx_mgpu.h), as the ensemble is not. */
+#define UMX_MAX_MIX_OUTPUTS 4
+#define UMX_MIX_COLUMNS 5
+#define UMX_MIX_COLUMN_MIXTURE 4
+/* host arithmetic, no context: the bitmask of the columns with any nonzero gain (bit 4: the mixture); -1 for n_out outside
+ * 1 .. UMX_MAX_MIX_OUTPUTS, gains == NULL or a gain that is not finite */
+int umx_hip_mix_columns(int n_out, const float *gains);
+/* umx_hip_separate_tracks(_rate) with the mix behind it: out_host[n_out * i + m] (2,length[i]) is output m of track i; one matrix for
+ * every lane.  rate == NULL: every track at 44100; shift_offset[i] < 0: split inference; n_tracks == 1 covers umx_hip_split_inference,
+ * _shift_inference and _shift_inference_rate.  At 44.1 kHz the mix of a finished region is formed right behind its normalisation,
+ * over the region's stems, and only the n_out buffers are downloaded, region by region; column 4 is the lane's own copy of the
+ * input (the shift padding is never downloaded).  UMX_FLAG_RESET_SEGMENTS as for the unmixed call. */
+int umx_hip_separate_tracks_mix(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *rate,
+                                const int *shift_offset, int n_out, const float *gains, float *const *out_host, unsigned flags,
+                                void (*progress)(float, void *), void *progress_user);
+/* umx_hip_shift_ensemble with the mix applied to the MEAN (column 4: the track), at 44.1 kHz, before the n_out buffers are
+ * resampled back and downloaded; out_host: n_out buffers (2,length) */
+int umx_hip_shift_ensemble_mix(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets, int n_out,
+                               const float *gains, float *const *out_host, unsigned flags, void (*progress)(float, void *),
+                               void *progress_user);
+/* the kernel on the caller's device buffers, queued on hip_stream (per-segment callers, tests): stems_dev[c] and mix_dev are (2,n)
+ * interleaved, float2-aligned, and may be NULL when no row uses their column (stems_dev itself too); UMX_ERR_ARG when a used
+ * column's pointer is NULL.  Writes exactly n frames of each of the n_out buffers of out_dev.  out_dev[m] == stems_dev[m] is allowed
+ * (every used input of a frame is read before any output of that frame is stored); other overlaps are not. */
+int umx_hip_mix_stems_device(umx_hip_ctx *ctx, int n_out, const float *gains, const float *const stems_dev[4], const float *mix_dev, int n,
+                             float *const *out_dev, void *hip_stream);
 /* testing, host only: the fp32 tap table of a rate pair (taps[phase * K + d + D]; cap floats at most), its phase count L, taps
  * per phase K and first offset -D.  UMX_ERR_ARG for a bad rate or a too small cap (the sizes are still reported). */
 int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase,

@@ -143,6 +143,16 @@ typedef struct umx_target_backend
 int umx_split_inference_targets(const umx_target_backend *be, const umx_p2p *p2p, int rank, int world, const float *audio,
                                 int length, int segment_samples, float *const out[4], char *err);
 
+/* ---- the stem mix matrix in words (include/umx_hip.h): the grammar of umx-cli's and umx-batch's UMX_MIX (host/mix_env.h),
+ *     "vocals=vocals;accompaniment=bass+drums+other;karaoke=mix-vocals;quiet=mix-0.5*vocals"
+ * outputs `name=expr` separated by ';' (1 .. UMX_MAX_MIX_OUTPUTS), expr a sequence of signed terms [+|-][<number>*]<source>, source =
+ * bass | drums | other | vocals | mix | residual; `residual` is column residual_slot (umx_hip_residual_slot of the call's flags), refused
+ * when that is < 0; a source may appear once per expression; names match [A-Za-z0-9_-]{1,63} and are unique.  Fills *n_out, names
+ * (UMX_MAX_MIX_OUTPUTS x UMX_MIX_NAME_LEN bytes, zero-terminated) and gains[m * 5 + c] (UMX_MAX_MIX_OUTPUTS x 5 floats, unused rows
+ * zero).  UMX_ERR_ARG with a message in err that names UMX_MIX and the offending piece; nothing else is written then. */
+#define UMX_MIX_NAME_LEN 64
+int umx_mix_parse(const char *spec, int residual_slot, int *n_out, char *names, float *gains, char *err);
+
 /* Plan of a track: the (offset, length) of every segment split_inference will run (umx.cpp:214-218),
  * used by the multi-GPU scheduler.  Returns the number of segments; fills up to cap entries. */
 int umx_segment_plan(int length, int segment_samples, int *offsets, int *lengths, int cap);

@@ -206,6 +206,13 @@ def hip_lib():
                                            C.c_void_p, C.c_void_p]
     lib.umx_hip_debug_shift_mean_ms.restype = C.c_float
     lib.umx_hip_debug_shift_mean_ms.argtypes = [C.c_void_p]
+    lib.umx_hip_mix_columns.argtypes = [C.c_int, _fp]
+    lib.umx_hip_separate_tracks_mix.argtypes = [C.c_void_p, C.c_int, C.POINTER(_fp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                C.c_int, _fp, C.POINTER(_fp), C.c_uint, C.c_void_p, C.c_void_p]
+    lib.umx_hip_shift_ensemble_mix.argtypes = [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, C.POINTER(_fp),
+                                               C.c_uint, C.c_void_p, C.c_void_p]
+    lib.umx_hip_mix_stems_device.argtypes = [C.c_void_p, C.c_int, _fp, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
+                                             C.c_void_p]
     _hip = lib
     return lib
 
@@ -219,6 +226,7 @@ CREATE_GEMM_STAGED = 0x40
 CREATE_GEMM_PLANES = 0x80
 MAX_TRACKS = 64
 MAX_SHIFTS = MAX_TRACKS  # umx_hip_shift_ensemble: one shift per track lane
+MAX_MIX_OUTPUTS, MIX_COLUMNS, MIX_COLUMN_MIXTURE = 4, 5, 4  # the stem mix matrix: rows of gains over 4 stem slots + the mixture
 MODEL_RATE = 44100
 RESAMPLE_MIN_RATE, RESAMPLE_MAX_RATE = 8000, 192000
 
@@ -239,7 +247,8 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_segment_masks_device", "umx_hip_target_mag_device", "umx_hip_segment_finish_device", "umx_hip_gate_reserve", "umx_hip_segment_discard", "umx_hip_pipeline_depth",
                "umx_hip_resampled_length", "umx_hip_resample_device", "umx_hip_shift_inference_rate", "umx_hip_separate_tracks_rate",
                "umx_hip_debug_resample_taps", "umx_hip_residual_slot", "umx_hip_segment_residual_device",
-               "umx_hip_ensemble_offsets", "umx_hip_shift_ensemble", "umx_hip_debug_shift_mean_ms"]
+               "umx_hip_ensemble_offsets", "umx_hip_shift_ensemble", "umx_hip_debug_shift_mean_ms",
+               "umx_hip_mix_columns", "umx_hip_separate_tracks_mix", "umx_hip_shift_ensemble_mix", "umx_hip_mix_stems_device"]
 
 
 def resampled_length(n, rate_in, rate_out):
@@ -257,6 +266,40 @@ def ensemble_offsets(n_shifts, first=None):
     if rc != 0:
         raise UmxError(rc, "ensemble_offsets: first must be below 22050")
     return list(out)
+
+
+def _mix_gains(gains):
+    """gains as the C calls take them: (n_out, float32[n_out * 5]) from an (n_out, 5) array-like (no checks: the library refuses)."""
+    g = np.ascontiguousarray(np.asarray(gains, np.float32))
+    if g.ndim != 2 or g.shape[1] != MIX_COLUMNS:
+        raise ValueError("mix gains: need an (n_out, 5) matrix: bass, drums, other, vocals slots and the mixture")
+    return g.shape[0], g.ravel()
+
+
+def mix_columns(gains):
+    """umx_hip_mix_columns: the bitmask of the columns of an (n_out, 5) gain matrix with any nonzero gain (bit 4: the mixture).
+    Host arithmetic."""
+    n_out, g = _mix_gains(gains)
+    mask = int(hip_lib().umx_hip_mix_columns(n_out, g.ctypes.data_as(_fp)))
+    if mask < 0:
+        raise UmxError(ERR_ARG, "mix_columns: need 1 .. 4 rows of five finite gains")
+    return mask
+
+
+def mix_parse(spec, residual_slot=-1):
+    """umx_mix_parse: the UMX_MIX grammar ("vocals=vocals;accompaniment=bass+drums+other;karaoke=mix-vocals") ->
+    (names, gains (n_out, 5) float32).  residual_slot: the column `residual` stands for (residual_slot(flags)), -1 = refuse it."""
+    lib = host_lib()
+    n_out = C.c_int(0)
+    names = C.create_string_buffer(MAX_MIX_OUTPUTS * 64)
+    gains = np.zeros(MAX_MIX_OUTPUTS * MIX_COLUMNS, np.float32)
+    err = C.create_string_buffer(256)
+    rc = lib.umx_mix_parse(str(spec).encode(), int(residual_slot), C.byref(n_out), names, gains.ctypes.data_as(_fp), err)
+    if rc != 0:
+        raise HostError(rc, err.value.decode())
+    raw = names.raw
+    return ([raw[64 * m:64 * (m + 1)].split(b"\0", 1)[0].decode() for m in range(n_out.value)],
+            gains.reshape(MAX_MIX_OUTPUTS, MIX_COLUMNS)[:n_out.value].copy())
 
 
 GATE_FUNCTIONS = ("tanh_epi", "tanh_hw", "sigmoid_hw", "tanhf", "sigmoid_ref")
@@ -508,22 +551,59 @@ class Engine:
                                                               None, None))
         return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t4] for t4, L in zip(outs, Ls)]
 
-    def separate_ensemble(self, wave, shifts=None, offsets=None, flags=0, rate=MODEL_RATE):
+    def separate_ensemble(self, wave, shifts=None, offsets=None, flags=0, rate=MODEL_RATE, gains=None):
         """(2,L) host array -> 4 x (2,L): umx_hip_shift_ensemble, the fp32 mean of the track separated at len(offsets) shift offsets,
-        one per track lane of one pass.  offsets None: the default offsets of `shifts` shifts (None = 1: offset 4033)."""
+        one per track lane of one pass.  offsets None: the default offsets of `shifts` shifts (None = 1: offset 4033).
+        gains: an (n_out, 5) mix matrix applied to the mean on the device (umx_hip_shift_ensemble_mix) -> n_out x (2,L)."""
         wave = np.asarray(wave, np.float32)
         L = wave.shape[1]
         a = np.ascontiguousarray(wave.T).ravel()
-        outs = [np.empty(2 * L, np.float32) for _ in range(4)]
-        arr = (_fp * 4)(*[o.ctypes.data_as(_fp) for o in outs])
+        n_out, g = (4, None) if gains is None else _mix_gains(gains)
+        outs = [np.empty(2 * L, np.float32) for _ in range(min(max(n_out, 0), MAX_MIX_OUTPUTS))]
+        arr = (_fp * max(1, len(outs)))(*[o.ctypes.data_as(_fp) for o in outs])
         if offsets is None:
             k, off = (1 if shifts is None else int(shifts)), None
         else:
             k, off = len(offsets), (C.c_int * len(offsets))(*[int(o) for o in offsets])
             if shifts is not None and int(shifts) != k:
                 raise ValueError("separate_ensemble: shifts and len(offsets) disagree")
-        self._check(self.lib.umx_hip_shift_ensemble(self.h, a.ctypes.data_as(_fp), L, int(rate), k, off, arr, flags, None, None))
+        if gains is None:
+            self._check(self.lib.umx_hip_shift_ensemble(self.h, a.ctypes.data_as(_fp), L, int(rate), k, off, arr, flags, None, None))
+        else:
+            self._check(self.lib.umx_hip_shift_ensemble_mix(self.h, a.ctypes.data_as(_fp), L, int(rate), k, off, n_out, g.ctypes.data_as(_fp),
+                                                            arr, flags, None, None))
         return [np.ascontiguousarray(o.reshape(L, 2).T) for o in outs]
+
+    # --- the stem mix matrix (DESIGN 17): weighted sums of the stems and of the input, formed on the device ---
+    def separate_mix(self, wave, gains, flags=0, shift_offset=None, rate=MODEL_RATE):
+        """separate() with an (n_out, 5) gain matrix behind it (umx_hip_separate_tracks_mix, one track): n_out x (2,L), output m =
+        sum_c gains[m][c] * column c, columns 0 .. 3 the stems separate() returns for these arguments, column 4 the input."""
+        if shift_offset is None and rate != MODEL_RATE:
+            shift_offset = 4033  # as separate(): umx_hip_shift_inference_rate's default
+        return self.separate_many_mix([wave], gains, flags, [shift_offset], None if rate == MODEL_RATE else [rate])[0]
+
+    def separate_many_mix(self, waves, gains, flags=0, shift_offsets=None, rates=None):
+        """separate_many() with one gain matrix for every lane: list of (2,L_i) -> list of [n_out x (2,L_i)]."""
+        n_out, g = _mix_gains(gains)
+        nt = len(waves)
+        ins = [np.ascontiguousarray(np.asarray(w, np.float32).T).ravel() for w in waves]
+        Ls = [np.asarray(w).shape[1] for w in waves]
+        outs = [[np.empty(2 * L, np.float32) for _ in range(min(max(n_out, 0), MAX_MIX_OUTPUTS))] for L in Ls]
+        a = (_fp * nt)(*[x.ctypes.data_as(_fp) for x in ins])
+        o = (_fp * max(1, sum(len(t) for t in outs)))(*[x.ctypes.data_as(_fp) for t in outs for x in t])
+        sh = (C.c_int * nt)(*[(-1 if s is None else s) for s in (shift_offsets or [None] * nt)])
+        rt = None if rates is None else (C.c_int * nt)(*[int(r) for r in rates])
+        self._check(self.lib.umx_hip_separate_tracks_mix(self.h, nt, a, (C.c_int * nt)(*Ls), rt, sh, n_out, g.ctypes.data_as(_fp), o, flags,
+                                                         None, None))
+        return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)]
+
+    def mix_stems_device(self, gains, stem_ptrs, mix_ptr, n, out_ptrs, hip_stream=None):
+        """umx_hip_mix_stems_device: the mix kernel on device buffers (2,n) interleaved, queued on hip_stream.  stem_ptrs: 4 device
+        addresses (None / 0 where the column is unused), mix_ptr likewise; out_ptrs: n_out addresses (out_ptrs[m] may be stem_ptrs[m])."""
+        n_out, g = _mix_gains(gains)
+        stems = (C.c_void_p * 4)(*[p or None for p in stem_ptrs])
+        outs = (C.c_void_p * max(1, len(out_ptrs)))(*[p or None for p in out_ptrs])
+        self._check(self.lib.umx_hip_mix_stems_device(self.h, n_out, g.ctypes.data_as(_fp), stems, mix_ptr or None, int(n), outs, hip_stream))
 
     def shift_mean_ms(self):
         """shift_mean_kernel's milliseconds in the last separate_ensemble with more than one shift (None: there has been none)."""
@@ -685,7 +765,7 @@ class Engine:
 HOST_SYMBOLS = ["umx_model_load", "umx_model_free", "umx_model_hidden", "umx_model_n_tensors", "umx_model_views",
                 "umx_model_data_bytes", "umx_model_load_progress", "umx_model_dequantize", "umx_wav_load",
                 "umx_wav_free", "umx_wav_write_f32", "umx_wav_load_rate", "umx_wav_write_f32_rate", "umx_split_inference", "umx_shift_inference",
-                "umx_segment_plan", "umx_transition_weight", "umx_split_inference_carry", "umx_split_inference_targets"]
+                "umx_segment_plan", "umx_transition_weight", "umx_split_inference_carry", "umx_split_inference_targets", "umx_mix_parse"]
 
 SEGMENT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _fp, C.c_int, C.POINTER(_fp))
 RESET_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
@@ -765,6 +845,7 @@ def host_lib():
     lib.umx_split_inference_targets.argtypes = [C.POINTER(TargetBackend), C.POINTER(P2P), C.c_int, C.c_int, _fp, C.c_int, C.c_int,
                                                 C.POINTER(_fp), C.c_char_p]
     lib.umx_segment_plan.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+    lib.umx_mix_parse.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.c_char_p, _fp, C.c_char_p]
     lib.umx_transition_weight.restype = C.c_float
     lib.umx_transition_weight.argtypes = [C.c_int, C.c_int, C.c_int]
     _host = lib

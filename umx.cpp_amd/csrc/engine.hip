@@ -40,6 +40,7 @@
 #include "residual_mask.h"
 #include "softmask.h"
 #include "shift_mean.h"
+#include "stem_mix.h"
 #include "gate_debug.h"
 
 using namespace umx;
@@ -558,10 +559,12 @@ struct umx_hip_ctx
     int track(const float *audio_host, int length, int shift_offset, float *const out_host[4], unsigned flags,
               void (*progress)(float, void *), void *progress_user);
     // rate == nullptr: every track at 44.1 kHz; else track i is at rate[i] and is resampled to 44.1 kHz and back on the device
+    // mix (stem_mix.h): out_host holds mix->n_out buffers per track instead of four, weighted sums of its stems and its input
     int tracks(int nt, const float *const *audio_host, const int *length, const int *shift_offset, float *const *out_host, unsigned flags,
-               void (*progress)(float, void *), void *progress_user, const int *rate = nullptr, bool ensemble = false);
+               void (*progress)(float, void *), void *progress_user, const int *rate = nullptr, bool ensemble = false,
+               const MixSpec *mix = nullptr);
     int tracks_once(int nt, const float *const *audio_host, const int *length, const int *shift_offset, float *const *out_host,
-                    unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate, bool ensemble);
+                    unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate, bool ensemble, const MixSpec *mix);
     // resampling (resample.h): the tap table of each (rate_in, rate_out) pair, built once and kept in HBM
     std::map<std::pair<int, int>, float *> rs_taps;
     int resample_plan(int rate_in, int rate_out, ResampleGeom &g, const float **taps_dev);

@@ -303,14 +303,16 @@ int umx_hip_ensemble_offsets(int n_shifts, int first, int *offsets_out)
 }
 
 // the one track as lanes 0 .. K-1 of the whole-track driver, lane k at offsets[k]; K = 1 IS umx_hip_shift_inference_rate
-int umx_hip_shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets,
-                           float *const out_host[4], unsigned flags, void (*progress)(float, void *), void *progress_user)
+// mix: out_host holds mix->n_out buffers, the mix of the mean
+static int shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets,
+                          float *const *out_host, unsigned flags, void (*progress)(float, void *), void *progress_user, const MixSpec *mix)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
-    if (!audio_host || !out_host || !out_host[0] || !out_host[1] || !out_host[2] || !out_host[3] || length < 1)
+    bool outs = out_host != nullptr;
+    for (int m = 0; outs && m < (mix ? mix->n_out : 4); ++m)
+        outs = out_host[m] != nullptr;
+    if (!audio_host || !outs || length < 1)
     {
-        ctx->set_error("shift ensemble: need audio, four outputs and length >= 1");
+        ctx->set_error(mix ? "shift ensemble: need audio, n_out outputs and length >= 1" : "shift ensemble: need audio, four outputs and length >= 1");
         return UMX_ERR_ARG;
     }
     if (n_shifts < 1 || n_shifts > UMX_MAX_SHIFTS || n_shifts > ctx->B)
@@ -337,7 +339,7 @@ int umx_hip_shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length
         off[k] = offsets[k];
     }
     if (n_shifts == 1)
-        return ctx->tracks(1, &audio_host, &length, off, out_host, flags, progress, progress_user, &rate);
+        return ctx->tracks(1, &audio_host, &length, off, out_host, flags, progress, progress_user, &rate, false, mix);
     const float *audio[UMX_MAX_SHIFTS];
     int lengths[UMX_MAX_SHIFTS], rates[UMX_MAX_SHIFTS];
     for (int k = 0; k < n_shifts; ++k)
@@ -346,7 +348,88 @@ int umx_hip_shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length
         lengths[k] = length;
         rates[k] = rate;
     }
-    return ctx->tracks(n_shifts, audio, lengths, off, out_host, flags, progress, progress_user, rates, true);
+    return ctx->tracks(n_shifts, audio, lengths, off, out_host, flags, progress, progress_user, rates, true, mix);
+}
+int umx_hip_shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets,
+                           float *const out_host[4], unsigned flags, void (*progress)(float, void *), void *progress_user)
+{
+    return ctx ? shift_ensemble(ctx, audio_host, length, rate, n_shifts, offsets, out_host, flags, progress, progress_user, nullptr) : UMX_ERR_ARG;
+}
+
+// ---------------------------------------------------------------- stem mix matrix (stem_mix.h)
+int umx_hip_mix_columns(int n_out, const float *gains) { return mix_spec_from(n_out, gains, nullptr); }
+
+static bool mix_checked(umx_hip_ctx *ctx, int n_out, const float *gains, MixSpec &spec)
+{
+    if (mix_spec_from(n_out, gains, &spec) >= 0)
+        return true;
+    ctx->set_error("mix: need 1 <= n_out <= 4 rows of five finite gains (bass, drums, other, vocals slots, mixture)");
+    return false;
+}
+
+int umx_hip_separate_tracks_mix(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *rate,
+                                const int *shift_offset, int n_out, const float *gains, float *const *out_host, unsigned flags,
+                                void (*progress)(float, void *), void *progress_user)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    MixSpec spec;
+    if (!mix_checked(ctx, n_out, gains, spec))
+        return UMX_ERR_ARG;
+    return ctx->tracks(n_tracks, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate, false, &spec);
+}
+
+int umx_hip_shift_ensemble_mix(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets, int n_out,
+                               const float *gains, float *const *out_host, unsigned flags, void (*progress)(float, void *),
+                               void *progress_user)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    MixSpec spec;
+    if (!mix_checked(ctx, n_out, gains, spec))
+        return UMX_ERR_ARG;
+    return shift_ensemble(ctx, audio_host, length, rate, n_shifts, offsets, out_host, flags, progress, progress_user, &spec);
+}
+
+// the kernel on the caller's device buffers: (2,n) interleaved stems and mixture -> n_out buffers (2,n), queued on hip_stream
+int umx_hip_mix_stems_device(umx_hip_ctx *ctx, int n_out, const float *gains, const float *const stems_dev[4], const float *mix_dev, int n,
+                             float *const *out_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    MixSpec spec;
+    if (!mix_checked(ctx, n_out, gains, spec))
+        return UMX_ERR_ARG;
+    if (n < 1 || !out_dev)
+    {
+        ctx->set_error("mix: need n >= 1 and n_out output buffers");
+        return UMX_ERR_ARG;
+    }
+    const float2 *src[MIX_COLUMNS] = {};
+    float2 *dst[UMX_MAX_MIX_OUTPUTS] = {};
+    for (int c = 0; c < MIX_COLUMNS; ++c)
+    {
+        const float *p = c == MIX_MIXTURE ? mix_dev : (stems_dev ? stems_dev[c] : nullptr);
+        if ((spec.cols >> c & 1u) && !p)
+        {
+            ctx->set_error("mix: a column with a nonzero gain has no buffer");
+            return UMX_ERR_ARG;
+        }
+        src[c] = reinterpret_cast<const float2 *>(p);
+    }
+    for (int m = 0; m < n_out; ++m)
+    {
+        if (!out_dev[m])
+        {
+            ctx->set_error("mix: need n >= 1 and n_out output buffers");
+            return UMX_ERR_ARG;
+        }
+        dst[m] = reinterpret_cast<float2 *>(out_dev[m]);
+    }
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    launch_stem_mix(spec, src, dst, n, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
 }
 
 // measuring: shift_mean_kernel's time in the last umx_hip_shift_ensemble call with more than one shift (events around its launch)

@@ -21,15 +21,16 @@ int umx_hip_ctx::track(const float *audio_host, int length, int shift_offset, fl
 // idle), the weighted overlap-add and the normalisation run per lane on the device, finished regions are downloaded
 // while later segments run.  nt == 1 is umx_hip_split_inference / umx_hip_shift_inference.
 int umx_hip_ctx::tracks(int nt, const float *const *audio_host, const int *length, const int *shift_offset, float *const *out_host,
-                        unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate, bool ensemble)
+                        unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate, bool ensemble,
+                        const MixSpec *mix)
 {
     // A persistent-kernel timeout inside a track cannot be repaired segment by segment (the overlap-add has consumed
     // the stems): everything is run again, once, with the per-step driver the timeout switches the context to.
     no_recovery = true;
-    int rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate, ensemble);
+    int rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate, ensemble, mix);
     if (rc == UMX_ERR_TIMEOUT) // (a resampled track is resampled again from its host copy, an ensemble placed in its lanes and averaged
-                               // again: tracks_once starts from scratch)
-        rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate, ensemble);
+                               // again, a mix formed again from fresh accumulators: tracks_once starts from scratch)
+        rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate, ensemble, mix);
     no_recovery = false;
     pending.clear();
     pending_lost = false;
@@ -37,10 +38,13 @@ int umx_hip_ctx::tracks(int nt, const float *const *audio_host, const int *lengt
 }
 
 int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *length_in, const int *shift_offset, float *const *out_host,
-                             unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate, bool ensemble)
+                             unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate, bool ensemble,
+                             const MixSpec *mix)
 {
     // ensemble: the caller (umx_hip_shift_ensemble) has repeated the one track's audio pointer, length and rate per lane
     // and checked the offsets; out_host holds that track's 4 stems
+    // mix: a checked matrix; a track has n_host = mix->n_out host buffers instead of four, out_host[n_host * lane + m]
+    const int n_host = mix ? mix->n_out : 4;
     if (nt < 1 || nt > B || !audio_host || !length_in || !shift_offset || !out_host)
     {
         set_error("tracks: need 1 <= n_tracks <= the context's track count and non-null argument arrays");
@@ -49,12 +53,16 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
     if (int rc = check_flags(flags))
         return rc;
     for (int ln = 0; ln < nt; ++ln)
-        if (!audio_host[ln] || length_in[ln] < 1 || shift_offset[ln] >= UMX_MAX_SHIFT || !out_host[ensemble ? 0 : 4 * ln] ||
-            !out_host[ensemble ? 1 : 4 * ln + 1] || !out_host[ensemble ? 2 : 4 * ln + 2] || !out_host[ensemble ? 3 : 4 * ln + 3])
+    {
+        bool ok = audio_host[ln] && length_in[ln] >= 1 && shift_offset[ln] < UMX_MAX_SHIFT;
+        for (int m = 0; m < n_host; ++m)
+            ok = ok && out_host[(ensemble ? 0 : n_host * ln) + m];
+        if (!ok)
         {
             set_error("track: need audio, outputs, length >= 1 and shift offset < 22050");
             return UMX_ERR_ARG;
         }
+    }
     // A track at another rate runs as the n44 = ceil(length L / M) frames of its 44.1 kHz version: `length` below is
     // that length, length_in the caller's.
     int length[LSTMB_MAX_TRACKS];
@@ -236,6 +244,21 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
         return e;
     };
 
+    // the mix of `count` frames of lane ln from padded frame `start` on, written over the lane's first n_out stem
+    // accumulators there (stems = those accumulators, or the ensemble's means from frame 0 on); column 4 is the lane's own padded
+    // input at the same index
+    auto queue_mix = [&](int ln, float *const stems[4], size_t stem_start, size_t in_start, int count, hipStream_t st) {
+        const float2 *src[MIX_COLUMNS];
+        float2 *dst[UMX_MAX_MIX_OUTPUTS];
+        for (int t = 0; t < 4; ++t)
+        {
+            src[t] = reinterpret_cast<const float2 *>(stems[t]) + stem_start;
+            dst[t] = reinterpret_cast<float2 *>(stems[t]) + stem_start;
+        }
+        src[MIX_MIXTURE] = reinterpret_cast<const float2 *>(trk[ln].in) + in_start;
+        launch_stem_mix(*mix, src, dst, count, st);
+    };
+
     const float total_reps = std::ceil((float)L2max / (float)stride); // umx.cpp:208 (of the longest track)
     float done = 0.f;
     // A sample is final once the segment that starts at or before it and the one before that have been blended
@@ -317,6 +340,9 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
             hipLaunchKernelGGL(track_normalise_kernel, dim3((rg.count + 255) / 256, 4), dim3(256), 0, st, tk, trk[ti].sumw, rg.start, rg.count);
             if (ensemble) // nothing is downloaded region by region: the lanes' stems are averaged behind the last segment
                 continue;
+            // the region is final: its mix goes over its stems right here, before `ready` (a resampled track is mixed whole, below)
+            if (mix && !resampled[ti])
+                queue_mix(ti, trk[ti].out, (size_t)rg.start, (size_t)rg.start, rg.count, st);
             if (hipEventCreateWithFlags(&rg.ready, hipEventDisableTiming) != hipSuccess || hipEventRecord(rg.ready, st) != hipSuccess)
             {
                 cleanup();
@@ -355,25 +381,29 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
         launch_shift_mean(lanes, nt, mean, length[0], last_st);
         (void)hipEventRecord(ens_ev[1], last_st);
         ens_timed = true;
+        if (mix) // the mix of the MEAN, over the means (column 4: lane 0's copy of the track); what follows handles n_host buffers
+            queue_mix(0, ens_out, 0, (size_t)lead[0], length[0], last_st);
         float *const *result = ens_out;
         if (resampled[0])
         {
             const float *src[4] = {ens_out[0], ens_out[1], ens_out[2], ens_out[3]};
-            cerr = launch_resample(rs_back[0], rs_back_taps[0], 4, src, length[0], rs_stage[0].out, length_in[0], last_st);
+            cerr = launch_resample(rs_back[0], rs_back_taps[0], n_host, src, length[0], rs_stage[0].out, length_in[0], last_st);
             result = rs_stage[0].out;
         }
         if (cerr == hipSuccess)
             cerr = hipStreamSynchronize(last_st);
-        for (int t = 0; t < 4 && cerr == hipSuccess; ++t)
+        for (int t = 0; t < n_host && cerr == hipSuccess; ++t)
             cerr = hipMemcpy(out_host[t], result[t], sizeof(float) * 2 * (size_t)length_in[0], hipMemcpyDeviceToHost);
     }
     for (int ln = 0; ln < nt && cerr == hipSuccess && !ensemble; ++ln)
         if (resampled[ln])
         {
+            if (mix) // the n44 frames are mixed at 44.1 kHz, then its n_host buffers go back
+                queue_mix(ln, trk[ln].out, (size_t)lead[ln], (size_t)lead[ln], length[ln], last_st);
             const float *src[4];
             for (int t = 0; t < 4; ++t)
                 src[t] = trk[ln].out[t] + 2 * (size_t)lead[ln];
-            cerr = launch_resample(rs_back[ln], rs_back_taps[ln], 4, src, length[ln], rs_stage[ln].out, length_in[ln], last_st);
+            cerr = launch_resample(rs_back[ln], rs_back_taps[ln], n_host, src, length[ln], rs_stage[ln].out, length_in[ln], last_st);
         }
     for (const Region &rg : regions) // umx.cpp:136-147: drop the shift
     {
@@ -386,8 +416,8 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
             continue;
         if (cerr == hipSuccess)
             cerr = hipEventSynchronize(rg.ready);
-        for (int t = 0; t < 4 && cerr == hipSuccess; ++t)
-            cerr = hipMemcpy(out_host[4 * ln + t] + 2 * (size_t)(lo - lead[ln]), trk[ln].out[t] + 2 * (size_t)lo,
+        for (int t = 0; t < n_host && cerr == hipSuccess; ++t)
+            cerr = hipMemcpy(out_host[n_host * ln + t] + 2 * (size_t)(lo - lead[ln]), trk[ln].out[t] + 2 * (size_t)lo,
                              sizeof(float) * 2 * (size_t)(hi - lo), hipMemcpyDeviceToHost);
     }
     cleanup();
@@ -398,8 +428,8 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
             if (!synced)
                 cerr = hipStreamSynchronize(last_st);
             synced = true;
-            for (int t = 0; t < 4 && cerr == hipSuccess; ++t)
-                cerr = hipMemcpy(out_host[4 * ln + t], rs_stage[ln].out[t], sizeof(float) * 2 * (size_t)length_in[ln], hipMemcpyDeviceToHost);
+            for (int t = 0; t < n_host && cerr == hipSuccess; ++t)
+                cerr = hipMemcpy(out_host[n_host * ln + t], rs_stage[ln].out[t], sizeof(float) * 2 * (size_t)length_in[ln], hipMemcpyDeviceToHost);
         }
     if (cerr != hipSuccess)
     {

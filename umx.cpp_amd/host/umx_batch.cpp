@@ -5,8 +5,10 @@
 // four stems, written to <out dir>/<wav stem>/target_{0..3}.wav.  More than 16 files are taken 16 at a time.
 // Environment: UMX_DEVICE, UMX_NO_WIENER, UMX_WIENER_ITERS, UMX_SHIFT_OFFSET, UMX_RESAMPLE (as umx-cli: files of any rate of
 // 8 .. 192 kHz, mixed rates in one pass through umx_hip_separate_tracks_rate, stems written at each file's rate), UMX_TARGETS and
-// UMX_RESIDUAL (as umx-cli: target_<t>.wav of the chosen targets and residual.wav per file; host/targets_env.h), UMX_SOFTMASK (as umx-cli).
+// UMX_RESIDUAL (as umx-cli: target_<t>.wav of the chosen targets and residual.wav per file; host/targets_env.h), UMX_SOFTMASK (as umx-cli),
+// UMX_MIX (as umx-cli, host/mix_env.h: the same matrix for every file, <out dir>/<wav stem>/<name>.wav and no target_*.wav).
 #include "../../include/umx_host.h"
+#include "mix_env.h"
 #include "shifts_env.h"
 #include "targets_env.h"
 
@@ -46,6 +48,16 @@ int main(int argc, const char **argv)
         fprintf(stderr, "UMX_SHIFTS=%d: umx-batch runs one FILE per track lane and has none left for shifts; use umx-cli per file\n", shifts);
         return 1;
     }
+    umx_mix_choice mixc;
+    const int mixed = umx_mix_from_env(mixc, (choice.flags & UMX_FLAG_RESIDUAL) ? umx_hip_residual_slot(choice.flags) : -1);
+    if (mixed < 0)
+        return 1;
+    if (mixed && umx_mix_silent_source(mixc, choice.write))
+    {
+        fprintf(stderr, "UMX_MIX: source \"%s\" does not run (UMX_TARGETS) and is not the residual's slot\n", umx_mix_silent_source(mixc, choice.write));
+        return 1;
+    }
+    const int per_file = mixed ? mixc.n_out : 4; // buffers of a file
     umx_model *model = nullptr;
     if (umx_model_load(model_file.c_str(), &model, err)) // umx.cpp:63-70
     {
@@ -86,8 +98,8 @@ int main(int argc, const char **argv)
         // shifts by the same 4033 samples.  Every file here gets that value too (not a fresh draw per batch of lanes),
         // so a file's stems do not depend on where in the argument list it stands; UMX_SHIFT_OFFSET overrides it.
         std::vector<int> n(nb, 0), shift(nb, env_int("UMX_SHIFT_OFFSET", -1) < 0 ? first_rand_shift : env_int("UMX_SHIFT_OFFSET", -1));
-        std::vector<std::vector<float>> stems(4 * nb);
-        std::vector<float *> out(4 * nb);
+        std::vector<std::vector<float>> stems(per_file * nb);
+        std::vector<float *> out(per_file * nb);
         std::vector<const float *> in(nb);
         std::vector<int> rate(nb, UMX_SAMPLE_RATE);
         for (int i = 0; i < nb; ++i)
@@ -101,14 +113,16 @@ int main(int argc, const char **argv)
             }
             in[i] = audio[i];
             audio_secs += n[i] / (double)rate[i];
-            for (int t = 0; t < 4; ++t)
+            for (int t = 0; t < per_file; ++t)
             {
-                stems[4 * i + t].resize((size_t)2 * n[i]);
-                out[4 * i + t] = stems[4 * i + t].data();
+                stems[per_file * i + t].resize((size_t)2 * n[i]);
+                out[per_file * i + t] = stems[per_file * i + t].data();
             }
         }
         const auto t0 = std::chrono::steady_clock::now();
-        if (resample ? umx_hip_separate_tracks_rate(ctx, nb, in.data(), n.data(), rate.data(), shift.data(), out.data(), flags, nullptr, nullptr)
+        if (mixed ? umx_hip_separate_tracks_mix(ctx, nb, in.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out, mixc.gains,
+                                                out.data(), flags, nullptr, nullptr)
+            : resample ? umx_hip_separate_tracks_rate(ctx, nb, in.data(), n.data(), rate.data(), shift.data(), out.data(), flags, nullptr, nullptr)
                      : umx_hip_separate_tracks(ctx, nb, in.data(), n.data(), shift.data(), out.data(), flags, nullptr, nullptr))
         {
             fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
@@ -123,13 +137,13 @@ int main(int argc, const char **argv)
             const std::filesystem::path dir = std::filesystem::path(out_dir) / name;
             std::error_code ec;
             std::filesystem::create_directories(dir, ec);
-            for (int t = 0; t < 4; ++t) // umx.cpp:75-96
+            for (int t = 0; t < per_file; ++t) // umx.cpp:75-96
             {
-                if (!choice.write[t]) // a target that did not run (UMX_TARGETS): a silent slot
+                if (!mixed && !choice.write[t]) // a target that did not run (UMX_TARGETS): a silent slot
                     continue;
-                const std::string p = (dir / choice.file[t]).string();
-                if (resample ? umx_wav_write_f32_rate(p.c_str(), out[4 * i + t], n[i], rate[i], err)
-                             : umx_wav_write_f32(p.c_str(), out[4 * i + t], n[i], err))
+                const std::string p = (dir / (mixed ? mixc.name[t] + ".wav" : choice.file[t])).string();
+                if (resample ? umx_wav_write_f32_rate(p.c_str(), out[per_file * i + t], n[i], rate[i], err)
+                             : umx_wav_write_f32(p.c_str(), out[per_file * i + t], n[i], err))
                 {
                     fprintf(stderr, "%s\n", err);
                     return 1;

@@ -15,7 +15,12 @@
 //                    (umx_hip_shift_ensemble; host/shifts_env.h), as track lanes of a context made like umx-batch's (create
 //                    flags 0: UMX_WEIGHTS_RESIDENT and UMX_GEMM do not apply); goes with every knob above except UMX_CLI_PER_SEGMENT.
 //                    1 or unset: one shift, the path and the files of a run without it
+//   UMX_MIX=<name=expr;...>   the stem mix matrix (grammar in host/mix_env.h): <out dir>/<name>.wav for each of the 1 .. 4
+//                    outputs, weighted sums of the stems and of the input formed on the device, and no target_*.wav; goes with every
+//                    knob above except UMX_CLI_PER_SEGMENT; a source whose target does not run (UMX_TARGETS) is refused.  Unset or
+//                    empty: the path and the files of a run without it
 #include "../../include/umx_host.h"
+#include "mix_env.h"
 #include "shifts_env.h"
 #include "targets_env.h"
 
@@ -75,6 +80,20 @@ int main(int argc, const char **argv)
         fprintf(stderr, "UMX_SHIFT_OFFSET: need an offset below %d\n", UMX_MAX_SHIFT);
         return 1;
     }
+    umx_mix_choice mixc;
+    const int mixed = umx_mix_from_env(mixc, (choice.flags & UMX_FLAG_RESIDUAL) ? umx_hip_residual_slot(choice.flags) : -1);
+    if (mixed < 0)
+        return 1;
+    if (mixed && env_int("UMX_CLI_PER_SEGMENT", 0))
+    {
+        fprintf(stderr, "UMX_MIX: the mix is formed on the device behind the overlap-add, UMX_CLI_PER_SEGMENT=1 does not go with it\n");
+        return 1;
+    }
+    if (mixed && umx_mix_silent_source(mixc, choice.write))
+    {
+        fprintf(stderr, "UMX_MIX: source \"%s\" does not run (UMX_TARGETS) and is not the residual's slot\n", umx_mix_silent_source(mixc, choice.write));
+        return 1;
+    }
     printf("umx-cli (MI355X / gfx950) main driver program\n");
 
     float *audio = nullptr;
@@ -127,7 +146,7 @@ int main(int argc, const char **argv)
     umx_backend be{hip_segment, hip_reset, &hb};
     std::vector<float> stems[4];
     float *out[4];
-    for (int t = 0; t < 4; ++t)
+    for (int t = 0; t < (mixed ? mixc.n_out : 4); ++t)
     {
         stems[t].resize((size_t)2 * n);
         out[t] = stems[t].data();
@@ -145,6 +164,18 @@ int main(int argc, const char **argv)
                                 print_progress, nullptr, err)) // umx.cpp:72-73
         {
             fprintf(stderr, "inference failed: %s\n", err);
+            return 1;
+        }
+    }
+    else if (mixed)
+    {
+        const int offset = env_int("UMX_SHIFT_OFFSET", -1) < 0 ? UMX_REFERENCE_SHIFT : env_int("UMX_SHIFT_OFFSET", -1);
+        if (shifts > 1 ? umx_hip_shift_ensemble_mix(ctx, audio, n, rate, shifts, shift_offsets, mixc.n_out, mixc.gains, out, hb.flags,
+                                                    print_progress, nullptr)
+                       : umx_hip_separate_tracks_mix(ctx, 1, &audio, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixc.gains, out,
+                                                     hb.flags, print_progress, nullptr))
+        {
+            fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
             return 1;
         }
     }
@@ -172,11 +203,11 @@ int main(int argc, const char **argv)
 
     std::error_code ec;
     std::filesystem::create_directories(out_dir, ec); // umx.cpp:84-86
-    for (int t = 0; t < 4; ++t)                       // umx.cpp:75-96
+    for (int t = 0; t < (mixed ? mixc.n_out : 4); ++t) // umx.cpp:75-96
     {
-        if (!choice.write[t]) // a target that did not run (UMX_TARGETS): a silent slot
+        if (!mixed && !choice.write[t]) // a target that did not run (UMX_TARGETS): a silent slot
             continue;
-        const std::string p = (std::filesystem::path(out_dir) / choice.file[t]).string();
+        const std::string p = (std::filesystem::path(out_dir) / (mixed ? mixc.name[t] + ".wav" : choice.file[t])).string();
         printf("Writing wav file %s\n", p.c_str());
         if (resample ? umx_wav_write_f32_rate(p.c_str(), out[t], n, rate, err) : umx_wav_write_f32(p.c_str(), out[t], n, err))
         {
