@@ -315,17 +315,20 @@ template <class K> static const void *kernel_ptr(K *k) { return reinterpret_cast
 //   lstm_persistent_kernel  one track; fp32- and u8-resident W_hh in one kernel (u8 = -1)
 //   lstm_batch_kernel       a group of 16 lanes per launch; lds = the 16-lane worst case (a launch passes what its lanes need)
 //   lstm_batch8_kernel      octets of 8 lanes x column shards of 64 units (lstm_batch8.h): Hl 512 (UMX-L) and 256 (umxhq),
-//                           u8-resident W_hh only; two octets per workgroup in turn: hidden 1024, 33 .. 64 lanes in one launch
+//                           u8-resident W_hh only; two octets per workgroup in turn: hidden 1024, 33 .. 64 lanes in one launch;
+//                           dbg = 1: lstm_batch8_dbg_kernel, the same with the phase profiler and the abort test (the launches that ask for either)
 enum { LSTM_PERSISTENT = 0, LSTM_BATCH, LSTM_BATCH8 };
 struct LstmKernel
 {
     int family, hl, u8, precise, octets;
     const void *fn;
     size_t lds;
+    int dbg = 0;
 };
 #define LSTM_ROW_P(HL, PR) {LSTM_PERSISTENT, HL, -1, PR, 1, kernel_ptr(lstm_persistent_kernel<HL / 8, PR>), 0}
 #define LSTM_ROW_B(HL, U8, PR) {LSTM_BATCH, HL, U8, PR, 1, kernel_ptr(lstm_batch_kernel<HL, U8, PR>), lstmb_lds_bytes(LSTMB_GROUP_TRACKS, lstmb_lanes(LSTMB_GROUP_TRACKS).bulk)}
-#define LSTM_ROW_8(HL, PR, NO) {LSTM_BATCH8, HL, 1, PR, NO, kernel_ptr(lstm_batch8_kernel<HL, PR, NO>), lstm8_lds_bytes(HL, NO)}
+#define LSTM_ROW_8(HL, PR, NO) {LSTM_BATCH8, HL, 1, PR, NO, kernel_ptr(lstm_batch8_kernel<HL, PR, NO>), lstm8_lds_bytes(HL, NO)}, \
+                               {LSTM_BATCH8, HL, 1, PR, NO, kernel_ptr(lstm_batch8_dbg_kernel<HL, PR, NO>), lstm8_lds_bytes(HL, NO), 1}
 #define LSTM_ROWS_P(HL) LSTM_ROW_P(HL, false), LSTM_ROW_P(HL, true)
 #define LSTM_ROWS_B(HL) LSTM_ROW_B(HL, false, false), LSTM_ROW_B(HL, false, true), LSTM_ROW_B(HL, true, false), LSTM_ROW_B(HL, true, true)
 #define LSTM_ROWS_8(HL) LSTM_ROW_8(HL, false, 1), LSTM_ROW_8(HL, true, 1), LSTM_ROW_8(HL, false, 2), LSTM_ROW_8(HL, true, 2)
@@ -340,10 +343,10 @@ static const LstmKernel kLstmKernels[] = {
 #undef LSTM_ROW_8
 #undef LSTM_ROW_B
 #undef LSTM_ROW_P
-static const LstmKernel *lstm_kernel(int family, int hl, bool u8, bool precise, int octets = 1)
+static const LstmKernel *lstm_kernel(int family, int hl, bool u8, bool precise, int octets = 1, bool dbg = false)
 {
     for (const LstmKernel &k : kLstmKernels)
-        if (k.family == family && k.hl == hl && (k.u8 < 0 || k.u8 == (int)u8) && k.precise == (int)precise && k.octets == octets)
+        if (k.family == family && k.hl == hl && (k.u8 < 0 || k.u8 == (int)u8) && k.precise == (int)precise && k.octets == octets && k.dbg == (int)dbg)
             return &k;
     return nullptr;
 }

@@ -636,6 +636,21 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
                 return UMX_ERR_ARG;
             }
             lstm_batch8_ok = per_cu[LSTM_BATCH8] != kNone && per_cu[LSTM_BATCH8] >= 1 && 8 * 32 <= per_cu[LSTM_BATCH8] * cus;
+            if (lstm_batch8_ok)
+            {
+                // lstm_batch8_kernel addresses its streams through buffer resources with 32-bit offsets (lstm_batch8.h): the rows of W_ih x,
+                // which it only loads, up to 2^32 bytes per target; the fp32 rows and the fused planes, which it stores, below
+                // LSTM8_OOR -- the lane offset of a lane with nothing to store, which the range check must drop
+                const unsigned long long rows = (unsigned long long)B * Tp + Mpad;
+                const unsigned long long p_bytes = (unsigned long long)B * Tp * 4ull * H * 4ull, out_bytes = (unsigned long long)B * Tp * 2ull * H * 4ull;
+                const unsigned long long plane_bytes = 2ull * rows * 2ull * H * 2ull;
+                const unsigned long long rs_bytes = 2ull * rows * 4ull; // the row sums, [2 dirs][rows]: stored through LSTM8_OOR bytes as well
+                if (p_bytes >= (1ull << 32) || out_bytes >= LSTM8_OOR || plane_bytes >= LSTM8_OOR || rs_bytes >= LSTM8_OOR)
+                {
+                    set_error("track lanes x segment length exceed the 32-bit addressing of the batched recurrence's streams: fewer lanes or a shorter segment");
+                    return UMX_ERR_ARG;
+                }
+            }
             // the persistent launches of a lstm_batch8 context are lstm_batch8_kernel's: its occupancy decides
             lstm_batch_capacity = per_cu[lstm_batch8_ok ? LSTM_BATCH8 : LSTM_BATCH] * cus;
             // the recurrence writes the plane GEMMs' A operands (layers 1, 2 and fc2's right half) and their row sums itself where

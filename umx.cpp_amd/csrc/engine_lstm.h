@@ -136,7 +136,9 @@ int umx_hip_ctx::run_lstm_layer_batched(Slot &sl, int layer, const int *active, 
     const LstmbLanes ll = lstmb_lanes(octets ? LSTMB_GROUP_TRACKS : std::min(top, span));
     a.nbp = ll.nbp;
     a.bulk = ll.bulk;
-    const LstmKernel *k = octets ? lstm_kernel(LSTM_BATCH8, Hl, true, last_flags & UMX_FLAG_PRECISE_ACT, octs)
+    // (the profiler and the abort test are lstm_batch8_dbg_kernel's: the default kernel's loop carries neither)
+    const bool dbg8 = (last_flags & (UMX_FLAG_LSTM_PROFILE | UMX_FLAG_DEBUG_LSTM_ABORT)) != 0;
+    const LstmKernel *k = octets ? lstm_kernel(LSTM_BATCH8, Hl, true, last_flags & UMX_FLAG_PRECISE_ACT, octs, dbg8)
                                  : lstm_kernel(LSTM_BATCH, Hl, wq, last_flags & UMX_FLAG_PRECISE_ACT);
     const void *fn = k->fn; // (init refused the context if its hidden size has no batched kernel)
     const size_t lds = octets ? k->lds : lstmb_lds_bytes(a.nbp, a.bulk);

@@ -104,11 +104,12 @@ __host__ __device__ inline size_t lstmb_granule_index(int slot, int chain, int k
     return ((((size_t)(slot * 8 + chain) * (Hl / 32) + (k >> 5)) * 4 + ((k & 7) >> 1)) * 4 + ((k & 31) >> 3)) * nbp + n;
 }
 // 16-byte granule store through the granule area's buffer resource.  FAST (all parties share one XCD L2): plain
-// store; SAFE: write-through (sc0 sc1).
+// store; SAFE: write-through (sc0 sc1).  scalar_offset: a wave-uniform part of the address; the range check takes it off the
+// resource's size (in range: byte_offset + 16 <= num_records - scalar_offset), so byte_offset >= num_records is dropped whatever it is.
 typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
-template <bool FAST> __device__ __forceinline__ void granule_store16(__amdgpu_buffer_rsrc_t rs, int byte_offset, uint4 v)
+template <bool FAST> __device__ __forceinline__ void granule_store16(__amdgpu_buffer_rsrc_t rs, int byte_offset, uint4 v, int scalar_offset = 0)
 {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, v), rs, byte_offset, 0, FAST ? 0 : 17);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, v), rs, byte_offset, scalar_offset, FAST ? 0 : 17);
 }
 // One (row, track) of the W_ih x + b_ih ring: 64 gate columns = 256 bytes, stored every LSTMB_RING_PITCH bytes.  The gate
 // lanes of a 16-lane read group differ in the TRACK and read the same 16 bytes of 16 different (row, track) blocks: at a
