@@ -122,10 +122,11 @@ int umx_hip_create(umx_hip_ctx **out, int device, int hidden_size, int segment_s
  * slightly closer; profiles/r02_accuracy_vs_float64.txt).  Rounds 1-2 also carried that fp32-MFMA flavour
  * (UMX_CREATE_GEMM_F32): removed in round 3; the flag is now refused with UMX_ERR_ARG. */
 #define UMX_CREATE_GEMM_F32 0x4u
-/* u8-resident weights (fc1, W_ih; W_hh in the batched LSTM kernel) on the bf16 matrix cores: q - 128 is an integer in
- * [-128, 127] and EXACT in bf16 and fp16, so by default the weight is ONE term (three products with the bf16-split
+/* u8-resident weights (fc1, W_ih; W_hh in the batched LSTM kernel) on the bf16 matrix cores: q - c is an integer of at
+ * most 255 and EXACT in bf16 and fp16 for any centre c in 0 .. 255 (gemm_bf16x3.h: the tensor's zero-weight code round(-o / s);
+ * the plane GEMMs and the batched recurrences: 128), so by default the weight is ONE term (three products with the bf16-split
  * activation instead of six; two with the fp16 planes of csrc/gemm_planes.h) and the affine map of model.cpp:610-616 is applied to the accumulated sum:
- *     sum_k a_k (q_k s + o) = s sum_k a_k (q_k - 128) + (o + 128 s) sum_k a_k.
+ *     sum_k a_k (q_k s + o) = s sum_k a_k (q_k - c) + (o + c s) sum_k a_k.
  * The reference rounds q*s+o to fp32 per weight first; the two differ by exactly that rounding (~1e-7 of the dot
  * product, the size of one fp32 rounding of the sum).  UMX_CREATE_U8_DEQUANT (environment UMX_U8=dequant) keeps the
  * per-weight form (dequantise, split in three, six products): bit-identical to UMX_CREATE_DEQUANTISE_AT_LOAD. */
@@ -480,6 +481,9 @@ int umx_hip_debug_lds_guard(umx_hip_ctx *ctx, int launches, int rounds, unsigned
 /* Testing hook (no GPU needed): the host-side fp32 -> fp16 conversion (round to nearest even, subnormals, overflow to
  * infinity) with which weights are re-encoded as fp16 planes at load time (csrc/gemm_planes.h); returns the 16 bits. */
 unsigned umx_hip_debug_f16_bits(float x);
+/* Testing (no GPU needed): the centre c of a u8 tensor's q - c in gemm_bf16x3's one-plane form (csrc/gemm_common.h quant_centre);
+ * *o2 = offset + c scale, formed in double and rounded once. */
+int umx_hip_debug_quant_centre(float scale, float offset, float *o2);
 
 #ifdef __cplusplus
 }

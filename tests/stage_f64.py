@@ -367,19 +367,22 @@ def describe_block(k, kind, T, run_len=None):
     return f"hop block {k} (samples {k * HOP}..{(k + 1) * HOP - 1})" + (": " + ", ".join(tags) if tags else "")
 
 
-def check(stage, got, ref64, ref32, kind, *, C=C_DEFAULT, floor=FLOOR, where="", T=None, run_len=None):
+def check(stage, got, ref64, ref32, kind, *, C=C_DEFAULT, floor=FLOOR, where="", T=None, run_len=None, yard64=None, gap=(0.0, 0.0)):
     """-> dict with the kernel's and the yardstick's distances to float64 and how far past its bound each is ("excess" <= 1 passes).
     `failure` is None or a message naming the stage, the place (`where`: geometry and lane) and the worst block -- or saying that the
-    float32 evaluation is too far from float64 here to measure the kernel by (YARDSTICK_CAP_*)."""
+    float32 evaluation is too far from float64 here to measure the kernel by (YARDSTICK_CAP_*).
+    yard64: the float64 evaluation the yardstick ref32 is measured against, where that is not ref64 (tests/skewed_weights.py: two
+    float64 references of one stage, one float32 evaluation); gap = (whole segment, worst block): an allowance added to the bounds."""
     rel, blk, k = distances(got, ref64, kind)
-    rel32, blk32, k32 = distances(ref32, ref64, kind)
-    b_rel, b_blk = C * rel32 + floor, C * blk32 + floor
+    rel32, blk32, k32 = distances(ref32, ref64 if yard64 is None else yard64, kind)
+    b_rel, b_blk = C * rel32 + floor + gap[0], C * blk32 + floor + gap[1]
     r = {"stage": stage, "where": where, "rel": rel, "rel32": rel32, "blk": blk, "blk32": blk32, "block": k,
          "ratio_rel": rel / max(rel32, 1e-30), "ratio_blk": blk / max(blk32, 1e-30),
          "excess": max(rel / b_rel, blk / b_blk), "failure": None}
     if not (np.isfinite(np.asarray(got)).all() and r["excess"] <= 1.0):
         T = T if T is not None else (np.asarray(ref64).shape[1] if kind == "spectrum" else np.asarray(ref64).shape[0])
-        r["failure"] = (f"{stage} {where}: rel L2 {rel:.3e} (bound {b_rel:.3e} = {C} x float32's {rel32:.3e} + {floor:g}); worst "
+        r["failure"] = (f"{stage} {where}: rel L2 {rel:.3e} (bound {b_rel:.3e} = {C} x float32's {rel32:.3e} + {floor:g}"
+                        + (f" + gap {gap[0]:.3e}" if gap[0] else "") + "); worst "
                         f"block {blk:.3e} (bound {b_blk:.3e}) at {describe_block(k, kind, T, run_len)}"
                         + ("" if np.isfinite(np.asarray(got)).all() else "; NON-FINITE values"))
     elif not (rel32 <= YARDSTICK_CAP_REL and blk32 <= YARDSTICK_CAP_BLK):

@@ -1,0 +1,193 @@
+"""The offset term of the quantised products on asymmetric weight ranges, without a GPU (tests/skewed_weights.py): every fixture of
+tests/test_gpu_affine_offset.py meets the sharpness and definition-gap conditions, and the float64 check those tests apply has teeth
+-- a numpy emulation of the plane arithmetic FAILS it with the fixed centres 128 / 32896 and with a per-tensor centre whose o + c s
+is formed in fp32, and passes it with the per-tensor centre and the sum formed in double.  On ggml.synth_weights unchanged all three
+forms pass: the suite's other fixtures cannot tell them apart."""
+import numpy as np
+import pytest
+
+import skewed_weights as sw
+import stage_f64 as sf
+import test_gpu_batch
+
+H, T = 128, 64
+STAGES = ("fc1", "lstm", "fc2", "mask")
+
+
+@pytest.fixture(scope="module")
+def ggml(pkg):
+    return pkg.ggml
+
+
+def _emulation_excess(ggml, targets, which=range(4)):
+    """(target, form, stage) -> (excess of the arithmetic check, excess of the parity check) at hidden 128, 64 frames."""
+    out = {}
+    for t in which:
+        acts = sw.cpu_activations(ggml, targets[t], H, T)
+        fns = sw.stage_functions(H, *acts)
+        refs = {k: sw.stage_refs(targets[t], f) for k, f in fns.items()}
+        for form in sw.FORMS:
+            em = sw.emulated_stages(targets[t], H, *acts, form)
+            for k in STAGES:
+                rows = sw.check_both(k, em[k], *refs[k], where=f"[target {t}, {form}]")
+                out[t, form, k] = tuple(r["excess"] for r in rows)
+                assert all((r["failure"] is None) == (r["excess"] <= 1.0) for r in rows), rows  # (the yardstick caps are never the reason)
+    return out
+
+
+@pytest.fixture(scope="module")
+def skewed(ggml, tmp_path_factory):
+    return sw.make_fixture(ggml, "h128_all", tmp_path_factory.mktemp("skewed"))[2]
+
+
+@pytest.fixture(scope="module")
+def skewed_excess(ggml, skewed):
+    return _emulation_excess(ggml, skewed)
+
+
+def test_gap_bound_is_half_the_regression_bound():
+    assert sw.GAP_BOUND == 0.5 * test_gpu_batch.REG_STAGE
+
+
+@pytest.mark.parametrize("name", sorted(sw.FIXTURES))
+def test_every_fixture_is_sharp_and_within_the_definition_gap(ggml, tmp_path, name):
+    """Sharpness from the file (make_fixture asserts it; here also that something IS skewed), the definition gap of every stage on
+    the CPU activations of the fixture, at the usual level and at 30 times it."""
+    Hh, fams, targets = sw.make_fixture(ggml, name, tmp_path)
+    far = [sw.zero_code_distance(r) >= (sw.SHARP_U16 if r["q"].dtype == np.uint16 else sw.SHARP_U8)
+           for d in targets for n, r in d.items() if sw.family(n) is not None]
+    per_target = {"fc1": 1, "fc2": 1, "fc3": 1, "ih": 6, "hh": 6}
+    assert sum(far) == 3 * sum(per_target[f] for f in fams), (name, sum(far))
+    for t in range(4 if Hh == 128 else 1):  # (the wide model serves a bitwise comparison only: one target, 16 frames)
+        for level in (1.0, 30.0):  # (the contexts play one lane at 30 times the level)
+            acts = sw.cpu_activations(ggml, targets[t], Hh, T if Hh == 128 else 16, level=level)
+            gaps = sw.definition_gaps(targets[t], sw.stage_functions(Hh, *acts))
+            print(name, "target", t, "level", level, {k: f"{a:.2e} / {b:.2e}" for k, (a, b) in gaps.items()})
+            sw.assert_gaps(gaps, f"{name}, target {t}, level {level}")
+
+
+def test_lstm_directions_and_targets_carry_different_variants():
+    for layer in range(3):
+        n = f"lstm.weight_hh_l{layer}"
+        for t in range(3):
+            assert {sw.variant(t, n), sw.variant(t, n + "_reverse")} == {"high", "low"}
+        assert sw.variant(0, n) != sw.variant(1, n)
+    assert [sw.variant(t, "fc1.weight") for t in range(4)] == ["high", "low", "low", None]
+    assert sw.variant(2, "fc2.weight") == "high" and sw.variant(0, "bn1.weight") is None
+
+
+def test_exact_affine_weights_differ_from_the_definition_only_by_fp32_rounding(skewed):
+    we, wd = sw.target_weights_exact(skewed[1]), sf.target_weights(skewed[1])
+    for k in we:
+        if sw.family(k) is None:
+            assert we[k] is wd[k]
+        else:
+            assert we[k].dtype == np.float64
+            err = np.abs(we[k] - wd[k]).max()
+            assert 0 < err <= 2.0 ** -23 * np.abs(we[k]).max() * 2, (k, err)
+
+
+def test_centres(skewed):
+    """The per-tensor centre is the zero-weight code, clamped so that q - c stays representable; a degenerate scale keeps 128 / 32896;
+    with the sum formed in double |o + c s| is at most half a code (+ one fp32 rounding of o)."""
+    for name, rec in skewed[0].items():
+        if sw.family(name) is None:
+            continue
+        u16 = rec["q"].dtype == np.uint16
+        s, o = float(rec["scale"]), float(rec["offset"])
+        c, o2 = sw.centre_and_o2(s, o, u16, "recentred_f64")
+        assert abs(c + o / s) <= 0.5 and abs(float(o2)) <= 0.5 * s * (1 + 1e-6), (name, c, o2)
+        assert sw.centre_and_o2(s, o, u16, "fixed")[0] == (sw.U16_CENTRE if u16 else sw.U8_CENTRE)
+    assert sw.centre_and_o2(1.0, 10.0, False, "recentred_f64")[0] == 0
+    assert sw.centre_and_o2(1.0, -1000.0, False, "recentred_f64")[0] == 255
+    assert sw.centre_and_o2(1.0, 5.0, True, "recentred_f64")[0] == 31
+    assert sw.centre_and_o2(1.0, -70000.0, True, "recentred_f64")[0] == 65504
+    for s in (0.0, np.inf, np.nan):
+        assert sw.centre_and_o2(s, 1.0, False, "recentred_f64")[0] == 128
+        assert sw.centre_and_o2(s, 1.0, True, "recentred_f32")[0] == 32896
+
+
+def test_plane_product_is_the_affine_product(skewed):
+    """Whatever the centre, the emulated product is the affine product to fp32 accuracy of its two terms (the identity holds)."""
+    rng = np.random.default_rng(1)
+    for name in ("fc2.weight", "lstm.weight_ih_l1_reverse"):
+        rec = skewed[2][name]
+        a = rng.standard_normal((5, rec["q"].shape[1])).astype(np.float32)
+        ref = a.astype(np.float64) @ sw.target_weights_exact(skewed[2])[name].T
+        for form in sw.FORMS:
+            got = sw.plane_product(a, rec["q"], rec["scale"], rec["offset"], form)
+            assert np.abs(got - ref).max() <= 1e-4 * np.abs(ref).max(), (name, form)
+
+
+def test_the_check_fails_the_fixed_centres(skewed_excess):
+    """c = 128 / 32896: fc1 of every skewed target is more than ten times outside the arithmetic bound AND the parity bound (K = 2974,
+    positive inputs); where the outlier sits at 25 sigma (target 0: "high") so are fc2 and the mask, by more than 1.5 times."""
+    for t in range(3):
+        assert min(skewed_excess[t, "fixed", "fc1"]) > 10, (t, skewed_excess[t, "fixed", "fc1"])
+    for k in ("fc2", "mask"):
+        assert min(skewed_excess[0, "fixed", k]) > 1.5, (k, skewed_excess[0, "fixed", k])
+
+
+def test_the_check_fails_a_per_tensor_centre_with_the_offset_formed_in_fp32(skewed_excess):
+    """The rounding of c s in fp32 is multiplied by the row sum again: fc1 of every skewed target fails, twice outside its bounds
+    for the "low" ones (targets 1 and 2)."""
+    for t in range(3):
+        assert skewed_excess[t, "recentred_f32", "fc1"][0] > 1.0, (t, skewed_excess[t, "recentred_f32", "fc1"])
+    for t in (1, 2):
+        assert min(skewed_excess[t, "recentred_f32", "fc1"]) > 2, (t, skewed_excess[t, "recentred_f32", "fc1"])
+
+
+def test_the_check_passes_the_per_tensor_centre_with_the_offset_formed_in_double(skewed_excess):
+    for t in range(4):
+        for k in STAGES:
+            arith, parity = skewed_excess[t, "recentred_f64", k]
+            assert arith <= 0.5 and parity <= 0.5, (t, k, arith, parity)
+
+
+def test_the_control_target_passes_under_every_form(skewed_excess):
+    for form in sw.FORMS:
+        for k in STAGES:
+            assert max(skewed_excess[sw.CONTROL_TARGET, form, k]) <= 1.0, (form, k)
+
+
+def test_plain_synthetic_weights_cannot_tell_the_forms_apart(ggml, tmp_path):
+    """ggml.synth_weights unchanged: all three forms pass every stage -- the reason the suite has been blind."""
+    path = str(tmp_path / "plain.bin")
+    ggml.write_model(path, ggml.synth_weights(H, seed=3), H, compress=False)
+    targets = ggml.read_model(path)[1]
+    sw.assert_sharp(targets, ())
+    ex = _emulation_excess(ggml, targets, which=(0, 1))
+    for key, (arith, parity) in ex.items():
+        assert arith <= 1.0 and parity <= 1.0, (key, arith, parity)
+
+
+def test_the_engine_s_quant_centre_is_the_numpy_form(pkg, skewed):
+    """csrc/gemm_common.h quant_centre through umx_hip_debug_quant_centre (host code, no GPU): the centre and the BITS of o + c s of
+    skewed_weights.centre_and_o2(..., "recentred_f64") for the fixture's u8 tensors, random (scale, offset) pairs, both clamps, exact
+    ties, and the degenerate scales and offsets that keep 128."""
+    import ctypes
+    lib = pkg.hip_lib()
+
+    def engine(s, o):
+        o2 = ctypes.c_float()
+        c = lib.umx_hip_debug_quant_centre(float(s), float(o), ctypes.byref(o2))
+        return c, np.float32(o2.value)
+
+    rng = np.random.default_rng(2)
+    pairs = [(r["scale"], r["offset"]) for d in skewed for n, r in d.items() if sw.family(n) is not None and r["q"].dtype == np.uint8]
+    pairs += [(np.float32(s), np.float32(-s * z)) for s, z in zip(rng.uniform(1e-4, 1e-1, 200), rng.uniform(-40, 300, 200))]
+    pairs += [(np.float32(1.0), np.float32(o)) for o in (10.0, 0.0, -0.5, -1.5, -2.5, -254.5, -255.0, -255.5, -1000.0)]
+    pairs += [(np.float32(-0.25), np.float32(3.0)), (np.float32(1e-30), np.float32(1.0)), (np.float32(1e30), np.float32(-1e30))]
+    for s, o in pairs:
+        c, o2 = engine(s, o)
+        wc, wo2 = sw.centre_and_o2(s, o, False, "recentred_f64")
+        assert c == wc and o2.view(np.uint32) == wo2.view(np.uint32), (s, o, c, wc, o2, wo2)
+        assert 0 <= c <= 255
+    assert engine(1.0, 10.0)[0] == 0 and engine(1.0, -1000.0)[0] == 255 and engine(1.0, -2.5)[0] == 2  # clamps; ties to even
+    with np.errstate(invalid="ignore", over="ignore"):
+        for s, o in ((0.0, 1.0), (-0.0, 1.0), (np.inf, 1.0), (-np.inf, 1.0), (np.nan, 1.0), (0.5, np.inf), (0.5, np.nan)):
+            assert engine(s, o)[0] == 128, (s, o)
+        for s in (0.0, np.inf):
+            c, o2 = engine(s, 1.0)
+            want = np.float32(np.float64(1.0) + 128.0 * np.float64(s))
+            assert o2.view(np.uint32) == want.view(np.uint32), (s, o2, want)

@@ -68,13 +68,15 @@ inline int gemm_weight(int mode, int layer) { return mode == G_FC1 ? W_FC1 : mod
 // One GEMM weight in HBM, [N][K] per plane.  Plane flavour (gemm_planes.h): `form` fp16 planes -- u8 as 1 exact plane of q - 128,
 // u16 as 2 planes whose sum is exactly q - 32896 (fp16(q - 32896) and the remainder, an integer of at most 16), fp32 as 2 split
 // terms of w / s with s a power of two; (s, o) = (scale, offset + c scale), or (s, 0).  Staged flavour (gemm_bf16x3.h): `form` is
-// the GemmBType -- BQ_U8 / BQ_U16 = the ggml file's bytes (BASELINE config 5) with (scale, offset), BQ_F32 = three bf16 planes
-// with (1, 0).  Two (s, o) pairs because W_ih of a layer is two file tensors (forward rows, then reverse rows).
+// the GemmBType -- BQ_U8 / BQ_U16 = the ggml file's bytes (BASELINE config 5) with (scale, offset) and, for the u8 one-plane form,
+// (c, o2) = (the tensor's centre, offset + c scale: quant_centre, gemm_common.h); BQ_F32 = three bf16 planes with (1, 0).  Two of
+// each because W_ih of a layer is two file tensors (forward rows, then reverse rows).
 struct GemmWeight
 {
     const void *p = nullptr;
     int form = 0;
     float s[2] = {1.f, 1.f}, o[2] = {0.f, 0.f};
+    float c[2] = {128.f, 128.f}, o2[2] = {0.f, 0.f};
 };
 
 struct TargetBufs // weights of one target (shared by both pipeline slots)

@@ -63,6 +63,13 @@ int umx_hip_pipeline_depth(const umx_hip_ctx *ctx) { return ctx ? ctx->nslots : 
 int umx_hip_lstm_is_batched(const umx_hip_ctx *ctx) { return ctx && ctx->lstm_batched ? 1 : 0; }
 
 unsigned umx_hip_debug_f16_bits(float x) { return f16_rne_bits(x); }
+int umx_hip_debug_quant_centre(float scale, float offset, float *o2)
+{
+    const QuantCentre qc = quant_centre(scale, offset);
+    if (o2)
+        *o2 = qc.o2;
+    return qc.c;
+}
 
 void umx_hip_destroy(umx_hip_ctx *ctx)
 {

@@ -226,6 +226,13 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
             }
             if (!gemm_planes)
             {
+                // the u8 one-plane form of gemm_bf16x3.h: the centre of each source tensor and offset + c scale (gemm_common.h)
+                for (int s = 0; s < d.nsrc && esz == 1; ++s)
+                {
+                    const QuantCentre qc = quant_centre(w.s[s], w.o[s]);
+                    w.c[s] = (float)qc.c;
+                    w.o2[s] = qc.o2;
+                }
                 w.form = esz == 1 ? BQ_U8 : BQ_U16;
                 return upload_weight(w, qh.data(), qh.size());
             }

@@ -42,6 +42,8 @@ void umx_hip_ctx::launch_gemm(Lane &sl, hipStream_t st, int mode, int layer, con
         t.Bq = w.p; // (t.B, the fp32 matrix of an earlier flavour, stays null)
         t.bs[0] = w.s[0]; t.bs[1] = w.s[1];
         t.bo[0] = w.o[0]; t.bo[1] = w.o[1];
+        t.bc[0] = w.c[0]; t.bc[1] = w.c[1];
+        t.bo2[0] = w.o2[0]; t.bo2[1] = w.o2[1];
         t.bsplit = mode == G_IH ? 2 * H : 0x7fffffff; // W_ih rows >= 4*Hl belong to the reverse direction's tensor
         bq = w.form; // the same for every target (one loader decision for all four)
     }

@@ -59,15 +59,15 @@ __device__ __forceinline__ void split3(const float (&x)[8], uint4 &p1, uint4 &p2
     p3 = make_uint4(o3[0], o3[1], o3[2], o3[3]);
 }
 
-// 8 u8 weights -> 8 bf16 values q - 128 (integers in [-128, 127] are exact in bf16: the fp32 value's upper half)
-__device__ __forceinline__ uint4 u8x8_to_bf16_centered(unsigned lo, unsigned hi)
+// 8 u8 weights -> 8 bf16 values q - c, c an integer in [0, 255] (integers of at most 255 are exact in bf16: the fp32 value's upper half)
+__device__ __forceinline__ uint4 u8x8_to_bf16_centered(unsigned lo, unsigned hi, float c)
 {
     unsigned o[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
     {
         const unsigned src = i < 2 ? lo : hi;
-        const float f0 = (float)((src >> (16 * (i & 1))) & 255u) - 128.0f, f1 = (float)((src >> (16 * (i & 1) + 8)) & 255u) - 128.0f;
+        const float f0 = (float)((src >> (16 * (i & 1))) & 255u) - c, f1 = (float)((src >> (16 * (i & 1) + 8)) & 255u) - c;
         o[i] = (__float_as_uint(f0) >> 16) | (__float_as_uint(f1) & 0xffff0000u);
     }
     return make_uint4(o[0], o[1], o[2], o[3]);
@@ -99,10 +99,10 @@ __host__ inline void split3_host(float x, unsigned short &p1, unsigned short &p2
     p3 = bf16_rne_bits(r2);
 }
 
-// BQ_U8X (u8-resident weights, the default for them): q - 128 is an integer in [-128, 127], EXACT in bf16, so the
-// weight needs ONE plane and the product three MFMAs (a1 + a2 + a3).(q - 128) instead of six; the affine map of
-// model.cpp:610-616 moves out of the dot product:
-//     sum_k a_k (q_k s + o) = s * sum_k a_k (q_k - 128) + (o + 128 s) * sum_k a_k
+// BQ_U8X (u8-resident weights, the default for them): q - c (c = the tensor's zero-weight code, quant_centre in gemm_common.h) is an
+// integer of at most 255, EXACT in bf16, so the weight needs ONE plane and the product three MFMAs (a1 + a2 + a3).(q - c) instead
+// of six; the affine map of model.cpp:610-616 moves out of the dot product:
+//     sum_k a_k (q_k s + o) = s * sum_k a_k (q_k - c) + (o + c s) * sum_k a_k
 // The row sums of A come for free from the staging threads (each already holds its 8 values of the K tile).  Half
 // the matrix-core time, a third less LDS traffic, no dequantise-and-split VALU work for B.  Against the reference's
 // per-weight rounding of q*s+o this differs by that rounding: ~1e-7 of the dot product, one fp32 rounding of the
@@ -145,6 +145,7 @@ template <int MODE, int BQ> __global__ __launch_bounds__(256, 2) void gemm_bf16x
     const int soffA0 = m0 * lda * 4, soffB0 = n0 * K * BEL;
     const int plane_stride = args.N * K * 2; // bytes between pre-split B planes
     const float bsc = tg.bs[n0 >= tg.bsplit ? 1 : 0], bof = tg.bo[n0 >= tg.bsplit ? 1 : 0]; // block-uniform
+    const float bctr = tg.bc[n0 >= tg.bsplit ? 1 : 0]; // BQ_U8X: the centre of q - c
     const int st_lds = st_row * BX_ROW_BYTES + st_half * 16;
 
     float4 ra0, ra1, rs0, rs1, rm0, rm1;
@@ -195,7 +196,7 @@ template <int MODE, int BQ> __global__ __launch_bounds__(256, 2) void gemm_bf16x
         *reinterpret_cast<uint4 *>(base + BX_PLANE_BYTES) = p2;                                        \
         *reinterpret_cast<uint4 *>(base + 2 * BX_PLANE_BYTES) = p3;                                    \
         if (BQ == BQ_U8X)                                                                              \
-            *reinterpret_cast<uint4 *>(base + BX_OPERAND_BYTES) = u8x8_to_bf16_centered(rb1.x, rb1.y); \
+            *reinterpret_cast<uint4 *>(base + BX_OPERAND_BYTES) = u8x8_to_bf16_centered(rb1.x, rb1.y, bctr); \
         else if (BQ == BQ_F32)                                                                         \
         {                                                                                              \
             *reinterpret_cast<uint4 *>(base + BX_OPERAND_BYTES) = rb1;                                 \
@@ -278,12 +279,12 @@ template <int MODE, int BQ> __global__ __launch_bounds__(256, 2) void gemm_bf16x
     BX_COMPUTE((nk - 1) & 1)
     if (BQ == BQ_U8X)
     {
-        // acc = sum a (q - 128)  ->  W x = s * acc + (o + 128 s) * rowsum(A).  The two k-halves of every row meet in
+        // acc = sum a (q - c)  ->  W x = s * acc + (o + c s) * rowsum(A).  The two k-halves of every row meet in
         // the LDS buffer the last tile did not use.
         float *rs = reinterpret_cast<float *>(bx_smem + (nk & 1) * BX_BUF_BYTES);
         rs[st_half * 128 + st_row] = rowsum;
         __syncthreads();
-        const float o2 = bof + 128.0f * bsc;
+        const float o2 = tg.bo2[n0 >= tg.bsplit ? 1 : 0];
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
