@@ -479,11 +479,16 @@ int umx_hip_debug_lstm_placement(umx_hip_ctx *ctx, unsigned long long *out, int 
  * into another workgroup's LDS. */
 int umx_hip_debug_lds_guard(umx_hip_ctx *ctx, int launches, int rounds, unsigned *out2);
 /* Testing hook (no GPU needed): the host-side fp32 -> fp16 conversion (round to nearest even, subnormals, overflow to
- * infinity) with which weights are re-encoded as fp16 planes at load time (csrc/gemm_planes.h); returns the 16 bits. */
+ * infinity) with which weights are re-encoded as fp16 planes at load time (csrc/quant_planes.h); returns the 16 bits. */
 unsigned umx_hip_debug_f16_bits(float x);
-/* Testing (no GPU needed): the centre c of a u8 tensor's q - c in gemm_bf16x3's one-plane form (csrc/gemm_common.h quant_centre);
+/* Testing (no GPU needed): the centre c of a u8 tensor's q - c in gemm_bf16x3's one-plane form (csrc/quant_planes.h quant_centre);
  * *o2 = offset + c scale, formed in double and rounded once. */
 int umx_hip_debug_quant_centre(float scale, float offset, float *o2);
+/* Testing (no GPU needed): the n codes q (elem_size 1: u8, 2: u16) of a file tensor with (scale, offset) as the plane GEMMs of
+ * track-batched contexts hold them (csrc/quant_planes.h quant_planes): hi[n] = the fp16 bits of q - c and, for u16, lo[n] = the fp16
+ * bits of the remainder (lo may be NULL for u8).  Returns the tensor's centre c (u8: 0 .. 255, u16: 31 .. 65504; 128 / 32896 for a
+ * zero or non-finite scale), or -1 for a bad argument; *o2 = offset + c scale, formed in double and rounded once. */
+int umx_hip_debug_quant_planes(const void *q, int elem_size, int n, float scale, float offset, unsigned short *hi, unsigned short *lo, float *o2);
 
 #ifdef __cplusplus
 }

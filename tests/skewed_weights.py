@@ -38,7 +38,7 @@ FAMILIES = ("fc1", "ih", "hh", "fc2", "fc3")
 ALL = frozenset(FAMILIES)
 HIGH, LOW = (-4.0, 25.0), (-14.0, 4.0)
 RANGES = {"high": HIGH, "low": LOW}
-U8_CENTRE, U16_CENTRE = 128, 32896           # the centres the kernels used for every tensor before the per-tensor centre
+U8_CENTRE, U16_CENTRE = 128, 32896           # the centres of every tensor before the per-tensor centre (W_hh in the batched recurrences: still)
 SHARP_U8, SHARP_U16 = 64.0, 16384.0          # codes between the zero-weight code and those centres: a quarter of the code range
 GAP_BOUND = 0.5 * 5e-6                       # half of tests/test_gpu_batch.py REG_STAGE (asserted equal in test_affine_offset_cpu.py)
 CONTROL_TARGET = 3                           # stays as ggml.synth_weights drew it
@@ -116,7 +116,10 @@ def skewed_weights(ggml, weights, families=ALL, seed=0):
 FIXTURES = {
     "h128_all": (128, 3, ALL, 5),
     "h128_hh": (128, 3, frozenset({"hh"}), 6),
-    "h512_all": (512, 81, ALL, 9),  # (the bitwise comparison of the plane-GEMM flavours, which needs 256 x 256 tiles)
+    "h512_all": (512, 81, ALL, 9),  # 256 x 256 tiles (W_ih, fc3) and lstm_batch8_kernel at K = 256; also the bitwise comparison of the flavours
+    "h1024_all": (1024, 81, ALL, 9),  # UMX-L's width: lstm_batch8_kernel at K = 512
+    "h512_hh": (512, 81, frozenset({"hh"}), 9),  # only W_hh skewed: the batched recurrences' own offset term (centre 128) at its real K
+    "h1024_hh": (1024, 81, frozenset({"hh"}), 9),
 }
 
 

@@ -10,12 +10,19 @@ Each stage is compared twice (skewed_weights.check_both), its references compute
 the yardstick is the float32 evaluation of the definition against the definition's float64, with stage_f64's caps.
 tests/test_affine_offset_cpu.py shows on a numpy emulation that this check fails the fixed centres and passes the per-tensor one.
 
-Covered here: the one-track context (gemm_bf16x3_kernel's u8 one-plane form, which centres every tensor at its zero-weight code);
-the per-weight form of a three-lane context (UMX_CREATE_U8_DEQUANT); lstm_batch_kernel's u8-resident W_hh on a model with only W_hh
-skewed (first segment, carried state, FLAG_PRECISE_ACT); and gemm_planes_kernel / _pp_kernel / _ps_kernel on 256 x 256 tiles bit for
-bit on the fully skewed hidden-512 model (W_ih and fc3; each flavour asserted by kernel name).
-The plane GEMMs (and W_ih through them) of track-batched contexts still centre at 128 / 32896 and do NOT meet the float64 check on
-skewed fc1 / W_ih / fc2 / fc3 (DESIGN 5 has the figures); those cases -- and hidden 512 / 1024 -- come with their centres.
+Covered here, every case with the kernels asserted by name:
+  * the one-track context (gemm_bf16x3_kernel's u8 one-plane form, which centres every tensor at its zero-weight code);
+  * the plane GEMMs of track-batched contexts, whose planes hold q - c with each source tensor's own centre since load_weight
+    forms them with csrc/quant_planes.h, on the fully skewed models: hidden 128 at three lanes (gemm_planes_kernel's 128 x 128 tiles,
+    lstm_batch_kernel; first segment and carried state), hidden 512 at ten lanes and hidden 1024 at nine (fc1 u8 and fc2 u16 on the
+    128 x 128 tiles, W_ih u8 and fc3 u16 on gemm_planes_ps_kernel's 256 x 256 tiles, lstm_batch8_kernel);
+  * gemm_planes_kernel / _pp_kernel / _ps_kernel on 256 x 256 tiles bit for bit on the fully skewed hidden-512 model, which ties the
+    other two flavours to the one checked against float64;
+  * the per-weight form of a three-lane context (UMX_CREATE_U8_DEQUANT);
+  * the batched recurrences' own W_hh offset term, which keeps the centre 128, on models with only W_hh skewed:
+    lstm_batch_kernel at K = 64 (first segment, carried state, FLAG_PRECISE_ACT), lstm_batch8_kernel at K = 256 (hidden 512, ten
+    lanes) and K = 512 (hidden 1024: nine lanes = one octet and a lane, 40 lanes = two octets per workgroup in turn), each on the
+    first segment and from a carried state.
 
 UMX_STAGE_F64_REPORT=<file>: append every check's distances to that file (JSON lines), as tests/test_gpu_geometry_f64.py does."""
 import numpy as np
@@ -75,27 +82,41 @@ def _state(eng, lane):
     return eng.track_stream_get(lane)
 
 
-def _three_lane_case(pkg, targets, test, *, flags=0, carried=False, check_lanes=(0, 1, 2), u8_dequant=False):
-    """hidden 128, three lanes, T = 41: lane 1 at 30 times the level (the adaptive row scale multiplies the offset term), lane 2 at
-    1e-5 of it.  carried: two calls, the second checked from the state the first left."""
-    N = sf._N(41, 517)
+def _lanes_case(pkg, targets, test, *, hidden, lanes, T, lstm_kernel, gemm_kernels, check_lanes, which=range(4), flags=0, carried=False,
+                u8_dequant=False, loud=(1,), quiet=(2,)):
+    """`lanes` lanes of a track-batched context: the lanes of `loud` at 30 times the level (the adaptive row scale multiplies the
+    offset term), those of `quiet` at 1e-5 of it.  carried: two calls, the second checked from the state the first left.
+    gemm_kernels: the kernel of fc1, W_ih, fc2, fc3."""
+    N = sf._N(T, 517)
     rep = sf.Report()
-    eng = pkg.Engine(targets, 128, N, tracks=3, u8_dequant=u8_dequant)
+    eng = pkg.Engine(targets, hidden, N, tracks=lanes, u8_dequant=u8_dequant)
     try:
-        levels = (np.float32(1.0), LOUD, QUIET)
-        states = [_zero_state(eng)] * 3
+        levels = [LOUD if b in loud else QUIET if b in quiet else np.float32(1.0) for b in range(lanes)]
+        states = [_zero_state(eng)] * lanes
         if carried:
-            geo._run(pkg, eng, _waves(pkg, N, 3, 2100, levels), flags)
-            states = [_state(eng, b) for b in range(3)]
-            assert all(np.abs(s).max() > 0 for s in states)
-        geo._run(pkg, eng, _waves(pkg, N, 3, 2200, levels), flags)
-        assert eng.lstm_kernel_name() == "lstm_batch_kernel", eng.lstm_kernel_name()
-        assert all(eng.gemm_kernel_name(m) == "gemm_planes_kernel" for m in range(4)), [eng.gemm_kernel_name(m) for m in range(4)]
-        worst = max(check_network_both(rep, eng, b, targets, states[b], test, parity_only=u8_dequant) for b in check_lanes)
+            geo._run(pkg, eng, _waves(pkg, N, lanes, 2100, levels), flags)
+            states = [_state(eng, b) for b in range(lanes)]
+            assert all(np.abs(states[b]).max() > 0 for b in check_lanes)
+        geo._run(pkg, eng, _waves(pkg, N, lanes, 2200, levels), flags)
+        assert eng.lstm_kernel_name() == lstm_kernel, eng.lstm_kernel_name()
+        names = tuple(eng.gemm_kernel_name(m) for m in range(4))
+        assert names == tuple(gemm_kernels), names
+        worst = max(check_network_both(rep, eng, b, targets, states[b], test, which=which, parity_only=u8_dequant) for b in check_lanes)
         print(f"{test}: worst ratio to the float32 evaluation {worst:.2f}")
     finally:
         eng.close()
     return rep
+
+
+SMALL_TILES = ("gemm_planes_kernel",) * 4
+# fc1 and fc2 (N = hidden) have too few 256 x 256 tiles at nine or ten lanes; W_ih (N = 4 hidden) and fc3 (N = 4352) take the persistent kernel
+MIXED_TILES = ("gemm_planes_kernel", "gemm_planes_ps_kernel", "gemm_planes_kernel", "gemm_planes_ps_kernel")
+
+
+def _three_lane_case(pkg, targets, test, **kw):
+    """hidden 128, three lanes, T = 41: lane 1 at 30 times the level, lane 2 at 1e-5 of it; 128 x 128 tiles, lstm_batch_kernel."""
+    return _lanes_case(pkg, targets, test, hidden=128, lanes=3, T=41, lstm_kernel="lstm_batch_kernel", gemm_kernels=SMALL_TILES,
+                       check_lanes=(0, 1, 2), **kw)
 
 
 def test_one_track_staged_u8_one_plane_form(pkg, fixtures):
@@ -134,6 +155,60 @@ def test_three_lanes_only_whh_skewed(pkg, fixtures, case):
     geo._finish(rep, f"affine_h128_hh_{case}")
 
 
+@pytest.mark.parametrize("case", ["first_segment", "carried_state"])
+def test_three_lanes_plane_gemms_on_the_skewed_model(pkg, fixtures, case):
+    """gemm_planes_kernel on 128 x 128 tiles (fc1, W_ih: u8, one plane; fc2, fc3: u16, two planes) and lstm_batch_kernel on the fully
+    skewed hidden-128 model, all four targets, lanes at 1, 30 and 1e-5 times the level.  With the centres 128 / 32896 fc1 of this
+    case is dozens of times outside its bound (tests/test_affine_offset_cpu.py's emulation: 45 - 113)."""
+    _, fams, targets = fixtures("h128_all")
+    assert fams == sw.ALL
+    rep = _three_lane_case(pkg, targets, f"three lanes, h128_all, {case}", carried=case == "carried_state")
+    geo._finish(rep, f"affine_h128_all_{case}")
+
+
+def test_ten_lanes_hidden_512_plane_gemms_on_the_skewed_model(pkg, fixtures):
+    """The shape of the bitwise flavour test below: hidden 512, ten lanes, T = 45, the second of two segments.  W_ih and fc3 on
+    gemm_planes_ps_kernel's 256 x 256 tiles, fc1 and fc2 on the 128 x 128 ones, lstm_batch8_kernel (K = 256); lanes 0, 1 (loud),
+    2 (quiet) and 9, all four targets."""
+    Hh, fams, targets = fixtures("h512_all")
+    assert fams == sw.ALL
+    rep = _lanes_case(pkg, targets, "ten lanes, h512_all", hidden=Hh, lanes=10, T=45, lstm_kernel="lstm_batch8_kernel", gemm_kernels=MIXED_TILES,
+                      check_lanes=(0, 1, 2, 9), carried=True)
+    geo._finish(rep, "affine_h512_all")
+
+
+def test_nine_lanes_hidden_1024_plane_gemms_on_the_skewed_model(pkg, fixtures):
+    """UMX-L's width, nine lanes (one octet and a lane), T = 41: W_ih (K = 1024) and fc3 on gemm_planes_ps_kernel, fc1 and fc2
+    (K = 2048) on the 128 x 128 tiles, lstm_batch8_kernel at K = 512; lanes 0 and 8, targets 0 - 2."""
+    Hh, fams, targets = fixtures("h1024_all")
+    assert fams == sw.ALL
+    rep = _lanes_case(pkg, targets, "nine lanes, h1024_all", hidden=Hh, lanes=9, T=41, lstm_kernel="lstm_batch8_kernel", gemm_kernels=MIXED_TILES,
+                      check_lanes=(0, 8), which=range(3))
+    geo._finish(rep, "affine_h1024_all")
+
+
+# fixture, lanes, lanes checked, targets checked (targets 0 and 1 carry opposite variants in every chain), kernels of fc1 / W_ih / fc2 / fc3
+BIG_TILES = ("gemm_planes_ps_kernel",) * 4  # 40 lanes: every GEMM has more 256 x 256 tiles than the chip has CUs
+WHH_CASES = {"h512_ten_lanes": ("h512_hh", 10, (0, 1, 9), range(4), MIXED_TILES),
+             "h1024_nine_lanes": ("h1024_hh", 9, (0, 8), (0, 1, 2), MIXED_TILES),
+             "h1024_forty_lanes": ("h1024_hh", 40, (0, 8, 33, 39), (0, 1), BIG_TILES)}
+
+
+@pytest.mark.parametrize("segment", ["first_segment", "carried_state"])
+@pytest.mark.parametrize("case", sorted(WHH_CASES))
+def test_batch8_recurrence_only_whh_skewed(pkg, fixtures, case, segment):
+    """lstm_batch8_kernel's u8-resident W_hh offset term at its real K (256 at hidden 512, 512 at hidden 1024) on a sharp fixture:
+    only W_hh skewed, so every other product is the plain one.  The kernel keeps the centre 128 for W_hh: |h| < 1 and the row sum
+    comes out of the same accumulation as the products, so the fixed centre costs little here (the emulation: at most 0.31 of the
+    bound) -- this test is what holds that.  Lane 1 at 30 times the level, lane 2 at 1e-5 of it, lane 33 (where present) at 30 times."""
+    name, lanes, check_lanes, which, kernels = WHH_CASES[case]
+    Hh, fams, targets = fixtures(name)
+    assert fams == {"hh"}
+    rep = _lanes_case(pkg, targets, f"{case}, {name}, {segment}", hidden=Hh, lanes=lanes, T=41, lstm_kernel="lstm_batch8_kernel",
+                      gemm_kernels=kernels, check_lanes=check_lanes, which=which, carried=segment == "carried_state", loud=(1, 33))
+    geo._finish(rep, f"affine_{name}_{lanes}_{segment}")
+
+
 FLAVOURS = ((("UMX_GEMM_PP", "0"), "gemm_planes_kernel"), (("UMX_GEMM_PS", "0"), "gemm_planes_pp_kernel"), (None, "gemm_planes_ps_kernel"))
 
 
@@ -142,8 +217,9 @@ def test_plane_gemm_flavours_give_the_same_bits_on_the_skewed_model(pkg, fixture
     the fully skewed hidden-512 model, ten lanes, T = 45, two segments: stems, carried state and every stage tap agree bit for bit.
     W_ih (u8, one plane, the two directions' bs / bo2 / bsplit) and fc3 (u16, two planes) have enough 256 x 256 tiles at this size for
     the setting to select the kernel -- asserted by name per flavour; fc1 and fc2 stay on gemm_planes_kernel's 128 x 128 tiles (at
-    hidden 128 every GEMM would, and the comparison would be one kernel against itself).  Kernel against kernel: it holds whatever
-    the centre is, and would fail if one flavour formed the offset term differently."""
+    hidden 128 every GEMM would, and the comparison would be one kernel against itself).  Kernel against kernel: it would fail if one
+    flavour formed the offset term differently; test_ten_lanes_hidden_512_plane_gemms_on_the_skewed_model holds the shipped flavour
+    of this very context to float64."""
     Hh, _, targets = fixtures("h512_all")
     B, N = 10, sf._N(45, 517)
     levels = [np.float32(1.0), LOUD, QUIET] + [np.float32(1.0)] * (B - 3)

@@ -128,6 +128,8 @@ def hip_lib():
     lib.umx_hip_debug_f16_bits.restype = C.c_uint
     lib.umx_hip_debug_quant_centre.argtypes = [C.c_float, C.c_float, C.POINTER(C.c_float)]
     lib.umx_hip_debug_quant_centre.restype = C.c_int
+    lib.umx_hip_debug_quant_planes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    lib.umx_hip_debug_quant_planes.restype = C.c_int
     lib.umx_hip_track_stream_reset.argtypes = [C.c_void_p, C.c_int]
     lib.umx_hip_track_stream_get.argtypes = [C.c_void_p, C.c_int, _fp]
     lib.umx_hip_track_stream_set.argtypes = [C.c_void_p, C.c_int, _fp]
@@ -245,7 +247,7 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_lstm_was_persistent", "umx_hip_lstm_mode", "umx_hip_lstm_kernel_name", "umx_hip_gemm_kernel_name", "umx_hip_debug_wiener_bins", "umx_hip_debug_gate_math", "umx_hip_debug_lstm_profile", "umx_hip_debug_lstm_placement",
                "umx_hip_stream_layer_floats", "umx_hip_stream_get_layer", "umx_hip_stream_set_layer",
                "umx_hip_segment_begin", "umx_hip_segment_lstm_layer", "umx_hip_segment_end",
-               "umx_hip_split_inference", "umx_hip_shift_inference", "umx_hip_debug_lds_guard", "umx_hip_debug_f16_bits", "umx_hip_debug_quant_centre",
+               "umx_hip_split_inference", "umx_hip_shift_inference", "umx_hip_debug_lds_guard", "umx_hip_debug_f16_bits", "umx_hip_debug_quant_centre", "umx_hip_debug_quant_planes",
                "umx_hip_segment_masks_device", "umx_hip_target_mag_device", "umx_hip_segment_finish_device", "umx_hip_gate_reserve", "umx_hip_segment_discard", "umx_hip_pipeline_depth",
                "umx_hip_resampled_length", "umx_hip_resample_device", "umx_hip_shift_inference_rate", "umx_hip_separate_tracks_rate",
                "umx_hip_debug_resample_taps", "umx_hip_residual_slot", "umx_hip_segment_residual_device",

@@ -65,11 +65,11 @@ std::string g_create_error = "";
 enum { W_FC1 = 0, W_IH0, W_IH1, W_IH2, W_FC2, W_FC3, W_COUNT };
 inline int gemm_weight(int mode, int layer) { return mode == G_FC1 ? W_FC1 : mode == G_IH ? W_IH0 + layer : mode == G_FC2 ? W_FC2 : W_FC3; }
 
-// One GEMM weight in HBM, [N][K] per plane.  Plane flavour (gemm_planes.h): `form` fp16 planes -- u8 as 1 exact plane of q - 128,
-// u16 as 2 planes whose sum is exactly q - 32896 (fp16(q - 32896) and the remainder, an integer of at most 16), fp32 as 2 split
-// terms of w / s with s a power of two; (s, o) = (scale, offset + c scale), or (s, 0).  Staged flavour (gemm_bf16x3.h): `form` is
+// One GEMM weight in HBM, [N][K] per plane.  Plane flavour (gemm_planes.h): `form` fp16 planes -- u8 as 1 exact plane of q - c,
+// u16 as 2 planes whose sum is exactly q - c (fp16(q - c) and the remainder, an integer of at most 16), c each source tensor's own
+// centre (quant_planes.h), fp32 as 2 split terms of w / s with s a power of two; (s, o) = (scale, offset + c scale), or (s, 0).  Staged flavour (gemm_bf16x3.h): `form` is
 // the GemmBType -- BQ_U8 / BQ_U16 = the ggml file's bytes (BASELINE config 5) with (scale, offset) and, for the u8 one-plane form,
-// (c, o2) = (the tensor's centre, offset + c scale: quant_centre, gemm_common.h); BQ_F32 = three bf16 planes with (1, 0).  Two of
+// (c, o2) = (the tensor's centre, offset + c scale: quant_centre, quant_planes.h); BQ_F32 = three bf16 planes with (1, 0).  Two of
 // each because W_ih of a layer is two file tensors (forward rows, then reverse rows).
 struct GemmWeight
 {

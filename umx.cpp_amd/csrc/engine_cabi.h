@@ -70,6 +70,15 @@ int umx_hip_debug_quant_centre(float scale, float offset, float *o2)
         *o2 = qc.o2;
     return qc.c;
 }
+int umx_hip_debug_quant_planes(const void *q, int elem_size, int n, float scale, float offset, unsigned short *hi, unsigned short *lo, float *o2)
+{
+    if (!q || !hi || n < 0 || (elem_size != 1 && elem_size != 2) || (elem_size == 2 && !lo))
+        return -1;
+    const QuantCentre qc = quant_planes(q, elem_size, 1, n, nullptr, (size_t)n, scale, offset, hi, lo);
+    if (o2)
+        *o2 = qc.o2;
+    return qc.c;
+}
 
 void umx_hip_destroy(umx_hip_ctx *ctx)
 {

@@ -194,14 +194,9 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
         weight_bytes += bytes;
         return UMX_OK;
     };
-    // element i of a matrix of fp16 planes `plane` elements apart: fp16(v) and, with two planes, fp16 of the remainder
-    auto fill_planes = [](std::vector<unsigned short> &host, size_t plane, size_t i, int nbp, float v) {
-        host[i] = f16_rne_bits(v);
-        if (nbp == 2)
-            host[plane + i] = f16_rne_bits(v - f16_bits_to_float(host[i]));
-    };
     // Weight d of target tg in the form of the context's GEMM flavour (GemmWeight).  Integers as the file holds them if all
-    // four targets do: the file's bytes (staged), or exact planes of q - c (plane flavour, unless UMX_CREATE_U8_DEQUANT).
+    // four targets do: the file's bytes (staged), or exact planes of q - c, c per source tensor (plane flavour, unless
+    // UMX_CREATE_U8_DEQUANT; quant_planes.h).
     // Otherwise dequantised fp32: two split planes of w * 2^e, 2^e bringing the source tensor's largest finite |w| into
     // [2^14, 2^15) (plane flavour), or three bf16 planes (staged).
     const bool exact_ok = keepq && !u8_dequant;
@@ -215,6 +210,24 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
         if (q && (!gemm_planes || exact_ok))
         {
             const size_t esz = d.dtype == UMX_DTYPE_U8 ? 1 : 2;
+            if (gemm_planes)
+            {
+                // u8: q - c in one plane.  u16: q - c as fp16 + exact remainder.  c is each source tensor's own centre and goes into
+                // the offset: the kernels take (scale, offset + c scale).  Rows that no source row maps to and columns past cols
+                // stay plane value 0.
+                w.form = (int)esz;
+                planes.assign(w.form * n, 0);
+                for (int s = 0; s < d.nsrc; ++s)
+                {
+                    const umx_tensor_view *tv = view(tg, d.name[s]);
+                    unsigned short *hi = planes.data() + (size_t)s * d.dst_rows * d.cols_pad;
+                    const QuantCentre qc = quant_planes(tv->data, (int)esz, d.rows, d.cols, d.dst_row ? d.dst_row->data() : nullptr, (size_t)d.cols_pad,
+                                                        tv->scale, tv->offset, hi, esz == 2 ? hi + n : nullptr);
+                    w.s[s] = tv->scale;
+                    w.o[s] = qc.o2;
+                }
+                return upload_weight(w, planes.data(), planes.size() * sizeof(unsigned short));
+            }
             std::vector<unsigned char> qh(n * esz, 0);
             for (int s = 0; s < d.nsrc; ++s)
             {
@@ -224,35 +237,15 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
                 w.s[s] = tv->scale;
                 w.o[s] = tv->offset;
             }
-            if (!gemm_planes)
+            // the u8 one-plane form of gemm_bf16x3.h: the centre of each source tensor and offset + c scale (quant_planes.h)
+            for (int s = 0; s < d.nsrc && esz == 1; ++s)
             {
-                // the u8 one-plane form of gemm_bf16x3.h: the centre of each source tensor and offset + c scale (gemm_common.h)
-                for (int s = 0; s < d.nsrc && esz == 1; ++s)
-                {
-                    const QuantCentre qc = quant_centre(w.s[s], w.o[s]);
-                    w.c[s] = (float)qc.c;
-                    w.o2[s] = qc.o2;
-                }
-                w.form = esz == 1 ? BQ_U8 : BQ_U16;
-                return upload_weight(w, qh.data(), qh.size());
+                const QuantCentre qc = quant_centre(w.s[s], w.o[s]);
+                w.c[s] = (float)qc.c;
+                w.o2[s] = qc.o2;
             }
-            // u8: q - 128 in one plane.  u16: q - 32896 (= 256 (qh - 128) + (ql - 128)) as fp16 + exact remainder, |remainder|
-            // <= 16 = 2^-11 of the plane above it, so that a2 x remainder need not be formed (gemm_planes.h).  The constant
-            // goes into the offset: (scale, offset + c scale).
-            w.form = esz == 1 ? 1 : 2;
-            const float c = esz == 1 ? 128.0f : 32896.0f;
-            planes.assign(w.form * n, 0);
-            for (size_t i = 0; i < n; ++i)
-                if ((int)(i % d.cols_pad) < d.cols)
-                {
-                    uint16_t qv = qh[i * esz];
-                    if (esz == 2)
-                        memcpy(&qv, &qh[i * 2], 2);
-                    fill_planes(planes, n, i, w.form, (float)qv - c);
-                }
-            for (int s = 0; s < d.nsrc; ++s)
-                w.o[s] = w.o[s] + c * w.s[s];
-            return upload_weight(w, planes.data(), planes.size() * sizeof(unsigned short));
+            w.form = esz == 1 ? BQ_U8 : BQ_U16;
+            return upload_weight(w, qh.data(), qh.size());
         }
         std::vector<float> f(n, 0.f), v;
         if (gemm_planes)
@@ -279,7 +272,7 @@ int umx_hip_ctx::init(int device_, int hidden, int segment_samples, const umx_te
                 }
                 const size_t b0 = (size_t)s * d.dst_rows * d.cols_pad;
                 for (size_t i = b0; i < b0 + (size_t)d.dst_rows * d.cols_pad; ++i)
-                    fill_planes(planes, n, i, 2, f[i] * scale);
+                    f16_split(f[i] * scale, &planes[i], &planes[n + i]);
             }
         }
         if (gemm_planes)

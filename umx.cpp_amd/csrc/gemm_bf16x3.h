@@ -99,7 +99,7 @@ __host__ inline void split3_host(float x, unsigned short &p1, unsigned short &p2
     p3 = bf16_rne_bits(r2);
 }
 
-// BQ_U8X (u8-resident weights, the default for them): q - c (c = the tensor's zero-weight code, quant_centre in gemm_common.h) is an
+// BQ_U8X (u8-resident weights, the default for them): q - c (c = the tensor's zero-weight code, quant_centre in quant_planes.h) is an
 // integer of at most 255, EXACT in bf16, so the weight needs ONE plane and the product three MFMAs (a1 + a2 + a3).(q - c) instead
 // of six; the affine map of model.cpp:610-616 moves out of the dot product:
 //     sum_k a_k (q_k s + o) = s * sum_k a_k (q_k - c) + (o + c s) * sum_k a_k

@@ -18,6 +18,7 @@
 #include <cmath>
 #include <type_traits>
 #include "common.h"
+#include "quant_planes.h"
 
 namespace umx
 {
@@ -48,29 +49,8 @@ struct GemmTarget
     int bsplit;
 };
 
-// The affine map w = q s + o of a quantised tensor is applied to the accumulated sum,
-//     sum_k a_k (q_k s + o) = s sum_k a_k (q_k - c) + (o + c s) sum_k a_k,
-// and the two terms cancel by |o + c s| sum a: the fp32 roundings of the accumulators and of the row sum are multiplied by
-// |o + c s| / s codes.  For the u8 one-plane form of gemm_bf16x3.h c is therefore the code that stands for a zero weight,
-// round(-o / s), per source tensor -- |o + c s| <= s / 2, whatever outlier skews the tensor's range --, clamped to 0 .. 255 so that
-// |q - c| <= 255 stays exact in one bf16 plane.  A zero or non-finite scale keeps the middle of the code range.  o + c s is formed in
-// double and rounded once: the fp32 product c s is not exact for c != 2^n, and its rounding would be multiplied by the row sum again.
-// (The plane GEMMs and the batched recurrences still centre every tensor at 128 / 32896: DESIGN 5.)
-struct QuantCentre
-{
-    int c;
-    float o2;
-};
-__host__ inline QuantCentre quant_centre(float s, float o)
-{
-    int c = 128;
-    if (s - s == 0.f && s != 0.f && o - o == 0.f) // finite, non-zero scale; finite offset
-    {
-        const double z = std::nearbyint(-(double)o / (double)s);
-        c = (int)(z < 0.0 ? 0.0 : z > 255.0 ? 255.0 : z);
-    }
-    return {c, (float)((double)o + (double)c * (double)s)};
-}
+// The centre c of a quantised tensor's q - c and offset + c scale, per source tensor: quant_centre (quant_planes.h, host code).  The u8
+// one-plane form of gemm_bf16x3.h and the planes of gemm_planes.h (quant_planes, formed at load time) both take them from there.
 
 struct GemmArgs
 {

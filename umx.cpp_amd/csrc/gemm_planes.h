@@ -11,11 +11,12 @@
 //     bounded by 1 (tanh / LSTM outputs) -- then a1 = fp16(a'), a2 = fp16(a' - a1): a' = a1 + a2 to 2^-22 |a'| worst
 //     case (11 + 11 significand bits and the residual's sign), elements more than 2^17 below the row maximum to
 //     2^-39 of it; the inverse scale and the fp32 row sum travel with the row;
-//   * weights are re-encoded ONCE at load time as the integers they are: a u8 weight is q - 128 in ONE fp16 plane
-//     (exact), a u16 weight q - 32896 in TWO whose sum is exact -- P_hi = fp16(q - 32896) and the remainder P_lo, an
+//   * weights are re-encoded ONCE at load time as the integers they are: a u8 weight is q - c in ONE fp16 plane
+//     (exact), a u16 weight q - c in TWO whose sum is exact -- P_hi = fp16(q - c) and the remainder P_lo, an
 //     integer of at most 16 (until the end of round 4: the two bytes, 256 (qh - 128) and ql - 128) --, an fp32 weight two
 //     split terms under one power-of-two scale per file tensor; the affine map of model.cpp:610-616 is applied to the
-//     accumulated sum with the row sum of A:   sum_k a_k (q_k s + o) = s sum_k a_k (q_k - c) + (o + c s) sum_k a_k,   c = 128 or 32896
+//     accumulated sum with the row sum of A:   sum_k a_k (q_k s + o) = s sum_k a_k (q_k - c) + (o + c s) sum_k a_k,
+//     c = the source tensor's zero-weight code, 0 .. 255 / 31 .. 65504 (quant_centre, quant_planes.h); the kernels see (s, o + c s) only
 //   * tiles go global -> LDS by `buffer_load_dwordx4 ... lds` (no VGPRs, no ds_write, no VALU), 16 bytes per lane,
 //     the XOR swizzle of the LDS layout folded into WHICH 16 bytes a lane fetches;
 //   * products per 32x32x16 block: 2 (u8 weights) or 3 (u16 / fp32 weights: a2 P_hi, a1 P_lo, a1 P_hi; with |P_lo| <=
@@ -72,46 +73,7 @@ __host__ __device__ constexpr int gp_stages(int WM, int WN, int NBP)
 }
 __host__ __device__ constexpr int gp_lds_bytes(int WM, int WN, int NBP) { return gp_stages(WM, WN, NBP) * gp_stage_bytes(WM, WN, NBP); }
 
-// fp32 -> fp16 bits, round to nearest even, subnormals and overflow handled (weights at load time)
-__host__ inline unsigned short f16_rne_bits(float f)
-{
-    unsigned u;
-    memcpy(&u, &f, 4);
-    const unsigned sign = (u >> 16) & 0x8000u;
-    u &= 0x7fffffffu;
-    if (u >= 0x7f800000u)
-        return (unsigned short)(sign | 0x7c00u | (u > 0x7f800000u ? 0x200u : 0u));
-    if (u >= 0x477ff000u) // rounds to >= 65520: infinity
-        return (unsigned short)(sign | 0x7c00u);
-    if (u < 0x38800000u) // below 2^-14: subnormal, in units of 2^-24
-    {
-        if (u < 0x33000000u) // < 2^-25
-            return (unsigned short)sign;
-        float a;
-        memcpy(&a, &u, 4);
-        const float scaled = a * 16777216.0f; // exact
-        const float r = nearbyintf(scaled);   // default rounding mode: to nearest even
-        return (unsigned short)(sign | (unsigned)r);
-    }
-    const unsigned mant = u & 0x7fffffu, exp = (u >> 23) - 112u; // rebias 127 -> 15
-    unsigned h = (exp << 10) | (mant >> 13);
-    const unsigned rem = mant & 0x1fffu;
-    if (rem > 0x1000u || (rem == 0x1000u && (h & 1u)))
-        ++h; // a carry into the exponent is the correct result
-    return (unsigned short)(sign | h);
-}
-__host__ inline float f16_bits_to_float(unsigned short h)
-{
-    const unsigned sign = (unsigned)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-    float v;
-    if (e == 0)
-        v = ldexpf((float)m, -24);
-    else if (e == 31)
-        v = m ? NAN : INFINITY;
-    else
-        v = ldexpf((float)(m | 0x400u), (int)e - 25);
-    return sign ? -v : v;
-}
+// (f16_rne_bits / f16_bits_to_float, the conversions of the weights at load time: quant_planes.h)
 
 // split_planes_kernel: fp32 rows -> two fp16 planes of the scaled row + row sum + inverse scale.
 // grid (rows_out / 4, 1, targets), 256 threads = four rows; cols <= 512 ITER.
