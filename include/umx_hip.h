@@ -352,6 +352,41 @@ int umx_hip_shift_ensemble_mix(umx_hip_ctx *ctx, const float *audio_host, int le
  * (every used input of a frame is read before any output of that frame is stored); other overlaps are not. */
 int umx_hip_mix_stems_device(umx_hip_ctx *ctx, int n_out, const float *gains, const float *const stems_dev[4], const float *mix_dev, int n,
                              float *const *out_dev, void *hip_stream);
+/* Track queue: a catalogue job -- more tracks than track lanes, of different lengths -- through ONE run of the segment
+ * loop.  umx_hip_separate_tracks takes at most umx_hip_n_tracks tracks and a finished track's lane sits idle until the longest one
+ * ends; here a lane is refilled with the next job the moment its track ends.  Every job's `out` is, bit for bit, what
+ * umx_hip_separate_tracks (gains == NULL: four stems) or umx_hip_separate_tracks_mix (n_out, gains as that call takes them: n_out
+ * buffers) returns for that ONE track on this context with these flags; every per-call flag goes to every job.
+ * The schedule (umx_hip_queue_plan is its one statement in code; the driver walks the same object):
+ *   - before each call of the segment loop every lane without a track asks `next` for one, in ascending lane order;
+ *   - a job of S = ceil(padded length / stride) segments (padded length: length for shift_offset < 0, else length +
+ *     max(UMX_MAX_SHIFT - shift_offset, shift_offset); stride = 0.75 segment_samples) holds its lane for S consecutive calls;
+ *   - once `next` has returned 0 it is not called again; the run ends when no lane holds a track.
+ * Both callbacks run on the caller's thread, inside the call.  done(j) comes after the last byte of job j is in its buffers; `audio` and
+ * `out` of a job must stay valid from `next` to `done`.  done is called exactly once per job taken -- on an error return too, for
+ * the jobs already complete, and only for those (a job in flight then is abandoned: its buffers hold anything).
+ * UMX_ERR_ARG, with umx_hip_last_error naming the reason, for UMX_FLAG_RESET_SEGMENTS (the lanes are taken), a context that is not
+ * track-batched (umx_hip_lstm_is_batched: a job's bits must not depend on its lane), a job with length < 1, shift_offset >=
+ * UMX_MAX_SHIFT or a NULL buffer, and `next` returning < 0; the context stays usable.  A persistent-kernel timeout: as
+ * umx_hip_separate_tracks, the jobs in flight are run again from their first segment, once (the run then makes more calls than the
+ * plan); a second timeout is UMX_ERR_TIMEOUT.  Tracks at other sample rates and the shift ensemble are not offered here, and the
+ * multi-GPU driver (umx_mgpu.h) does not offer the queue. */
+typedef struct umx_queue_job
+{
+    const float *audio;                   /* (2,length) interleaved, 44.1 kHz */
+    int length, shift_offset;             /* as umx_hip_separate_tracks: < 0 split, >= 0 shift */
+    float *out[UMX_MAX_MIX_OUTPUTS];      /* n_out buffers (2,length); 4 stems when gains == NULL */
+    void *tag;                            /* the caller's, untouched */
+} umx_queue_job;
+typedef int (*umx_queue_next_fn)(void *user, umx_queue_job *job);        /* 1: *job filled in, 0: no more jobs, < 0: stop with UMX_ERR_ARG */
+typedef void (*umx_queue_done_fn)(void *user, const umx_queue_job *job); /* job's out buffers are complete */
+int umx_hip_separate_queue(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_done_fn done, void *user, int n_out, const float *gains,
+                           unsigned flags);
+/* host arithmetic, no context: the schedule above for n_jobs jobs of seg_count[j] >= 1 calls each on n_lanes (1 .. UMX_MAX_TRACKS)
+ * lanes: job j's lane, the call its first segment runs in, and the number of calls (each output may be NULL).  UMX_ERR_ARG otherwise. */
+int umx_hip_queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_out, int *first_call_out, int *n_calls_out);
+/* calls of the segment loop (infer_batch) the context's last queue run made; < 0 when there was none */
+int umx_hip_debug_queue_calls(umx_hip_ctx *ctx);
 /* testing, host only: the fp32 tap table of a rate pair (taps[phase * K + d + D]; cap floats at most), its phase count L, taps
  * per phase K and first offset -D.  UMX_ERR_ARG for a bad rate or a too small cap (the sizes are still reported). */
 int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase,

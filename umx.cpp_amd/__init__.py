@@ -80,6 +80,15 @@ def FLAG_WIENER_ITERS(n):
 _fp = C.POINTER(C.c_float)
 
 
+class QueueJob(C.Structure):
+    """include/umx_hip.h: umx_queue_job"""
+    _fields_ = [("audio", _fp), ("length", C.c_int), ("shift_offset", C.c_int), ("out", _fp * 4), ("tag", C.c_void_p)]
+
+
+QUEUE_NEXT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(QueueJob))
+QUEUE_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJob))
+
+
 class TensorView(C.Structure):
     """include/umx_hip.h: umx_tensor_view"""
     _fields_ = [("name", C.c_char_p), ("target", C.c_int), ("dtype", C.c_int), ("n_dims", C.c_int),
@@ -217,6 +226,9 @@ def hip_lib():
                                                C.c_uint, C.c_void_p, C.c_void_p]
     lib.umx_hip_mix_stems_device.argtypes = [C.c_void_p, C.c_int, _fp, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
                                              C.c_void_p]
+    lib.umx_hip_separate_queue.argtypes = [C.c_void_p, QUEUE_NEXT_FN, QUEUE_DONE_FN, C.c_void_p, C.c_int, _fp, C.c_uint]
+    lib.umx_hip_queue_plan.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.umx_hip_debug_queue_calls.argtypes = [C.c_void_p]
     _hip = lib
     return lib
 
@@ -252,7 +264,8 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_resampled_length", "umx_hip_resample_device", "umx_hip_shift_inference_rate", "umx_hip_separate_tracks_rate",
                "umx_hip_debug_resample_taps", "umx_hip_residual_slot", "umx_hip_segment_residual_device",
                "umx_hip_ensemble_offsets", "umx_hip_shift_ensemble", "umx_hip_debug_shift_mean_ms",
-               "umx_hip_mix_columns", "umx_hip_separate_tracks_mix", "umx_hip_shift_ensemble_mix", "umx_hip_mix_stems_device"]
+               "umx_hip_mix_columns", "umx_hip_separate_tracks_mix", "umx_hip_shift_ensemble_mix", "umx_hip_mix_stems_device",
+               "umx_hip_separate_queue", "umx_hip_queue_plan", "umx_hip_debug_queue_calls"]
 
 
 def resampled_length(n, rate_in, rate_out):
@@ -270,6 +283,18 @@ def ensemble_offsets(n_shifts, first=None):
     if rc != 0:
         raise UmxError(rc, "ensemble_offsets: first must be below 22050")
     return list(out)
+
+
+def queue_plan(lanes, seg_counts):
+    """umx_hip_queue_plan: the track queue's schedule for jobs of seg_counts[j] calls each on `lanes` lanes -> (lane of every job, the
+    call every job's first segment runs in, number of calls).  Host arithmetic."""
+    counts = [int(c) for c in seg_counts]
+    n = len(counts)
+    lane, first, calls = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), C.c_int(0)
+    rc = hip_lib().umx_hip_queue_plan(int(lanes), n, (C.c_int * max(n, 1))(*counts), lane, first, C.byref(calls))
+    if rc != 0:
+        raise UmxError(rc, f"queue_plan: need 1 .. {MAX_TRACKS} lanes and at least one job, every job of at least one segment")
+    return list(lane)[:n], list(first)[:n], calls.value
 
 
 def _mix_gains(gains):
@@ -600,6 +625,43 @@ class Engine:
         self._check(self.lib.umx_hip_separate_tracks_mix(self.h, nt, a, (C.c_int * nt)(*Ls), rt, sh, n_out, g.ctypes.data_as(_fp), o, flags,
                                                          None, None))
         return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)]
+
+    # --- the track queue: more tracks than lanes, a lane refilled with the next track the moment one ends ---
+    def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None):
+        """umx_hip_separate_queue: list of (2,L_i) -> list of [4 x (2,L_i)] (mix: an (n_out, 5) gain matrix -> n_out x (2,L_i)), every
+        job bit for bit what separate() / separate_mix() returns for it alone on this engine; the jobs are handed out in list order."""
+        nj = len(waves)
+        n_out, g = (4, None) if mix is None else _mix_gains(mix)
+        ins = [np.ascontiguousarray(np.asarray(w, np.float32).T).ravel() for w in waves]
+        Ls = [np.asarray(w).shape[1] for w in waves]
+        outs = [[np.empty(2 * L, np.float32) for _ in range(min(max(n_out, 0), MAX_MIX_OUTPUTS))] for L in Ls]
+        shifts = [(-1 if s is None else int(s)) for s in (shift_offsets or [None] * nj)]
+        state = {"next": 0, "done": []}
+
+        def _next(_user, job):
+            j = state["next"]
+            if j >= nj:
+                return 0
+            state["next"] = j + 1
+            job[0].audio = ins[j].ctypes.data_as(_fp)
+            job[0].length, job[0].shift_offset = Ls[j], shifts[j]
+            for m, o in enumerate(outs[j]):
+                job[0].out[m] = o.ctypes.data_as(_fp)
+            job[0].tag = j + 1
+            return 1
+
+        def _done(_user, job):
+            state["done"].append(int(job[0].tag) - 1)
+
+        self._check(self.lib.umx_hip_separate_queue(self.h, QUEUE_NEXT_FN(_next), QUEUE_DONE_FN(_done), None, n_out,
+                                                    None if g is None else g.ctypes.data_as(_fp), flags))
+        assert sorted(state["done"]) == list(range(nj)), state
+        return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)]
+
+    def queue_calls(self):
+        """Calls of the segment loop the engine's last separate_queue made (umx_hip_debug_queue_calls); None: there has been none."""
+        n = int(self.lib.umx_hip_debug_queue_calls(self.h))
+        return None if n < 0 else n
 
     def mix_stems_device(self, gains, stem_ptrs, mix_ptr, n, out_ptrs, hip_stream=None):
         """umx_hip_mix_stems_device: the mix kernel on device buffers (2,n) interleaved, queued on hip_stream.  stem_ptrs: 4 device

@@ -586,6 +586,19 @@ struct umx_hip_ctx
     };
     std::vector<TrackBufs> trk;
     hipEvent_t trk_acc_ev[kMaxSlots] = {};
+    // what tracks_once and the track queue share (engine_tracks.h)
+    int track_bufs_grow(TrackBufs &tb_, size_t frames);
+    int track_bufs_segs(TrackBufs &tb_);
+    hipError_t track_upload_until(float *in_dev, const float *audio_host, int length, int lead, long long &uploaded, long long padded_end);
+    void track_mix(const MixSpec &mix, float *const stems[4], size_t stem_start, const float *in, size_t in_start, int count, hipStream_t st);
+    int track_region(const TrackBufs &tb_, float *const seg_stems[4], int offset, int nn, int L2, int stride, const MixSpec *mix, hipStream_t st);
+    hipError_t track_region_download(const TrackBufs &tb_, int start, int count, int lead, int length, int n_host, float *const *out_host,
+                                     hipEvent_t ready);
+    // track queue (engine_queue.h): B + 2 accumulator sets (in, out, sumw of TrackBufs; grow-only) lent to the jobs in flight
+    std::vector<TrackBufs> qpool;
+    int queue_calls = -1; // infer_batch calls of the last queue run
+    int queue(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags);
+    int queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags);
     int phase_begin(const float *audio_host, int n, unsigned flags);
     int phase_begin_device(const float *audio_dev, int n, unsigned flags);
     int phase_end_device(float *const out_dev_[4]);
@@ -669,5 +682,6 @@ struct umx_hip_ctx
 #include "engine_lstm.h"
 #include "engine_stages.h"
 #include "engine_tracks.h"
+#include "engine_queue.h"
 #include "engine_phased.h"
 #include "engine_cabi.h"

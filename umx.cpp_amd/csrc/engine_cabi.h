@@ -407,6 +407,23 @@ int umx_hip_shift_ensemble_mix(umx_hip_ctx *ctx, const float *audio_host, int le
     return shift_ensemble(ctx, audio_host, length, rate, n_shifts, offsets, out_host, flags, progress, progress_user, &spec);
 }
 
+// ---------------------------------------------------------------- track queue (engine_queue.h)
+int umx_hip_separate_queue(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_done_fn done, void *user, int n_out, const float *gains,
+                           unsigned flags)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    MixSpec spec;
+    if (gains && !mix_checked(ctx, n_out, gains, spec))
+        return UMX_ERR_ARG;
+    return ctx->queue(next, done, user, gains ? &spec : nullptr, flags);
+}
+int umx_hip_queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_out, int *first_call_out, int *n_calls_out)
+{
+    return queue_plan(n_lanes, n_jobs, seg_count, lane_out, first_call_out, n_calls_out);
+}
+int umx_hip_debug_queue_calls(umx_hip_ctx *ctx) { return ctx ? ctx->queue_calls : -1; }
+
 // the kernel on the caller's device buffers: (2,n) interleaved stems and mixture -> n_out buffers (2,n), queued on hip_stream
 int umx_hip_mix_stems_device(umx_hip_ctx *ctx, int n_out, const float *gains, const float *const stems_dev[4], const float *mix_dev, int n,
                              float *const *out_dev, void *hip_stream)

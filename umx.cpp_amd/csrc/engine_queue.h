@@ -1,0 +1,433 @@
+// engine_queue.h -- part of engine.hip (one translation unit: the kernels inline into their launchers): the track queue,
+// umx_hip_separate_queue: more tracks than lanes, of different lengths, a lane refilled with the next track the moment one ends.
+// Included by engine.hip behind engine_tracks.h (whose helpers it shares with tracks_once); not a stand-alone header.
+// ---------------------------------------------------------------- track queue
+namespace
+{
+// The schedule of include/umx_hip.h (umx_hip_separate_queue), stated once: umx_hip_queue_plan walks it over known segment counts, the
+// driver below over the jobs its `next` callback hands out.  Before each call every lane that wants() a job is offered one, in
+// ascending lane order (take); step() is one call of infer_batch: every busy lane runs one segment.
+struct QueueSchedule
+{
+    int n_lanes, call = 0, left[LSTMB_MAX_TRACKS] = {}; // left: calls a lane's job still needs
+    explicit QueueSchedule(int n) : n_lanes(n) {}
+    bool wants(int lane) const { return left[lane] == 0; }
+    void take(int lane, int segs) { left[lane] = segs; }
+    bool busy() const
+    {
+        for (int ln = 0; ln < n_lanes; ++ln)
+            if (left[ln] > 0)
+                return true;
+        return false;
+    }
+    void step()
+    {
+        for (int ln = 0; ln < n_lanes; ++ln)
+            if (left[ln] > 0)
+                --left[ln];
+        ++call;
+    }
+    void reset()
+    {
+        for (int ln = 0; ln < n_lanes; ++ln)
+            left[ln] = 0;
+    }
+};
+
+int queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_out, int *first_call_out, int *n_calls_out)
+{
+    if (n_lanes < 1 || n_lanes > LSTMB_MAX_TRACKS || n_jobs < 1 || !seg_count)
+        return UMX_ERR_ARG;
+    for (int j = 0; j < n_jobs; ++j)
+        if (seg_count[j] < 1)
+            return UMX_ERR_ARG;
+    QueueSchedule sched(n_lanes);
+    int j = 0;
+    for (;;)
+    {
+        for (int ln = 0; ln < n_lanes && j < n_jobs; ++ln)
+            if (sched.wants(ln))
+            {
+                if (lane_out)
+                    lane_out[j] = ln;
+                if (first_call_out)
+                    first_call_out[j] = sched.call;
+                sched.take(ln, seg_count[j++]);
+            }
+        if (!sched.busy())
+            break;
+        sched.step();
+    }
+    if (n_calls_out)
+        *n_calls_out = sched.call;
+    return UMX_OK;
+}
+} // namespace
+
+int umx_hip_ctx::queue(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags)
+{
+    if (!next || !done)
+    {
+        set_error("queue: need the next and the done callback");
+        return UMX_ERR_ARG;
+    }
+    if (flags & UMX_FLAG_RESET_SEGMENTS)
+    {
+        set_error("queue: UMX_FLAG_RESET_SEGMENTS does not go with it (the track lanes carry the jobs)");
+        return UMX_ERR_ARG;
+    }
+    if (!lstm_batched)
+    {
+        set_error("queue: needs a track-batched context (umx_hip_create_tracks with 2+ lanes, or UMX_CREATE_LSTM_BATCHED): a job's stems "
+                  "must not depend on its lane");
+        return UMX_ERR_ARG;
+    }
+    if (int rc = check_flags(flags))
+        return rc;
+    if (ph_next != -1)
+    {
+        set_error("queue: a phased segment is open (umx_hip_segment_end first)");
+        return UMX_ERR_ARG;
+    }
+    UMX_HIP_CHECK(hipSetDevice(device));
+    if (int rc = sync_all())
+        return rc;
+    // As tracks(): a persistent-kernel timeout cannot be repaired segment by segment (the overlap-add has consumed the stems); the
+    // jobs in flight are run again from their first segment (queue_run).  No call is logged for a replay: `pending` stays empty.
+    no_recovery = true;
+    pending.clear();
+    pending_lost = true;
+    const int rc = queue_run(next, done, user, mix, flags);
+    no_recovery = false;
+    pending.clear();
+    pending_lost = false;
+    return rc;
+}
+
+int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags)
+{
+    const int n_host = mix ? mix->n_out : 4;
+    const int stride = (int)((1 - 0.25f) * N); // umx.cpp:181, inference.hpp:15
+    const size_t n_sets = (size_t)B + 2;
+    if (qpool.size() < n_sets)
+        qpool.resize(n_sets);
+    if (trk.size() < (size_t)B) // (the per-slot segment stems stay with the lane)
+        trk.resize(B);
+    if (!trk_acc_ev[0])
+        for (int s = 0; s < nslots; ++s)
+            UMX_HIP_CHECK(hipEventCreateWithFlags(&trk_acc_ev[s], hipEventDisableTiming));
+
+    struct Job // a job in flight = the accumulator set it borrowed: jobs[set]
+    {
+        umx_queue_job job;
+        int lead = 0, L2 = 0, segs = 0, regions_left = 0;
+        long long uploaded = 0;
+        unsigned long long seq = 0; // order in which `next` handed the jobs out
+        bool live = false;
+    };
+    struct LaneJob
+    {
+        int set = -1, seg = 0; // the lane's job and its next segment
+    };
+    struct QRegion
+    {
+        int set, start, count;
+        hipEvent_t ready;
+    };
+    std::vector<Job> jobs(n_sets);
+    LaneJob lanes[LSTMB_MAX_TRACKS];
+    QueueSchedule sched(B);
+    std::vector<QRegion> prev, cur; // finished regions of the previous call and of the one being queued
+    std::vector<int> redo;          // after a timeout: the jobs to run again, ahead of `next`
+    bool exhausted = false, retried = false;
+    int last_slot = -1;
+    unsigned long long seq = 0;
+    queue_calls = 0;
+
+    auto drop_events = [&]() {
+        for (std::vector<QRegion> *v : {&prev, &cur})
+        {
+            for (QRegion &r : *v)
+                (void)hipEventDestroy(r.ready);
+            v->clear();
+        }
+    };
+    auto fail = [&](int rc) { // nothing of this run may still be running, or be copied, when the caller has its buffers back
+        const std::string why = err;
+        (void)sync_all();
+        drop_events();
+        set_error(why);
+        return rc;
+    };
+    // a timeout among the calls so far: umx_hip_sync has drained the device, zeroed the state and switched to the per-step driver;
+    // every job in flight starts again, in the order the jobs were taken
+    auto restart = [&]() {
+        drop_events();
+        redo.clear();
+        for (size_t s = 0; s < n_sets; ++s)
+            if (jobs[s].live)
+                redo.push_back((int)s);
+        std::sort(redo.begin(), redo.end(), [&](int a, int b) { return jobs[a].seq < jobs[b].seq; });
+        for (int s : redo)
+        {
+            jobs[s].uploaded = 0;
+            jobs[s].regions_left = jobs[s].segs;
+        }
+        for (int ln = 0; ln < B; ++ln)
+            lanes[ln] = LaneJob();
+        sched.reset();
+        last_slot = -1;
+        pending_lost = true;
+    };
+    // The regions in v to the host (event wait, then copy; the event goes as soon as it is consumed).  A job whose last region has
+    // arrived is complete -- once no launch up to its last call has timed out: done(), and its set goes back to the pool.
+    // 0: fine; > 0: an error code (set_error done); < 0: a timeout was met for the first time and the jobs in flight start again
+    auto drain = [&](std::vector<QRegion> &v) -> int {
+        std::vector<int> finished;
+        hipError_t e = hipSuccess;
+        for (QRegion &r : v)
+        {
+            Job &jb = jobs[r.set];
+            if (e == hipSuccess) // (also for a region that is all shift padding: the set is not lent again while the device works on it)
+                e = hipEventSynchronize(r.ready);
+            if (e == hipSuccess)
+                e = track_region_download(qpool[r.set], r.start, r.count, jb.lead, jb.job.length, n_host, jb.job.out, r.ready);
+            (void)hipEventDestroy(r.ready);
+            if (--jb.regions_left == 0)
+                finished.push_back(r.set);
+        }
+        v.clear();
+        if (e != hipSuccess)
+        {
+            set_error(std::string("queue: download failed: ") + hipGetErrorString(e));
+            return UMX_ERR_HIP;
+        }
+        if (finished.empty())
+            return 0;
+        bool timed_out = false;
+        for (int si = 0; si < nslots && slot[si].status; ++si)
+        {
+            unsigned st = 0;
+            if (hipMemcpy(&st, slot[si].status, sizeof st, hipMemcpyDeviceToHost) != hipSuccess)
+            {
+                set_error("queue: reading the recurrence's status failed");
+                return UMX_ERR_HIP;
+            }
+            timed_out = timed_out || st != 0;
+        }
+        if (timed_out)
+        {
+            const int rc = umx_hip_sync(this); // UMX_ERR_TIMEOUT under no_recovery
+            if (rc != UMX_ERR_TIMEOUT)
+                return rc ? rc : UMX_ERR_HIP;
+            if (retried)
+                return rc;
+            retried = true;
+            restart();
+            return -1;
+        }
+        for (int s : finished)
+        {
+            done(user, &jobs[s].job);
+            jobs[s].live = false;
+        }
+        return 0;
+    };
+
+    for (;;)
+    {
+        // ---- every lane without a track asks for one, in ascending lane order
+        bool restarted = false;
+        for (int ln = 0; ln < B && !restarted; ++ln)
+        {
+            if (!sched.wants(ln) || (redo.empty() && exhausted))
+                continue;
+            int set = -1;
+            if (!redo.empty())
+            {
+                set = redo.front();
+                redo.erase(redo.begin());
+            }
+            else
+            {
+                auto free_set = [&](size_t need) { // the smallest free set that is large enough, else the largest free one (it grows)
+                    int best = -1;
+                    for (size_t s = 0; s < n_sets; ++s)
+                    {
+                        if (jobs[s].live)
+                            continue;
+                        if (best < 0)
+                            best = (int)s;
+                        const size_t cb = qpool[best].cap, cs = qpool[s].cap;
+                        if (cb >= need ? (cs >= need && cs < cb) : cs > cb)
+                            best = (int)s;
+                    }
+                    return best;
+                };
+                if (free_set(0) < 0) // every set is lent: the previous call's regions go to the host before this call is queued
+                {
+                    const int d = drain(prev);
+                    if (d > 0)
+                        return fail(d);
+                    if (d < 0)
+                    {
+                        restarted = true;
+                        break;
+                    }
+                }
+                umx_queue_job j;
+                memset(&j, 0, sizeof j);
+                const int r = next(user, &j);
+                if (r == 0)
+                {
+                    exhausted = true; // (and next is not called again)
+                    continue;
+                }
+                if (r < 0)
+                {
+                    set_error("queue: the next callback stopped the run");
+                    return fail(UMX_ERR_ARG);
+                }
+                bool ok = j.audio && j.length >= 1 && j.shift_offset < UMX_MAX_SHIFT;
+                for (int m = 0; m < n_host; ++m)
+                    ok = ok && j.out[m];
+                if (!ok)
+                {
+                    set_error("queue: a job needs audio, its n_out outputs, length >= 1 and shift offset < 22050");
+                    return fail(UMX_ERR_ARG);
+                }
+                // umx.cpp:120-122 (see tracks_once)
+                const long long l2 = j.shift_offset < 0 ? (long long)j.length
+                                                        : (long long)j.length + std::max(UMX_MAX_SHIFT - j.shift_offset, j.shift_offset);
+                if (l2 > 0x7fffffff / 2)
+                {
+                    set_error("queue: a job is too long");
+                    return fail(UMX_ERR_ARG);
+                }
+                set = free_set((size_t)l2);
+                if (int rc = track_bufs_grow(qpool[set], (size_t)l2))
+                    return fail(rc);
+                Job &jb = jobs[set];
+                jb.job = j;
+                jb.lead = j.shift_offset < 0 ? 0 : j.shift_offset;
+                jb.L2 = (int)l2;
+                jb.segs = (int)((l2 + stride - 1) / stride);
+                jb.regions_left = jb.segs;
+                jb.uploaded = 0;
+                jb.seq = seq++;
+                jb.live = true;
+            }
+            if (int rc = track_bufs_segs(trk[ln]))
+                return fail(rc);
+            lanes[ln].set = set;
+            lanes[ln].seg = 0;
+            sched.take(ln, jobs[set].segs);
+        }
+        if (restarted)
+            continue;
+        if (!sched.busy()) // no lane holds a track: what is left is the last call's regions
+        {
+            if (prev.empty())
+                break;
+            const int d = drain(prev);
+            if (d > 0)
+                return fail(d);
+            continue;
+        }
+
+        // ---- one call: the next segment of every lane's job
+        const int si = next_slot();
+        hipStream_t st = slot[si].stream;
+        const float *ain[LSTMB_MAX_TRACKS] = {};
+        int nn[LSTMB_MAX_TRACKS] = {}, seg_off[LSTMB_MAX_TRACKS] = {}, nl = 0;
+        float *outs[4 * LSTMB_MAX_TRACKS] = {};
+        bool waited = false;
+        for (int ln = 0; ln < B; ++ln)
+        {
+            if (lanes[ln].set < 0)
+                continue;
+            Job &jb = jobs[lanes[ln].set];
+            TrackBufs &tb_ = qpool[lanes[ln].set];
+            const long long so = (long long)lanes[ln].seg * stride;
+            if (lanes[ln].seg == 0)
+            {
+                // A refilled lane starts clean, in stream order: behind the previous call (the lane's previous occupant has run its last
+                // recurrence) the lane's state slice, the set's accumulators and the shift padding of its padded input are zeroed in one
+                // launch.  The set itself is free: the host has its last region.  The span of `in` the uploads fill is not touched, so they
+                // need no ordering against this kernel.
+                if (!waited && last_slot >= 0)
+                    (void)hipStreamWaitEvent(st, trk_acc_ev[last_slot], 0);
+                waited = true;
+                TrackBeginSpans sp = {};
+                for (int t = 0; t < 4; ++t)
+                {
+                    sp.p[t] = tb_.out[t];
+                    sp.n[t] = 2 * (unsigned long long)jb.L2;
+                }
+                sp.p[4] = tb_.sumw;
+                sp.n[4] = (unsigned long long)jb.L2;
+                sp.p[5] = tb_.in;
+                sp.n[5] = 2 * (unsigned long long)jb.lead;
+                sp.p[6] = tb_.in + 2 * ((size_t)jb.lead + (size_t)jb.job.length);
+                sp.n[6] = 2 * (unsigned long long)(jb.L2 - jb.lead - jb.job.length);
+                sp.p[7] = state + state_floats() * (size_t)ln;
+                sp.n[7] = state_floats();
+                sp.count = TRACK_BEGIN_SPANS;
+                launch_track_begin(sp, st);
+            }
+            if (track_upload_until(tb_.in, jb.job.audio, jb.job.length, jb.lead, jb.uploaded, so + N) != hipSuccess)
+            {
+                set_error("queue: upload failed");
+                return fail(UMX_ERR_HIP);
+            }
+            seg_off[ln] = (int)so;
+            ain[ln] = tb_.in + 2 * (size_t)so;
+            nn[ln] = std::min(N, jb.L2 - (int)so);
+            for (int t = 0; t < 4; ++t)
+                outs[4 * ln + t] = trk[ln].seg[si][t];
+            nl = ln + 1;
+        }
+        pending_lost = true;
+        if (int rc = infer_batch(nl, ain, nn, outs, flags))
+            return fail(rc);
+        ++queue_calls;
+        if (last_slot >= 0) // accumulate in segment order (two segments overlap by a quarter)
+            (void)hipStreamWaitEvent(st, trk_acc_ev[last_slot], 0);
+        for (int ln = 0; ln < nl; ++ln)
+        {
+            if (!ain[ln])
+                continue;
+            const int set = lanes[ln].set;
+            QRegion rg;
+            rg.set = set;
+            rg.start = seg_off[ln];
+            rg.count = track_region(qpool[set], trk[ln].seg[si], seg_off[ln], nn[ln], jobs[set].L2, stride, mix, st);
+            if (hipEventCreateWithFlags(&rg.ready, hipEventDisableTiming) != hipSuccess)
+            {
+                set_error("queue: event creation failed");
+                return fail(UMX_ERR_HIP);
+            }
+            if (hipEventRecord(rg.ready, st) != hipSuccess)
+            {
+                (void)hipEventDestroy(rg.ready);
+                set_error("queue: event creation failed");
+                return fail(UMX_ERR_HIP);
+            }
+            cur.push_back(rg);
+            if (++lanes[ln].seg == jobs[set].segs) // the lane is free for the next call; the job lives on until its regions are down
+                lanes[ln] = LaneJob();
+        }
+        (void)hipEventRecord(trk_acc_ev[si], st);
+        last_slot = si;
+        sched.step();
+        // ---- while the device runs this call: the regions of the one before
+        const int d = drain(prev);
+        if (d > 0)
+            return fail(d);
+        if (d < 0)
+            continue;
+        prev.swap(cur);
+    }
+    UMX_HIP_CHECK(hipGetLastError());
+    return umx_hip_sync(this);
+}

@@ -37,6 +37,107 @@ int umx_hip_ctx::tracks(int nt, const float *const *audio_host, const int *lengt
     return rc;
 }
 
+// ---------------------------------------------------------------- what the whole-track drivers share (tracks_once, engine_queue.h)
+// grow-only accumulators of one track: the (shifted) track, 4 stems, the weight sum, `frames` frames each
+int umx_hip_ctx::track_bufs_grow(TrackBufs &tb_, size_t frames)
+{
+    if (frames <= tb_.cap)
+        return UMX_OK;
+    const size_t cap = frames + frames / 8;
+    for (float **p : {&tb_.in, &tb_.out[0], &tb_.out[1], &tb_.out[2], &tb_.out[3], &tb_.sumw})
+        if (*p)
+        {
+            allocs.erase(std::find(allocs.begin(), allocs.end(), (void *)*p));
+            (void)hipFree(*p);
+            *p = nullptr;
+        }
+    tb_.cap = 0;
+    if (int rc = dalloc(&tb_.in, 2 * cap, false))
+        return rc;
+    for (int t = 0; t < 4; ++t)
+        if (int rc = dalloc(&tb_.out[t], 2 * cap, false))
+            return rc;
+    if (int rc = dalloc(&tb_.sumw, cap, false))
+        return rc;
+    tb_.cap = cap;
+    return UMX_OK;
+}
+
+// the per-slot segment stems of a track lane
+int umx_hip_ctx::track_bufs_segs(TrackBufs &tb_)
+{
+    if (!tb_.seg[0][0])
+        for (int s = 0; s < nslots; ++s)
+            for (int t = 0; t < 4; ++t)
+                if (int rc = dalloc(&tb_.seg[s][t], (size_t)2 * N, false))
+                    return rc;
+    return UMX_OK;
+}
+
+// The track goes up segment by segment (round 6): a call needs the samples up to the end of its last segment, and the rest of a
+// pageable upload (14 GB/s: 15 ms for ten minutes of stereo) runs while the device is busy with the segments before it -- the
+// slots' streams do not wait for the null stream, and launches are queued ahead of the copy.
+// Samples of the padded signal `in_dev` (the track behind `lead` frames of silence) below `padded_end` must be there; `uploaded`:
+// host samples of the track already on the device.
+hipError_t umx_hip_ctx::track_upload_until(float *in_dev, const float *audio_host, int length, int lead, long long &uploaded, long long padded_end)
+{
+    const long long want = std::min<long long>(length, padded_end - lead);
+    if (want <= uploaded)
+        return hipSuccess;
+    const hipError_t e = hipMemcpy(in_dev + 2 * ((size_t)lead + (size_t)uploaded), audio_host + 2 * (size_t)uploaded,
+                                   sizeof(float) * 2 * (size_t)(want - uploaded), hipMemcpyHostToDevice);
+    uploaded = want;
+    return e;
+}
+
+// the mix of `count` frames from padded frame `stem_start` on, written over the first n_out of the four stem buffers there
+// (the track's accumulators, or an ensemble's means from frame 0 on); column 4 is `in` (the track's padded input) from in_start on
+void umx_hip_ctx::track_mix(const MixSpec &mix, float *const stems[4], size_t stem_start, const float *in, size_t in_start, int count, hipStream_t st)
+{
+    const float2 *src[MIX_COLUMNS];
+    float2 *dst[UMX_MAX_MIX_OUTPUTS];
+    for (int t = 0; t < 4; ++t)
+    {
+        src[t] = reinterpret_cast<const float2 *>(stems[t]) + stem_start;
+        dst[t] = reinterpret_cast<float2 *>(stems[t]) + stem_start;
+    }
+    src[MIX_MIXTURE] = reinterpret_cast<const float2 *>(in) + in_start;
+    launch_stem_mix(mix, src, dst, count, st);
+}
+
+// A segment's stems `seg` (nn frames at padded frame `offset` of a track of L2 padded frames) blended into the track's accumulators.
+// A sample is final once the segment that starts at or before it and the one before that have been blended in: region
+// [offset, offset + stride) right after this segment.  It is normalised there and then and, with `mix`, mixed (over its stems).
+// Returns the region's frame count.
+int umx_hip_ctx::track_region(const TrackBufs &tb_, float *const seg_stems[4], int offset, int nn, int L2, int stride, const MixSpec *mix, hipStream_t st)
+{
+    Stems4 tk, seg;
+    for (int t = 0; t < 4; ++t)
+    {
+        tk.p[t] = reinterpret_cast<float2 *>(tb_.out[t]);
+        seg.p[t] = reinterpret_cast<float2 *>(seg_stems[t]);
+    }
+    hipLaunchKernelGGL(track_accumulate_kernel, dim3((nn + 255) / 256, 4), dim3(256), 0, st, tk, tb_.sumw, seg, offset, nn, N);
+    const int count = (int)std::min<long long>((long long)offset + stride, L2) - offset;
+    hipLaunchKernelGGL(track_normalise_kernel, dim3((count + 255) / 256, 4), dim3(256), 0, st, tk, tb_.sumw, offset, count);
+    if (mix)
+        track_mix(*mix, tb_.out, (size_t)offset, tb_.in, (size_t)offset, count, st);
+    return count;
+}
+
+// umx.cpp:136-147: a finished region without the shift, to the track's n_host host buffers, once `ready` has passed
+hipError_t umx_hip_ctx::track_region_download(const TrackBufs &tb_, int start, int count, int lead, int length, int n_host, float *const *out_host,
+                                              hipEvent_t ready)
+{
+    const long long lo = std::max<long long>(start, lead), hi = std::min<long long>((long long)start + count, (long long)lead + length);
+    if (hi <= lo)
+        return hipSuccess;
+    hipError_t cerr = hipEventSynchronize(ready);
+    for (int t = 0; t < n_host && cerr == hipSuccess; ++t)
+        cerr = hipMemcpy(out_host[t] + 2 * (size_t)(lo - lead), tb_.out[t] + 2 * (size_t)lo, sizeof(float) * 2 * (size_t)(hi - lo), hipMemcpyDeviceToHost);
+    return cerr;
+}
+
 int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *length_in, const int *shift_offset, float *const *out_host,
                              unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate, bool ensemble,
                              const MixSpec *mix)
@@ -128,32 +229,11 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
         trk.resize(seg_lanes);
     for (int ln = 0; ln < seg_lanes; ++ln)
     {
-        TrackBufs &tb_ = trk[ln];
-        if (ln < nt && (size_t)L2[ln] > tb_.cap) // grow-only track buffers
-        {
-            const size_t cap = (size_t)L2[ln] + (size_t)L2[ln] / 8;
-            for (float **p : {&tb_.in, &tb_.out[0], &tb_.out[1], &tb_.out[2], &tb_.out[3], &tb_.sumw})
-                if (*p)
-                {
-                    allocs.erase(std::find(allocs.begin(), allocs.end(), (void *)*p));
-                    (void)hipFree(*p);
-                    *p = nullptr;
-                }
-            tb_.cap = 0;
-            if (int rc = dalloc(&tb_.in, 2 * cap, false))
+        if (ln < nt)
+            if (int rc = track_bufs_grow(trk[ln], (size_t)L2[ln]))
                 return rc;
-            for (int t = 0; t < 4; ++t)
-                if (int rc = dalloc(&tb_.out[t], 2 * cap, false))
-                    return rc;
-            if (int rc = dalloc(&tb_.sumw, cap, false))
-                return rc;
-            tb_.cap = cap;
-        }
-        if (!tb_.seg[0][0])
-            for (int s = 0; s < nslots; ++s)
-                for (int t = 0; t < 4; ++t)
-                    if (int rc = dalloc(&tb_.seg[s][t], (size_t)2 * N, false))
-                        return rc;
+        if (int rc = track_bufs_segs(trk[ln]))
+            return rc;
     }
     if (!trk_acc_ev[0])
         for (int s = 0; s < nslots; ++s)
@@ -235,28 +315,12 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
         if (resampled[ln] || ensemble)
             uploaded[ln] = length[ln];
     auto upload_until = [&](int ti, long long padded_end) -> hipError_t { // samples of the padded signal below `padded_end` must be there
-        const long long want = std::min<long long>(length[ti], padded_end - lead[ti]);
-        if (want <= uploaded[ti])
-            return hipSuccess;
-        const hipError_t e = hipMemcpy(trk[ti].in + 2 * ((size_t)lead[ti] + (size_t)uploaded[ti]), audio_host[ti] + 2 * (size_t)uploaded[ti],
-                                       sizeof(float) * 2 * (size_t)(want - uploaded[ti]), hipMemcpyHostToDevice);
-        uploaded[ti] = want;
-        return e;
+        return track_upload_until(trk[ti].in, audio_host[ti], length[ti], lead[ti], uploaded[ti], padded_end);
     };
 
-    // the mix of `count` frames of lane ln from padded frame `start` on, written over the lane's first n_out stem
-    // accumulators there (stems = those accumulators, or the ensemble's means from frame 0 on); column 4 is the lane's own padded
-    // input at the same index
+    // the mix of `count` frames of lane ln (track_mix); column 4 is the lane's own padded input at the same index
     auto queue_mix = [&](int ln, float *const stems[4], size_t stem_start, size_t in_start, int count, hipStream_t st) {
-        const float2 *src[MIX_COLUMNS];
-        float2 *dst[UMX_MAX_MIX_OUTPUTS];
-        for (int t = 0; t < 4; ++t)
-        {
-            src[t] = reinterpret_cast<const float2 *>(stems[t]) + stem_start;
-            dst[t] = reinterpret_cast<float2 *>(stems[t]) + stem_start;
-        }
-        src[MIX_MIXTURE] = reinterpret_cast<const float2 *>(trk[ln].in) + in_start;
-        launch_stem_mix(*mix, src, dst, count, st);
+        track_mix(*mix, stems, stem_start, trk[ln].in, in_start, count, st);
     };
 
     const float total_reps = std::ceil((float)L2max / (float)stride); // umx.cpp:208 (of the longest track)
@@ -326,23 +390,14 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
             if (!ain[ln])
                 continue;
             const int ti = reset_lanes ? 0 : ln, offset = seg_off[ln];
-            Stems4 tk, seg;
-            for (int t = 0; t < 4; ++t)
-            {
-                tk.p[t] = reinterpret_cast<float2 *>(trk[ti].out[t]);
-                seg.p[t] = reinterpret_cast<float2 *>(trk[ln].seg[si][t]);
-            }
-            hipLaunchKernelGGL(track_accumulate_kernel, dim3((nn[ln] + 255) / 256, 4), dim3(256), 0, st, tk, trk[ti].sumw, seg, offset, nn[ln], N);
             Region rg;
             rg.lane = ti;
             rg.start = offset;
-            rg.count = (int)std::min<long long>((long long)offset + stride, L2[ti]) - offset;
-            hipLaunchKernelGGL(track_normalise_kernel, dim3((rg.count + 255) / 256, 4), dim3(256), 0, st, tk, trk[ti].sumw, rg.start, rg.count);
-            if (ensemble) // nothing is downloaded region by region: the lanes' stems are averaged behind the last segment
+            // the region is final: its mix goes over its stems right here, before `ready` (a resampled track is mixed whole, below;
+            // an ensemble's lanes are averaged behind the last segment, nothing is downloaded region by region)
+            rg.count = track_region(trk[ti], trk[ln].seg[si], offset, nn[ln], L2[ti], stride, mix && !ensemble && !resampled[ti] ? mix : nullptr, st);
+            if (ensemble)
                 continue;
-            // the region is final: its mix goes over its stems right here, before `ready` (a resampled track is mixed whole, below)
-            if (mix && !resampled[ti])
-                queue_mix(ti, trk[ti].out, (size_t)rg.start, (size_t)rg.start, rg.count, st);
             if (hipEventCreateWithFlags(&rg.ready, hipEventDisableTiming) != hipSuccess || hipEventRecord(rg.ready, st) != hipSuccess)
             {
                 cleanup();
@@ -410,15 +465,8 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
         const int ln = rg.lane;
         if (resampled[ln])
             continue;
-        const long long lo = std::max<long long>(rg.start, lead[ln]),
-                        hi = std::min<long long>((long long)rg.start + rg.count, (long long)lead[ln] + length[ln]);
-        if (hi <= lo)
-            continue;
         if (cerr == hipSuccess)
-            cerr = hipEventSynchronize(rg.ready);
-        for (int t = 0; t < n_host && cerr == hipSuccess; ++t)
-            cerr = hipMemcpy(out_host[n_host * ln + t] + 2 * (size_t)(lo - lead[ln]), trk[ln].out[t] + 2 * (size_t)lo,
-                             sizeof(float) * 2 * (size_t)(hi - lo), hipMemcpyDeviceToHost);
+            cerr = track_region_download(trk[ln], rg.start, rg.count, lead[ln], length[ln], n_host, out_host + n_host * ln, rg.ready);
     }
     cleanup();
     bool synced = false;

@@ -77,4 +77,47 @@ __global__ void track_normalise_kernel(Stems4 track, const float *sum_w, int sta
     track.p[t][k] = o;
 }
 
+// Track queue (engine_queue.h): what a job must find clean when it takes a lane, zeroed in ONE launch in stream order --
+// the spans of its accumulator set (4 stems and the weight sum over the padded length, the shift padding either side of the track
+// in the padded input) and the lane's slice of the streaming LSTM state (umx.cpp:167-171, 186-195).
+#define TRACK_BEGIN_SPANS 8
+struct TrackBeginSpans
+{
+    float *p[TRACK_BEGIN_SPANS]; // each at least 4-byte aligned
+    unsigned long long n[TRACK_BEGIN_SPANS]; // floats
+    int count;
+};
+
+// 16-byte stores over the aligned body of every span, scalar stores for the up to 3 floats either side; grid-stride
+__global__ void track_begin_kernel(TrackBeginSpans sp)
+{
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (size_t)gridDim.x * blockDim.x;
+    for (int k = 0; k < sp.count; ++k)
+    {
+        float *p = sp.p[k];
+        const size_t n = (size_t)sp.n[k];
+        size_t head = ((16 - (reinterpret_cast<size_t>(p) & 15)) & 15) / 4;
+        if (head > n)
+            head = n;
+        const size_t nv = (n - head) / 4, tail0 = head + 4 * nv;
+        if (tid < head)
+            p[tid] = 0.f;
+        float4 *q = reinterpret_cast<float4 *>(p + head);
+        for (size_t i = tid; i < nv; i += nthreads)
+            q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tid < n - tail0)
+            p[tail0 + tid] = 0.f;
+    }
+}
+
+inline void launch_track_begin(const TrackBeginSpans &sp, hipStream_t st)
+{
+    unsigned long long total = 0;
+    for (int k = 0; k < sp.count; ++k)
+        total += sp.n[k];
+    const unsigned long long want = (total / 4 + 255) / 256;
+    const unsigned blocks = want < 1 ? 1u : want > 2048 ? 2048u : (unsigned)want;
+    hipLaunchKernelGGL(track_begin_kernel, dim3(blocks), dim3(256), 0, st, sp);
+}
+
 } // namespace umx

@@ -2,7 +2,11 @@
 // up to 16 files at a time.  The reference is one track per process; on the GPU the LSTM recurrence of one track is
 // bound by hand-off latency, not arithmetic, so the engine runs several tracks as track lanes of ONE context
 // (umx_hip_create_tracks / umx_hip_separate_tracks): per file the same shift_inference -> split_inference, the same
-// four stems, written to <out dir>/<wav stem>/target_{0..3}.wav.  More than 16 files are taken 16 at a time.
+// four stems, written to <out dir>/<wav stem>/target_{0..3}.wav.  More files than track lanes (at most 64; UMX_BATCH_LANES=<1..64> caps
+// them) go through the track queue (umx_hip_separate_queue): a lane takes the next file the moment its file ends, one
+// thread decodes files ahead (at most lanes + 2 decoded files in memory), one writes the stems, and the GPU waits for neither.
+// UMX_BATCH_QUEUE=0 forces the pass-by-pass loop (`lanes` files decoded, run for as long as the longest, written), which also serves
+// UMX_RESAMPLE=1 (the queue takes 44.1 kHz tracks only).  Either way a file's stems and its output directory are the same.
 // Environment: UMX_DEVICE, UMX_NO_WIENER, UMX_WIENER_ITERS, UMX_SHIFT_OFFSET, UMX_RESAMPLE (as umx-cli: files of any rate of
 // 8 .. 192 kHz, mixed rates in one pass through umx_hip_separate_tracks_rate, stems written at each file's rate), UMX_TARGETS and
 // UMX_RESIDUAL (as umx-cli: target_<t>.wav of the chosen targets and residual.wav per file; host/targets_env.h), UMX_SOFTMASK (as umx-cli),
@@ -13,11 +17,15 @@
 #include "targets_env.h"
 
 #include <chrono>
+#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
+#include <deque>
 #include <filesystem>
+#include <mutex>
 #include <set>
 #include <string>
+#include <thread>
 #include <vector>
 
 static int env_int(const char *name, int dflt)
@@ -25,6 +33,68 @@ static int env_int(const char *name, int dflt)
     const char *v = getenv(name);
     return v && *v ? atoi(v) : dflt;
 }
+
+// The track queue's two ends.  A decoded file waits in `decoded` until a lane takes it (next); its stems wait in `unwritten` from the
+// moment they are complete (done) until the writer has written them.  `permits` bounds the decoded files in memory (waiting or in a
+// lane) to lanes + 2 -- as many as the engine can have in flight, so the reader can always decode the file `next` waits for --
+// and max_unwritten the finished ones: done waits for the writer rather than let stems pile up.
+struct FileJob
+{
+    int index = 0, n = 0;
+    float *audio = nullptr;
+    std::vector<std::vector<float>> stems;
+};
+struct BatchQueue
+{
+    std::mutex m;
+    std::condition_variable cv;
+    std::deque<FileJob *> decoded, unwritten;
+    int permits = 0, per_file = 4, shift_offset = 0;
+    size_t max_unwritten = 0;
+    bool reader_done = false, no_more_stems = false;
+    double audio_secs = 0;
+    std::string error; // the first thing that went wrong, on any thread: the run stops
+
+    static int next(void *user, umx_queue_job *job)
+    {
+        BatchQueue &q = *static_cast<BatchQueue *>(user);
+        FileJob *fj = nullptr;
+        {
+            std::unique_lock<std::mutex> lock(q.m);
+            q.cv.wait(lock, [&]() { return !q.decoded.empty() || q.reader_done || !q.error.empty(); });
+            if (!q.error.empty())
+                return -1;
+            if (q.decoded.empty())
+                return 0;
+            fj = q.decoded.front();
+            q.decoded.pop_front();
+        }
+        fj->stems.resize(q.per_file);
+        for (int t = 0; t < q.per_file; ++t)
+        {
+            fj->stems[t].resize((size_t)2 * fj->n);
+            job->out[t] = fj->stems[t].data();
+        }
+        job->audio = fj->audio;
+        job->length = fj->n;
+        job->shift_offset = q.shift_offset;
+        job->tag = fj;
+        return 1;
+    }
+    static void done(void *user, const umx_queue_job *job)
+    {
+        BatchQueue &q = *static_cast<BatchQueue *>(user);
+        FileJob *fj = static_cast<FileJob *>(job->tag);
+        umx_wav_free(fj->audio);
+        fj->audio = nullptr;
+        std::unique_lock<std::mutex> lock(q.m);
+        ++q.permits;
+        q.cv.notify_all();
+        q.cv.wait(lock, [&]() { return q.unwritten.size() < q.max_unwritten || !q.error.empty(); });
+        q.unwritten.push_back(fj);
+        q.cv.notify_all();
+    }
+};
 
 int main(int argc, const char **argv)
 {
@@ -35,7 +105,13 @@ int main(int argc, const char **argv)
     }
     const std::string model_file = argv[1], out_dir = argv[2];
     const int nfiles = argc - 3;
-    int lanes = std::min(nfiles, UMX_MAX_TRACKS);
+    const int lanes_cap = env_int("UMX_BATCH_LANES", UMX_MAX_TRACKS);
+    if (lanes_cap < 1 || lanes_cap > UMX_MAX_TRACKS)
+    {
+        fprintf(stderr, "UMX_BATCH_LANES: need 1 .. %d, got %d\n", UMX_MAX_TRACKS, lanes_cap);
+        return 1;
+    }
+    int lanes = std::min(std::min(nfiles, UMX_MAX_TRACKS), lanes_cap);
     char err[UMX_ERRLEN] = "";
     umx_target_choice choice;
     if (!umx_targets_from_env(choice))
@@ -89,15 +165,126 @@ int main(int argc, const char **argv)
     double audio_secs = 0, wall = 0;
     const int first_rand_shift = UMX_REFERENCE_SHIFT; // glibc's first unseeded rand() % 22050 (not rand() here: umx_hip.h)
     const bool resample = env_int("UMX_RESAMPLE", 0) != 0;
-    std::set<std::string> used_names; // output directories are named after the file's stem: a/x.wav and b/x.wav must not collide
-    for (int f0 = 0; f0 < nfiles; f0 += lanes)
+    // output directories are named after the file's stem, in argument order: a/x.wav and b/x.wav must not collide (the second is x_2)
+    std::set<std::string> used_names;
+    std::vector<std::string> names(nfiles);
+    for (int f = 0; f < nfiles; ++f)
+    {
+        names[f] = std::filesystem::path(argv[3 + f]).stem().string();
+        for (int k = 2; !used_names.insert(names[f]).second; ++k)
+            names[f] = std::filesystem::path(argv[3 + f]).stem().string() + "_" + std::to_string(k);
+    }
+    // umx.cpp:75-96: the buffers of file f to its directory
+    auto write_file = [&](int f, float *const *bufs, int n, int rate_, char *err_) -> bool {
+        const std::filesystem::path dir = std::filesystem::path(out_dir) / names[f];
+        std::error_code ec;
+        std::filesystem::create_directories(dir, ec);
+        for (int t = 0; t < per_file; ++t)
+        {
+            if (!mixed && !choice.write[t]) // a target that did not run (UMX_TARGETS): a silent slot
+                continue;
+            const std::string p = (dir / (mixed ? mixc.name[t] + ".wav" : choice.file[t])).string();
+            if (resample ? umx_wav_write_f32_rate(p.c_str(), bufs[t], n, rate_, err_) : umx_wav_write_f32(p.c_str(), bufs[t], n, err_))
+                return false;
+        }
+        return true;
+    };
+    const int shift_offset = env_int("UMX_SHIFT_OFFSET", -1) < 0 ? first_rand_shift : env_int("UMX_SHIFT_OFFSET", -1);
+    // more files than lanes: the track queue (a one-lane context is not track-batched and keeps the loop, as UMX_RESAMPLE does)
+    const bool queued = nfiles > lanes && env_int("UMX_BATCH_QUEUE", 1) != 0 && !resample && umx_hip_lstm_is_batched(ctx);
+    if (queued)
+    {
+        BatchQueue q;
+        q.permits = lanes + 2;
+        q.max_unwritten = (size_t)lanes + 2;
+        q.per_file = per_file;
+        q.shift_offset = shift_offset;
+        std::thread reader([&]() {
+            for (int f = 0; f < nfiles; ++f)
+            {
+                {
+                    std::unique_lock<std::mutex> lock(q.m);
+                    q.cv.wait(lock, [&]() { return q.permits > 0 || !q.error.empty(); });
+                    if (!q.error.empty())
+                        break;
+                    --q.permits;
+                }
+                FileJob *fj = new FileJob;
+                fj->index = f;
+                int ch = 0;
+                char rerr[UMX_ERRLEN] = "";
+                const bool bad = umx_wav_load(argv[3 + f], &fj->audio, &fj->n, &ch, rerr) != 0; // umx.cpp:56
+                std::lock_guard<std::mutex> lock(q.m);
+                if (bad)
+                {
+                    q.error = std::string(argv[3 + f]) + ": " + rerr;
+                    delete fj;
+                    break;
+                }
+                q.audio_secs += fj->n / (double)UMX_SAMPLE_RATE;
+                q.decoded.push_back(fj);
+                q.cv.notify_all();
+            }
+            std::lock_guard<std::mutex> lock(q.m);
+            q.reader_done = true;
+            q.cv.notify_all();
+        });
+        std::thread writer([&]() {
+            for (;;)
+            {
+                FileJob *fj = nullptr;
+                {
+                    std::unique_lock<std::mutex> lock(q.m);
+                    q.cv.wait(lock, [&]() { return !q.unwritten.empty() || q.no_more_stems; });
+                    if (q.unwritten.empty())
+                        return;
+                    fj = q.unwritten.front();
+                }
+                char werr[UMX_ERRLEN] = "";
+                float *bufs[UMX_MAX_MIX_OUTPUTS];
+                for (int t = 0; t < per_file; ++t)
+                    bufs[t] = fj->stems[t].data();
+                const bool ok = write_file(fj->index, bufs, fj->n, UMX_SAMPLE_RATE, werr);
+                std::lock_guard<std::mutex> lock(q.m);
+                q.unwritten.pop_front(); // (counted until it is written: the stems are in memory until then)
+                if (!ok && q.error.empty())
+                    q.error = werr;
+                delete fj;
+                q.cv.notify_all();
+            }
+        });
+        const auto t0 = std::chrono::steady_clock::now();
+        const int qrc = umx_hip_separate_queue(ctx, BatchQueue::next, BatchQueue::done, &q, mixc.n_out, mixed ? mixc.gains : nullptr, flags);
+        wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        {
+            std::lock_guard<std::mutex> lock(q.m);
+            if (qrc && q.error.empty())
+                q.error = std::string("inference failed: ") + umx_hip_last_error(ctx);
+            q.no_more_stems = true;
+            q.cv.notify_all();
+        }
+        reader.join();
+        writer.join();
+        for (FileJob *fj : q.decoded) // (decoded ahead of a run that stopped)
+        {
+            umx_wav_free(fj->audio);
+            delete fj;
+        }
+        if (!q.error.empty())
+        {
+            fprintf(stderr, "%s\n", q.error.c_str());
+            return 1;
+        }
+        audio_secs = q.audio_secs;
+    }
+    for (int f0 = 0; !queued && f0 < nfiles; f0 += lanes) // pass by pass: `lanes` files decoded, run as long as the longest, written
     {
         const int nb = std::min(lanes, nfiles - f0);
         std::vector<float *> audio(nb, nullptr);
         // umx.cpp:115 draws rand() % 22050 once per PROCESS, and the reference never seeds rand(): every run of its CLI
         // shifts by the same 4033 samples.  Every file here gets that value too (not a fresh draw per batch of lanes),
         // so a file's stems do not depend on where in the argument list it stands; UMX_SHIFT_OFFSET overrides it.
-        std::vector<int> n(nb, 0), shift(nb, env_int("UMX_SHIFT_OFFSET", -1) < 0 ? first_rand_shift : env_int("UMX_SHIFT_OFFSET", -1));
+        std::vector<int> n(nb, 0), shift(nb, shift_offset);
         std::vector<std::vector<float>> stems(per_file * nb);
         std::vector<float *> out(per_file * nb);
         std::vector<const float *> in(nb);
@@ -131,23 +318,10 @@ int main(int argc, const char **argv)
         wall += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         for (int i = 0; i < nb; ++i)
         {
-            std::string name = std::filesystem::path(argv[3 + f0 + i]).stem().string();
-            for (int k = 2; !used_names.insert(name).second; ++k)
-                name = std::filesystem::path(argv[3 + f0 + i]).stem().string() + "_" + std::to_string(k);
-            const std::filesystem::path dir = std::filesystem::path(out_dir) / name;
-            std::error_code ec;
-            std::filesystem::create_directories(dir, ec);
-            for (int t = 0; t < per_file; ++t) // umx.cpp:75-96
+            if (!write_file(f0 + i, &out[per_file * i], n[i], rate[i], err))
             {
-                if (!mixed && !choice.write[t]) // a target that did not run (UMX_TARGETS): a silent slot
-                    continue;
-                const std::string p = (dir / (mixed ? mixc.name[t] + ".wav" : choice.file[t])).string();
-                if (resample ? umx_wav_write_f32_rate(p.c_str(), out[per_file * i + t], n[i], rate[i], err)
-                             : umx_wav_write_f32(p.c_str(), out[per_file * i + t], n[i], err))
-                {
-                    fprintf(stderr, "%s\n", err);
-                    return 1;
-                }
+                fprintf(stderr, "%s\n", err);
+                return 1;
             }
             umx_wav_free(audio[i]);
         }
