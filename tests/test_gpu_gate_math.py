@@ -86,10 +86,10 @@ def _state(eng, lane):
     return eng.stream_get() if eng.tracks == 1 else eng.track_stream_get(lane)
 
 
-def _recurrence_case(pkg, targets, test, H, tracks, T, kernel, check_lanes, which, sat=True, flags=0, loud_lane=None):
+def _recurrence_case(pkg, targets, test, H, tracks, T, kernel, check_lanes, which, sat=True, flags=0, loud_lane=None, after_run=None):
     """Two calls of a context; the network stages of the second against float64 on `check_lanes`, and the saturation shares from the
     float64 restatement on the engine's own fc1 tap.  loud_lane: that lane's audio at 30 times the usual level (fc1's tanh_epi
-    saturates)."""
+    saturates).  after_run(eng): further assertions on the context after the second call (tests/test_gpu_one_track_f64.py)."""
     N = sf._N(T, 517)
     level = np.float32(sf.SAT_INPUT_LEVEL if sat else 1.0)
     rep = sf.Report()
@@ -102,6 +102,8 @@ def _recurrence_case(pkg, targets, test, H, tracks, T, kernel, check_lanes, whic
             waves[loud_lane] = geo._audio(pkg, N, 1300) * np.float32(30.0)
         geo._run(pkg, eng, waves, flags)
         assert eng.lstm_kernel_name() == kernel, eng.lstm_kernel_name()
+        if after_run is not None:
+            after_run(eng)
         for b in check_lanes:
             where = f"{test}, {'saturating' if sat else 'plain'} weights, flags {flags:#x}" + (", audio x 30" if b == loud_lane else "")
             c0 = states[b].reshape(4, 3, 2, 2, H // 2)[:, :, :, 1]
