@@ -48,6 +48,10 @@ FLOOR = 2e-7                 # ... plus this (about two float32 ulps, relative),
 # lstm 0.7 / 0.7 (1.1 / 1.1), fc2 (K = 2048) 3.0 / 3.1, mask 2.2 / 2.3; target_mag 1.0 everywhere.  No check uses more than 0.61 of its
 # bound (fc2 at hidden 1024).  tests/bf16x3_emu.py reproduces fc1's and fc2's figures when the emulated accumulator is rounded after
 # every 4 products of a matrix instruction.
+# Measured on an MI355X over tests/test_gpu_sparse_lanes.py (sparse lane sets in 64-lane contexts, T = 6 and 7, whole segment / worst
+# frame; profiles/sparse_lanes_f64_report.jsonl): hidden 1024 fc1 1.4 / 1.1, lstm 0.7 / 0.7, fc2 1.8 / 1.4, mask 1.4 / 1.4, hidden 512
+# fc1 1.4 / 1.0, lstm 0.8 / 0.9, fc2 1.5 / 1.4, mask 1.2 / 1.2; spec 3.8 / 3.9 (inside the floor), y 1.7 / 1.7, stems 1.1 / 1.2,
+# target_mag 1.0; no check uses more than 0.44 of its bound.
 # The bound scales with the float32 evaluation's own error, so a formula that float32 evaluates badly would make the check toothless:
 # where the float32 evaluation is itself further than this from float64 (whole segment / worst block), the check fails instead.
 # Measured on the GPU tests: at most 2.1e-4 / 5.3e-4 (the Wiener filter, on the mono and the click lanes).  About 2e-2 / 5e-2 on a
