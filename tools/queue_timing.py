@@ -8,9 +8,9 @@
                 both walls, both call counts and umx_hip_queue_plan's prediction; the queue's count must EQUAL the prediction
     equal       `lanes` equal 600 s jobs (the schedule of umx_hip_separate_tracks): the queue against umx_hip_separate_tracks
     plain       umx_hip_shift_inference of one 600 s track on a one-lane context (the figure of profiles/mix_timing.txt)
-Every case runs in a fresh process per tree (this one; with --parent-root also a built checkout of the parent commit, which has no
-queue: its `equal` and `plain` give the no-regression margins, max - min over its own runs).  UMX_TIMING_ROOT tells a child which tree
-to load.  A first process reports the HBM the context leaves free; if the accumulators of the longest lengths would not fit, every
+Every case runs in a fresh process per tree (this one; with --parent-root also a built checkout of the parent commit: each row of
+this tree is compared with the parent's row, and the margin is the parent's own run-to-run spread, max - min over its runs; a parent
+without a queue gives the margins of `equal` and `plain` only).  UMX_TIMING_ROOT tells a child which tree to load.  A first process reports the HBM the context leaves free; if the accumulators of the longest lengths would not fit, every
 length is scaled by one factor and the table says so.  The jobs read slices of ONE synthetic track and the outputs come from a pool of lanes + 2 buffer sets: a job's stems are
 not kept."""
 import argparse
@@ -217,8 +217,15 @@ def main():
         pt, pp = par["equal_tracks"], par["plain"]
         say(f"equal      umx_hip_separate_tracks {med(pt):>28} ms  (parent commit)")
         say(f"plain      umx_hip_shift_inference {med(pp):>28} ms  (parent commit)")
-        for what, new, old in (("equal: queue - parent's umx_hip_separate_tracks", eq, pt), ("equal: this tree's umx_hip_separate_tracks - parent's", et, pt),
-                               ("plain: this tree - parent", tree["plain"], pp)):
+        rows = [("equal: this tree's umx_hip_separate_tracks - parent's", et, pt), ("plain: this tree - parent", tree["plain"], pp)]
+        if par["queue"]:  # the parent has a queue of its own: each queue row against the parent's row
+            pq, pe = par["catalogue_queue"], par["equal_queue"]
+            say(f"catalogue  queue                 {med(pq):>28} ms  {par['catalogue_queue_calls']} calls  (parent commit)")
+            say(f"equal      queue                 {med(pe):>28} ms  {par['equal_queue_calls']} calls  (parent commit)")
+            rows = [("catalogue: queue - parent's queue", q, pq), ("equal: queue - parent's queue", eq, pe)] + rows
+        else:
+            rows.insert(0, ("equal: queue - parent's umx_hip_separate_tracks", eq, pt))
+        for what, new, old in rows:
             d, spread = statistics.median(new) - statistics.median(old), max(old) - min(old)
             say(f"# {what} = {d:+.1f} ms; the parent's run-to-run spread (max - min of its {len(old)} runs) is {spread:.1f} ms: "
                 f"{'no slower (within the spread)' if d <= spread else 'SLOWER than the spread'}")

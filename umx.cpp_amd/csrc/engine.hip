@@ -560,16 +560,23 @@ struct umx_hip_ctx
     bool lstm_writes_planes = false; // ... and writes that GEMM's A planes itself
     size_t state_floats() const { return (size_t)4 * 12 * Hl; }
     // phased form of one segment (exact multi-GPU carry): front | layer 0 | layer 1 | layer 2 | back
-    // whole track on the device (split_inference / shift_inference, umx.cpp:99-295)
-    int track(const float *audio_host, int length, int shift_offset, float *const out_host[4], unsigned flags,
-              void (*progress)(float, void *), void *progress_user);
-    // rate == nullptr: every track at 44.1 kHz; else track i is at rate[i] and is resampled to 44.1 kHz and back on the device
-    // mix (stem_mix.h): out_host holds mix->n_out buffers per track instead of four, weighted sums of its stems and its input
-    int tracks(int nt, const float *const *audio_host, const int *length, const int *shift_offset, float *const *out_host, unsigned flags,
-               void (*progress)(float, void *), void *progress_user, const int *rate = nullptr, bool ensemble = false,
-               const MixSpec *mix = nullptr);
-    int tracks_once(int nt, const float *const *audio_host, const int *length, const int *shift_offset, float *const *out_host,
-                    unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate, bool ensemble, const MixSpec *mix);
+    // whole tracks on the device (split_inference / shift_inference, umx.cpp:99-295; engine_tracks.h, engine_queue.h)
+    struct TrackRequest // what tracks() is asked for: n_tracks tracks, one per track lane
+    {
+        int n_tracks = 0;
+        const float *const *audio = nullptr;
+        const int *length = nullptr;
+        const int *rate = nullptr; // nullptr: every track at 44.1 kHz; else track i is at rate[i], resampled to 44.1 kHz and back on the device
+        const int *shift_offset = nullptr; // < 0: no shift buffer (plain split_inference)
+        float *const *out = nullptr; // four host buffers per track; with mix, mix->n_out: out[n_host * track + m]
+        unsigned flags = 0;
+        void (*progress)(float, void *) = nullptr;
+        void *progress_user = nullptr;
+        bool ensemble = false;       // the lanes are ONE track at n_tracks shift offsets, `out` the buffers of their mean
+        const MixSpec *mix = nullptr; // stem_mix.h, DESIGN 17: weighted sums of a track's stems and its input instead of the stems
+    };
+    int tracks(const TrackRequest &rq);
+    int tracks_once(const TrackRequest &rq);
     // resampling (resample.h): the tap table of each (rate_in, rate_out) pair, built once and kept in HBM
     std::map<std::pair<int, int>, float *> rs_taps;
     int resample_plan(int rate_in, int rate_out, ResampleGeom &g, const float **taps_dev);
@@ -585,16 +592,65 @@ struct umx_hip_ctx
         size_t cap = 0;
     };
     std::vector<TrackBufs> trk;
-    hipEvent_t trk_acc_ev[kMaxSlots] = {};
-    // what tracks_once and the track queue share (engine_tracks.h)
+    hipEvent_t trk_acc_ev[kMaxSlots] = {}; // per slot: behind the overlap-add of the last call that ran in it
+    // ---- what tracks_once and the track queue share (engine_tracks.h)
+    struct TrackJob // a track resident on the device
+    {
+        const float *audio = nullptr; // on the host
+        int length = 0;               // frames as the segments see them (the 44.1 kHz version's of a resampled track)
+        int lead = 0, L2 = 0, segs = 0; // track_geometry: frames of silence before the track, padded frames, segments
+        long long uploaded = 0;       // host frames already on the device
+        TrackBufs *acc = nullptr;     // the accumulator set it writes
+        bool by_region = true;        // its final regions are mixed in place and leave region by region (false: an ensemble lane, a
+                                      // resampled track -- mixed and downloaded whole behind the last segment)
+    };
+    struct TrackLane // a lane of one call: its job (nullptr: idle) and the padded frame at which its segment starts
+    {
+        TrackJob *job = nullptr;
+        long long start = 0;
+    };
+    struct TrackRegion // `count` final frames of a job from padded frame `start` on, on the device once `ready` has passed
+    {
+        TrackJob *job;
+        int start, count;
+        hipEvent_t ready;
+    };
+    struct TrackRegions // owns the events of its regions: whichever way a driver returns, none is left behind
+    {
+        std::vector<TrackRegion> v;
+        TrackRegions() = default;
+        TrackRegions(const TrackRegions &) = delete;
+        TrackRegions &operator=(const TrackRegions &) = delete;
+        ~TrackRegions() { clear(); }
+        void clear()
+        {
+            for (TrackRegion &r : v)
+                if (r.ready)
+                    (void)hipEventDestroy(r.ready);
+            v.clear();
+        }
+    };
+    struct TrackRun // the scope of a whole-track run: a timeout inside it cannot be repaired call by call (the overlap-add has consumed
+    {               // the stems), so umx_hip_sync reports it to the driver; no call of the run stays in the replay log
+        umx_hip_ctx &c;
+        explicit TrackRun(umx_hip_ctx &c_) : c(c_) { c.no_recovery = true; }
+        ~TrackRun()
+        {
+            c.no_recovery = false;
+            c.pending.clear();
+            c.pending_lost = false;
+        }
+    };
+    int track_stride() const { return (int)((1 - 0.25f) * N); } // umx.cpp:181, inference.hpp:15
+    static bool track_job_ok(const float *audio, int length, int shift_offset, float *const *out, int n_host);
+    static bool track_geometry(int length, int shift_offset, int stride, TrackJob &j);
+    int grow_frames(std::initializer_list<std::pair<float **, int>> bufs, size_t &cap, size_t frames);
     int track_bufs_grow(TrackBufs &tb_, size_t frames);
-    int track_bufs_segs(TrackBufs &tb_);
-    hipError_t track_upload_until(float *in_dev, const float *audio_host, int length, int lead, long long &uploaded, long long padded_end);
+    hipError_t track_upload_until(TrackJob &j, long long padded_end);
     void track_mix(const MixSpec &mix, float *const stems[4], size_t stem_start, const float *in, size_t in_start, int count, hipStream_t st);
-    int track_region(const TrackBufs &tb_, float *const seg_stems[4], int offset, int nn, int L2, int stride, const MixSpec *mix, hipStream_t st);
-    hipError_t track_region_download(const TrackBufs &tb_, int start, int count, int lead, int length, int n_host, float *const *out_host,
-                                     hipEvent_t ready);
-    // track queue (engine_queue.h, DESIGN 18): B + 2 accumulator sets (in, out, sumw of TrackBufs; grow-only) lent to the jobs in flight
+    hipError_t track_region_download(const TrackRegion &r, int n_host, float *const *out_host);
+    int track_call(const TrackLane *lanes, int nl, unsigned flags, const MixSpec *mix, int &last_slot, TrackRegions &regions);
+    // track queue (engine_queue.h): B + 2 accumulator sets (in, out, sumw of TrackBufs; grow-only) lent to the jobs in flight
     std::vector<TrackBufs> qpool;
     int queue_calls = -1; // infer_batch calls of the last queue run
     int queue(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags);
@@ -669,8 +725,8 @@ struct umx_hip_ctx
             if (!(flags & UMX_FLAG_SKIP_TARGET(tg)))
                 active[nact++] = tg;
     }
-    // shift ensemble (shift_mean.h): `ensemble` of tracks() = the nt lanes are ONE track (audio_host[0], length[0], rate[0])
-    // at nt shift offsets, out_host its 4 stems: one upload, the lanes' stems averaged on the device into ens_out (grow-only), one
+    // shift ensemble (shift_mean.h): TrackRequest::ensemble = the lanes are ONE track (audio[0], length[0], rate[0])
+    // at n_tracks shift offsets, `out` its 4 stems: one upload, the lanes' stems averaged on the device into ens_out (grow-only), one
     // download.  Only umx_hip_shift_ensemble with more than one shift touches these.
     float *ens_out[4] = {};
     size_t ens_cap = 0;          // frames

@@ -217,15 +217,19 @@ int umx_hip_stream_set_layer(umx_hip_ctx *ctx, int layer, const float *host_src)
     return stream_layer_copy(ctx, layer, const_cast<float *>(host_src), false);
 }
 
+// The whole-track entry points fill one request record (umx_hip_ctx::TrackRequest, in its field order; its checks are tracks_once's).
+// A one-track entry point passes the addresses of its own arguments; shift offset < 0: no shift buffer (plain split_inference).
 int umx_hip_split_inference(umx_hip_ctx *ctx, const float *audio_host, int length, float *const out_host[4],
                             unsigned flags, void (*progress)(float, void *), void *progress_user)
 {
-    return ctx ? ctx->track(audio_host, length, -1, out_host, flags, progress, progress_user) : UMX_ERR_ARG;
+    const int no_shift = -1;
+    return ctx ? ctx->tracks({1, &audio_host, &length, nullptr, &no_shift, out_host, flags, progress, progress_user}) : UMX_ERR_ARG;
 }
 int umx_hip_separate_tracks(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *shift_offset,
                             float *const *out_host, unsigned flags, void (*progress)(float, void *), void *progress_user)
 {
-    return ctx ? ctx->tracks(n_tracks, audio_host, length, shift_offset, out_host, flags, progress, progress_user) : UMX_ERR_ARG;
+    return ctx ? ctx->tracks({n_tracks, audio_host, length, nullptr, shift_offset, out_host, flags, progress, progress_user})
+               : UMX_ERR_ARG;
 }
 long long umx_hip_resampled_length(long long n, int rate_in, int rate_out) { return resampled_length(n, rate_in, rate_out); }
 
@@ -259,14 +263,9 @@ int umx_hip_shift_inference_rate(umx_hip_ctx *ctx, const float *audio_host, int 
 {
     if (!ctx)
         return UMX_ERR_ARG;
-    if (!out_host)
-    {
-        ctx->set_error("track: need audio, outputs, length >= 1 and shift offset < 22050");
-        return UMX_ERR_ARG;
-    }
     if (offset < 0)
         offset = UMX_REFERENCE_SHIFT;
-    return ctx->tracks(1, &audio_host, &length, &offset, out_host, flags, progress, progress_user, &rate);
+    return ctx->tracks({1, &audio_host, &length, &rate, &offset, out_host, flags, progress, progress_user});
 }
 int umx_hip_separate_tracks_rate(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *rate,
                                  const int *shift_offset, float *const *out_host, unsigned flags, void (*progress)(float, void *),
@@ -274,7 +273,7 @@ int umx_hip_separate_tracks_rate(umx_hip_ctx *ctx, int n_tracks, const float *co
 {
     if (!ctx || !rate)
         return UMX_ERR_ARG;
-    return ctx->tracks(n_tracks, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate);
+    return ctx->tracks({n_tracks, audio_host, length, rate, shift_offset, out_host, flags, progress, progress_user});
 }
 
 int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase, int *first_offset)
@@ -303,7 +302,7 @@ int umx_hip_shift_inference(umx_hip_ctx *ctx, const float *audio_host, int lengt
         return UMX_ERR_ARG;
     if (offset < 0)
         offset = UMX_REFERENCE_SHIFT; // umx.cpp:115: rand() % 22050, never seeded in the reference (see umx_hip.h)
-    return ctx->track(audio_host, length, offset, out_host, flags, progress, progress_user);
+    return ctx->tracks({1, &audio_host, &length, nullptr, &offset, out_host, flags, progress, progress_user});
 }
 
 // the default offsets of a K-shift ensemble: K steps of MAX_SHIFT / K from `first` on, wrapped into the shift buffer
@@ -323,10 +322,7 @@ int umx_hip_ensemble_offsets(int n_shifts, int first, int *offsets_out)
 static int shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets,
                           float *const *out_host, unsigned flags, void (*progress)(float, void *), void *progress_user, const MixSpec *mix)
 {
-    bool outs = out_host != nullptr;
-    for (int m = 0; outs && m < (mix ? mix->n_out : 4); ++m)
-        outs = out_host[m] != nullptr;
-    if (!audio_host || !outs || length < 1)
+    if (!umx_hip_ctx::track_job_ok(audio_host, length, 0, out_host, mix ? mix->n_out : 4))
     {
         ctx->set_error(mix ? "shift ensemble: need audio, n_out outputs and length >= 1" : "shift ensemble: need audio, four outputs and length >= 1");
         return UMX_ERR_ARG;
@@ -354,8 +350,6 @@ static int shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length,
         }
         off[k] = offsets[k];
     }
-    if (n_shifts == 1)
-        return ctx->tracks(1, &audio_host, &length, off, out_host, flags, progress, progress_user, &rate, false, mix);
     const float *audio[UMX_MAX_SHIFTS];
     int lengths[UMX_MAX_SHIFTS], rates[UMX_MAX_SHIFTS];
     for (int k = 0; k < n_shifts; ++k)
@@ -364,7 +358,10 @@ static int shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length,
         lengths[k] = length;
         rates[k] = rate;
     }
-    return ctx->tracks(n_shifts, audio, lengths, off, out_host, flags, progress, progress_user, rates, true, mix);
+    umx_hip_ctx::TrackRequest rq = {n_shifts, audio, lengths, rates, off, out_host, flags, progress, progress_user};
+    rq.ensemble = n_shifts > 1;
+    rq.mix = mix;
+    return ctx->tracks(rq);
 }
 int umx_hip_shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets,
                            float *const out_host[4], unsigned flags, void (*progress)(float, void *), void *progress_user)
@@ -392,7 +389,9 @@ int umx_hip_separate_tracks_mix(umx_hip_ctx *ctx, int n_tracks, const float *con
     MixSpec spec;
     if (!mix_checked(ctx, n_out, gains, spec))
         return UMX_ERR_ARG;
-    return ctx->tracks(n_tracks, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate, false, &spec);
+    umx_hip_ctx::TrackRequest rq = {n_tracks, audio_host, length, rate, shift_offset, out_host, flags, progress, progress_user};
+    rq.mix = &spec;
+    return ctx->tracks(rq);
 }
 
 int umx_hip_shift_ensemble_mix(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets, int n_out,

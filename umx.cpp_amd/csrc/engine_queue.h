@@ -1,6 +1,9 @@
 // engine_queue.h -- part of engine.hip (one translation unit: the kernels inline into their launchers): the track queue,
 // umx_hip_separate_queue: more tracks than lanes, of different lengths, a lane refilled with the next track the moment one ends.
-// Included by engine.hip behind engine_tracks.h (whose helpers it shares with tracks_once); not a stand-alone header.
+// This file holds what only a queue has: the schedule (QueueSchedule, umx_hip_queue_plan), the pool of accumulator sets lent to the
+// jobs in flight, the in-stream zeroing of a refilled lane, the download of the previous call's regions behind every call, and the
+// restart after a timeout.  A job's checks and geometry, the body of a call and the region list are those of engine_tracks.h
+// (track_job_ok, track_geometry, track_call, TrackRegions).  Included by engine.hip behind engine_tracks.h; not a stand-alone header.
 // ---------------------------------------------------------------- track queue
 namespace
 {
@@ -94,87 +97,62 @@ int umx_hip_ctx::queue(umx_queue_next_fn next, umx_queue_done_fn done, void *use
         return rc;
     // As tracks(): a persistent-kernel timeout cannot be repaired segment by segment (the overlap-add has consumed the stems); the
     // jobs in flight are run again from their first segment (queue_run).  No call is logged for a replay: `pending` stays empty.
-    no_recovery = true;
+    TrackRun run(*this);
     pending.clear();
     pending_lost = true;
-    const int rc = queue_run(next, done, user, mix, flags);
-    no_recovery = false;
-    pending.clear();
-    pending_lost = false;
-    return rc;
+    return queue_run(next, done, user, mix, flags);
 }
 
 int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags)
 {
     const int n_host = mix ? mix->n_out : 4;
-    const int stride = (int)((1 - 0.25f) * N); // umx.cpp:181, inference.hpp:15
+    const int stride = track_stride();
     const size_t n_sets = (size_t)B + 2;
     if (qpool.size() < n_sets)
         qpool.resize(n_sets);
     if (trk.size() < (size_t)B) // (the per-slot segment stems stay with the lane)
         trk.resize(B);
-    if (!trk_acc_ev[0])
-        for (int s = 0; s < nslots; ++s)
-            UMX_HIP_CHECK(hipEventCreateWithFlags(&trk_acc_ev[s], hipEventDisableTiming));
 
-    struct Job // a job in flight = the accumulator set it borrowed: jobs[set]
+    struct Job : TrackJob // a job in flight = the accumulator set it borrowed: jobs[set].acc == &qpool[set]
     {
         umx_queue_job job;
-        int lead = 0, L2 = 0, segs = 0, regions_left = 0;
-        long long uploaded = 0;
+        int regions_left = 0;
         unsigned long long seq = 0; // order in which `next` handed the jobs out
         bool live = false;
     };
-    struct LaneJob
-    {
-        int set = -1, seg = 0; // the lane's job and its next segment
-    };
-    struct QRegion
-    {
-        int set, start, count;
-        hipEvent_t ready;
-    };
     std::vector<Job> jobs(n_sets);
-    LaneJob lanes[LSTMB_MAX_TRACKS];
+    TrackLane lanes[LSTMB_MAX_TRACKS]; // a lane's job and where its next segment starts
     QueueSchedule sched(B);
-    std::vector<QRegion> prev, cur; // finished regions of the previous call and of the one being queued
-    std::vector<int> redo;          // after a timeout: the jobs to run again, ahead of `next`
+    TrackRegions prev, cur; // finished regions of the previous call and of the one being queued
+    std::vector<Job *> redo; // after a timeout: the jobs to run again, ahead of `next`
     bool exhausted = false, retried = false;
     int last_slot = -1;
     unsigned long long seq = 0;
     queue_calls = 0;
 
-    auto drop_events = [&]() {
-        for (std::vector<QRegion> *v : {&prev, &cur})
-        {
-            for (QRegion &r : *v)
-                (void)hipEventDestroy(r.ready);
-            v->clear();
-        }
-    };
     auto fail = [&](int rc) { // nothing of this run may still be running, or be copied, when the caller has its buffers back
         const std::string why = err;
         (void)sync_all();
-        drop_events();
         set_error(why);
         return rc;
     };
     // a timeout among the calls so far: umx_hip_sync has drained the device, zeroed the state and switched to the per-step driver;
     // every job in flight starts again, in the order the jobs were taken
     auto restart = [&]() {
-        drop_events();
+        prev.clear();
+        cur.clear();
         redo.clear();
-        for (size_t s = 0; s < n_sets; ++s)
-            if (jobs[s].live)
-                redo.push_back((int)s);
-        std::sort(redo.begin(), redo.end(), [&](int a, int b) { return jobs[a].seq < jobs[b].seq; });
-        for (int s : redo)
+        for (Job &jb : jobs)
+            if (jb.live)
+                redo.push_back(&jb);
+        std::sort(redo.begin(), redo.end(), [](const Job *a, const Job *b) { return a->seq < b->seq; });
+        for (Job *jb : redo)
         {
-            jobs[s].uploaded = 0;
-            jobs[s].regions_left = jobs[s].segs;
+            jb->uploaded = 0;
+            jb->regions_left = jb->segs;
         }
         for (int ln = 0; ln < B; ++ln)
-            lanes[ln] = LaneJob();
+            lanes[ln] = TrackLane();
         sched.reset();
         last_slot = -1;
         pending_lost = true;
@@ -182,19 +160,20 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void 
     // The regions in v to the host (event wait, then copy; the event goes as soon as it is consumed).  A job whose last region has
     // arrived is complete -- once no launch up to its last call has timed out: done(), and its set goes back to the pool.
     // 0: fine; > 0: an error code (set_error done); < 0: a timeout was met for the first time and the jobs in flight start again
-    auto drain = [&](std::vector<QRegion> &v) -> int {
-        std::vector<int> finished;
+    auto drain = [&](TrackRegions &v) -> int {
+        std::vector<Job *> finished;
         hipError_t e = hipSuccess;
-        for (QRegion &r : v)
+        for (TrackRegion &r : v.v)
         {
-            Job &jb = jobs[r.set];
+            Job &jb = *static_cast<Job *>(r.job);
             if (e == hipSuccess) // (also for a region that is all shift padding: the set is not lent again while the device works on it)
                 e = hipEventSynchronize(r.ready);
             if (e == hipSuccess)
-                e = track_region_download(qpool[r.set], r.start, r.count, jb.lead, jb.job.length, n_host, jb.job.out, r.ready);
+                e = track_region_download(r, n_host, jb.job.out);
             (void)hipEventDestroy(r.ready);
+            r.ready = nullptr;
             if (--jb.regions_left == 0)
-                finished.push_back(r.set);
+                finished.push_back(&jb);
         }
         v.clear();
         if (e != hipSuccess)
@@ -226,10 +205,10 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void 
             restart();
             return -1;
         }
-        for (int s : finished)
+        for (Job *jb : finished)
         {
-            done(user, &jobs[s].job);
-            jobs[s].live = false;
+            done(user, &jb->job);
+            jb->live = false;
         }
         return 0;
     };
@@ -242,10 +221,10 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void 
         {
             if (!sched.wants(ln) || (redo.empty() && exhausted))
                 continue;
-            int set = -1;
+            Job *jb = nullptr;
             if (!redo.empty())
             {
-                set = redo.front();
+                jb = redo.front();
                 redo.erase(redo.begin());
             }
             else
@@ -288,46 +267,38 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void 
                     set_error("queue: the next callback stopped the run");
                     return fail(UMX_ERR_ARG);
                 }
-                bool ok = j.audio && j.length >= 1 && j.shift_offset < UMX_MAX_SHIFT;
-                for (int m = 0; m < n_host; ++m)
-                    ok = ok && j.out[m];
-                if (!ok)
+                if (!track_job_ok(j.audio, j.length, j.shift_offset, j.out, n_host))
                 {
                     set_error("queue: a job needs audio, its n_out outputs, length >= 1 and shift offset < 22050");
                     return fail(UMX_ERR_ARG);
                 }
-                // umx.cpp:120-122 (see tracks_once)
-                const long long l2 = j.shift_offset < 0 ? (long long)j.length
-                                                        : (long long)j.length + std::max(UMX_MAX_SHIFT - j.shift_offset, j.shift_offset);
-                if (l2 > 0x7fffffff / 2)
+                TrackJob tj; // (the geometry first: the set is chosen by its size)
+                if (!track_geometry(j.length, j.shift_offset, stride, tj))
                 {
                     set_error("queue: a job is too long");
                     return fail(UMX_ERR_ARG);
                 }
-                set = free_set((size_t)l2);
-                if (int rc = track_bufs_grow(qpool[set], (size_t)l2))
+                const int set = free_set((size_t)tj.L2);
+                if (int rc = track_bufs_grow(qpool[set], (size_t)tj.L2))
                     return fail(rc);
-                Job &jb = jobs[set];
-                jb.job = j;
-                jb.lead = j.shift_offset < 0 ? 0 : j.shift_offset;
-                jb.L2 = (int)l2;
-                jb.segs = (int)((l2 + stride - 1) / stride);
-                jb.regions_left = jb.segs;
-                jb.uploaded = 0;
-                jb.seq = seq++;
-                jb.live = true;
+                tj.audio = j.audio;
+                tj.acc = &qpool[set];
+                jb = &jobs[set];
+                static_cast<TrackJob &>(*jb) = tj;
+                jb->job = j;
+                jb->regions_left = tj.segs;
+                jb->seq = seq++;
+                jb->live = true;
             }
-            if (int rc = track_bufs_segs(trk[ln]))
-                return fail(rc);
-            lanes[ln].set = set;
-            lanes[ln].seg = 0;
-            sched.take(ln, jobs[set].segs);
+            lanes[ln].job = jb;
+            lanes[ln].start = 0;
+            sched.take(ln, jb->segs);
         }
         if (restarted)
             continue;
         if (!sched.busy()) // no lane holds a track: what is left is the last call's regions
         {
-            if (prev.empty())
+            if (prev.v.empty())
                 break;
             const int d = drain(prev);
             if (d > 0)
@@ -336,20 +307,15 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void 
         }
 
         // ---- one call: the next segment of every lane's job
-        const int si = next_slot();
-        hipStream_t st = slot[si].stream;
-        const float *ain[LSTMB_MAX_TRACKS] = {};
-        int nn[LSTMB_MAX_TRACKS] = {}, seg_off[LSTMB_MAX_TRACKS] = {}, nl = 0;
-        float *outs[4 * LSTMB_MAX_TRACKS] = {};
+        const hipStream_t st = slot[next_slot()].stream;
+        int nl = 0;
         bool waited = false;
         for (int ln = 0; ln < B; ++ln)
         {
-            if (lanes[ln].set < 0)
+            const TrackJob *jb = lanes[ln].job;
+            if (!jb)
                 continue;
-            Job &jb = jobs[lanes[ln].set];
-            TrackBufs &tb_ = qpool[lanes[ln].set];
-            const long long so = (long long)lanes[ln].seg * stride;
-            if (lanes[ln].seg == 0)
+            if (lanes[ln].start == 0)
             {
                 // A refilled lane starts clean, in stream order: behind the previous call (the lane's previous occupant has run its last
                 // recurrence) the lane's state slice, the set's accumulators and the shift padding of its padded input are zeroed in one
@@ -358,67 +324,33 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void 
                 if (!waited && last_slot >= 0)
                     (void)hipStreamWaitEvent(st, trk_acc_ev[last_slot], 0);
                 waited = true;
+                const TrackBufs &tb_ = *jb->acc;
                 TrackBeginSpans sp = {};
                 for (int t = 0; t < 4; ++t)
                 {
                     sp.p[t] = tb_.out[t];
-                    sp.n[t] = 2 * (unsigned long long)jb.L2;
+                    sp.n[t] = 2 * (unsigned long long)jb->L2;
                 }
                 sp.p[4] = tb_.sumw;
-                sp.n[4] = (unsigned long long)jb.L2;
+                sp.n[4] = (unsigned long long)jb->L2;
                 sp.p[5] = tb_.in;
-                sp.n[5] = 2 * (unsigned long long)jb.lead;
-                sp.p[6] = tb_.in + 2 * ((size_t)jb.lead + (size_t)jb.job.length);
-                sp.n[6] = 2 * (unsigned long long)(jb.L2 - jb.lead - jb.job.length);
+                sp.n[5] = 2 * (unsigned long long)jb->lead;
+                sp.p[6] = tb_.in + 2 * ((size_t)jb->lead + (size_t)jb->length);
+                sp.n[6] = 2 * (unsigned long long)(jb->L2 - jb->lead - jb->length);
                 sp.p[7] = state + state_floats() * (size_t)ln;
                 sp.n[7] = state_floats();
                 sp.count = TRACK_BEGIN_SPANS;
                 launch_track_begin(sp, st);
             }
-            if (track_upload_until(tb_.in, jb.job.audio, jb.job.length, jb.lead, jb.uploaded, so + N) != hipSuccess)
-            {
-                set_error("queue: upload failed");
-                return fail(UMX_ERR_HIP);
-            }
-            seg_off[ln] = (int)so;
-            ain[ln] = tb_.in + 2 * (size_t)so;
-            nn[ln] = std::min(N, jb.L2 - (int)so);
-            for (int t = 0; t < 4; ++t)
-                outs[4 * ln + t] = trk[ln].seg[si][t];
             nl = ln + 1;
         }
         pending_lost = true;
-        if (int rc = infer_batch(nl, ain, nn, outs, flags))
+        if (int rc = track_call(lanes, nl, flags, mix, last_slot, cur))
             return fail(rc);
         ++queue_calls;
-        if (last_slot >= 0) // accumulate in segment order (two segments overlap by a quarter)
-            (void)hipStreamWaitEvent(st, trk_acc_ev[last_slot], 0);
         for (int ln = 0; ln < nl; ++ln)
-        {
-            if (!ain[ln])
-                continue;
-            const int set = lanes[ln].set;
-            QRegion rg;
-            rg.set = set;
-            rg.start = seg_off[ln];
-            rg.count = track_region(qpool[set], trk[ln].seg[si], seg_off[ln], nn[ln], jobs[set].L2, stride, mix, st);
-            if (hipEventCreateWithFlags(&rg.ready, hipEventDisableTiming) != hipSuccess)
-            {
-                set_error("queue: event creation failed");
-                return fail(UMX_ERR_HIP);
-            }
-            if (hipEventRecord(rg.ready, st) != hipSuccess)
-            {
-                (void)hipEventDestroy(rg.ready);
-                set_error("queue: event creation failed");
-                return fail(UMX_ERR_HIP);
-            }
-            cur.push_back(rg);
-            if (++lanes[ln].seg == jobs[set].segs) // the lane is free for the next call; the job lives on until its regions are down
-                lanes[ln] = LaneJob();
-        }
-        (void)hipEventRecord(trk_acc_ev[si], st);
-        last_slot = si;
+            if (lanes[ln].job && (lanes[ln].start += stride) >= lanes[ln].job->L2)
+                lanes[ln] = TrackLane(); // the lane is free for the next call; the job lives on until its regions are down
         sched.step();
         // ---- while the device runs this call: the regions of the one before
         const int d = drain(prev);
@@ -426,7 +358,7 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void 
             return fail(d);
         if (d < 0)
             continue;
-        prev.swap(cur);
+        prev.v.swap(cur.v);
     }
     UMX_HIP_CHECK(hipGetLastError());
     return umx_hip_sync(this);

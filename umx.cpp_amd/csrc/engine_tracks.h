@@ -1,92 +1,96 @@
-// engine_tracks.h -- part of engine.hip (one translation unit: the kernels inline into their launchers): whole tracks on the device: split_inference / shift_inference for one track or one per lane.
-// Included by engine.hip behind the definition of umx_hip_ctx; not a stand-alone header.
+// engine_tracks.h -- part of engine.hip (one translation unit: the kernels inline into their launchers): whole tracks on the device.
+// What every whole-track driver shares, stated once each -- the checks of a job (track_job_ok), its padded geometry (track_geometry),
+// the grow-only buffers (grow_frames), the body of one segment call (track_call) and the list of finished regions that owns its
+// events (TrackRegions, engine.hip) -- and the driver of umx_hip_split_inference / umx_hip_shift_inference / umx_hip_separate_tracks* /
+// umx_hip_shift_ensemble* (tracks, tracks_once): one track per lane, or the segments of one track as the lanes (reset mode).
+// The track queue is the other driver (engine_queue.h).  Included by engine.hip behind the definition of umx_hip_ctx; not a
+// stand-alone header.
 // ---------------------------------------------------------------- whole track
-// shift_inference (umx.cpp:99-150) around split_inference (umx.cpp:152-295) with the track resident in HBM:
-// one upload, the segments queued back to back through the two pipeline slots (so consecutive segments
-// overlap exactly as in bench.py), the weighted overlap-add and the final normalisation on the device, one
-// download.  shift_offset < 0: no shift buffer (plain split_inference).
-int umx_hip_ctx::track(const float *audio_host, int length, int shift_offset, float *const out_host[4], unsigned flags,
-                       void (*progress)(float, void *), void *progress_user)
-{
-    if (!out_host)
-    {
-        set_error("track: need audio, outputs, length >= 1 and shift offset < 22050");
-        return UMX_ERR_ARG;
-    }
-    return tracks(1, &audio_host, &length, &shift_offset, out_host, flags, progress, progress_user);
-}
-
-// shift_inference (umx.cpp:99-150) around split_inference (umx.cpp:152-295) for `nt` tracks at once, one per track
+// shift_inference (umx.cpp:99-150) around split_inference (umx.cpp:152-295) for rq.n_tracks tracks at once, one per track
 // lane: the tracks stay in HBM, call s runs segment s of every track that still has one (a finished track's lane sits
-// idle), the weighted overlap-add and the normalisation run per lane on the device, finished regions are downloaded
-// while later segments run.  nt == 1 is umx_hip_split_inference / umx_hip_shift_inference.
-int umx_hip_ctx::tracks(int nt, const float *const *audio_host, const int *length, const int *shift_offset, float *const *out_host,
-                        unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate, bool ensemble,
-                        const MixSpec *mix)
+// idle; with one track the segments are queued back to back through the pipeline slots, so consecutive segments overlap exactly as
+// in bench.py), the weighted overlap-add and the normalisation run per lane on the device, finished regions are downloaded
+// while later segments run.  n_tracks == 1 is umx_hip_split_inference / umx_hip_shift_inference.
+int umx_hip_ctx::tracks(const TrackRequest &rq)
 {
     // A persistent-kernel timeout inside a track cannot be repaired segment by segment (the overlap-add has consumed
     // the stems): everything is run again, once, with the per-step driver the timeout switches the context to.
-    no_recovery = true;
-    int rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate, ensemble, mix);
+    TrackRun run(*this);
+    int rc = tracks_once(rq);
     if (rc == UMX_ERR_TIMEOUT) // (a resampled track is resampled again from its host copy, an ensemble placed in its lanes and averaged
                                // again, a mix formed again from fresh accumulators: tracks_once starts from scratch)
-        rc = tracks_once(nt, audio_host, length, shift_offset, out_host, flags, progress, progress_user, rate, ensemble, mix);
-    no_recovery = false;
-    pending.clear();
-    pending_lost = false;
+        rc = tracks_once(rq);
     return rc;
 }
 
 // ---------------------------------------------------------------- what the whole-track drivers share (tracks_once, engine_queue.h)
-// grow-only accumulators of one track: the (shifted) track, 4 stems, the weight sum, `frames` frames each
-int umx_hip_ctx::track_bufs_grow(TrackBufs &tb_, size_t frames)
+// The checks of one job: its audio, n_host outputs (`out` itself may be missing), length >= 1, shift offset < UMX_MAX_SHIFT (< 0:
+// no shift).  The caller names the refusal.
+bool umx_hip_ctx::track_job_ok(const float *audio, int length, int shift_offset, float *const *out, int n_host)
 {
-    if (frames <= tb_.cap)
+    bool ok = audio && out && length >= 1 && shift_offset < UMX_MAX_SHIFT;
+    for (int m = 0; ok && m < n_host; ++m)
+        ok = out[m] != nullptr;
+    return ok;
+}
+
+// The padded signal of a track of `length` frames: `lead` frames of silence (the shift), the track, silence up to L2 frames; `segs`
+// segments start in it, `stride` frames apart.  false: too long (j is then undefined).
+bool umx_hip_ctx::track_geometry(int length, int shift_offset, int stride, TrackJob &j)
+{
+    // umx.cpp:120-122: length + max_shift - offset -- which the reference overruns for offset > max_shift / 2 (its
+    // block write is [offset, offset + length)); the same size where the reference is defined, large enough elsewhere
+    const long long l2 = shift_offset < 0 ? (long long)length : (long long)length + std::max(UMX_MAX_SHIFT - shift_offset, shift_offset);
+    if (l2 > 0x7fffffff / 2)
+        return false;
+    j.length = length;
+    j.lead = shift_offset < 0 ? 0 : shift_offset;
+    j.L2 = (int)l2;
+    j.segs = (int)((l2 + stride - 1) / stride); // umx.cpp:214-217
+    j.uploaded = 0;
+    return true;
+}
+
+// Grow-only device buffers: every pointer of `bufs` has room for (its floats per frame) x `frames`; `cap`: the frames they hold now.
+// Too small: all are freed and allocated again with an eighth to spare (their contents are lost).
+int umx_hip_ctx::grow_frames(std::initializer_list<std::pair<float **, int>> bufs, size_t &cap, size_t frames)
+{
+    if (frames <= cap)
         return UMX_OK;
-    const size_t cap = frames + frames / 8;
-    for (float **p : {&tb_.in, &tb_.out[0], &tb_.out[1], &tb_.out[2], &tb_.out[3], &tb_.sumw})
-        if (*p)
+    for (const auto &b : bufs)
+        if (*b.first)
         {
-            allocs.erase(std::find(allocs.begin(), allocs.end(), (void *)*p));
-            (void)hipFree(*p);
-            *p = nullptr;
+            allocs.erase(std::find(allocs.begin(), allocs.end(), (void *)*b.first));
+            (void)hipFree(*b.first);
+            *b.first = nullptr;
         }
-    tb_.cap = 0;
-    if (int rc = dalloc(&tb_.in, 2 * cap, false))
-        return rc;
-    for (int t = 0; t < 4; ++t)
-        if (int rc = dalloc(&tb_.out[t], 2 * cap, false))
+    cap = 0;
+    const size_t want = frames + frames / 8;
+    for (const auto &b : bufs)
+        if (int rc = dalloc(b.first, (size_t)b.second * want, false))
             return rc;
-    if (int rc = dalloc(&tb_.sumw, cap, false))
-        return rc;
-    tb_.cap = cap;
+    cap = want;
     return UMX_OK;
 }
 
-// the per-slot segment stems of a track lane
-int umx_hip_ctx::track_bufs_segs(TrackBufs &tb_)
+// the accumulators of one track: the (shifted) track, 4 stems, the weight sum, `frames` frames each
+int umx_hip_ctx::track_bufs_grow(TrackBufs &tb_, size_t frames)
 {
-    if (!tb_.seg[0][0])
-        for (int s = 0; s < nslots; ++s)
-            for (int t = 0; t < 4; ++t)
-                if (int rc = dalloc(&tb_.seg[s][t], (size_t)2 * N, false))
-                    return rc;
-    return UMX_OK;
+    return grow_frames({{&tb_.in, 2}, {&tb_.out[0], 2}, {&tb_.out[1], 2}, {&tb_.out[2], 2}, {&tb_.out[3], 2}, {&tb_.sumw, 1}}, tb_.cap, frames);
 }
 
 // The track goes up segment by segment (round 6): a call needs the samples up to the end of its last segment, and the rest of a
 // pageable upload (14 GB/s: 15 ms for ten minutes of stereo) runs while the device is busy with the segments before it -- the
 // slots' streams do not wait for the null stream, and launches are queued ahead of the copy.
-// Samples of the padded signal `in_dev` (the track behind `lead` frames of silence) below `padded_end` must be there; `uploaded`:
-// host samples of the track already on the device.
-hipError_t umx_hip_ctx::track_upload_until(float *in_dev, const float *audio_host, int length, int lead, long long &uploaded, long long padded_end)
+// Samples of the job's padded signal (the track behind `lead` frames of silence) below `padded_end` must be there.
+hipError_t umx_hip_ctx::track_upload_until(TrackJob &j, long long padded_end)
 {
-    const long long want = std::min<long long>(length, padded_end - lead);
-    if (want <= uploaded)
+    const long long want = std::min<long long>(j.length, padded_end - j.lead);
+    if (want <= j.uploaded)
         return hipSuccess;
-    const hipError_t e = hipMemcpy(in_dev + 2 * ((size_t)lead + (size_t)uploaded), audio_host + 2 * (size_t)uploaded,
-                                   sizeof(float) * 2 * (size_t)(want - uploaded), hipMemcpyHostToDevice);
-    uploaded = want;
+    const hipError_t e = hipMemcpy(j.acc->in + 2 * ((size_t)j.lead + (size_t)j.uploaded), j.audio + 2 * (size_t)j.uploaded,
+                                   sizeof(float) * 2 * (size_t)(want - j.uploaded), hipMemcpyHostToDevice);
+    j.uploaded = want;
     return e;
 }
 
@@ -105,65 +109,121 @@ void umx_hip_ctx::track_mix(const MixSpec &mix, float *const stems[4], size_t st
     launch_stem_mix(mix, src, dst, count, st);
 }
 
-// A segment's stems `seg` (nn frames at padded frame `offset` of a track of L2 padded frames) blended into the track's accumulators.
-// A sample is final once the segment that starts at or before it and the one before that have been blended in: region
-// [offset, offset + stride) right after this segment.  It is normalised there and then and, with `mix`, mixed (over its stems).
-// Returns the region's frame count.
-int umx_hip_ctx::track_region(const TrackBufs &tb_, float *const seg_stems[4], int offset, int nn, int L2, int stride, const MixSpec *mix, hipStream_t st)
+// umx.cpp:136-147: a finished region without the shift, to its job's n_host host buffers, once it is ready
+hipError_t umx_hip_ctx::track_region_download(const TrackRegion &r, int n_host, float *const *out_host)
 {
-    Stems4 tk, seg;
-    for (int t = 0; t < 4; ++t)
-    {
-        tk.p[t] = reinterpret_cast<float2 *>(tb_.out[t]);
-        seg.p[t] = reinterpret_cast<float2 *>(seg_stems[t]);
-    }
-    hipLaunchKernelGGL(track_accumulate_kernel, dim3((nn + 255) / 256, 4), dim3(256), 0, st, tk, tb_.sumw, seg, offset, nn, N);
-    const int count = (int)std::min<long long>((long long)offset + stride, L2) - offset;
-    hipLaunchKernelGGL(track_normalise_kernel, dim3((count + 255) / 256, 4), dim3(256), 0, st, tk, tb_.sumw, offset, count);
-    if (mix)
-        track_mix(*mix, tb_.out, (size_t)offset, tb_.in, (size_t)offset, count, st);
-    return count;
-}
-
-// umx.cpp:136-147: a finished region without the shift, to the track's n_host host buffers, once `ready` has passed
-hipError_t umx_hip_ctx::track_region_download(const TrackBufs &tb_, int start, int count, int lead, int length, int n_host, float *const *out_host,
-                                              hipEvent_t ready)
-{
-    const long long lo = std::max<long long>(start, lead), hi = std::min<long long>((long long)start + count, (long long)lead + length);
+    const TrackJob &j = *r.job;
+    const long long lo = std::max<long long>(r.start, j.lead), hi = std::min<long long>((long long)r.start + r.count, (long long)j.lead + j.length);
     if (hi <= lo)
         return hipSuccess;
-    hipError_t cerr = hipEventSynchronize(ready);
+    hipError_t cerr = hipEventSynchronize(r.ready);
     for (int t = 0; t < n_host && cerr == hipSuccess; ++t)
-        cerr = hipMemcpy(out_host[t] + 2 * (size_t)(lo - lead), tb_.out[t] + 2 * (size_t)lo, sizeof(float) * 2 * (size_t)(hi - lo), hipMemcpyDeviceToHost);
+        cerr = hipMemcpy(out_host[t] + 2 * (size_t)(lo - j.lead), j.acc->out[t] + 2 * (size_t)lo, sizeof(float) * 2 * (size_t)(hi - lo), hipMemcpyDeviceToHost);
     return cerr;
 }
 
-int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *length_in, const int *shift_offset, float *const *out_host,
-                             unsigned flags, void (*progress)(float, void *), void *progress_user, const int *rate, bool ensemble,
-                             const MixSpec *mix)
+// One call of infer_batch for the whole-track drivers: lane ln runs the segment of lanes[ln].job that starts at padded frame
+// lanes[ln].start.  Which job sits in which lane is the caller's: a track per lane (tracks_once), segment k of the one track in
+// lane k (its reset mode), whatever job the lane holds (the queue).  The segment's stems are the lane's (trk[ln].seg of the slot), the
+// accumulators the job's.  Whatever the caller zeroes for this call it has queued on slot[next_slot()].stream, which is the stream
+// of this call: next_slot() moves on with infer_batch.  last_slot: the slot of the previous call of the run (-1: none), then this one.
+int umx_hip_ctx::track_call(const TrackLane *lanes, int nl, unsigned flags, const MixSpec *mix, int &last_slot, TrackRegions &regions)
+{
+    const int si = next_slot(), stride = track_stride();
+    const hipStream_t st = slot[si].stream;
+    if (!trk_acc_ev[0])
+        for (int s = 0; s < nslots; ++s)
+            UMX_HIP_CHECK(hipEventCreateWithFlags(&trk_acc_ev[s], hipEventDisableTiming));
+    const float *ain[LSTMB_MAX_TRACKS] = {};
+    int nn[LSTMB_MAX_TRACKS] = {};
+    float *outs[4 * LSTMB_MAX_TRACKS] = {};
+    for (int ln = 0; ln < nl; ++ln)
+    {
+        TrackJob *j = lanes[ln].job;
+        if (!j)
+            continue;
+        if (!trk[ln].seg[0][0]) // the lane's per-slot segment stems, on first use
+            for (int s = 0; s < nslots; ++s)
+                for (int t = 0; t < 4; ++t)
+                    if (int rc = dalloc(&trk[ln].seg[s][t], (size_t)2 * N, false))
+                        return rc;
+        if (track_upload_until(*j, lanes[ln].start + N) != hipSuccess)
+        {
+            set_error("track: upload failed");
+            return UMX_ERR_HIP;
+        }
+        ain[ln] = j->acc->in + 2 * (size_t)lanes[ln].start;
+        nn[ln] = (int)std::min<long long>(N, j->L2 - lanes[ln].start);
+        for (int t = 0; t < 4; ++t)
+            outs[4 * ln + t] = trk[ln].seg[si][t];
+    }
+    if (int rc = infer_batch(nl, ain, nn, outs, flags))
+        return rc;
+    if (last_slot >= 0) // accumulate in segment order (two segments overlap by a quarter)
+        (void)hipStreamWaitEvent(st, trk_acc_ev[last_slot], 0);
+    for (int ln = 0; ln < nl; ++ln)
+    {
+        TrackJob *j = lanes[ln].job;
+        if (!j)
+            continue;
+        // The segment's stems (nn frames at padded frame `start`) are blended into the job's accumulators.  A sample is final once
+        // the segment that starts at or before it and the one before that have been blended in: region [start_i, start_{i+1}) right
+        // after segment i.  It is normalised there and then (and mixed over its stems, before `ready`), and the host downloads it
+        // while the GPU is already busy with the following segments.
+        const TrackBufs &tb_ = *j->acc;
+        Stems4 tk, seg;
+        for (int t = 0; t < 4; ++t)
+        {
+            tk.p[t] = reinterpret_cast<float2 *>(tb_.out[t]);
+            seg.p[t] = reinterpret_cast<float2 *>(trk[ln].seg[si][t]);
+        }
+        TrackRegion rg = {j, (int)lanes[ln].start, 0, nullptr};
+        rg.count = (int)std::min<long long>((long long)rg.start + stride, j->L2) - rg.start;
+        hipLaunchKernelGGL(track_accumulate_kernel, dim3((nn[ln] + 255) / 256, 4), dim3(256), 0, st, tk, tb_.sumw, seg, rg.start, nn[ln], N);
+        hipLaunchKernelGGL(track_normalise_kernel, dim3((rg.count + 255) / 256, 4), dim3(256), 0, st, tk, tb_.sumw, rg.start, rg.count);
+        if (!j->by_region)
+            continue;
+        if (mix)
+            track_mix(*mix, tb_.out, (size_t)rg.start, tb_.in, (size_t)rg.start, rg.count, st);
+        if (hipEventCreateWithFlags(&rg.ready, hipEventDisableTiming) != hipSuccess)
+        {
+            set_error("track: event creation failed");
+            return UMX_ERR_HIP;
+        }
+        regions.v.push_back(rg); // (the list owns the event from here on)
+        if (hipEventRecord(rg.ready, st) != hipSuccess)
+        {
+            set_error("track: event creation failed");
+            return UMX_ERR_HIP;
+        }
+    }
+    (void)hipEventRecord(trk_acc_ev[si], st);
+    last_slot = si;
+    return UMX_OK;
+}
+
+int umx_hip_ctx::tracks_once(const TrackRequest &rq)
 {
     // ensemble: the caller (umx_hip_shift_ensemble) has repeated the one track's audio pointer, length and rate per lane
-    // and checked the offsets; out_host holds that track's 4 stems
-    // mix: a checked matrix; a track has n_host = mix->n_out host buffers instead of four, out_host[n_host * lane + m]
-    const int n_host = mix ? mix->n_out : 4;
-    if (nt < 1 || nt > B || !audio_host || !length_in || !shift_offset || !out_host)
+    // and checked the offsets; rq.out holds that track's buffers
+    // mix: a checked matrix; a track has n_host = mix->n_out host buffers instead of four
+    const int nt = rq.n_tracks, n_host = rq.mix ? rq.mix->n_out : 4;
+    const int *const length_in = rq.length;
+    const bool ensemble = rq.ensemble;
+    const MixSpec *const mix = rq.mix;
+    if (nt < 1 || nt > B || !rq.audio || !length_in || !rq.shift_offset)
     {
         set_error("tracks: need 1 <= n_tracks <= the context's track count and non-null argument arrays");
         return UMX_ERR_ARG;
     }
-    if (int rc = check_flags(flags))
+    if (int rc = check_flags(rq.flags))
         return rc;
     for (int ln = 0; ln < nt; ++ln)
-    {
-        bool ok = audio_host[ln] && length_in[ln] >= 1 && shift_offset[ln] < UMX_MAX_SHIFT;
-        for (int m = 0; m < n_host; ++m)
-            ok = ok && out_host[(ensemble ? 0 : n_host * ln) + m];
-        if (!ok)
+        if (!track_job_ok(rq.audio[ln], length_in[ln], rq.shift_offset[ln], rq.out && !ensemble ? rq.out + n_host * ln : rq.out, n_host))
         {
             set_error("track: need audio, outputs, length >= 1 and shift offset < 22050");
             return UMX_ERR_ARG;
         }
-    }
     // A track at another rate runs as the n44 = ceil(length L / M) frames of its 44.1 kHz version: `length` below is
     // that length, length_in the caller's.
     int length[LSTMB_MAX_TRACKS];
@@ -173,9 +233,9 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
     for (int ln = 0; ln < nt; ++ln)
     {
         length[ln] = length_in[ln];
-        if (!rate || rate[ln] == RS_MODEL_RATE)
+        if (!rq.rate || rq.rate[ln] == RS_MODEL_RATE)
             continue;
-        const long long n44 = resampled_length(length_in[ln], rate[ln], RS_MODEL_RATE);
+        const long long n44 = resampled_length(length_in[ln], rq.rate[ln], RS_MODEL_RATE);
         if (n44 < 1 || n44 > 0x7fffffff / 2)
         {
             set_error(n44 < 1 ? "track: sample rate outside 8000 .. 192000 Hz" : "track: too long");
@@ -183,9 +243,9 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
         }
         length[ln] = (int)n44;
         resampled[ln] = true;
-        if (int rc = resample_plan(rate[ln], RS_MODEL_RATE, rs_fwd[ln], &rs_fwd_taps[ln]))
+        if (int rc = resample_plan(rq.rate[ln], RS_MODEL_RATE, rs_fwd[ln], &rs_fwd_taps[ln]))
             return rc;
-        if (int rc = resample_plan(RS_MODEL_RATE, rate[ln], rs_back[ln], &rs_back_taps[ln]))
+        if (int rc = resample_plan(RS_MODEL_RATE, rq.rate[ln], rs_back[ln], &rs_back_taps[ln]))
             return rc;
     }
     if (ph_next != -1)
@@ -196,8 +256,8 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
     // Reset mode (UMX_FLAG_RESET_SEGMENTS, SURVEY 8(e)'s mode table): every segment starts from a ZERO lstm_data instead of the one
     // the previous segment left behind (umx.cpp:167-171 makes it once per track, :226-227 hands it to every call) -- a declared
     // deviation, opt-in.  The segments of a track are then independent, and up to B of them ride as the track lanes of ONE call.
-    const bool reset_lanes = (flags & UMX_FLAG_RESET_SEGMENTS) != 0;
-    flags &= ~(unsigned)UMX_FLAG_RESET_SEGMENTS;
+    const bool reset_lanes = (rq.flags & UMX_FLAG_RESET_SEGMENTS) != 0;
+    const unsigned flags = rq.flags & ~(unsigned)UMX_FLAG_RESET_SEGMENTS;
     if (reset_lanes && (nt != 1 || !lstm_batched || B < 2 || ensemble))
     {
         set_error("track: UMX_FLAG_RESET_SEGMENTS takes ONE track on a context made by umx_hip_create_tracks with at least 2 lanes");
@@ -206,67 +266,49 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
     UMX_HIP_CHECK(hipSetDevice(device));
     if (int rc = sync_all())
         return rc;
-    int lead[LSTMB_MAX_TRACKS], L2[LSTMB_MAX_TRACKS], L2max = 0;
+    const int stride = track_stride();
+    TrackJob job[LSTMB_MAX_TRACKS]; // lane ln's track
+    int L2max = 0, max_segs = 0;
     for (int ln = 0; ln < nt; ++ln)
     {
-        lead[ln] = shift_offset[ln] < 0 ? 0 : shift_offset[ln];
-        // umx.cpp:120-122: length + max_shift - offset -- which the reference overruns for offset > max_shift / 2 (its
-        // block write is [offset, offset + length)); the same size where the reference is defined, large enough elsewhere
-        const long long l2 = shift_offset[ln] < 0 ? (long long)length[ln]
-                                                  : (long long)length[ln] + std::max(UMX_MAX_SHIFT - shift_offset[ln], shift_offset[ln]);
-        if (l2 > 0x7fffffff / 2)
+        TrackJob &j = job[ln];
+        if (!track_geometry(length[ln], rq.shift_offset[ln], stride, j))
         {
             set_error("track: too long");
             return UMX_ERR_ARG;
         }
-        L2[ln] = (int)l2;
-        L2max = std::max(L2max, L2[ln]);
+        j.audio = rq.audio[ln];
+        j.by_region = !ensemble && !resampled[ln];
+        L2max = std::max(L2max, j.L2);
+        max_segs = std::max(max_segs, j.segs);
     }
-    const int stride = (int)((1 - 0.25f) * N); // umx.cpp:181, inference.hpp:15
     // lanes whose per-segment stem buffers are needed: one per track, or (reset mode) one per segment of a call
-    const int seg_lanes = reset_lanes ? (int)std::min<long long>(B, ((long long)L2max + stride - 1) / stride) : nt;
+    const int seg_lanes = reset_lanes ? std::min(B, max_segs) : nt;
     if (trk.size() < (size_t)seg_lanes)
         trk.resize(seg_lanes);
-    for (int ln = 0; ln < seg_lanes; ++ln)
+    for (int ln = 0; ln < nt; ++ln)
     {
-        if (ln < nt)
-            if (int rc = track_bufs_grow(trk[ln], (size_t)L2[ln]))
-                return rc;
-        if (int rc = track_bufs_segs(trk[ln]))
+        job[ln].acc = &trk[ln];
+        if (int rc = track_bufs_grow(trk[ln], (size_t)job[ln].L2))
             return rc;
     }
-    if (!trk_acc_ev[0])
-        for (int s = 0; s < nslots; ++s)
-            UMX_HIP_CHECK(hipEventCreateWithFlags(&trk_acc_ev[s], hipEventDisableTiming));
-    if (ensemble && (size_t)length[0] > ens_cap) // the mean of the lanes' stems: n44 frames, grow-only
-    {
-        for (float *&p : ens_out)
-            if (p)
-            {
-                allocs.erase(std::find(allocs.begin(), allocs.end(), (void *)p));
-                (void)hipFree(p);
-                p = nullptr;
-            }
-        ens_cap = 0;
-        const size_t cap = (size_t)length[0] + (size_t)length[0] / 8;
-        for (float *&p : ens_out)
-            if (int rc = dalloc(&p, 2 * cap, false))
-                return rc;
-        ens_cap = cap;
-    }
+    if (ensemble) // the mean of the lanes' stems: n44 frames
+        if (int rc = grow_frames({{&ens_out[0], 2}, {&ens_out[1], 2}, {&ens_out[2], 2}, {&ens_out[3], 2}}, ens_cap, (size_t)length[0]))
+            return rc;
     // umx.cpp:167-171: a fresh, zeroed lstm_data per track; umx.cpp:186-195: zeroed accumulators (and F4)
     UMX_HIP_CHECK(hipMemset(state, 0, sizeof(float) * state_floats() * (reset_lanes ? B : nt)));
     clear_used();
     for (int ln = 0; ln < nt; ++ln) // (reset mode: nt = 1)
     {
-        TrackBufs &tb_ = trk[ln];
-        UMX_HIP_CHECK(hipMemset(tb_.in, 0, sizeof(float) * 2 * (size_t)L2[ln]));
+        const TrackBufs &tb_ = trk[ln];
+        const size_t frames = (size_t)job[ln].L2;
+        UMX_HIP_CHECK(hipMemset(tb_.in, 0, sizeof(float) * 2 * frames));
         for (int t = 0; t < 4; ++t)
-            UMX_HIP_CHECK(hipMemset(tb_.out[t], 0, sizeof(float) * 2 * (size_t)L2[ln]));
-        UMX_HIP_CHECK(hipMemset(tb_.sumw, 0, sizeof(float) * (size_t)L2[ln]));
+            UMX_HIP_CHECK(hipMemset(tb_.out[t], 0, sizeof(float) * 2 * frames));
+        UMX_HIP_CHECK(hipMemset(tb_.sumw, 0, sizeof(float) * frames));
     }
     // a resampled track goes up whole at its own rate, into a grow-only staging buffer, and is resampled straight into the padded
-    // 44.1 kHz signal (upload_until below then has nothing left to do for it)
+    // 44.1 kHz signal (track_upload_until then has nothing left to do for it)
     if (rs_stage.size() < (size_t)nt)
         rs_stage.resize(nt);
     for (int ln = 0; ln < (ensemble ? 1 : nt); ++ln) // (an ensemble's one track: staged and resampled once, into lane 0)
@@ -274,211 +316,127 @@ int umx_hip_ctx::tracks_once(int nt, const float *const *audio_host, const int *
         if (!resampled[ln])
             continue;
         RsStage &rs = rs_stage[ln];
-        if ((size_t)length_in[ln] > rs.cap)
-        {
-            for (float **p : {&rs.in, &rs.out[0], &rs.out[1], &rs.out[2], &rs.out[3]})
-                if (*p)
-                {
-                    allocs.erase(std::find(allocs.begin(), allocs.end(), (void *)*p));
-                    (void)hipFree(*p);
-                    *p = nullptr;
-                }
-            rs.cap = 0;
-            const size_t cap = (size_t)length_in[ln] + (size_t)length_in[ln] / 8;
-            for (float **p : {&rs.in, &rs.out[0], &rs.out[1], &rs.out[2], &rs.out[3]})
-                if (int rc = dalloc(p, 2 * cap, false))
-                    return rc;
-            rs.cap = cap;
-        }
-        UMX_HIP_CHECK(hipMemcpy(rs.in, audio_host[ln], sizeof(float) * 2 * (size_t)length_in[ln], hipMemcpyHostToDevice));
+        if (int rc = grow_frames({{&rs.in, 2}, {&rs.out[0], 2}, {&rs.out[1], 2}, {&rs.out[2], 2}, {&rs.out[3], 2}}, rs.cap, (size_t)length_in[ln]))
+            return rc;
+        UMX_HIP_CHECK(hipMemcpy(rs.in, rq.audio[ln], sizeof(float) * 2 * (size_t)length_in[ln], hipMemcpyHostToDevice));
         const float *src = rs.in;
-        float *dst = trk[ln].in + 2 * (size_t)lead[ln];
+        float *dst = trk[ln].in + 2 * (size_t)job[ln].lead;
         UMX_HIP_CHECK(launch_resample(rs_fwd[ln], rs_fwd_taps[ln], 1, &src, length_in[ln], &dst, length[ln], nullptr));
     }
     // an ensemble's track crosses PCIe once, whole, into lane 0 (unless the resampler has just written it there); the other lanes
     // get it from lane 0, device to device, behind their own shift's zeros (the memsets above)
     if (ensemble)
     {
-        float *first = trk[0].in + 2 * (size_t)lead[0];
+        float *first = trk[0].in + 2 * (size_t)job[0].lead;
         const size_t bytes = sizeof(float) * 2 * (size_t)length[0];
         if (!resampled[0])
-            UMX_HIP_CHECK(hipMemcpy(first, audio_host[0], bytes, hipMemcpyHostToDevice));
+            UMX_HIP_CHECK(hipMemcpy(first, rq.audio[0], bytes, hipMemcpyHostToDevice));
         for (int ln = 1; ln < nt; ++ln)
-            UMX_HIP_CHECK(hipMemcpy(trk[ln].in + 2 * (size_t)lead[ln], first, bytes, hipMemcpyDeviceToDevice));
+            UMX_HIP_CHECK(hipMemcpy(trk[ln].in + 2 * (size_t)job[ln].lead, first, bytes, hipMemcpyDeviceToDevice));
     }
     UMX_HIP_CHECK(hipDeviceSynchronize());
-    // The track goes up segment by segment (round 6): a call needs the samples up to the end of its last segment, and the rest of a
-    // pageable upload (14 GB/s: 15 ms for ten minutes of stereo) runs while the device is busy with the segments before it -- the
-    // slots' streams do not wait for the null stream, and launches are queued ahead of the copy.
-    long long uploaded[LSTMB_MAX_TRACKS] = {}; // host samples of each track already on the device
     for (int ln = 0; ln < nt; ++ln)
-        if (resampled[ln] || ensemble)
-            uploaded[ln] = length[ln];
-    auto upload_until = [&](int ti, long long padded_end) -> hipError_t { // samples of the padded signal below `padded_end` must be there
-        return track_upload_until(trk[ti].in, audio_host[ti], length[ti], lead[ti], uploaded[ti], padded_end);
-    };
-
-    // the mix of `count` frames of lane ln (track_mix); column 4 is the lane's own padded input at the same index
-    auto queue_mix = [&](int ln, float *const stems[4], size_t stem_start, size_t in_start, int count, hipStream_t st) {
-        track_mix(*mix, stems, stem_start, trk[ln].in, in_start, count, st);
-    };
+        if (resampled[ln] || ensemble) // (on the device whole already)
+            job[ln].uploaded = length[ln];
 
     const float total_reps = std::ceil((float)L2max / (float)stride); // umx.cpp:208 (of the longest track)
     float done = 0.f;
-    // A sample is final once the segment that starts at or before it and the one before that have been blended
-    // in: region [offset_i, offset_{i+1}) right after segment i.  It is normalised there and then, and the host
-    // downloads it while the GPU is already busy with the following segments.
-    struct Region
-    {
-        int lane, start, count;
-        hipEvent_t ready;
-    };
-    std::vector<Region> regions;
-    auto cleanup = [&]() {
-        for (Region &r : regions)
-            (void)hipEventDestroy(r.ready);
-    };
-    int last_slot = -1, iseg = 0;
+    TrackRegions regions;
+    int last_slot = -1;
     const int per_call = reset_lanes ? seg_lanes : 1; // segments of a track per call
-    for (long long off = 0; off < L2max; off += (long long)stride * per_call, ++iseg)
+    const int nl = reset_lanes ? per_call : nt;        // lanes of a call: lane = track (its segment at `off`), or lane k = segment k of the call
+    for (long long off = 0; off < L2max; off += (long long)stride * per_call)
     {
-        const int si = next_slot();
-        const float *ain[LSTMB_MAX_TRACKS] = {};
-        int nn[LSTMB_MAX_TRACKS] = {}, seg_off[LSTMB_MAX_TRACKS] = {};
-        float *outs[4 * LSTMB_MAX_TRACKS] = {};
-        const int nl = reset_lanes ? per_call : nt; // lanes of this call: lane = track (its segment at `off`), or lane k = segment k of the call
+        TrackLane lanes[LSTMB_MAX_TRACKS];
+        int queued = 0; // segments of the longest track in this call
         for (int ln = 0; ln < nl; ++ln)
         {
-            const int ti = reset_lanes ? 0 : ln;
+            TrackJob &j = job[reset_lanes ? 0 : ln];
             const long long so = reset_lanes ? off + (long long)ln * stride : off;
-            if (so < L2[ti]) // this track still has a segment here (umx.cpp:214-217)
-            {
-                seg_off[ln] = (int)so;
-                ain[ln] = trk[ti].in + 2 * (size_t)so;
-                nn[ln] = std::min(N, L2[ti] - (int)so);
-                if (upload_until(ti, so + N) != hipSuccess)
-                {
-                    cleanup();
-                    set_error("track: upload failed");
-                    return UMX_ERR_HIP;
-                }
-                for (int t = 0; t < 4; ++t)
-                    outs[4 * ln + t] = trk[ln].seg[si][t];
-            }
+            if (so >= j.L2) // this track has no segment here any more (umx.cpp:214-217)
+                continue;
+            lanes[ln].job = &j;
+            lanes[ln].start = so;
+            queued = reset_lanes ? queued + 1 : 1;
         }
-        if (reset_lanes && iseg > 0) // every segment from a zero state: the previous call has left its own behind
+        if (reset_lanes && off > 0) // every segment from a zero state: the previous call has left its own behind
         {
-            if (int rc = sync_all())
+            // (the samples of this call go up first, while the device is still busy with the previous one)
+            if (track_upload_until(job[0], off + (long long)stride * (per_call - 1) + N) != hipSuccess)
             {
-                cleanup();
-                return rc;
+                set_error("track: upload failed");
+                return UMX_ERR_HIP;
             }
+            if (int rc = sync_all())
+                return rc;
             UMX_HIP_CHECK(hipMemset(state, 0, sizeof(float) * state_floats() * B));
             UMX_HIP_CHECK(hipDeviceSynchronize());
         }
-        const int rc = infer_batch(nl, ain, nn, outs, flags);
-        if (rc)
-        {
-            cleanup();
+        if (int rc = track_call(lanes, nl, flags, mix, last_slot, regions))
             return rc;
-        }
-        hipStream_t st = slot[si].stream;
-        if (last_slot >= 0) // accumulate in segment order (two segments overlap by a quarter)
-            (void)hipStreamWaitEvent(st, trk_acc_ev[last_slot], 0);
-        for (int ln = 0; ln < nl; ++ln)
+        // umx.cpp:229, once per QUEUED segment (queued, not finished: the device runs behind the host here) of the longest track: one
+        // per call, or (reset mode) one per lane of the call
+        for (int q = 0; q < queued; ++q)
         {
-            if (!ain[ln])
-                continue;
-            const int ti = reset_lanes ? 0 : ln, offset = seg_off[ln];
-            Region rg;
-            rg.lane = ti;
-            rg.start = offset;
-            // the region is final: its mix goes over its stems right here, before `ready` (a resampled track is mixed whole, below;
-            // an ensemble's lanes are averaged behind the last segment, nothing is downloaded region by region)
-            rg.count = track_region(trk[ti], trk[ln].seg[si], offset, nn[ln], L2[ti], stride, mix && !ensemble && !resampled[ti] ? mix : nullptr, st);
-            if (ensemble)
-                continue;
-            if (hipEventCreateWithFlags(&rg.ready, hipEventDisableTiming) != hipSuccess || hipEventRecord(rg.ready, st) != hipSuccess)
-            {
-                cleanup();
-                set_error("track: event creation failed");
-                return UMX_ERR_HIP;
-            }
-            regions.push_back(rg);
+            done += 1.0f / total_reps;
+            if (rq.progress)
+                rq.progress(done, rq.progress_user);
         }
-        (void)hipEventRecord(trk_acc_ev[si], st);
-        last_slot = si;
-        done += 1.0f / total_reps; // umx.cpp:229 (queued, not finished: the device runs behind the host here)
-        if (progress)
-            progress(done, progress_user);
     }
-    // a resampled track's four stems: n44 frames from the shift on, back to the caller's rate in one launch behind the last
-    // segment's overlap-add (they are downloaded whole below, not region by region)
+    // What leaves whole, behind the last segment's overlap-add: four stem buffers of lane ln's track from frame `start` on are mixed
+    // at 44.1 kHz (column 4: the lane's padded input), a resampled track's n_host buffers go back to the caller's rate in one launch
+    // into the lane's rs_stage, and `whole` notes where the host finds them.
     hipError_t cerr = hipSuccess;
     const hipStream_t last_st = slot[last_slot].stream;
+    float *whole[LSTMB_MAX_TRACKS][4] = {};
+    bool any_whole = false;
+    auto leaves_whole = [&](int ln, float *const stems[4], size_t start) {
+        const TrackJob &j = job[ln];
+        if (mix)
+            track_mix(*mix, stems, start, j.acc->in, (size_t)j.lead, j.length, last_st);
+        const float *src[4];
+        for (int t = 0; t < 4; ++t)
+            src[t] = whole[ln][t] = stems[t] + 2 * start;
+        if (resampled[ln])
+        {
+            cerr = launch_resample(rs_back[ln], rs_back_taps[ln], n_host, src, j.length, rs_stage[ln].out, length_in[ln], last_st);
+            std::copy(rs_stage[ln].out, rs_stage[ln].out + 4, whole[ln]);
+        }
+        any_whole = true;
+    };
     if (ensemble)
     {
         // Every lane's last overlap-add is ordered before this stream's (trk_acc_ev chains the calls).  The mean of the lanes' `length`
-        // frames from their shifts on goes to ens_out; a resampled track's four means (n44 frames) then go back to the caller's rate
-        // in one launch, as a single resampled track's stems would.
-        ShiftMeanLanes lanes = {};
+        // frames from their shifts on goes to ens_out, from frame 0 on; it leaves as a single track's stems would (column 4 of its
+        // mix: lane 0's copy of the track).
+        ShiftMeanLanes mean_of = {};
         Stems4 mean;
         for (int t = 0; t < 4; ++t)
         {
             for (int ln = 0; ln < nt; ++ln)
-                lanes.src[ln][t] = reinterpret_cast<const float2 *>(trk[ln].out[t]) + lead[ln];
+                mean_of.src[ln][t] = reinterpret_cast<const float2 *>(trk[ln].out[t]) + job[ln].lead;
             mean.p[t] = reinterpret_cast<float2 *>(ens_out[t]);
         }
         for (hipEvent_t &e : ens_ev)
             if (!e)
                 UMX_HIP_CHECK(hipEventCreate(&e));
         (void)hipEventRecord(ens_ev[0], last_st);
-        launch_shift_mean(lanes, nt, mean, length[0], last_st);
+        launch_shift_mean(mean_of, nt, mean, length[0], last_st);
         (void)hipEventRecord(ens_ev[1], last_st);
         ens_timed = true;
-        if (mix) // the mix of the MEAN, over the means (column 4: lane 0's copy of the track); what follows handles n_host buffers
-            queue_mix(0, ens_out, 0, (size_t)lead[0], length[0], last_st);
-        float *const *result = ens_out;
-        if (resampled[0])
-        {
-            const float *src[4] = {ens_out[0], ens_out[1], ens_out[2], ens_out[3]};
-            cerr = launch_resample(rs_back[0], rs_back_taps[0], n_host, src, length[0], rs_stage[0].out, length_in[0], last_st);
-            result = rs_stage[0].out;
-        }
-        if (cerr == hipSuccess)
-            cerr = hipStreamSynchronize(last_st);
-        for (int t = 0; t < n_host && cerr == hipSuccess; ++t)
-            cerr = hipMemcpy(out_host[t], result[t], sizeof(float) * 2 * (size_t)length_in[0], hipMemcpyDeviceToHost);
+        leaves_whole(0, ens_out, 0);
     }
     for (int ln = 0; ln < nt && cerr == hipSuccess && !ensemble; ++ln)
         if (resampled[ln])
-        {
-            if (mix) // the n44 frames are mixed at 44.1 kHz, then its n_host buffers go back
-                queue_mix(ln, trk[ln].out, (size_t)lead[ln], (size_t)lead[ln], length[ln], last_st);
-            const float *src[4];
-            for (int t = 0; t < 4; ++t)
-                src[t] = trk[ln].out[t] + 2 * (size_t)lead[ln];
-            cerr = launch_resample(rs_back[ln], rs_back_taps[ln], n_host, src, length[ln], rs_stage[ln].out, length_in[ln], last_st);
-        }
-    for (const Region &rg : regions) // umx.cpp:136-147: drop the shift
-    {
-        const int ln = rg.lane;
-        if (resampled[ln])
-            continue;
+            leaves_whole(ln, trk[ln].out, (size_t)job[ln].lead);
+    for (const TrackRegion &rg : regions.v) // umx.cpp:136-147: drop the shift
         if (cerr == hipSuccess)
-            cerr = track_region_download(trk[ln], rg.start, rg.count, lead[ln], length[ln], n_host, out_host + n_host * ln, rg.ready);
-    }
-    cleanup();
-    bool synced = false;
-    for (int ln = 0; ln < nt && cerr == hipSuccess && !ensemble; ++ln)
-        if (resampled[ln])
-        {
-            if (!synced)
-                cerr = hipStreamSynchronize(last_st);
-            synced = true;
-            for (int t = 0; t < n_host && cerr == hipSuccess; ++t)
-                cerr = hipMemcpy(out_host[n_host * ln + t], rs_stage[ln].out[t], sizeof(float) * 2 * (size_t)length_in[ln], hipMemcpyDeviceToHost);
-        }
+            cerr = track_region_download(rg, n_host, rq.out + n_host * (rg.job - job));
+    if (any_whole && cerr == hipSuccess)
+        cerr = hipStreamSynchronize(last_st);
+    for (int ln = 0; ln < nt; ++ln)
+        for (int t = 0; t < n_host && whole[ln][0] && cerr == hipSuccess; ++t) // (an ensemble's one result: lane 0)
+            cerr = hipMemcpy(rq.out[n_host * ln + t], whole[ln][t], sizeof(float) * 2 * (size_t)length_in[ln], hipMemcpyDeviceToHost);
     if (cerr != hipSuccess)
     {
         set_error(hipGetErrorString(cerr));
