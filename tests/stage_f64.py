@@ -267,8 +267,9 @@ def mixture_phase(spec, mags, precision, bins=None):
 
 
 def target_weights(file_target):
-    """One target of ggml.read_model -> name -> the file's dequantised float32 tensor."""
-    return {k: v["f32"] for k, v in file_target.items()}
+    """One target of ggml.read_model -> name -> the file's dequantised float32 tensor; a bare float32 array (tests/fp32_weights.py)
+    is the tensor itself."""
+    return {k: (v["f32"] if isinstance(v, dict) else v) for k, v in file_target.items()}
 
 
 def _t(a, dt):

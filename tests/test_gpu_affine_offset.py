@@ -19,6 +19,8 @@ Covered here, every case with the kernels asserted by name:
   * gemm_planes_kernel / _pp_kernel / _ps_kernel on 256 x 256 tiles bit for bit on the fully skewed hidden-512 model, which ties the
     other two flavours to the one checked against float64;
   * the per-weight form of a three-lane context (UMX_CREATE_U8_DEQUANT);
+    (the fp32-resident family that form belongs to -- form 2 of the plane GEMMs, lstm_batch_kernel<WQ = false>, the one-track
+    context on float32 tensors -- is held to float64 at hidden 512 / 1024 by tests/test_gpu_fp32_weights_f64.py);
   * the batched recurrences' own W_hh offset term, which keeps the centre 128, on models with only W_hh skewed:
     lstm_batch_kernel at K = 64 (first segment, carried state, FLAG_PRECISE_ACT), lstm_batch8_kernel at K = 256 (hidden 512, ten
     lanes) and K = 512 (hidden 1024: nine lanes = one octet and a lane, 40 lanes = two octets per workgroup in turn), each on the
