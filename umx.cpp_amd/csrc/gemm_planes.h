@@ -19,17 +19,22 @@
 //     c = the source tensor's zero-weight code, 0 .. 255 / 31 .. 65504 (quant_centre, quant_planes.h); the kernels see (s, o + c s) only
 //   * tiles go global -> LDS by `buffer_load_dwordx4 ... lds` (no VGPRs, no ds_write, no VALU), 16 bytes per lane,
 //     the XOR swizzle of the LDS layout folded into WHICH 16 bytes a lane fetches;
-//   * products per 32x32x16 block: 2 (u8 weights) or 3 (u16 / fp32 weights: a2 P_hi, a1 P_lo, a1 P_hi; with |P_lo| <=
+//   * products per block and K tile: 2 (u8 weights) or 3 (u16 / fp32 weights: a2 P_hi, a1 P_lo, a1 P_hi; with |P_lo| <=
 //     2^-11 |P_hi| the fourth, a2 P_lo, is 2^-22 of the sum -- the size of the activations' own split error -- and is not
 //     formed: DESIGN 4.6 (h)), every one exact in the fp32 accumulator's input (22-bit products), fp32 accumulate.
 //     (Round 2's first build used three bf16 planes per activation: 3 / 5 / 6 products and 6 bytes per activation
 //     element; profiles/r02_v1_*.)
-// Block tile (64 WM) x (64 WN) x 32, WM x WN waves, each 2 x 2 MFMA tiles of v_mfma_f32_32x32x16_f16.  The kernel is
+// Block tile (64 WM) x (64 WN) x 32, WM x WN waves, each 4 x 4 blocks of v_mfma_f32_16x16x32_f16: ONE instruction per block, term
+// and K tile (GP_MFMA_K32 below; until round 6, and with -DGP_MFMA_K32=0, 2 x 2 tiles of v_mfma_f32_32x32x16_f16, two instructions of
+// 16 k each).  Same fragment bytes, registers and cycles per flop -- but the chip holds a higher clock under the 16x16x32 stream:
+// +11 .. +14 % on these kernels, of which +4 % (W_ih) come back as cycles; W_ih 9.07 -> 8.53 ms, fc3 13.9 -> 12.5 per 64-lane launch
+// (profiles/gemm_mfma_k32_ab.txt).  The 16 x 16 results go back into the 32x32 register layout by two lane swaps per register pair
+// (gp_k32_to_square) before the affine fix-up, so the epilogues and their whole-line stores are the same code.  The kernel is
 // bound by the bytes it pulls out of the L2s as much as by the matrix pipe, so the default tile is 256 x 256 (16 waves,
 // one workgroup per CU: half the bytes per flop of 128 x 128), fed by launches that cover every track lane at once
 // (M = lanes x Tp rows); 128 x 128 remains for launches too small to fill the chip with the large tile.  LDS rows are
 // 64 bytes (32 k) as four 16-byte chunks, chunk c of row r stored at chunk c ^ ((r >> 2) & 3): a ds_read_b128 group
-// (16 lanes = rows of 4 residues mod 4 x 4 values of (r >> 2) & 3) then touches every bank exactly once.  STAGES
+// (16 lanes: which ones, and which chunk each takes so that the group touches every bank exactly once: gp_k32_frag_offset).  STAGES
 // buffers (3 where LDS allows), one barrier per K tile.  XCD-aware tile order and epilogues: gemm_common.h.
 #pragma once
 #include "gemm_bf16x3.h"
@@ -90,6 +95,65 @@ struct SplitArgs
 };
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// The matrix instruction of the three plane-GEMM kernels (this file, gemm_planes_pp.h, gemm_planes_ps.h): 1 = v_mfma_f32_16x16x32_f16,
+// 0 = v_mfma_f32_32x32x16_f16 (the form until round 6; A/B builds, tools/build_variants.sh).  Same wave tiles, same fragment bytes and
+// registers, same cycles per flop; one instruction per accumulator, term and 32-k trip where the 32x32x16 form has two of 16 k each, so
+// an accumulator is rounded once per term and trip instead of twice.  All three kernels follow the switch together: one arithmetic.
+#ifndef GP_MFMA_K32
+#define GP_MFMA_K32 1
+#endif
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+// A lane's fragment of a 16-row block for v_mfma_f32_16x16x32_f16: row l & 15 and, as the instruction's k = 8 q + j (q = l >> 4), the
+// tile's k = 8 c + j with c = (q + 3) & 3 = 3, 0, 1, 2: BOTH operands take their chunks in this order, so every product meets its
+// partner (the order of the 32 k inside one instruction is the only thing that changes).  Chunk c of a row is stored at chunk
+// c ^ ((row >> 2) & 3) of its 64 bytes; blocks start at multiples of 16 rows, so the swizzle is the lane's own.  Why not c = q: a
+// ds_read_b128 is served in the four lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32, i.e. rows 0-3 and 12-15
+// of one q beside rows 4-11 of the next.  With c = q the two land on the same physical chunks -- a 2-way bank conflict on every read,
+// measured (SQ_LDS_BANK_CONFLICT half of SQ_LDS_IDX_ACTIVE, profiles/gemm_mfma_k32_ab.txt); with chunks 3 apart in a pair of q they
+// take the four physical chunks once each: every bank once (tests/test_gemm_k32_layout_model.py), counter 0.  (Every order with
+// c(0) ^ c(1) = c(2) ^ c(3) = 3 does that; they differ in the low bits of the sums only.)
+__device__ __forceinline__ int gp_k32_frag_offset(int lane)
+{
+    const int q = lane >> 4, c = (q + 3) & 3;
+    return (lane & 15) * 64 + (c ^ ((lane >> 2) & 3)) * 16;
+}
+// The 16x16 result layout (register j: row 4 (l >> 4) + j, column l & 15) put back into the 32x32x16 layout the epilogues index (register
+// R: row (R & 3) + 8 (R >> 2) + 4 (l >> 5), column l & 31).  x = the four registers of block (16-row half bm, columns 0 .. 15) of a
+// 32 x 32 square, y = those of block (bm, columns 16 .. 31): afterwards x = registers 8 bm .. 8 bm + 3 of the square, y = 8 bm + 4 .. + 7.
+// v_permlane16_swap exchanges the odd 16-lane rows of x with the even rows of y, v_permlane32_swap lanes 32 .. 63 of x with lanes 0 .. 31
+// of y (tests/test_gemm_k32_layout_model.py).
+__device__ __forceinline__ void gp_k32_to_square(floatx4 &x, floatx4 &y)
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+    {
+        auto s = __builtin_amdgcn_permlane16_swap(__float_as_uint(x[j]), __float_as_uint(y[j]), false, false);
+        s = __builtin_amdgcn_permlane32_swap(s[0], s[1], false, false);
+        x[j] = __uint_as_float(s[0]);
+        y[j] = __uint_as_float(s[1]);
+    }
+}
+// a wave tile of 2 MI x 4 blocks of 16 x 16 -> the MI x 2 squares of 32 x 32 that the affine fix-up and gemm_epilogue take
+template <int MI> __device__ __forceinline__ void gp_k32_to_squares(const floatx4 (&acc4)[2 * MI][4], floatx16 (&acc)[MI][2])
+{
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int bm = 0; bm < 2; ++bm)
+            {
+                floatx4 x = acc4[2 * mi + bm][2 * ni], y = acc4[2 * mi + bm][2 * ni + 1];
+                gp_k32_to_square(x, y);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                {
+                    acc[mi][ni][8 * bm + j] = x[j];
+                    acc[mi][ni][8 * bm + 4 + j] = y[j];
+                }
+            }
+}
 
 __device__ __forceinline__ void split2_f16(const float (&x)[8], float scale, uint4 &p1, uint4 &p2)
 {
@@ -331,6 +395,38 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16) ? 1 : 2) void gemm_pl
         }                                                                                                            \
     }
 
+#define GP_LD(off) (*reinterpret_cast<const f16x8 *>(gp_smem + (off)))
+#if GP_MFMA_K32
+    floatx4 acc4[2 * MI][4]; // [16-row block along M][16-column block along N] of the wave's (32 MI) x 64 block
+#pragma unroll
+    for (int bm = 0; bm < 2 * MI; ++bm)
+#pragma unroll
+        for (int bn = 0; bn < 4; ++bn)
+            acc4[bm][bn] = floatx4{0.f, 0.f, 0.f, 0.f};
+    // fragment of rows (w*32*MI + 16 bm + (lane & 15)), one 8-k chunk of the 32-k tile per lane group: gp_k32_frag_offset
+    const int fragA = wm * 32 * MI * 64 + gp_k32_frag_offset(lane), fragB = 2 * A_PL + wn * 64 * 64 + gp_k32_frag_offset(lane);
+    // one term of a 32-k tile: one instruction per 16 x 16 block
+#define GP_TERM(PA, PB)                                                                                              \
+    {                                                                                                                \
+        f16x8 bf[4];                                                                                                 \
+        _Pragma("unroll") for (int bn = 0; bn < 4; ++bn) bf[bn] = GP_LD(bo + fragB + (PB)*B_PL + bn * 16 * 64);      \
+        _Pragma("unroll") for (int bm = 0; bm < 2 * MI; ++bm)                                                        \
+        {                                                                                                            \
+            const f16x8 am = GP_LD(bo + fragA + (PA)*A_PL + bm * 16 * 64);                                           \
+            _Pragma("unroll") for (int bn = 0; bn < 4; ++bn)                                                         \
+                acc4[bm][bn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bf[bn], acc4[bm][bn], 0, 0, 0);            \
+        }                                                                                                            \
+    }
+    // smallest terms first
+#define GP_COMPUTE(buf)                                                                                              \
+    {                                                                                                                \
+        const int bo = (buf)*BUF_BYTES;                                                                              \
+        GP_TERM(1, 0)                                                                                                \
+        if (NBP == 2) /* B = P_hi + P_lo, |P_lo| <= 2^-11 |P_hi|: a2 P_hi, a1 P_lo, a1 P_hi (a2 P_lo, 2^-22 of the sum, is not formed) */ \
+            GP_TERM(0, 1)                                                                                            \
+        GP_TERM(0, 0)                                                                                                \
+    }
+#else
     floatx16 acc[MI][2]; // [32-row tile along M][32-column tile along N] of the wave's (32 MI) x 64 block
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
@@ -343,7 +439,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16) ? 1 : 2) void gemm_pl
     // fragment of rows (w*32*MI + mi*32 + lr), k = kk*16 + lh*8 .. +8: logical chunk 2 kk + lh, swizzled by the row
     const int sw = (lr >> 2) & 3; // rows 32 apart share it
     const int fragA = (wm * 32 * MI + lr) * 64, fragB = 2 * A_PL + (wn * 64 + lr) * 64;
-#define GP_LD(off) (*reinterpret_cast<const f16x8 *>(gp_smem + (off)))
 #define GP_MFMA(A, B, C) C = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, B, C, 0, 0, 0);
 #define GP_TERM(PA, PB, KK)                                                                                          \
     {                                                                                                                \
@@ -372,6 +467,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16) ? 1 : 2) void gemm_pl
             }                                                                                                        \
         }                                                                                                            \
     }
+#endif
 
     // s_waitcnt vmcnt(n): all but the n most recent DMA instructions of this wave have landed
 #define GP_WAIT(n) __builtin_amdgcn_s_waitcnt(0x0f70 | (n))
@@ -456,9 +552,14 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16) ? 1 : 2) void gemm_pl
 #undef GP_WAIT
 #undef GP_DMA
 #undef GP_LD
-#undef GP_MFMA
 #undef GP_TERM
 #undef GP_COMPUTE
+#if GP_MFMA_K32
+    floatx16 acc[MI][2];
+    gp_k32_to_squares<MI>(acc4, acc);
+#else
+#undef GP_MFMA
+#endif
     {
         // acc = 2^e_m sum a (q - c)  ->  W x = (s 2^-e_m) acc + (o + c s) rowsum(A).  The two per-row factors are
         // computed once per row of the block and handed to the lanes through LDS (the stage buffers are free now);

@@ -12,12 +12,16 @@
 //      phase      2i            2i+1          2i+2          2i+3
 //      group 0    M(i)     |    C(i)     |    M(i+1)   |    C(i+1)   |        M = DMA issue + ALL fragment reads of
 //      group 1    C(i-1)   |    M(i)     |    C(i)     |    M(i+1)   |            one unit into registers
-//                          ^ s_barrier (all eight waves) at every phase boundary      C = that unit's 32 matrix instructions
+//                          ^ s_barrier (all eight waves) at every phase boundary      C = that unit's matrix instructions
 //
 // so that at any time one wave of a SIMD owns the matrix pipe while the other reads the fragments of its next unit
 // (20 KB per wave: 640 cycles of the LDS port for the four reading waves against 1,024 cycles of matrix instructions).
-// A unit is a whole 32-k tile: 32 matrix instructions and 80 fragment registers for one-plane (u8) weights, 48 and 96 for
-// two-plane (u16) ones, beside the 128 accumulator registers of the 128 x 64 wave tile.  Group 0 issues all LDS-DMA (in its M phase, into the stage both groups finished reading one barrier ago) and
+// A unit is a whole 32-k tile: 80 fragment registers for one-plane (u8) weights, 96 for two-plane (u16) ones, beside the 128
+// accumulator registers of the 128 x 64 wave tile, and 64 / 96 instructions of v_mfma_f32_16x16x32_f16 -- the wave tile as 8 x 4 blocks
+// of 16 x 16, one instruction per block and term (a2 P, then a1 P_lo, then a1 P_hi; GP_MFMA_K32 in gemm_planes.h, where the fragment
+// addressing and the way back into the epilogue's 32x32 register layout live; -DGP_MFMA_K32=0: 32 / 48 instructions of
+// v_mfma_f32_32x32x16_f16, the form until round 6.  Same cycles in the matrix pipe, a higher clock: profiles/gemm_mfma_k32_ab.txt).
+// Group 0 issues all LDS-DMA (in its M phase, into the stage both groups finished reading one barrier ago) and
 // waits for a tile at the end of the C phase before the M phase that reads it: a tile has two trips to arrive, as in
 // gemm_planes_kernel.  Every accumulator sees the same sequence of matrix instructions as there: bit-identical results.
 #pragma once
@@ -36,7 +40,7 @@ template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_plan
     constexpr int MI = 4, BM = 256, BN = 256;
     constexpr int A_PL = BM * 64, B_PL = BN * 64; // bytes of one plane tile of each operand
     constexpr int BUF_BYTES = 2 * A_PL + NBP * B_PL, STAGES = gp_stages(4, 4, NBP);
-    constexpr int PH = 1, KKP = 2 / PH; // phases per K tile, 16-k steps per phase (half-tile phases for the two-plane weights
+    [[maybe_unused]] constexpr int PH = 1, KKP = 2 / PH; // phases per K tile, 16-k steps per phase (half-tile phases for the two-plane weights
                                         // -- 32 matrix instructions per phase like the one-plane form -- measured slower: four
                                         // barriers per trip; fc2 4.9 against 4.6 ms, fc3 9.4 against 9.0)
     static_assert(NBP == 1 || NBP == 2, "weight planes: 1 (u8) or 2 (u16, fp32)");
@@ -93,6 +97,41 @@ template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_plan
         }                                                                                                            \
     }
 
+#define PP_LD(off) (*reinterpret_cast<const f16x8 *>(gp_smem + (off)))
+#if GP_MFMA_K32
+    // v_mfma_f32_16x16x32_f16: the wave tile as 8 x 4 blocks of 16 x 16, one instruction per block, term and trip; a unit's fragments are
+    // the same bytes in the same number of registers (8 row blocks x 2 planes of A, 4 column blocks x NBP planes of B)
+    floatx4 acc4[2 * MI][4]; // [16-row block][16-column block]
+#pragma unroll
+    for (int bm = 0; bm < 2 * MI; ++bm)
+#pragma unroll
+        for (int bn = 0; bn < 4; ++bn)
+            acc4[bm][bn] = floatx4{0.f, 0.f, 0.f, 0.f};
+    const int fragA = wm * 32 * MI * 64 + gp_k32_frag_offset(lane), fragB = 2 * A_PL + wn * 64 * 64 + gp_k32_frag_offset(lane);
+    f16x8 fa[2][2 * MI], fb[NBP][4];
+#define PP_LOAD(buf, ph)                                                                                             \
+    {                                                                                                                \
+        const int bo = (buf)*BUF_BYTES;                                                                              \
+        _Pragma("unroll") for (int p = 0; p < NBP; ++p)                                                              \
+            _Pragma("unroll") for (int bn = 0; bn < 4; ++bn)                                                         \
+                fb[p][bn] = PP_LD(bo + fragB + p * B_PL + bn * 16 * 64);                                             \
+        _Pragma("unroll") for (int p = 1; p >= 0; --p)                                                               \
+            _Pragma("unroll") for (int bm = 0; bm < 2 * MI; ++bm)                                                    \
+                fa[p][bm] = PP_LD(bo + fragA + p * A_PL + bm * 16 * 64);                                             \
+    }
+#define PP_TERM(PA, PB)                                                                                              \
+    _Pragma("unroll") for (int bm = 0; bm < 2 * MI; ++bm)                                                            \
+        _Pragma("unroll") for (int bn = 0; bn < 4; ++bn)                                                             \
+            acc4[bm][bn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[PA][bm], fb[PB][bn], acc4[bm][bn], 0, 0, 0);
+    // smallest terms first, term by term across the blocks: the order of gemm_planes_kernel
+#define PP_MMA()                                                                                                     \
+    {                                                                                                                \
+        PP_TERM(1, 0)                                                                                                \
+        if (NBP == 2)                                                                                                \
+            PP_TERM(0, NBP - 1)                                                                                      \
+        PP_TERM(0, 0)                                                                                                \
+    }
+#else
     floatx16 acc[MI][2];
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
@@ -105,7 +144,6 @@ template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_plan
     const int sw = (lr >> 2) & 3;
     const int fragA = (wm * 32 * MI + lr) * 64, fragB = 2 * A_PL + (wn * 64 + lr) * 64;
     f16x8 fa[2][MI][KKP], fb[NBP][2][KKP]; // the fragments of one unit: 16 + 4 (u8) or 8 + 4 (u16) x 4 registers
-#define PP_LD(off) (*reinterpret_cast<const f16x8 *>(gp_smem + (off)))
 #define PP_LOAD(buf, ph)                                                                                             \
     {                                                                                                                \
         const int bo = (buf)*BUF_BYTES;                                                                              \
@@ -141,6 +179,7 @@ template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_plan
             PP_TERM(1, 0, kl) PP_TERM(0, NBP - 1, kl) PP_TERM(0, 0, kl)                                              \
         }                                                                                                            \
     }
+#endif
     // vmcnt(n): all but the n most recent DMA instructions of this wave have landed (n <= 63: bits 3:0 and 15:14)
 #define PP_WAIT_VM(n) __builtin_amdgcn_s_waitcnt(0x0f70 | ((n) & 15) | (((n) >> 4) << 14))
 #define PP_WAIT_LDS() __builtin_amdgcn_s_waitcnt(0xc07f) // lgkmcnt(0)
@@ -227,12 +266,19 @@ template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_plan
 #undef PP_DMA
 #undef PP_LD
 #undef PP_LOAD
+#if !GP_MFMA_K32
 #undef PP_MFMA
+#endif
 #undef PP_TERM
 #undef PP_MMA
 #undef PP_WAIT_VM
 #undef PP_WAIT_LDS
 #undef PP_BARRIER
+#if GP_MFMA_K32
+    // the accumulators into the 32x32 register layout the fix-up and the epilogue index: two lane swaps per register pair
+    floatx16 acc[MI][2];
+    gp_k32_to_squares<MI>(acc4, acc);
+#endif
     {
         // the affine fix-up and the epilogue of gemm_planes_kernel (the stage buffers are free now)
         const int sel = n0 >= tg.bsplit ? 1 : 0;

@@ -1,6 +1,6 @@
 // gemm_planes_ps.h -- the ping-pong plane GEMM of gemm_planes_pp.h as a PERSISTENT kernel: one workgroup per CU walks a list of
 // 256 x 256 tiles flattened over the four targets, the K loop never drains between tiles, and a tile's epilogue runs INSIDE the first
-// trip of the next tile, one 32-row band of the wave tile at a time, each band followed by the matrix instructions that restart its
+// trip of the next tile, one 32-row band of the wave tile at a time, followed by the matrix instructions that restart the
 // accumulators from zero (inference.cpp:86,127,143 and lstm.cpp:132-136: the four dense products of a target).
 //
 // What a tile of gemm_planes_pp_kernel loses outside its main loop (profiles/r06_pp_tile_profile.txt): the wait for its
@@ -15,17 +15,21 @@
 //     otherwise make them count store acknowledgements (the first form relaxed them to "all but the 63 youngest operations", which
 //     still waits for 65 acknowledgements: fc3 +2.5 %, -DPS_PREWAIT=0);
 //   * the accumulators are the only copy of a tile's result, so its epilogue must be ISSUED before the next tile's first matrix
-//     instruction overwrites them -- but not a cycle earlier: trip 0 of a tile handles band mi = 0 .. 3 as { fix-up, bn / bias /
-//     activation and stores of the previous tile's band ; the band's matrix instructions of the first 16-k step, starting from a zero
-//     C operand }, so the matrix pipe restarts band by band under the vector and store work of the next band.  Only the first 16-k
-//     step's fragments are in registers meanwhile (the second step's are read behind the last band): the epilogue's temporaries take
-//     the place of those 40 / 48 registers;
+//     instruction overwrites them -- but not a cycle earlier: trip 0 of a tile runs the previous tile's epilogue band by band (mi =
+//     0 .. 3: the band's accumulators put back into the 32x32 register layout by lane swaps, fix-up, bn / bias / activation, stores),
+//     then restarts the bands' accumulators with the tile's FIRST TERM a2 P_hi from a zero C operand (v_mfma_f32_16x16x32_f16, one
+//     instruction per 16 x 16 block and term: gemm_planes.h GP_MFMA_K32; with -DGP_MFMA_K32=0 the first 16-k step of
+//     v_mfma_f32_32x32x16_f16, all terms).  Only the first term's fragments are in registers meanwhile -- the a2 plane of A and the
+//     first plane of B, 48 registers; the a1 plane and P_lo are read behind the last band --: the epilogue's temporaries take the
+//     place of the other 32 / 48.  Both wave groups run this epilogue in the SAME phase (group 0 in its C phase, group 1 at the end
+//     of its M phase, its barrier behind the epilogue): the CU's store path and vector pipes serve eight waves at once;
 //   * per-row factors of the affine fix-up, the rows' byte offsets (fc3: row -> (track lane, frame)) and the per-column vectors of the
 //     epilogue are tables in LDS behind the stage buffers: raw by LDS-DMA (no registers) three trips before a tile's end, finished by
 //     group 0 in the M phase of the next tile's first trip; the epilogue reads a row group's three vectors one group AHEAD of their use
 //     and the column vectors once per tile -- its instruction stream is vector work and stores, not LDS round trips.
 // Every accumulator sees the matrix instructions of gemm_planes_pp_kernel in the same order (the order ACROSS accumulators differs
 // in trip 0 only) and every output element the same scalar expression: bit-identical results (tests/test_gpu_batch.py).
+// (One arithmetic for gemm_planes_kernel, gemm_planes_pp_kernel and this kernel: they follow GP_MFMA_K32 together.)
 // Group 1 reads the second half of a first trip's fragments one phase later than the ping-pong schedule has it -- while group 0 is
 // in the M phase of trip 1, whose staging would overwrite exactly that stage: group 0 issues trip 1's staging at the START of its C
 // phase instead (one phase later; the stage it fills is needed three -- two-stage form: one -- phases on).
@@ -35,7 +39,6 @@
 namespace umx
 {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
 constexpr int PS_TAB_ROWS = 4, PS_TAB_COLS = 8; // row tables: rsc -> scale, rs0 -> offset, rs1 -> byte offset of the row, rs2; column tables: rm, var -> sd, 1/sd, gw, gb, osc, omn, fc3 column offset
 __host__ __device__ constexpr int ps_lds_bytes(int NBP) { return gp_lds_bytes(4, 4, NBP) + (PS_TAB_ROWS + PS_TAB_COLS) * 256 * 4; }
@@ -62,7 +65,8 @@ constexpr unsigned PS_DROP = 0x40000000u; // an offset the rebased mask resource
 template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_planes_ps_kernel(GemmPArgs args, int ntg)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char gp_smem[];
-    constexpr int MI = 4, BM = 256, BN = 256, KKP = 2;
+    constexpr int MI = 4, BM = 256, BN = 256;
+    [[maybe_unused]] constexpr int KKP = 2; // 16-k steps per trip of the 32x32x16 form
     constexpr int A_PL = BM * 64, B_PL = BN * 64;
     constexpr int BUF_BYTES = 2 * A_PL + NBP * B_PL, STAGES = gp_stages(4, 4, NBP);
     static_assert(NBP == 1 || NBP == 2, "weight planes: 1 (u8) or 2 (u16, fp32)");
@@ -70,7 +74,8 @@ template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_plan
     float *const coltab = rowtab + PS_TAB_ROWS * 256;                               // [8][256]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, ws = wave & 3;
-    const int wm = grp, wn = ws, lr = lane & 31, lh = lane >> 5;
+    const int wm = grp, wn = ws;
+    [[maybe_unused]] const int lr = lane & 31, lh = lane >> 5; // the lane's row and k half in a 32x32x16 fragment
     const int K = args.K, lda = args.lda, nk = K / GP_BK;
 
     // ---- this workgroup's tiles: the flat order of gemm_planes_pp_kernel (groups of GEMM_GROUP_M row tiles, column tiles inside)
@@ -164,12 +169,68 @@ template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_plan
         }                                                                                                            \
     }
 
+#define PS_LD(off) (*reinterpret_cast<const f16x8 *>(gp_smem + (off)))
+#if GP_MFMA_K32
+    // v_mfma_f32_16x16x32_f16 (gemm_planes_pp_kernel's form): 8 x 4 blocks of 16 x 16, band mi = row blocks 2 mi and 2 mi + 1.  A trip's
+    // fragments in two halves: FIRST = what the smallest term a2 P_hi needs (the a2 plane of A, the first plane of B), REST = the a1 plane
+    // and P_lo.  The first trip of a tile reads FIRST up front and REST behind the last band.
+    floatx4 acc4[2 * MI][4];
+    const floatx4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    const int fragA = wm * 32 * MI * 64 + gp_k32_frag_offset(lane), fragB = 2 * A_PL + wn * 64 * 64 + gp_k32_frag_offset(lane);
+    f16x8 fa[2][2 * MI], fb[NBP][4];
+#define PS_LOAD_KL(buf, kl)                                                                                          \
+    {                                                                                                                \
+        const int bo = (buf)*BUF_BYTES;                                                                              \
+        if ((kl) == 0)                                                                                               \
+        {                                                                                                            \
+            _Pragma("unroll") for (int bn = 0; bn < 4; ++bn) fb[0][bn] = PS_LD(bo + fragB + bn * 16 * 64);           \
+            _Pragma("unroll") for (int bm = 0; bm < 2 * MI; ++bm) fa[1][bm] = PS_LD(bo + fragA + A_PL + bm * 16 * 64); \
+        }                                                                                                            \
+        else                                                                                                         \
+        {                                                                                                            \
+            if (NBP == 2)                                                                                            \
+            {                                                                                                        \
+                _Pragma("unroll") for (int bn = 0; bn < 4; ++bn) fb[NBP - 1][bn] = PS_LD(bo + fragB + (NBP - 1) * B_PL + bn * 16 * 64); \
+            }                                                                                                        \
+            _Pragma("unroll") for (int bm = 0; bm < 2 * MI; ++bm) fa[0][bm] = PS_LD(bo + fragA + bm * 16 * 64);      \
+        }                                                                                                            \
+    }
+#define PS_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_f16(A, B, C, 0, 0, 0)
+    // the first term of a tile for band mi, from a zero C operand
+#define PS_BAND(mi, kl, ZERO)                                                                                        \
+    _Pragma("unroll") for (int bm = 2 * (mi); bm < 2 * (mi) + 2; ++bm)                                               \
+        _Pragma("unroll") for (int bn = 0; bn < 4; ++bn)                                                             \
+            acc4[bm][bn] = PS_MFMA(fa[1][bm], fb[0][bn], (ZERO) ? zero4 : acc4[bm][bn]);
+    // one term over the wave tile in gemm_planes_pp_kernel's instruction order
+#define PS_TERM(PA, PB)                                                                                              \
+    _Pragma("unroll") for (int bm = 0; bm < 2 * MI; ++bm)                                                            \
+        _Pragma("unroll") for (int bn = 0; bn < 4; ++bn)                                                             \
+            acc4[bm][bn] = PS_MFMA(fa[PA][bm], fb[PB][bn], acc4[bm][bn]);
+    // step 0 = the first term, step 1 = the other one or two: smallest first (gemm_planes_kernel's order per accumulator)
+#define PS_STEP(kl)                                                                                                  \
+    {                                                                                                                \
+        if ((kl) == 0)                                                                                               \
+            PS_TERM(1, 0)                                                                                            \
+        else                                                                                                         \
+        {                                                                                                            \
+            if (NBP == 2)                                                                                            \
+                PS_TERM(0, NBP - 1)                                                                                  \
+            PS_TERM(0, 0)                                                                                            \
+        }                                                                                                            \
+    }
+    // element R of square (mi, ni) in the 32x32 register layout, once PS_EPI_SWAP has run over the band
+#define PS_ACC(mi, ni, R) acc4[2 * (mi) + ((R) >> 3)][2 * (ni) + (((R) >> 2) & 1)][(R)&3]
+    // row blocks 2 mi + bm of the waiting tile into the 32x32 register layout (in place: two lane swaps per register pair)
+#define PS_EPI_SWAP(mi, bm)                                                                                          \
+    _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) gp_k32_to_square(acc4[2 * (mi) + (bm)][2 * ni], acc4[2 * (mi) + (bm)][2 * ni + 1]);
+#else
     floatx16 acc[MI][2];
     const floatx16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const int sw = (lr >> 2) & 3;
     const int fragA = (wm * 32 * MI + lr) * 64, fragB = 2 * A_PL + (wn * 64 + lr) * 64;
     f16x8 fa[2][MI][KKP], fb[NBP][2][KKP];
-#define PS_LD(off) (*reinterpret_cast<const f16x8 *>(gp_smem + (off)))
+#define PS_ACC(mi, ni, R) acc[mi][ni][R]
+#define PS_EPI_SWAP(mi, bm)
 #define PS_LOAD_KL(buf, kl)                                                                                          \
     {                                                                                                                \
         const int bo = (buf)*BUF_BYTES;                                                                              \
@@ -212,6 +273,7 @@ template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_plan
             PS_TERM(0, NBP - 1, kl)                                                                                  \
         PS_TERM(0, 0, kl)                                                                                            \
     }
+#endif
 #define PS_WAIT_VM(n) __builtin_amdgcn_s_waitcnt(0x0f70 | ((n) & 15) | (((n) >> 4) << 14))
 #define PS_WAIT_LDS() __builtin_amdgcn_s_waitcnt(0xc07f) // lgkmcnt(0)
 #define PS_BARRIER()                                                                                                 \
@@ -289,12 +351,16 @@ template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_plan
         const unsigned ro_[4] = {nx_ro.x, nx_ro.y, nx_ro.z, nx_ro.w};                                                \
         if ((mi)*4 + rq + 1 < 16)                                                                                    \
             PS_EPI_ROWS((mi)*4 + rq + 1)                                                                             \
+        if ((rq & 1) == 0)                                                                                           \
+        {                                                                                                            \
+            PS_EPI_SWAP(mi, rq >> 1) /* groups rq and rq + 1 are the two halves of one 16-row block */               \
+        }                                                                                                            \
         float ys_[2][4];                                                                                             \
         unsigned os_[2][4];                                                                                          \
         _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                             \
             _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                            \
             {                                                                                                        \
-                float y = mus_[j] * acc[mi][ni][4 * rq + j] + ads_[j];                                               \
+                float y = mus_[j] * PS_ACC(mi, ni, 4 * rq + j) + ads_[j];                                            \
                 if (MODE == G_IH)                                                                                    \
                     y = y + cv[ni][4]; /* lstm.cpp:132-135: W_ih x + b_ih */                                         \
                 else                                                                                                 \
@@ -392,7 +458,7 @@ template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_plan
     }
 
     // ---- the phases of a trip.  M: staging of trip u + STAGES - 1, the fragments of this trip (FIRST trip of a tile: of its first
-    // 16-k step only).  LATE: group 0 stages at the start of its C phase (kt = 1: group 1 is still reading trip u - 1's stage).
+    // term -- 32x32x16 form: its first 16-k step -- only).  LATE: group 0 stages at the start of its C phase (kt = 1: group 1 is still reading trip u - 1's stage).
     // YOUNG: the wait of a trip behind an epilogue -- about a stage that landed before the epilogue's stores were issued (PS_PREWAIT).
     int cur = 0, u = 0;
 #define PS_M(FIRST, LATE, YOUNG1, TAB, FINISH, SPLIT)                                                                       \
@@ -453,7 +519,7 @@ template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_plan
         cur = cur + 1 == STAGES ? 0 : cur + 1;                                                                       \
         ++u;                                                                                                         \
     }
-    // the second 16-k step of a tile's first trip: its fragments are read here, behind the bands
+    // the other terms (32x32x16 form: the second 16-k step) of a tile's first trip: their fragments are read here, behind the bands
 #define PS_C_FIRST_TAIL()                                                                                            \
     {                                                                                                                \
         PS_LOAD_KL(cur, 1)                                                                                           \
@@ -519,8 +585,8 @@ template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_plan
         if (tile + 1 < ntiles)
         {
             // ---- first trip of the next tile (the staging cursor entered it STAGES - 1 trips ago), the waiting tile's epilogue inside:
-            // band by band { fix-up, activation, stores ; the band's first 16-k step from a zero C operand } -- the matrix pipe restarts
-            // under the next band's vector and store work
+            // band by band { lane swaps into the 32x32 layout, fix-up, activation, stores }, then the bands' first term (32x32x16 form:
+            // first 16-k step) from a zero C operand
             c_m0 = n_m0;
             c_n0 = n_n0;
             c_tgi = n_tgi;
@@ -579,6 +645,8 @@ template <int MODE, int NBP> __global__ __launch_bounds__(512, 1) void gemm_plan
 #undef PS_BAND
 #undef PS_TERM
 #undef PS_STEP
+#undef PS_ACC
+#undef PS_EPI_SWAP
 #undef PS_WAIT_VM
 #undef PS_WAIT_LDS
 #undef PS_BARRIER
