@@ -387,6 +387,53 @@ int umx_hip_separate_queue(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_d
 int umx_hip_queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_out, int *first_call_out, int *n_calls_out);
 /* calls of the segment loop (infer_batch) the context's last queue run made; < 0 when there was none */
 int umx_hip_debug_queue_calls(umx_hip_ctx *ctx);
+/* 16-bit PCM in and out of the whole-track drivers.  Almost all audio is 16-bit PCM: kept as int16 across PCIe it is 4 B
+ * per stereo frame up instead of 8 and 4 B per output buffer and frame down instead of 8, converted on the device.  The rules, to the bit:
+ *   decode   x = (float)q / 32767.0f, the correctly rounded fp32 quotient -- what umx_wav_load gives for a 16-bit file, so an int16
+ *            upload runs on the bits the float loader would have produced
+ *   encode   of output buffer m (its index in the call's `out` list, 0 .. 3), channel ch, frame k of the CALLER's track at the
+ *            caller's rate (k starts at 0; not a position in a region or in the padded signal):
+ *                v = x * 32767.0f                      one fp32 rounding, no fused multiply-add
+ *                if dither: v = v + d(seed, m, ch, k)  one fp32 rounding
+ *                r = rintf(v)                          nearest, ties to even
+ *                q = r is NaN ? 0 : (int16) min(max(r, -32768.f), 32767.f)
+ *   dither   TPDF, deterministic and counter based, so that regions, lanes and a rerun after a timeout give the same bits: with
+ *            h(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 in uint32,
+ *                a = h(seed + 0x9e3779b9 * (2 m + ch + 1)),  w = h(a ^ (uint32) k),
+ *                d = (((float)(w & 0xffff) + (float)(w >> 16)) - 65535.0f) * (1.0f / 65536.0f), in (-1, 1), every step exact.
+ * encode(decode(q)) == q for every code without dither, within 1 LSB with it.
+ * The _io forms below are the calls they are named after with the formats of the host buffers chosen per call; io == NULL, or
+ * UMX_SAMPLE_F32 both ways, IS that call: the same launches, nothing allocated.  UMX_SAMPLE_S16 in: audio[i] points at length[i]
+ * interleaved int16 stereo frames; out: every output buffer receives exactly length[i] such frames.  On the device a format costs 4 B
+ * per frame of the track for the input and 4 B per frame and output buffer, only while it is used.  UMX_ERR_ARG, naming the reason
+ * and leaving the context usable, for a format that is neither of the two, for dither != 0 with an fp32 output and for a NULL buffer.
+ * Reset mode, other sample rates (the dither is indexed at the caller's rate), the mix matrix (gains == NULL: the four stems, n_out
+ * ignored) and every per-call flag work as in the fp32 calls.  The shift ensemble, the multi-GPU driver (umx_mgpu.h) and the
+ * per-segment infer calls do not offer the formats. */
+#define UMX_SAMPLE_F32 0
+#define UMX_SAMPLE_S16 1
+typedef struct umx_sample_io
+{
+    int in_format, out_format; /* UMX_SAMPLE_* of the audio and of the output buffers */
+    int dither;                /* != 0: TPDF dither before the rounding (UMX_SAMPLE_S16 outputs only) */
+    unsigned dither_seed;
+} umx_sample_io;
+/* umx_hip_separate_tracks_mix (rate == NULL: 44100 for all; gains == NULL: umx_hip_separate_tracks_rate) with the formats */
+int umx_hip_separate_tracks_io(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                               const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                               const umx_sample_io *io, void (*progress)(float, void *), void *progress_user);
+/* umx_hip_separate_queue with the formats: a job's audio and out[] are read as io says (the caller casts its int16 pointers) */
+int umx_hip_separate_queue_io(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_done_fn done, void *user, int n_out, const float *gains,
+                              unsigned flags, const umx_sample_io *io);
+/* the two kernels on the caller's device buffers, queued on hip_stream: n int16 stereo frames (4-byte aligned) <-> (2,n) interleaved
+ * fp32 (8-byte aligned); exactly n frames of every output are written.  Encode: 1 .. 4 buffers in one launch, buffer b is output b
+ * of the rule above, its frame i frame first_frame + i; of io only dither and dither_seed are read (NULL: no dither). */
+int umx_hip_pcm16_decode_device(umx_hip_ctx *ctx, const int16_t *in_dev, int n, float *out_dev, void *hip_stream);
+int umx_hip_pcm16_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
+                                const umx_sample_io *io, int16_t *const *out_dev, void *hip_stream);
+/* the same rules on the host (no GPU, no context): n_values samples; n_frames stereo frames of output buffer `buffer` */
+int umx_hip_pcm16_decode_host(const int16_t *q, long long n_values, float *x);
+int umx_hip_pcm16_encode_host(const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, int16_t *q);
 /* testing, host only: the fp32 tap table of a rate pair (taps[phase * K + d + D]; cap floats at most), its phase count L, taps
  * per phase K and first offset -D.  UMX_ERR_ARG for a bad rate or a too small cap (the sizes are still reported). */
 int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase,

@@ -54,6 +54,15 @@ int umx_wav_write_f32(const char *path, const float *audio, int n_frames, char *
 int umx_wav_load_rate(const char *path, float **audio_out, int *n_frames_out, int *channels_in_file, int *rate_out, char *err);
 /* stereo 32-bit IEEE float WAV at `rate` Hz */
 int umx_wav_write_f32_rate(const char *path, const float *audio, int n_frames, int rate, char *err);
+/* 16-bit PCM as it is, for the int16 form of the whole-track calls (include/umx_hip.h: umx_sample_io).  load: a malloc'ed
+ * buffer of n interleaved int16 stereo frames, mono duplicated, from a 16-bit PCM file only -- every other encoding is
+ * UMX_HOST_ERR_AUDIO, and the caller takes the float loader; rate_out == NULL: 44100 Hz only, else any rate of 8000 .. 192000 Hz,
+ * reported; audio_out == NULL: only the file's head is read -- the same status, channels and rate, and the frames a load would return
+ * (what the head declares, bounded by the file's size).
+ * write: stereo, format tag 1, 16 bits, block align 4, at `rate` Hz. */
+int umx_wav_load_pcm16(const char *path, int16_t **audio_out, int *n_frames_out, int *channels_in_file, int *rate_out, char *err);
+void umx_wav_free_pcm16(int16_t *audio);
+int umx_wav_write_pcm16_rate(const char *path, const int16_t *audio, int n_frames, int rate, char *err);
 
 /* ---- segmented apply: replaces split_inference / shift_inference (umx.cpp:99-295).
  * The backend is the per-segment call (umx_inference, umx.cpp:226-227): audio (2,n) -> out[4] (2,n);

@@ -21,6 +21,7 @@ NB, CROP, KX, NOUT, NFFT, HOP = 2049, 1487, 2976, 4098, 4096, 1024
 SEGMENT_SAMPLES = 60 * 44100  # inference.hpp:13 x dsp.hpp:16
 
 UMX_OK, ERR_ARG, ERR_HIP, ERR_MODEL, ERR_TIMEOUT, ERR_NODEVICE = 0, 1, 2, 3, 4, 5
+HOST_ERR_AUDIO = 12  # include/umx_host.h: unsupported sample rate / channel count / encoding
 DTYPE_F32, DTYPE_U8, DTYPE_U16 = 0, 1, 2
 FLAG_NO_WIENER = 0x1
 FLAG_SOFTMASK = 0x2  # first estimates X g_j / (eps + sum g), g = mask |X| (Open-Unmix's softmask=True)
@@ -84,6 +85,14 @@ class QueueJob(C.Structure):
     """include/umx_hip.h: umx_queue_job"""
     _fields_ = [("audio", _fp), ("length", C.c_int), ("shift_offset", C.c_int), ("out", _fp * 4), ("tag", C.c_void_p)]
 
+
+class SampleIO(C.Structure):
+    """include/umx_hip.h: umx_sample_io"""
+    _fields_ = [("in_format", C.c_int), ("out_format", C.c_int), ("dither", C.c_int), ("dither_seed", C.c_uint)]
+
+
+SAMPLE_F32, SAMPLE_S16 = 0, 1  # UMX_SAMPLE_*: the formats of the host buffers of the whole-track calls (DESIGN 19)
+_i16p = C.POINTER(C.c_int16)
 
 QUEUE_NEXT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(QueueJob))
 QUEUE_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJob))
@@ -229,6 +238,15 @@ def hip_lib():
     lib.umx_hip_separate_queue.argtypes = [C.c_void_p, QUEUE_NEXT_FN, QUEUE_DONE_FN, C.c_void_p, C.c_int, _fp, C.c_uint]
     lib.umx_hip_queue_plan.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.umx_hip_debug_queue_calls.argtypes = [C.c_void_p]
+    lib.umx_hip_separate_tracks_io.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                               C.POINTER(C.c_int), C.c_int, _fp, C.POINTER(C.c_void_p), C.c_uint, C.POINTER(SampleIO),
+                                               C.c_void_p, C.c_void_p]
+    lib.umx_hip_separate_queue_io.argtypes = [C.c_void_p, QUEUE_NEXT_FN, QUEUE_DONE_FN, C.c_void_p, C.c_int, _fp, C.c_uint, C.POINTER(SampleIO)]
+    lib.umx_hip_pcm16_decode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.umx_hip_pcm16_encode_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.POINTER(SampleIO),
+                                                C.POINTER(C.c_void_p), C.c_void_p]
+    lib.umx_hip_pcm16_decode_host.argtypes = [_i16p, C.c_longlong, _fp]
+    lib.umx_hip_pcm16_encode_host.argtypes = [_fp, C.c_int, C.c_int, C.c_longlong, C.POINTER(SampleIO), _i16p]
     _hip = lib
     return lib
 
@@ -265,7 +283,37 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_debug_resample_taps", "umx_hip_residual_slot", "umx_hip_segment_residual_device",
                "umx_hip_ensemble_offsets", "umx_hip_shift_ensemble", "umx_hip_debug_shift_mean_ms",
                "umx_hip_mix_columns", "umx_hip_separate_tracks_mix", "umx_hip_shift_ensemble_mix", "umx_hip_mix_stems_device",
-               "umx_hip_separate_queue", "umx_hip_queue_plan", "umx_hip_debug_queue_calls"]
+               "umx_hip_separate_queue", "umx_hip_queue_plan", "umx_hip_debug_queue_calls",
+               "umx_hip_separate_tracks_io", "umx_hip_separate_queue_io", "umx_hip_pcm16_decode_device", "umx_hip_pcm16_encode_device",
+               "umx_hip_pcm16_decode_host", "umx_hip_pcm16_encode_host"]
+
+
+def sample_io(in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None):
+    """A umx_sample_io: dither_seed None = no dither, else TPDF dither with that seed."""
+    return SampleIO(int(in_format), int(out_format), 0 if dither_seed is None else 1, 0 if dither_seed is None else int(dither_seed) & 0xFFFFFFFF)
+
+
+def pcm16_decode_host(q):
+    """umx_hip_pcm16_decode_host: int16 array -> float32 array of the same shape, x = q / 32767 (no GPU)."""
+    q = np.ascontiguousarray(q, np.int16)
+    x = np.empty(q.shape, np.float32)
+    rc = hip_lib().umx_hip_pcm16_decode_host(q.ctypes.data_as(_i16p), q.size, x.ctypes.data_as(_fp))
+    if rc != UMX_OK:
+        raise UmxError(rc, "umx_hip_pcm16_decode_host")
+    return x
+
+
+def pcm16_encode_host(x, buffer=0, first_frame=0, dither_seed=None):
+    """umx_hip_pcm16_encode_host: (2,n) float32 -> (2,n) int16 as output buffer `buffer` of a call, frame 0 of x being frame
+    first_frame of the track (no GPU)."""
+    a = np.ascontiguousarray(np.asarray(x, np.float32).T)
+    q = np.empty(a.shape, np.int16)
+    io = sample_io(SAMPLE_F32, SAMPLE_S16, dither_seed)
+    rc = hip_lib().umx_hip_pcm16_encode_host(a.ctypes.data_as(_fp), a.shape[0], int(buffer), int(first_frame), C.byref(io),
+                                             q.ctypes.data_as(_i16p))
+    if rc != UMX_OK:
+        raise UmxError(rc, "umx_hip_pcm16_encode_host")
+    return np.ascontiguousarray(q.T)
 
 
 def resampled_length(n, rate_in, rate_out):
@@ -626,15 +674,52 @@ class Engine:
                                                          None, None))
         return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)]
 
+    # --- 16-bit PCM in and out: int16 frames across PCIe, converted on the device ---
+    def separate_many_io(self, waves, in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None, flags=0, shift_offsets=None,
+                         rates=None, gains=None, io=None):
+        """umx_hip_separate_tracks_io: separate_many() / separate_many_mix() (gains) with the formats of the host buffers chosen:
+        SAMPLE_S16 in takes (2,L_i) int16 arrays, SAMPLE_S16 out returns int16 arrays, dithered with dither_seed unless it is None.
+        io: a SampleIO passed as it is instead (tests of the refusals)."""
+        nt = len(waves)
+        io = sample_io(in_format, out_format, dither_seed) if io is None else io
+        n_out, g = (4, None) if gains is None else _mix_gains(gains)
+        tin = np.int16 if io.in_format == SAMPLE_S16 else np.float32
+        tout = np.int16 if io.out_format == SAMPLE_S16 else np.float32
+        ins = [np.ascontiguousarray(np.asarray(w, tin).T).ravel() for w in waves]
+        Ls = [np.asarray(w).shape[1] for w in waves]
+        outs = [[np.empty(2 * L, tout) for _ in range(min(max(n_out, 0), MAX_MIX_OUTPUTS))] for L in Ls]
+        a = (C.c_void_p * nt)(*[x.ctypes.data for x in ins])
+        o = (C.c_void_p * max(1, sum(len(t) for t in outs)))(*[x.ctypes.data for t in outs for x in t])
+        sh = (C.c_int * nt)(*[(-1 if s is None else s) for s in (shift_offsets or [None] * nt)])
+        rt = None if rates is None else (C.c_int * nt)(*[int(r) for r in rates])
+        self._check(self.lib.umx_hip_separate_tracks_io(self.h, nt, a, (C.c_int * nt)(*Ls), rt, sh, n_out,
+                                                        None if g is None else g.ctypes.data_as(_fp), o, flags, C.byref(io), None, None))
+        return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)]
+
+    def pcm16_decode_device(self, in_ptr, n, out_ptr, hip_stream=None):
+        """umx_hip_pcm16_decode_device: n int16 stereo frames at device address in_ptr -> (2,n) interleaved fp32 at out_ptr."""
+        self._check(self.lib.umx_hip_pcm16_decode_device(self.h, C.c_void_p(in_ptr), int(n), C.c_void_p(out_ptr), hip_stream))
+
+    def pcm16_encode_device(self, in_ptrs, n, out_ptrs, first_frame=0, dither_seed=None, hip_stream=None):
+        """umx_hip_pcm16_encode_device: 1 .. 4 device buffers (2,n) interleaved fp32 -> n int16 stereo frames each, buffer b as output b."""
+        nb = len(in_ptrs)
+        assert len(out_ptrs) == nb
+        io = sample_io(SAMPLE_F32, SAMPLE_S16, dither_seed)
+        self._check(self.lib.umx_hip_pcm16_encode_device(self.h, nb, (C.c_void_p * nb)(*in_ptrs), int(n), int(first_frame), C.byref(io),
+                                                         (C.c_void_p * nb)(*out_ptrs), hip_stream))
+
     # --- the track queue (DESIGN 18): more tracks than lanes, a lane refilled with the next track the moment one ends ---
-    def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None):
+    def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None, io=None):
         """umx_hip_separate_queue: list of (2,L_i) -> list of [4 x (2,L_i)] (mix: an (n_out, 5) gain matrix -> n_out x (2,L_i)), every
-        job bit for bit what separate() / separate_mix() returns for it alone on this engine; the jobs are handed out in list order."""
+        job bit for bit what separate() / separate_mix() returns for it alone on this engine; the jobs are handed out in list order.
+        io: a SampleIO (sample_io()) -> umx_hip_separate_queue_io, int16 arrays in and / or out as it says."""
         nj = len(waves)
         n_out, g = (4, None) if mix is None else _mix_gains(mix)
-        ins = [np.ascontiguousarray(np.asarray(w, np.float32).T).ravel() for w in waves]
+        tin = np.int16 if io is not None and io.in_format == SAMPLE_S16 else np.float32
+        tout = np.int16 if io is not None and io.out_format == SAMPLE_S16 else np.float32
+        ins = [np.ascontiguousarray(np.asarray(w, tin).T).ravel() for w in waves]
         Ls = [np.asarray(w).shape[1] for w in waves]
-        outs = [[np.empty(2 * L, np.float32) for _ in range(min(max(n_out, 0), MAX_MIX_OUTPUTS))] for L in Ls]
+        outs = [[np.empty(2 * L, tout) for _ in range(min(max(n_out, 0), MAX_MIX_OUTPUTS))] for L in Ls]
         shifts = [(-1 if s is None else int(s)) for s in (shift_offsets or [None] * nj)]
         state = {"next": 0, "done": []}
 
@@ -643,18 +728,22 @@ class Engine:
             if j >= nj:
                 return 0
             state["next"] = j + 1
-            job[0].audio = ins[j].ctypes.data_as(_fp)
+            job[0].audio = C.cast(ins[j].ctypes.data, _fp)  # (read as io says: the caller casts)
             job[0].length, job[0].shift_offset = Ls[j], shifts[j]
             for m, o in enumerate(outs[j]):
-                job[0].out[m] = o.ctypes.data_as(_fp)
+                job[0].out[m] = C.cast(o.ctypes.data, _fp)
             job[0].tag = j + 1
             return 1
 
         def _done(_user, job):
             state["done"].append(int(job[0].tag) - 1)
 
-        self._check(self.lib.umx_hip_separate_queue(self.h, QUEUE_NEXT_FN(_next), QUEUE_DONE_FN(_done), None, n_out,
-                                                    None if g is None else g.ctypes.data_as(_fp), flags))
+        if io is None:
+            self._check(self.lib.umx_hip_separate_queue(self.h, QUEUE_NEXT_FN(_next), QUEUE_DONE_FN(_done), None, n_out,
+                                                        None if g is None else g.ctypes.data_as(_fp), flags))
+        else:
+            self._check(self.lib.umx_hip_separate_queue_io(self.h, QUEUE_NEXT_FN(_next), QUEUE_DONE_FN(_done), None, n_out,
+                                                           None if g is None else g.ctypes.data_as(_fp), flags, C.byref(io)))
         assert sorted(state["done"]) == list(range(nj)), state
         return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)]
 
@@ -830,7 +919,8 @@ class Engine:
 # ------------------------------------------------------------------ C++17 host library (umx_host.h)
 HOST_SYMBOLS = ["umx_model_load", "umx_model_free", "umx_model_hidden", "umx_model_n_tensors", "umx_model_views",
                 "umx_model_data_bytes", "umx_model_load_progress", "umx_model_dequantize", "umx_wav_load",
-                "umx_wav_free", "umx_wav_write_f32", "umx_wav_load_rate", "umx_wav_write_f32_rate", "umx_split_inference", "umx_shift_inference",
+                "umx_wav_free", "umx_wav_write_f32", "umx_wav_load_rate", "umx_wav_write_f32_rate",
+                "umx_wav_load_pcm16", "umx_wav_free_pcm16", "umx_wav_write_pcm16_rate", "umx_split_inference", "umx_shift_inference",
                 "umx_segment_plan", "umx_transition_weight", "umx_split_inference_carry", "umx_split_inference_targets", "umx_mix_parse"]
 
 SEGMENT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _fp, C.c_int, C.POINTER(_fp))
@@ -902,6 +992,9 @@ def host_lib():
     lib.umx_wav_write_f32.argtypes = [C.c_char_p, _fp, C.c_int, C.c_char_p]
     lib.umx_wav_load_rate.argtypes = [C.c_char_p, C.POINTER(_fp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p]
     lib.umx_wav_write_f32_rate.argtypes = [C.c_char_p, _fp, C.c_int, C.c_int, C.c_char_p]
+    lib.umx_wav_load_pcm16.argtypes = [C.c_char_p, C.POINTER(_i16p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p]
+    lib.umx_wav_free_pcm16.argtypes = [_i16p]
+    lib.umx_wav_write_pcm16_rate.argtypes = [C.c_char_p, _i16p, C.c_int, C.c_int, C.c_char_p]
     lib.umx_split_inference.argtypes = [C.POINTER(Backend), _fp, C.c_int, C.c_int, C.POINTER(_fp), PROGRESS_FN,
                                         C.c_void_p, C.c_char_p]
     lib.umx_shift_inference.argtypes = [C.POINTER(Backend), _fp, C.c_int, C.c_int, C.c_int, C.POINTER(_fp),
@@ -1012,6 +1105,28 @@ def wav_write(path, wave, rate=MODEL_RATE):
         rc = host_lib().umx_wav_write_f32(str(path).encode(), a.ctypes.data_as(_fp), a.shape[0], err)
     else:
         rc = host_lib().umx_wav_write_f32_rate(str(path).encode(), a.ctypes.data_as(_fp), a.shape[0], int(rate), err)
+    if rc:
+        raise HostError(rc, err.value.decode())
+
+
+def wav_load_pcm16(path):
+    """umx_wav_load_pcm16: a 16-bit PCM file as it is -> ((2,n) int16, channels in file, sample rate); HostError for any other encoding."""
+    lib = host_lib()
+    p, n, ch, rate = _i16p(), C.c_int(), C.c_int(), C.c_int()
+    err = C.create_string_buffer(256)
+    rc = lib.umx_wav_load_pcm16(str(path).encode(), C.byref(p), C.byref(n), C.byref(ch), C.byref(rate), err)
+    if rc:
+        raise HostError(rc, err.value.decode())
+    a = np.ctypeslib.as_array(p, shape=(max(n.value, 1), 2))[:n.value].copy()
+    lib.umx_wav_free_pcm16(p)
+    return np.ascontiguousarray(a.T), ch.value, rate.value
+
+
+def wav_write_pcm16(path, wave, rate=MODEL_RATE):
+    """umx_wav_write_pcm16_rate: (2,n) int16 -> stereo 16-bit PCM WAV at `rate` Hz."""
+    a = np.ascontiguousarray(np.asarray(wave, np.int16).T)
+    err = C.create_string_buffer(256)
+    rc = host_lib().umx_wav_write_pcm16_rate(str(path).encode(), a.ctypes.data_as(_i16p), a.shape[0], int(rate), err)
     if rc:
         raise HostError(rc, err.value.decode())
 

@@ -41,6 +41,7 @@
 #include "softmask.h"
 #include "shift_mean.h"
 #include "stem_mix.h"
+#include "pcm16.h"
 #include "gate_debug.h"
 
 using namespace umx;
@@ -574,6 +575,7 @@ struct umx_hip_ctx
         void *progress_user = nullptr;
         bool ensemble = false;       // the lanes are ONE track at n_tracks shift offsets, `out` the buffers of their mean
         const MixSpec *mix = nullptr; // stem_mix.h, DESIGN 17: weighted sums of a track's stems and its input instead of the stems
+        umx_sample_io io = {};        // pcm16.h, DESIGN 19: how `audio` and `out` are read (UMX_SAMPLE_S16: int16 frames behind the float pointers)
     };
     int tracks(const TrackRequest &rq);
     int tracks_once(const TrackRequest &rq);
@@ -590,13 +592,19 @@ struct umx_hip_ctx
     {
         float *in = nullptr, *out[4] = {}, *sumw = nullptr, *seg[kMaxSlots][4] = {};
         size_t cap = 0;
+        // DESIGN 19, only once a job asks for UMX_SAMPLE_S16: the track as uploaded and its outputs as they leave, one word per frame of
+        // the CALLER's track (no shift padding), each grow-only on its own
+        uint32_t *in16 = nullptr, *out16[4] = {};
+        size_t cap_in16 = 0, cap_out16[4] = {};
+        hipEvent_t in16_ev = nullptr; // behind the most recent decode out of in16 (track_upload_until): every call that reads `in` waits for it
     };
     std::vector<TrackBufs> trk;
     hipEvent_t trk_acc_ev[kMaxSlots] = {}; // per slot: behind the overlap-add of the last call that ran in it
     // ---- what tracks_once and the track queue share (engine_tracks.h)
     struct TrackJob // a track resident on the device
     {
-        const float *audio = nullptr; // on the host
+        const float *audio = nullptr; // on the host (io.in_format UMX_SAMPLE_S16: int16 frames)
+        umx_sample_io io = {};        // the formats of `audio` and of the host buffers its regions go to
         int length = 0;               // frames as the segments see them (the 44.1 kHz version's of a resampled track)
         int lead = 0, L2 = 0, segs = 0; // track_geometry: frames of silence before the track, padded frames, segments
         long long uploaded = 0;       // host frames already on the device
@@ -646,15 +654,19 @@ struct umx_hip_ctx
     static bool track_geometry(int length, int shift_offset, int stride, TrackJob &j);
     int grow_frames(std::initializer_list<std::pair<float **, int>> bufs, size_t &cap, size_t frames);
     int track_bufs_grow(TrackBufs &tb_, size_t frames);
-    hipError_t track_upload_until(TrackJob &j, long long padded_end);
+    int grow_words(uint32_t *&p, size_t &cap, size_t frames);
+    int track_pcm16_grow(TrackBufs &tb_, const umx_sample_io &io, size_t frames, int n_host);
+    void track_encode(const TrackBufs &tb_, const umx_sample_io &io, int n_host, float *const src[4], size_t src_start, int count,
+                      long long first_frame, hipStream_t st);
+    hipError_t track_upload_until(TrackJob &j, long long padded_end, hipStream_t st);
     void track_mix(const MixSpec &mix, float *const stems[4], size_t stem_start, const float *in, size_t in_start, int count, hipStream_t st);
     hipError_t track_region_download(const TrackRegion &r, int n_host, float *const *out_host);
     int track_call(const TrackLane *lanes, int nl, unsigned flags, const MixSpec *mix, int &last_slot, TrackRegions &regions);
     // track queue (engine_queue.h): B + 2 accumulator sets (in, out, sumw of TrackBufs; grow-only) lent to the jobs in flight
     std::vector<TrackBufs> qpool;
     int queue_calls = -1; // infer_batch calls of the last queue run
-    int queue(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags);
-    int queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags);
+    int queue(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io);
+    int queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io);
     int phase_begin(const float *audio_host, int n, unsigned flags);
     int phase_begin_device(const float *audio_dev, int n, unsigned flags);
     int phase_end_device(float *const out_dev_[4]);

@@ -94,6 +94,10 @@ void umx_hip_destroy(umx_hip_ctx *ctx)
     for (hipEvent_t e : ctx->ens_ev)
         if (e)
             (void)hipEventDestroy(e);
+    for (const std::vector<umx_hip_ctx::TrackBufs> *sets : {&ctx->trk, &ctx->qpool})
+        for (const umx_hip_ctx::TrackBufs &tb_ : *sets)
+            if (tb_.in16_ev)
+                (void)hipEventDestroy(tb_.in16_ev);
     if (ctx->order_ev)
         (void)hipEventDestroy(ctx->order_ev);
     if (ctx->copy_stream)
@@ -415,7 +419,115 @@ int umx_hip_separate_queue(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_d
     MixSpec spec;
     if (gains && !mix_checked(ctx, n_out, gains, spec))
         return UMX_ERR_ARG;
-    return ctx->queue(next, done, user, gains ? &spec : nullptr, flags);
+    return ctx->queue(next, done, user, gains ? &spec : nullptr, flags, umx_sample_io{});
+}
+
+// ---------------------------------------------------------------- 16-bit PCM in and out (pcm16.h)
+// io == NULL or fp32 both ways: the fp32 call itself
+static bool sample_io_checked(umx_hip_ctx *ctx, const umx_sample_io *io)
+{
+    const char *why = sample_io_refusal(io);
+    if (why)
+        ctx->set_error(why);
+    return !why;
+}
+
+int umx_hip_separate_tracks_io(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                               const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                               const umx_sample_io *io, void (*progress)(float, void *), void *progress_user)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!sample_io_checked(ctx, io))
+        return UMX_ERR_ARG;
+    MixSpec spec;
+    if (gains && !mix_checked(ctx, n_out, gains, spec))
+        return UMX_ERR_ARG;
+    // (the request keeps its float pointers: the formats say how the driver reads them)
+    umx_hip_ctx::TrackRequest rq = {n_tracks, reinterpret_cast<const float *const *>(audio_host), length, rate, shift_offset,
+                                    reinterpret_cast<float *const *>(out_host), flags, progress, progress_user};
+    rq.mix = gains ? &spec : nullptr;
+    if (io)
+        rq.io = *io;
+    return ctx->tracks(rq);
+}
+
+int umx_hip_separate_queue_io(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_done_fn done, void *user, int n_out, const float *gains,
+                              unsigned flags, const umx_sample_io *io)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!sample_io_checked(ctx, io))
+        return UMX_ERR_ARG;
+    MixSpec spec;
+    if (gains && !mix_checked(ctx, n_out, gains, spec))
+        return UMX_ERR_ARG;
+    return ctx->queue(next, done, user, gains ? &spec : nullptr, flags, io ? *io : umx_sample_io{});
+}
+
+int umx_hip_pcm16_decode_device(umx_hip_ctx *ctx, const int16_t *in_dev, int n, float *out_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!in_dev || !out_dev || n < 1)
+    {
+        ctx->set_error("pcm16 decode: need both buffers and n >= 1");
+        return UMX_ERR_ARG;
+    }
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    launch_pcm16_decode(reinterpret_cast<const uint32_t *>(in_dev), reinterpret_cast<float2 *>(out_dev), n, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+
+int umx_hip_pcm16_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
+                                const umx_sample_io *io, int16_t *const *out_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (n_buffers < 1 || n_buffers > 4 || !in_dev || !out_dev || n < 1 || first_frame < 0)
+    {
+        ctx->set_error("pcm16 encode: need 1 .. 4 buffers, n >= 1 and first_frame >= 0");
+        return UMX_ERR_ARG;
+    }
+    const float2 *src[4] = {};
+    uint32_t *dst[4] = {};
+    for (int b = 0; b < n_buffers; ++b)
+    {
+        if (!in_dev[b] || !out_dev[b])
+        {
+            ctx->set_error("pcm16 encode: null buffer");
+            return UMX_ERR_ARG;
+        }
+        src[b] = reinterpret_cast<const float2 *>(in_dev[b]);
+        dst[b] = reinterpret_cast<uint32_t *>(out_dev[b]);
+    }
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    launch_pcm16_encode(n_buffers, src, dst, n, first_frame, io && io->dither, io ? io->dither_seed : 0u, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+
+int umx_hip_pcm16_decode_host(const int16_t *q, long long n_values, float *x)
+{
+    if (!q || !x || n_values < 0)
+        return UMX_ERR_ARG;
+    for (long long i = 0; i < n_values; ++i)
+        x[i] = pcm16_decode(q[i]);
+    return UMX_OK;
+}
+
+int umx_hip_pcm16_encode_host(const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, int16_t *q)
+{
+    if (!x || !q || n_frames < 0 || buffer < 0 || buffer >= UMX_MAX_MIX_OUTPUTS || first_frame < 0)
+        return UMX_ERR_ARG;
+    const bool dither = io && io->dither;
+    const uint32_t seed = io ? io->dither_seed : 0u;
+    const uint32_t key[2] = {pcm16_dither_key(seed, buffer, 0), pcm16_dither_key(seed, buffer, 1)};
+    for (int i = 0; i < n_frames; ++i)
+        for (int ch = 0; ch < 2; ++ch)
+            q[2 * (size_t)i + ch] = pcm16_encode(x[2 * (size_t)i + ch], dither, key[ch], first_frame + i);
+    return UMX_OK;
 }
 int umx_hip_queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_out, int *first_call_out, int *n_calls_out)
 {

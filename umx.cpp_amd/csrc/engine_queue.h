@@ -67,7 +67,7 @@ int queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_out, int
 }
 } // namespace
 
-int umx_hip_ctx::queue(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags)
+int umx_hip_ctx::queue(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io)
 {
     if (!next || !done)
     {
@@ -100,10 +100,10 @@ int umx_hip_ctx::queue(umx_queue_next_fn next, umx_queue_done_fn done, void *use
     TrackRun run(*this);
     pending.clear();
     pending_lost = true;
-    return queue_run(next, done, user, mix, flags);
+    return queue_run(next, done, user, mix, flags, io);
 }
 
-int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags)
+int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io)
 {
     const int n_host = mix ? mix->n_out : 4;
     const int stride = track_stride();
@@ -281,7 +281,10 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void 
                 const int set = free_set((size_t)tj.L2);
                 if (int rc = track_bufs_grow(qpool[set], (size_t)tj.L2))
                     return fail(rc);
+                if (int rc = track_pcm16_grow(qpool[set], io, (size_t)tj.length, n_host)) // (nothing for an fp32 run)
+                    return fail(rc);
                 tj.audio = j.audio;
+                tj.io = io;
                 tj.acc = &qpool[set];
                 jb = &jobs[set];
                 static_cast<TrackJob &>(*jb) = tj;

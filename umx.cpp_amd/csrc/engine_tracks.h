@@ -79,17 +79,86 @@ int umx_hip_ctx::track_bufs_grow(TrackBufs &tb_, size_t frames)
     return grow_frames({{&tb_.in, 2}, {&tb_.out[0], 2}, {&tb_.out[1], 2}, {&tb_.out[2], 2}, {&tb_.out[3], 2}, {&tb_.sumw, 1}}, tb_.cap, frames);
 }
 
+// one grow-only buffer of `frames` int16 frames (a word each); too small: freed and allocated again with an eighth to spare
+int umx_hip_ctx::grow_words(uint32_t *&p, size_t &cap, size_t frames)
+{
+    if (frames <= cap)
+        return UMX_OK;
+    if (p)
+    {
+        allocs.erase(std::find(allocs.begin(), allocs.end(), (void *)p));
+        (void)hipFree(p);
+        p = nullptr;
+    }
+    cap = 0;
+    const size_t want = frames + frames / 8;
+    if (int rc = dalloc(&p, want, false))
+        return rc;
+    cap = want;
+    return UMX_OK;
+}
+
+// the int16 side of an accumulator set for a job of `frames` frames at the caller's rate: the staging of its upload, n_host outputs
+int umx_hip_ctx::track_pcm16_grow(TrackBufs &tb_, const umx_sample_io &io, size_t frames, int n_host)
+{
+    if (io.in_format == UMX_SAMPLE_S16)
+        if (int rc = grow_words(tb_.in16, tb_.cap_in16, frames))
+            return rc;
+    for (int t = 0; t < n_host && io.out_format == UMX_SAMPLE_S16; ++t)
+        if (int rc = grow_words(tb_.out16[t], tb_.cap_out16[t], frames))
+            return rc;
+    return UMX_OK;
+}
+
+// `count` frames of the first n_host of `src` from frame src_start on -> the set's int16 outputs from frame first_frame on, which is
+// their frame number in the caller's track (the k of the dither)
+void umx_hip_ctx::track_encode(const TrackBufs &tb_, const umx_sample_io &io, int n_host, float *const src[4], size_t src_start, int count,
+                               long long first_frame, hipStream_t st)
+{
+    const float2 *s[4] = {};
+    uint32_t *d[4] = {};
+    for (int t = 0; t < n_host; ++t)
+    {
+        s[t] = reinterpret_cast<const float2 *>(src[t]) + src_start;
+        d[t] = tb_.out16[t] + first_frame;
+    }
+    launch_pcm16_encode(n_host, s, d, count, first_frame, io.dither != 0, io.dither_seed, st);
+}
+
 // The track goes up segment by segment (round 6): a call needs the samples up to the end of its last segment, and the rest of a
 // pageable upload (14 GB/s: 15 ms for ten minutes of stereo) runs while the device is busy with the segments before it -- the
 // slots' streams do not wait for the null stream, and launches are queued ahead of the copy.
 // Samples of the job's padded signal (the track behind `lead` frames of silence) below `padded_end` must be there.
-hipError_t umx_hip_ctx::track_upload_until(TrackJob &j, long long padded_end)
+// An int16 track goes into the set's staging buffer, at its frame number, and is decoded from there into the padded signal
+// on `st`, the stream of the call that needs these frames.  Unlike the fp32 copy the decode is not finished when this returns, and a
+// LATER call reads the last quarter of these frames too (segments overlap) -- on another slot stream, which on a one-track context is
+// not ordered behind this one before its STFT.  So every call's stream first waits for the set's `in16_ev`, recorded behind the most
+// recent decode of the set: each decode is then behind all earlier ones, and every reader behind every decode queued before it.  (A
+// set's event may stem from its previous job: that work has long finished.)
+hipError_t umx_hip_ctx::track_upload_until(TrackJob &j, long long padded_end, hipStream_t st)
 {
+    const bool s16 = j.io.in_format == UMX_SAMPLE_S16;
+    if (s16 && j.acc->in16_ev)
+        if (hipError_t e = hipStreamWaitEvent(st, j.acc->in16_ev, 0))
+            return e;
     const long long want = std::min<long long>(j.length, padded_end - j.lead);
     if (want <= j.uploaded)
         return hipSuccess;
-    const hipError_t e = hipMemcpy(j.acc->in + 2 * ((size_t)j.lead + (size_t)j.uploaded), j.audio + 2 * (size_t)j.uploaded,
-                                   sizeof(float) * 2 * (size_t)(want - j.uploaded), hipMemcpyHostToDevice);
+    const size_t from = (size_t)j.uploaded, count = (size_t)(want - j.uploaded);
+    hipError_t e;
+    if (s16)
+    {
+        e = hipMemcpy(j.acc->in16 + from, reinterpret_cast<const uint32_t *>(j.audio) + from, sizeof(uint32_t) * count, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !j.acc->in16_ev)
+            e = hipEventCreateWithFlags(&j.acc->in16_ev, hipEventDisableTiming);
+        if (e == hipSuccess)
+        {
+            launch_pcm16_decode(j.acc->in16 + from, reinterpret_cast<float2 *>(j.acc->in) + (size_t)j.lead + from, (int)count, st);
+            e = hipEventRecord(j.acc->in16_ev, st);
+        }
+    }
+    else
+        e = hipMemcpy(j.acc->in + 2 * ((size_t)j.lead + from), j.audio + 2 * from, sizeof(float) * 2 * count, hipMemcpyHostToDevice);
     j.uploaded = want;
     return e;
 }
@@ -117,8 +186,12 @@ hipError_t umx_hip_ctx::track_region_download(const TrackRegion &r, int n_host, 
     if (hi <= lo)
         return hipSuccess;
     hipError_t cerr = hipEventSynchronize(r.ready);
+    const size_t first = (size_t)(lo - j.lead), count = (size_t)(hi - lo);
     for (int t = 0; t < n_host && cerr == hipSuccess; ++t)
-        cerr = hipMemcpy(out_host[t] + 2 * (size_t)(lo - j.lead), j.acc->out[t] + 2 * (size_t)lo, sizeof(float) * 2 * (size_t)(hi - lo), hipMemcpyDeviceToHost);
+        if (j.io.out_format == UMX_SAMPLE_S16) // (encoded behind the region's normalisation and mix, at its frame number: track_call)
+            cerr = hipMemcpy(reinterpret_cast<uint32_t *>(out_host[t]) + first, j.acc->out16[t] + first, sizeof(uint32_t) * count, hipMemcpyDeviceToHost);
+        else
+            cerr = hipMemcpy(out_host[t] + 2 * first, j.acc->out[t] + 2 * (size_t)lo, sizeof(float) * 2 * count, hipMemcpyDeviceToHost);
     return cerr;
 }
 
@@ -147,7 +220,7 @@ int umx_hip_ctx::track_call(const TrackLane *lanes, int nl, unsigned flags, cons
                 for (int t = 0; t < 4; ++t)
                     if (int rc = dalloc(&trk[ln].seg[s][t], (size_t)2 * N, false))
                         return rc;
-        if (track_upload_until(*j, lanes[ln].start + N) != hipSuccess)
+        if (track_upload_until(*j, lanes[ln].start + N, st) != hipSuccess)
         {
             set_error("track: upload failed");
             return UMX_ERR_HIP;
@@ -185,6 +258,12 @@ int umx_hip_ctx::track_call(const TrackLane *lanes, int nl, unsigned flags, cons
             continue;
         if (mix)
             track_mix(*mix, tb_.out, (size_t)rg.start, tb_.in, (size_t)rg.start, rg.count, st);
+        if (j->io.out_format == UMX_SAMPLE_S16) // the region's frames of the caller's track, as they will leave (not over the
+        {                                       // accumulators: the next segment's overlap-add still reads its neighbours)
+            const long long lo = std::max<long long>(rg.start, j->lead), hi = std::min<long long>((long long)rg.start + rg.count, (long long)j->lead + j->length);
+            if (hi > lo)
+                track_encode(tb_, j->io, mix ? mix->n_out : 4, tb_.out, (size_t)lo, (int)(hi - lo), lo - j->lead, st);
+        }
         if (hipEventCreateWithFlags(&rg.ready, hipEventDisableTiming) != hipSuccess)
         {
             set_error("track: event creation failed");
@@ -278,6 +357,7 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
             return UMX_ERR_ARG;
         }
         j.audio = rq.audio[ln];
+        j.io = rq.io;
         j.by_region = !ensemble && !resampled[ln];
         L2max = std::max(L2max, j.L2);
         max_segs = std::max(max_segs, j.segs);
@@ -290,6 +370,8 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     {
         job[ln].acc = &trk[ln];
         if (int rc = track_bufs_grow(trk[ln], (size_t)job[ln].L2))
+            return rc;
+        if (int rc = track_pcm16_grow(trk[ln], rq.io, (size_t)length_in[ln], n_host)) // (nothing for an fp32 call)
             return rc;
     }
     if (ensemble) // the mean of the lanes' stems: n44 frames
@@ -318,7 +400,13 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         RsStage &rs = rs_stage[ln];
         if (int rc = grow_frames({{&rs.in, 2}, {&rs.out[0], 2}, {&rs.out[1], 2}, {&rs.out[2], 2}, {&rs.out[3], 2}}, rs.cap, (size_t)length_in[ln]))
             return rc;
-        UMX_HIP_CHECK(hipMemcpy(rs.in, rq.audio[ln], sizeof(float) * 2 * (size_t)length_in[ln], hipMemcpyHostToDevice));
+        if (rq.io.in_format == UMX_SAMPLE_S16) // (decoded on the null stream, as the resampler below is launched)
+        {
+            UMX_HIP_CHECK(hipMemcpy(trk[ln].in16, rq.audio[ln], sizeof(uint32_t) * (size_t)length_in[ln], hipMemcpyHostToDevice));
+            launch_pcm16_decode(trk[ln].in16, reinterpret_cast<float2 *>(rs.in), length_in[ln], nullptr);
+        }
+        else
+            UMX_HIP_CHECK(hipMemcpy(rs.in, rq.audio[ln], sizeof(float) * 2 * (size_t)length_in[ln], hipMemcpyHostToDevice));
         const float *src = rs.in;
         float *dst = trk[ln].in + 2 * (size_t)job[ln].lead;
         UMX_HIP_CHECK(launch_resample(rs_fwd[ln], rs_fwd_taps[ln], 1, &src, length_in[ln], &dst, length[ln], nullptr));
@@ -362,7 +450,7 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         if (reset_lanes && off > 0) // every segment from a zero state: the previous call has left its own behind
         {
             // (the samples of this call go up first, while the device is still busy with the previous one)
-            if (track_upload_until(job[0], off + (long long)stride * (per_call - 1) + N) != hipSuccess)
+            if (track_upload_until(job[0], off + (long long)stride * (per_call - 1) + N, slot[next_slot()].stream) != hipSuccess)
             {
                 set_error("track: upload failed");
                 return UMX_ERR_HIP;
@@ -402,6 +490,12 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
             cerr = launch_resample(rs_back[ln], rs_back_taps[ln], n_host, src, j.length, rs_stage[ln].out, length_in[ln], last_st);
             std::copy(rs_stage[ln].out, rs_stage[ln].out + 4, whole[ln]);
         }
+        if (rq.io.out_format == UMX_SAMPLE_S16 && cerr == hipSuccess) // at the caller's rate and length, frame 0 first
+        {
+            track_encode(*j.acc, rq.io, n_host, whole[ln], 0, length_in[ln], 0, last_st);
+            for (int t = 0; t < n_host; ++t)
+                whole[ln][t] = reinterpret_cast<float *>(j.acc->out16[t]);
+        }
         any_whole = true;
     };
     if (ensemble)
@@ -436,7 +530,8 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         cerr = hipStreamSynchronize(last_st);
     for (int ln = 0; ln < nt; ++ln)
         for (int t = 0; t < n_host && whole[ln][0] && cerr == hipSuccess; ++t) // (an ensemble's one result: lane 0)
-            cerr = hipMemcpy(rq.out[n_host * ln + t], whole[ln][t], sizeof(float) * 2 * (size_t)length_in[ln], hipMemcpyDeviceToHost);
+            cerr = hipMemcpy(rq.out[n_host * ln + t], whole[ln][t], (rq.io.out_format == UMX_SAMPLE_S16 ? sizeof(uint32_t) : sizeof(float) * 2) * (size_t)length_in[ln],
+                             hipMemcpyDeviceToHost);
     if (cerr != hipSuccess)
     {
         set_error(hipGetErrorString(cerr));

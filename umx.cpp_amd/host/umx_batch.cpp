@@ -10,7 +10,9 @@
 // Environment: UMX_DEVICE, UMX_NO_WIENER, UMX_WIENER_ITERS, UMX_SHIFT_OFFSET, UMX_RESAMPLE (as umx-cli: files of any rate of
 // 8 .. 192 kHz, mixed rates in one pass through umx_hip_separate_tracks_rate, stems written at each file's rate), UMX_TARGETS and
 // UMX_RESIDUAL (as umx-cli: target_<t>.wav of the chosen targets and residual.wav per file; host/targets_env.h), UMX_SOFTMASK (as umx-cli),
-// UMX_MIX (as umx-cli, host/mix_env.h: the same matrix for every file, <out dir>/<wav stem>/<name>.wav and no target_*.wav).
+// UMX_MIX (as umx-cli, host/mix_env.h: the same matrix for every file, <out dir>/<wav stem>/<name>.wav and no target_*.wav),
+// UMX_PCM16 and UMX_PCM16_DITHER (as umx-cli, DESIGN 19: every output a 16-bit PCM WAV quantised on the device, through the queue and
+// the pass-by-pass loop alike; the files go up as int16 when ALL of them are 16-bit PCM -- a run has one input format -- else as fp32).
 #include "../../include/umx_host.h"
 #include "mix_env.h"
 #include "shifts_env.h"
@@ -42,7 +44,9 @@ struct FileJob
 {
     int index = 0, n = 0;
     float *audio = nullptr;
+    int16_t *audio16 = nullptr; // UMX_PCM16 with 16-bit PCM files: the file's samples as they are
     std::vector<std::vector<float>> stems;
+    std::vector<std::vector<int16_t>> stems16; // UMX_PCM16: the outputs as they are written
 };
 struct BatchQueue
 {
@@ -50,6 +54,7 @@ struct BatchQueue
     std::condition_variable cv;
     std::deque<FileJob *> decoded, unwritten;
     int permits = 0, per_file = 4, shift_offset = 0;
+    umx_sample_io io = {UMX_SAMPLE_F32, UMX_SAMPLE_F32, 0, 0};
     size_t max_unwritten = 0;
     bool reader_done = false, no_more_stems = false;
     double audio_secs = 0;
@@ -70,12 +75,19 @@ struct BatchQueue
             q.decoded.pop_front();
         }
         fj->stems.resize(q.per_file);
+        fj->stems16.resize(q.per_file);
         for (int t = 0; t < q.per_file; ++t)
-        {
-            fj->stems[t].resize((size_t)2 * fj->n);
-            job->out[t] = fj->stems[t].data();
-        }
-        job->audio = fj->audio;
+            if (q.io.out_format == UMX_SAMPLE_S16) // (read as the formats say: the caller casts)
+            {
+                fj->stems16[t].resize((size_t)2 * fj->n);
+                job->out[t] = reinterpret_cast<float *>(fj->stems16[t].data());
+            }
+            else
+            {
+                fj->stems[t].resize((size_t)2 * fj->n);
+                job->out[t] = fj->stems[t].data();
+            }
+        job->audio = fj->audio16 ? reinterpret_cast<const float *>(fj->audio16) : fj->audio;
         job->length = fj->n;
         job->shift_offset = q.shift_offset;
         job->tag = fj;
@@ -86,7 +98,9 @@ struct BatchQueue
         BatchQueue &q = *static_cast<BatchQueue *>(user);
         FileJob *fj = static_cast<FileJob *>(job->tag);
         umx_wav_free(fj->audio);
+        umx_wav_free_pcm16(fj->audio16);
         fj->audio = nullptr;
+        fj->audio16 = nullptr;
         std::unique_lock<std::mutex> lock(q.m);
         ++q.permits;
         q.cv.notify_all();
@@ -134,6 +148,30 @@ int main(int argc, const char **argv)
         return 1;
     }
     const int per_file = mixed ? mixc.n_out : 4; // buffers of a file
+    const bool pcm16 = env_int("UMX_PCM16", 0) != 0;
+    if (!pcm16 && getenv("UMX_PCM16_DITHER"))
+    {
+        fprintf(stderr, "UMX_PCM16_DITHER: needs UMX_PCM16=1\n");
+        return 1;
+    }
+    const bool resample = env_int("UMX_RESAMPLE", 0) != 0;
+    umx_sample_io io = {UMX_SAMPLE_F32, pcm16 ? UMX_SAMPLE_S16 : UMX_SAMPLE_F32, 0, 0};
+    if (const char *seed = getenv("UMX_PCM16_DITHER"))
+    {
+        io.dither = 1;
+        io.dither_seed = (unsigned)strtoul(seed, nullptr, 0);
+    }
+    if (pcm16) // one input format per run: int16 when every file's head says 16-bit PCM
+    {
+        io.in_format = UMX_SAMPLE_S16;
+        for (int f = 0; f < nfiles && io.in_format == UMX_SAMPLE_S16; ++f)
+        {
+            int n = 0, ch = 0, rate = 0;
+            if (umx_wav_load_pcm16(argv[3 + f], nullptr, &n, &ch, resample ? &rate : nullptr, err))
+                io.in_format = UMX_SAMPLE_F32; // (whatever is wrong with the file, the float loader reports it)
+        }
+    }
+    const bool in16 = io.in_format == UMX_SAMPLE_S16;
     umx_model *model = nullptr;
     if (umx_model_load(model_file.c_str(), &model, err)) // umx.cpp:63-70
     {
@@ -164,7 +202,6 @@ int main(int argc, const char **argv)
     const unsigned flags = choice.flags | (env_int("UMX_NO_WIENER", 0) ? UMX_FLAG_NO_WIENER : 0) | (wiener_iters > 1 ? UMX_FLAG_WIENER_ITERS(wiener_iters) : 0u);
     double audio_secs = 0, wall = 0;
     const int first_rand_shift = UMX_REFERENCE_SHIFT; // glibc's first unseeded rand() % 22050 (not rand() here: umx_hip.h)
-    const bool resample = env_int("UMX_RESAMPLE", 0) != 0;
     // output directories are named after the file's stem, in argument order: a/x.wav and b/x.wav must not collide (the second is x_2)
     std::set<std::string> used_names;
     std::vector<std::string> names(nfiles);
@@ -175,7 +212,7 @@ int main(int argc, const char **argv)
             names[f] = std::filesystem::path(argv[3 + f]).stem().string() + "_" + std::to_string(k);
     }
     // umx.cpp:75-96: the buffers of file f to its directory
-    auto write_file = [&](int f, float *const *bufs, int n, int rate_, char *err_) -> bool {
+    auto write_file = [&](int f, float *const *bufs, int16_t *const *bufs16, int n, int rate_, char *err_) -> bool {
         const std::filesystem::path dir = std::filesystem::path(out_dir) / names[f];
         std::error_code ec;
         std::filesystem::create_directories(dir, ec);
@@ -184,7 +221,9 @@ int main(int argc, const char **argv)
             if (!mixed && !choice.write[t]) // a target that did not run (UMX_TARGETS): a silent slot
                 continue;
             const std::string p = (dir / (mixed ? mixc.name[t] + ".wav" : choice.file[t])).string();
-            if (resample ? umx_wav_write_f32_rate(p.c_str(), bufs[t], n, rate_, err_) : umx_wav_write_f32(p.c_str(), bufs[t], n, err_))
+            if (pcm16 ? umx_wav_write_pcm16_rate(p.c_str(), bufs16[t], n, rate_, err_)
+                : resample ? umx_wav_write_f32_rate(p.c_str(), bufs[t], n, rate_, err_)
+                           : umx_wav_write_f32(p.c_str(), bufs[t], n, err_))
                 return false;
         }
         return true;
@@ -199,6 +238,7 @@ int main(int argc, const char **argv)
         q.max_unwritten = (size_t)lanes + 2;
         q.per_file = per_file;
         q.shift_offset = shift_offset;
+        q.io = io;
         std::thread reader([&]() {
             for (int f = 0; f < nfiles; ++f)
             {
@@ -213,7 +253,8 @@ int main(int argc, const char **argv)
                 fj->index = f;
                 int ch = 0;
                 char rerr[UMX_ERRLEN] = "";
-                const bool bad = umx_wav_load(argv[3 + f], &fj->audio, &fj->n, &ch, rerr) != 0; // umx.cpp:56
+                const bool bad = (in16 ? umx_wav_load_pcm16(argv[3 + f], &fj->audio16, &fj->n, &ch, nullptr, rerr)
+                                       : umx_wav_load(argv[3 + f], &fj->audio, &fj->n, &ch, rerr)) != 0; // umx.cpp:56
                 std::lock_guard<std::mutex> lock(q.m);
                 if (bad)
                 {
@@ -242,9 +283,13 @@ int main(int argc, const char **argv)
                 }
                 char werr[UMX_ERRLEN] = "";
                 float *bufs[UMX_MAX_MIX_OUTPUTS];
+                int16_t *bufs16[UMX_MAX_MIX_OUTPUTS];
                 for (int t = 0; t < per_file; ++t)
+                {
                     bufs[t] = fj->stems[t].data();
-                const bool ok = write_file(fj->index, bufs, fj->n, UMX_SAMPLE_RATE, werr);
+                    bufs16[t] = fj->stems16[t].data();
+                }
+                const bool ok = write_file(fj->index, bufs, bufs16, fj->n, UMX_SAMPLE_RATE, werr);
                 std::lock_guard<std::mutex> lock(q.m);
                 q.unwritten.pop_front(); // (counted until it is written: the stems are in memory until then)
                 if (!ok && q.error.empty())
@@ -254,7 +299,8 @@ int main(int argc, const char **argv)
             }
         });
         const auto t0 = std::chrono::steady_clock::now();
-        const int qrc = umx_hip_separate_queue(ctx, BatchQueue::next, BatchQueue::done, &q, mixc.n_out, mixed ? mixc.gains : nullptr, flags);
+        const int qrc = pcm16 ? umx_hip_separate_queue_io(ctx, BatchQueue::next, BatchQueue::done, &q, mixc.n_out, mixed ? mixc.gains : nullptr, flags, &io)
+                              : umx_hip_separate_queue(ctx, BatchQueue::next, BatchQueue::done, &q, mixc.n_out, mixed ? mixc.gains : nullptr, flags);
         wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         {
             std::lock_guard<std::mutex> lock(q.m);
@@ -268,6 +314,7 @@ int main(int argc, const char **argv)
         for (FileJob *fj : q.decoded) // (decoded ahead of a run that stopped)
         {
             umx_wav_free(fj->audio);
+            umx_wav_free_pcm16(fj->audio16);
             delete fj;
         }
         if (!q.error.empty())
@@ -281,6 +328,10 @@ int main(int argc, const char **argv)
     {
         const int nb = std::min(lanes, nfiles - f0);
         std::vector<float *> audio(nb, nullptr);
+        std::vector<int16_t *> audio16(nb, nullptr);
+        std::vector<std::vector<int16_t>> stems16(per_file * nb);
+        std::vector<int16_t *> out16(per_file * nb);
+        std::vector<const void *> in_io(nb);
         // umx.cpp:115 draws rand() % 22050 once per PROCESS, and the reference never seeds rand(): every run of its CLI
         // shifts by the same 4033 samples.  Every file here gets that value too (not a fresh draw per batch of lanes),
         // so a file's stems do not depend on where in the argument list it stands; UMX_SHIFT_OFFSET overrides it.
@@ -292,22 +343,30 @@ int main(int argc, const char **argv)
         for (int i = 0; i < nb; ++i)
         {
             int ch = 0;
-            if (resample ? umx_wav_load_rate(argv[3 + f0 + i], &audio[i], &n[i], &ch, &rate[i], err)
-                         : umx_wav_load(argv[3 + f0 + i], &audio[i], &n[i], &ch, err)) // umx.cpp:56
+            if (in16       ? umx_wav_load_pcm16(argv[3 + f0 + i], &audio16[i], &n[i], &ch, resample ? &rate[i] : nullptr, err)
+                : resample ? umx_wav_load_rate(argv[3 + f0 + i], &audio[i], &n[i], &ch, &rate[i], err)
+                           : umx_wav_load(argv[3 + f0 + i], &audio[i], &n[i], &ch, err)) // umx.cpp:56
             {
                 fprintf(stderr, "%s: %s\n", argv[3 + f0 + i], err);
                 return 1;
             }
             in[i] = audio[i];
+            in_io[i] = in16 ? (const void *)audio16[i] : (const void *)audio[i];
             audio_secs += n[i] / (double)rate[i];
             for (int t = 0; t < per_file; ++t)
             {
-                stems[per_file * i + t].resize((size_t)2 * n[i]);
+                if (pcm16)
+                    stems16[per_file * i + t].resize((size_t)2 * n[i]);
+                else
+                    stems[per_file * i + t].resize((size_t)2 * n[i]);
                 out[per_file * i + t] = stems[per_file * i + t].data();
+                out16[per_file * i + t] = stems16[per_file * i + t].data();
             }
         }
         const auto t0 = std::chrono::steady_clock::now();
-        if (mixed ? umx_hip_separate_tracks_mix(ctx, nb, in.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out, mixc.gains,
+        if (pcm16 ? umx_hip_separate_tracks_io(ctx, nb, in_io.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out,
+                                               mixed ? mixc.gains : nullptr, reinterpret_cast<void *const *>(out16.data()), flags, &io, nullptr, nullptr)
+            : mixed ? umx_hip_separate_tracks_mix(ctx, nb, in.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out, mixc.gains,
                                                 out.data(), flags, nullptr, nullptr)
             : resample ? umx_hip_separate_tracks_rate(ctx, nb, in.data(), n.data(), rate.data(), shift.data(), out.data(), flags, nullptr, nullptr)
                      : umx_hip_separate_tracks(ctx, nb, in.data(), n.data(), shift.data(), out.data(), flags, nullptr, nullptr))
@@ -318,12 +377,13 @@ int main(int argc, const char **argv)
         wall += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         for (int i = 0; i < nb; ++i)
         {
-            if (!write_file(f0 + i, &out[per_file * i], n[i], rate[i], err))
+            if (!write_file(f0 + i, &out[per_file * i], &out16[per_file * i], n[i], rate[i], err))
             {
                 fprintf(stderr, "%s\n", err);
                 return 1;
             }
             umx_wav_free(audio[i]);
+            umx_wav_free_pcm16(audio16[i]);
         }
     }
     printf("Separated %d file(s), %.2f s of audio in %.3f s (%.1fx realtime, host buffers in/out, %d track lanes)\n", nfiles, audio_secs, wall,

@@ -19,6 +19,10 @@
 //                    outputs, weighted sums of the stems and of the input formed on the device, and no target_*.wav; goes with every
 //                    knob above except UMX_CLI_PER_SEGMENT; a source whose target does not run (UMX_TARGETS) is refused.  Unset or
 //                    empty: the path and the files of a run without it
+//   UMX_PCM16=1      16-bit PCM across PCIe (umx_hip_separate_tracks_io): the stems, or the UMX_MIX outputs, are written as
+//                    16-bit PCM WAVs under the same names, quantised on the device, and a 16-bit PCM input goes up as int16 (any other
+//                    encoding as fp32); UMX_PCM16_DITHER=<seed> adds TPDF dither with that seed.  Goes with UMX_RESAMPLE, UMX_TARGETS /
+//                    UMX_RESIDUAL, UMX_MIX and the other knobs; not with UMX_SHIFTS > 1 or UMX_CLI_PER_SEGMENT.  Unset: today's files
 #include "../../include/umx_host.h"
 #include "mix_env.h"
 #include "shifts_env.h"
@@ -94,12 +98,32 @@ int main(int argc, const char **argv)
         fprintf(stderr, "UMX_MIX: source \"%s\" does not run (UMX_TARGETS) and is not the residual's slot\n", umx_mix_silent_source(mixc, choice.write));
         return 1;
     }
+    const bool pcm16 = env_int("UMX_PCM16", 0) != 0;
+    if (pcm16 && (shifts > 1 || env_int("UMX_CLI_PER_SEGMENT", 0)))
+    {
+        fprintf(stderr, "UMX_PCM16: the shift ensemble (UMX_SHIFTS > 1) and UMX_CLI_PER_SEGMENT=1 do not offer 16-bit PCM transfers\n");
+        return 1;
+    }
+    if (!pcm16 && getenv("UMX_PCM16_DITHER"))
+    {
+        fprintf(stderr, "UMX_PCM16_DITHER: needs UMX_PCM16=1\n");
+        return 1;
+    }
+    umx_sample_io io = {UMX_SAMPLE_F32, pcm16 ? UMX_SAMPLE_S16 : UMX_SAMPLE_F32, 0, 0};
+    if (const char *seed = getenv("UMX_PCM16_DITHER"))
+    {
+        io.dither = 1;
+        io.dither_seed = (unsigned)strtoul(seed, nullptr, 0);
+    }
     printf("umx-cli (MI355X / gfx950) main driver program\n");
 
     float *audio = nullptr;
+    int16_t *audio16 = nullptr;
     int n = 0, ch = 0, rate = UMX_SAMPLE_RATE;
     const bool resample = env_int("UMX_RESAMPLE", 0) != 0;
-    if (resample ? umx_wav_load_rate(wav_file.c_str(), &audio, &n, &ch, &rate, err) : umx_wav_load(wav_file.c_str(), &audio, &n, &ch, err)) // umx.cpp:56
+    if (pcm16 && umx_wav_load_pcm16(wav_file.c_str(), &audio16, &n, &ch, resample ? &rate : nullptr, err) == UMX_OK)
+        io.in_format = UMX_SAMPLE_S16; // (any other encoding, and every other failure, is the float loader's to take or to report)
+    else if (resample ? umx_wav_load_rate(wav_file.c_str(), &audio, &n, &ch, &rate, err) : umx_wav_load(wav_file.c_str(), &audio, &n, &ch, err)) // umx.cpp:56
     {
         fprintf(stderr, "%s\n", err);
         return 1;
@@ -145,10 +169,14 @@ int main(int argc, const char **argv)
         hb.flags |= UMX_FLAG_LSTM_STEPWISE;
     umx_backend be{hip_segment, hip_reset, &hb};
     std::vector<float> stems[4];
+    std::vector<int16_t> stems16[4];
     float *out[4];
     for (int t = 0; t < (mixed ? mixc.n_out : 4); ++t)
     {
-        stems[t].resize((size_t)2 * n);
+        if (pcm16)
+            stems16[t].resize((size_t)2 * n);
+        else
+            stems[t].resize((size_t)2 * n);
         out[t] = stems[t].data();
     }
     const auto t2 = std::chrono::steady_clock::now();
@@ -164,6 +192,20 @@ int main(int argc, const char **argv)
                                 print_progress, nullptr, err)) // umx.cpp:72-73
         {
             fprintf(stderr, "inference failed: %s\n", err);
+            return 1;
+        }
+    }
+    else if (pcm16)
+    {
+        const int offset = env_int("UMX_SHIFT_OFFSET", -1) < 0 ? UMX_REFERENCE_SHIFT : env_int("UMX_SHIFT_OFFSET", -1);
+        const void *in = io.in_format == UMX_SAMPLE_S16 ? (const void *)audio16 : (const void *)audio;
+        void *out16[4];
+        for (int t = 0; t < 4; ++t)
+            out16[t] = stems16[t].data();
+        if (umx_hip_separate_tracks_io(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out16,
+                                       hb.flags, &io, print_progress, nullptr))
+        {
+            fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
             return 1;
         }
     }
@@ -209,13 +251,16 @@ int main(int argc, const char **argv)
             continue;
         const std::string p = (std::filesystem::path(out_dir) / (mixed ? mixc.name[t] + ".wav" : choice.file[t])).string();
         printf("Writing wav file %s\n", p.c_str());
-        if (resample ? umx_wav_write_f32_rate(p.c_str(), out[t], n, rate, err) : umx_wav_write_f32(p.c_str(), out[t], n, err))
+        if (pcm16 ? umx_wav_write_pcm16_rate(p.c_str(), stems16[t].data(), n, rate, err)
+            : resample ? umx_wav_write_f32_rate(p.c_str(), out[t], n, rate, err)
+                       : umx_wav_write_f32(p.c_str(), out[t], n, err))
         {
             fprintf(stderr, "%s\n", err);
             return 1;
         }
     }
     umx_wav_free(audio);
+    umx_wav_free_pcm16(audio16);
     umx_hip_destroy(ctx);
     return 0;
 }

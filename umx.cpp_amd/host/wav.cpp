@@ -26,14 +26,20 @@ uint16_t u16(const unsigned char *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 } // namespace
 
 // any_rate: report the file's rate in *rate_out (8000 .. 192000 Hz) instead of refusing all but 44100
-static int wav_load(const char *path, float **audio_out, int *n_frames_out, int *channels_in_file, bool any_rate, int *rate_out, char *err)
+// pcm16: the file's int16 samples as they are (16-bit PCM files only) in *pcm16_out instead of floats in *audio_out; without
+// pcm16_out only the file's head is read and what it declares reported (is it 16-bit PCM, its frames, channels, rate)
+static int wav_load(const char *path, float **audio_out, bool pcm16, int16_t **pcm16_out, int *n_frames_out, int *channels_in_file, bool any_rate, int *rate_out, char *err)
 {
-    if (!path || !audio_out || !n_frames_out)
+    const bool probe = pcm16 && !pcm16_out;
+    if (!path || (!pcm16 && !audio_out) || !n_frames_out)
     {
-        seterr(err, any_rate ? "umx_wav_load_rate: null argument" : "umx_wav_load: null argument");
+        seterr(err, pcm16 ? "umx_wav_load_pcm16: null argument" : any_rate ? "umx_wav_load_rate: null argument" : "umx_wav_load: null argument");
         return UMX_ERR_ARG;
     }
-    *audio_out = nullptr;
+    if (pcm16_out)
+        *pcm16_out = nullptr;
+    if (audio_out)
+        *audio_out = nullptr;
     *n_frames_out = 0;
     FILE *f = fopen(path, "rb");
     if (!f)
@@ -42,12 +48,20 @@ static int wav_load(const char *path, float **audio_out, int *n_frames_out, int 
         return UMX_HOST_ERR_IO;
     }
     std::vector<unsigned char> b;
+    size_t file_size = 0; // probe: the head is all that is read, the size bounds what it declares
     {
         unsigned char chunk[1 << 16];
         size_t n;
         while ((n = fread(chunk, 1, sizeof chunk, f)) > 0)
+        {
             b.insert(b.end(), chunk, chunk + n);
+            if (probe)
+                break;
+        }
+        if (probe && fseek(f, 0, SEEK_END) == 0 && ftell(f) > 0)
+            file_size = (size_t)ftell(f);
         fclose(f);
+        file_size = std::max(file_size, b.size());
     }
     if (b.size() < 12 || memcmp(b.data(), "RIFF", 4) || memcmp(b.data() + 8, "WAVE", 4))
     {
@@ -76,7 +90,7 @@ static int wav_load(const char *path, float **audio_out, int *n_frames_out, int 
         else if (!memcmp(ck, "data", 4))
         {
             data = b.data() + body;
-            data_len = std::min(len, b.size() - body);
+            data_len = std::min(len, file_size - body);
             break;
         }
         pos = body + len + (len & 1);
@@ -116,6 +130,33 @@ static int wav_load(const char *path, float **audio_out, int *n_frames_out, int 
         return UMX_HOST_ERR_AUDIO;
     }
     const size_t n = data_len / ((size_t)bps * channels);
+    if (pcm16)
+    {
+        if (fmt_tag != 1 || bits != 16)
+        {
+            seterr(err, "not a 16-bit PCM file (the float loader takes it)");
+            return UMX_HOST_ERR_AUDIO;
+        }
+        if (probe)
+        {
+            *n_frames_out = (int)n;
+            return UMX_OK;
+        }
+        int16_t *q = (int16_t *)malloc(sizeof(int16_t) * 2 * std::max<size_t>(n, 1));
+        if (!q)
+        {
+            seterr(err, "out of memory");
+            return UMX_HOST_ERR_IO;
+        }
+        for (size_t i = 0; i < n; ++i) // mono duplicated, as the float loader does
+        {
+            q[2 * i] = (int16_t)u16(data + (channels == 1 ? i : 2 * i) * 2);
+            q[2 * i + 1] = (int16_t)u16(data + (channels == 1 ? i : 2 * i + 1) * 2);
+        }
+        *pcm16_out = q;
+        *n_frames_out = (int)n;
+        return UMX_OK;
+    }
     float *out = (float *)malloc(sizeof(float) * 2 * std::max<size_t>(n, 1));
     if (!out)
     {
@@ -158,13 +199,20 @@ static int wav_load(const char *path, float **audio_out, int *n_frames_out, int 
 
 extern "C" int umx_wav_load(const char *path, float **audio_out, int *n_frames_out, int *channels_in_file, char *err)
 {
-    return wav_load(path, audio_out, n_frames_out, channels_in_file, false, nullptr, err);
+    return wav_load(path, audio_out, false, nullptr, n_frames_out, channels_in_file, false, nullptr, err);
 }
 
 extern "C" int umx_wav_load_rate(const char *path, float **audio_out, int *n_frames_out, int *channels_in_file, int *rate_out, char *err)
 {
-    return wav_load(path, audio_out, n_frames_out, channels_in_file, true, rate_out, err);
+    return wav_load(path, audio_out, false, nullptr, n_frames_out, channels_in_file, true, rate_out, err);
 }
+
+extern "C" int umx_wav_load_pcm16(const char *path, int16_t **audio_out, int *n_frames_out, int *channels_in_file, int *rate_out, char *err)
+{
+    return wav_load(path, nullptr, true, audio_out, n_frames_out, channels_in_file, rate_out != nullptr, rate_out, err);
+}
+
+extern "C" void umx_wav_free_pcm16(int16_t *audio) { free(audio); }
 
 extern "C" void umx_wav_free(float *audio) { free(audio); }
 
@@ -173,11 +221,25 @@ extern "C" int umx_wav_write_f32(const char *path, const float *audio, int n_fra
     return umx_wav_write_f32_rate(path, audio, n_frames, UMX_SAMPLE_RATE, err);
 }
 
+// bits: 32 = IEEE float samples, 16 = PCM samples
+static int wav_write(const char *path, const void *audio, int n_frames, int rate, int bits, char *err);
+
 extern "C" int umx_wav_write_f32_rate(const char *path, const float *audio, int n_frames, int rate, char *err)
 {
+    return wav_write(path, audio, n_frames, rate, 32, err);
+}
+
+extern "C" int umx_wav_write_pcm16_rate(const char *path, const int16_t *audio, int n_frames, int rate, char *err)
+{
+    return wav_write(path, audio, n_frames, rate, 16, err);
+}
+
+static int wav_write(const char *path, const void *audio, int n_frames, int rate, int bits, char *err)
+{
+    const uint32_t bps = (uint32_t)bits / 8;
     if (!path || !audio || n_frames < 0 || rate < 1)
     {
-        seterr(err, "umx_wav_write_f32: bad argument");
+        seterr(err, bits == 16 ? "umx_wav_write_pcm16: bad argument" : "umx_wav_write_f32: bad argument");
         return UMX_ERR_ARG;
     }
     FILE *f = fopen(path, "wb");
@@ -186,7 +248,7 @@ extern "C" int umx_wav_write_f32_rate(const char *path, const float *audio, int 
         seterr(err, std::string("cannot create ") + path);
         return UMX_HOST_ERR_IO;
     }
-    const uint32_t data_bytes = (uint32_t)n_frames * 2u * 4u;
+    const uint32_t data_bytes = (uint32_t)n_frames * 2u * bps;
     unsigned char h[44];
     auto p32 = [&](int o, uint32_t v) { h[o] = v & 255; h[o + 1] = (v >> 8) & 255; h[o + 2] = (v >> 16) & 255; h[o + 3] = (v >> 24) & 255; };
     auto p16 = [&](int o, uint16_t v) { h[o] = v & 255; h[o + 1] = (v >> 8) & 255; };
@@ -194,15 +256,15 @@ extern "C" int umx_wav_write_f32_rate(const char *path, const float *audio, int 
     p32(4, 36 + data_bytes);
     memcpy(h + 8, "WAVEfmt ", 8);
     p32(16, 16);
-    p16(20, 3); // WAVE_FORMAT_IEEE_FLOAT
+    p16(20, bits == 16 ? 1 : 3); // WAVE_FORMAT_PCM / WAVE_FORMAT_IEEE_FLOAT
     p16(22, 2);
     p32(24, (uint32_t)rate);
-    p32(28, (uint32_t)rate * 2 * 4);
-    p16(32, 8);
-    p16(34, 32);
+    p32(28, (uint32_t)rate * 2 * bps);
+    p16(32, (uint16_t)(2 * bps));
+    p16(34, (uint16_t)bits);
     memcpy(h + 36, "data", 4);
     p32(40, data_bytes);
-    bool ok = fwrite(h, 1, 44, f) == 44 && fwrite(audio, 4, (size_t)n_frames * 2, f) == (size_t)n_frames * 2;
+    bool ok = fwrite(h, 1, 44, f) == 44 && fwrite(audio, bps, (size_t)n_frames * 2, f) == (size_t)n_frames * 2;
     ok = (fclose(f) == 0) && ok;
     if (!ok)
     {
