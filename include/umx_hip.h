@@ -434,6 +434,72 @@ int umx_hip_pcm16_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *co
 /* the same rules on the host (no GPU, no context): n_values samples; n_frames stereo frames of output buffer `buffer` */
 int umx_hip_pcm16_decode_host(const int16_t *q, long long n_values, float *x);
 int umx_hip_pcm16_encode_host(const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, int16_t *q);
+/* Output levels and clip handling.  A separated stem is not bounded by the mixture: Wiener stems of a track mastered to
+ * full scale, or a mix row such as mix - 0.5 vocals, pass 1.0, and the int16 encode clamps.  The levels of what leaves are measured
+ * on the device, where every output frame is final before it is encoded or copied.  The rules, to the bit:
+ *   levels of output buffer m, over both channels of the `length` frames that leave for the caller -- at the caller's rate, behind
+ *   the mix, before any encode and before any rescale:
+ *     peak[m]        the largest |x| over the samples that are not NaN (+inf counts: the peak is then inf); 0 when there is none.
+ *                    Exact: an unsigned integer maximum over the bit patterns of |x|.
+ *     over_unity[m]  the number of samples with |x| > 1.0f (NaN is not one of them, +-inf is)
+ *     nonfinite[m]   the number of samples that are NaN or +-inf
+ *     clipped[m]     0 for an fp32 output; for a UMX_SAMPLE_S16 output the number of samples whose rounded value r of the encode rule
+ *                    above is > 32767.f or < -32768.f, that is, where the clamp changed the value.  r includes the dither term when
+ *                    dither is on and the rescale divisor when rescale is on; +-inf is counted, NaN is not (it is in nonfinite).
+ *   All four are maxima or integer counts: they do not depend on how the track is cut into regions, which lane a job rides in, the
+ *   queue, reset mode or a rerun after a timeout.  (A sum of squares has no order-independent exact form; it is not part of the record.)
+ *   rescale (UMX_CLIP_RESCALE): one divisor per track, common to all of its outputs (the stems still add up to the mixture over it;
+ *   Demucs' rescale is per file).  P = the maximum of peak[m] over the outputs that leave; g = 1.01f * P, one fp32 product.  If P is
+ *   not finite, or if !(g > 1.0f), the divisor is 1 and the output is, bit for bit, the clamp-mode output.  Otherwise every sample
+ *   becomes x / g, the correctly rounded fp32 quotient; for a UMX_SAMPLE_S16 output the unchanged encode rule follows (dither as
+ *   before), for an fp32 output the quotient is what leaves.  With a finite P nothing clamps afterwards (|x / g| <= 1 / 1.01 up to
+ *   rounding, |v| < 32443, the dither is below 1 in size): clipped is then 0.  The divisor is formed on the device from the peak
+ *   words; it is reported as `gain` (1 in clamp mode).
+ * The shift ensemble, the multi-GPU driver (umx_mgpu.h) and the per-segment umx_hip_infer_* calls do not offer levels or rescale. */
+#define UMX_CLIP_CLAMP 0
+#define UMX_CLIP_RESCALE 1
+typedef struct umx_levels_acc /* the device record: zero it, let launches accumulate, copy it back */
+{
+    unsigned peak_bits[4]; /* bit pattern of peak[m] */
+    unsigned long long over_unity[4], clipped[4], nonfinite[4];
+} umx_levels_acc;
+typedef struct umx_levels /* what a whole-track call reports per track */
+{
+    float peak[4];
+    float gain;
+    int n_out;
+    unsigned long long over_unity[4], clipped[4], nonfinite[4];
+} umx_levels;
+/* umx_hip_separate_tracks_io with a clip mode and levels: n_tracks records, or NULL.  clip_mode == UMX_CLIP_CLAMP and levels == NULL
+ * IS the _io call: the same launches, nothing allocated.  Clamp mode with levels adds one measuring launch per finished region; a
+ * rescaled track leaves whole behind its last segment (mix, levels, rescaled encode or in-place division, one download per output).
+ * UMX_ERR_ARG, naming the reason and leaving the context usable, for an unknown clip_mode and for everything the _io call refuses. */
+int umx_hip_separate_tracks_levels(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                                   const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                                   const umx_sample_io *io, int clip_mode, umx_levels *levels, void (*progress)(float, void *),
+                                   void *progress_user);
+/* umx_hip_separate_queue_io with a clip mode; every job is measured and its done callback receives the record, valid during the
+ * callback only.  A rescaled job is one whole-track region queued with its last segment. */
+typedef void (*umx_queue_levels_fn)(void *user, const umx_queue_job *job, const umx_levels *levels);
+int umx_hip_separate_queue_levels(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_levels_fn done, void *user, int n_out,
+                                  const float *gains, unsigned flags, const umx_sample_io *io, int clip_mode);
+/* the kernels on the caller's device buffers ((2,n) interleaved fp32, 8-byte aligned), queued on hip_stream; acc_dev: a
+ * umx_levels_acc in device memory that the caller has zeroed, launches accumulate into it.
+ * levels: buffer b of 1 .. 4 is output b, its frame i frame first_frame + i; io == NULL or an fp32 out_format: clipped stays as it
+ * is, else the clamped samples of the plain encode are counted with io's dither.  Exactly the record is written.
+ * pcm16_encode_rescaled: the encode of umx_hip_pcm16_encode_device on x / g, g formed from acc_dev's peak words by the rule; the
+ * samples it clamps (possible only where the divisor is 1) are added to acc_dev's clipped.  rescale: x / g in place (nothing is
+ * written where the divisor is 1). */
+int umx_hip_levels_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
+                          const umx_sample_io *io, umx_levels_acc *acc_dev, void *hip_stream);
+int umx_hip_pcm16_encode_rescaled_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
+                                         const umx_sample_io *io, int16_t *const *out_dev, umx_levels_acc *acc_dev, void *hip_stream);
+int umx_hip_rescale_device(umx_hip_ctx *ctx, int n_buffers, float *const *bufs_dev, int n, const umx_levels_acc *acc_dev, void *hip_stream);
+/* the same rules on the host (no GPU, no context): n_frames stereo frames of output buffer `buffer` accumulate into *acc; clipped is
+ * counted for a UMX_SAMPLE_S16 out_format of io, on x / clip_divisor when clip_divisor != 1.  The divisor of peaks peak[0 .. n). */
+int umx_hip_levels_host(const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, float clip_divisor,
+                        umx_levels_acc *acc);
+float umx_hip_rescale_gain(const float *peak, int n);
 /* testing, host only: the fp32 tap table of a rate pair (taps[phase * K + d + D]; cap floats at most), its phase count L, taps
  * per phase K and first offset -D.  UMX_ERR_ARG for a bad rate or a too small cap (the sizes are still reported). */
 int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase,

@@ -97,6 +97,28 @@ _i16p = C.POINTER(C.c_int16)
 QUEUE_NEXT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(QueueJob))
 QUEUE_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJob))
 
+CLIP_CLAMP, CLIP_RESCALE = 0, 1  # UMX_CLIP_*: what a whole-track call does with outputs beyond full scale
+
+
+class LevelsAcc(C.Structure):
+    """include/umx_hip.h: umx_levels_acc, the record the measuring launches accumulate into"""
+    _fields_ = [("peak_bits", C.c_uint * 4), ("over_unity", C.c_ulonglong * 4), ("clipped", C.c_ulonglong * 4),
+                ("nonfinite", C.c_ulonglong * 4)]
+
+
+class Levels(C.Structure):
+    """include/umx_hip.h: umx_levels, what a whole-track call reports per track"""
+    _fields_ = [("peak", C.c_float * 4), ("gain", C.c_float), ("n_out", C.c_int), ("over_unity", C.c_ulonglong * 4),
+                ("clipped", C.c_ulonglong * 4), ("nonfinite", C.c_ulonglong * 4)]
+
+    def as_dict(self):
+        n = self.n_out
+        return {"peak": np.array(self.peak[:n], np.float32), "gain": np.float32(self.gain), "over_unity": list(self.over_unity[:n]),
+                "clipped": list(self.clipped[:n]), "nonfinite": list(self.nonfinite[:n])}
+
+
+QUEUE_LEVELS_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJob), C.POINTER(Levels))
+
 
 class TensorView(C.Structure):
     """include/umx_hip.h: umx_tensor_view"""
@@ -247,6 +269,19 @@ def hip_lib():
                                                 C.POINTER(C.c_void_p), C.c_void_p]
     lib.umx_hip_pcm16_decode_host.argtypes = [_i16p, C.c_longlong, _fp]
     lib.umx_hip_pcm16_encode_host.argtypes = [_fp, C.c_int, C.c_int, C.c_longlong, C.POINTER(SampleIO), _i16p]
+    lib.umx_hip_separate_tracks_levels.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                   C.POINTER(C.c_int), C.c_int, _fp, C.POINTER(C.c_void_p), C.c_uint, C.POINTER(SampleIO),
+                                                   C.c_int, C.POINTER(Levels), C.c_void_p, C.c_void_p]
+    lib.umx_hip_separate_queue_levels.argtypes = [C.c_void_p, QUEUE_NEXT_FN, QUEUE_LEVELS_FN, C.c_void_p, C.c_int, _fp, C.c_uint,
+                                                  C.POINTER(SampleIO), C.c_int]
+    lib.umx_hip_levels_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.POINTER(SampleIO), C.c_void_p,
+                                          C.c_void_p]
+    lib.umx_hip_pcm16_encode_rescaled_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.POINTER(SampleIO),
+                                                         C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+    lib.umx_hip_rescale_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
+    lib.umx_hip_levels_host.argtypes = [_fp, C.c_int, C.c_int, C.c_longlong, C.POINTER(SampleIO), C.c_float, C.POINTER(LevelsAcc)]
+    lib.umx_hip_rescale_gain.argtypes = [_fp, C.c_int]
+    lib.umx_hip_rescale_gain.restype = C.c_float
     _hip = lib
     return lib
 
@@ -285,7 +320,9 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_mix_columns", "umx_hip_separate_tracks_mix", "umx_hip_shift_ensemble_mix", "umx_hip_mix_stems_device",
                "umx_hip_separate_queue", "umx_hip_queue_plan", "umx_hip_debug_queue_calls",
                "umx_hip_separate_tracks_io", "umx_hip_separate_queue_io", "umx_hip_pcm16_decode_device", "umx_hip_pcm16_encode_device",
-               "umx_hip_pcm16_decode_host", "umx_hip_pcm16_encode_host"]
+               "umx_hip_pcm16_decode_host", "umx_hip_pcm16_encode_host",
+               "umx_hip_separate_tracks_levels", "umx_hip_separate_queue_levels", "umx_hip_levels_device",
+               "umx_hip_pcm16_encode_rescaled_device", "umx_hip_rescale_device", "umx_hip_levels_host", "umx_hip_rescale_gain"]
 
 
 def sample_io(in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None):
@@ -314,6 +351,24 @@ def pcm16_encode_host(x, buffer=0, first_frame=0, dither_seed=None):
     if rc != UMX_OK:
         raise UmxError(rc, "umx_hip_pcm16_encode_host")
     return np.ascontiguousarray(q.T)
+
+
+def levels_host(x, buffer=0, first_frame=0, io=None, clip_divisor=1.0, acc=None):
+    """umx_hip_levels_host: the levels of a (2,n) float32 array as output buffer `buffer` of a call, accumulated into the LevelsAcc
+    `acc` (None: a fresh one), which is returned; clipped is counted for an io with a SAMPLE_S16 output, on x / clip_divisor (no GPU)."""
+    a = np.ascontiguousarray(np.asarray(x, np.float32).T)
+    acc = LevelsAcc() if acc is None else acc
+    rc = hip_lib().umx_hip_levels_host(a.ctypes.data_as(_fp), a.shape[0], int(buffer), int(first_frame), None if io is None else C.byref(io),
+                                       C.c_float(clip_divisor), C.byref(acc))
+    if rc != UMX_OK:
+        raise UmxError(rc, "umx_hip_levels_host")
+    return acc
+
+
+def rescale_gain(peaks):
+    """umx_hip_rescale_gain: the divisor of a track whose outputs peak at `peaks` (1: nothing is divided), as float32 (no GPU)."""
+    p = np.ascontiguousarray(np.atleast_1d(np.asarray(peaks, np.float32)))
+    return np.float32(hip_lib().umx_hip_rescale_gain(p.ctypes.data_as(_fp), p.size))
 
 
 def resampled_length(n, rate_in, rate_out):
@@ -696,6 +751,48 @@ class Engine:
                                                         None if g is None else g.ctypes.data_as(_fp), o, flags, C.byref(io), None, None))
         return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)]
 
+    # --- output levels and clip handling: what leaves is measured on the device; rescale divides a track by one divisor ---
+    def separate_many_levels(self, waves, clip=CLIP_CLAMP, io=None, flags=0, shift_offsets=None, rates=None, gains=None, levels=True):
+        """umx_hip_separate_tracks_levels: separate_many_io() (io: a SampleIO, None = fp32 both ways) with a clip mode -> (outputs,
+        [Levels per track]); levels=False passes NULL for the records and returns None for them."""
+        nt = len(waves)
+        io = sample_io() if io is None else io
+        n_out, g = (4, None) if gains is None else _mix_gains(gains)
+        tin = np.int16 if io.in_format == SAMPLE_S16 else np.float32
+        tout = np.int16 if io.out_format == SAMPLE_S16 else np.float32
+        ins = [np.ascontiguousarray(np.asarray(w, tin).T).ravel() for w in waves]
+        Ls = [np.asarray(w).shape[1] for w in waves]
+        outs = [[np.empty(2 * L, tout) for _ in range(min(max(n_out, 0), MAX_MIX_OUTPUTS))] for L in Ls]
+        a = (C.c_void_p * nt)(*[x.ctypes.data for x in ins])
+        o = (C.c_void_p * max(1, sum(len(t) for t in outs)))(*[x.ctypes.data for t in outs for x in t])
+        sh = (C.c_int * nt)(*[(-1 if s is None else s) for s in (shift_offsets or [None] * nt)])
+        rt = None if rates is None else (C.c_int * nt)(*[int(r) for r in rates])
+        lv = (Levels * nt)() if levels else None
+        self._check(self.lib.umx_hip_separate_tracks_levels(self.h, nt, a, (C.c_int * nt)(*Ls), rt, sh, n_out,
+                                                            None if g is None else g.ctypes.data_as(_fp), o, flags, C.byref(io), int(clip), lv,
+                                                            None, None))
+        return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)], (list(lv) if levels else None)
+
+    def levels_device(self, in_ptrs, n, acc_ptr, first_frame=0, io=None, hip_stream=None):
+        """umx_hip_levels_device: 1 .. 4 device buffers (2,n) interleaved fp32 measured into the umx_levels_acc at device address acc_ptr."""
+        nb = len(in_ptrs)
+        self._check(self.lib.umx_hip_levels_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(first_frame),
+                                                   None if io is None else C.byref(io), C.c_void_p(acc_ptr), hip_stream))
+
+    def pcm16_encode_rescaled_device(self, in_ptrs, n, out_ptrs, acc_ptr, first_frame=0, dither_seed=None, hip_stream=None):
+        """umx_hip_pcm16_encode_rescaled_device: pcm16_encode_device() on x / g, g formed on the device from the record at acc_ptr."""
+        nb = len(in_ptrs)
+        assert len(out_ptrs) == nb
+        io = sample_io(SAMPLE_F32, SAMPLE_S16, dither_seed)
+        self._check(self.lib.umx_hip_pcm16_encode_rescaled_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(first_frame),
+                                                                  C.byref(io), (C.c_void_p * max(1, nb))(*out_ptrs), C.c_void_p(acc_ptr),
+                                                                  hip_stream))
+
+    def rescale_device(self, ptrs, n, acc_ptr, hip_stream=None):
+        """umx_hip_rescale_device: 1 .. 4 device buffers (2,n) interleaved fp32 divided in place by the divisor of the record at acc_ptr."""
+        nb = len(ptrs)
+        self._check(self.lib.umx_hip_rescale_device(self.h, nb, (C.c_void_p * max(1, nb))(*ptrs), int(n), C.c_void_p(acc_ptr), hip_stream))
+
     def pcm16_decode_device(self, in_ptr, n, out_ptr, hip_stream=None):
         """umx_hip_pcm16_decode_device: n int16 stereo frames at device address in_ptr -> (2,n) interleaved fp32 at out_ptr."""
         self._check(self.lib.umx_hip_pcm16_decode_device(self.h, C.c_void_p(in_ptr), int(n), C.c_void_p(out_ptr), hip_stream))
@@ -709,10 +806,11 @@ class Engine:
                                                          (C.c_void_p * nb)(*out_ptrs), hip_stream))
 
     # --- the track queue: more tracks than lanes, a lane refilled with the next track the moment one ends ---
-    def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None, io=None):
+    def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None, io=None, clip=None, levels=False):
         """umx_hip_separate_queue: list of (2,L_i) -> list of [4 x (2,L_i)] (mix: an (n_out, 5) gain matrix -> n_out x (2,L_i)), every
         job bit for bit what separate() / separate_mix() returns for it alone on this engine; the jobs are handed out in list order.
-        io: a SampleIO (sample_io()) -> umx_hip_separate_queue_io, int16 arrays in and / or out as it says."""
+        io: a SampleIO (sample_io()) -> umx_hip_separate_queue_io, int16 arrays in and / or out as it says.
+        clip (CLIP_CLAMP / CLIP_RESCALE) or levels=True -> umx_hip_separate_queue_levels: returns (outputs, [Levels per job])."""
         nj = len(waves)
         n_out, g = (4, None) if mix is None else _mix_gains(mix)
         tin = np.int16 if io is not None and io.in_format == SAMPLE_S16 else np.float32
@@ -738,6 +836,18 @@ class Engine:
         def _done(_user, job):
             state["done"].append(int(job[0].tag) - 1)
 
+        if clip is not None or levels:
+            got = [None] * nj
+
+            def _done_levels(_user, job, lv):
+                _done(_user, job)
+                got[int(job[0].tag) - 1] = Levels.from_buffer_copy(lv[0])  # (valid during the callback only)
+
+            self._check(self.lib.umx_hip_separate_queue_levels(self.h, QUEUE_NEXT_FN(_next), QUEUE_LEVELS_FN(_done_levels), None, n_out,
+                                                               None if g is None else g.ctypes.data_as(_fp), flags,
+                                                               None if io is None else C.byref(io), int(clip or CLIP_CLAMP)))
+            assert sorted(state["done"]) == list(range(nj)), state
+            return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)], got
         if io is None:
             self._check(self.lib.umx_hip_separate_queue(self.h, QUEUE_NEXT_FN(_next), QUEUE_DONE_FN(_done), None, n_out,
                                                         None if g is None else g.ctypes.data_as(_fp), flags))

@@ -42,6 +42,7 @@
 #include "shift_mean.h"
 #include "stem_mix.h"
 #include "pcm16.h"
+#include "levels.h"
 #include "gate_debug.h"
 
 using namespace umx;
@@ -576,6 +577,8 @@ struct umx_hip_ctx
         bool ensemble = false;       // the lanes are ONE track at n_tracks shift offsets, `out` the buffers of their mean
         const MixSpec *mix = nullptr; // stem_mix.h, DESIGN 17: weighted sums of a track's stems and its input instead of the stems
         umx_sample_io io = {};        // pcm16.h, DESIGN 19: how `audio` and `out` are read (UMX_SAMPLE_S16: int16 frames behind the float pointers)
+        int clip_mode = UMX_CLIP_CLAMP; // levels.h, DESIGN 20: UMX_CLIP_RESCALE: every track leaves whole, over its common divisor
+        umx_levels *levels = nullptr; // n_tracks records of what left, or nullptr: not wanted
     };
     int tracks(const TrackRequest &rq);
     int tracks_once(const TrackRequest &rq);
@@ -597,6 +600,7 @@ struct umx_hip_ctx
         uint32_t *in16 = nullptr, *out16[4] = {};
         size_t cap_in16 = 0, cap_out16[4] = {};
         hipEvent_t in16_ev = nullptr; // behind the most recent decode out of in16 (track_upload_until): every call that reads `in` waits for it
+        umx_levels_acc *lev = nullptr; // DESIGN 20, only once a job measures: the record of what leaves, zeroed with the accumulators
     };
     std::vector<TrackBufs> trk;
     hipEvent_t trk_acc_ev[kMaxSlots] = {}; // per slot: behind the overlap-add of the last call that ran in it
@@ -610,7 +614,11 @@ struct umx_hip_ctx
         long long uploaded = 0;       // host frames already on the device
         TrackBufs *acc = nullptr;     // the accumulator set it writes
         bool by_region = true;        // its final regions are mixed in place and leave region by region (false: an ensemble lane, a
-                                      // resampled track -- mixed and downloaded whole behind the last segment)
+                                      // resampled track, a rescaled one -- mixed and downloaded whole behind the last segment)
+        int clip_mode = UMX_CLIP_CLAMP; // UMX_CLIP_RESCALE divides what leaves by the track's divisor (and measures for it)
+        bool levels = false;          // what leaves is measured into acc->lev
+        bool whole_region = false;    // not by_region, and track_call itself finishes it behind its last segment as ONE region: the
+                                      // frames [lead, lead + length) (a rescaled track at 44.1 kHz)
     };
     struct TrackLane // a lane of one call: its job (nullptr: idle) and the padded frame at which its segment starts
     {
@@ -658,6 +666,9 @@ struct umx_hip_ctx
     int track_pcm16_grow(TrackBufs &tb_, const umx_sample_io &io, size_t frames, int n_host);
     void track_encode(const TrackBufs &tb_, const umx_sample_io &io, int n_host, float *const src[4], size_t src_start, int count,
                       long long first_frame, hipStream_t st);
+    int track_levels_grow(TrackBufs &tb_);
+    void track_leave(const TrackJob &j, int n_host, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st);
+    hipError_t track_levels_report(const TrackJob &j, int n_host, umx_levels &lv);
     hipError_t track_upload_until(TrackJob &j, long long padded_end, hipStream_t st);
     void track_mix(const MixSpec &mix, float *const stems[4], size_t stem_start, const float *in, size_t in_start, int count, hipStream_t st);
     hipError_t track_region_download(const TrackRegion &r, int n_host, float *const *out_host);
@@ -665,8 +676,15 @@ struct umx_hip_ctx
     // track queue (engine_queue.h): B + 2 accumulator sets (in, out, sumw of TrackBufs; grow-only) lent to the jobs in flight
     std::vector<TrackBufs> qpool;
     int queue_calls = -1; // infer_batch calls of the last queue run
-    int queue(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io);
-    int queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io);
+    struct QueueDone // the done callback of a run: the plain one, or the one that receives every job's levels
+    {
+        umx_queue_done_fn plain = nullptr;
+        umx_queue_levels_fn with_levels = nullptr;
+        int clip_mode = UMX_CLIP_CLAMP;
+        bool measures() const { return with_levels != nullptr; }
+    };
+    int queue(umx_queue_next_fn next, const QueueDone &done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io);
+    int queue_run(umx_queue_next_fn next, const QueueDone &done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io);
     int phase_begin(const float *audio_host, int n, unsigned flags);
     int phase_begin_device(const float *audio_dev, int n, unsigned flags);
     int phase_end_device(float *const out_dev_[4]);

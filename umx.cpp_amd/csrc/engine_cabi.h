@@ -419,7 +419,9 @@ int umx_hip_separate_queue(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_d
     MixSpec spec;
     if (gains && !mix_checked(ctx, n_out, gains, spec))
         return UMX_ERR_ARG;
-    return ctx->queue(next, done, user, gains ? &spec : nullptr, flags, umx_sample_io{});
+    umx_hip_ctx::QueueDone qd;
+    qd.plain = done;
+    return ctx->queue(next, qd, user, gains ? &spec : nullptr, flags, umx_sample_io{});
 }
 
 // ---------------------------------------------------------------- 16-bit PCM in and out (pcm16.h)
@@ -462,7 +464,9 @@ int umx_hip_separate_queue_io(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queu
     MixSpec spec;
     if (gains && !mix_checked(ctx, n_out, gains, spec))
         return UMX_ERR_ARG;
-    return ctx->queue(next, done, user, gains ? &spec : nullptr, flags, io ? *io : umx_sample_io{});
+    umx_hip_ctx::QueueDone qd;
+    qd.plain = done;
+    return ctx->queue(next, qd, user, gains ? &spec : nullptr, flags, io ? *io : umx_sample_io{});
 }
 
 int umx_hip_pcm16_decode_device(umx_hip_ctx *ctx, const int16_t *in_dev, int n, float *out_dev, void *hip_stream)
@@ -529,6 +533,162 @@ int umx_hip_pcm16_encode_host(const float *x, int n_frames, int buffer, long lon
             q[2 * (size_t)i + ch] = pcm16_encode(x[2 * (size_t)i + ch], dither, key[ch], first_frame + i);
     return UMX_OK;
 }
+// ---------------------------------------------------------------- output levels and clip handling (levels.h)
+static bool clip_mode_checked(umx_hip_ctx *ctx, int clip_mode)
+{
+    const char *why = clip_mode_refusal(clip_mode);
+    if (why)
+        ctx->set_error(why);
+    return !why;
+}
+
+// clip_mode == UMX_CLIP_CLAMP and levels == NULL: the request of umx_hip_separate_tracks_io, field for field
+int umx_hip_separate_tracks_levels(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                                   const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                                   const umx_sample_io *io, int clip_mode, umx_levels *levels, void (*progress)(float, void *),
+                                   void *progress_user)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!sample_io_checked(ctx, io) || !clip_mode_checked(ctx, clip_mode))
+        return UMX_ERR_ARG;
+    MixSpec spec;
+    if (gains && !mix_checked(ctx, n_out, gains, spec))
+        return UMX_ERR_ARG;
+    umx_hip_ctx::TrackRequest rq = {n_tracks, reinterpret_cast<const float *const *>(audio_host), length, rate, shift_offset,
+                                    reinterpret_cast<float *const *>(out_host), flags, progress, progress_user};
+    rq.mix = gains ? &spec : nullptr;
+    if (io)
+        rq.io = *io;
+    rq.clip_mode = clip_mode;
+    rq.levels = levels;
+    return ctx->tracks(rq);
+}
+
+int umx_hip_separate_queue_levels(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_levels_fn done, void *user, int n_out,
+                                  const float *gains, unsigned flags, const umx_sample_io *io, int clip_mode)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!sample_io_checked(ctx, io) || !clip_mode_checked(ctx, clip_mode))
+        return UMX_ERR_ARG;
+    MixSpec spec;
+    if (gains && !mix_checked(ctx, n_out, gains, spec))
+        return UMX_ERR_ARG;
+    umx_hip_ctx::QueueDone qd;
+    qd.with_levels = done;
+    qd.clip_mode = clip_mode;
+    return ctx->queue(next, qd, user, gains ? &spec : nullptr, flags, io ? *io : umx_sample_io{});
+}
+
+// 1 .. 4 non-null device buffers of a kernel's entry point -> p[]; false: refused (set_error done)
+static bool levels_buffers(umx_hip_ctx *ctx, const char *what, int n_buffers, const void *const *bufs, int n, long long first_frame, const void *p[4])
+{
+    if (n_buffers < 1 || n_buffers > 4 || !bufs || n < 1 || first_frame < 0)
+    {
+        ctx->set_error(std::string(what) + ": need 1 .. 4 buffers, n >= 1 and first_frame >= 0");
+        return false;
+    }
+    for (int b = 0; b < n_buffers; ++b)
+    {
+        if (!bufs[b])
+        {
+            ctx->set_error(std::string(what) + ": null buffer");
+            return false;
+        }
+        p[b] = bufs[b];
+    }
+    return true;
+}
+
+int umx_hip_levels_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
+                          const umx_sample_io *io, umx_levels_acc *acc_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    const void *in[4] = {};
+    if (!levels_buffers(ctx, "levels", n_buffers, reinterpret_cast<const void *const *>(in_dev), n, first_frame, in))
+        return UMX_ERR_ARG;
+    const float2 *src[4] = {};
+    for (int b = 0; b < n_buffers; ++b)
+        src[b] = static_cast<const float2 *>(in[b]);
+    if (!acc_dev)
+    {
+        ctx->set_error("levels: null record");
+        return UMX_ERR_ARG;
+    }
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    launch_stem_levels(n_buffers, src, n, first_frame, io && io->out_format == UMX_SAMPLE_S16, io && io->dither, io ? io->dither_seed : 0u, acc_dev,
+                       (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+
+int umx_hip_pcm16_encode_rescaled_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
+                                         const umx_sample_io *io, int16_t *const *out_dev, umx_levels_acc *acc_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    const void *in[4] = {}, *out[4] = {};
+    if (!levels_buffers(ctx, "rescaled pcm16 encode", n_buffers, reinterpret_cast<const void *const *>(in_dev), n, first_frame, in) ||
+        !levels_buffers(ctx, "rescaled pcm16 encode", n_buffers, reinterpret_cast<const void *const *>(out_dev), n, first_frame, out))
+        return UMX_ERR_ARG;
+    const float2 *src[4] = {};
+    uint32_t *dst[4] = {};
+    for (int b = 0; b < n_buffers; ++b)
+    {
+        src[b] = static_cast<const float2 *>(in[b]);
+        dst[b] = static_cast<uint32_t *>(const_cast<void *>(out[b]));
+    }
+    if (!acc_dev)
+    {
+        ctx->set_error("rescaled pcm16 encode: null record");
+        return UMX_ERR_ARG;
+    }
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    launch_pcm16_encode_rescaled(n_buffers, src, dst, n, first_frame, io && io->dither, io ? io->dither_seed : 0u, acc_dev, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+
+int umx_hip_rescale_device(umx_hip_ctx *ctx, int n_buffers, float *const *bufs_dev, int n, const umx_levels_acc *acc_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    const void *in[4] = {};
+    if (!levels_buffers(ctx, "rescale", n_buffers, reinterpret_cast<const void *const *>(bufs_dev), n, 0, in))
+        return UMX_ERR_ARG;
+    float2 *p[4] = {};
+    for (int b = 0; b < n_buffers; ++b)
+        p[b] = static_cast<float2 *>(const_cast<void *>(in[b]));
+    if (!acc_dev)
+    {
+        ctx->set_error("rescale: null record");
+        return UMX_ERR_ARG;
+    }
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    launch_stem_rescale(n_buffers, p, n, acc_dev, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+
+int umx_hip_levels_host(const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, float clip_divisor,
+                        umx_levels_acc *acc)
+{
+    if (!x || !acc || n_frames < 0 || buffer < 0 || buffer >= UMX_MAX_MIX_OUTPUTS || first_frame < 0)
+        return UMX_ERR_ARG;
+    levels_host(x, n_frames, buffer, first_frame, io && io->out_format == UMX_SAMPLE_S16, io && io->dither, io ? io->dither_seed : 0u, clip_divisor, *acc);
+    return UMX_OK;
+}
+
+float umx_hip_rescale_gain(const float *peak, int n)
+{
+    uint32_t p = 0;
+    for (int m = 0; peak && m < n; ++m)
+        p = std::max(p, levels_abs_bits(peak[m]));
+    return levels_divisor(p);
+}
+
 int umx_hip_queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_out, int *first_call_out, int *n_calls_out)
 {
     return queue_plan(n_lanes, n_jobs, seg_count, lane_out, first_call_out, n_calls_out);

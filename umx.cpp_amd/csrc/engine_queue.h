@@ -67,9 +67,9 @@ int queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_out, int
 }
 } // namespace
 
-int umx_hip_ctx::queue(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io)
+int umx_hip_ctx::queue(umx_queue_next_fn next, const QueueDone &done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io)
 {
-    if (!next || !done)
+    if (!next || (!done.plain && !done.with_levels))
     {
         set_error("queue: need the next and the done callback");
         return UMX_ERR_ARG;
@@ -103,8 +103,9 @@ int umx_hip_ctx::queue(umx_queue_next_fn next, umx_queue_done_fn done, void *use
     return queue_run(next, done, user, mix, flags, io);
 }
 
-int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io)
+int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io)
 {
+    const bool rescale = done.clip_mode == UMX_CLIP_RESCALE, measure = done.measures() || rescale;
     const int n_host = mix ? mix->n_out : 4;
     const int stride = track_stride();
     const size_t n_sets = (size_t)B + 2;
@@ -149,7 +150,7 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void 
         for (Job *jb : redo)
         {
             jb->uploaded = 0;
-            jb->regions_left = jb->segs;
+            jb->regions_left = jb->by_region ? jb->segs : 1;
         }
         for (int ln = 0; ln < B; ++ln)
             lanes[ln] = TrackLane();
@@ -207,7 +208,18 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void 
         }
         for (Job *jb : finished)
         {
-            done(user, &jb->job);
+            if (done.with_levels) // the job's record, behind its last region
+            {
+                umx_levels lv;
+                if ((e = track_levels_report(*jb, n_host, lv)) != hipSuccess)
+                {
+                    set_error(std::string("queue: reading a job's levels failed: ") + hipGetErrorString(e));
+                    return UMX_ERR_HIP;
+                }
+                done.with_levels(user, &jb->job, &lv);
+            }
+            else
+                done.plain(user, &jb->job);
             jb->live = false;
         }
         return 0;
@@ -283,13 +295,20 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void 
                     return fail(rc);
                 if (int rc = track_pcm16_grow(qpool[set], io, (size_t)tj.length, n_host)) // (nothing for an fp32 run)
                     return fail(rc);
+                if (measure)
+                    if (int rc = track_levels_grow(qpool[set]))
+                        return fail(rc);
                 tj.audio = j.audio;
                 tj.io = io;
+                tj.clip_mode = done.clip_mode;
+                tj.levels = measure;
+                tj.by_region = !rescale; // (a rescaled job: one whole-track region, queued with its last segment)
+                tj.whole_region = rescale;
                 tj.acc = &qpool[set];
                 jb = &jobs[set];
                 static_cast<TrackJob &>(*jb) = tj;
                 jb->job = j;
-                jb->regions_left = tj.segs;
+                jb->regions_left = tj.by_region ? tj.segs : 1;
                 jb->seq = seq++;
                 jb->live = true;
             }
@@ -344,6 +363,8 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, umx_queue_done_fn done, void 
                 sp.n[7] = state_floats();
                 sp.count = TRACK_BEGIN_SPANS;
                 launch_track_begin(sp, st);
+                if (jb->levels) // ... and the set's record of what leaves (also on a restart: the job measures from zero again)
+                    (void)hipMemsetAsync(tb_.lev, 0, sizeof(umx_levels_acc), st);
             }
             nl = ln + 1;
         }

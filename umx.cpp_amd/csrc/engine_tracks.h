@@ -125,6 +125,57 @@ void umx_hip_ctx::track_encode(const TrackBufs &tb_, const umx_sample_io &io, in
     launch_pcm16_encode(n_host, s, d, count, first_frame, io.dither != 0, io.dither_seed, st);
 }
 
+// the set's record of what leaves (112 bytes, allocated once a job measures; the driver zeroes it with the accumulators)
+int umx_hip_ctx::track_levels_grow(TrackBufs &tb_)
+{
+    return tb_.lev ? UMX_OK : dalloc(&tb_.lev, 1, true);
+}
+
+// What every finished span of a job goes through behind its mix, on its way out: `count` frames of the first n_host of `src` from
+// frame src_start on, which are the frames from first_frame on of the caller's track.  They are measured (a job with levels), then
+// encoded into the set's int16 outputs (track_encode), or -- a rescaled job, whose span is the whole track, so that the record's
+// peaks are final -- encoded over the track's divisor, an fp32 output divided in place.  A job without levels or rescale: track_encode alone.
+void umx_hip_ctx::track_leave(const TrackJob &j, int n_host, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st)
+{
+    const TrackBufs &tb_ = *j.acc;
+    const bool s16 = j.io.out_format == UMX_SAMPLE_S16, rescale = j.clip_mode == UMX_CLIP_RESCALE;
+    if (!j.levels && !rescale)
+    {
+        if (s16)
+            track_encode(tb_, j.io, n_host, src, src_start, count, first_frame, st);
+        return;
+    }
+    const float2 *s[4] = {};
+    float2 *sw[4] = {};
+    uint32_t *d[4] = {};
+    for (int t = 0; t < n_host; ++t)
+    {
+        s[t] = sw[t] = reinterpret_cast<float2 *>(src[t]) + src_start;
+        d[t] = s16 ? tb_.out16[t] + first_frame : nullptr;
+    }
+    // (a rescaled int16 track: its encode counts what it clamps itself, with the divisor it forms)
+    launch_stem_levels(n_host, s, count, first_frame, s16 && !rescale, j.io.dither != 0, j.io.dither_seed, tb_.lev, st);
+    if (!rescale)
+    {
+        if (s16)
+            track_encode(tb_, j.io, n_host, src, src_start, count, first_frame, st);
+    }
+    else if (s16)
+        launch_pcm16_encode_rescaled(n_host, s, d, count, first_frame, j.io.dither != 0, j.io.dither_seed, tb_.lev, st);
+    else
+        launch_stem_rescale(n_host, sw, count, tb_.lev, st);
+}
+
+// the job's record to the host (its last launch has finished: the caller has waited for the job's last region), as the call reports it
+hipError_t umx_hip_ctx::track_levels_report(const TrackJob &j, int n_host, umx_levels &lv)
+{
+    umx_levels_acc acc;
+    const hipError_t e = hipMemcpy(&acc, j.acc->lev, sizeof acc, hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+        levels_report(acc, n_host, j.clip_mode == UMX_CLIP_RESCALE, lv);
+    return e;
+}
+
 // The track goes up segment by segment (round 6): a call needs the samples up to the end of its last segment, and the rest of a
 // pageable upload (14 GB/s: 15 ms for ten minutes of stereo) runs while the device is busy with the segments before it -- the
 // slots' streams do not wait for the null stream, and launches are queued ahead of the copy.
@@ -255,14 +306,21 @@ int umx_hip_ctx::track_call(const TrackLane *lanes, int nl, unsigned flags, cons
         hipLaunchKernelGGL(track_accumulate_kernel, dim3((nn[ln] + 255) / 256, 4), dim3(256), 0, st, tk, tb_.sumw, seg, rg.start, nn[ln], N);
         hipLaunchKernelGGL(track_normalise_kernel, dim3((rg.count + 255) / 256, 4), dim3(256), 0, st, tk, tb_.sumw, rg.start, rg.count);
         if (!j->by_region)
-            continue;
+        {
+            // a rescaled track is ONE region, behind its last segment's overlap-add (its divisor needs every peak)
+            if (!j->whole_region || (long long)rg.start + stride < j->L2)
+                continue;
+            rg.start = j->lead;
+            rg.count = j->length;
+        }
         if (mix)
             track_mix(*mix, tb_.out, (size_t)rg.start, tb_.in, (size_t)rg.start, rg.count, st);
-        if (j->io.out_format == UMX_SAMPLE_S16) // the region's frames of the caller's track, as they will leave (not over the
-        {                                       // accumulators: the next segment's overlap-add still reads its neighbours)
+        if (j->io.out_format == UMX_SAMPLE_S16 || j->levels) // the region's frames of the caller's track, as they will
+        {                                                    // leave (an int16 copy is not written over the accumulators: the next
+                                                             // segment's overlap-add still reads its neighbours)
             const long long lo = std::max<long long>(rg.start, j->lead), hi = std::min<long long>((long long)rg.start + rg.count, (long long)j->lead + j->length);
             if (hi > lo)
-                track_encode(tb_, j->io, mix ? mix->n_out : 4, tb_.out, (size_t)lo, (int)(hi - lo), lo - j->lead, st);
+                track_leave(*j, mix ? mix->n_out : 4, tb_.out, (size_t)lo, (int)(hi - lo), lo - j->lead, st);
         }
         if (hipEventCreateWithFlags(&rg.ready, hipEventDisableTiming) != hipSuccess)
         {
@@ -297,6 +355,13 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     }
     if (int rc = check_flags(rq.flags))
         return rc;
+    // a rescaled track measures for its divisor whether or not the caller wants the record
+    const bool rescale = rq.clip_mode == UMX_CLIP_RESCALE, measure = rq.levels || rescale;
+    if (measure && ensemble)
+    {
+        set_error("track: the shift ensemble does not offer levels or rescale");
+        return UMX_ERR_ARG;
+    }
     for (int ln = 0; ln < nt; ++ln)
         if (!track_job_ok(rq.audio[ln], length_in[ln], rq.shift_offset[ln], rq.out && !ensemble ? rq.out + n_host * ln : rq.out, n_host))
         {
@@ -358,7 +423,10 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         }
         j.audio = rq.audio[ln];
         j.io = rq.io;
-        j.by_region = !ensemble && !resampled[ln];
+        j.by_region = !ensemble && !resampled[ln] && !rescale;
+        j.clip_mode = rq.clip_mode;
+        j.levels = measure;
+        j.whole_region = rescale && !resampled[ln]; // (a resampled one leaves through leaves_whole below, behind its way back)
         L2max = std::max(L2max, j.L2);
         max_segs = std::max(max_segs, j.segs);
     }
@@ -373,6 +441,9 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
             return rc;
         if (int rc = track_pcm16_grow(trk[ln], rq.io, (size_t)length_in[ln], n_host)) // (nothing for an fp32 call)
             return rc;
+        if (measure)
+            if (int rc = track_levels_grow(trk[ln]))
+                return rc;
     }
     if (ensemble) // the mean of the lanes' stems: n44 frames
         if (int rc = grow_frames({{&ens_out[0], 2}, {&ens_out[1], 2}, {&ens_out[2], 2}, {&ens_out[3], 2}}, ens_cap, (size_t)length[0]))
@@ -388,6 +459,8 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         for (int t = 0; t < 4; ++t)
             UMX_HIP_CHECK(hipMemset(tb_.out[t], 0, sizeof(float) * 2 * frames));
         UMX_HIP_CHECK(hipMemset(tb_.sumw, 0, sizeof(float) * frames));
+        if (measure)
+            UMX_HIP_CHECK(hipMemset(tb_.lev, 0, sizeof(umx_levels_acc)));
     }
     // a resampled track goes up whole at its own rate, into a grow-only staging buffer, and is resampled straight into the padded
     // 44.1 kHz signal (track_upload_until then has nothing left to do for it)
@@ -490,10 +563,10 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
             cerr = launch_resample(rs_back[ln], rs_back_taps[ln], n_host, src, j.length, rs_stage[ln].out, length_in[ln], last_st);
             std::copy(rs_stage[ln].out, rs_stage[ln].out + 4, whole[ln]);
         }
-        if (rq.io.out_format == UMX_SAMPLE_S16 && cerr == hipSuccess) // at the caller's rate and length, frame 0 first
+        if (cerr == hipSuccess) // at the caller's rate and length, frame 0 first: measured, encoded, rescaled as the job says
         {
-            track_encode(*j.acc, rq.io, n_host, whole[ln], 0, length_in[ln], 0, last_st);
-            for (int t = 0; t < n_host; ++t)
+            track_leave(j, n_host, whole[ln], 0, length_in[ln], 0, last_st);
+            for (int t = 0; t < n_host && rq.io.out_format == UMX_SAMPLE_S16; ++t)
                 whole[ln][t] = reinterpret_cast<float *>(j.acc->out16[t]);
         }
         any_whole = true;
@@ -532,6 +605,10 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         for (int t = 0; t < n_host && whole[ln][0] && cerr == hipSuccess; ++t) // (an ensemble's one result: lane 0)
             cerr = hipMemcpy(rq.out[n_host * ln + t], whole[ln][t], (rq.io.out_format == UMX_SAMPLE_S16 ? sizeof(uint32_t) : sizeof(float) * 2) * (size_t)length_in[ln],
                              hipMemcpyDeviceToHost);
+    // every job's record, once: its last measuring launch is behind its last region, which the host has
+    umx_levels reports[LSTMB_MAX_TRACKS];
+    for (int ln = 0; ln < nt && rq.levels && cerr == hipSuccess; ++ln)
+        cerr = track_levels_report(job[ln], n_host, reports[ln]);
     if (cerr != hipSuccess)
     {
         set_error(hipGetErrorString(cerr));
@@ -540,6 +617,8 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     UMX_HIP_CHECK(hipGetLastError());
     if (int rc = umx_hip_sync(this)) // surfaces a persistent-kernel timeout
         return rc;
+    if (rq.levels) // (only what a run without a timeout measured is reported)
+        std::copy(reports, reports + nt, rq.levels);
     return UMX_OK;
 }
 

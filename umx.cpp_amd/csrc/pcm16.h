@@ -40,12 +40,18 @@ __host__ __device__ inline uint32_t pcm16_dither_key(uint32_t seed, int m, int c
 __host__ __device__ inline uint32_t pcm16_dither_word(uint32_t key, long long k) { return pcm16_hash(key ^ (uint32_t)k); }
 __host__ __device__ inline float pcm16_dither(uint32_t w) { return (((float)(w & 0xffffu) + (float)(w >> 16)) - 65535.0f) * (1.0f / 65536.0f); }
 
-__host__ __device__ inline int16_t pcm16_encode(float x, bool dither, uint32_t key, long long k)
+// the encode rule up to and including its rounding: r, before the NaN test and the clamp (levels.h counts the clamped samples from it)
+__host__ __device__ inline float pcm16_round(float x, bool dither, uint32_t key, long long k)
 {
     float v = x * 32767.0f;
     if (dither)
         v = v + pcm16_dither(pcm16_dither_word(key, k));
-    const float r = rintf(v);
+    return rintf(v);
+}
+
+__host__ __device__ inline int16_t pcm16_encode(float x, bool dither, uint32_t key, long long k)
+{
+    const float r = pcm16_round(x, dither, key, k);
     if (r != r)
         return 0;
     return (int16_t)(r < -32768.f ? -32768.f : r > 32767.f ? 32767.f : r);

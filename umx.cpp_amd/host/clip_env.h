@@ -1,0 +1,73 @@
+// clip_env.h -- UMX_CLIP and UMX_LEVELS of umx-cli and umx-batch: what happens to outputs beyond full scale, and whether the levels
+// of what was written are printed (output levels and clip handling; include/umx_hip.h).
+//   UMX_CLIP=clamp|rescale   clamp (the default, and unset or empty): today's files byte for byte -- a 16-bit PCM output clamps, a
+//                            float one keeps its samples beyond 1.0.  rescale (Demucs' --clip-mode rescale, per track instead of per
+//                            file): every output of a file is divided by max(1.01 * peak over the file's outputs, 1) on the device.
+//   UMX_LEVELS=1             one line per output file on stdout, measured on the device:
+//                            levels <file> peak=<%.9g> over_unity=<n> clipped=<n> nonfinite=<n> gain=<%.9g>
+// Both go with UMX_PCM16, UMX_MIX, UMX_TARGETS / UMX_RESIDUAL and UMX_RESAMPLE, through umx-batch's queue and its pass-by-pass loop;
+// not with UMX_SHIFTS > 1 or UMX_CLI_PER_SEGMENT (the shift ensemble and the per-segment calls do not offer them).
+#pragma once
+#include "../../include/umx_hip.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+struct umx_clip_choice
+{
+    int clip_mode = UMX_CLIP_CLAMP;
+    bool levels = false;
+    bool active() const { return clip_mode != UMX_CLIP_CLAMP || levels; } // false: the calls and the files of a run without the two
+};
+
+// false, with a message that names the variable, for a value outside the grammar above (nullptr: unset)
+inline bool umx_clip_parse(const char *clip, const char *levels, umx_clip_choice &c, std::string &err)
+{
+    c = umx_clip_choice();
+    if (clip && *clip)
+    {
+        if (!strcmp(clip, "rescale"))
+            c.clip_mode = UMX_CLIP_RESCALE;
+        else if (strcmp(clip, "clamp"))
+        {
+            err = std::string("UMX_CLIP: need clamp or rescale, got \"") + clip + "\"";
+            return false;
+        }
+    }
+    if (levels && *levels)
+    {
+        if (strcmp(levels, "0") && strcmp(levels, "1"))
+        {
+            err = std::string("UMX_LEVELS: need 0 or 1, got \"") + levels + "\"";
+            return false;
+        }
+        c.levels = levels[0] == '1';
+    }
+    return true;
+}
+
+// false: refused, message on stderr.  not_offered: the reason this run cannot take the two (nullptr: it can)
+inline bool umx_clip_from_env(umx_clip_choice &c, const char *not_offered)
+{
+    std::string err;
+    if (!umx_clip_parse(getenv("UMX_CLIP"), getenv("UMX_LEVELS"), c, err))
+    {
+        fprintf(stderr, "%s\n", err.c_str());
+        return false;
+    }
+    if (c.active() && not_offered)
+    {
+        fprintf(stderr, "UMX_CLIP / UMX_LEVELS: %s\n", not_offered);
+        return false;
+    }
+    return true;
+}
+
+// the line of output m of a track, written to `file`
+inline void umx_levels_print(const char *file, const umx_levels &lv, int m)
+{
+    printf("levels %s peak=%.9g over_unity=%llu clipped=%llu nonfinite=%llu gain=%.9g\n", file, (double)lv.peak[m], lv.over_unity[m], lv.clipped[m],
+           lv.nonfinite[m], (double)lv.gain);
+}

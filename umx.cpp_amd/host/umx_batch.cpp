@@ -13,7 +13,10 @@
 // UMX_MIX (as umx-cli, host/mix_env.h: the same matrix for every file, <out dir>/<wav stem>/<name>.wav and no target_*.wav),
 // UMX_PCM16 and UMX_PCM16_DITHER (as umx-cli, DESIGN 19: every output a 16-bit PCM WAV quantised on the device, through the queue and
 // the pass-by-pass loop alike; the files go up as int16 when ALL of them are 16-bit PCM -- a run has one input format -- else as fp32).
+// UMX_CLIP and UMX_LEVELS (as umx-cli; host/clip_env.h): rescale instead of clamp, and one `levels <file> ...` line per
+// file written, through the queue (umx_hip_separate_queue_levels) and the pass-by-pass loop (umx_hip_separate_tracks_levels) alike.
 #include "../../include/umx_host.h"
+#include "clip_env.h"
 #include "mix_env.h"
 #include "shifts_env.h"
 #include "targets_env.h"
@@ -47,6 +50,7 @@ struct FileJob
     int16_t *audio16 = nullptr; // UMX_PCM16 with 16-bit PCM files: the file's samples as they are
     std::vector<std::vector<float>> stems;
     std::vector<std::vector<int16_t>> stems16; // UMX_PCM16: the outputs as they are written
+    umx_levels levels = {};                    // UMX_CLIP / UMX_LEVELS: what the queue measured
 };
 struct BatchQueue
 {
@@ -108,6 +112,11 @@ struct BatchQueue
         q.unwritten.push_back(fj);
         q.cv.notify_all();
     }
+    static void done_levels(void *user, const umx_queue_job *job, const umx_levels *levels) // (valid during the callback only)
+    {
+        static_cast<FileJob *>(job->tag)->levels = *levels;
+        done(user, job);
+    }
 };
 
 int main(int argc, const char **argv)
@@ -154,6 +163,9 @@ int main(int argc, const char **argv)
         fprintf(stderr, "UMX_PCM16_DITHER: needs UMX_PCM16=1\n");
         return 1;
     }
+    umx_clip_choice clipc;
+    if (!umx_clip_from_env(clipc, nullptr))
+        return 1;
     const bool resample = env_int("UMX_RESAMPLE", 0) != 0;
     umx_sample_io io = {UMX_SAMPLE_F32, pcm16 ? UMX_SAMPLE_S16 : UMX_SAMPLE_F32, 0, 0};
     if (const char *seed = getenv("UMX_PCM16_DITHER"))
@@ -212,7 +224,7 @@ int main(int argc, const char **argv)
             names[f] = std::filesystem::path(argv[3 + f]).stem().string() + "_" + std::to_string(k);
     }
     // umx.cpp:75-96: the buffers of file f to its directory
-    auto write_file = [&](int f, float *const *bufs, int16_t *const *bufs16, int n, int rate_, char *err_) -> bool {
+    auto write_file = [&](int f, float *const *bufs, int16_t *const *bufs16, int n, int rate_, const umx_levels &lv, char *err_) -> bool {
         const std::filesystem::path dir = std::filesystem::path(out_dir) / names[f];
         std::error_code ec;
         std::filesystem::create_directories(dir, ec);
@@ -225,6 +237,8 @@ int main(int argc, const char **argv)
                 : resample ? umx_wav_write_f32_rate(p.c_str(), bufs[t], n, rate_, err_)
                            : umx_wav_write_f32(p.c_str(), bufs[t], n, err_))
                 return false;
+            if (clipc.levels)
+                umx_levels_print(p.c_str(), lv, t);
         }
         return true;
     };
@@ -289,7 +303,7 @@ int main(int argc, const char **argv)
                     bufs[t] = fj->stems[t].data();
                     bufs16[t] = fj->stems16[t].data();
                 }
-                const bool ok = write_file(fj->index, bufs, bufs16, fj->n, UMX_SAMPLE_RATE, werr);
+                const bool ok = write_file(fj->index, bufs, bufs16, fj->n, UMX_SAMPLE_RATE, fj->levels, werr);
                 std::lock_guard<std::mutex> lock(q.m);
                 q.unwritten.pop_front(); // (counted until it is written: the stems are in memory until then)
                 if (!ok && q.error.empty())
@@ -299,7 +313,9 @@ int main(int argc, const char **argv)
             }
         });
         const auto t0 = std::chrono::steady_clock::now();
-        const int qrc = pcm16 ? umx_hip_separate_queue_io(ctx, BatchQueue::next, BatchQueue::done, &q, mixc.n_out, mixed ? mixc.gains : nullptr, flags, &io)
+        const int qrc = clipc.active() ? umx_hip_separate_queue_levels(ctx, BatchQueue::next, BatchQueue::done_levels, &q, mixc.n_out,
+                                                                       mixed ? mixc.gains : nullptr, flags, &io, clipc.clip_mode)
+                        : pcm16 ? umx_hip_separate_queue_io(ctx, BatchQueue::next, BatchQueue::done, &q, mixc.n_out, mixed ? mixc.gains : nullptr, flags, &io)
                               : umx_hip_separate_queue(ctx, BatchQueue::next, BatchQueue::done, &q, mixc.n_out, mixed ? mixc.gains : nullptr, flags);
         wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         {
@@ -340,6 +356,8 @@ int main(int argc, const char **argv)
         std::vector<float *> out(per_file * nb);
         std::vector<const float *> in(nb);
         std::vector<int> rate(nb, UMX_SAMPLE_RATE);
+        std::vector<umx_levels> levels(nb);
+        std::vector<void *> out_io(per_file * nb); // (read as the formats say)
         for (int i = 0; i < nb; ++i)
         {
             int ch = 0;
@@ -361,10 +379,14 @@ int main(int argc, const char **argv)
                     stems[per_file * i + t].resize((size_t)2 * n[i]);
                 out[per_file * i + t] = stems[per_file * i + t].data();
                 out16[per_file * i + t] = stems16[per_file * i + t].data();
+                out_io[per_file * i + t] = pcm16 ? (void *)out16[per_file * i + t] : (void *)out[per_file * i + t];
             }
         }
         const auto t0 = std::chrono::steady_clock::now();
-        if (pcm16 ? umx_hip_separate_tracks_io(ctx, nb, in_io.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out,
+        if (clipc.active() ? umx_hip_separate_tracks_levels(ctx, nb, in_io.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out,
+                                                            mixed ? mixc.gains : nullptr, out_io.data(), flags, &io, clipc.clip_mode,
+                                                            clipc.levels ? levels.data() : nullptr, nullptr, nullptr)
+            : pcm16 ? umx_hip_separate_tracks_io(ctx, nb, in_io.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out,
                                                mixed ? mixc.gains : nullptr, reinterpret_cast<void *const *>(out16.data()), flags, &io, nullptr, nullptr)
             : mixed ? umx_hip_separate_tracks_mix(ctx, nb, in.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out, mixc.gains,
                                                 out.data(), flags, nullptr, nullptr)
@@ -377,7 +399,7 @@ int main(int argc, const char **argv)
         wall += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         for (int i = 0; i < nb; ++i)
         {
-            if (!write_file(f0 + i, &out[per_file * i], &out16[per_file * i], n[i], rate[i], err))
+            if (!write_file(f0 + i, &out[per_file * i], &out16[per_file * i], n[i], rate[i], levels[i], err))
             {
                 fprintf(stderr, "%s\n", err);
                 return 1;

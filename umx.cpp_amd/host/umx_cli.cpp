@@ -23,7 +23,11 @@
 //                    16-bit PCM WAVs under the same names, quantised on the device, and a 16-bit PCM input goes up as int16 (any other
 //                    encoding as fp32); UMX_PCM16_DITHER=<seed> adds TPDF dither with that seed.  Goes with UMX_RESAMPLE, UMX_TARGETS /
 //                    UMX_RESIDUAL, UMX_MIX and the other knobs; not with UMX_SHIFTS > 1 or UMX_CLI_PER_SEGMENT.  Unset: today's files
+//   UMX_CLIP=clamp|rescale, UMX_LEVELS=1   what happens to outputs beyond full scale, and one `levels <file> ...` line per file written
+//                    (umx_hip_separate_tracks_levels; host/clip_env.h); with and without UMX_PCM16 and the knobs it goes
+//                    with; not with UMX_SHIFTS > 1 or UMX_CLI_PER_SEGMENT.  Unset (or clamp, 0): today's files
 #include "../../include/umx_host.h"
+#include "clip_env.h"
 #include "mix_env.h"
 #include "shifts_env.h"
 #include "targets_env.h"
@@ -109,6 +113,12 @@ int main(int argc, const char **argv)
         fprintf(stderr, "UMX_PCM16_DITHER: needs UMX_PCM16=1\n");
         return 1;
     }
+    umx_clip_choice clipc;
+    if (!umx_clip_from_env(clipc, shifts > 1 || env_int("UMX_CLI_PER_SEGMENT", 0)
+                                      ? "the shift ensemble (UMX_SHIFTS > 1) and UMX_CLI_PER_SEGMENT=1 do not offer levels or rescale"
+                                      : nullptr))
+        return 1;
+    umx_levels levels = {};
     umx_sample_io io = {UMX_SAMPLE_F32, pcm16 ? UMX_SAMPLE_S16 : UMX_SAMPLE_F32, 0, 0};
     if (const char *seed = getenv("UMX_PCM16_DITHER"))
     {
@@ -195,15 +205,16 @@ int main(int argc, const char **argv)
             return 1;
         }
     }
-    else if (pcm16)
+    else if (pcm16 || clipc.active())
     {
+        // (clamp without levels IS umx_hip_separate_tracks_io)
         const int offset = env_int("UMX_SHIFT_OFFSET", -1) < 0 ? UMX_REFERENCE_SHIFT : env_int("UMX_SHIFT_OFFSET", -1);
         const void *in = io.in_format == UMX_SAMPLE_S16 ? (const void *)audio16 : (const void *)audio;
         void *out16[4];
         for (int t = 0; t < 4; ++t)
-            out16[t] = stems16[t].data();
-        if (umx_hip_separate_tracks_io(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out16,
-                                       hb.flags, &io, print_progress, nullptr))
+            out16[t] = pcm16 ? (void *)stems16[t].data() : (void *)stems[t].data();
+        if (umx_hip_separate_tracks_levels(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out16,
+                                           hb.flags, &io, clipc.clip_mode, clipc.levels ? &levels : nullptr, print_progress, nullptr))
         {
             fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
             return 1;
@@ -258,6 +269,8 @@ int main(int argc, const char **argv)
             fprintf(stderr, "%s\n", err);
             return 1;
         }
+        if (clipc.levels)
+            umx_levels_print(p.c_str(), levels, t);
     }
     umx_wav_free(audio);
     umx_wav_free_pcm16(audio16);
