@@ -447,7 +447,7 @@ int umx_hip_pcm16_encode_host(const float *x, int n_frames, int buffer, long lon
  *                    above is > 32767.f or < -32768.f, that is, where the clamp changed the value.  r includes the dither term when
  *                    dither is on and the rescale divisor when rescale is on; +-inf is counted, NaN is not (it is in nonfinite).
  *   All four are maxima or integer counts: they do not depend on how the track is cut into regions, which lane a job rides in, the
- *   queue, reset mode or a rerun after a timeout.  (A sum of squares has no order-independent exact form; it is not part of the record.)
+ *   queue, reset mode or a rerun after a timeout.  (A sum of squares has no such form unless it is tied to fixed hops: umx_loudness below.)
  *   rescale (UMX_CLIP_RESCALE): one divisor per track, common to all of its outputs (the stems still add up to the mixture over it;
  *   Demucs' rescale is per file).  P = the maximum of peak[m] over the outputs that leave; g = 1.01f * P, one fp32 product.  If P is
  *   not finite, or if !(g > 1.0f), the divisor is 1 and the output is, bit for bit, the clamp-mode output.  Otherwise every sample
@@ -500,6 +500,69 @@ int umx_hip_rescale_device(umx_hip_ctx *ctx, int n_buffers, float *const *bufs_d
 int umx_hip_levels_host(const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, float clip_divisor,
                         umx_levels_acc *acc);
 float umx_hip_rescale_gain(const float *peak, int n);
+/* Loudness of every output: ITU-R BS.1770-4 / EBU R128 integrated and momentary loudness, from K-weighted hop energies
+ * measured on the device where every output frame is final.  A sum of squares is made independent of regions, lanes, the queue and
+ * reset mode by tying it to fixed hops anchored at frame 0 of the caller's track and computing every hop in one fixed order.  The
+ * rules, to the bit; all arithmetic in double, the inputs the fp32 samples umx_levels measures (at the caller's rate, behind the mix,
+ * before any rescale and before any encode):
+ *   hop        hop = (rate + 5) / 10 frames, integer arithmetic.  Hop b of output m is the frames [b hop, (b + 1) hop) of the caller's
+ *              track; a last incomplete hop is not measured (BS.1770 measures no incomplete block): hops = length / hop.
+ *   K-weight   two biquads per rate, formed on the host in double from the analogue prototypes, as libebur128 (ebur128_init_filter) does:
+ *              shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / rate), Vh = 10^(G/20),
+ *                Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2; b = [(Vh + Vb K/Q + K^2)/a0, 2 (K^2 - Vh)/a0, (Vh - Vb K/Q + K^2)/a0],
+ *                a = [1, 2 (K^2 - 1)/a0, (1 - K/Q + K^2)/a0]
+ *              high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773; b = [1, -2, 1], a as above with this stage's K and Q
+ *              (at 48000 these are the seven coefficients of the BS.1770-4 table to 9e-16)
+ *   E[m][ch][b]  the sum over hop b's frames of the squared output of the cascade (shelf, then high-pass) of channel ch.  The cascade
+ *              starts from a ZERO state at frame max(0, b - 1) hop and runs sample by sample in transposed direct form II; per stage,
+ *              with state (s1, s2): u = fma(b1, x, s2); y = fma(b0, x, s1); s1 = fma(-a1, y, u); s2 = fma(-a2, y, b2 * x).  The squares
+ *              are added in frame order, E = fma(y, y, E).  One hop (100 ms) of warm-up stands for the filter's infinite history (the
+ *              slowest pole has decayed by e^-24 by then; hop 0 is exact, the standard's filter starts from rest too): against the
+ *              full-history filter every hop energy is within 1.2e-11 relative, integrated loudness within 2e-11 LU.  A hop is thus a
+ *              function of 2 hop samples and of nothing else; a NaN reaches two hops and stops.
+ *   blocks     block j is hops j .. j+3 (400 ms, 75 % overlap): P_j = sum over both channels (weights 1, 1) and the four hops of E,
+ *              over 4 hop; l_j = -0.691 + 10 log10 P_j.  Absolute gate: l_j > -70.  Relative gate: G = -0.691 + 10 log10(mean of P_j
+ *              over the absolutely gated blocks) - 10.  integrated = -0.691 + 10 log10(mean of P_j over the blocks with l_j > -70 and
+ *              l_j > G); momentary_max = the maximum of l_j over all blocks.  Comparisons are IEEE: a NaN block passes no gate and is no
+ *              maximum; an inf block passes the absolute gate and is the maximum (it puts G at inf, which no block is above:
+ *              integrated is then -INFINITY with gated 0, and momentary_max = inf says why).  With no block, or none gated in, both are -INFINITY.  `blocks` and `gated` are the counts.
+ * The shift ensemble, the multi-GPU driver (umx_mgpu.h) and the per-segment umx_hip_infer_* calls do not offer loudness. */
+typedef struct umx_loudness /* what a whole-track call reports per track */
+{
+    double integrated[4], momentary_max[4]; /* LUFS */
+    long long blocks[4], gated[4];
+    long long hops; /* length / hop: measured hops per channel */
+    int n_out;
+    int hop; /* frames */
+} umx_loudness;
+/* umx_hip_separate_tracks_levels with loudness: n_tracks records, or NULL; hop_energy: NULL, or per track NULL or a buffer of
+ * n_out * 2 * (length / hop) doubles that receives E, laid out [output][channel][hop] (the envelope, for activity detection).  The
+ * rate of a track is rate[i], 44100 when rate == NULL.  loudness == NULL and hop_energy == NULL IS the _levels call: the same
+ * launches, nothing allocated.  Otherwise one launch per finished region computes the hops that have become final (a track that
+ * leaves whole -- rescaled, or at another rate: one launch, before the divisor), and E comes back once, behind the last region.
+ * UMX_ERR_ARG, naming the reason and leaving the context usable, for the shift ensemble and for everything the _levels call refuses
+ * (a rate outside 8000 .. 192000 among it). */
+int umx_hip_separate_tracks_loudness(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                                     const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                                     const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,
+                                     double *const *hop_energy, void (*progress)(float, void *), void *progress_user);
+/* umx_hip_separate_queue_levels whose done callback also receives the job's loudness record and its hop energies
+ * (n_out * 2 * loudness->hops doubles, [output][channel][hop]); all three are valid during the callback only. */
+typedef void (*umx_queue_loudness_fn)(void *user, const umx_queue_job *job, const umx_levels *levels, const umx_loudness *loudness,
+                                      const double *hop_energy);
+int umx_hip_separate_queue_loudness(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_loudness_fn done, void *user, int n_out,
+                                    const float *gains, unsigned flags, const umx_sample_io *io, int clip_mode);
+/* the kernel on the caller's device buffers, queued on hip_stream: 1 .. 4 buffers of (2,n) interleaved fp32 (8-byte aligned), frame 0
+ * first; hops [first_hop, first_hop + n_hops) of each go to E_dev[(buffer * 2 + channel) * (n / hop) + b], and exactly those entries
+ * are written (n_hops == 0: none).  UMX_ERR_ARG for a rate outside 8000 .. 192000, n > 2^30 - 1 and hops beyond n / hop. */
+int umx_hip_kweight_hops_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, int rate, long long first_hop,
+                                long long n_hops, double *E_dev, void *hip_stream);
+/* the same rules on the host (no GPU, no context).  coeffs: b0 b1 b2 and 1 a1 a2 of the shelf (pb, pa) and the high-pass (rb, ra).
+ * hops_host: one buffer, E[channel * (n / hop) + b].  gate: one output's two channels, E[channel * hops + b]. */
+int umx_hip_kweight_coeffs(int rate, double pb[3], double pa[3], double rb[3], double ra[3]);
+int umx_hip_kweight_hops_host(const float *x, int n, int rate, long long first_hop, long long n_hops, double *E);
+int umx_hip_loudness_gate(const double *E, long long hops, int hop, double *integrated, double *momentary_max, long long *blocks,
+                          long long *gated);
 /* testing, host only: the fp32 tap table of a rate pair (taps[phase * K + d + D]; cap floats at most), its phase count L, taps
  * per phase K and first offset -D.  UMX_ERR_ARG for a bad rate or a too small cap (the sizes are still reported). */
 int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase,

@@ -120,6 +120,21 @@ class Levels(C.Structure):
 QUEUE_LEVELS_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJob), C.POINTER(Levels))
 
 
+class Loudness(C.Structure):
+    """include/umx_hip.h: umx_loudness, the BS.1770-4 / R128 loudness of a track's outputs"""
+    _fields_ = [("integrated", C.c_double * 4), ("momentary_max", C.c_double * 4), ("blocks", C.c_longlong * 4),
+                ("gated", C.c_longlong * 4), ("hops", C.c_longlong), ("n_out", C.c_int), ("hop", C.c_int)]
+
+    def as_dict(self):
+        n = self.n_out
+        return {"integrated": np.array(self.integrated[:n]), "momentary_max": np.array(self.momentary_max[:n]),
+                "blocks": list(self.blocks[:n]), "gated": list(self.gated[:n]), "hops": int(self.hops), "hop": int(self.hop)}
+
+
+_dp = C.POINTER(C.c_double)
+QUEUE_LOUDNESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJob), C.POINTER(Levels), C.POINTER(Loudness), _dp)
+
+
 class TensorView(C.Structure):
     """include/umx_hip.h: umx_tensor_view"""
     _fields_ = [("name", C.c_char_p), ("target", C.c_int), ("dtype", C.c_int), ("n_dims", C.c_int),
@@ -282,6 +297,17 @@ def hip_lib():
     lib.umx_hip_levels_host.argtypes = [_fp, C.c_int, C.c_int, C.c_longlong, C.POINTER(SampleIO), C.c_float, C.POINTER(LevelsAcc)]
     lib.umx_hip_rescale_gain.argtypes = [_fp, C.c_int]
     lib.umx_hip_rescale_gain.restype = C.c_float
+    lib.umx_hip_separate_tracks_loudness.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                     C.POINTER(C.c_int), C.c_int, _fp, C.POINTER(C.c_void_p), C.c_uint, C.POINTER(SampleIO),
+                                                     C.c_int, C.POINTER(Levels), C.POINTER(Loudness), C.POINTER(C.c_void_p), C.c_void_p,
+                                                     C.c_void_p]
+    lib.umx_hip_separate_queue_loudness.argtypes = [C.c_void_p, QUEUE_NEXT_FN, QUEUE_LOUDNESS_FN, C.c_void_p, C.c_int, _fp, C.c_uint,
+                                                    C.POINTER(SampleIO), C.c_int]
+    lib.umx_hip_kweight_hops_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_longlong, C.c_longlong,
+                                                C.c_void_p, C.c_void_p]
+    lib.umx_hip_kweight_coeffs.argtypes = [C.c_int, _dp, _dp, _dp, _dp]
+    lib.umx_hip_kweight_hops_host.argtypes = [_fp, C.c_int, C.c_int, C.c_longlong, C.c_longlong, _dp]
+    lib.umx_hip_loudness_gate.argtypes = [_dp, C.c_longlong, C.c_int, _dp, _dp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     _hip = lib
     return lib
 
@@ -322,7 +348,9 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_separate_tracks_io", "umx_hip_separate_queue_io", "umx_hip_pcm16_decode_device", "umx_hip_pcm16_encode_device",
                "umx_hip_pcm16_decode_host", "umx_hip_pcm16_encode_host",
                "umx_hip_separate_tracks_levels", "umx_hip_separate_queue_levels", "umx_hip_levels_device",
-               "umx_hip_pcm16_encode_rescaled_device", "umx_hip_rescale_device", "umx_hip_levels_host", "umx_hip_rescale_gain"]
+               "umx_hip_pcm16_encode_rescaled_device", "umx_hip_rescale_device", "umx_hip_levels_host", "umx_hip_rescale_gain",
+               "umx_hip_separate_tracks_loudness", "umx_hip_separate_queue_loudness", "umx_hip_kweight_hops_device",
+               "umx_hip_kweight_coeffs", "umx_hip_kweight_hops_host", "umx_hip_loudness_gate"]
 
 
 def sample_io(in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None):
@@ -369,6 +397,41 @@ def rescale_gain(peaks):
     """umx_hip_rescale_gain: the divisor of a track whose outputs peak at `peaks` (1: nothing is divided), as float32 (no GPU)."""
     p = np.ascontiguousarray(np.atleast_1d(np.asarray(peaks, np.float32)))
     return np.float32(hip_lib().umx_hip_rescale_gain(p.ctypes.data_as(_fp), p.size))
+
+
+def kweight_coeffs(rate):
+    """umx_hip_kweight_coeffs: BS.1770-4's K-weighting at `rate` -> (pb, pa, rb, ra), float64 triples: b and [1, a1, a2] of the shelf
+    and of the high-pass stage (no GPU)."""
+    c = [(C.c_double * 3)() for _ in range(4)]
+    rc = hip_lib().umx_hip_kweight_coeffs(int(rate), *c)
+    if rc != UMX_OK:
+        raise UmxError(rc, "umx_hip_kweight_coeffs")
+    return tuple(np.array(list(x), np.float64) for x in c)
+
+
+def kweight_hops_host(x, rate, first_hop=0, n_hops=None):
+    """umx_hip_kweight_hops_host: the K-weighted hop energies of a (2,n) float32 array by the rule of DESIGN 21 -> (2, n // hop)
+    float64; hops outside [first_hop, first_hop + n_hops) stay NaN (no GPU)."""
+    a = np.ascontiguousarray(np.asarray(x, np.float32).T)
+    hops = a.shape[0] // ((int(rate) + 5) // 10)
+    n_hops = hops - first_hop if n_hops is None else n_hops
+    E = np.full((2, hops), np.nan)
+    rc = hip_lib().umx_hip_kweight_hops_host(a.ctypes.data_as(_fp), a.shape[0], int(rate), int(first_hop), int(n_hops), E.ctypes.data_as(_dp))
+    if rc != UMX_OK:
+        raise UmxError(rc, "umx_hip_kweight_hops_host")
+    return E
+
+
+def loudness_gate(E, hop):
+    """umx_hip_loudness_gate: blocks and gates over one output's hop energies E (2, hops) -> (integrated LUFS, momentary_max LUFS,
+    blocks, gated) (no GPU)."""
+    E = np.ascontiguousarray(np.asarray(E, np.float64))
+    assert E.ndim == 2 and E.shape[0] == 2
+    i, m, b, g = C.c_double(), C.c_double(), C.c_longlong(), C.c_longlong()
+    rc = hip_lib().umx_hip_loudness_gate(E.ctypes.data_as(_dp), E.shape[1], int(hop), C.byref(i), C.byref(m), C.byref(b), C.byref(g))
+    if rc != UMX_OK:
+        raise UmxError(rc, "umx_hip_loudness_gate")
+    return i.value, m.value, b.value, g.value
 
 
 def resampled_length(n, rate_in, rate_out):
@@ -773,6 +836,45 @@ class Engine:
                                                             None, None))
         return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)], (list(lv) if levels else None)
 
+    # --- loudness of every output: K-weighted hop energies measured on the device, blocks and gates formed on the host ---
+    def separate_many_loudness(self, waves, clip=CLIP_CLAMP, io=None, flags=0, shift_offsets=None, rates=None, gains=None, levels=True,
+                               loudness=True, envelopes=True):
+        """umx_hip_separate_tracks_loudness: separate_many_levels() -> (outputs, [Levels per track], [Loudness per track], [(n_out, 2,
+        hops) float64 hop energies per track]); levels / loudness / envelopes = False pass NULL and return None for them."""
+        nt = len(waves)
+        io = sample_io() if io is None else io
+        n_out, g = (4, None) if gains is None else _mix_gains(gains)
+        tin = np.int16 if io.in_format == SAMPLE_S16 else np.float32
+        tout = np.int16 if io.out_format == SAMPLE_S16 else np.float32
+        ins = [np.ascontiguousarray(np.asarray(w, tin).T).ravel() for w in waves]
+        Ls = [np.asarray(w).shape[1] for w in waves]
+        n_host = min(max(n_out, 0), MAX_MIX_OUTPUTS)
+        outs = [[np.empty(2 * L, tout) for _ in range(n_host)] for L in Ls]
+        a = (C.c_void_p * nt)(*[x.ctypes.data for x in ins])
+        o = (C.c_void_p * max(1, sum(len(t) for t in outs)))(*[x.ctypes.data for t in outs for x in t])
+        sh = (C.c_int * nt)(*[(-1 if s is None else s) for s in (shift_offsets or [None] * nt)])
+        rt = None if rates is None else (C.c_int * nt)(*[int(r) for r in rates])
+        lv = (Levels * nt)() if levels else None
+        ld = (Loudness * nt)() if loudness else None
+        env = ep = None
+        if envelopes:  # (a rate the call will refuse: any size does)
+            hops = [L // max(1, ((44100 if rates is None else int(r)) + 5) // 10) for L, r in zip(Ls, rates or [44100] * nt)]
+            env = [np.full((n_host, 2, h), np.nan) for h in hops]
+            ep = (C.c_void_p * nt)(*[e.ctypes.data if e.size else None for e in env])
+        self._check(self.lib.umx_hip_separate_tracks_loudness(self.h, nt, a, (C.c_int * nt)(*Ls), rt, sh, n_out,
+                                                              None if g is None else g.ctypes.data_as(_fp), o, flags, C.byref(io), int(clip), lv,
+                                                              ld, ep, None, None))
+        return ([[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)], (list(lv) if levels else None),
+                (list(ld) if loudness else None), env)
+
+    def kweight_hops_device(self, in_ptrs, n, rate, E_ptr, first_hop=0, n_hops=None, hip_stream=None):
+        """umx_hip_kweight_hops_device: hops [first_hop, first_hop + n_hops) of 1 .. 4 device buffers (2,n) interleaved fp32 into the
+        float64 array [buffer][channel][n // hop] at device address E_ptr."""
+        nb = len(in_ptrs)
+        hops = int(n) // max(1, (int(rate) + 5) // 10)
+        self._check(self.lib.umx_hip_kweight_hops_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(rate), int(first_hop),
+                                                         int(hops - first_hop if n_hops is None else n_hops), C.c_void_p(E_ptr), hip_stream))
+
     def levels_device(self, in_ptrs, n, acc_ptr, first_frame=0, io=None, hip_stream=None):
         """umx_hip_levels_device: 1 .. 4 device buffers (2,n) interleaved fp32 measured into the umx_levels_acc at device address acc_ptr."""
         nb = len(in_ptrs)
@@ -806,11 +908,12 @@ class Engine:
                                                          (C.c_void_p * nb)(*out_ptrs), hip_stream))
 
     # --- the track queue: more tracks than lanes, a lane refilled with the next track the moment one ends ---
-    def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None, io=None, clip=None, levels=False):
+    def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None, io=None, clip=None, levels=False, loudness=False):
         """umx_hip_separate_queue: list of (2,L_i) -> list of [4 x (2,L_i)] (mix: an (n_out, 5) gain matrix -> n_out x (2,L_i)), every
         job bit for bit what separate() / separate_mix() returns for it alone on this engine; the jobs are handed out in list order.
         io: a SampleIO (sample_io()) -> umx_hip_separate_queue_io, int16 arrays in and / or out as it says.
-        clip (CLIP_CLAMP / CLIP_RESCALE) or levels=True -> umx_hip_separate_queue_levels: returns (outputs, [Levels per job])."""
+        clip (CLIP_CLAMP / CLIP_RESCALE) or levels=True -> umx_hip_separate_queue_levels: returns (outputs, [Levels per job]).
+        loudness=True -> umx_hip_separate_queue_loudness: returns (outputs, [Levels], [Loudness], [(n_out, 2, hops) float64])."""
         nj = len(waves)
         n_out, g = (4, None) if mix is None else _mix_gains(mix)
         tin = np.int16 if io is not None and io.in_format == SAMPLE_S16 else np.float32
@@ -836,6 +939,21 @@ class Engine:
         def _done(_user, job):
             state["done"].append(int(job[0].tag) - 1)
 
+        if loudness:
+            got, loud, env = [None] * nj, [None] * nj, [None] * nj
+
+            def _done_loudness(_user, job, lv, ld, e):
+                _done(_user, job)
+                j = int(job[0].tag) - 1
+                got[j], loud[j] = Levels.from_buffer_copy(lv[0]), Loudness.from_buffer_copy(ld[0])  # (valid during the callback only)
+                h = int(loud[j].hops)
+                env[j] = (np.ctypeslib.as_array(e, shape=(n_out * 2 * h,)).copy() if h else np.zeros(0)).reshape(n_out, 2, h)
+
+            self._check(self.lib.umx_hip_separate_queue_loudness(self.h, QUEUE_NEXT_FN(_next), QUEUE_LOUDNESS_FN(_done_loudness), None, n_out,
+                                                                 None if g is None else g.ctypes.data_as(_fp), flags,
+                                                                 None if io is None else C.byref(io), int(clip or CLIP_CLAMP)))
+            assert sorted(state["done"]) == list(range(nj)), state
+            return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)], got, loud, env
         if clip is not None or levels:
             got = [None] * nj
 

@@ -43,6 +43,7 @@
 #include "stem_mix.h"
 #include "pcm16.h"
 #include "levels.h"
+#include "loudness.h"
 #include "gate_debug.h"
 
 using namespace umx;
@@ -579,6 +580,8 @@ struct umx_hip_ctx
         umx_sample_io io = {};        // pcm16.h, DESIGN 19: how `audio` and `out` are read (UMX_SAMPLE_S16: int16 frames behind the float pointers)
         int clip_mode = UMX_CLIP_CLAMP; // levels.h, DESIGN 20: UMX_CLIP_RESCALE: every track leaves whole, over its common divisor
         umx_levels *levels = nullptr; // n_tracks records of what left, or nullptr: not wanted
+        umx_loudness *loudness = nullptr; // loudness.h, DESIGN 21: n_tracks records, or nullptr
+        double *const *hop_energy = nullptr; // per track nullptr or room for its hop energies; either of the two: the tracks are measured
     };
     int tracks(const TrackRequest &rq);
     int tracks_once(const TrackRequest &rq);
@@ -601,6 +604,8 @@ struct umx_hip_ctx
         size_t cap_in16 = 0, cap_out16[4] = {};
         hipEvent_t in16_ev = nullptr; // behind the most recent decode out of in16 (track_upload_until): every call that reads `in` waits for it
         umx_levels_acc *lev = nullptr; // DESIGN 20, only once a job measures: the record of what leaves, zeroed with the accumulators
+        double *hopE = nullptr;        // DESIGN 21, only once a job measures loudness: its hop energies [output][channel][hop], grow-only,
+        size_t cap_hopE = 0;           // zeroed with the accumulators (cap: doubles)
     };
     std::vector<TrackBufs> trk;
     hipEvent_t trk_acc_ev[kMaxSlots] = {}; // per slot: behind the overlap-add of the last call that ran in it
@@ -619,6 +624,11 @@ struct umx_hip_ctx
         bool levels = false;          // what leaves is measured into acc->lev
         bool whole_region = false;    // not by_region, and track_call itself finishes it behind its last segment as ONE region: the
                                       // frames [lead, lead + length) (a rescaled track at 44.1 kHz)
+        // the K-weighted hop energies of what leaves go to acc->hopE
+        bool loudness = false;
+        int loud_rate = 0;            // the caller's rate: hop = kweight_hop(loud_rate) frames
+        long long loud_hops = 0;      // hops of the caller's track (its length at that rate / hop)
+        long long hops_done = 0;      // hops already launched (a restart begins again at 0)
     };
     struct TrackLane // a lane of one call: its job (nullptr: idle) and the padded frame at which its segment starts
     {
@@ -667,8 +677,10 @@ struct umx_hip_ctx
     void track_encode(const TrackBufs &tb_, const umx_sample_io &io, int n_host, float *const src[4], size_t src_start, int count,
                       long long first_frame, hipStream_t st);
     int track_levels_grow(TrackBufs &tb_);
-    void track_leave(const TrackJob &j, int n_host, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st);
+    void track_leave(TrackJob &j, int n_host, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st);
     hipError_t track_levels_report(const TrackJob &j, int n_host, umx_levels &lv);
+    int track_loudness_grow(TrackBufs &tb_, TrackJob &j, int rate, int length_at_rate, int n_host);
+    hipError_t track_loudness_report(const TrackJob &j, int n_host, std::vector<double> &E, umx_loudness &ld);
     hipError_t track_upload_until(TrackJob &j, long long padded_end, hipStream_t st);
     void track_mix(const MixSpec &mix, float *const stems[4], size_t stem_start, const float *in, size_t in_start, int count, hipStream_t st);
     hipError_t track_region_download(const TrackRegion &r, int n_host, float *const *out_host);
@@ -680,8 +692,9 @@ struct umx_hip_ctx
     {
         umx_queue_done_fn plain = nullptr;
         umx_queue_levels_fn with_levels = nullptr;
+        umx_queue_loudness_fn with_loudness = nullptr; // levels, the loudness record and the hop energies
         int clip_mode = UMX_CLIP_CLAMP;
-        bool measures() const { return with_levels != nullptr; }
+        bool measures() const { return with_levels != nullptr || with_loudness != nullptr; }
     };
     int queue(umx_queue_next_fn next, const QueueDone &done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io);
     int queue_run(umx_queue_next_fn next, const QueueDone &done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io);

@@ -689,6 +689,116 @@ float umx_hip_rescale_gain(const float *peak, int n)
     return levels_divisor(p);
 }
 
+// ---------------------------------------------------------------- loudness of every output (loudness.h)
+// loudness == NULL and hop_energy == NULL: the request of umx_hip_separate_tracks_levels, field for field
+int umx_hip_separate_tracks_loudness(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                                     const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                                     const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,
+                                     double *const *hop_energy, void (*progress)(float, void *), void *progress_user)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!sample_io_checked(ctx, io) || !clip_mode_checked(ctx, clip_mode))
+        return UMX_ERR_ARG;
+    MixSpec spec;
+    if (gains && !mix_checked(ctx, n_out, gains, spec))
+        return UMX_ERR_ARG;
+    umx_hip_ctx::TrackRequest rq = {n_tracks, reinterpret_cast<const float *const *>(audio_host), length, rate, shift_offset,
+                                    reinterpret_cast<float *const *>(out_host), flags, progress, progress_user};
+    rq.mix = gains ? &spec : nullptr;
+    if (io)
+        rq.io = *io;
+    rq.clip_mode = clip_mode;
+    rq.levels = levels;
+    rq.loudness = loudness;
+    rq.hop_energy = hop_energy;
+    return ctx->tracks(rq);
+}
+
+int umx_hip_separate_queue_loudness(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_loudness_fn done, void *user, int n_out,
+                                    const float *gains, unsigned flags, const umx_sample_io *io, int clip_mode)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!sample_io_checked(ctx, io) || !clip_mode_checked(ctx, clip_mode))
+        return UMX_ERR_ARG;
+    MixSpec spec;
+    if (gains && !mix_checked(ctx, n_out, gains, spec))
+        return UMX_ERR_ARG;
+    umx_hip_ctx::QueueDone qd;
+    qd.with_loudness = done;
+    qd.clip_mode = clip_mode;
+    return ctx->queue(next, qd, user, gains ? &spec : nullptr, flags, io ? *io : umx_sample_io{});
+}
+
+int umx_hip_kweight_hops_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, int rate, long long first_hop,
+                                long long n_hops, double *E_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!kweight_rate_ok(rate))
+    {
+        ctx->set_error("k-weighted hops: sample rate outside 8000 .. 192000 Hz");
+        return UMX_ERR_ARG;
+    }
+    const void *in[4] = {};
+    if (!levels_buffers(ctx, "k-weighted hops", n_buffers, reinterpret_cast<const void *const *>(in_dev), n, 0, in))
+        return UMX_ERR_ARG;
+    const int hop = kweight_hop(rate);
+    const long long hops_total = n / hop;
+    if (!E_dev || n > 0x7fffffff / 2 || first_hop < 0 || n_hops < 0 || first_hop > hops_total || n_hops > hops_total - first_hop)
+    {
+        ctx->set_error("k-weighted hops: need E, n <= 2^30 - 1 and 0 <= first_hop, first_hop + n_hops <= n / hop");
+        return UMX_ERR_ARG;
+    }
+    const float2 *src[4] = {};
+    for (int b = 0; b < n_buffers; ++b)
+        src[b] = static_cast<const float2 *>(in[b]);
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    launch_kweight_hops(n_buffers, src, kweight_coeffs(rate), hop, hops_total, first_hop, n_hops, E_dev, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+
+int umx_hip_kweight_coeffs(int rate, double pb[3], double pa[3], double rb[3], double ra[3])
+{
+    if (!kweight_rate_ok(rate) || !pb || !pa || !rb || !ra)
+        return UMX_ERR_ARG;
+    const KWeight k = kweight_coeffs(rate);
+    pa[0] = ra[0] = 1.0;
+    for (int i = 0; i < 3; ++i)
+    {
+        pb[i] = k.pb[i];
+        rb[i] = k.rb[i];
+    }
+    for (int i = 0; i < 2; ++i)
+    {
+        pa[1 + i] = k.pa[i];
+        ra[1 + i] = k.ra[i];
+    }
+    return UMX_OK;
+}
+
+int umx_hip_kweight_hops_host(const float *x, int n, int rate, long long first_hop, long long n_hops, double *E)
+{
+    if (!x || !E || n < 1 || !kweight_rate_ok(rate))
+        return UMX_ERR_ARG;
+    const long long hops_total = n / kweight_hop(rate);
+    if (first_hop < 0 || n_hops < 0 || first_hop > hops_total || n_hops > hops_total - first_hop)
+        return UMX_ERR_ARG;
+    kweight_hops_host(x, n, rate, first_hop, n_hops, E);
+    return UMX_OK;
+}
+
+int umx_hip_loudness_gate(const double *E, long long hops, int hop, double *integrated, double *momentary_max, long long *blocks,
+                          long long *gated)
+{
+    if ((!E && hops > 0) || hops < 0 || hop < 1 || !integrated || !momentary_max || !blocks || !gated)
+        return UMX_ERR_ARG;
+    loudness_gate(E, hops, hop, *integrated, *momentary_max, *blocks, *gated);
+    return UMX_OK;
+}
+
 int umx_hip_queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_out, int *first_call_out, int *n_calls_out)
 {
     return queue_plan(n_lanes, n_jobs, seg_count, lane_out, first_call_out, n_calls_out);

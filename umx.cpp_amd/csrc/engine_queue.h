@@ -69,7 +69,7 @@ int queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_out, int
 
 int umx_hip_ctx::queue(umx_queue_next_fn next, const QueueDone &done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io)
 {
-    if (!next || (!done.plain && !done.with_levels))
+    if (!next || (!done.plain && !done.with_levels && !done.with_loudness))
     {
         set_error("queue: need the next and the done callback");
         return UMX_ERR_ARG;
@@ -150,6 +150,7 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
         for (Job *jb : redo)
         {
             jb->uploaded = 0;
+            jb->hops_done = 0; // (its hop energies are zeroed with its accumulators and measured again)
             jb->regions_left = jb->by_region ? jb->segs : 1;
         }
         for (int ln = 0; ln < B; ++ln)
@@ -208,15 +209,22 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
         }
         for (Job *jb : finished)
         {
-            if (done.with_levels) // the job's record, behind its last region
+            if (done.measures()) // the job's records, behind its last region
             {
                 umx_levels lv;
-                if ((e = track_levels_report(*jb, n_host, lv)) != hipSuccess)
+                umx_loudness ld;
+                std::vector<double> hopE;
+                if ((e = track_levels_report(*jb, n_host, lv)) == hipSuccess && done.with_loudness)
+                    e = track_loudness_report(*jb, n_host, hopE, ld);
+                if (e != hipSuccess)
                 {
                     set_error(std::string("queue: reading a job's levels failed: ") + hipGetErrorString(e));
                     return UMX_ERR_HIP;
                 }
-                done.with_levels(user, &jb->job, &lv);
+                if (done.with_loudness)
+                    done.with_loudness(user, &jb->job, &lv, &ld, hopE.data());
+                else
+                    done.with_levels(user, &jb->job, &lv);
             }
             else
                 done.plain(user, &jb->job);
@@ -298,6 +306,9 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
                 if (measure)
                     if (int rc = track_levels_grow(qpool[set]))
                         return fail(rc);
+                if (done.with_loudness) // (a queue's jobs are at 44.1 kHz)
+                    if (int rc = track_loudness_grow(qpool[set], tj, RS_MODEL_RATE, tj.length, n_host))
+                        return fail(rc);
                 tj.audio = j.audio;
                 tj.io = io;
                 tj.clip_mode = done.clip_mode;
@@ -365,6 +376,8 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
                 launch_track_begin(sp, st);
                 if (jb->levels) // ... and the set's record of what leaves (also on a restart: the job measures from zero again)
                     (void)hipMemsetAsync(tb_.lev, 0, sizeof(umx_levels_acc), st);
+                if (jb->loudness) // ... and its hop energies
+                    (void)hipMemsetAsync(tb_.hopE, 0, sizeof(double) * std::max<size_t>(1, (size_t)n_host * 2 * (size_t)jb->loud_hops), st);
             }
             nl = ln + 1;
         }

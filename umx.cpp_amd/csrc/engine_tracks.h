@@ -135,10 +135,26 @@ int umx_hip_ctx::track_levels_grow(TrackBufs &tb_)
 // frame src_start on, which are the frames from first_frame on of the caller's track.  They are measured (a job with levels), then
 // encoded into the set's int16 outputs (track_encode), or -- a rescaled job, whose span is the whole track, so that the record's
 // peaks are final -- encoded over the track's divisor, an fp32 output divided in place.  A job without levels or rescale: track_encode alone.
-void umx_hip_ctx::track_leave(const TrackJob &j, int n_host, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st)
+// A job with loudness: first of all, and before any divisor, the hops that these frames complete are launched -- hop b once
+// frame (b + 1) hop - 1 is final.  Their warm-up reads frames of the spans before this one: those are still in `src`, at their frame
+// numbers (the int16 copy goes elsewhere, a mix was written in place before its span left), so frame 0 is at src_start - first_frame.
+void umx_hip_ctx::track_leave(TrackJob &j, int n_host, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st)
 {
     const TrackBufs &tb_ = *j.acc;
     const bool s16 = j.io.out_format == UMX_SAMPLE_S16, rescale = j.clip_mode == UMX_CLIP_RESCALE;
+    if (j.loudness)
+    {
+        const int hop = kweight_hop(j.loud_rate);
+        const long long final_hops = std::min<long long>((first_frame + count) / hop, j.loud_hops);
+        if (final_hops > j.hops_done)
+        {
+            const float2 *s0[4] = {};
+            for (int t = 0; t < n_host; ++t)
+                s0[t] = reinterpret_cast<const float2 *>(src[t]) + src_start - first_frame;
+            launch_kweight_hops(n_host, s0, kweight_coeffs(j.loud_rate), hop, j.loud_hops, j.hops_done, final_hops - j.hops_done, tb_.hopE, st);
+            j.hops_done = final_hops;
+        }
+    }
     if (!j.levels && !rescale)
     {
         if (s16)
@@ -173,6 +189,50 @@ hipError_t umx_hip_ctx::track_levels_report(const TrackJob &j, int n_host, umx_l
     const hipError_t e = hipMemcpy(&acc, j.acc->lev, sizeof acc, hipMemcpyDeviceToHost);
     if (e == hipSuccess)
         levels_report(acc, n_host, j.clip_mode == UMX_CLIP_RESCALE, lv);
+    return e;
+}
+
+// the job measures loudness at the caller's `rate`, over its length_at_rate frames there; the set's hop energies
+// (n_host x 2 x hops doubles, grow-only, allocated once a job asks; the driver zeroes them with the accumulators)
+int umx_hip_ctx::track_loudness_grow(TrackBufs &tb_, TrackJob &j, int rate, int length_at_rate, int n_host)
+{
+    if (!kweight_rate_ok(rate))
+    {
+        set_error("loudness: sample rate outside 8000 .. 192000 Hz");
+        return UMX_ERR_ARG;
+    }
+    if (length_at_rate > 0x7fffffff / 2) // (the kernel counts frames in an int, with room for a workgroup's rows beyond the last hop)
+    {
+        set_error("loudness: track too long");
+        return UMX_ERR_ARG;
+    }
+    j.loudness = true;
+    j.loud_rate = rate;
+    j.loud_hops = length_at_rate / kweight_hop(rate);
+    j.hops_done = 0;
+    const size_t want = std::max<size_t>(1, (size_t)n_host * 2 * (size_t)j.loud_hops);
+    if (want <= tb_.cap_hopE)
+        return UMX_OK;
+    if (tb_.hopE)
+    {
+        allocs.erase(std::find(allocs.begin(), allocs.end(), (void *)tb_.hopE));
+        (void)hipFree(tb_.hopE);
+        tb_.hopE = nullptr;
+    }
+    tb_.cap_hopE = 0;
+    if (int rc = dalloc(&tb_.hopE, want + want / 8, false))
+        return rc;
+    tb_.cap_hopE = want + want / 8;
+    return UMX_OK;
+}
+
+// the job's hop energies to the host (its last launch has finished, as for track_levels_report) and the record formed from them
+hipError_t umx_hip_ctx::track_loudness_report(const TrackJob &j, int n_host, std::vector<double> &E, umx_loudness &ld)
+{
+    E.assign((size_t)n_host * 2 * (size_t)j.loud_hops, 0.0);
+    const hipError_t e = E.empty() ? hipSuccess : hipMemcpy(E.data(), j.acc->hopE, sizeof(double) * E.size(), hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+        loudness_report(E.data(), j.loud_hops, kweight_hop(j.loud_rate), n_host, ld);
     return e;
 }
 
@@ -315,7 +375,7 @@ int umx_hip_ctx::track_call(const TrackLane *lanes, int nl, unsigned flags, cons
         }
         if (mix)
             track_mix(*mix, tb_.out, (size_t)rg.start, tb_.in, (size_t)rg.start, rg.count, st);
-        if (j->io.out_format == UMX_SAMPLE_S16 || j->levels) // the region's frames of the caller's track, as they will
+        if (j->io.out_format == UMX_SAMPLE_S16 || j->levels || j->loudness) // the region's frames of the caller's track, as they will
         {                                                    // leave (an int16 copy is not written over the accumulators: the next
                                                              // segment's overlap-add still reads its neighbours)
             const long long lo = std::max<long long>(rg.start, j->lead), hi = std::min<long long>((long long)rg.start + rg.count, (long long)j->lead + j->length);
@@ -360,6 +420,13 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     if (measure && ensemble)
     {
         set_error("track: the shift ensemble does not offer levels or rescale");
+        return UMX_ERR_ARG;
+    }
+    // the tracks' hop energies are measured when the caller wants the records or the energies themselves
+    const bool loud = rq.loudness || rq.hop_energy;
+    if (loud && ensemble)
+    {
+        set_error("track: the shift ensemble does not offer loudness");
         return UMX_ERR_ARG;
     }
     for (int ln = 0; ln < nt; ++ln)
@@ -444,6 +511,9 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         if (measure)
             if (int rc = track_levels_grow(trk[ln]))
                 return rc;
+        if (loud)
+            if (int rc = track_loudness_grow(trk[ln], job[ln], rq.rate ? rq.rate[ln] : RS_MODEL_RATE, length_in[ln], n_host))
+                return rc;
     }
     if (ensemble) // the mean of the lanes' stems: n44 frames
         if (int rc = grow_frames({{&ens_out[0], 2}, {&ens_out[1], 2}, {&ens_out[2], 2}, {&ens_out[3], 2}}, ens_cap, (size_t)length[0]))
@@ -461,6 +531,8 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         UMX_HIP_CHECK(hipMemset(tb_.sumw, 0, sizeof(float) * frames));
         if (measure)
             UMX_HIP_CHECK(hipMemset(tb_.lev, 0, sizeof(umx_levels_acc)));
+        if (loud)
+            UMX_HIP_CHECK(hipMemset(tb_.hopE, 0, sizeof(double) * std::max<size_t>(1, (size_t)n_host * 2 * (size_t)job[ln].loud_hops)));
     }
     // a resampled track goes up whole at its own rate, into a grow-only staging buffer, and is resampled straight into the padded
     // 44.1 kHz signal (track_upload_until then has nothing left to do for it)
@@ -552,7 +624,7 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     float *whole[LSTMB_MAX_TRACKS][4] = {};
     bool any_whole = false;
     auto leaves_whole = [&](int ln, float *const stems[4], size_t start) {
-        const TrackJob &j = job[ln];
+        TrackJob &j = job[ln];
         if (mix)
             track_mix(*mix, stems, start, j.acc->in, (size_t)j.lead, j.length, last_st);
         const float *src[4];
@@ -609,6 +681,11 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     umx_levels reports[LSTMB_MAX_TRACKS];
     for (int ln = 0; ln < nt && rq.levels && cerr == hipSuccess; ++ln)
         cerr = track_levels_report(job[ln], n_host, reports[ln]);
+    // and its hop energies, once, from which the host forms the loudness record
+    umx_loudness loud_reports[LSTMB_MAX_TRACKS];
+    std::vector<double> hopE[LSTMB_MAX_TRACKS];
+    for (int ln = 0; ln < nt && loud && cerr == hipSuccess; ++ln)
+        cerr = track_loudness_report(job[ln], n_host, hopE[ln], loud_reports[ln]);
     if (cerr != hipSuccess)
     {
         set_error(hipGetErrorString(cerr));
@@ -619,6 +696,11 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         return rc;
     if (rq.levels) // (only what a run without a timeout measured is reported)
         std::copy(reports, reports + nt, rq.levels);
+    if (rq.loudness)
+        std::copy(loud_reports, loud_reports + nt, rq.loudness);
+    for (int ln = 0; ln < nt && rq.hop_energy; ++ln)
+        if (rq.hop_energy[ln])
+            std::copy(hopE[ln].begin(), hopE[ln].end(), rq.hop_energy[ln]);
     return UMX_OK;
 }
 

@@ -5,11 +5,15 @@
 //                            file): every output of a file is divided by max(1.01 * peak over the file's outputs, 1) on the device.
 //   UMX_LEVELS=1             one line per output file on stdout, measured on the device:
 //                            levels <file> peak=<%.9g> over_unity=<n> clipped=<n> nonfinite=<n> gain=<%.9g>
-// Both go with UMX_PCM16, UMX_MIX, UMX_TARGETS / UMX_RESIDUAL and UMX_RESAMPLE, through umx-batch's queue and its pass-by-pass loop;
+//   UMX_LOUDNESS=1           one more line per output file, its ITU-R BS.1770-4 / EBU R128 loudness measured on the device:
+//                            loudness <file> integrated=<LUFS> momentary_max=<LUFS> blocks=<n> gated=<n>      (-inf is printed as -inf)
+//                            UMX_MIX="m=mix" gives the loudness of the input itself.
+// All go with UMX_PCM16, UMX_MIX, UMX_TARGETS / UMX_RESIDUAL and UMX_RESAMPLE, through umx-batch's queue and its pass-by-pass loop;
 // not with UMX_SHIFTS > 1 or UMX_CLI_PER_SEGMENT (the shift ensemble and the per-segment calls do not offer them).
 #pragma once
 #include "../../include/umx_hip.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,7 +23,8 @@ struct umx_clip_choice
 {
     int clip_mode = UMX_CLIP_CLAMP;
     bool levels = false;
-    bool active() const { return clip_mode != UMX_CLIP_CLAMP || levels; } // false: the calls and the files of a run without the two
+    bool loudness = false;
+    bool active() const { return clip_mode != UMX_CLIP_CLAMP || levels || loudness; } // false: the calls and the files of a run without the three
 };
 
 // false, with a message that names the variable, for a value outside the grammar above (nullptr: unset)
@@ -62,6 +67,21 @@ inline bool umx_clip_from_env(umx_clip_choice &c, const char *not_offered)
         fprintf(stderr, "UMX_CLIP / UMX_LEVELS: %s\n", not_offered);
         return false;
     }
+    if (const char *loud = getenv("UMX_LOUDNESS"))
+        if (*loud)
+        {
+            if (strcmp(loud, "0") && strcmp(loud, "1"))
+            {
+                fprintf(stderr, "UMX_LOUDNESS: need 0 or 1, got \"%s\"\n", loud);
+                return false;
+            }
+            c.loudness = loud[0] == '1';
+            if (c.loudness && not_offered)
+            {
+                fprintf(stderr, "UMX_LOUDNESS: %s (nor loudness)\n", not_offered);
+                return false;
+            }
+        }
     return true;
 }
 
@@ -70,4 +90,19 @@ inline void umx_levels_print(const char *file, const umx_levels &lv, int m)
 {
     printf("levels %s peak=%.9g over_unity=%llu clipped=%llu nonfinite=%llu gain=%.9g\n", file, (double)lv.peak[m], lv.over_unity[m], lv.clipped[m],
            lv.nonfinite[m], (double)lv.gain);
+}
+
+// the loudness line of output m of a track, written to `file`
+inline void umx_loudness_print(const char *file, const umx_loudness &ld, int m)
+{
+    auto lufs = [](double v, char *buf, size_t cap) { // (-inf by name: printf's spelling of it is the C library's)
+        if (std::isinf(v))
+            snprintf(buf, cap, v < 0 ? "-inf" : "inf");
+        else
+            snprintf(buf, cap, "%.6f", v);
+    };
+    char a[40], b[40];
+    lufs(ld.integrated[m], a, sizeof a);
+    lufs(ld.momentary_max[m], b, sizeof b);
+    printf("loudness %s integrated=%s momentary_max=%s blocks=%lld gated=%lld\n", file, a, b, ld.blocks[m], ld.gated[m]);
 }

@@ -15,6 +15,8 @@
 // the pass-by-pass loop alike; the files go up as int16 when ALL of them are 16-bit PCM -- a run has one input format -- else as fp32).
 // UMX_CLIP and UMX_LEVELS (as umx-cli; host/clip_env.h): rescale instead of clamp, and one `levels <file> ...` line per
 // file written, through the queue (umx_hip_separate_queue_levels) and the pass-by-pass loop (umx_hip_separate_tracks_levels) alike.
+// UMX_LOUDNESS (as umx-cli): one `loudness <file> ...` line per file written, through the queue
+// (umx_hip_separate_queue_loudness) and the pass-by-pass loop (umx_hip_separate_tracks_loudness) alike.
 #include "../../include/umx_host.h"
 #include "clip_env.h"
 #include "mix_env.h"
@@ -51,6 +53,7 @@ struct FileJob
     std::vector<std::vector<float>> stems;
     std::vector<std::vector<int16_t>> stems16; // UMX_PCM16: the outputs as they are written
     umx_levels levels = {};                    // UMX_CLIP / UMX_LEVELS: what the queue measured
+    umx_loudness loudness = {};                // UMX_LOUDNESS: likewise
 };
 struct BatchQueue
 {
@@ -116,6 +119,11 @@ struct BatchQueue
     {
         static_cast<FileJob *>(job->tag)->levels = *levels;
         done(user, job);
+    }
+    static void done_loudness(void *user, const umx_queue_job *job, const umx_levels *levels, const umx_loudness *loudness, const double *)
+    {
+        static_cast<FileJob *>(job->tag)->loudness = *loudness;
+        done_levels(user, job, levels);
     }
 };
 
@@ -224,7 +232,8 @@ int main(int argc, const char **argv)
             names[f] = std::filesystem::path(argv[3 + f]).stem().string() + "_" + std::to_string(k);
     }
     // umx.cpp:75-96: the buffers of file f to its directory
-    auto write_file = [&](int f, float *const *bufs, int16_t *const *bufs16, int n, int rate_, const umx_levels &lv, char *err_) -> bool {
+    auto write_file = [&](int f, float *const *bufs, int16_t *const *bufs16, int n, int rate_, const umx_levels &lv, const umx_loudness &ld,
+                          char *err_) -> bool {
         const std::filesystem::path dir = std::filesystem::path(out_dir) / names[f];
         std::error_code ec;
         std::filesystem::create_directories(dir, ec);
@@ -239,6 +248,8 @@ int main(int argc, const char **argv)
                 return false;
             if (clipc.levels)
                 umx_levels_print(p.c_str(), lv, t);
+            if (clipc.loudness)
+                umx_loudness_print(p.c_str(), ld, t);
         }
         return true;
     };
@@ -303,7 +314,7 @@ int main(int argc, const char **argv)
                     bufs[t] = fj->stems[t].data();
                     bufs16[t] = fj->stems16[t].data();
                 }
-                const bool ok = write_file(fj->index, bufs, bufs16, fj->n, UMX_SAMPLE_RATE, fj->levels, werr);
+                const bool ok = write_file(fj->index, bufs, bufs16, fj->n, UMX_SAMPLE_RATE, fj->levels, fj->loudness, werr);
                 std::lock_guard<std::mutex> lock(q.m);
                 q.unwritten.pop_front(); // (counted until it is written: the stems are in memory until then)
                 if (!ok && q.error.empty())
@@ -313,7 +324,9 @@ int main(int argc, const char **argv)
             }
         });
         const auto t0 = std::chrono::steady_clock::now();
-        const int qrc = clipc.active() ? umx_hip_separate_queue_levels(ctx, BatchQueue::next, BatchQueue::done_levels, &q, mixc.n_out,
+        const int qrc = clipc.loudness ? umx_hip_separate_queue_loudness(ctx, BatchQueue::next, BatchQueue::done_loudness, &q, mixc.n_out,
+                                                                         mixed ? mixc.gains : nullptr, flags, &io, clipc.clip_mode)
+                        : clipc.active() ? umx_hip_separate_queue_levels(ctx, BatchQueue::next, BatchQueue::done_levels, &q, mixc.n_out,
                                                                        mixed ? mixc.gains : nullptr, flags, &io, clipc.clip_mode)
                         : pcm16 ? umx_hip_separate_queue_io(ctx, BatchQueue::next, BatchQueue::done, &q, mixc.n_out, mixed ? mixc.gains : nullptr, flags, &io)
                               : umx_hip_separate_queue(ctx, BatchQueue::next, BatchQueue::done, &q, mixc.n_out, mixed ? mixc.gains : nullptr, flags);
@@ -357,6 +370,7 @@ int main(int argc, const char **argv)
         std::vector<const float *> in(nb);
         std::vector<int> rate(nb, UMX_SAMPLE_RATE);
         std::vector<umx_levels> levels(nb);
+        std::vector<umx_loudness> loudness(nb);
         std::vector<void *> out_io(per_file * nb); // (read as the formats say)
         for (int i = 0; i < nb; ++i)
         {
@@ -383,9 +397,11 @@ int main(int argc, const char **argv)
             }
         }
         const auto t0 = std::chrono::steady_clock::now();
-        if (clipc.active() ? umx_hip_separate_tracks_levels(ctx, nb, in_io.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out,
-                                                            mixed ? mixc.gains : nullptr, out_io.data(), flags, &io, clipc.clip_mode,
-                                                            clipc.levels ? levels.data() : nullptr, nullptr, nullptr)
+        // (without UMX_LOUDNESS the _loudness call IS the _levels call)
+        if (clipc.active() ? umx_hip_separate_tracks_loudness(ctx, nb, in_io.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out,
+                                                              mixed ? mixc.gains : nullptr, out_io.data(), flags, &io, clipc.clip_mode,
+                                                              clipc.levels ? levels.data() : nullptr, clipc.loudness ? loudness.data() : nullptr,
+                                                              nullptr, nullptr, nullptr)
             : pcm16 ? umx_hip_separate_tracks_io(ctx, nb, in_io.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out,
                                                mixed ? mixc.gains : nullptr, reinterpret_cast<void *const *>(out16.data()), flags, &io, nullptr, nullptr)
             : mixed ? umx_hip_separate_tracks_mix(ctx, nb, in.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out, mixc.gains,
@@ -399,7 +415,7 @@ int main(int argc, const char **argv)
         wall += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         for (int i = 0; i < nb; ++i)
         {
-            if (!write_file(f0 + i, &out[per_file * i], &out16[per_file * i], n[i], rate[i], levels[i], err))
+            if (!write_file(f0 + i, &out[per_file * i], &out16[per_file * i], n[i], rate[i], levels[i], loudness[i], err))
             {
                 fprintf(stderr, "%s\n", err);
                 return 1;

@@ -26,6 +26,9 @@
 //   UMX_CLIP=clamp|rescale, UMX_LEVELS=1   what happens to outputs beyond full scale, and one `levels <file> ...` line per file written
 //                    (umx_hip_separate_tracks_levels; host/clip_env.h); with and without UMX_PCM16 and the knobs it goes
 //                    with; not with UMX_SHIFTS > 1 or UMX_CLI_PER_SEGMENT.  Unset (or clamp, 0): today's files
+//   UMX_LOUDNESS=1   one `loudness <file> integrated=<LUFS> momentary_max=<LUFS> blocks=<n> gated=<n>` line per file written, BS.1770-4 /
+//                    R128 loudness measured on the device (umx_hip_separate_tracks_loudness; host/clip_env.h); goes where
+//                    UMX_LEVELS goes.  Unset or 0: today's output
 #include "../../include/umx_host.h"
 #include "clip_env.h"
 #include "mix_env.h"
@@ -119,6 +122,7 @@ int main(int argc, const char **argv)
                                       : nullptr))
         return 1;
     umx_levels levels = {};
+    umx_loudness loudness = {};
     umx_sample_io io = {UMX_SAMPLE_F32, pcm16 ? UMX_SAMPLE_S16 : UMX_SAMPLE_F32, 0, 0};
     if (const char *seed = getenv("UMX_PCM16_DITHER"))
     {
@@ -213,8 +217,10 @@ int main(int argc, const char **argv)
         void *out16[4];
         for (int t = 0; t < 4; ++t)
             out16[t] = pcm16 ? (void *)stems16[t].data() : (void *)stems[t].data();
-        if (umx_hip_separate_tracks_levels(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out16,
-                                           hb.flags, &io, clipc.clip_mode, clipc.levels ? &levels : nullptr, print_progress, nullptr))
+        // (... and without UMX_LOUDNESS the _loudness call IS the _levels call)
+        if (umx_hip_separate_tracks_loudness(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out16,
+                                             hb.flags, &io, clipc.clip_mode, clipc.levels ? &levels : nullptr,
+                                             clipc.loudness ? &loudness : nullptr, nullptr, print_progress, nullptr))
         {
             fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
             return 1;
@@ -271,6 +277,8 @@ int main(int argc, const char **argv)
         }
         if (clipc.levels)
             umx_levels_print(p.c_str(), levels, t);
+        if (clipc.loudness)
+            umx_loudness_print(p.c_str(), loudness, t);
     }
     umx_wav_free(audio);
     umx_wav_free_pcm16(audio16);
