@@ -25,6 +25,19 @@ def test_hip_library_exports_every_declared_symbol(pkg):
     assert sorted(pkg.HIP_SYMBOLS) == names
 
 
+def test_whole_track_entry_points_refuse_a_null_context(pkg):
+    """Every rung of the whole-track ladder, the four queue entry points and the two shift ensembles return UMX_ERR_ARG for ctx == NULL
+    before they look at another argument: every pointer and callback behind it is NULL here, which a read would fault on.  No GPU."""
+    lib = pkg.hip_lib()
+    names = ["umx_hip_separate_tracks" + r for r in ("", "_rate", "_mix", "_io", "_levels", "_loudness")]
+    names += ["umx_hip_separate_queue" + r for r in ("", "_io", "_levels", "_loudness")] + ["umx_hip_shift_ensemble", "umx_hip_shift_ensemble_mix"]
+    callbacks = (pkg.QUEUE_NEXT_FN, pkg.QUEUE_DONE_FN, pkg.QUEUE_LEVELS_FN, pkg.QUEUE_LOUDNESS_FN)
+    for name in names:
+        fn = getattr(lib, name)
+        args = [(7 if t in (ctypes.c_int, ctypes.c_uint) else t() if t in callbacks else None) for t in fn.argtypes[1:]]
+        assert fn(None, *args) == pkg.ERR_ARG, name
+
+
 def test_cu_reservations_are_requests_per_device_not_one_global_value(pkg):
     """umx_hip_gate_reserve (include/umx_hip.h): two multi-GPU drivers on one device each file a request; destroying
     one gives back ITS request only; giving back a request that was never filed is an error.  Pure host state: runs without a GPU."""

@@ -434,6 +434,49 @@ def test_refusals_leave_the_context_usable(pkg, eng3, wave):
     _same(eng3.separate_many([wave], shift_offsets=[4033])[0], usual, "fp32 after the refusals")
 
 
+def test_refusal_precedence(pkg, eng1, wave):
+    """Several bad options in ONE call: every whole-track and queue entry point refuses the sample formats first, then the clip mode, then
+    the gains, in the words each check has always used (recorded from the library before the entry points shared their checks).  Nothing
+    is written, no callback runs, and the next plain call gives the usual bits."""
+    FORMAT, CLIP, MIX = "sample io: unknown sample format", "clip mode: unknown", "mix: need 1 <= n_out <= 4 rows of five finite gains"
+    usual = eng1.separate_many([wave], shift_offsets=[4033])[0]
+    n = wave.shape[1]
+    a = np.ascontiguousarray(wave.T)
+    outs = [np.full(2 * n, 0x5A5A, np.int16) for _ in range(4)]
+    ap, op = (C.c_void_p * 1)(a.ctypes.data), (C.c_void_p * 4)(*[o.ctypes.data for o in outs])
+    ln, sh = (C.c_int * 1)(n), (C.c_int * 1)(4033)
+    lv, ld = (pkg.Levels * 1)(), (pkg.Loudness * 1)()
+    hop = np.full(4 * 2 * (n // 4410 + 1), 7.0)
+    hp = (C.c_void_p * 1)(hop.ctypes.data)
+    nan = np.full((1, 5), np.nan, np.float32)
+    gp = nan.ctypes.data_as(pkg._fp)
+    bad_io, good_io = pkg.SampleIO(pkg.SAMPLE_F32, 7, 0, 0), pkg.SampleIO(pkg.SAMPLE_F32, pkg.SAMPLE_S16, 0, 0)
+    called = []
+    nxt = pkg.QUEUE_NEXT_FN(lambda u, j: called.append("next") or 0)
+    done = {"io": pkg.QUEUE_DONE_FN(lambda u, j: called.append("done")), "levels": pkg.QUEUE_LEVELS_FN(lambda u, j, l: called.append("done")),
+            "loudness": pkg.QUEUE_LOUDNESS_FN(lambda u, j, l, d, e: called.append("done"))}
+    lib, h = eng1.lib, eng1.h
+
+    def tracks(rung, io, clip):
+        head = (h, 1, ap, ln, None, sh, 1, gp, op, 0, C.byref(io))
+        tail = {"io": (), "levels": (clip, lv), "loudness": (clip, lv, ld, hp)}[rung]
+        return getattr(lib, "umx_hip_separate_tracks_" + rung)(*head, *tail, None, None)
+
+    def queue(rung, io, clip):
+        return getattr(lib, "umx_hip_separate_queue_" + rung)(h, nxt, done[rung], None, 1, gp, 0, C.byref(io), *(() if rung == "io" else (clip,)))
+
+    cases = [(call, rung, *c) for call in (tracks, queue) for rung in ("levels", "loudness")
+             for c in ((bad_io, 2, FORMAT), (good_io, 2, CLIP), (good_io, pkg.CLIP_RESCALE, MIX))]
+    cases += [(call, "io", bad_io, None, FORMAT) for call in (tracks, queue)]
+    for call, rung, io, clip, words in cases:
+        what = (call.__name__, rung, words)
+        assert call(rung, io, clip) == pkg.ERR_ARG, what
+        assert eng1.last_error().startswith(words), (what, eng1.last_error())
+        assert all(np.all(o == 0x5A5A) for o in outs) and np.all(hop == 7.0) and not called, what
+        assert bytes(lv[0]) == bytes(C.sizeof(pkg.Levels)) and bytes(ld[0]) == bytes(C.sizeof(pkg.Loudness)), what
+        _same(eng1.separate_many([wave], shift_offsets=[4033])[0], usual, ("fp32 after", what))
+
+
 # ---------------------------------------------------------------- the CLIs
 MIX_SPEC = "loud=3*mix;quiet=0.25*mix;vocals=vocals"  # GAINS as UMX_MIX
 MIX_FILES = ["loud.wav", "quiet.wav", "vocals.wav"]

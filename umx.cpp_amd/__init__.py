@@ -192,8 +192,6 @@ def hip_lib():
     lib.umx_hip_infer_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_uint]
     lib.umx_hip_infer_batch_async.argtypes = lib.umx_hip_infer_batch.argtypes
     lib.umx_hip_infer_batch_device.argtypes = lib.umx_hip_infer_batch.argtypes
-    lib.umx_hip_separate_tracks.argtypes = [C.c_void_p, C.c_int, C.POINTER(_fp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_fp),
-                                            C.c_uint, C.c_void_p, C.c_void_p]
     lib.umx_hip_order_after.argtypes = [C.c_void_p, C.c_void_p]
     lib.umx_hip_order_before.argtypes = [C.c_void_p, C.c_void_p]
     lib.umx_hip_weight_bytes.restype = C.c_size_t
@@ -256,8 +254,6 @@ def hip_lib():
                                             C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
     lib.umx_hip_shift_inference_rate.argtypes = [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.c_uint, C.c_void_p,
                                                  C.c_void_p]
-    lib.umx_hip_separate_tracks_rate.argtypes = [C.c_void_p, C.c_int, C.POINTER(_fp), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                                 C.POINTER(C.c_int), C.POINTER(_fp), C.c_uint, C.c_void_p, C.c_void_p]
     lib.umx_hip_debug_resample_taps.argtypes = [C.c_int, C.c_int, _fp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                 C.POINTER(C.c_int)]
     lib.umx_hip_ensemble_offsets.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
@@ -266,29 +262,17 @@ def hip_lib():
     lib.umx_hip_debug_shift_mean_ms.restype = C.c_float
     lib.umx_hip_debug_shift_mean_ms.argtypes = [C.c_void_p]
     lib.umx_hip_mix_columns.argtypes = [C.c_int, _fp]
-    lib.umx_hip_separate_tracks_mix.argtypes = [C.c_void_p, C.c_int, C.POINTER(_fp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                                C.c_int, _fp, C.POINTER(_fp), C.c_uint, C.c_void_p, C.c_void_p]
     lib.umx_hip_shift_ensemble_mix.argtypes = [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, C.POINTER(_fp),
                                                C.c_uint, C.c_void_p, C.c_void_p]
     lib.umx_hip_mix_stems_device.argtypes = [C.c_void_p, C.c_int, _fp, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
                                              C.c_void_p]
-    lib.umx_hip_separate_queue.argtypes = [C.c_void_p, QUEUE_NEXT_FN, QUEUE_DONE_FN, C.c_void_p, C.c_int, _fp, C.c_uint]
     lib.umx_hip_queue_plan.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.umx_hip_debug_queue_calls.argtypes = [C.c_void_p]
-    lib.umx_hip_separate_tracks_io.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                               C.POINTER(C.c_int), C.c_int, _fp, C.POINTER(C.c_void_p), C.c_uint, C.POINTER(SampleIO),
-                                               C.c_void_p, C.c_void_p]
-    lib.umx_hip_separate_queue_io.argtypes = [C.c_void_p, QUEUE_NEXT_FN, QUEUE_DONE_FN, C.c_void_p, C.c_int, _fp, C.c_uint, C.POINTER(SampleIO)]
     lib.umx_hip_pcm16_decode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.umx_hip_pcm16_encode_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.POINTER(SampleIO),
                                                 C.POINTER(C.c_void_p), C.c_void_p]
     lib.umx_hip_pcm16_decode_host.argtypes = [_i16p, C.c_longlong, _fp]
     lib.umx_hip_pcm16_encode_host.argtypes = [_fp, C.c_int, C.c_int, C.c_longlong, C.POINTER(SampleIO), _i16p]
-    lib.umx_hip_separate_tracks_levels.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                                   C.POINTER(C.c_int), C.c_int, _fp, C.POINTER(C.c_void_p), C.c_uint, C.POINTER(SampleIO),
-                                                   C.c_int, C.POINTER(Levels), C.c_void_p, C.c_void_p]
-    lib.umx_hip_separate_queue_levels.argtypes = [C.c_void_p, QUEUE_NEXT_FN, QUEUE_LEVELS_FN, C.c_void_p, C.c_int, _fp, C.c_uint,
-                                                  C.POINTER(SampleIO), C.c_int]
     lib.umx_hip_levels_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.POINTER(SampleIO), C.c_void_p,
                                           C.c_void_p]
     lib.umx_hip_pcm16_encode_rescaled_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.POINTER(SampleIO),
@@ -297,17 +281,33 @@ def hip_lib():
     lib.umx_hip_levels_host.argtypes = [_fp, C.c_int, C.c_int, C.c_longlong, C.POINTER(SampleIO), C.c_float, C.POINTER(LevelsAcc)]
     lib.umx_hip_rescale_gain.argtypes = [_fp, C.c_int]
     lib.umx_hip_rescale_gain.restype = C.c_float
-    lib.umx_hip_separate_tracks_loudness.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                                     C.POINTER(C.c_int), C.c_int, _fp, C.POINTER(C.c_void_p), C.c_uint, C.POINTER(SampleIO),
-                                                     C.c_int, C.POINTER(Levels), C.POINTER(Loudness), C.POINTER(C.c_void_p), C.c_void_p,
-                                                     C.c_void_p]
-    lib.umx_hip_separate_queue_loudness.argtypes = [C.c_void_p, QUEUE_NEXT_FN, QUEUE_LOUDNESS_FN, C.c_void_p, C.c_int, _fp, C.c_uint,
-                                                    C.POINTER(SampleIO), C.c_int]
     lib.umx_hip_kweight_hops_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_longlong, C.c_longlong,
                                                 C.c_void_p, C.c_void_p]
     lib.umx_hip_kweight_coeffs.argtypes = [C.c_int, _dp, _dp, _dp, _dp]
     lib.umx_hip_kweight_hops_host.argtypes = [_fp, C.c_int, C.c_int, C.c_longlong, C.c_longlong, _dp]
     lib.umx_hip_loudness_gate.argtypes = [_dp, C.c_longlong, C.c_int, _dp, _dp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    # The whole-track ladder, from one prefix: context, n_tracks, audio, lengths[, rates], shift offsets[, n_out, gains], outputs,
+    # flags -- then what a rung adds -- then progress and its user pointer.  The queue entry points likewise.
+    def tracks_args(ptr, rate=True, mix=True):
+        return ([C.c_void_p, C.c_int, C.POINTER(ptr), C.POINTER(C.c_int)] + [C.POINTER(C.c_int)] * (2 if rate else 1)
+                + ([C.c_int, _fp] if mix else []) + [C.POINTER(ptr), C.c_uint])
+
+    progress = [C.c_void_p, C.c_void_p]
+    wide = tracks_args(C.c_void_p) + [C.POINTER(SampleIO)]
+    lib.umx_hip_separate_tracks.argtypes = tracks_args(_fp, rate=False, mix=False) + progress
+    lib.umx_hip_separate_tracks_rate.argtypes = tracks_args(_fp, mix=False) + progress
+    lib.umx_hip_separate_tracks_mix.argtypes = tracks_args(_fp) + progress
+    lib.umx_hip_separate_tracks_io.argtypes = wide + progress
+    lib.umx_hip_separate_tracks_levels.argtypes = wide + [C.c_int, C.POINTER(Levels)] + progress
+    lib.umx_hip_separate_tracks_loudness.argtypes = wide + [C.c_int, C.POINTER(Levels), C.POINTER(Loudness), C.POINTER(C.c_void_p)] + progress
+
+    def queue_args(done_fn):
+        return [C.c_void_p, QUEUE_NEXT_FN, done_fn, C.c_void_p, C.c_int, _fp, C.c_uint]
+
+    lib.umx_hip_separate_queue.argtypes = queue_args(QUEUE_DONE_FN)
+    lib.umx_hip_separate_queue_io.argtypes = queue_args(QUEUE_DONE_FN) + [C.POINTER(SampleIO)]
+    lib.umx_hip_separate_queue_levels.argtypes = queue_args(QUEUE_LEVELS_FN) + [C.POINTER(SampleIO), C.c_int]
+    lib.umx_hip_separate_queue_loudness.argtypes = queue_args(QUEUE_LOUDNESS_FN) + [C.POINTER(SampleIO), C.c_int]
     _hip = lib
     return lib
 
@@ -409,6 +409,11 @@ def kweight_coeffs(rate):
     return tuple(np.array(list(x), np.float64) for x in c)
 
 
+def kweight_hop_count(n, rate):
+    """Whole hops (a tenth of a second: kweight_hop of csrc/loudness.h) in n frames at `rate`; a rate the calls refuse gives any size."""
+    return int(n) // max(1, (int(rate) + 5) // 10)
+
+
 def kweight_hops_host(x, rate, first_hop=0, n_hops=None):
     """umx_hip_kweight_hops_host: the K-weighted hop energies of a (2,n) float32 array by the rule of DESIGN 21 -> (2, n // hop)
     float64; hops outside [first_hop, first_hop + n_hops) stay NaN (no GPU)."""
@@ -469,6 +474,32 @@ def _mix_gains(gains):
     if g.ndim != 2 or g.shape[1] != MIX_COLUMNS:
         raise ValueError("mix gains: need an (n_out, 5) matrix: bass, drums, other, vocals slots and the mixture")
     return g.shape[0], g.ravel()
+
+
+class _TrackArgs:
+    """The marshalling of every whole-track call: a list of (2, L_i) arrays as the C entry points take it.  io: the
+    SampleIO of the call or None (int16 arrays where it says SAMPLE_S16, else float32); n_out: host buffers per track; ptr: the pointer
+    type of the C signature's arrays.  ins / outs: the contiguous (L_i, 2) inputs and the output buffers; a, o, n, sh, rt: the ctypes
+    arrays of audio, outputs, lengths, shift offsets (None = -1: no shift) and rates (None: all 44.1 kHz); result(): the outputs as a
+    list of [n_out x (2, L_i)]."""
+
+    def __init__(self, waves, io=None, n_out=4, shift_offsets=None, rates=None, ptr=C.c_void_p):
+        nt = len(waves)
+        tin = np.int16 if io is not None and io.in_format == SAMPLE_S16 else np.float32
+        tout = np.int16 if io is not None and io.out_format == SAMPLE_S16 else np.float32
+        self.ins = [np.ascontiguousarray(np.asarray(w, tin).T).ravel() for w in waves]
+        self.Ls = [np.asarray(w).shape[1] for w in waves]
+        self.n_host = min(max(n_out, 0), MAX_MIX_OUTPUTS)
+        self.outs = [[np.empty(2 * L, tout) for _ in range(self.n_host)] for L in self.Ls]
+        self.a = (ptr * nt)(*[C.cast(x.ctypes.data, ptr) for x in self.ins])
+        self.o = (ptr * max(1, nt * self.n_host))(*[C.cast(x.ctypes.data, ptr) for t in self.outs for x in t])
+        self.n = (C.c_int * nt)(*self.Ls)
+        self.shifts = [(-1 if s is None else int(s)) for s in (shift_offsets or [None] * nt)]
+        self.sh = (C.c_int * nt)(*self.shifts)
+        self.rt = None if rates is None else (C.c_int * nt)(*[int(r) for r in rates])
+
+    def result(self):
+        return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(self.outs, self.Ls)]
 
 
 def mix_columns(gains):
@@ -732,19 +763,12 @@ class Engine:
     def separate_many(self, waves, flags=0, shift_offsets=None, rates=None):
         """Several tracks at once, one per track lane (umx_hip_separate_tracks): list of (2,L_i) -> list of [4 x (2,L_i)].
         rates: one sample rate per track (umx_hip_separate_tracks_rate), None = all 44.1 kHz."""
-        nt = len(waves)
-        ins = [np.ascontiguousarray(np.asarray(w, np.float32).T).ravel() for w in waves]
-        Ls = [np.asarray(w).shape[1] for w in waves]
-        outs = [[np.empty(2 * L, np.float32) for _ in range(4)] for L in Ls]
-        a = (_fp * nt)(*[x.ctypes.data_as(_fp) for x in ins])
-        o = (_fp * (4 * nt))(*[x.ctypes.data_as(_fp) for t4 in outs for x in t4])
-        sh = (C.c_int * nt)(*[(-1 if s is None else s) for s in (shift_offsets or [None] * nt)])
+        m = _TrackArgs(waves, None, 4, shift_offsets, rates, _fp)
         if rates is None:
-            self._check(self.lib.umx_hip_separate_tracks(self.h, nt, a, (C.c_int * nt)(*Ls), sh, o, flags, None, None))
+            self._check(self.lib.umx_hip_separate_tracks(self.h, len(waves), m.a, m.n, m.sh, m.o, flags, None, None))
         else:
-            self._check(self.lib.umx_hip_separate_tracks_rate(self.h, nt, a, (C.c_int * nt)(*Ls), (C.c_int * nt)(*rates), sh, o, flags,
-                                                              None, None))
-        return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t4] for t4, L in zip(outs, Ls)]
+            self._check(self.lib.umx_hip_separate_tracks_rate(self.h, len(waves), m.a, m.n, m.rt, m.sh, m.o, flags, None, None))
+        return m.result()
 
     def separate_ensemble(self, wave, shifts=None, offsets=None, flags=0, rate=MODEL_RATE, gains=None):
         """(2,L) host array -> 4 x (2,L): umx_hip_shift_ensemble, the fp32 mean of the track separated at len(offsets) shift offsets,
@@ -780,17 +804,10 @@ class Engine:
     def separate_many_mix(self, waves, gains, flags=0, shift_offsets=None, rates=None):
         """separate_many() with one gain matrix for every lane: list of (2,L_i) -> list of [n_out x (2,L_i)]."""
         n_out, g = _mix_gains(gains)
-        nt = len(waves)
-        ins = [np.ascontiguousarray(np.asarray(w, np.float32).T).ravel() for w in waves]
-        Ls = [np.asarray(w).shape[1] for w in waves]
-        outs = [[np.empty(2 * L, np.float32) for _ in range(min(max(n_out, 0), MAX_MIX_OUTPUTS))] for L in Ls]
-        a = (_fp * nt)(*[x.ctypes.data_as(_fp) for x in ins])
-        o = (_fp * max(1, sum(len(t) for t in outs)))(*[x.ctypes.data_as(_fp) for t in outs for x in t])
-        sh = (C.c_int * nt)(*[(-1 if s is None else s) for s in (shift_offsets or [None] * nt)])
-        rt = None if rates is None else (C.c_int * nt)(*[int(r) for r in rates])
-        self._check(self.lib.umx_hip_separate_tracks_mix(self.h, nt, a, (C.c_int * nt)(*Ls), rt, sh, n_out, g.ctypes.data_as(_fp), o, flags,
+        m = _TrackArgs(waves, None, n_out, shift_offsets, rates, _fp)
+        self._check(self.lib.umx_hip_separate_tracks_mix(self.h, len(waves), m.a, m.n, m.rt, m.sh, n_out, g.ctypes.data_as(_fp), m.o, flags,
                                                          None, None))
-        return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)]
+        return m.result()
 
     # --- 16-bit PCM in and out (DESIGN 19): int16 frames across PCIe, converted on the device ---
     def separate_many_io(self, waves, in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None, flags=0, shift_offsets=None,
@@ -798,21 +815,12 @@ class Engine:
         """umx_hip_separate_tracks_io: separate_many() / separate_many_mix() (gains) with the formats of the host buffers chosen:
         SAMPLE_S16 in takes (2,L_i) int16 arrays, SAMPLE_S16 out returns int16 arrays, dithered with dither_seed unless it is None.
         io: a SampleIO passed as it is instead (tests of the refusals)."""
-        nt = len(waves)
         io = sample_io(in_format, out_format, dither_seed) if io is None else io
         n_out, g = (4, None) if gains is None else _mix_gains(gains)
-        tin = np.int16 if io.in_format == SAMPLE_S16 else np.float32
-        tout = np.int16 if io.out_format == SAMPLE_S16 else np.float32
-        ins = [np.ascontiguousarray(np.asarray(w, tin).T).ravel() for w in waves]
-        Ls = [np.asarray(w).shape[1] for w in waves]
-        outs = [[np.empty(2 * L, tout) for _ in range(min(max(n_out, 0), MAX_MIX_OUTPUTS))] for L in Ls]
-        a = (C.c_void_p * nt)(*[x.ctypes.data for x in ins])
-        o = (C.c_void_p * max(1, sum(len(t) for t in outs)))(*[x.ctypes.data for t in outs for x in t])
-        sh = (C.c_int * nt)(*[(-1 if s is None else s) for s in (shift_offsets or [None] * nt)])
-        rt = None if rates is None else (C.c_int * nt)(*[int(r) for r in rates])
-        self._check(self.lib.umx_hip_separate_tracks_io(self.h, nt, a, (C.c_int * nt)(*Ls), rt, sh, n_out,
-                                                        None if g is None else g.ctypes.data_as(_fp), o, flags, C.byref(io), None, None))
-        return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)]
+        m = _TrackArgs(waves, io, n_out, shift_offsets, rates)
+        self._check(self.lib.umx_hip_separate_tracks_io(self.h, len(waves), m.a, m.n, m.rt, m.sh, n_out,
+                                                        None if g is None else g.ctypes.data_as(_fp), m.o, flags, C.byref(io), None, None))
+        return m.result()
 
     # --- output levels and clip handling (DESIGN 20): what leaves is measured on the device; rescale divides a track by one divisor ---
     def separate_many_levels(self, waves, clip=CLIP_CLAMP, io=None, flags=0, shift_offsets=None, rates=None, gains=None, levels=True):
@@ -821,20 +829,12 @@ class Engine:
         nt = len(waves)
         io = sample_io() if io is None else io
         n_out, g = (4, None) if gains is None else _mix_gains(gains)
-        tin = np.int16 if io.in_format == SAMPLE_S16 else np.float32
-        tout = np.int16 if io.out_format == SAMPLE_S16 else np.float32
-        ins = [np.ascontiguousarray(np.asarray(w, tin).T).ravel() for w in waves]
-        Ls = [np.asarray(w).shape[1] for w in waves]
-        outs = [[np.empty(2 * L, tout) for _ in range(min(max(n_out, 0), MAX_MIX_OUTPUTS))] for L in Ls]
-        a = (C.c_void_p * nt)(*[x.ctypes.data for x in ins])
-        o = (C.c_void_p * max(1, sum(len(t) for t in outs)))(*[x.ctypes.data for t in outs for x in t])
-        sh = (C.c_int * nt)(*[(-1 if s is None else s) for s in (shift_offsets or [None] * nt)])
-        rt = None if rates is None else (C.c_int * nt)(*[int(r) for r in rates])
+        m = _TrackArgs(waves, io, n_out, shift_offsets, rates)
         lv = (Levels * nt)() if levels else None
-        self._check(self.lib.umx_hip_separate_tracks_levels(self.h, nt, a, (C.c_int * nt)(*Ls), rt, sh, n_out,
-                                                            None if g is None else g.ctypes.data_as(_fp), o, flags, C.byref(io), int(clip), lv,
+        self._check(self.lib.umx_hip_separate_tracks_levels(self.h, nt, m.a, m.n, m.rt, m.sh, n_out,
+                                                            None if g is None else g.ctypes.data_as(_fp), m.o, flags, C.byref(io), int(clip), lv,
                                                             None, None))
-        return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)], (list(lv) if levels else None)
+        return m.result(), (list(lv) if levels else None)
 
     # --- loudness of every output: K-weighted hop energies measured on the device, blocks and gates formed on the host ---
     def separate_many_loudness(self, waves, clip=CLIP_CLAMP, io=None, flags=0, shift_offsets=None, rates=None, gains=None, levels=True,
@@ -844,34 +844,23 @@ class Engine:
         nt = len(waves)
         io = sample_io() if io is None else io
         n_out, g = (4, None) if gains is None else _mix_gains(gains)
-        tin = np.int16 if io.in_format == SAMPLE_S16 else np.float32
-        tout = np.int16 if io.out_format == SAMPLE_S16 else np.float32
-        ins = [np.ascontiguousarray(np.asarray(w, tin).T).ravel() for w in waves]
-        Ls = [np.asarray(w).shape[1] for w in waves]
-        n_host = min(max(n_out, 0), MAX_MIX_OUTPUTS)
-        outs = [[np.empty(2 * L, tout) for _ in range(n_host)] for L in Ls]
-        a = (C.c_void_p * nt)(*[x.ctypes.data for x in ins])
-        o = (C.c_void_p * max(1, sum(len(t) for t in outs)))(*[x.ctypes.data for t in outs for x in t])
-        sh = (C.c_int * nt)(*[(-1 if s is None else s) for s in (shift_offsets or [None] * nt)])
-        rt = None if rates is None else (C.c_int * nt)(*[int(r) for r in rates])
+        m = _TrackArgs(waves, io, n_out, shift_offsets, rates)
         lv = (Levels * nt)() if levels else None
         ld = (Loudness * nt)() if loudness else None
         env = ep = None
         if envelopes:  # (a rate the call will refuse: any size does)
-            hops = [L // max(1, ((44100 if rates is None else int(r)) + 5) // 10) for L, r in zip(Ls, rates or [44100] * nt)]
-            env = [np.full((n_host, 2, h), np.nan) for h in hops]
+            env = [np.full((m.n_host, 2, kweight_hop_count(L, r)), np.nan) for L, r in zip(m.Ls, rates or [MODEL_RATE] * nt)]
             ep = (C.c_void_p * nt)(*[e.ctypes.data if e.size else None for e in env])
-        self._check(self.lib.umx_hip_separate_tracks_loudness(self.h, nt, a, (C.c_int * nt)(*Ls), rt, sh, n_out,
-                                                              None if g is None else g.ctypes.data_as(_fp), o, flags, C.byref(io), int(clip), lv,
+        self._check(self.lib.umx_hip_separate_tracks_loudness(self.h, nt, m.a, m.n, m.rt, m.sh, n_out,
+                                                              None if g is None else g.ctypes.data_as(_fp), m.o, flags, C.byref(io), int(clip), lv,
                                                               ld, ep, None, None))
-        return ([[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)], (list(lv) if levels else None),
-                (list(ld) if loudness else None), env)
+        return m.result(), (list(lv) if levels else None), (list(ld) if loudness else None), env
 
     def kweight_hops_device(self, in_ptrs, n, rate, E_ptr, first_hop=0, n_hops=None, hip_stream=None):
         """umx_hip_kweight_hops_device: hops [first_hop, first_hop + n_hops) of 1 .. 4 device buffers (2,n) interleaved fp32 into the
         float64 array [buffer][channel][n // hop] at device address E_ptr."""
         nb = len(in_ptrs)
-        hops = int(n) // max(1, (int(rate) + 5) // 10)
+        hops = kweight_hop_count(n, rate)
         self._check(self.lib.umx_hip_kweight_hops_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(rate), int(first_hop),
                                                          int(hops - first_hop if n_hops is None else n_hops), C.c_void_p(E_ptr), hip_stream))
 
@@ -916,12 +905,8 @@ class Engine:
         loudness=True -> umx_hip_separate_queue_loudness: returns (outputs, [Levels], [Loudness], [(n_out, 2, hops) float64])."""
         nj = len(waves)
         n_out, g = (4, None) if mix is None else _mix_gains(mix)
-        tin = np.int16 if io is not None and io.in_format == SAMPLE_S16 else np.float32
-        tout = np.int16 if io is not None and io.out_format == SAMPLE_S16 else np.float32
-        ins = [np.ascontiguousarray(np.asarray(w, tin).T).ravel() for w in waves]
-        Ls = [np.asarray(w).shape[1] for w in waves]
-        outs = [[np.empty(2 * L, tout) for _ in range(min(max(n_out, 0), MAX_MIX_OUTPUTS))] for L in Ls]
-        shifts = [(-1 if s is None else int(s)) for s in (shift_offsets or [None] * nj)]
+        m = _TrackArgs(waves, io, n_out, shift_offsets)
+        ins, Ls, outs, shifts = m.ins, m.Ls, m.outs, m.shifts
         state = {"next": 0, "done": []}
 
         def _next(_user, job):
@@ -953,7 +938,7 @@ class Engine:
                                                                  None if g is None else g.ctypes.data_as(_fp), flags,
                                                                  None if io is None else C.byref(io), int(clip or CLIP_CLAMP)))
             assert sorted(state["done"]) == list(range(nj)), state
-            return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)], got, loud, env
+            return m.result(), got, loud, env
         if clip is not None or levels:
             got = [None] * nj
 
@@ -965,7 +950,7 @@ class Engine:
                                                                None if g is None else g.ctypes.data_as(_fp), flags,
                                                                None if io is None else C.byref(io), int(clip or CLIP_CLAMP)))
             assert sorted(state["done"]) == list(range(nj)), state
-            return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)], got
+            return m.result(), got
         if io is None:
             self._check(self.lib.umx_hip_separate_queue(self.h, QUEUE_NEXT_FN(_next), QUEUE_DONE_FN(_done), None, n_out,
                                                         None if g is None else g.ctypes.data_as(_fp), flags))
@@ -973,7 +958,7 @@ class Engine:
             self._check(self.lib.umx_hip_separate_queue_io(self.h, QUEUE_NEXT_FN(_next), QUEUE_DONE_FN(_done), None, n_out,
                                                            None if g is None else g.ctypes.data_as(_fp), flags, C.byref(io)))
         assert sorted(state["done"]) == list(range(nj)), state
-        return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(outs, Ls)]
+        return m.result()
 
     def queue_calls(self):
         """Calls of the segment loop the engine's last separate_queue made (umx_hip_debug_queue_calls); None: there has been none."""

@@ -528,6 +528,23 @@ struct umx_hip_ctx
         *p = reinterpret_cast<T_ *>(q);
         return UMX_OK;
     }
+    // the release that goes with dalloc: p leaves `allocs` and the device, and is nulled; a pointer dalloc did not hand out is an error
+    template <class T_> int dfree(T_ *&p)
+    {
+        const auto it = std::find(allocs.begin(), allocs.end(), (void *)p);
+        if (it == allocs.end())
+        {
+            set_error("dfree: not a device buffer of this context");
+            return UMX_ERR_HIP;
+        }
+        allocs.erase(it);
+        (void)hipFree(p);
+        p = nullptr;
+        return UMX_OK;
+    }
+    // Grow-only device buffers (engine_tracks.h): every pointer of `bufs` has room for (its elements per unit) x `units`; `cap`: the
+    // units they hold now.  Too small: all are released and allocated again with an eighth to spare (their contents are lost).
+    template <class T_> int grow_only(std::initializer_list<std::pair<T_ **, int>> bufs, size_t &cap, size_t units);
     template <class T_> int upload(T_ **p, const std::vector<T_> &h)
     {
         int rc = dalloc(p, h.size(), false);
@@ -564,6 +581,19 @@ struct umx_hip_ctx
     size_t state_floats() const { return (size_t)4 * 12 * Hl; }
     // phased form of one segment (exact multi-GPU carry): front | layer 0 | layer 1 | layer 2 | back
     // whole tracks on the device (split_inference / shift_inference, umx.cpp:99-295; engine_tracks.h, engine_queue.h)
+    // What a whole-track call may ask for beyond its tracks: ONE record, filled by the C entry points (engine_cabi.h), carried by
+    // the request of tracks() and by queue(), and kept by every job (admit_job).  Its defaults are the plain call.
+    struct TrackOptions
+    {
+        const MixSpec *mix = nullptr;   // stem_mix.h, DESIGN 17: a checked matrix; weighted sums of a track's stems and its input instead of the stems
+        umx_sample_io io = {};          // pcm16.h, DESIGN 19: how the host audio and outputs are read (UMX_SAMPLE_S16: int16 frames behind the float pointers)
+        int clip_mode = UMX_CLIP_CLAMP; // levels.h, DESIGN 20: UMX_CLIP_RESCALE: every track leaves whole, over its common divisor
+        bool levels = false;            // the caller wants the record of what left
+        bool loudness = false;          // loudness.h, DESIGN 21: the hop energies of what leaves are measured
+        int n_host() const { return mix ? mix->n_out : 4; } // host buffers per track
+        bool rescale() const { return clip_mode == UMX_CLIP_RESCALE; }
+        bool measures() const { return levels || rescale(); } // a rescaled track measures for its divisor whether or not the caller wants the record
+    };
     struct TrackRequest // what tracks() is asked for: n_tracks tracks, one per track lane
     {
         int n_tracks = 0;
@@ -571,14 +601,12 @@ struct umx_hip_ctx
         const int *length = nullptr;
         const int *rate = nullptr; // nullptr: every track at 44.1 kHz; else track i is at rate[i], resampled to 44.1 kHz and back on the device
         const int *shift_offset = nullptr; // < 0: no shift buffer (plain split_inference)
-        float *const *out = nullptr; // four host buffers per track; with mix, mix->n_out: out[n_host * track + m]
+        float *const *out = nullptr; // opt.n_host() host buffers per track: out[n_host * track + m]
         unsigned flags = 0;
         void (*progress)(float, void *) = nullptr;
         void *progress_user = nullptr;
         bool ensemble = false;       // the lanes are ONE track at n_tracks shift offsets, `out` the buffers of their mean
-        const MixSpec *mix = nullptr; // stem_mix.h, DESIGN 17: weighted sums of a track's stems and its input instead of the stems
-        umx_sample_io io = {};        // pcm16.h, DESIGN 19: how `audio` and `out` are read (UMX_SAMPLE_S16: int16 frames behind the float pointers)
-        int clip_mode = UMX_CLIP_CLAMP; // levels.h, DESIGN 20: UMX_CLIP_RESCALE: every track leaves whole, over its common divisor
+        TrackOptions opt;            // (opt.levels, opt.loudness: whether the results below are wanted -- track_request, engine_cabi.h)
         umx_levels *levels = nullptr; // n_tracks records of what left, or nullptr: not wanted
         umx_loudness *loudness = nullptr; // loudness.h, DESIGN 21: n_tracks records, or nullptr
         double *const *hop_energy = nullptr; // per track nullptr or room for its hop energies; either of the two: the tracks are measured
@@ -612,20 +640,18 @@ struct umx_hip_ctx
     // ---- what tracks_once and the track queue share (engine_tracks.h)
     struct TrackJob // a track resident on the device
     {
-        const float *audio = nullptr; // on the host (io.in_format UMX_SAMPLE_S16: int16 frames)
-        umx_sample_io io = {};        // the formats of `audio` and of the host buffers its regions go to
+        const float *audio = nullptr; // on the host (opt.io.in_format UMX_SAMPLE_S16: int16 frames)
+        TrackOptions opt;             // what its call asked for (admit_job): mix, the formats of `audio` and of the host buffers its regions
+                                      // go to, the clip mode, whether what leaves is measured into acc->lev and acc->hopE
         int length = 0;               // frames as the segments see them (the 44.1 kHz version's of a resampled track)
         int lead = 0, L2 = 0, segs = 0; // track_geometry: frames of silence before the track, padded frames, segments
         long long uploaded = 0;       // host frames already on the device
         TrackBufs *acc = nullptr;     // the accumulator set it writes
         bool by_region = true;        // its final regions are mixed in place and leave region by region (false: an ensemble lane, a
                                       // resampled track, a rescaled one -- mixed and downloaded whole behind the last segment)
-        int clip_mode = UMX_CLIP_CLAMP; // UMX_CLIP_RESCALE divides what leaves by the track's divisor (and measures for it)
-        bool levels = false;          // what leaves is measured into acc->lev
         bool whole_region = false;    // not by_region, and track_call itself finishes it behind its last segment as ONE region: the
                                       // frames [lead, lead + length) (a rescaled track at 44.1 kHz)
-        // the K-weighted hop energies of what leaves go to acc->hopE
-        bool loudness = false;
+        // DESIGN 21 (opt.loudness): the K-weighted hop energies of what leaves go to acc->hopE
         int loud_rate = 0;            // the caller's rate: hop = kweight_hop(loud_rate) frames
         long long loud_hops = 0;      // hops of the caller's track (its length at that rate / hop)
         long long hops_done = 0;      // hops already launched (a restart begins again at 0)
@@ -670,34 +696,31 @@ struct umx_hip_ctx
     int track_stride() const { return (int)((1 - 0.25f) * N); } // umx.cpp:181, inference.hpp:15
     static bool track_job_ok(const float *audio, int length, int shift_offset, float *const *out, int n_host);
     static bool track_geometry(int length, int shift_offset, int stride, TrackJob &j);
-    int grow_frames(std::initializer_list<std::pair<float **, int>> bufs, size_t &cap, size_t frames);
     int track_bufs_grow(TrackBufs &tb_, size_t frames);
-    int grow_words(uint32_t *&p, size_t &cap, size_t frames);
     int track_pcm16_grow(TrackBufs &tb_, const umx_sample_io &io, size_t frames, int n_host);
     void track_encode(const TrackBufs &tb_, const umx_sample_io &io, int n_host, float *const src[4], size_t src_start, int count,
                       long long first_frame, hipStream_t st);
     int track_levels_grow(TrackBufs &tb_);
-    void track_leave(TrackJob &j, int n_host, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st);
+    int admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt, const float *audio, int rate, int length_at_rate, bool leaves_whole);
+    void track_leave(TrackJob &j, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st);
     hipError_t track_levels_report(const TrackJob &j, int n_host, umx_levels &lv);
     int track_loudness_grow(TrackBufs &tb_, TrackJob &j, int rate, int length_at_rate, int n_host);
     hipError_t track_loudness_report(const TrackJob &j, int n_host, std::vector<double> &E, umx_loudness &ld);
     hipError_t track_upload_until(TrackJob &j, long long padded_end, hipStream_t st);
     void track_mix(const MixSpec &mix, float *const stems[4], size_t stem_start, const float *in, size_t in_start, int count, hipStream_t st);
-    hipError_t track_region_download(const TrackRegion &r, int n_host, float *const *out_host);
-    int track_call(const TrackLane *lanes, int nl, unsigned flags, const MixSpec *mix, int &last_slot, TrackRegions &regions);
+    hipError_t track_region_download(const TrackRegion &r, float *const *out_host);
+    int track_call(const TrackLane *lanes, int nl, unsigned flags, int &last_slot, TrackRegions &regions);
     // track queue (engine_queue.h): B + 2 accumulator sets (in, out, sumw of TrackBufs; grow-only) lent to the jobs in flight
     std::vector<TrackBufs> qpool;
     int queue_calls = -1; // infer_batch calls of the last queue run
     struct QueueDone // the done callback of a run: the plain one, or the one that receives every job's levels
-    {
+    {               // (opt.levels of the run), or (opt.loudness) the one that also receives the loudness record and the hop energies
         umx_queue_done_fn plain = nullptr;
         umx_queue_levels_fn with_levels = nullptr;
-        umx_queue_loudness_fn with_loudness = nullptr; // levels, the loudness record and the hop energies
-        int clip_mode = UMX_CLIP_CLAMP;
-        bool measures() const { return with_levels != nullptr || with_loudness != nullptr; }
+        umx_queue_loudness_fn with_loudness = nullptr;
     };
-    int queue(umx_queue_next_fn next, const QueueDone &done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io);
-    int queue_run(umx_queue_next_fn next, const QueueDone &done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io);
+    int queue(umx_queue_next_fn next, const QueueDone &done, void *user, const TrackOptions &opt, unsigned flags);
+    int queue_run(umx_queue_next_fn next, const QueueDone &done, void *user, const TrackOptions &opt, unsigned flags);
     int phase_begin(const float *audio_host, int n, unsigned flags);
     int phase_begin_device(const float *audio_dev, int n, unsigned flags);
     int phase_end_device(float *const out_dev_[4]);

@@ -1,6 +1,28 @@
 // engine_cabi.h -- part of engine.hip (one translation unit: the kernels inline into their launchers): the C-ABI of include/umx_hip.h.
 // Included by engine.hip behind the definition of umx_hip_ctx; not a stand-alone header.
 // ---------------------------------------------------------------- C-ABI
+// The 1 .. 4 non-null device buffers of a kernel's entry point, as the kernel's frames (float2, or a word per int16 frame) -> p[];
+// false: refused (set_error done)
+template <class From, class To>
+static bool device_buffers(umx_hip_ctx *ctx, const char *what, int n_buffers, From *const *bufs, int n, long long first_frame, To *p[4])
+{
+    if (n_buffers < 1 || n_buffers > 4 || !bufs || n < 1 || first_frame < 0)
+    {
+        ctx->set_error(std::string(what) + ": need 1 .. 4 buffers, n >= 1 and first_frame >= 0");
+        return false;
+    }
+    for (int b = 0; b < n_buffers; ++b)
+    {
+        if (!bufs[b])
+        {
+            ctx->set_error(std::string(what) + ": null buffer");
+            return false;
+        }
+        p[b] = reinterpret_cast<To *>(bufs[b]);
+    }
+    return true;
+}
+
 extern "C"
 {
 
@@ -221,19 +243,100 @@ int umx_hip_stream_set_layer(umx_hip_ctx *ctx, int layer, const float *host_src)
     return stream_layer_copy(ctx, layer, const_cast<float *>(host_src), false);
 }
 
-// The whole-track entry points fill one request record (umx_hip_ctx::TrackRequest, in its field order; its checks are tracks_once's).
+// ---------------------------------------------------------------- the whole-track entry points
+// The ladder umx_hip_separate_tracks, _rate, _mix, _io, _levels, _loudness and the one-track forms are ONE path: the options of the
+// call are checked and recorded once (track_options_checked -> umx_hip_ctx::TrackOptions), the request is filled once (track_request;
+// its checks are tracks_once's), and separate_tracks does both.  A rung is its own preconditions, then that path with the arguments it
+// does not have at their neutral values -- NULL rate, gains, io, records, UMX_CLIP_CLAMP -- so a wider rung with neutral arguments IS
+// the rung below, field for field, by construction.  The queue entry points share queue_entry the same way.
+static const char *mix_refusal(int n_out, const float *gains, MixSpec &spec) // (NULL gains are refused: who takes "no mix" asks before)
+{
+    return mix_spec_from(n_out, gains, &spec) >= 0 ? nullptr
+                                                   : "mix: need 1 <= n_out <= 4 rows of five finite gains (bass, drums, other, vocals slots, mixture)";
+}
+static bool mix_checked(umx_hip_ctx *ctx, int n_out, const float *gains, MixSpec &spec)
+{
+    const char *why = mix_refusal(n_out, gains, spec);
+    if (why)
+        ctx->set_error(why);
+    return !why;
+}
+
+// The options of a call, checked in this order: the sample formats (pcm16.h; io == NULL or fp32 both ways: the fp32 call itself), the
+// clip mode (levels.h), the gains (stem_mix.h; NULL: no mix).  true: `opt` holds them, `spec` the matrix behind opt.mix; false: the
+// refusal is the context's error.
+static bool track_options_checked(umx_hip_ctx *ctx, const umx_sample_io *io, int clip_mode, int n_out, const float *gains, MixSpec &spec,
+                                  umx_hip_ctx::TrackOptions &opt)
+{
+    const char *why = sample_io_refusal(io);
+    if (!why)
+        why = clip_mode_refusal(clip_mode);
+    if (!why && gains)
+        why = mix_refusal(n_out, gains, spec);
+    if (why)
+    {
+        ctx->set_error(why);
+        return false;
+    }
+    opt.mix = gains ? &spec : nullptr;
+    if (io)
+        opt.io = *io;
+    opt.clip_mode = clip_mode;
+    return true;
+}
+
+// (the request keeps its float pointers: the formats say how the driver reads them; a wanted record makes the tracks measure)
+static umx_hip_ctx::TrackRequest track_request(int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                                               const int *shift_offset, void *const *out_host, unsigned flags, void (*progress)(float, void *),
+                                               void *progress_user, const umx_hip_ctx::TrackOptions &opt, umx_levels *levels = nullptr,
+                                               umx_loudness *loudness = nullptr, double *const *hop_energy = nullptr)
+{
+    umx_hip_ctx::TrackRequest rq = {n_tracks, reinterpret_cast<const float *const *>(audio_host), length, rate, shift_offset,
+                                    reinterpret_cast<float *const *>(out_host), flags, progress, progress_user};
+    rq.opt = opt;
+    rq.opt.levels = levels != nullptr;
+    rq.opt.loudness = loudness || hop_energy; // the records or the energies themselves
+    rq.levels = levels;
+    rq.loudness = loudness;
+    rq.hop_energy = hop_energy;
+    return rq;
+}
+
+static int separate_tracks(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                           const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                           const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness, double *const *hop_energy,
+                           void (*progress)(float, void *), void *progress_user)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    MixSpec spec;
+    umx_hip_ctx::TrackOptions opt;
+    if (!track_options_checked(ctx, io, clip_mode, n_out, gains, spec, opt))
+        return UMX_ERR_ARG;
+    return ctx->tracks(track_request(n_tracks, audio_host, length, rate, shift_offset, out_host, flags, progress, progress_user, opt, levels,
+                                     loudness, hop_energy));
+}
+// the rungs without sample formats: fp32 buffers, no clip handling, nothing measured
+static int separate_tracks_f32(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *rate,
+                               const int *shift_offset, int n_out, const float *gains, float *const *out_host, unsigned flags,
+                               void (*progress)(float, void *), void *progress_user)
+{
+    return separate_tracks(ctx, n_tracks, reinterpret_cast<const void *const *>(audio_host), length, rate, shift_offset, n_out, gains,
+                           reinterpret_cast<void *const *>(out_host), flags, nullptr, UMX_CLIP_CLAMP, nullptr, nullptr, nullptr, progress,
+                           progress_user);
+}
+
 // A one-track entry point passes the addresses of its own arguments; shift offset < 0: no shift buffer (plain split_inference).
 int umx_hip_split_inference(umx_hip_ctx *ctx, const float *audio_host, int length, float *const out_host[4],
                             unsigned flags, void (*progress)(float, void *), void *progress_user)
 {
     const int no_shift = -1;
-    return ctx ? ctx->tracks({1, &audio_host, &length, nullptr, &no_shift, out_host, flags, progress, progress_user}) : UMX_ERR_ARG;
+    return separate_tracks_f32(ctx, 1, &audio_host, &length, nullptr, &no_shift, 4, nullptr, out_host, flags, progress, progress_user);
 }
 int umx_hip_separate_tracks(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *shift_offset,
                             float *const *out_host, unsigned flags, void (*progress)(float, void *), void *progress_user)
 {
-    return ctx ? ctx->tracks({n_tracks, audio_host, length, nullptr, shift_offset, out_host, flags, progress, progress_user})
-               : UMX_ERR_ARG;
+    return separate_tracks_f32(ctx, n_tracks, audio_host, length, nullptr, shift_offset, 4, nullptr, out_host, flags, progress, progress_user);
 }
 long long umx_hip_resampled_length(long long n, int rate_in, int rate_out) { return resampled_length(n, rate_in, rate_out); }
 
@@ -265,11 +368,9 @@ int umx_hip_resample_device(umx_hip_ctx *ctx, int rate_in, int rate_out, int n_b
 int umx_hip_shift_inference_rate(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int offset, float *const out_host[4],
                                  unsigned flags, void (*progress)(float, void *), void *progress_user)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
     if (offset < 0)
         offset = UMX_REFERENCE_SHIFT;
-    return ctx->tracks({1, &audio_host, &length, &rate, &offset, out_host, flags, progress, progress_user});
+    return separate_tracks_f32(ctx, 1, &audio_host, &length, &rate, &offset, 4, nullptr, out_host, flags, progress, progress_user);
 }
 int umx_hip_separate_tracks_rate(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *rate,
                                  const int *shift_offset, float *const *out_host, unsigned flags, void (*progress)(float, void *),
@@ -277,7 +378,7 @@ int umx_hip_separate_tracks_rate(umx_hip_ctx *ctx, int n_tracks, const float *co
 {
     if (!ctx || !rate)
         return UMX_ERR_ARG;
-    return ctx->tracks({n_tracks, audio_host, length, rate, shift_offset, out_host, flags, progress, progress_user});
+    return separate_tracks_f32(ctx, n_tracks, audio_host, length, rate, shift_offset, 4, nullptr, out_host, flags, progress, progress_user);
 }
 
 int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase, int *first_offset)
@@ -302,11 +403,9 @@ int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t c
 int umx_hip_shift_inference(umx_hip_ctx *ctx, const float *audio_host, int length, int offset, float *const out_host[4],
                             unsigned flags, void (*progress)(float, void *), void *progress_user)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
     if (offset < 0)
         offset = UMX_REFERENCE_SHIFT; // umx.cpp:115: rand() % 22050, never seeded in the reference (see umx_hip.h)
-    return ctx->tracks({1, &audio_host, &length, nullptr, &offset, out_host, flags, progress, progress_user});
+    return separate_tracks_f32(ctx, 1, &audio_host, &length, nullptr, &offset, 4, nullptr, out_host, flags, progress, progress_user);
 }
 
 // the default offsets of a K-shift ensemble: K steps of MAX_SHIFT / K from `first` on, wrapped into the shift buffer
@@ -322,13 +421,17 @@ int umx_hip_ensemble_offsets(int n_shifts, int first, int *offsets_out)
 }
 
 // the one track as lanes 0 .. K-1 of the whole-track driver, lane k at offsets[k]; K = 1 IS umx_hip_shift_inference_rate
-// mix: out_host holds mix->n_out buffers, the mix of the mean
-static int shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets,
-                          float *const *out_host, unsigned flags, void (*progress)(float, void *), void *progress_user, const MixSpec *mix)
+// mix (gains == NULL: none): out_host holds n_out buffers, the mix of the mean
+static int shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets, int n_out,
+                          const float *gains, float *const *out_host, unsigned flags, void (*progress)(float, void *), void *progress_user)
 {
-    if (!umx_hip_ctx::track_job_ok(audio_host, length, 0, out_host, mix ? mix->n_out : 4))
+    MixSpec spec;
+    umx_hip_ctx::TrackOptions opt;
+    if (!track_options_checked(ctx, nullptr, UMX_CLIP_CLAMP, n_out, gains, spec, opt))
+        return UMX_ERR_ARG;
+    if (!umx_hip_ctx::track_job_ok(audio_host, length, 0, out_host, opt.n_host()))
     {
-        ctx->set_error(mix ? "shift ensemble: need audio, n_out outputs and length >= 1" : "shift ensemble: need audio, four outputs and length >= 1");
+        ctx->set_error(gains ? "shift ensemble: need audio, n_out outputs and length >= 1" : "shift ensemble: need audio, four outputs and length >= 1");
         return UMX_ERR_ARG;
     }
     if (n_shifts < 1 || n_shifts > UMX_MAX_SHIFTS || n_shifts > ctx->B)
@@ -354,7 +457,7 @@ static int shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length,
         }
         off[k] = offsets[k];
     }
-    const float *audio[UMX_MAX_SHIFTS];
+    const void *audio[UMX_MAX_SHIFTS];
     int lengths[UMX_MAX_SHIFTS], rates[UMX_MAX_SHIFTS];
     for (int k = 0; k < n_shifts; ++k)
     {
@@ -362,111 +465,77 @@ static int shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length,
         lengths[k] = length;
         rates[k] = rate;
     }
-    umx_hip_ctx::TrackRequest rq = {n_shifts, audio, lengths, rates, off, out_host, flags, progress, progress_user};
+    umx_hip_ctx::TrackRequest rq = track_request(n_shifts, audio, lengths, rates, off, reinterpret_cast<void *const *>(out_host), flags, progress,
+                                                 progress_user, opt);
     rq.ensemble = n_shifts > 1;
-    rq.mix = mix;
     return ctx->tracks(rq);
 }
 int umx_hip_shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets,
                            float *const out_host[4], unsigned flags, void (*progress)(float, void *), void *progress_user)
 {
-    return ctx ? shift_ensemble(ctx, audio_host, length, rate, n_shifts, offsets, out_host, flags, progress, progress_user, nullptr) : UMX_ERR_ARG;
+    return ctx ? shift_ensemble(ctx, audio_host, length, rate, n_shifts, offsets, 4, nullptr, out_host, flags, progress, progress_user) : UMX_ERR_ARG;
 }
 
 // ---------------------------------------------------------------- stem mix matrix (stem_mix.h)
 int umx_hip_mix_columns(int n_out, const float *gains) { return mix_spec_from(n_out, gains, nullptr); }
 
-static bool mix_checked(umx_hip_ctx *ctx, int n_out, const float *gains, MixSpec &spec)
-{
-    if (mix_spec_from(n_out, gains, &spec) >= 0)
-        return true;
-    ctx->set_error("mix: need 1 <= n_out <= 4 rows of five finite gains (bass, drums, other, vocals slots, mixture)");
-    return false;
-}
-
+// (the two entry points that ARE the mix refuse NULL gains, in the mix's words; the wider rungs read them as "no mix")
 int umx_hip_separate_tracks_mix(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *rate,
                                 const int *shift_offset, int n_out, const float *gains, float *const *out_host, unsigned flags,
                                 void (*progress)(float, void *), void *progress_user)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
     MixSpec spec;
-    if (!mix_checked(ctx, n_out, gains, spec))
+    if (!ctx || (!gains && !mix_checked(ctx, n_out, gains, spec)))
         return UMX_ERR_ARG;
-    umx_hip_ctx::TrackRequest rq = {n_tracks, audio_host, length, rate, shift_offset, out_host, flags, progress, progress_user};
-    rq.mix = &spec;
-    return ctx->tracks(rq);
+    return separate_tracks_f32(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, progress, progress_user);
 }
 
 int umx_hip_shift_ensemble_mix(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int n_shifts, const int *offsets, int n_out,
                                const float *gains, float *const *out_host, unsigned flags, void (*progress)(float, void *),
                                void *progress_user)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
     MixSpec spec;
-    if (!mix_checked(ctx, n_out, gains, spec))
+    if (!ctx || (!gains && !mix_checked(ctx, n_out, gains, spec)))
         return UMX_ERR_ARG;
-    return shift_ensemble(ctx, audio_host, length, rate, n_shifts, offsets, out_host, flags, progress, progress_user, &spec);
+    return shift_ensemble(ctx, audio_host, length, rate, n_shifts, offsets, n_out, gains, out_host, flags, progress, progress_user);
 }
 
 // ---------------------------------------------------------------- track queue (engine_queue.h)
-int umx_hip_separate_queue(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_done_fn done, void *user, int n_out, const float *gains,
-                           unsigned flags)
+// The four queue entry points differ in their done callback, and with it in what every job measures: a levels or loudness callback
+// makes every job measure.  Their options are checked as a track call's.
+static int queue_entry(umx_hip_ctx *ctx, umx_queue_next_fn next, const umx_hip_ctx::QueueDone &done, void *user, int n_out, const float *gains,
+                       unsigned flags, const umx_sample_io *io, int clip_mode)
 {
     if (!ctx)
         return UMX_ERR_ARG;
     MixSpec spec;
-    if (gains && !mix_checked(ctx, n_out, gains, spec))
+    umx_hip_ctx::TrackOptions opt;
+    if (!track_options_checked(ctx, io, clip_mode, n_out, gains, spec, opt))
         return UMX_ERR_ARG;
-    umx_hip_ctx::QueueDone qd;
-    qd.plain = done;
-    return ctx->queue(next, qd, user, gains ? &spec : nullptr, flags, umx_sample_io{});
+    opt.levels = done.with_levels || done.with_loudness;
+    opt.loudness = done.with_loudness != nullptr;
+    return ctx->queue(next, done, user, opt, flags);
+}
+int umx_hip_separate_queue(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_done_fn done, void *user, int n_out, const float *gains,
+                           unsigned flags)
+{
+    return queue_entry(ctx, next, {done, nullptr, nullptr}, user, n_out, gains, flags, nullptr, UMX_CLIP_CLAMP);
 }
 
 // ---------------------------------------------------------------- 16-bit PCM in and out (pcm16.h)
 // io == NULL or fp32 both ways: the fp32 call itself
-static bool sample_io_checked(umx_hip_ctx *ctx, const umx_sample_io *io)
-{
-    const char *why = sample_io_refusal(io);
-    if (why)
-        ctx->set_error(why);
-    return !why;
-}
-
 int umx_hip_separate_tracks_io(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
                                const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
                                const umx_sample_io *io, void (*progress)(float, void *), void *progress_user)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
-    if (!sample_io_checked(ctx, io))
-        return UMX_ERR_ARG;
-    MixSpec spec;
-    if (gains && !mix_checked(ctx, n_out, gains, spec))
-        return UMX_ERR_ARG;
-    // (the request keeps its float pointers: the formats say how the driver reads them)
-    umx_hip_ctx::TrackRequest rq = {n_tracks, reinterpret_cast<const float *const *>(audio_host), length, rate, shift_offset,
-                                    reinterpret_cast<float *const *>(out_host), flags, progress, progress_user};
-    rq.mix = gains ? &spec : nullptr;
-    if (io)
-        rq.io = *io;
-    return ctx->tracks(rq);
+    return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, UMX_CLIP_CLAMP, nullptr, nullptr,
+                           nullptr, progress, progress_user);
 }
 
 int umx_hip_separate_queue_io(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_done_fn done, void *user, int n_out, const float *gains,
                               unsigned flags, const umx_sample_io *io)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
-    if (!sample_io_checked(ctx, io))
-        return UMX_ERR_ARG;
-    MixSpec spec;
-    if (gains && !mix_checked(ctx, n_out, gains, spec))
-        return UMX_ERR_ARG;
-    umx_hip_ctx::QueueDone qd;
-    qd.plain = done;
-    return ctx->queue(next, qd, user, gains ? &spec : nullptr, flags, io ? *io : umx_sample_io{});
+    return queue_entry(ctx, next, {done, nullptr, nullptr}, user, n_out, gains, flags, io, UMX_CLIP_CLAMP);
 }
 
 int umx_hip_pcm16_decode_device(umx_hip_ctx *ctx, const int16_t *in_dev, int n, float *out_dev, void *hip_stream)
@@ -484,30 +553,27 @@ int umx_hip_pcm16_decode_device(umx_hip_ctx *ctx, const int16_t *in_dev, int n, 
     return UMX_OK;
 }
 
+// the dither of an int16 output as the kernels and their host restatements take it (io == NULL: none)
+struct DitherArg
+{
+    bool on;
+    uint32_t seed;
+};
+static DitherArg dither_of(const umx_sample_io *io) { return {io && io->dither, io ? io->dither_seed : 0u}; }
+
 int umx_hip_pcm16_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
                                 const umx_sample_io *io, int16_t *const *out_dev, void *hip_stream)
 {
     if (!ctx)
         return UMX_ERR_ARG;
-    if (n_buffers < 1 || n_buffers > 4 || !in_dev || !out_dev || n < 1 || first_frame < 0)
-    {
-        ctx->set_error("pcm16 encode: need 1 .. 4 buffers, n >= 1 and first_frame >= 0");
-        return UMX_ERR_ARG;
-    }
     const float2 *src[4] = {};
     uint32_t *dst[4] = {};
-    for (int b = 0; b < n_buffers; ++b)
-    {
-        if (!in_dev[b] || !out_dev[b])
-        {
-            ctx->set_error("pcm16 encode: null buffer");
-            return UMX_ERR_ARG;
-        }
-        src[b] = reinterpret_cast<const float2 *>(in_dev[b]);
-        dst[b] = reinterpret_cast<uint32_t *>(out_dev[b]);
-    }
+    if (!device_buffers(ctx, "pcm16 encode", n_buffers, in_dev, n, first_frame, src) ||
+        !device_buffers(ctx, "pcm16 encode", n_buffers, out_dev, n, first_frame, dst))
+        return UMX_ERR_ARG;
     UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
-    launch_pcm16_encode(n_buffers, src, dst, n, first_frame, io && io->dither, io ? io->dither_seed : 0u, (hipStream_t)hip_stream);
+    const DitherArg d = dither_of(io);
+    launch_pcm16_encode(n_buffers, src, dst, n, first_frame, d.on, d.seed, (hipStream_t)hip_stream);
     UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
     return UMX_OK;
 }
@@ -525,80 +591,28 @@ int umx_hip_pcm16_encode_host(const float *x, int n_frames, int buffer, long lon
 {
     if (!x || !q || n_frames < 0 || buffer < 0 || buffer >= UMX_MAX_MIX_OUTPUTS || first_frame < 0)
         return UMX_ERR_ARG;
-    const bool dither = io && io->dither;
-    const uint32_t seed = io ? io->dither_seed : 0u;
-    const uint32_t key[2] = {pcm16_dither_key(seed, buffer, 0), pcm16_dither_key(seed, buffer, 1)};
+    const DitherArg d = dither_of(io);
+    const uint32_t key[2] = {pcm16_dither_key(d.seed, buffer, 0), pcm16_dither_key(d.seed, buffer, 1)};
     for (int i = 0; i < n_frames; ++i)
         for (int ch = 0; ch < 2; ++ch)
-            q[2 * (size_t)i + ch] = pcm16_encode(x[2 * (size_t)i + ch], dither, key[ch], first_frame + i);
+            q[2 * (size_t)i + ch] = pcm16_encode(x[2 * (size_t)i + ch], d.on, key[ch], first_frame + i);
     return UMX_OK;
 }
 // ---------------------------------------------------------------- output levels and clip handling (levels.h)
-static bool clip_mode_checked(umx_hip_ctx *ctx, int clip_mode)
-{
-    const char *why = clip_mode_refusal(clip_mode);
-    if (why)
-        ctx->set_error(why);
-    return !why;
-}
-
 // clip_mode == UMX_CLIP_CLAMP and levels == NULL: the request of umx_hip_separate_tracks_io, field for field
 int umx_hip_separate_tracks_levels(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
                                    const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
                                    const umx_sample_io *io, int clip_mode, umx_levels *levels, void (*progress)(float, void *),
                                    void *progress_user)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
-    if (!sample_io_checked(ctx, io) || !clip_mode_checked(ctx, clip_mode))
-        return UMX_ERR_ARG;
-    MixSpec spec;
-    if (gains && !mix_checked(ctx, n_out, gains, spec))
-        return UMX_ERR_ARG;
-    umx_hip_ctx::TrackRequest rq = {n_tracks, reinterpret_cast<const float *const *>(audio_host), length, rate, shift_offset,
-                                    reinterpret_cast<float *const *>(out_host), flags, progress, progress_user};
-    rq.mix = gains ? &spec : nullptr;
-    if (io)
-        rq.io = *io;
-    rq.clip_mode = clip_mode;
-    rq.levels = levels;
-    return ctx->tracks(rq);
+    return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, clip_mode, levels, nullptr, nullptr,
+                           progress, progress_user);
 }
 
 int umx_hip_separate_queue_levels(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_levels_fn done, void *user, int n_out,
                                   const float *gains, unsigned flags, const umx_sample_io *io, int clip_mode)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
-    if (!sample_io_checked(ctx, io) || !clip_mode_checked(ctx, clip_mode))
-        return UMX_ERR_ARG;
-    MixSpec spec;
-    if (gains && !mix_checked(ctx, n_out, gains, spec))
-        return UMX_ERR_ARG;
-    umx_hip_ctx::QueueDone qd;
-    qd.with_levels = done;
-    qd.clip_mode = clip_mode;
-    return ctx->queue(next, qd, user, gains ? &spec : nullptr, flags, io ? *io : umx_sample_io{});
-}
-
-// 1 .. 4 non-null device buffers of a kernel's entry point -> p[]; false: refused (set_error done)
-static bool levels_buffers(umx_hip_ctx *ctx, const char *what, int n_buffers, const void *const *bufs, int n, long long first_frame, const void *p[4])
-{
-    if (n_buffers < 1 || n_buffers > 4 || !bufs || n < 1 || first_frame < 0)
-    {
-        ctx->set_error(std::string(what) + ": need 1 .. 4 buffers, n >= 1 and first_frame >= 0");
-        return false;
-    }
-    for (int b = 0; b < n_buffers; ++b)
-    {
-        if (!bufs[b])
-        {
-            ctx->set_error(std::string(what) + ": null buffer");
-            return false;
-        }
-        p[b] = bufs[b];
-    }
-    return true;
+    return queue_entry(ctx, next, {nullptr, done, nullptr}, user, n_out, gains, flags, io, clip_mode);
 }
 
 int umx_hip_levels_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
@@ -606,20 +620,17 @@ int umx_hip_levels_device(umx_hip_ctx *ctx, int n_buffers, const float *const *i
 {
     if (!ctx)
         return UMX_ERR_ARG;
-    const void *in[4] = {};
-    if (!levels_buffers(ctx, "levels", n_buffers, reinterpret_cast<const void *const *>(in_dev), n, first_frame, in))
-        return UMX_ERR_ARG;
     const float2 *src[4] = {};
-    for (int b = 0; b < n_buffers; ++b)
-        src[b] = static_cast<const float2 *>(in[b]);
+    if (!device_buffers(ctx, "levels", n_buffers, in_dev, n, first_frame, src))
+        return UMX_ERR_ARG;
     if (!acc_dev)
     {
         ctx->set_error("levels: null record");
         return UMX_ERR_ARG;
     }
     UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
-    launch_stem_levels(n_buffers, src, n, first_frame, io && io->out_format == UMX_SAMPLE_S16, io && io->dither, io ? io->dither_seed : 0u, acc_dev,
-                       (hipStream_t)hip_stream);
+    const DitherArg d = dither_of(io);
+    launch_stem_levels(n_buffers, src, n, first_frame, io && io->out_format == UMX_SAMPLE_S16, d.on, d.seed, acc_dev, (hipStream_t)hip_stream);
     UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
     return UMX_OK;
 }
@@ -629,24 +640,19 @@ int umx_hip_pcm16_encode_rescaled_device(umx_hip_ctx *ctx, int n_buffers, const 
 {
     if (!ctx)
         return UMX_ERR_ARG;
-    const void *in[4] = {}, *out[4] = {};
-    if (!levels_buffers(ctx, "rescaled pcm16 encode", n_buffers, reinterpret_cast<const void *const *>(in_dev), n, first_frame, in) ||
-        !levels_buffers(ctx, "rescaled pcm16 encode", n_buffers, reinterpret_cast<const void *const *>(out_dev), n, first_frame, out))
-        return UMX_ERR_ARG;
     const float2 *src[4] = {};
     uint32_t *dst[4] = {};
-    for (int b = 0; b < n_buffers; ++b)
-    {
-        src[b] = static_cast<const float2 *>(in[b]);
-        dst[b] = static_cast<uint32_t *>(const_cast<void *>(out[b]));
-    }
+    if (!device_buffers(ctx, "rescaled pcm16 encode", n_buffers, in_dev, n, first_frame, src) ||
+        !device_buffers(ctx, "rescaled pcm16 encode", n_buffers, out_dev, n, first_frame, dst))
+        return UMX_ERR_ARG;
     if (!acc_dev)
     {
         ctx->set_error("rescaled pcm16 encode: null record");
         return UMX_ERR_ARG;
     }
     UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
-    launch_pcm16_encode_rescaled(n_buffers, src, dst, n, first_frame, io && io->dither, io ? io->dither_seed : 0u, acc_dev, (hipStream_t)hip_stream);
+    const DitherArg d = dither_of(io);
+    launch_pcm16_encode_rescaled(n_buffers, src, dst, n, first_frame, d.on, d.seed, acc_dev, (hipStream_t)hip_stream);
     UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
     return UMX_OK;
 }
@@ -655,12 +661,9 @@ int umx_hip_rescale_device(umx_hip_ctx *ctx, int n_buffers, float *const *bufs_d
 {
     if (!ctx)
         return UMX_ERR_ARG;
-    const void *in[4] = {};
-    if (!levels_buffers(ctx, "rescale", n_buffers, reinterpret_cast<const void *const *>(bufs_dev), n, 0, in))
-        return UMX_ERR_ARG;
     float2 *p[4] = {};
-    for (int b = 0; b < n_buffers; ++b)
-        p[b] = static_cast<float2 *>(const_cast<void *>(in[b]));
+    if (!device_buffers(ctx, "rescale", n_buffers, bufs_dev, n, 0, p))
+        return UMX_ERR_ARG;
     if (!acc_dev)
     {
         ctx->set_error("rescale: null record");
@@ -677,7 +680,8 @@ int umx_hip_levels_host(const float *x, int n_frames, int buffer, long long firs
 {
     if (!x || !acc || n_frames < 0 || buffer < 0 || buffer >= UMX_MAX_MIX_OUTPUTS || first_frame < 0)
         return UMX_ERR_ARG;
-    levels_host(x, n_frames, buffer, first_frame, io && io->out_format == UMX_SAMPLE_S16, io && io->dither, io ? io->dither_seed : 0u, clip_divisor, *acc);
+    const DitherArg d = dither_of(io);
+    levels_host(x, n_frames, buffer, first_frame, io && io->out_format == UMX_SAMPLE_S16, d.on, d.seed, clip_divisor, *acc);
     return UMX_OK;
 }
 
@@ -696,39 +700,14 @@ int umx_hip_separate_tracks_loudness(umx_hip_ctx *ctx, int n_tracks, const void 
                                      const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,
                                      double *const *hop_energy, void (*progress)(float, void *), void *progress_user)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
-    if (!sample_io_checked(ctx, io) || !clip_mode_checked(ctx, clip_mode))
-        return UMX_ERR_ARG;
-    MixSpec spec;
-    if (gains && !mix_checked(ctx, n_out, gains, spec))
-        return UMX_ERR_ARG;
-    umx_hip_ctx::TrackRequest rq = {n_tracks, reinterpret_cast<const float *const *>(audio_host), length, rate, shift_offset,
-                                    reinterpret_cast<float *const *>(out_host), flags, progress, progress_user};
-    rq.mix = gains ? &spec : nullptr;
-    if (io)
-        rq.io = *io;
-    rq.clip_mode = clip_mode;
-    rq.levels = levels;
-    rq.loudness = loudness;
-    rq.hop_energy = hop_energy;
-    return ctx->tracks(rq);
+    return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, clip_mode, levels, loudness,
+                           hop_energy, progress, progress_user);
 }
 
 int umx_hip_separate_queue_loudness(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_loudness_fn done, void *user, int n_out,
                                     const float *gains, unsigned flags, const umx_sample_io *io, int clip_mode)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
-    if (!sample_io_checked(ctx, io) || !clip_mode_checked(ctx, clip_mode))
-        return UMX_ERR_ARG;
-    MixSpec spec;
-    if (gains && !mix_checked(ctx, n_out, gains, spec))
-        return UMX_ERR_ARG;
-    umx_hip_ctx::QueueDone qd;
-    qd.with_loudness = done;
-    qd.clip_mode = clip_mode;
-    return ctx->queue(next, qd, user, gains ? &spec : nullptr, flags, io ? *io : umx_sample_io{});
+    return queue_entry(ctx, next, {nullptr, nullptr, done}, user, n_out, gains, flags, io, clip_mode);
 }
 
 int umx_hip_kweight_hops_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, int rate, long long first_hop,
@@ -741,8 +720,8 @@ int umx_hip_kweight_hops_device(umx_hip_ctx *ctx, int n_buffers, const float *co
         ctx->set_error("k-weighted hops: sample rate outside 8000 .. 192000 Hz");
         return UMX_ERR_ARG;
     }
-    const void *in[4] = {};
-    if (!levels_buffers(ctx, "k-weighted hops", n_buffers, reinterpret_cast<const void *const *>(in_dev), n, 0, in))
+    const float2 *src[4] = {};
+    if (!device_buffers(ctx, "k-weighted hops", n_buffers, in_dev, n, 0, src))
         return UMX_ERR_ARG;
     const int hop = kweight_hop(rate);
     const long long hops_total = n / hop;
@@ -751,9 +730,6 @@ int umx_hip_kweight_hops_device(umx_hip_ctx *ctx, int n_buffers, const float *co
         ctx->set_error("k-weighted hops: need E, n <= 2^30 - 1 and 0 <= first_hop, first_hop + n_hops <= n / hop");
         return UMX_ERR_ARG;
     }
-    const float2 *src[4] = {};
-    for (int b = 0; b < n_buffers; ++b)
-        src[b] = static_cast<const float2 *>(in[b]);
     UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
     launch_kweight_hops(n_buffers, src, kweight_coeffs(rate), hop, hops_total, first_hop, n_hops, E_dev, (hipStream_t)hip_stream);
     UMX_HIP_CHECK_CTX(ctx, hipGetLastError());

@@ -2,8 +2,9 @@
 // umx_hip_separate_queue: more tracks than lanes, of different lengths, a lane refilled with the next track the moment one ends.
 // This file holds what only a queue has: the schedule (QueueSchedule, umx_hip_queue_plan), the pool of accumulator sets lent to the
 // jobs in flight, the in-stream zeroing of a refilled lane, the download of the previous call's regions behind every call, and the
-// restart after a timeout.  A job's checks and geometry, the body of a call and the region list are those of engine_tracks.h
-// (track_job_ok, track_geometry, track_call, TrackRegions).  Included by engine.hip behind engine_tracks.h; not a stand-alone header.
+// restart after a timeout.  A job's checks, geometry and admission, the body of a call and the region list are those of engine_tracks.h
+// (track_job_ok, track_geometry, admit_job, track_call, TrackRegions); the options of a run are the TrackOptions record of engine.hip,
+// which every job keeps.  Included by engine.hip behind engine_tracks.h; not a stand-alone header.
 // ---------------------------------------------------------------- track queue
 namespace
 {
@@ -67,7 +68,7 @@ int queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_out, int
 }
 } // namespace
 
-int umx_hip_ctx::queue(umx_queue_next_fn next, const QueueDone &done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io)
+int umx_hip_ctx::queue(umx_queue_next_fn next, const QueueDone &done, void *user, const TrackOptions &opt, unsigned flags)
 {
     if (!next || (!done.plain && !done.with_levels && !done.with_loudness))
     {
@@ -100,13 +101,12 @@ int umx_hip_ctx::queue(umx_queue_next_fn next, const QueueDone &done, void *user
     TrackRun run(*this);
     pending.clear();
     pending_lost = true;
-    return queue_run(next, done, user, mix, flags, io);
+    return queue_run(next, done, user, opt, flags);
 }
 
-int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *user, const MixSpec *mix, unsigned flags, const umx_sample_io &io)
+int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *user, const TrackOptions &opt, unsigned flags)
 {
-    const bool rescale = done.clip_mode == UMX_CLIP_RESCALE, measure = done.measures() || rescale;
-    const int n_host = mix ? mix->n_out : 4;
+    const int n_host = opt.n_host();
     const int stride = track_stride();
     const size_t n_sets = (size_t)B + 2;
     if (qpool.size() < n_sets)
@@ -171,7 +171,7 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
             if (e == hipSuccess) // (also for a region that is all shift padding: the set is not lent again while the device works on it)
                 e = hipEventSynchronize(r.ready);
             if (e == hipSuccess)
-                e = track_region_download(r, n_host, jb.job.out);
+                e = track_region_download(r, jb.job.out);
             (void)hipEventDestroy(r.ready);
             r.ready = nullptr;
             if (--jb.regions_left == 0)
@@ -209,7 +209,7 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
         }
         for (Job *jb : finished)
         {
-            if (done.measures()) // the job's records, behind its last region
+            if (opt.levels) // the job's records, behind its last region
             {
                 umx_levels lv;
                 umx_loudness ld;
@@ -299,23 +299,9 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
                     return fail(UMX_ERR_ARG);
                 }
                 const int set = free_set((size_t)tj.L2);
-                if (int rc = track_bufs_grow(qpool[set], (size_t)tj.L2))
+                // (a queue's jobs are at 44.1 kHz; a rescaled one is one whole-track region, queued with its last segment)
+                if (int rc = admit_job(tj, qpool[set], opt, j.audio, RS_MODEL_RATE, tj.length, false))
                     return fail(rc);
-                if (int rc = track_pcm16_grow(qpool[set], io, (size_t)tj.length, n_host)) // (nothing for an fp32 run)
-                    return fail(rc);
-                if (measure)
-                    if (int rc = track_levels_grow(qpool[set]))
-                        return fail(rc);
-                if (done.with_loudness) // (a queue's jobs are at 44.1 kHz)
-                    if (int rc = track_loudness_grow(qpool[set], tj, RS_MODEL_RATE, tj.length, n_host))
-                        return fail(rc);
-                tj.audio = j.audio;
-                tj.io = io;
-                tj.clip_mode = done.clip_mode;
-                tj.levels = measure;
-                tj.by_region = !rescale; // (a rescaled job: one whole-track region, queued with its last segment)
-                tj.whole_region = rescale;
-                tj.acc = &qpool[set];
                 jb = &jobs[set];
                 static_cast<TrackJob &>(*jb) = tj;
                 jb->job = j;
@@ -374,15 +360,15 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
                 sp.n[7] = state_floats();
                 sp.count = TRACK_BEGIN_SPANS;
                 launch_track_begin(sp, st);
-                if (jb->levels) // ... and the set's record of what leaves (also on a restart: the job measures from zero again)
+                if (jb->opt.measures()) // ... and the set's record of what leaves (also on a restart: the job measures from zero again)
                     (void)hipMemsetAsync(tb_.lev, 0, sizeof(umx_levels_acc), st);
-                if (jb->loudness) // ... and its hop energies
+                if (jb->opt.loudness) // ... and its hop energies
                     (void)hipMemsetAsync(tb_.hopE, 0, sizeof(double) * std::max<size_t>(1, (size_t)n_host * 2 * (size_t)jb->loud_hops), st);
             }
             nl = ln + 1;
         }
         pending_lost = true;
-        if (int rc = track_call(lanes, nl, flags, mix, last_slot, cur))
+        if (int rc = track_call(lanes, nl, flags, last_slot, cur))
             return fail(rc);
         ++queue_calls;
         for (int ln = 0; ln < nl; ++ln)

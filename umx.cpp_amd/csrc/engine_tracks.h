@@ -1,6 +1,8 @@
 // engine_tracks.h -- part of engine.hip (one translation unit: the kernels inline into their launchers): whole tracks on the device.
 // What every whole-track driver shares, stated once each -- the checks of a job (track_job_ok), its padded geometry (track_geometry),
-// the grow-only buffers (grow_frames), the body of one segment call (track_call) and the list of finished regions that owns its
+// the grow-only buffers (grow_only, on dfree, the one release beside dalloc), the admission of a job with the options of its call
+// (admit_job: what grows, in which order, and the by_region / whole_region rules; TrackOptions, engine.hip), what a finished span goes
+// through on its way out (track_leave), the body of one segment call (track_call) and the list of finished regions that owns its
 // events (TrackRegions, engine.hip) -- and the driver of umx_hip_split_inference / umx_hip_shift_inference / umx_hip_separate_tracks* /
 // umx_hip_shift_ensemble* (tracks, tracks_once): one track per lane, or the segments of one track as the lanes (reset mode).
 // The track queue is the other driver (engine_queue.h).  Included by engine.hip behind the definition of umx_hip_ctx; not a
@@ -51,21 +53,18 @@ bool umx_hip_ctx::track_geometry(int length, int shift_offset, int stride, Track
     return true;
 }
 
-// Grow-only device buffers: every pointer of `bufs` has room for (its floats per frame) x `frames`; `cap`: the frames they hold now.
-// Too small: all are freed and allocated again with an eighth to spare (their contents are lost).
-int umx_hip_ctx::grow_frames(std::initializer_list<std::pair<float **, int>> bufs, size_t &cap, size_t frames)
+// The grow-only device buffers of the whole-track drivers (declared in engine.hip): the accumulators and stagings (floats per frame), the
+// int16 side (a word per frame), the hop energies (doubles).
+template <class T_> int umx_hip_ctx::grow_only(std::initializer_list<std::pair<T_ **, int>> bufs, size_t &cap, size_t units)
 {
-    if (frames <= cap)
+    if (units <= cap)
         return UMX_OK;
     for (const auto &b : bufs)
         if (*b.first)
-        {
-            allocs.erase(std::find(allocs.begin(), allocs.end(), (void *)*b.first));
-            (void)hipFree(*b.first);
-            *b.first = nullptr;
-        }
+            if (int rc = dfree(*b.first))
+                return rc;
     cap = 0;
-    const size_t want = frames + frames / 8;
+    const size_t want = units + units / 8;
     for (const auto &b : bufs)
         if (int rc = dalloc(b.first, (size_t)b.second * want, false))
             return rc;
@@ -76,36 +75,18 @@ int umx_hip_ctx::grow_frames(std::initializer_list<std::pair<float **, int>> buf
 // the accumulators of one track: the (shifted) track, 4 stems, the weight sum, `frames` frames each
 int umx_hip_ctx::track_bufs_grow(TrackBufs &tb_, size_t frames)
 {
-    return grow_frames({{&tb_.in, 2}, {&tb_.out[0], 2}, {&tb_.out[1], 2}, {&tb_.out[2], 2}, {&tb_.out[3], 2}, {&tb_.sumw, 1}}, tb_.cap, frames);
+    return grow_only<float>({{&tb_.in, 2}, {&tb_.out[0], 2}, {&tb_.out[1], 2}, {&tb_.out[2], 2}, {&tb_.out[3], 2}, {&tb_.sumw, 1}}, tb_.cap, frames);
 }
 
-// one grow-only buffer of `frames` int16 frames (a word each); too small: freed and allocated again with an eighth to spare
-int umx_hip_ctx::grow_words(uint32_t *&p, size_t &cap, size_t frames)
-{
-    if (frames <= cap)
-        return UMX_OK;
-    if (p)
-    {
-        allocs.erase(std::find(allocs.begin(), allocs.end(), (void *)p));
-        (void)hipFree(p);
-        p = nullptr;
-    }
-    cap = 0;
-    const size_t want = frames + frames / 8;
-    if (int rc = dalloc(&p, want, false))
-        return rc;
-    cap = want;
-    return UMX_OK;
-}
-
-// the int16 side of an accumulator set for a job of `frames` frames at the caller's rate: the staging of its upload, n_host outputs
+// the int16 side of an accumulator set for a job of `frames` frames at the caller's rate (a word each): the staging of its
+// upload, n_host outputs, each grow-only on its own
 int umx_hip_ctx::track_pcm16_grow(TrackBufs &tb_, const umx_sample_io &io, size_t frames, int n_host)
 {
     if (io.in_format == UMX_SAMPLE_S16)
-        if (int rc = grow_words(tb_.in16, tb_.cap_in16, frames))
+        if (int rc = grow_only<uint32_t>({{&tb_.in16, 1}}, tb_.cap_in16, frames))
             return rc;
     for (int t = 0; t < n_host && io.out_format == UMX_SAMPLE_S16; ++t)
-        if (int rc = grow_words(tb_.out16[t], tb_.cap_out16[t], frames))
+        if (int rc = grow_only<uint32_t>({{&tb_.out16[t], 1}}, tb_.cap_out16[t], frames))
             return rc;
     return UMX_OK;
 }
@@ -138,11 +119,13 @@ int umx_hip_ctx::track_levels_grow(TrackBufs &tb_)
 // A job with loudness: first of all, and before any divisor, the hops that these frames complete are launched -- hop b once
 // frame (b + 1) hop - 1 is final.  Their warm-up reads frames of the spans before this one: those are still in `src`, at their frame
 // numbers (the int16 copy goes elsewhere, a mix was written in place before its span left), so frame 0 is at src_start - first_frame.
-void umx_hip_ctx::track_leave(TrackJob &j, int n_host, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st)
+void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st)
 {
     const TrackBufs &tb_ = *j.acc;
-    const bool s16 = j.io.out_format == UMX_SAMPLE_S16, rescale = j.clip_mode == UMX_CLIP_RESCALE;
-    if (j.loudness)
+    const umx_sample_io &io = j.opt.io;
+    const int n_host = j.opt.n_host();
+    const bool s16 = io.out_format == UMX_SAMPLE_S16, rescale = j.opt.rescale();
+    if (j.opt.loudness)
     {
         const int hop = kweight_hop(j.loud_rate);
         const long long final_hops = std::min<long long>((first_frame + count) / hop, j.loud_hops);
@@ -155,10 +138,10 @@ void umx_hip_ctx::track_leave(TrackJob &j, int n_host, float *const src[4], size
             j.hops_done = final_hops;
         }
     }
-    if (!j.levels && !rescale)
+    if (!j.opt.measures())
     {
         if (s16)
-            track_encode(tb_, j.io, n_host, src, src_start, count, first_frame, st);
+            track_encode(tb_, io, n_host, src, src_start, count, first_frame, st);
         return;
     }
     const float2 *s[4] = {};
@@ -170,14 +153,14 @@ void umx_hip_ctx::track_leave(TrackJob &j, int n_host, float *const src[4], size
         d[t] = s16 ? tb_.out16[t] + first_frame : nullptr;
     }
     // (a rescaled int16 track: its encode counts what it clamps itself, with the divisor it forms)
-    launch_stem_levels(n_host, s, count, first_frame, s16 && !rescale, j.io.dither != 0, j.io.dither_seed, tb_.lev, st);
+    launch_stem_levels(n_host, s, count, first_frame, s16 && !rescale, io.dither != 0, io.dither_seed, tb_.lev, st);
     if (!rescale)
     {
         if (s16)
-            track_encode(tb_, j.io, n_host, src, src_start, count, first_frame, st);
+            track_encode(tb_, io, n_host, src, src_start, count, first_frame, st);
     }
     else if (s16)
-        launch_pcm16_encode_rescaled(n_host, s, d, count, first_frame, j.io.dither != 0, j.io.dither_seed, tb_.lev, st);
+        launch_pcm16_encode_rescaled(n_host, s, d, count, first_frame, io.dither != 0, io.dither_seed, tb_.lev, st);
     else
         launch_stem_rescale(n_host, sw, count, tb_.lev, st);
 }
@@ -188,7 +171,7 @@ hipError_t umx_hip_ctx::track_levels_report(const TrackJob &j, int n_host, umx_l
     umx_levels_acc acc;
     const hipError_t e = hipMemcpy(&acc, j.acc->lev, sizeof acc, hipMemcpyDeviceToHost);
     if (e == hipSuccess)
-        levels_report(acc, n_host, j.clip_mode == UMX_CLIP_RESCALE, lv);
+        levels_report(acc, n_host, j.opt.rescale(), lv);
     return e;
 }
 
@@ -206,23 +189,37 @@ int umx_hip_ctx::track_loudness_grow(TrackBufs &tb_, TrackJob &j, int rate, int 
         set_error("loudness: track too long");
         return UMX_ERR_ARG;
     }
-    j.loudness = true;
     j.loud_rate = rate;
     j.loud_hops = length_at_rate / kweight_hop(rate);
     j.hops_done = 0;
-    const size_t want = std::max<size_t>(1, (size_t)n_host * 2 * (size_t)j.loud_hops);
-    if (want <= tb_.cap_hopE)
-        return UMX_OK;
-    if (tb_.hopE)
-    {
-        allocs.erase(std::find(allocs.begin(), allocs.end(), (void *)tb_.hopE));
-        (void)hipFree(tb_.hopE);
-        tb_.hopE = nullptr;
-    }
-    tb_.cap_hopE = 0;
-    if (int rc = dalloc(&tb_.hopE, want + want / 8, false))
+    return grow_only<double>({{&tb_.hopE, 1}}, tb_.cap_hopE, std::max<size_t>(1, (size_t)n_host * 2 * (size_t)j.loud_hops));
+}
+
+// The admission of a job, for both drivers (tracks_once; the queue, engine_queue.h): `j` has its geometry (track_geometry), `acc` is the
+// accumulator set it will write, `audio` its host audio of length_at_rate frames at `rate` -- the rate and length the caller sees --,
+// leaves_whole: it is an ensemble lane or a resampled track.  The set grows by what the options need, in this order (a failed
+// allocation returns at once): accumulators, int16 side, levels record, hop energies; then the job is filled.  What the driver zeroes,
+// and on which stream, is the driver's.
+int umx_hip_ctx::admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt, const float *audio, int rate, int length_at_rate, bool leaves_whole)
+{
+    j.opt = opt;
+    if (int rc = track_bufs_grow(acc, (size_t)j.L2))
         return rc;
-    tb_.cap_hopE = want + want / 8;
+    if (int rc = track_pcm16_grow(acc, opt.io, (size_t)length_at_rate, opt.n_host())) // (nothing for an fp32 call)
+        return rc;
+    if (opt.measures())
+        if (int rc = track_levels_grow(acc))
+            return rc;
+    if (opt.loudness)
+        if (int rc = track_loudness_grow(acc, j, rate, length_at_rate, opt.n_host()))
+            return rc;
+    j.audio = audio;
+    j.acc = &acc;
+    // Its final regions are mixed in place and leave region by region -- unless it leaves whole behind its last segment: an ensemble
+    // lane (its mean leaves), a resampled track (behind its way back: leaves_whole of tracks_once), a rescaled one (its divisor needs
+    // every peak).  The last, at 44.1 kHz, is finished by track_call itself as ONE region.
+    j.by_region = !leaves_whole && !opt.rescale();
+    j.whole_region = opt.rescale() && !leaves_whole;
     return UMX_OK;
 }
 
@@ -248,7 +245,7 @@ hipError_t umx_hip_ctx::track_loudness_report(const TrackJob &j, int n_host, std
 // set's event may stem from its previous job: that work has long finished.)
 hipError_t umx_hip_ctx::track_upload_until(TrackJob &j, long long padded_end, hipStream_t st)
 {
-    const bool s16 = j.io.in_format == UMX_SAMPLE_S16;
+    const bool s16 = j.opt.io.in_format == UMX_SAMPLE_S16;
     if (s16 && j.acc->in16_ev)
         if (hipError_t e = hipStreamWaitEvent(st, j.acc->in16_ev, 0))
             return e;
@@ -290,16 +287,17 @@ void umx_hip_ctx::track_mix(const MixSpec &mix, float *const stems[4], size_t st
 }
 
 // umx.cpp:136-147: a finished region without the shift, to its job's n_host host buffers, once it is ready
-hipError_t umx_hip_ctx::track_region_download(const TrackRegion &r, int n_host, float *const *out_host)
+hipError_t umx_hip_ctx::track_region_download(const TrackRegion &r, float *const *out_host)
 {
     const TrackJob &j = *r.job;
+    const int n_host = j.opt.n_host();
     const long long lo = std::max<long long>(r.start, j.lead), hi = std::min<long long>((long long)r.start + r.count, (long long)j.lead + j.length);
     if (hi <= lo)
         return hipSuccess;
     hipError_t cerr = hipEventSynchronize(r.ready);
     const size_t first = (size_t)(lo - j.lead), count = (size_t)(hi - lo);
     for (int t = 0; t < n_host && cerr == hipSuccess; ++t)
-        if (j.io.out_format == UMX_SAMPLE_S16) // (encoded behind the region's normalisation and mix, at its frame number: track_call)
+        if (j.opt.io.out_format == UMX_SAMPLE_S16) // (encoded behind the region's normalisation and mix, at its frame number: track_call)
             cerr = hipMemcpy(reinterpret_cast<uint32_t *>(out_host[t]) + first, j.acc->out16[t] + first, sizeof(uint32_t) * count, hipMemcpyDeviceToHost);
         else
             cerr = hipMemcpy(out_host[t] + 2 * first, j.acc->out[t] + 2 * (size_t)lo, sizeof(float) * 2 * count, hipMemcpyDeviceToHost);
@@ -311,7 +309,7 @@ hipError_t umx_hip_ctx::track_region_download(const TrackRegion &r, int n_host, 
 // lane k (its reset mode), whatever job the lane holds (the queue).  The segment's stems are the lane's (trk[ln].seg of the slot), the
 // accumulators the job's.  Whatever the caller zeroes for this call it has queued on slot[next_slot()].stream, which is the stream
 // of this call: next_slot() moves on with infer_batch.  last_slot: the slot of the previous call of the run (-1: none), then this one.
-int umx_hip_ctx::track_call(const TrackLane *lanes, int nl, unsigned flags, const MixSpec *mix, int &last_slot, TrackRegions &regions)
+int umx_hip_ctx::track_call(const TrackLane *lanes, int nl, unsigned flags, int &last_slot, TrackRegions &regions)
 {
     const int si = next_slot(), stride = track_stride();
     const hipStream_t st = slot[si].stream;
@@ -373,14 +371,15 @@ int umx_hip_ctx::track_call(const TrackLane *lanes, int nl, unsigned flags, cons
             rg.start = j->lead;
             rg.count = j->length;
         }
-        if (mix)
-            track_mix(*mix, tb_.out, (size_t)rg.start, tb_.in, (size_t)rg.start, rg.count, st);
-        if (j->io.out_format == UMX_SAMPLE_S16 || j->levels || j->loudness) // the region's frames of the caller's track, as they will
+        const TrackOptions &opt = j->opt;
+        if (opt.mix)
+            track_mix(*opt.mix, tb_.out, (size_t)rg.start, tb_.in, (size_t)rg.start, rg.count, st);
+        if (opt.io.out_format == UMX_SAMPLE_S16 || opt.measures() || opt.loudness) // the region's frames of the caller's track, as they will
         {                                                    // leave (an int16 copy is not written over the accumulators: the next
                                                              // segment's overlap-add still reads its neighbours)
             const long long lo = std::max<long long>(rg.start, j->lead), hi = std::min<long long>((long long)rg.start + rg.count, (long long)j->lead + j->length);
             if (hi > lo)
-                track_leave(*j, mix ? mix->n_out : 4, tb_.out, (size_t)lo, (int)(hi - lo), lo - j->lead, st);
+                track_leave(*j, tb_.out, (size_t)lo, (int)(hi - lo), lo - j->lead, st);
         }
         if (hipEventCreateWithFlags(&rg.ready, hipEventDisableTiming) != hipSuccess)
         {
@@ -404,10 +403,11 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     // ensemble: the caller (umx_hip_shift_ensemble) has repeated the one track's audio pointer, length and rate per lane
     // and checked the offsets; rq.out holds that track's buffers
     // mix: a checked matrix; a track has n_host = mix->n_out host buffers instead of four
-    const int nt = rq.n_tracks, n_host = rq.mix ? rq.mix->n_out : 4;
+    const TrackOptions &opt = rq.opt;
+    const int nt = rq.n_tracks, n_host = opt.n_host();
     const int *const length_in = rq.length;
     const bool ensemble = rq.ensemble;
-    const MixSpec *const mix = rq.mix;
+    const MixSpec *const mix = opt.mix;
     if (nt < 1 || nt > B || !rq.audio || !length_in || !rq.shift_offset)
     {
         set_error("tracks: need 1 <= n_tracks <= the context's track count and non-null argument arrays");
@@ -415,15 +415,12 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     }
     if (int rc = check_flags(rq.flags))
         return rc;
-    // a rescaled track measures for its divisor whether or not the caller wants the record
-    const bool rescale = rq.clip_mode == UMX_CLIP_RESCALE, measure = rq.levels || rescale;
+    const bool measure = opt.measures(), loud = opt.loudness;
     if (measure && ensemble)
     {
         set_error("track: the shift ensemble does not offer levels or rescale");
         return UMX_ERR_ARG;
     }
-    // the tracks' hop energies are measured when the caller wants the records or the energies themselves
-    const bool loud = rq.loudness || rq.hop_energy;
     if (loud && ensemble)
     {
         set_error("track: the shift ensemble does not offer loudness");
@@ -488,12 +485,6 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
             set_error("track: too long");
             return UMX_ERR_ARG;
         }
-        j.audio = rq.audio[ln];
-        j.io = rq.io;
-        j.by_region = !ensemble && !resampled[ln] && !rescale;
-        j.clip_mode = rq.clip_mode;
-        j.levels = measure;
-        j.whole_region = rescale && !resampled[ln]; // (a resampled one leaves through leaves_whole below, behind its way back)
         L2max = std::max(L2max, j.L2);
         max_segs = std::max(max_segs, j.segs);
     }
@@ -502,21 +493,10 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     if (trk.size() < (size_t)seg_lanes)
         trk.resize(seg_lanes);
     for (int ln = 0; ln < nt; ++ln)
-    {
-        job[ln].acc = &trk[ln];
-        if (int rc = track_bufs_grow(trk[ln], (size_t)job[ln].L2))
+        if (int rc = admit_job(job[ln], trk[ln], opt, rq.audio[ln], rq.rate ? rq.rate[ln] : RS_MODEL_RATE, length_in[ln], ensemble || resampled[ln]))
             return rc;
-        if (int rc = track_pcm16_grow(trk[ln], rq.io, (size_t)length_in[ln], n_host)) // (nothing for an fp32 call)
-            return rc;
-        if (measure)
-            if (int rc = track_levels_grow(trk[ln]))
-                return rc;
-        if (loud)
-            if (int rc = track_loudness_grow(trk[ln], job[ln], rq.rate ? rq.rate[ln] : RS_MODEL_RATE, length_in[ln], n_host))
-                return rc;
-    }
     if (ensemble) // the mean of the lanes' stems: n44 frames
-        if (int rc = grow_frames({{&ens_out[0], 2}, {&ens_out[1], 2}, {&ens_out[2], 2}, {&ens_out[3], 2}}, ens_cap, (size_t)length[0]))
+        if (int rc = grow_only<float>({{&ens_out[0], 2}, {&ens_out[1], 2}, {&ens_out[2], 2}, {&ens_out[3], 2}}, ens_cap, (size_t)length[0]))
             return rc;
     // umx.cpp:167-171: a fresh, zeroed lstm_data per track; umx.cpp:186-195: zeroed accumulators (and F4)
     UMX_HIP_CHECK(hipMemset(state, 0, sizeof(float) * state_floats() * (reset_lanes ? B : nt)));
@@ -543,9 +523,9 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         if (!resampled[ln])
             continue;
         RsStage &rs = rs_stage[ln];
-        if (int rc = grow_frames({{&rs.in, 2}, {&rs.out[0], 2}, {&rs.out[1], 2}, {&rs.out[2], 2}, {&rs.out[3], 2}}, rs.cap, (size_t)length_in[ln]))
+        if (int rc = grow_only<float>({{&rs.in, 2}, {&rs.out[0], 2}, {&rs.out[1], 2}, {&rs.out[2], 2}, {&rs.out[3], 2}}, rs.cap, (size_t)length_in[ln]))
             return rc;
-        if (rq.io.in_format == UMX_SAMPLE_S16) // (decoded on the null stream, as the resampler below is launched)
+        if (opt.io.in_format == UMX_SAMPLE_S16) // (decoded on the null stream, as the resampler below is launched)
         {
             UMX_HIP_CHECK(hipMemcpy(trk[ln].in16, rq.audio[ln], sizeof(uint32_t) * (size_t)length_in[ln], hipMemcpyHostToDevice));
             launch_pcm16_decode(trk[ln].in16, reinterpret_cast<float2 *>(rs.in), length_in[ln], nullptr);
@@ -605,7 +585,7 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
             UMX_HIP_CHECK(hipMemset(state, 0, sizeof(float) * state_floats() * B));
             UMX_HIP_CHECK(hipDeviceSynchronize());
         }
-        if (int rc = track_call(lanes, nl, flags, mix, last_slot, regions))
+        if (int rc = track_call(lanes, nl, flags, last_slot, regions))
             return rc;
         // umx.cpp:229, once per QUEUED segment (queued, not finished: the device runs behind the host here) of the longest track: one
         // per call, or (reset mode) one per lane of the call
@@ -637,8 +617,8 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         }
         if (cerr == hipSuccess) // at the caller's rate and length, frame 0 first: measured, encoded, rescaled as the job says
         {
-            track_leave(j, n_host, whole[ln], 0, length_in[ln], 0, last_st);
-            for (int t = 0; t < n_host && rq.io.out_format == UMX_SAMPLE_S16; ++t)
+            track_leave(j, whole[ln], 0, length_in[ln], 0, last_st);
+            for (int t = 0; t < n_host && opt.io.out_format == UMX_SAMPLE_S16; ++t)
                 whole[ln][t] = reinterpret_cast<float *>(j.acc->out16[t]);
         }
         any_whole = true;
@@ -670,12 +650,12 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
             leaves_whole(ln, trk[ln].out, (size_t)job[ln].lead);
     for (const TrackRegion &rg : regions.v) // umx.cpp:136-147: drop the shift
         if (cerr == hipSuccess)
-            cerr = track_region_download(rg, n_host, rq.out + n_host * (rg.job - job));
+            cerr = track_region_download(rg, rq.out + n_host * (rg.job - job));
     if (any_whole && cerr == hipSuccess)
         cerr = hipStreamSynchronize(last_st);
     for (int ln = 0; ln < nt; ++ln)
         for (int t = 0; t < n_host && whole[ln][0] && cerr == hipSuccess; ++t) // (an ensemble's one result: lane 0)
-            cerr = hipMemcpy(rq.out[n_host * ln + t], whole[ln][t], (rq.io.out_format == UMX_SAMPLE_S16 ? sizeof(uint32_t) : sizeof(float) * 2) * (size_t)length_in[ln],
+            cerr = hipMemcpy(rq.out[n_host * ln + t], whole[ln][t], (opt.io.out_format == UMX_SAMPLE_S16 ? sizeof(uint32_t) : sizeof(float) * 2) * (size_t)length_in[ln],
                              hipMemcpyDeviceToHost);
     // every job's record, once: its last measuring launch is behind its last region, which the host has
     umx_levels reports[LSTMB_MAX_TRACKS];

@@ -367,7 +367,6 @@ int main(int argc, const char **argv)
         std::vector<int> n(nb, 0), shift(nb, shift_offset);
         std::vector<std::vector<float>> stems(per_file * nb);
         std::vector<float *> out(per_file * nb);
-        std::vector<const float *> in(nb);
         std::vector<int> rate(nb, UMX_SAMPLE_RATE);
         std::vector<umx_levels> levels(nb);
         std::vector<umx_loudness> loudness(nb);
@@ -382,7 +381,6 @@ int main(int argc, const char **argv)
                 fprintf(stderr, "%s: %s\n", argv[3 + f0 + i], err);
                 return 1;
             }
-            in[i] = audio[i];
             in_io[i] = in16 ? (const void *)audio16[i] : (const void *)audio[i];
             audio_secs += n[i] / (double)rate[i];
             for (int t = 0; t < per_file; ++t)
@@ -397,17 +395,12 @@ int main(int argc, const char **argv)
             }
         }
         const auto t0 = std::chrono::steady_clock::now();
-        // (without UMX_LOUDNESS the _loudness call IS the _levels call)
-        if (clipc.active() ? umx_hip_separate_tracks_loudness(ctx, nb, in_io.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out,
-                                                              mixed ? mixc.gains : nullptr, out_io.data(), flags, &io, clipc.clip_mode,
-                                                              clipc.levels ? levels.data() : nullptr, clipc.loudness ? loudness.data() : nullptr,
-                                                              nullptr, nullptr, nullptr)
-            : pcm16 ? umx_hip_separate_tracks_io(ctx, nb, in_io.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out,
-                                               mixed ? mixc.gains : nullptr, reinterpret_cast<void *const *>(out16.data()), flags, &io, nullptr, nullptr)
-            : mixed ? umx_hip_separate_tracks_mix(ctx, nb, in.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out, mixc.gains,
-                                                out.data(), flags, nullptr, nullptr)
-            : resample ? umx_hip_separate_tracks_rate(ctx, nb, in.data(), n.data(), rate.data(), shift.data(), out.data(), flags, nullptr, nullptr)
-                     : umx_hip_separate_tracks(ctx, nb, in.data(), n.data(), shift.data(), out.data(), flags, nullptr, nullptr))
+        // one call for every run: what a run does not ask for at its neutral value (NULL rates, gains, records, fp32 formats, clamp) is the
+        // narrower entry point's request (include/umx_hip.h)
+        if (umx_hip_separate_tracks_loudness(ctx, nb, in_io.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out,
+                                             mixed ? mixc.gains : nullptr, out_io.data(), flags, &io, clipc.clip_mode,
+                                             clipc.levels ? levels.data() : nullptr, clipc.loudness ? loudness.data() : nullptr, nullptr, nullptr,
+                                             nullptr))
         {
             fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
             return 1;

@@ -209,49 +209,32 @@ int main(int argc, const char **argv)
             return 1;
         }
     }
-    else if (pcm16 || clipc.active())
+    else if (shifts > 1) // the shift ensemble: another driver (no 16-bit transfers, levels or loudness: refused above)
     {
-        // (clamp without levels IS umx_hip_separate_tracks_io)
+        if (mixed ? umx_hip_shift_ensemble_mix(ctx, audio, n, rate, shifts, shift_offsets, mixc.n_out, mixc.gains, out, hb.flags, print_progress,
+                                               nullptr)
+                  : umx_hip_shift_ensemble(ctx, audio, n, rate, shifts, shift_offsets, out, hb.flags, print_progress, nullptr))
+        {
+            fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
+            return 1;
+        }
+    }
+    else
+    {
+        // umx.cpp:72-73.  One call for every run: what a run does not ask for at its neutral value (NULL rate, gains, records, fp32
+        // formats, clamp) is the narrower entry point's request (include/umx_hip.h)
         const int offset = env_int("UMX_SHIFT_OFFSET", -1) < 0 ? UMX_REFERENCE_SHIFT : env_int("UMX_SHIFT_OFFSET", -1);
         const void *in = io.in_format == UMX_SAMPLE_S16 ? (const void *)audio16 : (const void *)audio;
-        void *out16[4];
+        void *out_io[4]; // (read as the formats say)
         for (int t = 0; t < 4; ++t)
-            out16[t] = pcm16 ? (void *)stems16[t].data() : (void *)stems[t].data();
-        // (... and without UMX_LOUDNESS the _loudness call IS the _levels call)
-        if (umx_hip_separate_tracks_loudness(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out16,
+            out_io[t] = pcm16 ? (void *)stems16[t].data() : (void *)stems[t].data();
+        if (umx_hip_separate_tracks_loudness(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out_io,
                                              hb.flags, &io, clipc.clip_mode, clipc.levels ? &levels : nullptr,
                                              clipc.loudness ? &loudness : nullptr, nullptr, print_progress, nullptr))
         {
             fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
             return 1;
         }
-    }
-    else if (mixed)
-    {
-        const int offset = env_int("UMX_SHIFT_OFFSET", -1) < 0 ? UMX_REFERENCE_SHIFT : env_int("UMX_SHIFT_OFFSET", -1);
-        if (shifts > 1 ? umx_hip_shift_ensemble_mix(ctx, audio, n, rate, shifts, shift_offsets, mixc.n_out, mixc.gains, out, hb.flags,
-                                                    print_progress, nullptr)
-                       : umx_hip_separate_tracks_mix(ctx, 1, &audio, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixc.gains, out,
-                                                     hb.flags, print_progress, nullptr))
-        {
-            fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
-            return 1;
-        }
-    }
-    else if (shifts > 1)
-    {
-        if (umx_hip_shift_ensemble(ctx, audio, n, rate, shifts, shift_offsets, out, hb.flags, print_progress, nullptr))
-        {
-            fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
-            return 1;
-        }
-    }
-    else if (resample ? umx_hip_shift_inference_rate(ctx, audio, n, rate, env_int("UMX_SHIFT_OFFSET", -1), out, hb.flags, print_progress, nullptr)
-                      : umx_hip_shift_inference(ctx, audio, n, env_int("UMX_SHIFT_OFFSET", -1), out, hb.flags, print_progress,
-                                                nullptr)) // umx.cpp:72-73
-    {
-        fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
-        return 1;
     }
     const auto t3 = std::chrono::steady_clock::now();
     const double secs = std::chrono::duration<double>(t3 - t2).count();
