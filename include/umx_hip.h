@@ -281,12 +281,35 @@ long long umx_hip_resampled_length(long long n, int rate_in, int rate_out);
  * n_out may differ from the natural length: beyond it the formula goes on (a decaying tail, then zeros). */
 int umx_hip_resample_device(umx_hip_ctx *ctx, int rate_in, int rate_out, int n_buffers, const float *const *in_dev, int n_in,
                             float *const *out_dev, int n_out, void *hip_stream);
+/* Ranges.  Output j reads the input frames c - D .. c + D + 1, c = floor(j M / L): that is its whole window, zero taps
+ * included, and nothing else decides its bits.  So a range of the outputs resampled on its own is, bit for bit, that range of the
+ * whole launch, and the two directions of the rule are host arithmetic in 64-bit integers:
+ *   umx_hip_resample_needs  the number of leading input frames that outputs [0, n_out_wanted) read: 0 for n_out_wanted == 0, else
+ *                           min(n_in, floor((n_out_wanted - 1) M / L) + D + 2)
+ *   umx_hip_resample_ready  the number of leading output frames whose whole window lies inside the first n_in_final input frames:
+ *                           n_out if n_in_final >= n_in (beyond n_in the input is zeros), else ceil((n_in_final - D - 1) L / M)
+ *                           clamped to 0 .. n_out (0 for n_in_final <= D + 1)
+ * Both return < 0 for a rate outside the range or a negative count.  needs(ready(f)) <= f and ready(needs(w)) >= w. */
+long long umx_hip_resample_needs(long long n_out_wanted, int rate_in, int rate_out, long long n_in);
+long long umx_hip_resample_ready(long long n_in_final, int rate_in, int rate_out, long long n_in, long long n_out);
+/* umx_hip_resample_device for the frames [first, first + count) of each n_out-frame output: it writes those frames and nothing
+ * else, with the bits the whole call gives them; n_in and n_out are still the whole buffers' lengths.  count == 0 launches nothing.
+ * `first` must be even (every 16-byte store stays as aligned as the whole call keeps it); UMX_ERR_ARG for an odd or negative first,
+ * count < 0, first + count > n_out, and whatever umx_hip_resample_device refuses. */
+int umx_hip_resample_range_device(umx_hip_ctx *ctx, int rate_in, int rate_out, int n_buffers, const float *const *in_dev, int n_in,
+                                  float *const *out_dev, int n_out, int first, int count, void *hip_stream);
+/* resampler launches of the context's last whole-track call or queue run: `forward` into 44.1 kHz, `backward` out of it (a
+ * whole-buffer launch counts as one; a call without a resampled track gives 0 and 0).  UMX_ERR_ARG when there has been none. */
+int umx_hip_debug_resample_launches(umx_hip_ctx *ctx, int *forward, int *backward);
 /* umx_hip_shift_inference / umx_hip_separate_tracks for tracks at `rate`: the stems come back with the caller's length at the
  * caller's rate, aligned sample for sample with the input.  The track is resampled to n44 = umx_hip_resampled_length(length,
  * rate, 44100) frames, separated exactly as umx_hip_shift_inference / _separate_tracks separate n44 frames at 44.1 kHz
  * (offset / shift_offset count 44.1 kHz samples, same meaning), and the four stems (those n44 frames, zero outside them) are
  * resampled back: bit for bit that composition.  A track at 44100 is not resampled: bitwise today's entry points.  A rate outside
- * 8000 .. 192000 is UMX_ERR_ARG.  Resampled tracks' stems are downloaded after the last segment, not region by region. */
+ * 8000 .. 192000 is UMX_ERR_ARG.  A resampled track goes in and out range by range: the native frames a segment's
+ * 44.1 kHz frames read (umx_hip_resample_needs) go up and through the resampler with the call that needs them, and behind every
+ * finished region the frames at the caller's rate that it completes (umx_hip_resample_ready) are resampled back and downloaded
+ * while later segments run -- the same bits.  A rescaled track (UMX_CLIP_RESCALE) and the shift ensemble still leave whole. */
 int umx_hip_shift_inference_rate(umx_hip_ctx *ctx, const float *audio_host, int length, int rate, int offset, float *const out_host[4],
                                  unsigned flags, void (*progress)(float, void *), void *progress_user);
 int umx_hip_separate_tracks_rate(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *rate,
@@ -369,14 +392,18 @@ int umx_hip_mix_stems_device(umx_hip_ctx *ctx, int n_out, const float *gains, co
  * track-batched (umx_hip_lstm_is_batched: a job's bits must not depend on its lane), a job with length < 1, shift_offset >=
  * UMX_MAX_SHIFT or a NULL buffer, and `next` returning < 0; the context stays usable.  A persistent-kernel timeout: as
  * umx_hip_separate_tracks, the jobs in flight are run again from their first segment, once (the run then makes more calls than the
- * plan); a second timeout is UMX_ERR_TIMEOUT.  Tracks at other sample rates and the shift ensemble are not offered here, and the
- * multi-GPU driver (umx_mgpu.h) does not offer the queue. */
+ * plan); a second timeout is UMX_ERR_TIMEOUT.  A job may be at any sample rate umx_hip_separate_tracks_rate takes (`rate`): it
+ * is bit for bit that call's result for the one track, holds its lane for the segments of its 44.1 kHz version (S above from
+ * umx_hip_resampled_length(length, rate, 44100)), and a rate outside 8000 .. 192000 is UMX_ERR_ARG.  The shift ensemble is not offered
+ * here, and the multi-GPU driver (umx_mgpu.h) does not offer the queue. */
 typedef struct umx_queue_job
 {
-    const float *audio;                   /* (2,length) interleaved, 44.1 kHz */
+    const float *audio;                   /* (2,length) interleaved, at `rate` */
     int length, shift_offset;             /* as umx_hip_separate_tracks: < 0 split, >= 0 shift */
     float *out[UMX_MAX_MIX_OUTPUTS];      /* n_out buffers (2,length); 4 stems when gains == NULL */
     void *tag;                            /* the caller's, untouched */
+    int rate;                             /* 0 or 44100: not resampled; else 8000 .. 192000: length and out are at this rate.  The struct is
+                                             zeroed before `next`, so a caller that never sets it has 44.1 kHz jobs */
 } umx_queue_job;
 typedef int (*umx_queue_next_fn)(void *user, umx_queue_job *job);        /* 1: *job filled in, 0: no more jobs, < 0: stop with UMX_ERR_ARG */
 typedef void (*umx_queue_done_fn)(void *user, const umx_queue_job *job); /* job's out buffers are complete */

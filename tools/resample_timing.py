@@ -4,7 +4,9 @@
                                               rocprofv3 --kernel-trace --stats for the kernel times): 48k -> 44.1k of the
                                               track, 44.1k -> 48k of its four stems in one launch
     python tools/resample_timing.py wall      umx_hip_shift_inference at 44.1 kHz against umx_hip_shift_inference_rate at
-                                              48 kHz on the same audio, alternated, host buffers in / out
+                                              48 kHz on the same audio, alternated, host buffers in / out; --reset adds both
+                                              in reset mode on a two-lane context.  One `wall ...` line of medians and
+                                              min .. max per mode: run it in fresh processes (DESIGN 23 alternates two trees)
 
 Bytes each launch must move (the floor the kernel time is held against) are printed with the shapes."""
 import argparse
@@ -27,6 +29,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=600.0)
     ap.add_argument("--hidden", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--reset", action="store_true", help="wall: also UMX_FLAG_RESET_SEGMENTS on a two-lane context")
     a = ap.parse_args()
     pkg = ge.load_package()
     import torch
@@ -37,6 +40,7 @@ def main():
         path = str(Path(td) / "m.bin.gz")
         pkg.ggml.write_model(path, pkg.ggml.synth_weights(a.hidden if a.what == "wall" else 128, seed=7), a.hidden if a.what == "wall" else 128)
         eng = pkg.Engine.from_file(path)
+        eng2 = pkg.Engine.from_file(path, tracks=2) if a.what == "wall" and a.reset else None
     x48 = pkg.ggml.synth_audio(n48, 5)
     if a.what == "kernels":
         src = torch.from_numpy(np.ascontiguousarray(x48.T).ravel()).cuda()
@@ -68,21 +72,28 @@ def main():
         a44, a48 = np.ascontiguousarray(x44.T).ravel(), np.ascontiguousarray(x48.T).ravel()
         o48 = (fp * 4)(*[o.ctypes.data_as(fp) for o in out48])
 
-        def run48():
+        def run48(e, flags):
             t0 = time.perf_counter()
-            rc = eng.lib.umx_hip_shift_inference_rate(eng.h, a48.ctypes.data_as(fp), n48, 48000, 4033, o48, 0, None, None)
+            rc = e.lib.umx_hip_shift_inference_rate(e.h, a48.ctypes.data_as(fp), n48, 48000, 4033, o48, flags, None, None)
             dt = time.perf_counter() - t0
-            assert rc == 0, eng.last_error()
+            assert rc == 0, e.last_error()
             return dt
-        run48()  # warm-up of both paths
-        eng.separate_interleaved(a44, n44, out44, 0, 4033)
-        t_44, t_48 = [], []
-        for _ in range(a.reps):
-            t_44.append(eng.separate_interleaved(a44, n44, out44, 0, 4033))
-            t_48.append(run48())
-        print(f"{a.seconds:.0f} s track, hidden {a.hidden}: shift_inference 44.1 kHz median {statistics.median(t_44) * 1e3:.1f} ms "
-              f"{[round(t * 1e3, 1) for t in t_44]}; shift_inference_rate 48 kHz median {statistics.median(t_48) * 1e3:.1f} ms "
-              f"{[round(t * 1e3, 1) for t in t_48]}")
+
+        for mode, e, flags in (("carry", eng, 0), ("reset", eng2, pkg.FLAG_RESET_SEGMENTS)):
+            if e is None:
+                continue
+            run48(e, flags)  # warm-up of both paths
+            e.separate_interleaved(a44, n44, out44, flags, 4033)
+            t_44, t_48 = [], []
+            for _ in range(a.reps):
+                t_44.append(e.separate_interleaved(a44, n44, out44, flags, 4033))
+                t_48.append(run48(e, flags))
+            launches = e.resample_launches() if hasattr(e, "resample_launches") else None
+            print(f"wall {mode} {a.seconds:.0f} s hidden {a.hidden}: 44.1 kHz median {statistics.median(t_44) * 1e3:.2f} ms "
+                  f"({min(t_44) * 1e3:.2f} .. {max(t_44) * 1e3:.2f}); 48 kHz median {statistics.median(t_48) * 1e3:.2f} ms "
+                  f"({min(t_48) * 1e3:.2f} .. {max(t_48) * 1e3:.2f}); resampler launches of the 48 kHz call {launches}", flush=True)
+        if eng2 is not None:
+            eng2.close()
     eng.close()
 
 

@@ -82,8 +82,14 @@ _fp = C.POINTER(C.c_float)
 
 
 class QueueJob(C.Structure):
-    """include/umx_hip.h: umx_queue_job"""
+    """include/umx_hip.h: umx_queue_job's members up to `tag` (the whole record: QueueJobRate)"""
     _fields_ = [("audio", _fp), ("length", C.c_int), ("shift_offset", C.c_int), ("out", _fp * 4), ("tag", C.c_void_p)]
+
+
+class QueueJobRate(QueueJob):
+    """umx_queue_job as it is since DESIGN 23: QueueJob's members (its layout up to `tag`: tests/test_queue_cpu.py pins that part) and
+    `rate` behind them.  The callbacks receive this record; the engine zeroes it before `next`, so rate stays 0 = 44.1 kHz unless set."""
+    _fields_ = [("rate", C.c_int)]
 
 
 class SampleIO(C.Structure):
@@ -94,8 +100,8 @@ class SampleIO(C.Structure):
 SAMPLE_F32, SAMPLE_S16 = 0, 1  # UMX_SAMPLE_*: the formats of the host buffers of the whole-track calls
 _i16p = C.POINTER(C.c_int16)
 
-QUEUE_NEXT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(QueueJob))
-QUEUE_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJob))
+QUEUE_NEXT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(QueueJobRate))
+QUEUE_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJobRate))
 
 CLIP_CLAMP, CLIP_RESCALE = 0, 1  # UMX_CLIP_*: what a whole-track call does with outputs beyond full scale
 
@@ -117,7 +123,7 @@ class Levels(C.Structure):
                 "clipped": list(self.clipped[:n]), "nonfinite": list(self.nonfinite[:n])}
 
 
-QUEUE_LEVELS_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJob), C.POINTER(Levels))
+QUEUE_LEVELS_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJobRate), C.POINTER(Levels))
 
 
 class Loudness(C.Structure):
@@ -132,7 +138,7 @@ class Loudness(C.Structure):
 
 
 _dp = C.POINTER(C.c_double)
-QUEUE_LOUDNESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJob), C.POINTER(Levels), C.POINTER(Loudness), _dp)
+QUEUE_LOUDNESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJobRate), C.POINTER(Levels), C.POINTER(Loudness), _dp)
 
 
 class TensorView(C.Structure):
@@ -252,6 +258,13 @@ def hip_lib():
     lib.umx_hip_resampled_length.argtypes = [C.c_longlong, C.c_int, C.c_int]
     lib.umx_hip_resample_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int,
                                             C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
+    lib.umx_hip_resample_needs.restype = C.c_longlong
+    lib.umx_hip_resample_needs.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_longlong]
+    lib.umx_hip_resample_ready.restype = C.c_longlong
+    lib.umx_hip_resample_ready.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.c_longlong]
+    lib.umx_hip_resample_range_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int,
+                                                  C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.umx_hip_debug_resample_launches.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.umx_hip_shift_inference_rate.argtypes = [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.c_uint, C.c_void_p,
                                                  C.c_void_p]
     lib.umx_hip_debug_resample_taps.argtypes = [C.c_int, C.c_int, _fp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -350,7 +363,8 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_separate_tracks_levels", "umx_hip_separate_queue_levels", "umx_hip_levels_device",
                "umx_hip_pcm16_encode_rescaled_device", "umx_hip_rescale_device", "umx_hip_levels_host", "umx_hip_rescale_gain",
                "umx_hip_separate_tracks_loudness", "umx_hip_separate_queue_loudness", "umx_hip_kweight_hops_device",
-               "umx_hip_kweight_coeffs", "umx_hip_kweight_hops_host", "umx_hip_loudness_gate"]
+               "umx_hip_kweight_coeffs", "umx_hip_kweight_hops_host", "umx_hip_loudness_gate",
+               "umx_hip_resample_needs", "umx_hip_resample_ready", "umx_hip_resample_range_device", "umx_hip_debug_resample_launches"]
 
 
 def sample_io(in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None):
@@ -442,6 +456,18 @@ def loudness_gate(E, hop):
 def resampled_length(n, rate_in, rate_out):
     """ceil(n L / M), the natural output length of the device resampler (host arithmetic; < 0 for a bad rate)."""
     return int(hip_lib().umx_hip_resampled_length(int(n), int(rate_in), int(rate_out)))
+
+
+def resample_needs(n_out_wanted, rate_in, rate_out, n_in):
+    """umx_hip_resample_needs: the leading input frames that outputs [0, n_out_wanted) of the device resampler read (host
+    arithmetic; < 0 for a bad rate or a negative count)."""
+    return int(hip_lib().umx_hip_resample_needs(int(n_out_wanted), int(rate_in), int(rate_out), int(n_in)))
+
+
+def resample_ready(n_in_final, rate_in, rate_out, n_in, n_out):
+    """umx_hip_resample_ready: the leading output frames whose whole window lies inside the first n_in_final input frames (DESIGN 23;
+    host arithmetic; < 0 for a bad rate or a negative count)."""
+    return int(hip_lib().umx_hip_resample_ready(int(n_in_final), int(rate_in), int(rate_out), int(n_in), int(n_out)))
 
 
 def ensemble_offsets(n_shifts, first=None):
@@ -897,9 +923,10 @@ class Engine:
                                                          (C.c_void_p * nb)(*out_ptrs), hip_stream))
 
     # --- the track queue: more tracks than lanes, a lane refilled with the next track the moment one ends ---
-    def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None, io=None, clip=None, levels=False, loudness=False):
+    def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None, io=None, clip=None, levels=False, loudness=False, rates=None):
         """umx_hip_separate_queue: list of (2,L_i) -> list of [4 x (2,L_i)] (mix: an (n_out, 5) gain matrix -> n_out x (2,L_i)), every
         job bit for bit what separate() / separate_mix() returns for it alone on this engine; the jobs are handed out in list order.
+        rates: one sample rate per job (None: all 44.1 kHz), as separate_many() takes them.
         io: a SampleIO (sample_io()) -> umx_hip_separate_queue_io, int16 arrays in and / or out as it says.
         clip (CLIP_CLAMP / CLIP_RESCALE) or levels=True -> umx_hip_separate_queue_levels: returns (outputs, [Levels per job]).
         loudness=True -> umx_hip_separate_queue_loudness: returns (outputs, [Levels], [Loudness], [(n_out, 2, hops) float64])."""
@@ -919,6 +946,8 @@ class Engine:
             for m, o in enumerate(outs[j]):
                 job[0].out[m] = C.cast(o.ctypes.data, _fp)
             job[0].tag = j + 1
+            if rates is not None:
+                job[0].rate = int(rates[j])
             return 1
 
         def _done(_user, job):
@@ -984,6 +1013,21 @@ class Engine:
         assert len(out_ptrs) == nb
         self._check(self.lib.umx_hip_resample_device(self.h, int(rate_in), int(rate_out), nb, (C.c_void_p * nb)(*in_ptrs), int(n_in),
                                                      (C.c_void_p * nb)(*out_ptrs), int(n_out), hip_stream))
+
+    def resample_range_device(self, rate_in, rate_out, in_ptrs, n_in, out_ptrs, n_out, first, count, hip_stream=None):
+        """umx_hip_resample_range_device: frames [first, first + count) of the n_out output frames of resample_device(), nothing else."""
+        nb = len(in_ptrs)
+        assert len(out_ptrs) == nb
+        self._check(self.lib.umx_hip_resample_range_device(self.h, int(rate_in), int(rate_out), nb, (C.c_void_p * nb)(*in_ptrs), int(n_in),
+                                                           (C.c_void_p * nb)(*out_ptrs), int(n_out), int(first), int(count), hip_stream))
+
+    def resample_launches(self):
+        """(forward, backward) resampler launches of the engine's last whole-track call or queue run (umx_hip_debug_resample_launches);
+        None: there has been none."""
+        f, b = C.c_int(), C.c_int()
+        if self.lib.umx_hip_debug_resample_launches(self.h, C.byref(f), C.byref(b)) != UMX_OK:
+            return None
+        return f.value, b.value
 
     def separate_interleaved(self, a, L, outs, flags=0, shift_offset=None):
         """The bare C call: a = (2,L) interleaved float32, outs = 4 preallocated float32[2L]; returns seconds."""

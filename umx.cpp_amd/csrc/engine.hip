@@ -616,21 +616,23 @@ struct umx_hip_ctx
     // resampling (resample.h): the tap table of each (rate_in, rate_out) pair, built once and kept in HBM
     std::map<std::pair<int, int>, float *> rs_taps;
     int resample_plan(int rate_in, int rate_out, ResampleGeom &g, const float **taps_dev);
-    struct RsStage // per track lane: the track and its four stems at the caller's rate (grow-only)
+    struct RsStage // per accumulator set, only once a resampled job borrows it: the track and its outputs at the caller's rate (grow-only)
     {
         float *in = nullptr, *out[4] = {};
         size_t cap = 0; // frames
     };
-    std::vector<RsStage> rs_stage;
+    int rs_launches[2] = {-1, -1}; // resampler launches (forward, backward) of the last whole-track call or queue run (umx_hip_debug_resample_launches)
     struct TrackBufs // whole-track driver, per track lane: the (shifted) track, 4 stem accumulators, weight sum, 2 x 4 segment stems
     {
         float *in = nullptr, *out[4] = {}, *sumw = nullptr, *seg[kMaxSlots][4] = {};
         size_t cap = 0;
+        RsStage rs; // the native-rate staging of a resampled job, frames at the caller's frame numbers
         // DESIGN 19, only once a job asks for UMX_SAMPLE_S16: the track as uploaded and its outputs as they leave, one word per frame of
         // the CALLER's track (no shift padding), each grow-only on its own
         uint32_t *in16 = nullptr, *out16[4] = {};
         size_t cap_in16 = 0, cap_out16[4] = {};
-        hipEvent_t in16_ev = nullptr; // behind the most recent decode out of in16 (track_upload_until): every call that reads `in` waits for it
+        hipEvent_t in_ev = nullptr; // behind the most recent kernel that wrote `in` -- a decode out of in16, a resampled range out of rs.in
+                                    // (track_upload_until): every call that reads `in` waits for it
         umx_levels_acc *lev = nullptr; // DESIGN 20, only once a job measures: the record of what leaves, zeroed with the accumulators
         double *hopE = nullptr;        // DESIGN 21, only once a job measures loudness: its hop energies [output][channel][hop], grow-only,
         size_t cap_hopE = 0;           // zeroed with the accumulators (cap: doubles)
@@ -638,6 +640,13 @@ struct umx_hip_ctx
     std::vector<TrackBufs> trk;
     hipEvent_t trk_acc_ev[kMaxSlots] = {}; // per slot: behind the overlap-add of the last call that ran in it
     // ---- what tracks_once and the track queue share (engine_tracks.h)
+    struct TrackResample // a job at another rate (track_rate_plan): the caller's rate and length, the two rate pairs' geometry and taps
+    {
+        int rate = 0, length = 0; // rate 0: the job is at 44.1 kHz, nothing below is used
+        ResampleGeom fwd, back;   // rate -> 44.1 kHz, 44.1 kHz -> rate
+        const float *fwd_taps = nullptr, *back_taps = nullptr;
+    };
+    int track_rate_plan(int rate, int length_at_rate, const char *too_long, TrackResample &rs, int &n44);
     struct TrackJob // a track resident on the device
     {
         const float *audio = nullptr; // on the host (opt.io.in_format UMX_SAMPLE_S16: int16 frames)
@@ -645,12 +654,15 @@ struct umx_hip_ctx
                                       // go to, the clip mode, whether what leaves is measured into acc->lev and acc->hopE
         int length = 0;               // frames as the segments see them (the 44.1 kHz version's of a resampled track)
         int lead = 0, L2 = 0, segs = 0; // track_geometry: frames of silence before the track, padded frames, segments
-        long long uploaded = 0;       // host frames already on the device
+        long long uploaded = 0;       // host frames already on the device (a resampled job: frames at its own rate, in the set's staging)
+        TrackResample rs;             // set before admit_job for a job at another rate; such a job goes in and out by ranges:
+        long long done44 = 0;         //   44.1 kHz frames already resampled into the padded signal (even, or `length`)
+        long long out_done = 0;       //   frames at the caller's rate already resampled back into the staging (even, or rs.length)
         TrackBufs *acc = nullptr;     // the accumulator set it writes
         bool by_region = true;        // its final regions are mixed in place and leave region by region (false: an ensemble lane, a
-                                      // resampled track, a rescaled one -- mixed and downloaded whole behind the last segment)
+                                      // rescaled track -- mixed and downloaded whole behind the last segment)
         bool whole_region = false;    // not by_region, and track_call itself finishes it behind its last segment as ONE region: the
-                                      // frames [lead, lead + length) (a rescaled track at 44.1 kHz)
+                                      // frames [lead, lead + length) (a rescaled track)
         // DESIGN 21 (opt.loudness): the K-weighted hop energies of what leaves go to acc->hopE
         int loud_rate = 0;            // the caller's rate: hop = kweight_hop(loud_rate) frames
         long long loud_hops = 0;      // hops of the caller's track (its length at that rate / hop)
@@ -666,6 +678,7 @@ struct umx_hip_ctx
         TrackJob *job;
         int start, count;
         hipEvent_t ready;
+        int rs_first = 0, rs_count = 0; // a resampled job: the frames at the caller's rate that left with it, in the set's staging
     };
     struct TrackRegions // owns the events of its regions: whichever way a driver returns, none is left behind
     {

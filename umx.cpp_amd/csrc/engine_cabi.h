@@ -118,8 +118,8 @@ void umx_hip_destroy(umx_hip_ctx *ctx)
             (void)hipEventDestroy(e);
     for (const std::vector<umx_hip_ctx::TrackBufs> *sets : {&ctx->trk, &ctx->qpool})
         for (const umx_hip_ctx::TrackBufs &tb_ : *sets)
-            if (tb_.in16_ev)
-                (void)hipEventDestroy(tb_.in16_ev);
+            if (tb_.in_ev)
+                (void)hipEventDestroy(tb_.in_ev);
     if (ctx->order_ev)
         (void)hipEventDestroy(ctx->order_ev);
     if (ctx->copy_stream)
@@ -339,9 +339,23 @@ int umx_hip_separate_tracks(umx_hip_ctx *ctx, int n_tracks, const float *const *
     return separate_tracks_f32(ctx, n_tracks, audio_host, length, nullptr, shift_offset, 4, nullptr, out_host, flags, progress, progress_user);
 }
 long long umx_hip_resampled_length(long long n, int rate_in, int rate_out) { return resampled_length(n, rate_in, rate_out); }
+long long umx_hip_resample_needs(long long n_out_wanted, int rate_in, int rate_out, long long n_in)
+{
+    return resample_needs(n_out_wanted, rate_in, rate_out, n_in);
+}
+long long umx_hip_resample_ready(long long n_in_final, int rate_in, int rate_out, long long n_in, long long n_out)
+{
+    return resample_ready(n_in_final, rate_in, rate_out, n_in, n_out);
+}
 
 int umx_hip_resample_device(umx_hip_ctx *ctx, int rate_in, int rate_out, int n_buffers, const float *const *in_dev, int n_in,
                             float *const *out_dev, int n_out, void *hip_stream)
+{
+    return umx_hip_resample_range_device(ctx, rate_in, rate_out, n_buffers, in_dev, n_in, out_dev, n_out, 0, n_out, hip_stream);
+}
+
+int umx_hip_resample_range_device(umx_hip_ctx *ctx, int rate_in, int rate_out, int n_buffers, const float *const *in_dev, int n_in,
+                                  float *const *out_dev, int n_out, int first, int count, void *hip_stream)
 {
     if (!ctx)
         return UMX_ERR_ARG;
@@ -356,12 +370,17 @@ int umx_hip_resample_device(umx_hip_ctx *ctx, int rate_in, int rate_out, int n_b
             ctx->set_error("resample: null buffer");
             return UMX_ERR_ARG;
         }
+    if (first < 0 || count < 0 || (first & 1) || (long long)first + count > (long long)n_out)
+    {
+        ctx->set_error("resample: a range needs an even first frame >= 0, count >= 0 and first + count <= n_out");
+        return UMX_ERR_ARG;
+    }
     ResampleGeom g;
     const float *taps = nullptr;
     UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
     if (int rc = ctx->resample_plan(rate_in, rate_out, g, &taps))
         return rc;
-    UMX_HIP_CHECK_CTX(ctx, launch_resample(g, taps, n_buffers, in_dev, n_in, out_dev, n_out, (hipStream_t)hip_stream));
+    UMX_HIP_CHECK_CTX(ctx, launch_resample(g, taps, n_buffers, in_dev, n_in, out_dev, n_out, first, count, (hipStream_t)hip_stream));
     return UMX_OK;
 }
 
@@ -780,6 +799,16 @@ int umx_hip_queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_
     return queue_plan(n_lanes, n_jobs, seg_count, lane_out, first_call_out, n_calls_out);
 }
 int umx_hip_debug_queue_calls(umx_hip_ctx *ctx) { return ctx ? ctx->queue_calls : -1; }
+int umx_hip_debug_resample_launches(umx_hip_ctx *ctx, int *forward, int *backward)
+{
+    if (!ctx || ctx->rs_launches[0] < 0)
+        return UMX_ERR_ARG;
+    if (forward)
+        *forward = ctx->rs_launches[0];
+    if (backward)
+        *backward = ctx->rs_launches[1];
+    return UMX_OK;
+}
 
 // the kernel on the caller's device buffers: (2,n) interleaved stems and mixture -> n_out buffers (2,n), queued on hip_stream
 int umx_hip_mix_stems_device(umx_hip_ctx *ctx, int n_out, const float *gains, const float *const stems_dev[4], const float *mix_dev, int n,

@@ -130,6 +130,7 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
     int last_slot = -1;
     unsigned long long seq = 0;
     queue_calls = 0;
+    rs_launches[0] = rs_launches[1] = 0;
 
     auto fail = [&](int rc) { // nothing of this run may still be running, or be copied, when the caller has its buffers back
         const std::string why = err;
@@ -149,7 +150,7 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
         std::sort(redo.begin(), redo.end(), [](const Job *a, const Job *b) { return a->seq < b->seq; });
         for (Job *jb : redo)
         {
-            jb->uploaded = 0;
+            jb->uploaded = jb->done44 = jb->out_done = 0; // (a resampled job goes through the resampler again, from its host copy)
             jb->hops_done = 0; // (its hop energies are zeroed with its accumulators and measured again)
             jb->regions_left = jb->by_region ? jb->segs : 1;
         }
@@ -292,15 +293,24 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
                     set_error("queue: a job needs audio, its n_out outputs, length >= 1 and shift offset < 22050");
                     return fail(UMX_ERR_ARG);
                 }
+                // A job at another rate (rate 0: 44.1 kHz) runs as the n44 frames of its 44.1 kHz version, as in tracks_once:
+                // its geometry, its set's size and the spans zeroed below are in those frames, its int16 side and loudness in its own.
+                const int rate = j.rate ? j.rate : RS_MODEL_RATE;
+                TrackResample rs;
+                int n44 = j.length;
+                if (rate != RS_MODEL_RATE)
+                    if (int rc = track_rate_plan(rate, j.length, "queue: a job is too long", rs, n44))
+                        return fail(rc);
                 TrackJob tj; // (the geometry first: the set is chosen by its size)
-                if (!track_geometry(j.length, j.shift_offset, stride, tj))
+                if (!track_geometry(n44, j.shift_offset, stride, tj))
                 {
                     set_error("queue: a job is too long");
                     return fail(UMX_ERR_ARG);
                 }
+                tj.rs = rs;
                 const int set = free_set((size_t)tj.L2);
-                // (a queue's jobs are at 44.1 kHz; a rescaled one is one whole-track region, queued with its last segment)
-                if (int rc = admit_job(tj, qpool[set], opt, j.audio, RS_MODEL_RATE, tj.length, false))
+                // (a rescaled job is one whole-track region, queued with its last segment)
+                if (int rc = admit_job(tj, qpool[set], opt, j.audio, rate, j.length, false))
                     return fail(rc);
                 jb = &jobs[set];
                 static_cast<TrackJob &>(*jb) = tj;

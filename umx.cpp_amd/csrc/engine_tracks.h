@@ -49,7 +49,7 @@ bool umx_hip_ctx::track_geometry(int length, int shift_offset, int stride, Track
     j.lead = shift_offset < 0 ? 0 : shift_offset;
     j.L2 = (int)l2;
     j.segs = (int)((l2 + stride - 1) / stride); // umx.cpp:214-217
-    j.uploaded = 0;
+    j.uploaded = j.done44 = j.out_done = 0;
     return true;
 }
 
@@ -195,16 +195,38 @@ int umx_hip_ctx::track_loudness_grow(TrackBufs &tb_, TrackJob &j, int rate, int 
     return grow_only<double>({{&tb_.hopE, 1}}, tb_.cap_hopE, std::max<size_t>(1, (size_t)n_host * 2 * (size_t)j.loud_hops));
 }
 
-// The admission of a job, for both drivers (tracks_once; the queue, engine_queue.h): `j` has its geometry (track_geometry), `acc` is the
-// accumulator set it will write, `audio` its host audio of length_at_rate frames at `rate` -- the rate and length the caller sees --,
-// leaves_whole: it is an ensemble lane or a resampled track.  The set grows by what the options need, in this order (a failed
-// allocation returns at once): accumulators, int16 side, levels record, hop energies; then the job is filled.  What the driver zeroes,
-// and on which stream, is the driver's.
+// A job at `rate` != 44.1 kHz: n44, the length of its 44.1 kHz version, which the segments see, and the record that
+// admit_job and the two edges of the segment loop need.  too_long: the caller's words for a track that does not fit.
+int umx_hip_ctx::track_rate_plan(int rate, int length_at_rate, const char *too_long, TrackResample &rs, int &n44)
+{
+    const long long n = resampled_length(length_at_rate, rate, RS_MODEL_RATE);
+    if (n < 1 || n > 0x7fffffff / 2)
+    {
+        set_error(n < 1 ? "track: sample rate outside 8000 .. 192000 Hz" : too_long);
+        return UMX_ERR_ARG;
+    }
+    n44 = (int)n;
+    rs.rate = rate;
+    rs.length = length_at_rate;
+    if (int rc = resample_plan(rate, RS_MODEL_RATE, rs.fwd, &rs.fwd_taps))
+        return rc;
+    return resample_plan(RS_MODEL_RATE, rate, rs.back, &rs.back_taps);
+}
+
+// The admission of a job, for both drivers (tracks_once; the queue, engine_queue.h): `j` has its geometry (track_geometry) and, at
+// another rate, its j.rs (track_rate_plan); `acc` is the accumulator set it will write, `audio` its host audio of length_at_rate
+// frames at `rate` -- the rate and length the caller sees --, leaves_whole: it is an ensemble lane.  The set grows by what the job
+// needs, in this order (a failed allocation returns at once): accumulators, native-rate staging (a job with j.rs), int16 side, levels
+// record, hop energies; then the job is filled.  What the driver zeroes, and on which stream, is the driver's.
 int umx_hip_ctx::admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt, const float *audio, int rate, int length_at_rate, bool leaves_whole)
 {
     j.opt = opt;
     if (int rc = track_bufs_grow(acc, (size_t)j.L2))
         return rc;
+    if (j.rs.rate)
+        if (int rc = grow_only<float>({{&acc.rs.in, 2}, {&acc.rs.out[0], 2}, {&acc.rs.out[1], 2}, {&acc.rs.out[2], 2}, {&acc.rs.out[3], 2}}, acc.rs.cap,
+                                      (size_t)j.rs.length))
+            return rc;
     if (int rc = track_pcm16_grow(acc, opt.io, (size_t)length_at_rate, opt.n_host())) // (nothing for an fp32 call)
         return rc;
     if (opt.measures())
@@ -215,9 +237,9 @@ int umx_hip_ctx::admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt,
             return rc;
     j.audio = audio;
     j.acc = &acc;
-    // Its final regions are mixed in place and leave region by region -- unless it leaves whole behind its last segment: an ensemble
-    // lane (its mean leaves), a resampled track (behind its way back: leaves_whole of tracks_once), a rescaled one (its divisor needs
-    // every peak).  The last, at 44.1 kHz, is finished by track_call itself as ONE region.
+    // Its final regions are mixed in place and leave region by region (a resampled job's through the way back, range by range: DESIGN
+    // 23) -- unless it leaves whole behind its last segment: an ensemble lane (its mean leaves: leaves_whole of tracks_once), a rescaled
+    // track (its divisor needs every peak).  The last is finished by track_call itself as ONE region.
     j.by_region = !leaves_whole && !opt.rescale();
     j.whole_region = opt.rescale() && !leaves_whole;
     return UMX_OK;
@@ -238,36 +260,63 @@ hipError_t umx_hip_ctx::track_loudness_report(const TrackJob &j, int n_host, std
 // slots' streams do not wait for the null stream, and launches are queued ahead of the copy.
 // Samples of the job's padded signal (the track behind `lead` frames of silence) below `padded_end` must be there.
 // An int16 track goes into the set's staging buffer, at its frame number, and is decoded from there into the padded signal
-// on `st`, the stream of the call that needs these frames.  Unlike the fp32 copy the decode is not finished when this returns, and a
-// LATER call reads the last quarter of these frames too (segments overlap) -- on another slot stream, which on a one-track context is
-// not ordered behind this one before its STFT.  So every call's stream first waits for the set's `in16_ev`, recorded behind the most
-// recent decode of the set: each decode is then behind all earlier ones, and every reader behind every decode queued before it.  (A
-// set's event may stem from its previous job: that work has long finished.)
+// on `st`, the stream of the call that needs these frames.  A track at another rate goes into the set's native-rate
+// staging, as far as the wanted 44.1 kHz frames read it (resample_needs), and that range of the padded signal is resampled from there
+// on `st`.  Unlike the fp32 copy these kernels are not finished when this returns, and a LATER call reads the last quarter of these
+// frames too (segments overlap) -- on another slot stream, which on a one-track context is not ordered behind this one before its
+// STFT.  So every call's stream first waits for the set's `in_ev`, recorded behind the most recent kernel that wrote the set's `in`:
+// each such kernel is then behind all earlier ones, and every reader behind every writer queued before it.  (A set's event may stem
+// from its previous job: that work has long finished.)
 hipError_t umx_hip_ctx::track_upload_until(TrackJob &j, long long padded_end, hipStream_t st)
 {
     const bool s16 = j.opt.io.in_format == UMX_SAMPLE_S16;
-    if (s16 && j.acc->in16_ev)
-        if (hipError_t e = hipStreamWaitEvent(st, j.acc->in16_ev, 0))
+    TrackBufs &tb_ = *j.acc;
+    if ((s16 || j.rs.rate) && tb_.in_ev)
+        if (hipError_t e = hipStreamWaitEvent(st, tb_.in_ev, 0))
             return e;
-    const long long want = std::min<long long>(j.length, padded_end - j.lead);
-    if (want <= j.uploaded)
-        return hipSuccess;
-    const size_t from = (size_t)j.uploaded, count = (size_t)(want - j.uploaded);
-    hipError_t e;
-    if (s16)
+    // what is wanted of the track as the segments see it, and what that needs of the host's frames
+    long long want = std::min<long long>(j.length, padded_end - j.lead), host_want = want;
+    if (j.rs.rate)
     {
-        e = hipMemcpy(j.acc->in16 + from, reinterpret_cast<const uint32_t *>(j.audio) + from, sizeof(uint32_t) * count, hipMemcpyHostToDevice);
-        if (e == hipSuccess && !j.acc->in16_ev)
-            e = hipEventCreateWithFlags(&j.acc->in16_ev, hipEventDisableTiming);
-        if (e == hipSuccess)
-        {
-            launch_pcm16_decode(j.acc->in16 + from, reinterpret_cast<float2 *>(j.acc->in) + (size_t)j.lead + from, (int)count, st);
-            e = hipEventRecord(j.acc->in16_ev, st);
-        }
+        if (want < j.length) // (a range starts at an even frame: resample.h)
+            want += want & 1;
+        if (want <= j.done44)
+            return hipSuccess;
+        host_want = resample_needs(want, j.rs.rate, RS_MODEL_RATE, j.rs.length);
     }
-    else
-        e = hipMemcpy(j.acc->in + 2 * ((size_t)j.lead + from), j.audio + 2 * from, sizeof(float) * 2 * count, hipMemcpyHostToDevice);
-    j.uploaded = want;
+    hipError_t e = hipSuccess;
+    if (host_want > j.uploaded)
+    {
+        const size_t from = (size_t)j.uploaded, count = (size_t)(host_want - j.uploaded);
+        float *const dst = j.rs.rate ? tb_.rs.in + 2 * from : tb_.in + 2 * ((size_t)j.lead + from); // where host frame `from` goes as fp32
+        if (s16)
+        {
+            e = hipMemcpy(tb_.in16 + from, reinterpret_cast<const uint32_t *>(j.audio) + from, sizeof(uint32_t) * count, hipMemcpyHostToDevice);
+            if (e == hipSuccess && !tb_.in_ev)
+                e = hipEventCreateWithFlags(&tb_.in_ev, hipEventDisableTiming);
+            if (e == hipSuccess)
+            {
+                launch_pcm16_decode(tb_.in16 + from, reinterpret_cast<float2 *>(dst), (int)count, st);
+                e = hipEventRecord(tb_.in_ev, st);
+            }
+        }
+        else
+            e = hipMemcpy(dst, j.audio + 2 * from, sizeof(float) * 2 * count, hipMemcpyHostToDevice);
+        j.uploaded = host_want;
+    }
+    if (j.rs.rate && e == hipSuccess) // (want > done44)
+    {
+        const float *src = tb_.rs.in;
+        float *out = tb_.in + 2 * (size_t)j.lead;
+        if (!tb_.in_ev)
+            e = hipEventCreateWithFlags(&tb_.in_ev, hipEventDisableTiming);
+        if (e == hipSuccess)
+            e = launch_resample(j.rs.fwd, j.rs.fwd_taps, 1, &src, j.rs.length, &out, j.length, (int)j.done44, (int)(want - j.done44), st);
+        if (e == hipSuccess)
+            e = hipEventRecord(tb_.in_ev, st);
+        ++rs_launches[0];
+        j.done44 = want;
+    }
     return e;
 }
 
@@ -286,19 +335,24 @@ void umx_hip_ctx::track_mix(const MixSpec &mix, float *const stems[4], size_t st
     launch_stem_mix(mix, src, dst, count, st);
 }
 
-// umx.cpp:136-147: a finished region without the shift, to its job's n_host host buffers, once it is ready
+// umx.cpp:136-147: a finished region without the shift, to its job's n_host host buffers, once it is ready.  A resampled job's region
+// is the range of frames at the caller's rate that left with it, in the set's staging at their frame numbers.
 hipError_t umx_hip_ctx::track_region_download(const TrackRegion &r, float *const *out_host)
 {
     const TrackJob &j = *r.job;
     const int n_host = j.opt.n_host();
     const long long lo = std::max<long long>(r.start, j.lead), hi = std::min<long long>((long long)r.start + r.count, (long long)j.lead + j.length);
-    if (hi <= lo)
+    const size_t first = j.rs.rate ? (size_t)r.rs_first : (size_t)(lo - j.lead); // in the caller's track
+    const long long n = j.rs.rate ? r.rs_count : hi - lo;
+    if (n <= 0)
         return hipSuccess;
     hipError_t cerr = hipEventSynchronize(r.ready);
-    const size_t first = (size_t)(lo - j.lead), count = (size_t)(hi - lo);
+    const size_t count = (size_t)n;
     for (int t = 0; t < n_host && cerr == hipSuccess; ++t)
         if (j.opt.io.out_format == UMX_SAMPLE_S16) // (encoded behind the region's normalisation and mix, at its frame number: track_call)
             cerr = hipMemcpy(reinterpret_cast<uint32_t *>(out_host[t]) + first, j.acc->out16[t] + first, sizeof(uint32_t) * count, hipMemcpyDeviceToHost);
+        else if (j.rs.rate)
+            cerr = hipMemcpy(out_host[t] + 2 * first, j.acc->rs.out[t] + 2 * first, sizeof(float) * 2 * count, hipMemcpyDeviceToHost);
         else
             cerr = hipMemcpy(out_host[t] + 2 * first, j.acc->out[t] + 2 * (size_t)lo, sizeof(float) * 2 * count, hipMemcpyDeviceToHost);
     return cerr;
@@ -374,7 +428,34 @@ int umx_hip_ctx::track_call(const TrackLane *lanes, int nl, unsigned flags, int 
         const TrackOptions &opt = j->opt;
         if (opt.mix)
             track_mix(*opt.mix, tb_.out, (size_t)rg.start, tb_.in, (size_t)rg.start, rg.count, st);
-        if (opt.io.out_format == UMX_SAMPLE_S16 || opt.measures() || opt.loudness) // the region's frames of the caller's track, as they will
+        if (j->rs.rate)
+        {
+            // DESIGN 23, the way back: the frames at the caller's rate whose whole window lies in what is final now (resample_ready; an even
+            // count, or all) are resampled from the accumulators into the set's staging and leave from there, at the caller's frame
+            // numbers; the range may be empty, the region stays one.  This stream is behind every earlier call's (trk_acc_ev), so the
+            // accumulators below the region and the staging's earlier frames (a loudness warm-up reads them) are there.
+            const long long fin = std::min<long long>(std::max<long long>((long long)rg.start + rg.count - j->lead, 0), j->length);
+            long long r = resample_ready(fin, RS_MODEL_RATE, j->rs.rate, j->length, j->rs.length);
+            if (r < j->rs.length)
+                r &= ~1LL;
+            rg.rs_first = (int)j->out_done;
+            rg.rs_count = (int)std::max<long long>(r - j->out_done, 0);
+            if (rg.rs_count > 0)
+            {
+                const float *src[4] = {};
+                for (int t = 0; t < opt.n_host(); ++t)
+                    src[t] = tb_.out[t] + 2 * (size_t)j->lead;
+                if (launch_resample(j->rs.back, j->rs.back_taps, opt.n_host(), src, j->length, tb_.rs.out, j->rs.length, rg.rs_first, rg.rs_count, st) != hipSuccess)
+                {
+                    set_error("track: resampling a region failed");
+                    return UMX_ERR_HIP;
+                }
+                ++rs_launches[1];
+                track_leave(*j, tb_.rs.out, (size_t)rg.rs_first, rg.rs_count, rg.rs_first, st);
+                j->out_done = r;
+            }
+        }
+        else if (opt.io.out_format == UMX_SAMPLE_S16 || opt.measures() || opt.loudness) // the region's frames of the caller's track, as they will
         {                                                    // leave (an int16 copy is not written over the accumulators: the next
                                                              // segment's overlap-add still reads its neighbours)
             const long long lo = std::max<long long>(rg.start, j->lead), hi = std::min<long long>((long long)rg.start + rg.count, (long long)j->lead + j->length);
@@ -435,26 +516,13 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     // A track at another rate runs as the n44 = ceil(length L / M) frames of its 44.1 kHz version: `length` below is
     // that length, length_in the caller's.
     int length[LSTMB_MAX_TRACKS];
-    bool resampled[LSTMB_MAX_TRACKS] = {};
-    ResampleGeom rs_fwd[LSTMB_MAX_TRACKS], rs_back[LSTMB_MAX_TRACKS];
-    const float *rs_fwd_taps[LSTMB_MAX_TRACKS] = {}, *rs_back_taps[LSTMB_MAX_TRACKS] = {};
+    TrackResample rs[LSTMB_MAX_TRACKS];
     for (int ln = 0; ln < nt; ++ln)
     {
         length[ln] = length_in[ln];
-        if (!rq.rate || rq.rate[ln] == RS_MODEL_RATE)
-            continue;
-        const long long n44 = resampled_length(length_in[ln], rq.rate[ln], RS_MODEL_RATE);
-        if (n44 < 1 || n44 > 0x7fffffff / 2)
-        {
-            set_error(n44 < 1 ? "track: sample rate outside 8000 .. 192000 Hz" : "track: too long");
-            return UMX_ERR_ARG;
-        }
-        length[ln] = (int)n44;
-        resampled[ln] = true;
-        if (int rc = resample_plan(rq.rate[ln], RS_MODEL_RATE, rs_fwd[ln], &rs_fwd_taps[ln]))
-            return rc;
-        if (int rc = resample_plan(RS_MODEL_RATE, rq.rate[ln], rs_back[ln], &rs_back_taps[ln]))
-            return rc;
+        if (rq.rate && rq.rate[ln] != RS_MODEL_RATE)
+            if (int rc = track_rate_plan(rq.rate[ln], length_in[ln], "track: too long", rs[ln], length[ln]))
+                return rc;
     }
     if (ph_next != -1)
     {
@@ -487,13 +555,16 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         }
         L2max = std::max(L2max, j.L2);
         max_segs = std::max(max_segs, j.segs);
+        if (!ensemble || ln == 0) // (an ensemble's one track is staged and resampled once, by lane 0; the other lanes get its 44.1 kHz frames)
+            j.rs = rs[ln];
     }
+    rs_launches[0] = rs_launches[1] = 0;
     // lanes whose per-segment stem buffers are needed: one per track, or (reset mode) one per segment of a call
     const int seg_lanes = reset_lanes ? std::min(B, max_segs) : nt;
     if (trk.size() < (size_t)seg_lanes)
         trk.resize(seg_lanes);
     for (int ln = 0; ln < nt; ++ln)
-        if (int rc = admit_job(job[ln], trk[ln], opt, rq.audio[ln], rq.rate ? rq.rate[ln] : RS_MODEL_RATE, length_in[ln], ensemble || resampled[ln]))
+        if (int rc = admit_job(job[ln], trk[ln], opt, rq.audio[ln], rq.rate ? rq.rate[ln] : RS_MODEL_RATE, length_in[ln], ensemble))
             return rc;
     if (ensemble) // the mean of the lanes' stems: n44 frames
         if (int rc = grow_only<float>({{&ens_out[0], 2}, {&ens_out[1], 2}, {&ens_out[2], 2}, {&ens_out[3], 2}}, ens_cap, (size_t)length[0]))
@@ -514,42 +585,28 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         if (loud)
             UMX_HIP_CHECK(hipMemset(tb_.hopE, 0, sizeof(double) * std::max<size_t>(1, (size_t)n_host * 2 * (size_t)job[ln].loud_hops)));
     }
-    // a resampled track goes up whole at its own rate, into a grow-only staging buffer, and is resampled straight into the padded
-    // 44.1 kHz signal (track_upload_until then has nothing left to do for it)
-    if (rs_stage.size() < (size_t)nt)
-        rs_stage.resize(nt);
-    for (int ln = 0; ln < (ensemble ? 1 : nt); ++ln) // (an ensemble's one track: staged and resampled once, into lane 0)
-    {
-        if (!resampled[ln])
-            continue;
-        RsStage &rs = rs_stage[ln];
-        if (int rc = grow_only<float>({{&rs.in, 2}, {&rs.out[0], 2}, {&rs.out[1], 2}, {&rs.out[2], 2}, {&rs.out[3], 2}}, rs.cap, (size_t)length_in[ln]))
-            return rc;
-        if (opt.io.in_format == UMX_SAMPLE_S16) // (decoded on the null stream, as the resampler below is launched)
+    // A resampled track goes up and through the resampler range by range, with the call that needs the frames (track_upload_until) --
+    // but an ensemble's: whole, now, in one launch, on the null stream.
+    if (ensemble && job[0].rs.rate)
+        if (track_upload_until(job[0], job[0].L2, nullptr) != hipSuccess)
         {
-            UMX_HIP_CHECK(hipMemcpy(trk[ln].in16, rq.audio[ln], sizeof(uint32_t) * (size_t)length_in[ln], hipMemcpyHostToDevice));
-            launch_pcm16_decode(trk[ln].in16, reinterpret_cast<float2 *>(rs.in), length_in[ln], nullptr);
+            set_error("track: upload failed");
+            return UMX_ERR_HIP;
         }
-        else
-            UMX_HIP_CHECK(hipMemcpy(rs.in, rq.audio[ln], sizeof(float) * 2 * (size_t)length_in[ln], hipMemcpyHostToDevice));
-        const float *src = rs.in;
-        float *dst = trk[ln].in + 2 * (size_t)job[ln].lead;
-        UMX_HIP_CHECK(launch_resample(rs_fwd[ln], rs_fwd_taps[ln], 1, &src, length_in[ln], &dst, length[ln], nullptr));
-    }
     // an ensemble's track crosses PCIe once, whole, into lane 0 (unless the resampler has just written it there); the other lanes
     // get it from lane 0, device to device, behind their own shift's zeros (the memsets above)
     if (ensemble)
     {
         float *first = trk[0].in + 2 * (size_t)job[0].lead;
         const size_t bytes = sizeof(float) * 2 * (size_t)length[0];
-        if (!resampled[0])
+        if (!job[0].rs.rate)
             UMX_HIP_CHECK(hipMemcpy(first, rq.audio[0], bytes, hipMemcpyHostToDevice));
         for (int ln = 1; ln < nt; ++ln)
             UMX_HIP_CHECK(hipMemcpy(trk[ln].in + 2 * (size_t)job[ln].lead, first, bytes, hipMemcpyDeviceToDevice));
     }
     UMX_HIP_CHECK(hipDeviceSynchronize());
-    for (int ln = 0; ln < nt; ++ln)
-        if (resampled[ln] || ensemble) // (on the device whole already)
+    for (int ln = 0; ln < nt && ensemble; ++ln) // (on the device whole already)
+        if (!job[ln].rs.rate)
             job[ln].uploaded = length[ln];
 
     const float total_reps = std::ceil((float)L2max / (float)stride); // umx.cpp:208 (of the longest track)
@@ -596,9 +653,9 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
                 rq.progress(done, rq.progress_user);
         }
     }
-    // What leaves whole, behind the last segment's overlap-add: four stem buffers of lane ln's track from frame `start` on are mixed
-    // at 44.1 kHz (column 4: the lane's padded input), a resampled track's n_host buffers go back to the caller's rate in one launch
-    // into the lane's rs_stage, and `whole` notes where the host finds them.
+    // What leaves whole, behind the last segment's overlap-add -- an ensemble's mean: its four buffers from frame `start` on are mixed
+    // at 44.1 kHz (column 4: lane 0's padded input), a resampled track's n_host buffers go back to the caller's rate in one launch
+    // into lane 0's staging, and `whole` notes where the host finds them.
     hipError_t cerr = hipSuccess;
     const hipStream_t last_st = slot[last_slot].stream;
     float *whole[LSTMB_MAX_TRACKS][4] = {};
@@ -610,10 +667,11 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         const float *src[4];
         for (int t = 0; t < 4; ++t)
             src[t] = whole[ln][t] = stems[t] + 2 * start;
-        if (resampled[ln])
+        if (j.rs.rate)
         {
-            cerr = launch_resample(rs_back[ln], rs_back_taps[ln], n_host, src, j.length, rs_stage[ln].out, length_in[ln], last_st);
-            std::copy(rs_stage[ln].out, rs_stage[ln].out + 4, whole[ln]);
+            cerr = launch_resample(j.rs.back, j.rs.back_taps, n_host, src, j.length, j.acc->rs.out, length_in[ln], 0, length_in[ln], last_st);
+            ++rs_launches[1];
+            std::copy(j.acc->rs.out, j.acc->rs.out + 4, whole[ln]);
         }
         if (cerr == hipSuccess) // at the caller's rate and length, frame 0 first: measured, encoded, rescaled as the job says
         {
@@ -645,9 +703,6 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         ens_timed = true;
         leaves_whole(0, ens_out, 0);
     }
-    for (int ln = 0; ln < nt && cerr == hipSuccess && !ensemble; ++ln)
-        if (resampled[ln])
-            leaves_whole(ln, trk[ln].out, (size_t)job[ln].lead);
     for (const TrackRegion &rg : regions.v) // umx.cpp:136-147: drop the shift
         if (cerr == hipSuccess)
             cerr = track_region_download(rg, rq.out + n_host * (rg.job - job));

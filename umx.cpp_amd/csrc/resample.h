@@ -54,6 +54,34 @@ inline bool resample_geom(int rate_in, int rate_out, ResampleGeom &g)
     return true;
 }
 
+// The range rule, host arithmetic in 64-bit integers.  Output j reads the input frames c - D .. c + D + 1, c = floor(j M / L):
+// the whole window, zero taps included.
+// resample_needs: the leading input frames that outputs [0, n_out_wanted) read: floor((n_out_wanted - 1) M / L) + D + 2, at most n_in.
+inline long long resample_needs(long long n_out_wanted, int rate_in, int rate_out, long long n_in)
+{
+    ResampleGeom g;
+    if (n_out_wanted < 0 || n_in < 0 || !resample_geom(rate_in, rate_out, g))
+        return -1;
+    if (n_out_wanted == 0)
+        return 0;
+    return std::min(n_in, (n_out_wanted - 1) * g.M / g.L + g.D + 2);
+}
+// resample_ready: the leading output frames whose whole window lies inside the first n_in_final input frames: j with
+// floor(j M / L) + D + 1 <= n_in_final - 1, that is j < (n_in_final - D - 1) L / M.  Beyond n_in the input is zeros, which are known:
+// n_in_final >= n_in makes all n_out outputs ready.
+inline long long resample_ready(long long n_in_final, int rate_in, int rate_out, long long n_in, long long n_out)
+{
+    ResampleGeom g;
+    if (n_in_final < 0 || n_in < 0 || n_out < 0 || !resample_geom(rate_in, rate_out, g))
+        return -1;
+    if (n_in_final >= n_in)
+        return n_out;
+    const long long a = n_in_final - g.D - 1;
+    if (a <= 0)
+        return 0;
+    return std::min(n_out, (a * g.L + g.M - 1) / g.M);
+}
+
 // natural output length ceil(n L / M) (torchaudio's target_length)
 inline long long resampled_length(long long n, int rate_in, int rate_out)
 {
@@ -90,21 +118,23 @@ typedef float rs_f2 __attribute__((ext_vector_type(2)));
 typedef unsigned rs_u4 __attribute__((ext_vector_type(4)));
 typedef unsigned rs_u2 __attribute__((ext_vector_type(2)));
 
-// One workgroup: `block` consecutive output frames of buffer blockIdx.y.  The input span those frames read is staged in LDS
+// One workgroup: `block` consecutive output frames of buffer blockIdx.y, of the range [first, end) of the n_out outputs: the grid starts
+// at frame `first` (even, so that a range's 16-byte stores are aligned as the whole launch's are), the last workgroup is clipped to `end`.
+// Everything is computed from the absolute frame j0, so a range gives the bits of the same frames of the whole launch.  The input span those frames read is staged in LDS
 // (16-byte loads through a buffer resource whose range is the valid part of the span: zeros outside [0, n_in) are written, not
 // loaded), the tap table too if it is small; then each thread forms two adjacent outputs and stores them as one 16-byte
-// non-temporal store.  The output resource covers exactly this workgroup's frames of [0, n_out).
+// non-temporal store.  The output resource covers exactly this workgroup's frames of [first, end).
 // LDS: span frames (float2), then the L x K taps if TAPS_LDS, in rows of K + 1: adjacent lanes read rows of different phases, and
 // with an even row stride (K is even) their addresses would fall on a few banks only (16 taps = 64 bytes: 16-way conflicts).
 template <bool TAPS_LDS>
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleIO io, const float *__restrict__ taps, int n_in, int n_out,
-                                                              int M, int L, int D, int K, int block, int span_cap)
+                                                              int first, int end, int M, int L, int D, int K, int block, int span_cap)
 {
     extern __shared__ float2 rs_lds[];
     float2 *xs = rs_lds;
     const int buf = blockIdx.y, tid = threadIdx.x;
-    const long long j0 = (long long)blockIdx.x * block;
-    const int nloc = (int)min((long long)block, (long long)n_out - j0);
+    const long long j0 = (long long)first + (long long)blockIdx.x * block;
+    const int nloc = (int)min((long long)block, (long long)min(end, n_out) - j0);
     const long long c0 = j0 * M / L, c1 = (j0 + nloc - 1) * M / L;
     const int phi0 = (int)(j0 * M - c0 * L);
     const long long s_lo = c0 - D, s_hi = c1 + D + 2; // staged input frames [s_lo, s_hi)
@@ -183,11 +213,12 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleIO io, con
     }
 }
 
-// n_buffers (1 .. 4) buffers of n_in frames -> n_out frames each; taps_dev = the table of resample_taps in device memory
+// n_buffers (1 .. 4) buffers of n_in frames -> frames [first, first + count) of their n_out output frames each (first even, the range
+// inside [0, n_out): the caller checks); taps_dev = the table of resample_taps in device memory.  (0, n_out) is the whole-buffer launch.
 inline hipError_t launch_resample(const ResampleGeom &g, const float *taps_dev, int n_buffers, const float *const *in, int n_in,
-                                  float *const *out, int n_out, hipStream_t st)
+                                  float *const *out, int n_out, int first, int count, hipStream_t st)
 {
-    if (n_out < 1)
+    if (count < 1)
         return hipSuccess;
     ResampleIO io = {};
     for (int b = 0; b < n_buffers; ++b)
@@ -195,14 +226,14 @@ inline hipError_t launch_resample(const ResampleGeom &g, const float *taps_dev, 
         io.in[b] = in[b];
         io.out[b] = out[b];
     }
-    const dim3 grid((unsigned)(((long long)n_out + g.block - 1) / g.block), (unsigned)n_buffers);
+    const dim3 grid((unsigned)(((long long)count + g.block - 1) / g.block), (unsigned)n_buffers);
     const bool taps_lds = (long long)g.L * (g.K + 1) <= RS_TAPS_LDS_MAX;
     const size_t lds = (size_t)g.span * sizeof(float2) + (taps_lds ? (size_t)g.L * (g.K + 1) * sizeof(float) : 0);
     if (taps_lds)
-        hipLaunchKernelGGL(resample_kernel<true>, grid, dim3(RS_THREADS), lds, st, io, taps_dev, n_in, n_out, g.M, g.L, g.D, g.K, g.block,
+        hipLaunchKernelGGL(resample_kernel<true>, grid, dim3(RS_THREADS), lds, st, io, taps_dev, n_in, n_out, first, first + count, g.M, g.L, g.D, g.K, g.block,
                            g.span);
     else
-        hipLaunchKernelGGL(resample_kernel<false>, grid, dim3(RS_THREADS), lds, st, io, taps_dev, n_in, n_out, g.M, g.L, g.D, g.K, g.block,
+        hipLaunchKernelGGL(resample_kernel<false>, grid, dim3(RS_THREADS), lds, st, io, taps_dev, n_in, n_out, first, first + count, g.M, g.L, g.D, g.K, g.block,
                            g.span);
     return hipGetLastError();
 }

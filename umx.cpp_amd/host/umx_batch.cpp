@@ -5,10 +5,11 @@
 // four stems, written to <out dir>/<wav stem>/target_{0..3}.wav.  More files than track lanes (at most 64; UMX_BATCH_LANES=<1..64> caps
 // them) go through the track queue (umx_hip_separate_queue): a lane takes the next file the moment its file ends, one
 // thread decodes files ahead (at most lanes + 2 decoded files in memory), one writes the stems, and the GPU waits for neither.
-// UMX_BATCH_QUEUE=0 forces the pass-by-pass loop (`lanes` files decoded, run for as long as the longest, written), which also serves
-// UMX_RESAMPLE=1 (the queue takes 44.1 kHz tracks only).  Either way a file's stems and its output directory are the same.
+// UMX_BATCH_QUEUE=0 forces the pass-by-pass loop (`lanes` files decoded, run for as long as the longest, written).  Either way a
+// file's stems and its output directory are the same.
 // Environment: UMX_DEVICE, UMX_NO_WIENER, UMX_WIENER_ITERS, UMX_SHIFT_OFFSET, UMX_RESAMPLE (as umx-cli: files of any rate of
-// 8 .. 192 kHz, mixed rates in one pass through umx_hip_separate_tracks_rate, stems written at each file's rate), UMX_TARGETS and
+// 8 .. 192 kHz, mixed rates in one run -- a queue job carries its file's rate, the loop goes through umx_hip_separate_tracks_rate --,
+// stems written at each file's rate), UMX_TARGETS and
 // UMX_RESIDUAL (as umx-cli: target_<t>.wav of the chosen targets and residual.wav per file; host/targets_env.h), UMX_SOFTMASK (as umx-cli),
 // UMX_MIX (as umx-cli, host/mix_env.h: the same matrix for every file, <out dir>/<wav stem>/<name>.wav and no target_*.wav),
 // UMX_PCM16 and UMX_PCM16_DITHER (as umx-cli, DESIGN 19: every output a 16-bit PCM WAV quantised on the device, through the queue and
@@ -47,7 +48,7 @@ static int env_int(const char *name, int dflt)
 // and max_unwritten the finished ones: done waits for the writer rather than let stems pile up.
 struct FileJob
 {
-    int index = 0, n = 0;
+    int index = 0, n = 0, rate = UMX_SAMPLE_RATE; // (the file's own rate with UMX_RESAMPLE=1)
     float *audio = nullptr;
     int16_t *audio16 = nullptr; // UMX_PCM16 with 16-bit PCM files: the file's samples as they are
     std::vector<std::vector<float>> stems;
@@ -97,6 +98,7 @@ struct BatchQueue
         job->audio = fj->audio16 ? reinterpret_cast<const float *>(fj->audio16) : fj->audio;
         job->length = fj->n;
         job->shift_offset = q.shift_offset;
+        job->rate = fj->rate;
         job->tag = fj;
         return 1;
     }
@@ -254,8 +256,8 @@ int main(int argc, const char **argv)
         return true;
     };
     const int shift_offset = env_int("UMX_SHIFT_OFFSET", -1) < 0 ? first_rand_shift : env_int("UMX_SHIFT_OFFSET", -1);
-    // more files than lanes: the track queue (a one-lane context is not track-batched and keeps the loop, as UMX_RESAMPLE does)
-    const bool queued = nfiles > lanes && env_int("UMX_BATCH_QUEUE", 1) != 0 && !resample && umx_hip_lstm_is_batched(ctx);
+    // more files than lanes: the track queue (a one-lane context is not track-batched and keeps the loop)
+    const bool queued = nfiles > lanes && env_int("UMX_BATCH_QUEUE", 1) != 0 && umx_hip_lstm_is_batched(ctx);
     if (queued)
     {
         BatchQueue q;
@@ -278,8 +280,9 @@ int main(int argc, const char **argv)
                 fj->index = f;
                 int ch = 0;
                 char rerr[UMX_ERRLEN] = "";
-                const bool bad = (in16 ? umx_wav_load_pcm16(argv[3 + f], &fj->audio16, &fj->n, &ch, nullptr, rerr)
-                                       : umx_wav_load(argv[3 + f], &fj->audio, &fj->n, &ch, rerr)) != 0; // umx.cpp:56
+                const bool bad = (in16       ? umx_wav_load_pcm16(argv[3 + f], &fj->audio16, &fj->n, &ch, resample ? &fj->rate : nullptr, rerr)
+                                  : resample ? umx_wav_load_rate(argv[3 + f], &fj->audio, &fj->n, &ch, &fj->rate, rerr)
+                                             : umx_wav_load(argv[3 + f], &fj->audio, &fj->n, &ch, rerr)) != 0; // umx.cpp:56
                 std::lock_guard<std::mutex> lock(q.m);
                 if (bad)
                 {
@@ -287,7 +290,7 @@ int main(int argc, const char **argv)
                     delete fj;
                     break;
                 }
-                q.audio_secs += fj->n / (double)UMX_SAMPLE_RATE;
+                q.audio_secs += fj->n / (double)fj->rate;
                 q.decoded.push_back(fj);
                 q.cv.notify_all();
             }
@@ -314,7 +317,7 @@ int main(int argc, const char **argv)
                     bufs[t] = fj->stems[t].data();
                     bufs16[t] = fj->stems16[t].data();
                 }
-                const bool ok = write_file(fj->index, bufs, bufs16, fj->n, UMX_SAMPLE_RATE, fj->levels, fj->loudness, werr);
+                const bool ok = write_file(fj->index, bufs, bufs16, fj->n, fj->rate, fj->levels, fj->loudness, werr);
                 std::lock_guard<std::mutex> lock(q.m);
                 q.unwritten.pop_front(); // (counted until it is written: the stems are in memory until then)
                 if (!ok && q.error.empty())
