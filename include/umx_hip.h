@@ -433,7 +433,7 @@ int umx_hip_debug_queue_calls(umx_hip_ctx *ctx);
  * UMX_SAMPLE_F32 both ways, IS that call: the same launches, nothing allocated.  UMX_SAMPLE_S16 in: audio[i] points at length[i]
  * interleaved int16 stereo frames; out: every output buffer receives exactly length[i] such frames.  On the device a format costs 4 B
  * per frame of the track for the input and 4 B per frame and output buffer, only while it is used.  UMX_ERR_ARG, naming the reason
- * and leaving the context usable, for a format that is neither of the two, for dither != 0 with an fp32 output and for a NULL buffer.
+ * and leaving the context usable, for a format that is none of UMX_SAMPLE_F32, _S16 and _S24 (below), for dither != 0 with an fp32 output and for a NULL buffer.
  * Reset mode, other sample rates (the dither is indexed at the caller's rate), the mix matrix (gains == NULL: the four stems, n_out
  * ignored) and every per-call flag work as in the fp32 calls.  The shift ensemble, the multi-GPU driver (umx_mgpu.h) and the
  * per-segment infer calls do not offer the formats. */
@@ -442,7 +442,7 @@ int umx_hip_debug_queue_calls(umx_hip_ctx *ctx);
 typedef struct umx_sample_io
 {
     int in_format, out_format; /* UMX_SAMPLE_* of the audio and of the output buffers */
-    int dither;                /* != 0: TPDF dither before the rounding (UMX_SAMPLE_S16 outputs only) */
+    int dither;                /* != 0: TPDF dither before the rounding (UMX_SAMPLE_S16 and UMX_SAMPLE_S24 outputs only) */
     unsigned dither_seed;
 } umx_sample_io;
 /* umx_hip_separate_tracks_mix (rate == NULL: 44100 for all; gains == NULL: umx_hip_separate_tracks_rate) with the formats */
@@ -461,6 +461,38 @@ int umx_hip_pcm16_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *co
 /* the same rules on the host (no GPU, no context): n_values samples; n_frames stereo frames of output buffer `buffer` */
 int umx_hip_pcm16_decode_host(const int16_t *q, long long n_values, float *x);
 int umx_hip_pcm16_encode_host(const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, int16_t *q);
+/* Packed 24-bit PCM in and out of the same calls: UMX_SAMPLE_S24 on either side of a umx_sample_io, in any combination
+ * with the two formats above.  Masters, stems handed to a mixer and most sources that are not 16-bit are 24-bit files; packed they
+ * are 6 B per stereo frame each way, and 24-bit is the one integer format that fp32 carries without loss.  The rules, to the bit:
+ *   layout   a sample is 3 bytes, little-endian, two's complement; a stereo frame is 6 bytes, L then R, exactly as a WAV data chunk
+ *            holds it.  A buffer is length x 6 bytes.  A DEVICE buffer must be 2-byte aligned (frames are 6 bytes, so an even base
+ *            is all it takes); the device entry points refuse an odd address with UMX_ERR_ARG.
+ *   decode   x = (float)q * 2^-23, that is q / 8388608.f: exact, and what umx_wav_load gives for a 24-bit file, so a packed upload
+ *            runs on the bits the float loader would have produced
+ *   encode   of output buffer m, channel ch, frame k of the caller's track (as above):
+ *                v = x * 8388608.0f                                       exact short of overflow
+ *                r = rint((double)v + (dither ? (double)d(seed, m, ch, k) : 0.0))   the sum in double, ONE rounding (ties to even)
+ *                q = r is NaN ? 0 : min(max(r, -8388608), 8388607)
+ *            The sum is formed in double because at |v| >= 2^22 an fp32 v + d falls on a 0.5 grid before the rounding (rintf of the
+ *            fp32 sum differs from this rule for 2.79 M of the 2^24 codes); the double sum is exact for every finite v below 2^24.
+ *   dither   the d of the int16 rule: the same hash, the same keys (seed, m, ch), the same frame index k of the caller's track at the
+ *            caller's rate; here it lies in (-1, 1) LSB of the 24-bit grid
+ * encode(decode(q)) == q for all 2^24 codes without dither, within 1 LSB with it.  Full scale: the decode divides by 2^23 (the
+ * loader's scale), so the largest code is (2^23 - 1) / 2^23 < 1 and +1.0f encodes to 8388607 AND counts as clipped (-1.0f is code
+ * -8388608, not clipped).  clipped[m] of umx_levels, for a UMX_SAMPLE_S24 output: the samples with r > 8388607 or r < -8388608, r
+ * with the dither term and over the rescale divisor, exactly as for int16; the divisor rule is unchanged, and with a finite peak
+ * |v| <= 2^23 / 1.01 up to rounding (8305552.5), so nothing clamps and clipped is 0.  dither != 0 with an fp32 output stays refused.
+ * On the device a format costs 6 B per frame of the track for the input and 6 B per frame and output buffer, only while it is used.
+ * The kernels on the caller's device buffers, queued on hip_stream: n packed frames (2-byte aligned) <-> (2,n) interleaved fp32
+ * (8-byte aligned); exactly 6 n bytes of every packed output are written and no neighbouring byte is touched.  Encode: as
+ * umx_hip_pcm16_encode_device; encode_rescaled: as umx_hip_pcm16_encode_rescaled_device below (on x / g, adds what it clamps to
+ * acc_dev's clipped).  The host forms: n_values samples of 3 bytes; n_frames stereo frames of output buffer `buffer`. */
+#define UMX_SAMPLE_S24 3
+int umx_hip_pcm24_decode_device(umx_hip_ctx *ctx, const void *in_dev, int n, float *out_dev, void *hip_stream);
+int umx_hip_pcm24_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
+                                const umx_sample_io *io, void *const *out_dev, void *hip_stream);
+int umx_hip_pcm24_decode_host(const void *q, long long n_values, float *x);
+int umx_hip_pcm24_encode_host(const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, void *q);
 /* Output levels and clip handling.  A separated stem is not bounded by the mixture: Wiener stems of a track mastered to
  * full scale, or a mix row such as mix - 0.5 vocals, pass 1.0, and the int16 encode clamps.  The levels of what leaves are measured
  * on the device, where every output frame is final before it is encoded or copied.  The rules, to the bit:
@@ -513,7 +545,7 @@ int umx_hip_separate_queue_levels(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_
 /* the kernels on the caller's device buffers ((2,n) interleaved fp32, 8-byte aligned), queued on hip_stream; acc_dev: a
  * umx_levels_acc in device memory that the caller has zeroed, launches accumulate into it.
  * levels: buffer b of 1 .. 4 is output b, its frame i frame first_frame + i; io == NULL or an fp32 out_format: clipped stays as it
- * is, else the clamped samples of the plain encode are counted with io's dither.  Exactly the record is written.
+ * is, else the clamped samples of that format's plain encode are counted with io's dither.  Exactly the record is written.
  * pcm16_encode_rescaled: the encode of umx_hip_pcm16_encode_device on x / g, g formed from acc_dev's peak words by the rule; the
  * samples it clamps (possible only where the divisor is 1) are added to acc_dev's clipped.  rescale: x / g in place (nothing is
  * written where the divisor is 1). */
@@ -521,9 +553,11 @@ int umx_hip_levels_device(umx_hip_ctx *ctx, int n_buffers, const float *const *i
                           const umx_sample_io *io, umx_levels_acc *acc_dev, void *hip_stream);
 int umx_hip_pcm16_encode_rescaled_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
                                          const umx_sample_io *io, int16_t *const *out_dev, umx_levels_acc *acc_dev, void *hip_stream);
+int umx_hip_pcm24_encode_rescaled_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
+                                         const umx_sample_io *io, void *const *out_dev, umx_levels_acc *acc_dev, void *hip_stream);
 int umx_hip_rescale_device(umx_hip_ctx *ctx, int n_buffers, float *const *bufs_dev, int n, const umx_levels_acc *acc_dev, void *hip_stream);
 /* the same rules on the host (no GPU, no context): n_frames stereo frames of output buffer `buffer` accumulate into *acc; clipped is
- * counted for a UMX_SAMPLE_S16 out_format of io, on x / clip_divisor when clip_divisor != 1.  The divisor of peaks peak[0 .. n). */
+ * counted for a UMX_SAMPLE_S16 or UMX_SAMPLE_S24 out_format of io (by that format's rule), on x / clip_divisor when clip_divisor != 1.  The divisor of peaks peak[0 .. n). */
 int umx_hip_levels_host(const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, float clip_divisor,
                         umx_levels_acc *acc);
 float umx_hip_rescale_gain(const float *peak, int n);

@@ -63,6 +63,12 @@ int umx_wav_write_f32_rate(const char *path, const float *audio, int n_frames, i
 int umx_wav_load_pcm16(const char *path, int16_t **audio_out, int *n_frames_out, int *channels_in_file, int *rate_out, char *err);
 void umx_wav_free_pcm16(int16_t *audio);
 int umx_wav_write_pcm16_rate(const char *path, const int16_t *audio, int n_frames, int rate, char *err);
+/* 24-bit PCM as it is, for UMX_SAMPLE_S24: the same three with packed frames -- 6 bytes each, L then R, 3 bytes per sample
+ * little-endian, as the data chunk holds them; mono duplicated; from a 24-bit PCM file only.  audio_out == NULL probes as above.
+ * write: fmt tag 1, 24 bits, block align 6. */
+int umx_wav_load_pcm24(const char *path, unsigned char **audio_out, int *n_frames_out, int *channels_in_file, int *rate_out, char *err);
+void umx_wav_free_pcm24(unsigned char *audio);
+int umx_wav_write_pcm24_rate(const char *path, const unsigned char *audio, int n_frames, int rate, char *err);
 
 /* ---- segmented apply: replaces split_inference / shift_inference (umx.cpp:99-295).
  * The backend is the per-segment call (umx_inference, umx.cpp:226-227): audio (2,n) -> out[4] (2,n);

@@ -98,7 +98,9 @@ class SampleIO(C.Structure):
 
 
 SAMPLE_F32, SAMPLE_S16 = 0, 1  # UMX_SAMPLE_*: the formats of the host buffers of the whole-track calls
+SAMPLE_S24 = 3  # packed 24-bit PCM, 6 bytes per stereo frame; 2 stays an unknown format
 _i16p = C.POINTER(C.c_int16)
+_u8p = C.POINTER(C.c_uint8)
 
 QUEUE_NEXT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(QueueJobRate))
 QUEUE_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJobRate))
@@ -286,6 +288,13 @@ def hip_lib():
                                                 C.POINTER(C.c_void_p), C.c_void_p]
     lib.umx_hip_pcm16_decode_host.argtypes = [_i16p, C.c_longlong, _fp]
     lib.umx_hip_pcm16_encode_host.argtypes = [_fp, C.c_int, C.c_int, C.c_longlong, C.POINTER(SampleIO), _i16p]
+    lib.umx_hip_pcm24_decode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.umx_hip_pcm24_encode_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.POINTER(SampleIO),
+                                                C.POINTER(C.c_void_p), C.c_void_p]
+    lib.umx_hip_pcm24_encode_rescaled_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.POINTER(SampleIO),
+                                                         C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+    lib.umx_hip_pcm24_decode_host.argtypes = [_u8p, C.c_longlong, _fp]
+    lib.umx_hip_pcm24_encode_host.argtypes = [_fp, C.c_int, C.c_int, C.c_longlong, C.POINTER(SampleIO), _u8p]
     lib.umx_hip_levels_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.POINTER(SampleIO), C.c_void_p,
                                           C.c_void_p]
     lib.umx_hip_pcm16_encode_rescaled_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.POINTER(SampleIO),
@@ -364,7 +373,9 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_pcm16_encode_rescaled_device", "umx_hip_rescale_device", "umx_hip_levels_host", "umx_hip_rescale_gain",
                "umx_hip_separate_tracks_loudness", "umx_hip_separate_queue_loudness", "umx_hip_kweight_hops_device",
                "umx_hip_kweight_coeffs", "umx_hip_kweight_hops_host", "umx_hip_loudness_gate",
-               "umx_hip_resample_needs", "umx_hip_resample_ready", "umx_hip_resample_range_device", "umx_hip_debug_resample_launches"]
+               "umx_hip_resample_needs", "umx_hip_resample_ready", "umx_hip_resample_range_device", "umx_hip_debug_resample_launches",
+               "umx_hip_pcm24_decode_device", "umx_hip_pcm24_encode_device", "umx_hip_pcm24_encode_rescaled_device",
+               "umx_hip_pcm24_decode_host", "umx_hip_pcm24_encode_host"]
 
 
 def sample_io(in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None):
@@ -395,9 +406,55 @@ def pcm16_encode_host(x, buffer=0, first_frame=0, dither_seed=None):
     return np.ascontiguousarray(q.T)
 
 
+def pcm24_pack(q):
+    """(2,L) int32 codes of -8388608 .. 8388607 -> the 6 L bytes of L packed stereo frames (uint8): 3 bytes per sample, little-endian,
+    L then R, as a 24-bit WAV data chunk holds them."""
+    a = np.ascontiguousarray(np.asarray(q, np.int32).T)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("pcm24_pack: need a (2, L) array")
+    if a.size and (a.min() < -8388608 or a.max() > 8388607):
+        raise ValueError("pcm24_pack: codes outside -8388608 .. 8388607")
+    return np.ascontiguousarray(a.astype("<i4").view(np.uint8).reshape(-1, 4)[:, :3]).ravel()
+
+
+def pcm24_unpack(b):
+    """The bytes of L packed stereo frames (uint8, 6 L of them) -> (2,L) int32 codes."""
+    b = np.ascontiguousarray(b, np.uint8).ravel()
+    if b.size % 6:
+        raise ValueError("pcm24_unpack: need a multiple of 6 bytes")
+    w = np.zeros((b.size // 3, 4), np.uint8)
+    w[:, 1:] = b.reshape(-1, 3)
+    return np.ascontiguousarray((w.view("<i4").ravel().astype(np.int32) >> 8).reshape(-1, 2).T)
+
+
+def pcm24_decode_host(q):
+    """umx_hip_pcm24_decode_host: int32 codes (any shape) -> float32 array of the same shape, x = q / 2^23, through the packed bytes
+    (no GPU)."""
+    q = np.ascontiguousarray(q, np.int32)
+    b = np.ascontiguousarray(q.ravel().astype("<i4").view(np.uint8).reshape(-1, 4)[:, :3]).ravel()  # 3 bytes per sample
+    x = np.empty(q.shape, np.float32)
+    rc = hip_lib().umx_hip_pcm24_decode_host(b.ctypes.data_as(_u8p), q.size, x.ctypes.data_as(_fp))
+    if rc != UMX_OK:
+        raise UmxError(rc, "umx_hip_pcm24_decode_host")
+    return x
+
+
+def pcm24_encode_host(x, buffer=0, first_frame=0, dither_seed=None):
+    """umx_hip_pcm24_encode_host: (2,n) float32 -> (2,n) int32 codes as output buffer `buffer` of a call, frame 0 of x being frame
+    first_frame of the track (no GPU)."""
+    a = np.ascontiguousarray(np.asarray(x, np.float32).T)
+    b = np.empty(6 * a.shape[0], np.uint8)
+    io = sample_io(SAMPLE_F32, SAMPLE_S24, dither_seed)
+    rc = hip_lib().umx_hip_pcm24_encode_host(a.ctypes.data_as(_fp), a.shape[0], int(buffer), int(first_frame), C.byref(io),
+                                             b.ctypes.data_as(_u8p))
+    if rc != UMX_OK:
+        raise UmxError(rc, "umx_hip_pcm24_encode_host")
+    return pcm24_unpack(b)
+
+
 def levels_host(x, buffer=0, first_frame=0, io=None, clip_divisor=1.0, acc=None):
     """umx_hip_levels_host: the levels of a (2,n) float32 array as output buffer `buffer` of a call, accumulated into the LevelsAcc
-    `acc` (None: a fresh one), which is returned; clipped is counted for an io with a SAMPLE_S16 output, on x / clip_divisor (no GPU)."""
+    `acc` (None: a fresh one), which is returned; clipped is counted for an io with a SAMPLE_S16 or SAMPLE_S24 output, on x / clip_divisor (no GPU)."""
     a = np.ascontiguousarray(np.asarray(x, np.float32).T)
     acc = LevelsAcc() if acc is None else acc
     rc = hip_lib().umx_hip_levels_host(a.ctypes.data_as(_fp), a.shape[0], int(buffer), int(first_frame), None if io is None else C.byref(io),
@@ -504,19 +561,28 @@ def _mix_gains(gains):
 
 class _TrackArgs:
     """The marshalling of every whole-track call: a list of (2, L_i) arrays as the C entry points take it.  io: the
-    SampleIO of the call or None (int16 arrays where it says SAMPLE_S16, else float32); n_out: host buffers per track; ptr: the pointer
+    SampleIO of the call or None (int16 arrays where it says SAMPLE_S16, (2,L) int32 codes where it says SAMPLE_S24 -- packed to 6
+    bytes a frame here and unpacked again --, else float32); n_out: host buffers per track; ptr: the pointer
     type of the C signature's arrays.  ins / outs: the contiguous (L_i, 2) inputs and the output buffers; a, o, n, sh, rt: the ctypes
     arrays of audio, outputs, lengths, shift offsets (None = -1: no shift) and rates (None: all 44.1 kHz); result(): the outputs as a
     list of [n_out x (2, L_i)]."""
 
     def __init__(self, waves, io=None, n_out=4, shift_offsets=None, rates=None, ptr=C.c_void_p):
         nt = len(waves)
-        tin = np.int16 if io is not None and io.in_format == SAMPLE_S16 else np.float32
-        tout = np.int16 if io is not None and io.out_format == SAMPLE_S16 else np.float32
-        self.ins = [np.ascontiguousarray(np.asarray(w, tin).T).ravel() for w in waves]
+        fin = SAMPLE_F32 if io is None else io.in_format
+        self.fout = SAMPLE_F32 if io is None else io.out_format
+        tin = np.int16 if fin == SAMPLE_S16 else np.float32
+        tout = np.int16 if self.fout == SAMPLE_S16 else np.float32
+        if fin == SAMPLE_S24:
+            self.ins = [pcm24_pack(w) for w in waves]
+        else:
+            self.ins = [np.ascontiguousarray(np.asarray(w, tin).T).ravel() for w in waves]
         self.Ls = [np.asarray(w).shape[1] for w in waves]
         self.n_host = min(max(n_out, 0), MAX_MIX_OUTPUTS)
-        self.outs = [[np.empty(2 * L, tout) for _ in range(self.n_host)] for L in self.Ls]
+        if self.fout == SAMPLE_S24:
+            self.outs = [[np.empty(6 * L, np.uint8) for _ in range(self.n_host)] for L in self.Ls]
+        else:
+            self.outs = [[np.empty(2 * L, tout) for _ in range(self.n_host)] for L in self.Ls]
         self.a = (ptr * nt)(*[C.cast(x.ctypes.data, ptr) for x in self.ins])
         self.o = (ptr * max(1, nt * self.n_host))(*[C.cast(x.ctypes.data, ptr) for t in self.outs for x in t])
         self.n = (C.c_int * nt)(*self.Ls)
@@ -525,6 +591,8 @@ class _TrackArgs:
         self.rt = None if rates is None else (C.c_int * nt)(*[int(r) for r in rates])
 
     def result(self):
+        if self.fout == SAMPLE_S24:
+            return [[pcm24_unpack(x) for x in t] for t in self.outs]
         return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(self.outs, self.Ls)]
 
 
@@ -905,6 +973,29 @@ class Engine:
                                                                   C.byref(io), (C.c_void_p * max(1, nb))(*out_ptrs), C.c_void_p(acc_ptr),
                                                                   hip_stream))
 
+    def pcm24_encode_rescaled_device(self, in_ptrs, n, out_ptrs, acc_ptr, first_frame=0, dither_seed=None, hip_stream=None):
+        """umx_hip_pcm24_encode_rescaled_device: pcm24_encode_device() on x / g, g formed on the device from the record at acc_ptr."""
+        nb = len(in_ptrs)
+        assert len(out_ptrs) == nb
+        io = sample_io(SAMPLE_F32, SAMPLE_S24, dither_seed)
+        self._check(self.lib.umx_hip_pcm24_encode_rescaled_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(first_frame),
+                                                                  C.byref(io), (C.c_void_p * max(1, nb))(*out_ptrs), C.c_void_p(acc_ptr),
+                                                                  hip_stream))
+
+    def pcm24_decode_device(self, in_ptr, n, out_ptr, hip_stream=None):
+        """umx_hip_pcm24_decode_device: n packed 24-bit stereo frames (6 n bytes, 2-byte aligned) at device address in_ptr -> (2,n)
+        interleaved fp32 at out_ptr."""
+        self._check(self.lib.umx_hip_pcm24_decode_device(self.h, C.c_void_p(in_ptr), int(n), C.c_void_p(out_ptr), hip_stream))
+
+    def pcm24_encode_device(self, in_ptrs, n, out_ptrs, first_frame=0, dither_seed=None, hip_stream=None):
+        """umx_hip_pcm24_encode_device: 1 .. 4 device buffers (2,n) interleaved fp32 -> n packed 24-bit stereo frames each (6 n bytes,
+        2-byte aligned), buffer b as output b."""
+        nb = len(in_ptrs)
+        assert len(out_ptrs) == nb
+        io = sample_io(SAMPLE_F32, SAMPLE_S24, dither_seed)
+        self._check(self.lib.umx_hip_pcm24_encode_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(first_frame), C.byref(io),
+                                                         (C.c_void_p * max(1, nb))(*out_ptrs), hip_stream))
+
     def rescale_device(self, ptrs, n, acc_ptr, hip_stream=None):
         """umx_hip_rescale_device: 1 .. 4 device buffers (2,n) interleaved fp32 divided in place by the divisor of the record at acc_ptr."""
         nb = len(ptrs)
@@ -1177,7 +1268,8 @@ class Engine:
 HOST_SYMBOLS = ["umx_model_load", "umx_model_free", "umx_model_hidden", "umx_model_n_tensors", "umx_model_views",
                 "umx_model_data_bytes", "umx_model_load_progress", "umx_model_dequantize", "umx_wav_load",
                 "umx_wav_free", "umx_wav_write_f32", "umx_wav_load_rate", "umx_wav_write_f32_rate",
-                "umx_wav_load_pcm16", "umx_wav_free_pcm16", "umx_wav_write_pcm16_rate", "umx_split_inference", "umx_shift_inference",
+                "umx_wav_load_pcm16", "umx_wav_free_pcm16", "umx_wav_write_pcm16_rate",
+                "umx_wav_load_pcm24", "umx_wav_free_pcm24", "umx_wav_write_pcm24_rate", "umx_split_inference", "umx_shift_inference",
                 "umx_segment_plan", "umx_transition_weight", "umx_split_inference_carry", "umx_split_inference_targets", "umx_mix_parse"]
 
 SEGMENT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _fp, C.c_int, C.POINTER(_fp))
@@ -1252,6 +1344,9 @@ def host_lib():
     lib.umx_wav_load_pcm16.argtypes = [C.c_char_p, C.POINTER(_i16p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p]
     lib.umx_wav_free_pcm16.argtypes = [_i16p]
     lib.umx_wav_write_pcm16_rate.argtypes = [C.c_char_p, _i16p, C.c_int, C.c_int, C.c_char_p]
+    lib.umx_wav_load_pcm24.argtypes = [C.c_char_p, C.POINTER(_u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p]
+    lib.umx_wav_free_pcm24.argtypes = [_u8p]
+    lib.umx_wav_write_pcm24_rate.argtypes = [C.c_char_p, _u8p, C.c_int, C.c_int, C.c_char_p]
     lib.umx_split_inference.argtypes = [C.POINTER(Backend), _fp, C.c_int, C.c_int, C.POINTER(_fp), PROGRESS_FN,
                                         C.c_void_p, C.c_char_p]
     lib.umx_shift_inference.argtypes = [C.POINTER(Backend), _fp, C.c_int, C.c_int, C.c_int, C.POINTER(_fp),
@@ -1384,6 +1479,31 @@ def wav_write_pcm16(path, wave, rate=MODEL_RATE):
     a = np.ascontiguousarray(np.asarray(wave, np.int16).T)
     err = C.create_string_buffer(256)
     rc = host_lib().umx_wav_write_pcm16_rate(str(path).encode(), a.ctypes.data_as(_i16p), a.shape[0], int(rate), err)
+    if rc:
+        raise HostError(rc, err.value.decode())
+
+
+def wav_load_pcm24(path, probe=False):
+    """umx_wav_load_pcm24: a 24-bit PCM file as it is -> ((2,n) int32 codes, channels in file, sample rate); HostError for any other
+    encoding.  probe=True reads the file's head only -> (frames, channels in file, sample rate)."""
+    lib = host_lib()
+    p, n, ch, rate = _u8p(), C.c_int(), C.c_int(), C.c_int()
+    err = C.create_string_buffer(256)
+    rc = lib.umx_wav_load_pcm24(str(path).encode(), None if probe else C.byref(p), C.byref(n), C.byref(ch), C.byref(rate), err)
+    if rc:
+        raise HostError(rc, err.value.decode())
+    if probe:
+        return n.value, ch.value, rate.value
+    b = np.ctypeslib.as_array(p, shape=(max(n.value, 1) * 6,))[:6 * n.value].copy()
+    lib.umx_wav_free_pcm24(p)
+    return pcm24_unpack(b), ch.value, rate.value
+
+
+def wav_write_pcm24(path, wave, rate=MODEL_RATE):
+    """umx_wav_write_pcm24_rate: (2,n) int32 codes -> stereo 24-bit PCM WAV at `rate` Hz."""
+    b = pcm24_pack(wave)
+    err = C.create_string_buffer(256)
+    rc = host_lib().umx_wav_write_pcm24_rate(str(path).encode(), b.ctypes.data_as(_u8p), b.size // 6, int(rate), err)
     if rc:
         raise HostError(rc, err.value.decode())
 

@@ -42,6 +42,7 @@
 #include "shift_mean.h"
 #include "stem_mix.h"
 #include "pcm16.h"
+#include "pcm24.h"
 #include "levels.h"
 #include "loudness.h"
 #include "gate_debug.h"
@@ -627,8 +628,8 @@ struct umx_hip_ctx
         float *in = nullptr, *out[4] = {}, *sumw = nullptr, *seg[kMaxSlots][4] = {};
         size_t cap = 0;
         RsStage rs; // the native-rate staging of a resampled job, frames at the caller's frame numbers
-        // DESIGN 19, only once a job asks for UMX_SAMPLE_S16: the track as uploaded and its outputs as they leave, one word per frame of
-        // the CALLER's track (no shift padding), each grow-only on its own
+        // DESIGN 19, 24, only once a job asks for UMX_SAMPLE_S16 or UMX_SAMPLE_S24: the track as uploaded and its outputs as they leave, 4
+        // or 6 bytes per frame of the CALLER's track (no shift padding; capacities in words), each grow-only on its own
         uint32_t *in16 = nullptr, *out16[4] = {};
         size_t cap_in16 = 0, cap_out16[4] = {};
         hipEvent_t in_ev = nullptr; // behind the most recent kernel that wrote `in` -- a decode out of in16, a resampled range out of rs.in

@@ -617,6 +617,102 @@ int umx_hip_pcm16_encode_host(const float *x, int n_frames, int buffer, long lon
             q[2 * (size_t)i + ch] = pcm16_encode(x[2 * (size_t)i + ch], d.on, key[ch], first_frame + i);
     return UMX_OK;
 }
+// ---------------------------------------------------------------- packed 24-bit PCM in and out (pcm24.h)
+// a packed device buffer: 2-byte aligned (its frames are 6 bytes, so an even base is all it takes)
+static bool pcm24_aligned(umx_hip_ctx *ctx, const char *what, int n_buffers, const void *const *bufs)
+{
+    for (int b = 0; b < n_buffers; ++b)
+        if ((uintptr_t)bufs[b] & 1)
+        {
+            ctx->set_error(std::string(what) + ": a packed 24-bit buffer must be 2-byte aligned");
+            return false;
+        }
+    return true;
+}
+
+int umx_hip_pcm24_decode_device(umx_hip_ctx *ctx, const void *in_dev, int n, float *out_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!in_dev || !out_dev || n < 1)
+    {
+        ctx->set_error("pcm24 decode: need both buffers and n >= 1");
+        return UMX_ERR_ARG;
+    }
+    if (!pcm24_aligned(ctx, "pcm24 decode", 1, &in_dev))
+        return UMX_ERR_ARG;
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    launch_pcm24_decode(static_cast<const uint8_t *>(in_dev), reinterpret_cast<float2 *>(out_dev), n, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+
+int umx_hip_pcm24_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
+                                const umx_sample_io *io, void *const *out_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    const float2 *src[4] = {};
+    uint8_t *dst[4] = {};
+    if (!device_buffers(ctx, "pcm24 encode", n_buffers, in_dev, n, first_frame, src) ||
+        !device_buffers(ctx, "pcm24 encode", n_buffers, out_dev, n, first_frame, dst) || !pcm24_aligned(ctx, "pcm24 encode", n_buffers, out_dev))
+        return UMX_ERR_ARG;
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    const DitherArg d = dither_of(io);
+    launch_pcm24_encode(n_buffers, src, dst, n, first_frame, d.on, d.seed, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+
+int umx_hip_pcm24_encode_rescaled_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
+                                         const umx_sample_io *io, void *const *out_dev, umx_levels_acc *acc_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    const float2 *src[4] = {};
+    uint8_t *dst[4] = {};
+    if (!device_buffers(ctx, "rescaled pcm24 encode", n_buffers, in_dev, n, first_frame, src) ||
+        !device_buffers(ctx, "rescaled pcm24 encode", n_buffers, out_dev, n, first_frame, dst) ||
+        !pcm24_aligned(ctx, "rescaled pcm24 encode", n_buffers, out_dev))
+        return UMX_ERR_ARG;
+    if (!acc_dev)
+    {
+        ctx->set_error("rescaled pcm24 encode: null record");
+        return UMX_ERR_ARG;
+    }
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    const DitherArg d = dither_of(io);
+    launch_pcm24_encode_rescaled(n_buffers, src, dst, n, first_frame, d.on, d.seed, acc_dev, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+
+// n_values samples of 3 bytes each
+int umx_hip_pcm24_decode_host(const void *q, long long n_values, float *x)
+{
+    if (!q || !x || n_values < 0)
+        return UMX_ERR_ARG;
+    const uint8_t *p = static_cast<const uint8_t *>(q);
+    for (long long i = 0; i < n_values; ++i)
+        x[i] = pcm24_decode(pcm24_load(p + 3 * (size_t)i));
+    return UMX_OK;
+}
+
+int umx_hip_pcm24_encode_host(const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, void *q)
+{
+    if (!x || !q || n_frames < 0 || buffer < 0 || buffer >= UMX_MAX_MIX_OUTPUTS || first_frame < 0)
+        return UMX_ERR_ARG;
+    const DitherArg d = dither_of(io);
+    const uint32_t key[2] = {pcm16_dither_key(d.seed, buffer, 0), pcm16_dither_key(d.seed, buffer, 1)};
+    uint8_t *p = static_cast<uint8_t *>(q);
+    for (int i = 0; i < n_frames; ++i)
+        for (int ch = 0; ch < 2; ++ch)
+            pcm24_store(p + 3 * (2 * (size_t)i + ch), pcm24_encode(x[2 * (size_t)i + ch], d.on, key[ch], first_frame + i));
+    return UMX_OK;
+}
+
+// the output format whose plain encode clamps what levels count as clipped (io == NULL or an fp32 output: none)
+static int clip_format_of(const umx_sample_io *io) { return io ? io->out_format : UMX_SAMPLE_F32; }
 // ---------------------------------------------------------------- output levels and clip handling (levels.h)
 // clip_mode == UMX_CLIP_CLAMP and levels == NULL: the request of umx_hip_separate_tracks_io, field for field
 int umx_hip_separate_tracks_levels(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
@@ -649,7 +745,7 @@ int umx_hip_levels_device(umx_hip_ctx *ctx, int n_buffers, const float *const *i
     }
     UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
     const DitherArg d = dither_of(io);
-    launch_stem_levels(n_buffers, src, n, first_frame, io && io->out_format == UMX_SAMPLE_S16, d.on, d.seed, acc_dev, (hipStream_t)hip_stream);
+    launch_stem_levels(n_buffers, src, n, first_frame, clip_format_of(io), d.on, d.seed, acc_dev, (hipStream_t)hip_stream);
     UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
     return UMX_OK;
 }
@@ -700,7 +796,7 @@ int umx_hip_levels_host(const float *x, int n_frames, int buffer, long long firs
     if (!x || !acc || n_frames < 0 || buffer < 0 || buffer >= UMX_MAX_MIX_OUTPUTS || first_frame < 0)
         return UMX_ERR_ARG;
     const DitherArg d = dither_of(io);
-    levels_host(x, n_frames, buffer, first_frame, io && io->out_format == UMX_SAMPLE_S16, d.on, d.seed, clip_divisor, *acc);
+    levels_host(x, n_frames, buffer, first_frame, clip_format_of(io), d.on, d.seed, clip_divisor, *acc);
     return UMX_OK;
 }
 

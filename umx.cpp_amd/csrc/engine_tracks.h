@@ -78,25 +78,37 @@ int umx_hip_ctx::track_bufs_grow(TrackBufs &tb_, size_t frames)
     return grow_only<float>({{&tb_.in, 2}, {&tb_.out[0], 2}, {&tb_.out[1], 2}, {&tb_.out[2], 2}, {&tb_.out[3], 2}, {&tb_.sumw, 1}}, tb_.cap, frames);
 }
 
-// the int16 side of an accumulator set for a job of `frames` frames at the caller's rate (a word each): the staging of its
-// upload, n_host outputs, each grow-only on its own
+// the integer side of an accumulator set for a job of `frames` frames at the caller's rate -- 4 B (int16) or 6 B
+// (packed 24-bit) a frame, counted in words: the staging of its upload, n_host outputs, each grow-only on its own
+static size_t int_side_words(int format, size_t frames) { return format == UMX_SAMPLE_S24 ? (3 * frames + 1) / 2 : frames; }
 int umx_hip_ctx::track_pcm16_grow(TrackBufs &tb_, const umx_sample_io &io, size_t frames, int n_host)
 {
-    if (io.in_format == UMX_SAMPLE_S16)
-        if (int rc = grow_only<uint32_t>({{&tb_.in16, 1}}, tb_.cap_in16, frames))
+    if (io.in_format != UMX_SAMPLE_F32)
+        if (int rc = grow_only<uint32_t>({{&tb_.in16, 1}}, tb_.cap_in16, int_side_words(io.in_format, frames)))
             return rc;
-    for (int t = 0; t < n_host && io.out_format == UMX_SAMPLE_S16; ++t)
-        if (int rc = grow_only<uint32_t>({{&tb_.out16[t], 1}}, tb_.cap_out16[t], frames))
+    for (int t = 0; t < n_host && io.out_format != UMX_SAMPLE_F32; ++t)
+        if (int rc = grow_only<uint32_t>({{&tb_.out16[t], 1}}, tb_.cap_out16[t], int_side_words(io.out_format, frames)))
             return rc;
     return UMX_OK;
 }
 
-// `count` frames of the first n_host of `src` from frame src_start on -> the set's int16 outputs from frame first_frame on, which is
-// their frame number in the caller's track (the k of the dither)
+// `count` frames of the first n_host of `src` from frame src_start on -> the set's integer outputs from frame first_frame on, which is
+// their frame number in the caller's track (the k of the dither); the kernel is the output format's (packed 24-bit: at byte 6 x frame)
 void umx_hip_ctx::track_encode(const TrackBufs &tb_, const umx_sample_io &io, int n_host, float *const src[4], size_t src_start, int count,
                                long long first_frame, hipStream_t st)
 {
     const float2 *s[4] = {};
+    if (io.out_format == UMX_SAMPLE_S24)
+    {
+        uint8_t *d24[4] = {};
+        for (int t = 0; t < n_host; ++t)
+        {
+            s[t] = reinterpret_cast<const float2 *>(src[t]) + src_start;
+            d24[t] = reinterpret_cast<uint8_t *>(tb_.out16[t]) + 6 * (size_t)first_frame;
+        }
+        launch_pcm24_encode(n_host, s, d24, count, first_frame, io.dither != 0, io.dither_seed, st);
+        return;
+    }
     uint32_t *d[4] = {};
     for (int t = 0; t < n_host; ++t)
     {
@@ -124,7 +136,7 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
     const TrackBufs &tb_ = *j.acc;
     const umx_sample_io &io = j.opt.io;
     const int n_host = j.opt.n_host();
-    const bool s16 = io.out_format == UMX_SAMPLE_S16, rescale = j.opt.rescale();
+    const bool s16 = io.out_format == UMX_SAMPLE_S16, s24 = io.out_format == UMX_SAMPLE_S24, rescale = j.opt.rescale();
     if (j.opt.loudness)
     {
         const int hop = kweight_hop(j.loud_rate);
@@ -140,27 +152,31 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
     }
     if (!j.opt.measures())
     {
-        if (s16)
+        if (s16 || s24)
             track_encode(tb_, io, n_host, src, src_start, count, first_frame, st);
         return;
     }
     const float2 *s[4] = {};
     float2 *sw[4] = {};
     uint32_t *d[4] = {};
+    uint8_t *d24[4] = {};
     for (int t = 0; t < n_host; ++t)
     {
         s[t] = sw[t] = reinterpret_cast<float2 *>(src[t]) + src_start;
         d[t] = s16 ? tb_.out16[t] + first_frame : nullptr;
+        d24[t] = s24 ? reinterpret_cast<uint8_t *>(tb_.out16[t]) + 6 * (size_t)first_frame : nullptr;
     }
-    // (a rescaled int16 track: its encode counts what it clamps itself, with the divisor it forms)
-    launch_stem_levels(n_host, s, count, first_frame, s16 && !rescale, io.dither != 0, io.dither_seed, tb_.lev, st);
+    // (a rescaled integer track: its encode counts what it clamps itself, with the divisor it forms)
+    launch_stem_levels(n_host, s, count, first_frame, rescale ? UMX_SAMPLE_F32 : io.out_format, io.dither != 0, io.dither_seed, tb_.lev, st);
     if (!rescale)
     {
-        if (s16)
+        if (s16 || s24)
             track_encode(tb_, io, n_host, src, src_start, count, first_frame, st);
     }
     else if (s16)
         launch_pcm16_encode_rescaled(n_host, s, d, count, first_frame, io.dither != 0, io.dither_seed, tb_.lev, st);
+    else if (s24)
+        launch_pcm24_encode_rescaled(n_host, s, d24, count, first_frame, io.dither != 0, io.dither_seed, tb_.lev, st);
     else
         launch_stem_rescale(n_host, sw, count, tb_.lev, st);
 }
@@ -269,9 +285,9 @@ hipError_t umx_hip_ctx::track_loudness_report(const TrackJob &j, int n_host, std
 // from its previous job: that work has long finished.)
 hipError_t umx_hip_ctx::track_upload_until(TrackJob &j, long long padded_end, hipStream_t st)
 {
-    const bool s16 = j.opt.io.in_format == UMX_SAMPLE_S16;
+    const bool s16 = j.opt.io.in_format == UMX_SAMPLE_S16, s24 = j.opt.io.in_format == UMX_SAMPLE_S24;
     TrackBufs &tb_ = *j.acc;
-    if ((s16 || j.rs.rate) && tb_.in_ev)
+    if ((s16 || s24 || j.rs.rate) && tb_.in_ev)
         if (hipError_t e = hipStreamWaitEvent(st, tb_.in_ev, 0))
             return e;
     // what is wanted of the track as the segments see it, and what that needs of the host's frames
@@ -289,14 +305,20 @@ hipError_t umx_hip_ctx::track_upload_until(TrackJob &j, long long padded_end, hi
     {
         const size_t from = (size_t)j.uploaded, count = (size_t)(host_want - j.uploaded);
         float *const dst = j.rs.rate ? tb_.rs.in + 2 * from : tb_.in + 2 * ((size_t)j.lead + from); // where host frame `from` goes as fp32
-        if (s16)
+        if (s16 || s24)
         {
-            e = hipMemcpy(tb_.in16 + from, reinterpret_cast<const uint32_t *>(j.audio) + from, sizeof(uint32_t) * count, hipMemcpyHostToDevice);
+            // (the staging holds the host's bytes at their own offsets: 4 or 6 x frame)
+            const size_t fb = sample_frame_bytes(j.opt.io.in_format);
+            uint8_t *const stage = reinterpret_cast<uint8_t *>(tb_.in16) + fb * from;
+            e = hipMemcpy(stage, reinterpret_cast<const uint8_t *>(j.audio) + fb * from, fb * count, hipMemcpyHostToDevice);
             if (e == hipSuccess && !tb_.in_ev)
                 e = hipEventCreateWithFlags(&tb_.in_ev, hipEventDisableTiming);
             if (e == hipSuccess)
             {
-                launch_pcm16_decode(tb_.in16 + from, reinterpret_cast<float2 *>(dst), (int)count, st);
+                if (s24)
+                    launch_pcm24_decode(stage, reinterpret_cast<float2 *>(dst), (int)count, st);
+                else
+                    launch_pcm16_decode(tb_.in16 + from, reinterpret_cast<float2 *>(dst), (int)count, st);
                 e = hipEventRecord(tb_.in_ev, st);
             }
         }
@@ -349,8 +371,12 @@ hipError_t umx_hip_ctx::track_region_download(const TrackRegion &r, float *const
     hipError_t cerr = hipEventSynchronize(r.ready);
     const size_t count = (size_t)n;
     for (int t = 0; t < n_host && cerr == hipSuccess; ++t)
-        if (j.opt.io.out_format == UMX_SAMPLE_S16) // (encoded behind the region's normalisation and mix, at its frame number: track_call)
-            cerr = hipMemcpy(reinterpret_cast<uint32_t *>(out_host[t]) + first, j.acc->out16[t] + first, sizeof(uint32_t) * count, hipMemcpyDeviceToHost);
+        if (j.opt.io.out_format != UMX_SAMPLE_F32) // (encoded behind the region's normalisation and mix, at its frame number: track_call)
+        {
+            const size_t fb = sample_frame_bytes(j.opt.io.out_format); // 4 or 6 x frame on both sides
+            cerr = hipMemcpy(reinterpret_cast<uint8_t *>(out_host[t]) + fb * first, reinterpret_cast<const uint8_t *>(j.acc->out16[t]) + fb * first,
+                             fb * count, hipMemcpyDeviceToHost);
+        }
         else if (j.rs.rate)
             cerr = hipMemcpy(out_host[t] + 2 * first, j.acc->rs.out[t] + 2 * first, sizeof(float) * 2 * count, hipMemcpyDeviceToHost);
         else
@@ -455,7 +481,7 @@ int umx_hip_ctx::track_call(const TrackLane *lanes, int nl, unsigned flags, int 
                 j->out_done = r;
             }
         }
-        else if (opt.io.out_format == UMX_SAMPLE_S16 || opt.measures() || opt.loudness) // the region's frames of the caller's track, as they will
+        else if (opt.io.out_format != UMX_SAMPLE_F32 || opt.measures() || opt.loudness) // the region's frames of the caller's track, as they will
         {                                                    // leave (an int16 copy is not written over the accumulators: the next
                                                              // segment's overlap-add still reads its neighbours)
             const long long lo = std::max<long long>(rg.start, j->lead), hi = std::min<long long>((long long)rg.start + rg.count, (long long)j->lead + j->length);
@@ -676,7 +702,7 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         if (cerr == hipSuccess) // at the caller's rate and length, frame 0 first: measured, encoded, rescaled as the job says
         {
             track_leave(j, whole[ln], 0, length_in[ln], 0, last_st);
-            for (int t = 0; t < n_host && opt.io.out_format == UMX_SAMPLE_S16; ++t)
+            for (int t = 0; t < n_host && opt.io.out_format != UMX_SAMPLE_F32; ++t)
                 whole[ln][t] = reinterpret_cast<float *>(j.acc->out16[t]);
         }
         any_whole = true;
@@ -710,7 +736,7 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         cerr = hipStreamSynchronize(last_st);
     for (int ln = 0; ln < nt; ++ln)
         for (int t = 0; t < n_host && whole[ln][0] && cerr == hipSuccess; ++t) // (an ensemble's one result: lane 0)
-            cerr = hipMemcpy(rq.out[n_host * ln + t], whole[ln][t], (opt.io.out_format == UMX_SAMPLE_S16 ? sizeof(uint32_t) : sizeof(float) * 2) * (size_t)length_in[ln],
+            cerr = hipMemcpy(rq.out[n_host * ln + t], whole[ln][t], sample_frame_bytes(opt.io.out_format) * (size_t)length_in[ln],
                              hipMemcpyDeviceToHost);
     // every job's record, once: its last measuring launch is behind its last region, which the host has
     umx_levels reports[LSTMB_MAX_TRACKS];

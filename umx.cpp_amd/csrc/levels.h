@@ -3,8 +3,9 @@
 // host entry points (umx_hip_levels_host, umx_hip_rescale_gain) and for the kernels below:
 //   peak        the unsigned maximum of the bit patterns of |x| over the samples that are not NaN (+inf counts), 0 when there is none
 //   over_unity  samples with |x| > 1.0f; nonfinite: NaN or +-inf
-//   clipped     int16 outputs only: samples whose rounded value r of the encode rule (pcm16_round, with its dither, on x / g when a
-//               divisor applies) is > 32767.f or < -32768.f; +-inf counts, NaN does not
+//   clipped     integer outputs only: samples whose rounded value r of the output format's encode rule (pcm16_round / pcm24_round,
+//               with its dither, on x / g when a divisor applies) lies outside the format's codes: > 32767.f or < -32768.f for
+//               int16, > 8388607 or < -8388608 for packed 24-bit; +-inf counts, NaN does not
 //   rescale     P = max peak over the outputs that leave, g = 1.01f * P (one fp32 product); P not finite or !(g > 1.0f): divisor 1,
 //               nothing is divided; else every sample is x / g, correctly rounded, and the unchanged encode follows
 // All of it is maxima and integer counts: regions, lanes, the queue and a rerun give the same record.  The record (umx_levels_acc) is
@@ -12,6 +13,7 @@
 #pragma once
 #include "common.h"
 #include "pcm16.h"
+#include "pcm24.h"
 
 namespace umx
 {
@@ -48,6 +50,15 @@ __host__ __device__ inline bool levels_is_over_unity(uint32_t abs_bits) { return
 __host__ __device__ inline uint32_t levels_peak_term(uint32_t abs_bits) { return levels_is_nan(abs_bits) ? 0u : abs_bits; }
 // did the clamp of the encode rule change the rounded value r (a NaN r: no)
 __host__ __device__ inline bool levels_is_clipped(float r) { return r > 32767.f || r < -32768.f; }
+// the same question of sample x as it leaves in clip_format (UMX_SAMPLE_S16 or UMX_SAMPLE_S24; an fp32 output: never)
+__host__ __device__ inline bool levels_clips(float x, int clip_format, bool dither, uint32_t key, long long k)
+{
+    if (clip_format == UMX_SAMPLE_S16)
+        return levels_is_clipped(pcm16_round(x, dither, key, k));
+    if (clip_format == UMX_SAMPLE_S24)
+        return pcm24_is_clipped(pcm24_round(x, dither, key, k));
+    return false;
+}
 
 // the divisor of a track whose largest peak has the bit pattern peak_bits (the maximum of the record's peak words); 1: none
 __host__ __device__ inline float levels_divisor(uint32_t peak_bits)
@@ -81,7 +92,7 @@ struct LevelsArgs
     uint32_t key[4][2]; // pcm16_dither_key of (seed, b, channel)
     long long first_frame;
     int dither;
-    int count_clipped; // the outputs leave through the plain int16 encode: count what it clamps
+    int clip_format; // UMX_SAMPLE_S16 / UMX_SAMPLE_S24: the outputs leave through that format's plain encode, count what it clamps; else nothing
 };
 
 #define LEVELS_THREADS 256
@@ -138,8 +149,10 @@ __global__ __launch_bounds__(LEVELS_THREADS) void stem_levels_kernel(LevelsArgs 
                     const uint32_t p = levels_peak_term(u);
                     v[b] = p > v[b] ? p : v[b];
                     v[4 + b] += levels_is_over_unity(u) ? 1u : 0u;
-                    if (a.count_clipped)
+                    if (a.clip_format == UMX_SAMPLE_S16)
                         v[8 + b] += levels_is_clipped(pcm16_round(xs[ch], a.dither != 0, a.key[b][ch], k)) ? 1u : 0u;
+                    else if (a.clip_format == UMX_SAMPLE_S24)
+                        v[8 + b] += pcm24_is_clipped(pcm24_round(xs[ch], a.dither != 0, a.key[b][ch], k)) ? 1u : 0u;
                     v[12 + b] += levels_is_nonfinite(u) ? 1u : 0u;
                 }
             }
@@ -185,6 +198,24 @@ __global__ __launch_bounds__(LEVELS_THREADS) void pcm16_encode_rescaled_kernel(P
         atomicAdd(&acc->clipped[threadIdx.x], (unsigned long long)total);
 }
 
+// pcm24_encode_kernel (pcm24.h) on x / g, the twin of the kernel above: the same divisor, the same count of what it clamps
+struct Pcm24Rescaled
+{
+    float g;
+    bool divide;
+    __device__ float operator()(float x) const { return divide ? levels_rescaled(x, g) : x; }
+};
+__global__ __launch_bounds__(LEVELS_THREADS) void pcm24_encode_rescaled_kernel(Pcm24EncodeArgs a, int n, umx_levels_acc *acc)
+{
+    __shared__ uint32_t red[LEVELS_WAVES * 4];
+    const float g = levels_divisor(*acc);
+    uint32_t v[4] = {};
+    pcm24_encode_frames<true>(a, n, Pcm24Rescaled{g, g != 1.0f}, v);
+    const uint32_t total = levels_block_reduce<4, 0>(v, red);
+    if (threadIdx.x < 4 && total != 0)
+        atomicAdd(&acc->clipped[threadIdx.x], (unsigned long long)total);
+}
+
 struct RescaleBufs
 {
     float2 *p[4]; // nullptr: none
@@ -211,7 +242,7 @@ __global__ __launch_bounds__(LEVELS_THREADS) void stem_rescale_kernel(RescaleBuf
 inline int levels_blocks(int n) { return std::max(1, std::min((n + LEVELS_THREADS - 1) / LEVELS_THREADS, 1024)); }
 
 // buffers 0 .. nb-1 of a call's `out` list, n frames from frame first_frame of the caller's track on, into the record acc
-inline void launch_stem_levels(int nb, const float2 *const *src, int n, long long first_frame, bool count_clipped, bool dither, uint32_t seed,
+inline void launch_stem_levels(int nb, const float2 *const *src, int n, long long first_frame, int clip_format, bool dither, uint32_t seed,
                                umx_levels_acc *acc, hipStream_t st)
 {
     if (n < 1 || nb < 1)
@@ -225,7 +256,7 @@ inline void launch_stem_levels(int nb, const float2 *const *src, int n, long lon
     }
     a.first_frame = first_frame;
     a.dither = dither ? 1 : 0;
-    a.count_clipped = count_clipped ? 1 : 0;
+    a.clip_format = clip_format;
     hipLaunchKernelGGL(stem_levels_kernel, dim3(levels_blocks(n)), dim3(LEVELS_THREADS), 0, st, a, n, acc);
 }
 
@@ -247,6 +278,15 @@ inline void launch_pcm16_encode_rescaled(int nb, const float2 *const *src, uint3
     hipLaunchKernelGGL(pcm16_encode_rescaled_kernel, dim3(pcm16_blocks(n)), dim3(LEVELS_THREADS), 0, st, a, n, acc);
 }
 
+inline void launch_pcm24_encode_rescaled(int nb, const float2 *const *src, uint8_t *const *dst, int n, long long first_frame, bool dither,
+                                         uint32_t seed, umx_levels_acc *acc, hipStream_t st)
+{
+    if (n < 1 || nb < 1)
+        return;
+    hipLaunchKernelGGL(pcm24_encode_rescaled_kernel, dim3(pcm24_blocks(n)), dim3(LEVELS_THREADS), 0, st,
+                       pcm24_encode_args(nb, src, dst, first_frame, dither, seed), n, acc);
+}
+
 inline void launch_stem_rescale(int nb, float2 *const *bufs, int n, const umx_levels_acc *acc, hipStream_t st)
 {
     if (n < 1 || nb < 1)
@@ -258,7 +298,7 @@ inline void launch_stem_rescale(int nb, float2 *const *bufs, int n, const umx_le
 }
 
 // the rules over n_frames interleaved stereo frames of output buffer `buffer`, into a host record (umx_hip_levels_host)
-inline void levels_host(const float *x, int n_frames, int buffer, long long first_frame, bool count_clipped, bool dither, uint32_t seed,
+inline void levels_host(const float *x, int n_frames, int buffer, long long first_frame, int clip_format, bool dither, uint32_t seed,
                         float divisor, umx_levels_acc &acc)
 {
     const uint32_t key[2] = {pcm16_dither_key(seed, buffer, 0), pcm16_dither_key(seed, buffer, 1)};
@@ -270,8 +310,7 @@ inline void levels_host(const float *x, int n_frames, int buffer, long long firs
             acc.peak_bits[buffer] = p > acc.peak_bits[buffer] ? p : acc.peak_bits[buffer];
             acc.over_unity[buffer] += levels_is_over_unity(u) ? 1 : 0;
             acc.nonfinite[buffer] += levels_is_nonfinite(u) ? 1 : 0;
-            if (count_clipped)
-                acc.clipped[buffer] += levels_is_clipped(pcm16_round(divisor != 1.0f ? levels_rescaled(s, divisor) : s, dither, key[ch], first_frame + i)) ? 1 : 0;
+            acc.clipped[buffer] += levels_clips(divisor != 1.0f ? levels_rescaled(s, divisor) : s, clip_format, dither, key[ch], first_frame + i) ? 1 : 0;
         }
 }
 

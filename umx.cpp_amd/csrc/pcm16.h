@@ -124,16 +124,6 @@ inline void launch_pcm16_encode(int nb, const float2 *const *src, uint32_t *cons
     hipLaunchKernelGGL(pcm16_encode_kernel, dim3(pcm16_blocks(n)), dim3(256), 0, st, a, n);
 }
 
-// what an entry point refuses (nullptr: fine): io == nullptr is the fp32 call
-inline const char *sample_io_refusal(const umx_sample_io *io)
-{
-    if (!io)
-        return nullptr;
-    if ((io->in_format != UMX_SAMPLE_F32 && io->in_format != UMX_SAMPLE_S16) || (io->out_format != UMX_SAMPLE_F32 && io->out_format != UMX_SAMPLE_S16))
-        return "sample io: unknown sample format (UMX_SAMPLE_F32 or UMX_SAMPLE_S16)";
-    if (io->dither && io->out_format != UMX_SAMPLE_S16)
-        return "sample io: dither goes with a UMX_SAMPLE_S16 output only";
-    return nullptr;
-}
+// (what an entry point refuses of a umx_sample_io: sample_io_refusal, pcm24.h, which knows every format)
 
 } // namespace umx

@@ -14,6 +14,8 @@
 // UMX_MIX (as umx-cli, host/mix_env.h: the same matrix for every file, <out dir>/<wav stem>/<name>.wav and no target_*.wav),
 // UMX_PCM16 and UMX_PCM16_DITHER (as umx-cli, DESIGN 19: every output a 16-bit PCM WAV quantised on the device, through the queue and
 // the pass-by-pass loop alike; the files go up as int16 when ALL of them are 16-bit PCM -- a run has one input format -- else as fp32).
+// UMX_PCM24 and UMX_PCM24_DITHER (as umx-cli, DESIGN 24: every output a 24-bit PCM WAV; one input format per run: packed 24-bit when
+// every file's head says 24-bit PCM, else int16 when every file is 16-bit PCM, else fp32; not together with UMX_PCM16).
 // UMX_CLIP and UMX_LEVELS (as umx-cli; host/clip_env.h): rescale instead of clamp, and one `levels <file> ...` line per
 // file written, through the queue (umx_hip_separate_queue_levels) and the pass-by-pass loop (umx_hip_separate_tracks_levels) alike.
 // UMX_LOUDNESS (as umx-cli): one `loudness <file> ...` line per file written, through the queue
@@ -42,6 +44,19 @@ static int env_int(const char *name, int dflt)
     return v && *v ? atoi(v) : dflt;
 }
 
+// int16 units of an integer output frame (4 bytes of int16, 6 bytes of packed 24-bit PCM); 0 for fp32
+static size_t int_units(int format) { return format == UMX_SAMPLE_S24 ? 3 : format == UMX_SAMPLE_S16 ? 2 : 0; }
+// a file of the run's integer input format as it is, behind an int16 pointer (free: umx_wav_free_pcm16)
+static int load_int(int format, const char *path, int16_t **audio, int *n, int *ch, int *rate, char *err)
+{
+    if (format != UMX_SAMPLE_S24)
+        return umx_wav_load_pcm16(path, audio, n, ch, rate, err);
+    unsigned char *p = nullptr;
+    const int rc = umx_wav_load_pcm24(path, &p, n, ch, rate, err);
+    *audio = reinterpret_cast<int16_t *>(p);
+    return rc;
+}
+
 // The track queue's two ends.  A decoded file waits in `decoded` until a lane takes it (next); its stems wait in `unwritten` from the
 // moment they are complete (done) until the writer has written them.  `permits` bounds the decoded files in memory (waiting or in a
 // lane) to lanes + 2 -- as many as the engine can have in flight, so the reader can always decode the file `next` waits for --
@@ -50,9 +65,10 @@ struct FileJob
 {
     int index = 0, n = 0, rate = UMX_SAMPLE_RATE; // (the file's own rate with UMX_RESAMPLE=1)
     float *audio = nullptr;
-    int16_t *audio16 = nullptr; // UMX_PCM16 with 16-bit PCM files: the file's samples as they are
+    int16_t *audio16 = nullptr; // UMX_PCM16 / UMX_PCM24 with integer PCM files: the file's samples as they are (int16 frames, or packed
+                                // 24-bit frames of 6 bytes behind this pointer: load_int below)
     std::vector<std::vector<float>> stems;
-    std::vector<std::vector<int16_t>> stems16; // UMX_PCM16: the outputs as they are written
+    std::vector<std::vector<int16_t>> stems16; // UMX_PCM16 / UMX_PCM24: the outputs as they are written (2 or 3 int16 units a frame)
     umx_levels levels = {};                    // UMX_CLIP / UMX_LEVELS: what the queue measured
     umx_loudness loudness = {};                // UMX_LOUDNESS: likewise
 };
@@ -85,9 +101,9 @@ struct BatchQueue
         fj->stems.resize(q.per_file);
         fj->stems16.resize(q.per_file);
         for (int t = 0; t < q.per_file; ++t)
-            if (q.io.out_format == UMX_SAMPLE_S16) // (read as the formats say: the caller casts)
+            if (q.io.out_format != UMX_SAMPLE_F32) // (read as the formats say: the caller casts)
             {
-                fj->stems16[t].resize((size_t)2 * fj->n);
+                fj->stems16[t].resize(int_units(q.io.out_format) * fj->n);
                 job->out[t] = reinterpret_cast<float *>(fj->stems16[t].data());
             }
             else
@@ -173,27 +189,45 @@ int main(int argc, const char **argv)
         fprintf(stderr, "UMX_PCM16_DITHER: needs UMX_PCM16=1\n");
         return 1;
     }
+    const bool pcm24 = env_int("UMX_PCM24", 0) != 0;
+    if (pcm24 && pcm16)
+    {
+        fprintf(stderr, "UMX_PCM24: does not go with UMX_PCM16=1 (one output format per run)\n");
+        return 1;
+    }
+    if (!pcm24 && getenv("UMX_PCM24_DITHER"))
+    {
+        fprintf(stderr, "UMX_PCM24_DITHER: needs UMX_PCM24=1\n");
+        return 1;
+    }
     umx_clip_choice clipc;
     if (!umx_clip_from_env(clipc, nullptr))
         return 1;
     const bool resample = env_int("UMX_RESAMPLE", 0) != 0;
-    umx_sample_io io = {UMX_SAMPLE_F32, pcm16 ? UMX_SAMPLE_S16 : UMX_SAMPLE_F32, 0, 0};
-    if (const char *seed = getenv("UMX_PCM16_DITHER"))
+    umx_sample_io io = {UMX_SAMPLE_F32, pcm24 ? UMX_SAMPLE_S24 : pcm16 ? UMX_SAMPLE_S16 : UMX_SAMPLE_F32, 0, 0};
+    if (const char *seed = getenv(pcm24 ? "UMX_PCM24_DITHER" : "UMX_PCM16_DITHER"))
     {
         io.dither = 1;
         io.dither_seed = (unsigned)strtoul(seed, nullptr, 0);
     }
-    if (pcm16) // one input format per run: int16 when every file's head says 16-bit PCM
-    {
-        io.in_format = UMX_SAMPLE_S16;
-        for (int f = 0; f < nfiles && io.in_format == UMX_SAMPLE_S16; ++f)
+    // one input format per run: packed 24-bit when every file's head says 24-bit PCM (UMX_PCM24 only), else int16 when every file's head
+    // says 16-bit PCM, else fp32 (whatever is wrong with a file, the float loader reports it)
+    auto every_file_is = [&](int bits) {
+        for (int f = 0; f < nfiles; ++f)
         {
             int n = 0, ch = 0, rate = 0;
-            if (umx_wav_load_pcm16(argv[3 + f], nullptr, &n, &ch, resample ? &rate : nullptr, err))
-                io.in_format = UMX_SAMPLE_F32; // (whatever is wrong with the file, the float loader reports it)
+            if (bits == 24 ? umx_wav_load_pcm24(argv[3 + f], nullptr, &n, &ch, resample ? &rate : nullptr, err)
+                           : umx_wav_load_pcm16(argv[3 + f], nullptr, &n, &ch, resample ? &rate : nullptr, err))
+                return false;
         }
-    }
-    const bool in16 = io.in_format == UMX_SAMPLE_S16;
+        return true;
+    };
+    if (pcm24 && every_file_is(24))
+        io.in_format = UMX_SAMPLE_S24;
+    else if ((pcm16 || pcm24) && every_file_is(16))
+        io.in_format = UMX_SAMPLE_S16;
+    const bool in16 = io.in_format != UMX_SAMPLE_F32; // (the files go up as they are: int16, or packed 24-bit)
+    const bool int_out = pcm16 || pcm24;
     umx_model *model = nullptr;
     if (umx_model_load(model_file.c_str(), &model, err)) // umx.cpp:63-70
     {
@@ -244,7 +278,8 @@ int main(int argc, const char **argv)
             if (!mixed && !choice.write[t]) // a target that did not run (UMX_TARGETS): a silent slot
                 continue;
             const std::string p = (dir / (mixed ? mixc.name[t] + ".wav" : choice.file[t])).string();
-            if (pcm16 ? umx_wav_write_pcm16_rate(p.c_str(), bufs16[t], n, rate_, err_)
+            if (pcm24   ? umx_wav_write_pcm24_rate(p.c_str(), reinterpret_cast<const unsigned char *>(bufs16[t]), n, rate_, err_)
+                : pcm16 ? umx_wav_write_pcm16_rate(p.c_str(), bufs16[t], n, rate_, err_)
                 : resample ? umx_wav_write_f32_rate(p.c_str(), bufs[t], n, rate_, err_)
                            : umx_wav_write_f32(p.c_str(), bufs[t], n, err_))
                 return false;
@@ -280,7 +315,7 @@ int main(int argc, const char **argv)
                 fj->index = f;
                 int ch = 0;
                 char rerr[UMX_ERRLEN] = "";
-                const bool bad = (in16       ? umx_wav_load_pcm16(argv[3 + f], &fj->audio16, &fj->n, &ch, resample ? &fj->rate : nullptr, rerr)
+                const bool bad = (in16       ? load_int(io.in_format, argv[3 + f], &fj->audio16, &fj->n, &ch, resample ? &fj->rate : nullptr, rerr)
                                   : resample ? umx_wav_load_rate(argv[3 + f], &fj->audio, &fj->n, &ch, &fj->rate, rerr)
                                              : umx_wav_load(argv[3 + f], &fj->audio, &fj->n, &ch, rerr)) != 0; // umx.cpp:56
                 std::lock_guard<std::mutex> lock(q.m);
@@ -331,7 +366,7 @@ int main(int argc, const char **argv)
                                                                          mixed ? mixc.gains : nullptr, flags, &io, clipc.clip_mode)
                         : clipc.active() ? umx_hip_separate_queue_levels(ctx, BatchQueue::next, BatchQueue::done_levels, &q, mixc.n_out,
                                                                        mixed ? mixc.gains : nullptr, flags, &io, clipc.clip_mode)
-                        : pcm16 ? umx_hip_separate_queue_io(ctx, BatchQueue::next, BatchQueue::done, &q, mixc.n_out, mixed ? mixc.gains : nullptr, flags, &io)
+                        : int_out ? umx_hip_separate_queue_io(ctx, BatchQueue::next, BatchQueue::done, &q, mixc.n_out, mixed ? mixc.gains : nullptr, flags, &io)
                               : umx_hip_separate_queue(ctx, BatchQueue::next, BatchQueue::done, &q, mixc.n_out, mixed ? mixc.gains : nullptr, flags);
         wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         {
@@ -377,7 +412,7 @@ int main(int argc, const char **argv)
         for (int i = 0; i < nb; ++i)
         {
             int ch = 0;
-            if (in16       ? umx_wav_load_pcm16(argv[3 + f0 + i], &audio16[i], &n[i], &ch, resample ? &rate[i] : nullptr, err)
+            if (in16       ? load_int(io.in_format, argv[3 + f0 + i], &audio16[i], &n[i], &ch, resample ? &rate[i] : nullptr, err)
                 : resample ? umx_wav_load_rate(argv[3 + f0 + i], &audio[i], &n[i], &ch, &rate[i], err)
                            : umx_wav_load(argv[3 + f0 + i], &audio[i], &n[i], &ch, err)) // umx.cpp:56
             {
@@ -388,13 +423,13 @@ int main(int argc, const char **argv)
             audio_secs += n[i] / (double)rate[i];
             for (int t = 0; t < per_file; ++t)
             {
-                if (pcm16)
-                    stems16[per_file * i + t].resize((size_t)2 * n[i]);
+                if (int_out)
+                    stems16[per_file * i + t].resize(int_units(io.out_format) * n[i]);
                 else
                     stems[per_file * i + t].resize((size_t)2 * n[i]);
                 out[per_file * i + t] = stems[per_file * i + t].data();
                 out16[per_file * i + t] = stems16[per_file * i + t].data();
-                out_io[per_file * i + t] = pcm16 ? (void *)out16[per_file * i + t] : (void *)out[per_file * i + t];
+                out_io[per_file * i + t] = int_out ? (void *)out16[per_file * i + t] : (void *)out[per_file * i + t];
             }
         }
         const auto t0 = std::chrono::steady_clock::now();

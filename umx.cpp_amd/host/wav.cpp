@@ -26,18 +26,19 @@ uint16_t u16(const unsigned char *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 } // namespace
 
 // any_rate: report the file's rate in *rate_out (8000 .. 192000 Hz) instead of refusing all but 44100
-// pcm16: the file's int16 samples as they are (16-bit PCM files only) in *pcm16_out instead of floats in *audio_out; without
-// pcm16_out only the file's head is read and what it declares reported (is it 16-bit PCM, its frames, channels, rate)
-static int wav_load(const char *path, float **audio_out, bool pcm16, int16_t **pcm16_out, int *n_frames_out, int *channels_in_file, bool any_rate, int *rate_out, char *err)
+// pcm: 16 or 24 (0: floats) -- the file's integer samples as they are (PCM files of that width only: int16, or packed 3-byte samples)
+// in *pcm_out instead of floats in *audio_out; without pcm_out only the file's head is read and what it declares reported (is it PCM
+// of that width, its frames, channels, rate)
+static int wav_load(const char *path, float **audio_out, int pcm, void **pcm_out, int *n_frames_out, int *channels_in_file, bool any_rate, int *rate_out, char *err)
 {
-    const bool probe = pcm16 && !pcm16_out;
-    if (!path || (!pcm16 && !audio_out) || !n_frames_out)
+    const bool probe = pcm && !pcm_out;
+    if (!path || (!pcm && !audio_out) || !n_frames_out)
     {
-        seterr(err, pcm16 ? "umx_wav_load_pcm16: null argument" : any_rate ? "umx_wav_load_rate: null argument" : "umx_wav_load: null argument");
+        seterr(err, pcm == 24 ? "umx_wav_load_pcm24: null argument" : pcm ? "umx_wav_load_pcm16: null argument" : any_rate ? "umx_wav_load_rate: null argument" : "umx_wav_load: null argument");
         return UMX_ERR_ARG;
     }
-    if (pcm16_out)
-        *pcm16_out = nullptr;
+    if (pcm_out)
+        *pcm_out = nullptr;
     if (audio_out)
         *audio_out = nullptr;
     *n_frames_out = 0;
@@ -130,11 +131,11 @@ static int wav_load(const char *path, float **audio_out, bool pcm16, int16_t **p
         return UMX_HOST_ERR_AUDIO;
     }
     const size_t n = data_len / ((size_t)bps * channels);
-    if (pcm16)
+    if (pcm)
     {
-        if (fmt_tag != 1 || bits != 16)
+        if (fmt_tag != 1 || bits != pcm)
         {
-            seterr(err, "not a 16-bit PCM file (the float loader takes it)");
+            seterr(err, pcm == 24 ? "not a 24-bit PCM file (the float loader takes it)" : "not a 16-bit PCM file (the float loader takes it)");
             return UMX_HOST_ERR_AUDIO;
         }
         if (probe)
@@ -142,6 +143,26 @@ static int wav_load(const char *path, float **audio_out, bool pcm16, int16_t **p
             *n_frames_out = (int)n;
             return UMX_OK;
         }
+    }
+    if (pcm == 24)
+    {
+        unsigned char *q = (unsigned char *)malloc(6 * std::max<size_t>(n, 1));
+        if (!q)
+        {
+            seterr(err, "out of memory");
+            return UMX_HOST_ERR_IO;
+        }
+        for (size_t i = 0; i < n; ++i) // mono duplicated, as the float loader does
+        {
+            memcpy(q + 6 * i, data + (channels == 1 ? i : 2 * i) * 3, 3);
+            memcpy(q + 6 * i + 3, data + (channels == 1 ? i : 2 * i + 1) * 3, 3);
+        }
+        *pcm_out = q;
+        *n_frames_out = (int)n;
+        return UMX_OK;
+    }
+    if (pcm)
+    {
         int16_t *q = (int16_t *)malloc(sizeof(int16_t) * 2 * std::max<size_t>(n, 1));
         if (!q)
         {
@@ -153,7 +174,7 @@ static int wav_load(const char *path, float **audio_out, bool pcm16, int16_t **p
             q[2 * i] = (int16_t)u16(data + (channels == 1 ? i : 2 * i) * 2);
             q[2 * i + 1] = (int16_t)u16(data + (channels == 1 ? i : 2 * i + 1) * 2);
         }
-        *pcm16_out = q;
+        *pcm_out = q;
         *n_frames_out = (int)n;
         return UMX_OK;
     }
@@ -199,18 +220,33 @@ static int wav_load(const char *path, float **audio_out, bool pcm16, int16_t **p
 
 extern "C" int umx_wav_load(const char *path, float **audio_out, int *n_frames_out, int *channels_in_file, char *err)
 {
-    return wav_load(path, audio_out, false, nullptr, n_frames_out, channels_in_file, false, nullptr, err);
+    return wav_load(path, audio_out, 0, nullptr, n_frames_out, channels_in_file, false, nullptr, err);
 }
 
 extern "C" int umx_wav_load_rate(const char *path, float **audio_out, int *n_frames_out, int *channels_in_file, int *rate_out, char *err)
 {
-    return wav_load(path, audio_out, false, nullptr, n_frames_out, channels_in_file, true, rate_out, err);
+    return wav_load(path, audio_out, 0, nullptr, n_frames_out, channels_in_file, true, rate_out, err);
 }
 
 extern "C" int umx_wav_load_pcm16(const char *path, int16_t **audio_out, int *n_frames_out, int *channels_in_file, int *rate_out, char *err)
 {
-    return wav_load(path, nullptr, true, audio_out, n_frames_out, channels_in_file, rate_out != nullptr, rate_out, err);
+    void *q = nullptr;
+    const int rc = wav_load(path, nullptr, 16, audio_out ? &q : nullptr, n_frames_out, channels_in_file, rate_out != nullptr, rate_out, err);
+    if (audio_out)
+        *audio_out = (int16_t *)q;
+    return rc;
 }
+
+extern "C" int umx_wav_load_pcm24(const char *path, unsigned char **audio_out, int *n_frames_out, int *channels_in_file, int *rate_out, char *err)
+{
+    void *q = nullptr;
+    const int rc = wav_load(path, nullptr, 24, audio_out ? &q : nullptr, n_frames_out, channels_in_file, rate_out != nullptr, rate_out, err);
+    if (audio_out)
+        *audio_out = (unsigned char *)q;
+    return rc;
+}
+
+extern "C" void umx_wav_free_pcm24(unsigned char *audio) { free(audio); }
 
 extern "C" void umx_wav_free_pcm16(int16_t *audio) { free(audio); }
 
@@ -221,7 +257,7 @@ extern "C" int umx_wav_write_f32(const char *path, const float *audio, int n_fra
     return umx_wav_write_f32_rate(path, audio, n_frames, UMX_SAMPLE_RATE, err);
 }
 
-// bits: 32 = IEEE float samples, 16 = PCM samples
+// bits: 32 = IEEE float samples, 16 = PCM samples, 24 = packed PCM samples
 static int wav_write(const char *path, const void *audio, int n_frames, int rate, int bits, char *err);
 
 extern "C" int umx_wav_write_f32_rate(const char *path, const float *audio, int n_frames, int rate, char *err)
@@ -234,12 +270,17 @@ extern "C" int umx_wav_write_pcm16_rate(const char *path, const int16_t *audio, 
     return wav_write(path, audio, n_frames, rate, 16, err);
 }
 
+extern "C" int umx_wav_write_pcm24_rate(const char *path, const unsigned char *audio, int n_frames, int rate, char *err)
+{
+    return wav_write(path, audio, n_frames, rate, 24, err);
+}
+
 static int wav_write(const char *path, const void *audio, int n_frames, int rate, int bits, char *err)
 {
     const uint32_t bps = (uint32_t)bits / 8;
     if (!path || !audio || n_frames < 0 || rate < 1)
     {
-        seterr(err, bits == 16 ? "umx_wav_write_pcm16: bad argument" : "umx_wav_write_f32: bad argument");
+        seterr(err, bits == 24 ? "umx_wav_write_pcm24: bad argument" : bits == 16 ? "umx_wav_write_pcm16: bad argument" : "umx_wav_write_f32: bad argument");
         return UMX_ERR_ARG;
     }
     FILE *f = fopen(path, "wb");
@@ -256,7 +297,7 @@ static int wav_write(const char *path, const void *audio, int n_frames, int rate
     p32(4, 36 + data_bytes);
     memcpy(h + 8, "WAVEfmt ", 8);
     p32(16, 16);
-    p16(20, bits == 16 ? 1 : 3); // WAVE_FORMAT_PCM / WAVE_FORMAT_IEEE_FLOAT
+    p16(20, bits == 32 ? 3 : 1); // WAVE_FORMAT_PCM / WAVE_FORMAT_IEEE_FLOAT
     p16(22, 2);
     p32(24, (uint32_t)rate);
     p32(28, (uint32_t)rate * 2 * bps);
