@@ -388,6 +388,53 @@ def test_levels_rescale_and_loudness_of_an_s24_output(pkg, eng1, eng3, qwave):
                 _same([env[ln]], [env32[ln]], ("loudness under rescale", ln, seed))  # ... and before any divisor
 
 
+def test_dispatch_matrix_every_format_pair_clip_mode_and_dither(pkg, eng1, qwave):
+    """Every (in, out) format pair x clip mode x dither seed through umx_hip_separate_tracks_levels, on one track whose regions all
+    start at odd frames (shift offset 4033: the 24-bit head / tail path, byte offsets of 6 x an odd frame) and whose first mix row
+    passes full scale: the bytes and the levels record of each call are the fp32 call's composed with pcm16_ref / pcm24_ref /
+    levels_ref, bit for bit.  36 cases; the 6 that ask for dither with an fp32 output are the documented refusal (sample io: dither
+    goes with an integer output only), and it is that refusal they are held to."""
+    F32, S16, S24 = pkg.SAMPLE_F32, pkg.SAMPLE_S16, pkg.SAMPLE_S24
+    kw = {"gains": GAINS, "shift_offsets": [4033]}
+    q24 = np.ascontiguousarray(qwave[:, :25739])
+    x = ref.decode(q24)
+    q16 = ref16.encode(x)
+    plain_x = eng1.separate_many_mix([x], GAINS, shift_offsets=[4033])[0]
+    plain_16 = eng1.separate_many_mix([ref16.decode(q16)], GAINS, shift_offsets=[4033])[0]
+    cases = 0
+    for fin, given, stems in ((F32, x, plain_x), (S16, q16, plain_16), (S24, q24, plain_x)):
+        base = [lev.levels(s, m) for m, s in enumerate(stems)]
+        g_track = lev.gain([b["peak"] for b in base])
+        assert g_track > 1 and base[0]["over_unity"] > 100 and base[1]["over_unity"] == 0, base
+        for fout in (F32, S16, S24):
+            for clip in (pkg.CLIP_CLAMP, pkg.CLIP_RESCALE):
+                for seed in (None, SEED):
+                    cases += 1
+                    what = (fin, fout, clip, seed)
+                    io = pkg.sample_io(fin, fout, seed)
+                    if fout == F32 and seed is not None:
+                        with pytest.raises(pkg.UmxError) as e:
+                            eng1.separate_many_levels([given], clip, io, **kw)
+                        assert e.value.code == pkg.ERR_ARG and "dither" in str(e.value), (what, str(e.value))
+                        continue
+                    outs, lvs = eng1.separate_many_levels([given], clip, io, **kw)
+                    g = g_track if clip == pkg.CLIP_RESCALE else np.float32(1.0)
+                    left = [lev.rescaled(s, g) for s in stems]
+                    if fout == S16:
+                        want = [ref16.encode(s, m, 0, seed) for m, s in enumerate(left)]
+                        clipped = [lev.levels(s, m, 0, True, seed, g)["clipped"] for m, s in enumerate(stems)]
+                    elif fout == S24:
+                        want = [ref.encode(s, m, 0, seed) for m, s in enumerate(left)]
+                        clipped = [ref.clipped(s, m, 0, seed) for m, s in enumerate(left)]
+                    else:
+                        want, clipped = left, [0, 0, 0]
+                    _same(outs[0], want, what)
+                    recs = [{**{k: base[m][k] for k in ("peak_bits", "over_unity", "nonfinite")}, "clipped": clipped[m]} for m in range(3)]
+                    assert _records(lvs[0], 3) == recs and np.float32(lvs[0].gain) == g and lvs[0].n_out == 3, (what, _records(lvs[0], 3), recs)
+                    assert (clipped[0] > 100) == (fout != F32 and clip == pkg.CLIP_CLAMP) and clipped[1] == 0, (what, clipped)
+    assert cases == 36
+
+
 def _c_call(pkg, eng, audio_ptrs, lengths, shifts, out_ptrs, io):
     nt = len(lengths)
     a = None if audio_ptrs is None else (C.c_void_p * nt)(*audio_ptrs)

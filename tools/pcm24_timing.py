@@ -144,12 +144,12 @@ def kernel_main(a):
     cases = [("pcm16_decode_kernel", 12, lambda: eng.pcm16_decode_device(p16[0], n, src[0], hip_stream=hs)),
              ("pcm24_decode_kernel", 14, lambda: eng.pcm24_decode_device(p24[0], n, src[0], hip_stream=hs)),
              ("pcm24_decode_kernel, address 2 mod 4", 14, lambda: eng.pcm24_decode_device(p24odd[0], n, src[0], hip_stream=hs)),
-             ("pcm16_encode_kernel x 4, dither", 48, lambda: eng.pcm16_encode_device(src, n, p16, 0, 7, hip_stream=hs)),
-             ("pcm24_encode_kernel x 4, dither", 56, lambda: eng.pcm24_encode_device(src, n, p24, 0, 7, hip_stream=hs)),
-             ("pcm24_encode_kernel x 4, dither, 2 mod 4", 56, lambda: eng.pcm24_encode_device(src, n, p24odd, 1, 7, hip_stream=hs)),
-             ("pcm24_encode_kernel x 4, no dither", 56, lambda: eng.pcm24_encode_device(src, n, p24, 0, None, hip_stream=hs)),
-             ("pcm16_encode_rescaled_kernel x 4, dither", 48, lambda: eng.pcm16_encode_rescaled_device(src, n, p16, acc.data_ptr(), 0, 7, hip_stream=hs)),
-             ("pcm24_encode_rescaled_kernel x 4, dither", 56, lambda: eng.pcm24_encode_rescaled_device(src, n, p24, acc.data_ptr(), 0, 7, hip_stream=hs))]
+             ("encode_kernel<SampleS16> x 4, dither", 48, lambda: eng.pcm16_encode_device(src, n, p16, 0, 7, hip_stream=hs)),
+             ("encode_kernel<SampleS24> x 4, dither", 56, lambda: eng.pcm24_encode_device(src, n, p24, 0, 7, hip_stream=hs)),
+             ("encode_kernel<SampleS24> x 4, dither, 2 mod 4", 56, lambda: eng.pcm24_encode_device(src, n, p24odd, 1, 7, hip_stream=hs)),
+             ("encode_kernel<SampleS24> x 4, no dither", 56, lambda: eng.pcm24_encode_device(src, n, p24, 0, None, hip_stream=hs)),
+             ("encode_rescaled_kernel<SampleS16> x 4, dither", 48, lambda: eng.pcm16_encode_rescaled_device(src, n, p16, acc.data_ptr(), 0, 7, hip_stream=hs)),
+             ("encode_rescaled_kernel<SampleS24> x 4, dither", 56, lambda: eng.pcm24_encode_rescaled_device(src, n, p24, acc.data_ptr(), 0, 7, hip_stream=hs))]
     lines = [f"# {torch.cuda.get_device_name(0)}; {n} frames ({a.single_seconds:.0f} s), stream events, 1 warm-up launch, median of {a.reps} (min .. max); "
              "GB/s: bytes read + written over the median"]
     order = [0, 1, 2, 3, 4, 5, 6, 7, 8]
@@ -165,7 +165,7 @@ def kernel_main(a):
             ms.append(t0.elapsed_time(t1))
         v = ms[1:]
         m = statistics.median(v)
-        lines.append(f"{what:<44} {m * 1e3:9.1f} us ({min(v) * 1e3:.1f} .. {max(v) * 1e3:.1f})  {bytes_per_frame * n / (m * 1e-3) / 1e9:7.0f} GB/s")
+        lines.append(f"{what:<46} {m * 1e3:9.1f} us ({min(v) * 1e3:.1f} .. {max(v) * 1e3:.1f})  {bytes_per_frame * n / (m * 1e-3) / 1e9:7.0f} GB/s")
     eng.close()
     print("\n".join(lines))
     if a.out:

@@ -393,17 +393,22 @@ def pcm16_decode_host(q):
     return x
 
 
+def _encode_host(fmt, x, buffer, first_frame, dither_seed):
+    """umx_hip_pcm<fmt>_encode_host (fmt: 16 or 24) of a (2,n) float32 x -> the n frames as the format holds them: (n,2) int16, or 6 n bytes."""
+    a = np.ascontiguousarray(np.asarray(x, np.float32).T)
+    q, qp, out_format = {16: (np.empty(a.shape, np.int16), _i16p, SAMPLE_S16), 24: (np.empty(6 * a.shape[0], np.uint8), _u8p, SAMPLE_S24)}[fmt]
+    io = sample_io(SAMPLE_F32, out_format, dither_seed)
+    name = f"umx_hip_pcm{fmt}_encode_host"
+    rc = getattr(hip_lib(), name)(a.ctypes.data_as(_fp), a.shape[0], int(buffer), int(first_frame), C.byref(io), q.ctypes.data_as(qp))
+    if rc != UMX_OK:
+        raise UmxError(rc, name)
+    return q
+
+
 def pcm16_encode_host(x, buffer=0, first_frame=0, dither_seed=None):
     """umx_hip_pcm16_encode_host: (2,n) float32 -> (2,n) int16 as output buffer `buffer` of a call, frame 0 of x being frame
     first_frame of the track (no GPU)."""
-    a = np.ascontiguousarray(np.asarray(x, np.float32).T)
-    q = np.empty(a.shape, np.int16)
-    io = sample_io(SAMPLE_F32, SAMPLE_S16, dither_seed)
-    rc = hip_lib().umx_hip_pcm16_encode_host(a.ctypes.data_as(_fp), a.shape[0], int(buffer), int(first_frame), C.byref(io),
-                                             q.ctypes.data_as(_i16p))
-    if rc != UMX_OK:
-        raise UmxError(rc, "umx_hip_pcm16_encode_host")
-    return np.ascontiguousarray(q.T)
+    return np.ascontiguousarray(_encode_host(16, x, buffer, first_frame, dither_seed).T)
 
 
 def pcm24_pack(q):
@@ -442,14 +447,7 @@ def pcm24_decode_host(q):
 def pcm24_encode_host(x, buffer=0, first_frame=0, dither_seed=None):
     """umx_hip_pcm24_encode_host: (2,n) float32 -> (2,n) int32 codes as output buffer `buffer` of a call, frame 0 of x being frame
     first_frame of the track (no GPU)."""
-    a = np.ascontiguousarray(np.asarray(x, np.float32).T)
-    b = np.empty(6 * a.shape[0], np.uint8)
-    io = sample_io(SAMPLE_F32, SAMPLE_S24, dither_seed)
-    rc = hip_lib().umx_hip_pcm24_encode_host(a.ctypes.data_as(_fp), a.shape[0], int(buffer), int(first_frame), C.byref(io),
-                                             b.ctypes.data_as(_u8p))
-    if rc != UMX_OK:
-        raise UmxError(rc, "umx_hip_pcm24_encode_host")
-    return pcm24_unpack(b)
+    return pcm24_unpack(_encode_host(24, x, buffer, first_frame, dither_seed))
 
 
 def levels_host(x, buffer=0, first_frame=0, io=None, clip_divisor=1.0, acc=None):
@@ -964,37 +962,37 @@ class Engine:
         self._check(self.lib.umx_hip_levels_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(first_frame),
                                                    None if io is None else C.byref(io), C.c_void_p(acc_ptr), hip_stream))
 
-    def pcm16_encode_rescaled_device(self, in_ptrs, n, out_ptrs, acc_ptr, first_frame=0, dither_seed=None, hip_stream=None):
-        """umx_hip_pcm16_encode_rescaled_device: pcm16_encode_device() on x / g, g formed on the device from the record at acc_ptr."""
+    def _encode_device(self, fmt, in_ptrs, n, out_ptrs, first_frame, dither_seed, hip_stream, acc_ptr=None):
+        """umx_hip_pcm<fmt>_encode_device, or with acc_ptr umx_hip_pcm<fmt>_encode_rescaled_device (fmt: 16 or 24)."""
         nb = len(in_ptrs)
         assert len(out_ptrs) == nb
-        io = sample_io(SAMPLE_F32, SAMPLE_S16, dither_seed)
-        self._check(self.lib.umx_hip_pcm16_encode_rescaled_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(first_frame),
-                                                                  C.byref(io), (C.c_void_p * max(1, nb))(*out_ptrs), C.c_void_p(acc_ptr),
-                                                                  hip_stream))
+        io = sample_io(SAMPLE_F32, {16: SAMPLE_S16, 24: SAMPLE_S24}[fmt], dither_seed)
+        fn = getattr(self.lib, f"umx_hip_pcm{fmt}_encode_device" if acc_ptr is None else f"umx_hip_pcm{fmt}_encode_rescaled_device")
+        tail = (hip_stream,) if acc_ptr is None else (C.c_void_p(acc_ptr), hip_stream)
+        self._check(fn(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(first_frame), C.byref(io), (C.c_void_p * max(1, nb))(*out_ptrs),
+                       *tail))
+
+    def _decode_device(self, fmt, in_ptr, n, out_ptr, hip_stream):
+        """umx_hip_pcm<fmt>_decode_device (fmt: 16 or 24)."""
+        self._check(getattr(self.lib, f"umx_hip_pcm{fmt}_decode_device")(self.h, C.c_void_p(in_ptr), int(n), C.c_void_p(out_ptr), hip_stream))
+
+    def pcm16_encode_rescaled_device(self, in_ptrs, n, out_ptrs, acc_ptr, first_frame=0, dither_seed=None, hip_stream=None):
+        """umx_hip_pcm16_encode_rescaled_device: pcm16_encode_device() on x / g, g formed on the device from the record at acc_ptr."""
+        self._encode_device(16, in_ptrs, n, out_ptrs, first_frame, dither_seed, hip_stream, acc_ptr)
 
     def pcm24_encode_rescaled_device(self, in_ptrs, n, out_ptrs, acc_ptr, first_frame=0, dither_seed=None, hip_stream=None):
         """umx_hip_pcm24_encode_rescaled_device: pcm24_encode_device() on x / g, g formed on the device from the record at acc_ptr."""
-        nb = len(in_ptrs)
-        assert len(out_ptrs) == nb
-        io = sample_io(SAMPLE_F32, SAMPLE_S24, dither_seed)
-        self._check(self.lib.umx_hip_pcm24_encode_rescaled_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(first_frame),
-                                                                  C.byref(io), (C.c_void_p * max(1, nb))(*out_ptrs), C.c_void_p(acc_ptr),
-                                                                  hip_stream))
+        self._encode_device(24, in_ptrs, n, out_ptrs, first_frame, dither_seed, hip_stream, acc_ptr)
 
     def pcm24_decode_device(self, in_ptr, n, out_ptr, hip_stream=None):
         """umx_hip_pcm24_decode_device: n packed 24-bit stereo frames (6 n bytes, 2-byte aligned) at device address in_ptr -> (2,n)
         interleaved fp32 at out_ptr."""
-        self._check(self.lib.umx_hip_pcm24_decode_device(self.h, C.c_void_p(in_ptr), int(n), C.c_void_p(out_ptr), hip_stream))
+        self._decode_device(24, in_ptr, n, out_ptr, hip_stream)
 
     def pcm24_encode_device(self, in_ptrs, n, out_ptrs, first_frame=0, dither_seed=None, hip_stream=None):
         """umx_hip_pcm24_encode_device: 1 .. 4 device buffers (2,n) interleaved fp32 -> n packed 24-bit stereo frames each (6 n bytes,
         2-byte aligned), buffer b as output b."""
-        nb = len(in_ptrs)
-        assert len(out_ptrs) == nb
-        io = sample_io(SAMPLE_F32, SAMPLE_S24, dither_seed)
-        self._check(self.lib.umx_hip_pcm24_encode_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(first_frame), C.byref(io),
-                                                         (C.c_void_p * max(1, nb))(*out_ptrs), hip_stream))
+        self._encode_device(24, in_ptrs, n, out_ptrs, first_frame, dither_seed, hip_stream)
 
     def rescale_device(self, ptrs, n, acc_ptr, hip_stream=None):
         """umx_hip_rescale_device: 1 .. 4 device buffers (2,n) interleaved fp32 divided in place by the divisor of the record at acc_ptr."""
@@ -1003,15 +1001,11 @@ class Engine:
 
     def pcm16_decode_device(self, in_ptr, n, out_ptr, hip_stream=None):
         """umx_hip_pcm16_decode_device: n int16 stereo frames at device address in_ptr -> (2,n) interleaved fp32 at out_ptr."""
-        self._check(self.lib.umx_hip_pcm16_decode_device(self.h, C.c_void_p(in_ptr), int(n), C.c_void_p(out_ptr), hip_stream))
+        self._decode_device(16, in_ptr, n, out_ptr, hip_stream)
 
     def pcm16_encode_device(self, in_ptrs, n, out_ptrs, first_frame=0, dither_seed=None, hip_stream=None):
         """umx_hip_pcm16_encode_device: 1 .. 4 device buffers (2,n) interleaved fp32 -> n int16 stereo frames each, buffer b as output b."""
-        nb = len(in_ptrs)
-        assert len(out_ptrs) == nb
-        io = sample_io(SAMPLE_F32, SAMPLE_S16, dither_seed)
-        self._check(self.lib.umx_hip_pcm16_encode_device(self.h, nb, (C.c_void_p * nb)(*in_ptrs), int(n), int(first_frame), C.byref(io),
-                                                         (C.c_void_p * nb)(*out_ptrs), hip_stream))
+        self._encode_device(16, in_ptrs, n, out_ptrs, first_frame, dither_seed, hip_stream)
 
     # --- the track queue (DESIGN 18): more tracks than lanes, a lane refilled with the next track the moment one ends ---
     def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None, io=None, clip=None, levels=False, loudness=False, rates=None):

@@ -41,6 +41,7 @@
 #include "softmask.h"
 #include "shift_mean.h"
 #include "stem_mix.h"
+#include "sample_format.h"
 #include "pcm16.h"
 #include "pcm24.h"
 #include "levels.h"
@@ -630,9 +631,9 @@ struct umx_hip_ctx
         RsStage rs; // the native-rate staging of a resampled job, frames at the caller's frame numbers
         // DESIGN 19, 24, only once a job asks for UMX_SAMPLE_S16 or UMX_SAMPLE_S24: the track as uploaded and its outputs as they leave, 4
         // or 6 bytes per frame of the CALLER's track (no shift padding; capacities in words), each grow-only on its own
-        uint32_t *in16 = nullptr, *out16[4] = {};
-        size_t cap_in16 = 0, cap_out16[4] = {};
-        hipEvent_t in_ev = nullptr; // behind the most recent kernel that wrote `in` -- a decode out of in16, a resampled range out of rs.in
+        uint32_t *in_int = nullptr, *out_int[4] = {};
+        size_t cap_in_int = 0, cap_out_int[4] = {};
+        hipEvent_t in_ev = nullptr; // behind the most recent kernel that wrote `in` -- a decode out of in_int, a resampled range out of rs.in
                                     // (track_upload_until): every call that reads `in` waits for it
         umx_levels_acc *lev = nullptr; // DESIGN 20, only once a job measures: the record of what leaves, zeroed with the accumulators
         double *hopE = nullptr;        // DESIGN 21, only once a job measures loudness: its hop energies [output][channel][hop], grow-only,
@@ -711,9 +712,9 @@ struct umx_hip_ctx
     static bool track_job_ok(const float *audio, int length, int shift_offset, float *const *out, int n_host);
     static bool track_geometry(int length, int shift_offset, int stride, TrackJob &j);
     int track_bufs_grow(TrackBufs &tb_, size_t frames);
-    int track_pcm16_grow(TrackBufs &tb_, const umx_sample_io &io, size_t frames, int n_host);
+    int track_int_grow(TrackBufs &tb_, const umx_sample_io &io, size_t frames, int n_host);
     void track_encode(const TrackBufs &tb_, const umx_sample_io &io, int n_host, float *const src[4], size_t src_start, int count,
-                      long long first_frame, hipStream_t st);
+                      long long first_frame, umx_levels_acc *acc, hipStream_t st);
     int track_levels_grow(TrackBufs &tb_);
     int admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt, const float *audio, int rate, int length_at_rate, bool leaves_whole);
     void track_leave(TrackJob &j, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st);

@@ -23,6 +23,91 @@ static bool device_buffers(umx_hip_ctx *ctx, const char *what, int n_buffers, Fr
     return true;
 }
 
+// ---------------------------------------------------------------- the integer sample formats behind their entry points (sample_format.h)
+// the dither of an integer output as the kernels and their host restatements take it (io == NULL: none)
+struct DitherArg
+{
+    bool on;
+    uint32_t seed;
+};
+static DitherArg dither_of(const umx_sample_io *io) { return {io && io->dither, io ? io->dither_seed : 0u}; }
+
+// a device buffer of `format`: at the alignment its trait asks for
+static bool sample_aligned(umx_hip_ctx *ctx, const char *what, int format, int n_buffers, const void *const *bufs)
+{
+    return with_sample_format(format, [&](auto t) {
+        for (int b = 0; b < n_buffers; ++b)
+            if ((uintptr_t)bufs[b] & (uintptr_t)(decltype(t)::align - 1))
+            {
+                ctx->set_error(std::string(what) + ": " + decltype(t)::misaligned());
+                return false;
+            }
+        return true;
+    });
+}
+
+// The six device entry points of the two integer formats.  what: their name in messages ("pcm16 decode", "rescaled pcm24 encode").
+static int decode_device(umx_hip_ctx *ctx, const char *what, int format, const void *in_dev, int n, float *out_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!in_dev || !out_dev || n < 1)
+    {
+        ctx->set_error(std::string(what) + ": need both buffers and n >= 1");
+        return UMX_ERR_ARG;
+    }
+    if (!sample_aligned(ctx, what, format, 1, &in_dev))
+        return UMX_ERR_ARG;
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    launch_decode(format, in_dev, reinterpret_cast<float2 *>(out_dev), n, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+
+// rescaled: over the divisor of the record acc_dev, which must be there (else acc_dev is not looked at: the plain encode)
+static int encode_device(umx_hip_ctx *ctx, const char *what, int format, int n_buffers, const float *const *in_dev, int n, long long first_frame,
+                         const umx_sample_io *io, void *const *out_dev, bool rescaled, umx_levels_acc *acc_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    const float2 *src[4] = {};
+    uint8_t *dst[4] = {};
+    if (!device_buffers(ctx, what, n_buffers, in_dev, n, first_frame, src) || !device_buffers(ctx, what, n_buffers, out_dev, n, first_frame, dst) ||
+        !sample_aligned(ctx, what, format, n_buffers, out_dev))
+        return UMX_ERR_ARG;
+    if (rescaled && !acc_dev)
+    {
+        ctx->set_error(std::string(what) + ": null record");
+        return UMX_ERR_ARG;
+    }
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    const DitherArg d = dither_of(io);
+    launch_encode(format, n_buffers, src, dst, n, first_frame, d.on, d.seed, rescaled ? acc_dev : nullptr, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+
+// the host restatements: n_values samples, and n_frames stereo frames of output buffer `buffer`
+template <class T> static int decode_host(T t, const void *q, long long n_values, float *x)
+{
+    if (!q || !x || n_values < 0)
+        return UMX_ERR_ARG;
+    for (long long i = 0; i < n_values; ++i)
+        x[i] = load_sample(t, q, (size_t)i);
+    return UMX_OK;
+}
+template <class T> static int encode_host(T t, const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, void *q)
+{
+    if (!x || !q || n_frames < 0 || buffer < 0 || buffer >= UMX_MAX_MIX_OUTPUTS || first_frame < 0)
+        return UMX_ERR_ARG;
+    const DitherArg d = dither_of(io);
+    const uint32_t key[2] = {sample_dither_key(d.seed, buffer, 0), sample_dither_key(d.seed, buffer, 1)};
+    for (int i = 0; i < n_frames; ++i)
+        for (int ch = 0; ch < 2; ++ch)
+            store_sample(t, q, 2 * (size_t)i + ch, T::clamp(T::round(x[2 * (size_t)i + ch], d.on, key[ch], first_frame + i)));
+    return UMX_OK;
+}
+
 extern "C"
 {
 
@@ -559,156 +644,40 @@ int umx_hip_separate_queue_io(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queu
 
 int umx_hip_pcm16_decode_device(umx_hip_ctx *ctx, const int16_t *in_dev, int n, float *out_dev, void *hip_stream)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
-    if (!in_dev || !out_dev || n < 1)
-    {
-        ctx->set_error("pcm16 decode: need both buffers and n >= 1");
-        return UMX_ERR_ARG;
-    }
-    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
-    launch_pcm16_decode(reinterpret_cast<const uint32_t *>(in_dev), reinterpret_cast<float2 *>(out_dev), n, (hipStream_t)hip_stream);
-    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
-    return UMX_OK;
+    return decode_device(ctx, "pcm16 decode", UMX_SAMPLE_S16, in_dev, n, out_dev, hip_stream);
 }
-
-// the dither of an int16 output as the kernels and their host restatements take it (io == NULL: none)
-struct DitherArg
-{
-    bool on;
-    uint32_t seed;
-};
-static DitherArg dither_of(const umx_sample_io *io) { return {io && io->dither, io ? io->dither_seed : 0u}; }
-
 int umx_hip_pcm16_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
                                 const umx_sample_io *io, int16_t *const *out_dev, void *hip_stream)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
-    const float2 *src[4] = {};
-    uint32_t *dst[4] = {};
-    if (!device_buffers(ctx, "pcm16 encode", n_buffers, in_dev, n, first_frame, src) ||
-        !device_buffers(ctx, "pcm16 encode", n_buffers, out_dev, n, first_frame, dst))
-        return UMX_ERR_ARG;
-    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
-    const DitherArg d = dither_of(io);
-    launch_pcm16_encode(n_buffers, src, dst, n, first_frame, d.on, d.seed, (hipStream_t)hip_stream);
-    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
-    return UMX_OK;
+    return encode_device(ctx, "pcm16 encode", UMX_SAMPLE_S16, n_buffers, in_dev, n, first_frame, io, reinterpret_cast<void *const *>(out_dev), false,
+                         nullptr, hip_stream);
 }
-
-int umx_hip_pcm16_decode_host(const int16_t *q, long long n_values, float *x)
-{
-    if (!q || !x || n_values < 0)
-        return UMX_ERR_ARG;
-    for (long long i = 0; i < n_values; ++i)
-        x[i] = pcm16_decode(q[i]);
-    return UMX_OK;
-}
-
+int umx_hip_pcm16_decode_host(const int16_t *q, long long n_values, float *x) { return decode_host(SampleS16(), q, n_values, x); }
 int umx_hip_pcm16_encode_host(const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, int16_t *q)
 {
-    if (!x || !q || n_frames < 0 || buffer < 0 || buffer >= UMX_MAX_MIX_OUTPUTS || first_frame < 0)
-        return UMX_ERR_ARG;
-    const DitherArg d = dither_of(io);
-    const uint32_t key[2] = {pcm16_dither_key(d.seed, buffer, 0), pcm16_dither_key(d.seed, buffer, 1)};
-    for (int i = 0; i < n_frames; ++i)
-        for (int ch = 0; ch < 2; ++ch)
-            q[2 * (size_t)i + ch] = pcm16_encode(x[2 * (size_t)i + ch], d.on, key[ch], first_frame + i);
-    return UMX_OK;
-}
-// ---------------------------------------------------------------- packed 24-bit PCM in and out (pcm24.h, DESIGN 24)
-// a packed device buffer: 2-byte aligned (its frames are 6 bytes, so an even base is all it takes)
-static bool pcm24_aligned(umx_hip_ctx *ctx, const char *what, int n_buffers, const void *const *bufs)
-{
-    for (int b = 0; b < n_buffers; ++b)
-        if ((uintptr_t)bufs[b] & 1)
-        {
-            ctx->set_error(std::string(what) + ": a packed 24-bit buffer must be 2-byte aligned");
-            return false;
-        }
-    return true;
+    return encode_host(SampleS16(), x, n_frames, buffer, first_frame, io, q);
 }
 
+// ---------------------------------------------------------------- packed 24-bit PCM in and out (pcm24.h, DESIGN 24)
 int umx_hip_pcm24_decode_device(umx_hip_ctx *ctx, const void *in_dev, int n, float *out_dev, void *hip_stream)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
-    if (!in_dev || !out_dev || n < 1)
-    {
-        ctx->set_error("pcm24 decode: need both buffers and n >= 1");
-        return UMX_ERR_ARG;
-    }
-    if (!pcm24_aligned(ctx, "pcm24 decode", 1, &in_dev))
-        return UMX_ERR_ARG;
-    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
-    launch_pcm24_decode(static_cast<const uint8_t *>(in_dev), reinterpret_cast<float2 *>(out_dev), n, (hipStream_t)hip_stream);
-    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
-    return UMX_OK;
+    return decode_device(ctx, "pcm24 decode", UMX_SAMPLE_S24, in_dev, n, out_dev, hip_stream);
 }
-
 int umx_hip_pcm24_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
                                 const umx_sample_io *io, void *const *out_dev, void *hip_stream)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
-    const float2 *src[4] = {};
-    uint8_t *dst[4] = {};
-    if (!device_buffers(ctx, "pcm24 encode", n_buffers, in_dev, n, first_frame, src) ||
-        !device_buffers(ctx, "pcm24 encode", n_buffers, out_dev, n, first_frame, dst) || !pcm24_aligned(ctx, "pcm24 encode", n_buffers, out_dev))
-        return UMX_ERR_ARG;
-    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
-    const DitherArg d = dither_of(io);
-    launch_pcm24_encode(n_buffers, src, dst, n, first_frame, d.on, d.seed, (hipStream_t)hip_stream);
-    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
-    return UMX_OK;
+    return encode_device(ctx, "pcm24 encode", UMX_SAMPLE_S24, n_buffers, in_dev, n, first_frame, io, out_dev, false, nullptr, hip_stream);
 }
-
 int umx_hip_pcm24_encode_rescaled_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
                                          const umx_sample_io *io, void *const *out_dev, umx_levels_acc *acc_dev, void *hip_stream)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
-    const float2 *src[4] = {};
-    uint8_t *dst[4] = {};
-    if (!device_buffers(ctx, "rescaled pcm24 encode", n_buffers, in_dev, n, first_frame, src) ||
-        !device_buffers(ctx, "rescaled pcm24 encode", n_buffers, out_dev, n, first_frame, dst) ||
-        !pcm24_aligned(ctx, "rescaled pcm24 encode", n_buffers, out_dev))
-        return UMX_ERR_ARG;
-    if (!acc_dev)
-    {
-        ctx->set_error("rescaled pcm24 encode: null record");
-        return UMX_ERR_ARG;
-    }
-    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
-    const DitherArg d = dither_of(io);
-    launch_pcm24_encode_rescaled(n_buffers, src, dst, n, first_frame, d.on, d.seed, acc_dev, (hipStream_t)hip_stream);
-    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
-    return UMX_OK;
+    return encode_device(ctx, "rescaled pcm24 encode", UMX_SAMPLE_S24, n_buffers, in_dev, n, first_frame, io, out_dev, true, acc_dev, hip_stream);
 }
-
 // n_values samples of 3 bytes each
-int umx_hip_pcm24_decode_host(const void *q, long long n_values, float *x)
-{
-    if (!q || !x || n_values < 0)
-        return UMX_ERR_ARG;
-    const uint8_t *p = static_cast<const uint8_t *>(q);
-    for (long long i = 0; i < n_values; ++i)
-        x[i] = pcm24_decode(pcm24_load(p + 3 * (size_t)i));
-    return UMX_OK;
-}
-
+int umx_hip_pcm24_decode_host(const void *q, long long n_values, float *x) { return decode_host(SampleS24(), q, n_values, x); }
 int umx_hip_pcm24_encode_host(const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, void *q)
 {
-    if (!x || !q || n_frames < 0 || buffer < 0 || buffer >= UMX_MAX_MIX_OUTPUTS || first_frame < 0)
-        return UMX_ERR_ARG;
-    const DitherArg d = dither_of(io);
-    const uint32_t key[2] = {pcm16_dither_key(d.seed, buffer, 0), pcm16_dither_key(d.seed, buffer, 1)};
-    uint8_t *p = static_cast<uint8_t *>(q);
-    for (int i = 0; i < n_frames; ++i)
-        for (int ch = 0; ch < 2; ++ch)
-            pcm24_store(p + 3 * (2 * (size_t)i + ch), pcm24_encode(x[2 * (size_t)i + ch], d.on, key[ch], first_frame + i));
-    return UMX_OK;
+    return encode_host(SampleS24(), x, n_frames, buffer, first_frame, io, q);
 }
 
 // the output format whose plain encode clamps what levels count as clipped (io == NULL or an fp32 output: none)
@@ -753,23 +722,8 @@ int umx_hip_levels_device(umx_hip_ctx *ctx, int n_buffers, const float *const *i
 int umx_hip_pcm16_encode_rescaled_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
                                          const umx_sample_io *io, int16_t *const *out_dev, umx_levels_acc *acc_dev, void *hip_stream)
 {
-    if (!ctx)
-        return UMX_ERR_ARG;
-    const float2 *src[4] = {};
-    uint32_t *dst[4] = {};
-    if (!device_buffers(ctx, "rescaled pcm16 encode", n_buffers, in_dev, n, first_frame, src) ||
-        !device_buffers(ctx, "rescaled pcm16 encode", n_buffers, out_dev, n, first_frame, dst))
-        return UMX_ERR_ARG;
-    if (!acc_dev)
-    {
-        ctx->set_error("rescaled pcm16 encode: null record");
-        return UMX_ERR_ARG;
-    }
-    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
-    const DitherArg d = dither_of(io);
-    launch_pcm16_encode_rescaled(n_buffers, src, dst, n, first_frame, d.on, d.seed, acc_dev, (hipStream_t)hip_stream);
-    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
-    return UMX_OK;
+    return encode_device(ctx, "rescaled pcm16 encode", UMX_SAMPLE_S16, n_buffers, in_dev, n, first_frame, io, reinterpret_cast<void *const *>(out_dev),
+                         true, acc_dev, hip_stream);
 }
 
 int umx_hip_rescale_device(umx_hip_ctx *ctx, int n_buffers, float *const *bufs_dev, int n, const umx_levels_acc *acc_dev, void *hip_stream)

@@ -54,7 +54,7 @@ bool umx_hip_ctx::track_geometry(int length, int shift_offset, int stride, Track
 }
 
 // The grow-only device buffers of the whole-track drivers (declared in engine.hip): the accumulators and stagings (floats per frame), the
-// int16 side (a word per frame), the hop energies (doubles).
+// integer side (words: a frame's bytes rounded up), the hop energies (doubles).
 template <class T_> int umx_hip_ctx::grow_only(std::initializer_list<std::pair<T_ **, int>> bufs, size_t &cap, size_t units)
 {
     if (units <= cap)
@@ -78,44 +78,34 @@ int umx_hip_ctx::track_bufs_grow(TrackBufs &tb_, size_t frames)
     return grow_only<float>({{&tb_.in, 2}, {&tb_.out[0], 2}, {&tb_.out[1], 2}, {&tb_.out[2], 2}, {&tb_.out[3], 2}, {&tb_.sumw, 1}}, tb_.cap, frames);
 }
 
-// the integer side of an accumulator set for a job of `frames` frames at the caller's rate -- 4 B (int16) or 6 B
-// (packed 24-bit) a frame, counted in words: the staging of its upload, n_host outputs, each grow-only on its own
-static size_t int_side_words(int format, size_t frames) { return format == UMX_SAMPLE_S24 ? (3 * frames + 1) / 2 : frames; }
-int umx_hip_ctx::track_pcm16_grow(TrackBufs &tb_, const umx_sample_io &io, size_t frames, int n_host)
+// the integer side of an accumulator set for a job of `frames` frames at the caller's rate -- sample_frame_bytes of
+// the format a frame, rounded up to whole words: the staging of its upload, n_host outputs, each grow-only on its own
+int umx_hip_ctx::track_int_grow(TrackBufs &tb_, const umx_sample_io &io, size_t frames, int n_host)
 {
+    auto words = [&](int format) { return (sample_frame_bytes(format) * frames + 3) / 4; };
     if (io.in_format != UMX_SAMPLE_F32)
-        if (int rc = grow_only<uint32_t>({{&tb_.in16, 1}}, tb_.cap_in16, int_side_words(io.in_format, frames)))
+        if (int rc = grow_only<uint32_t>({{&tb_.in_int, 1}}, tb_.cap_in_int, words(io.in_format)))
             return rc;
     for (int t = 0; t < n_host && io.out_format != UMX_SAMPLE_F32; ++t)
-        if (int rc = grow_only<uint32_t>({{&tb_.out16[t], 1}}, tb_.cap_out16[t], int_side_words(io.out_format, frames)))
+        if (int rc = grow_only<uint32_t>({{&tb_.out_int[t], 1}}, tb_.cap_out_int[t], words(io.out_format)))
             return rc;
     return UMX_OK;
 }
 
 // `count` frames of the first n_host of `src` from frame src_start on -> the set's integer outputs from frame first_frame on, which is
-// their frame number in the caller's track (the k of the dither); the kernel is the output format's (packed 24-bit: at byte 6 x frame)
+// their frame number in the caller's track (the k of the dither), at byte frame_bytes x first_frame; the kernel is the output
+// format's (launch_encode).  acc: over the divisor of that record, counting what clamps into it (nullptr: the plain encode).
 void umx_hip_ctx::track_encode(const TrackBufs &tb_, const umx_sample_io &io, int n_host, float *const src[4], size_t src_start, int count,
-                               long long first_frame, hipStream_t st)
+                               long long first_frame, umx_levels_acc *acc, hipStream_t st)
 {
     const float2 *s[4] = {};
-    if (io.out_format == UMX_SAMPLE_S24)
-    {
-        uint8_t *d24[4] = {};
-        for (int t = 0; t < n_host; ++t)
-        {
-            s[t] = reinterpret_cast<const float2 *>(src[t]) + src_start;
-            d24[t] = reinterpret_cast<uint8_t *>(tb_.out16[t]) + 6 * (size_t)first_frame;
-        }
-        launch_pcm24_encode(n_host, s, d24, count, first_frame, io.dither != 0, io.dither_seed, st);
-        return;
-    }
-    uint32_t *d[4] = {};
+    uint8_t *d[4] = {};
     for (int t = 0; t < n_host; ++t)
     {
         s[t] = reinterpret_cast<const float2 *>(src[t]) + src_start;
-        d[t] = tb_.out16[t] + first_frame;
+        d[t] = reinterpret_cast<uint8_t *>(tb_.out_int[t]) + sample_frame_bytes(io.out_format) * (size_t)first_frame;
     }
-    launch_pcm16_encode(n_host, s, d, count, first_frame, io.dither != 0, io.dither_seed, st);
+    launch_encode(io.out_format, n_host, s, d, count, first_frame, io.dither != 0, io.dither_seed, acc, st);
 }
 
 // the set's record of what leaves (112 bytes, allocated once a job measures; the driver zeroes it with the accumulators)
@@ -136,7 +126,7 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
     const TrackBufs &tb_ = *j.acc;
     const umx_sample_io &io = j.opt.io;
     const int n_host = j.opt.n_host();
-    const bool s16 = io.out_format == UMX_SAMPLE_S16, s24 = io.out_format == UMX_SAMPLE_S24, rescale = j.opt.rescale();
+    const bool integer = io.out_format != UMX_SAMPLE_F32, rescale = j.opt.rescale();
     if (j.opt.loudness)
     {
         const int hop = kweight_hop(j.loud_rate);
@@ -152,32 +142,19 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
     }
     if (!j.opt.measures())
     {
-        if (s16 || s24)
-            track_encode(tb_, io, n_host, src, src_start, count, first_frame, st);
+        if (integer)
+            track_encode(tb_, io, n_host, src, src_start, count, first_frame, nullptr, st);
         return;
     }
     const float2 *s[4] = {};
     float2 *sw[4] = {};
-    uint32_t *d[4] = {};
-    uint8_t *d24[4] = {};
     for (int t = 0; t < n_host; ++t)
-    {
         s[t] = sw[t] = reinterpret_cast<float2 *>(src[t]) + src_start;
-        d[t] = s16 ? tb_.out16[t] + first_frame : nullptr;
-        d24[t] = s24 ? reinterpret_cast<uint8_t *>(tb_.out16[t]) + 6 * (size_t)first_frame : nullptr;
-    }
     // (a rescaled integer track: its encode counts what it clamps itself, with the divisor it forms)
     launch_stem_levels(n_host, s, count, first_frame, rescale ? UMX_SAMPLE_F32 : io.out_format, io.dither != 0, io.dither_seed, tb_.lev, st);
-    if (!rescale)
-    {
-        if (s16 || s24)
-            track_encode(tb_, io, n_host, src, src_start, count, first_frame, st);
-    }
-    else if (s16)
-        launch_pcm16_encode_rescaled(n_host, s, d, count, first_frame, io.dither != 0, io.dither_seed, tb_.lev, st);
-    else if (s24)
-        launch_pcm24_encode_rescaled(n_host, s, d24, count, first_frame, io.dither != 0, io.dither_seed, tb_.lev, st);
-    else
+    if (integer)
+        track_encode(tb_, io, n_host, src, src_start, count, first_frame, rescale ? tb_.lev : nullptr, st);
+    else if (rescale)
         launch_stem_rescale(n_host, sw, count, tb_.lev, st);
 }
 
@@ -243,7 +220,7 @@ int umx_hip_ctx::admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt,
         if (int rc = grow_only<float>({{&acc.rs.in, 2}, {&acc.rs.out[0], 2}, {&acc.rs.out[1], 2}, {&acc.rs.out[2], 2}, {&acc.rs.out[3], 2}}, acc.rs.cap,
                                       (size_t)j.rs.length))
             return rc;
-    if (int rc = track_pcm16_grow(acc, opt.io, (size_t)length_at_rate, opt.n_host())) // (nothing for an fp32 call)
+    if (int rc = track_int_grow(acc, opt.io, (size_t)length_at_rate, opt.n_host())) // (nothing for an fp32 call)
         return rc;
     if (opt.measures())
         if (int rc = track_levels_grow(acc))
@@ -285,9 +262,9 @@ hipError_t umx_hip_ctx::track_loudness_report(const TrackJob &j, int n_host, std
 // from its previous job: that work has long finished.)
 hipError_t umx_hip_ctx::track_upload_until(TrackJob &j, long long padded_end, hipStream_t st)
 {
-    const bool s16 = j.opt.io.in_format == UMX_SAMPLE_S16, s24 = j.opt.io.in_format == UMX_SAMPLE_S24;
+    const bool integer = j.opt.io.in_format != UMX_SAMPLE_F32;
     TrackBufs &tb_ = *j.acc;
-    if ((s16 || s24 || j.rs.rate) && tb_.in_ev)
+    if ((integer || j.rs.rate) && tb_.in_ev)
         if (hipError_t e = hipStreamWaitEvent(st, tb_.in_ev, 0))
             return e;
     // what is wanted of the track as the segments see it, and what that needs of the host's frames
@@ -305,20 +282,17 @@ hipError_t umx_hip_ctx::track_upload_until(TrackJob &j, long long padded_end, hi
     {
         const size_t from = (size_t)j.uploaded, count = (size_t)(host_want - j.uploaded);
         float *const dst = j.rs.rate ? tb_.rs.in + 2 * from : tb_.in + 2 * ((size_t)j.lead + from); // where host frame `from` goes as fp32
-        if (s16 || s24)
+        if (integer)
         {
             // (the staging holds the host's bytes at their own offsets: 4 or 6 x frame)
             const size_t fb = sample_frame_bytes(j.opt.io.in_format);
-            uint8_t *const stage = reinterpret_cast<uint8_t *>(tb_.in16) + fb * from;
+            uint8_t *const stage = reinterpret_cast<uint8_t *>(tb_.in_int) + fb * from;
             e = hipMemcpy(stage, reinterpret_cast<const uint8_t *>(j.audio) + fb * from, fb * count, hipMemcpyHostToDevice);
             if (e == hipSuccess && !tb_.in_ev)
                 e = hipEventCreateWithFlags(&tb_.in_ev, hipEventDisableTiming);
             if (e == hipSuccess)
             {
-                if (s24)
-                    launch_pcm24_decode(stage, reinterpret_cast<float2 *>(dst), (int)count, st);
-                else
-                    launch_pcm16_decode(tb_.in16 + from, reinterpret_cast<float2 *>(dst), (int)count, st);
+                launch_decode(j.opt.io.in_format, stage, reinterpret_cast<float2 *>(dst), (int)count, st);
                 e = hipEventRecord(tb_.in_ev, st);
             }
         }
@@ -374,7 +348,7 @@ hipError_t umx_hip_ctx::track_region_download(const TrackRegion &r, float *const
         if (j.opt.io.out_format != UMX_SAMPLE_F32) // (encoded behind the region's normalisation and mix, at its frame number: track_call)
         {
             const size_t fb = sample_frame_bytes(j.opt.io.out_format); // 4 or 6 x frame on both sides
-            cerr = hipMemcpy(reinterpret_cast<uint8_t *>(out_host[t]) + fb * first, reinterpret_cast<const uint8_t *>(j.acc->out16[t]) + fb * first,
+            cerr = hipMemcpy(reinterpret_cast<uint8_t *>(out_host[t]) + fb * first, reinterpret_cast<const uint8_t *>(j.acc->out_int[t]) + fb * first,
                              fb * count, hipMemcpyDeviceToHost);
         }
         else if (j.rs.rate)
@@ -703,7 +677,7 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         {
             track_leave(j, whole[ln], 0, length_in[ln], 0, last_st);
             for (int t = 0; t < n_host && opt.io.out_format != UMX_SAMPLE_F32; ++t)
-                whole[ln][t] = reinterpret_cast<float *>(j.acc->out16[t]);
+                whole[ln][t] = reinterpret_cast<float *>(j.acc->out_int[t]);
         }
         any_whole = true;
     };

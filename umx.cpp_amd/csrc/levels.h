@@ -3,7 +3,7 @@
 // host entry points (umx_hip_levels_host, umx_hip_rescale_gain) and for the kernels below:
 //   peak        the unsigned maximum of the bit patterns of |x| over the samples that are not NaN (+inf counts), 0 when there is none
 //   over_unity  samples with |x| > 1.0f; nonfinite: NaN or +-inf
-//   clipped     integer outputs only: samples whose rounded value r of the output format's encode rule (pcm16_round / pcm24_round,
+//   clipped     integer outputs only: samples whose rounded value r of the output format's encode rule (the trait's round,
 //               with its dither, on x / g when a divisor applies) lies outside the format's codes: > 32767.f or < -32768.f for
 //               int16, > 8388607 or < -8388608 for packed 24-bit; +-inf counts, NaN does not
 //   rescale     P = max peak over the outputs that leave, g = 1.01f * P (one fp32 product); P not finite or !(g > 1.0f): divisor 1,
@@ -48,17 +48,6 @@ __host__ __device__ inline bool levels_is_nonfinite(uint32_t abs_bits) { return 
 __host__ __device__ inline bool levels_is_over_unity(uint32_t abs_bits) { return abs_bits > LEVELS_ONE_BITS && abs_bits <= LEVELS_INF_BITS; }
 // what a sample contributes to the peak (a NaN: nothing)
 __host__ __device__ inline uint32_t levels_peak_term(uint32_t abs_bits) { return levels_is_nan(abs_bits) ? 0u : abs_bits; }
-// did the clamp of the encode rule change the rounded value r (a NaN r: no)
-__host__ __device__ inline bool levels_is_clipped(float r) { return r > 32767.f || r < -32768.f; }
-// the same question of sample x as it leaves in clip_format (UMX_SAMPLE_S16 or UMX_SAMPLE_S24; an fp32 output: never)
-__host__ __device__ inline bool levels_clips(float x, int clip_format, bool dither, uint32_t key, long long k)
-{
-    if (clip_format == UMX_SAMPLE_S16)
-        return levels_is_clipped(pcm16_round(x, dither, key, k));
-    if (clip_format == UMX_SAMPLE_S24)
-        return pcm24_is_clipped(pcm24_round(x, dither, key, k));
-    return false;
-}
 
 // the divisor of a track whose largest peak has the bit pattern peak_bits (the maximum of the record's peak words); 1: none
 __host__ __device__ inline float levels_divisor(uint32_t peak_bits)
@@ -75,25 +64,7 @@ __host__ __device__ inline float levels_divisor(const umx_levels_acc &acc)
         p = acc.peak_bits[m] > p ? acc.peak_bits[m] : p;
     return levels_divisor(p);
 }
-// x over a divisor g > 1 (levels_divisor's other answer, 1, divides nothing: the callers test for it)
-__host__ __device__ inline float levels_rescaled(float x, float g)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fdiv_rn(x, g);
-#else
-    return x / g;
-#endif
-}
-
-// src[b] from the first frame on; b = the output's index in the call's `out` list, nullptr: none
-struct LevelsArgs
-{
-    const float2 *src[4];
-    uint32_t key[4][2]; // pcm16_dither_key of (seed, b, channel)
-    long long first_frame;
-    int dither;
-    int clip_format; // UMX_SAMPLE_S16 / UMX_SAMPLE_S24: the outputs leave through that format's plain encode, count what it clamps; else nothing
-};
+// (x over that divisor: sample_rescaled; whether a format's clamp changes a sample: sample_clips -- both in sample_format.h)
 
 #define LEVELS_THREADS 256
 #define LEVELS_WAVES (LEVELS_THREADS / 64)
@@ -128,7 +99,7 @@ template <int NV, int NMAX> __device__ inline uint32_t levels_block_reduce(uint3
 
 // n frames of up to four buffers, one frame per thread, grid-strided: frame i of buffer b is frame first_frame + i of the caller's
 // track.  8 B read per frame and buffer; per workgroup one atomic per quantity and buffer that has something to add.
-__global__ __launch_bounds__(LEVELS_THREADS) void stem_levels_kernel(LevelsArgs a, int n, umx_levels_acc *acc)
+__global__ __launch_bounds__(LEVELS_THREADS) void stem_levels_kernel(EncodeArgs a, int clip_format, int n, umx_levels_acc *acc)
 {
     __shared__ uint32_t red[LEVELS_WAVES * 16];
     uint32_t v[16] = {}; // [quantity: peak, over_unity, clipped, nonfinite][buffer]
@@ -149,10 +120,7 @@ __global__ __launch_bounds__(LEVELS_THREADS) void stem_levels_kernel(LevelsArgs 
                     const uint32_t p = levels_peak_term(u);
                     v[b] = p > v[b] ? p : v[b];
                     v[4 + b] += levels_is_over_unity(u) ? 1u : 0u;
-                    if (a.clip_format == UMX_SAMPLE_S16)
-                        v[8 + b] += levels_is_clipped(pcm16_round(xs[ch], a.dither != 0, a.key[b][ch], k)) ? 1u : 0u;
-                    else if (a.clip_format == UMX_SAMPLE_S24)
-                        v[8 + b] += pcm24_is_clipped(pcm24_round(xs[ch], a.dither != 0, a.key[b][ch], k)) ? 1u : 0u;
+                    v[8 + b] += sample_clips(xs[ch], clip_format, a.dither != 0, a.key[b][ch], k) ? 1u : 0u;
                     v[12 + b] += levels_is_nonfinite(u) ? 1u : 0u;
                 }
             }
@@ -168,49 +136,21 @@ __global__ __launch_bounds__(LEVELS_THREADS) void stem_levels_kernel(LevelsArgs 
     }
 }
 
-// pcm16_encode_kernel on x / g, g formed here from the record's peak words (final in stream order: the measuring launches precede
-// this one).  Where the divisor is 1 these are the plain encode's bits, and only there a sample can clamp: those are counted into
-// the record's `clipped`, which the measuring launches of a rescaled track leave alone.
-__global__ __launch_bounds__(LEVELS_THREADS) void pcm16_encode_rescaled_kernel(Pcm16EncodeArgs a, int n, umx_levels_acc *acc)
+// The encode of format T (its memory shape: encode_frames of pcm16.h / pcm24.h), plain ...
+template <class T> __global__ __launch_bounds__(LEVELS_THREADS) void encode_kernel(EncodeArgs a, int n)
 {
-    __shared__ uint32_t red[LEVELS_WAVES * 4];
-    const float g = levels_divisor(*acc);
-    const bool divide = g != 1.0f;
-    uint32_t v[4] = {};
-    const size_t step = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)n; i += step)
-    {
-        const long long k = a.first_frame + (long long)i;
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-            if (a.dst[b])
-            {
-                float2 x = a.src[b][i];
-                if (divide)
-                    x = make_float2(levels_rescaled(x.x, g), levels_rescaled(x.y, g));
-                v[b] += (levels_is_clipped(pcm16_round(x.x, a.dither != 0, a.key[b][0], k)) ? 1u : 0u) +
-                        (levels_is_clipped(pcm16_round(x.y, a.dither != 0, a.key[b][1], k)) ? 1u : 0u);
-                a.dst[b][i] = pcm16_frame(pcm16_encode(x.x, a.dither != 0, a.key[b][0], k), pcm16_encode(x.y, a.dither != 0, a.key[b][1], k));
-            }
-    }
-    const uint32_t total = levels_block_reduce<4, 0>(v, red);
-    if (threadIdx.x < 4 && total != 0)
-        atomicAdd(&acc->clipped[threadIdx.x], (unsigned long long)total);
+    uint32_t unused[4] = {};
+    encode_frames<false>(T(), a, n, Plain(), unused);
 }
-
-// pcm24_encode_kernel (pcm24.h) on x / g, the twin of the kernel above: the same divisor, the same count of what it clamps
-struct Pcm24Rescaled
-{
-    float g;
-    bool divide;
-    __device__ float operator()(float x) const { return divide ? levels_rescaled(x, g) : x; }
-};
-__global__ __launch_bounds__(LEVELS_THREADS) void pcm24_encode_rescaled_kernel(Pcm24EncodeArgs a, int n, umx_levels_acc *acc)
+// ... and on x / g, g formed here from the record's peak words (final in stream order: the measuring launches precede this one).
+// Where the divisor is 1 these are the plain encode's bits, and only there a sample can clamp: those are counted into the record's
+// `clipped`, which the measuring launches of a rescaled track leave alone.
+template <class T> __global__ __launch_bounds__(LEVELS_THREADS) void encode_rescaled_kernel(EncodeArgs a, int n, umx_levels_acc *acc)
 {
     __shared__ uint32_t red[LEVELS_WAVES * 4];
     const float g = levels_divisor(*acc);
     uint32_t v[4] = {};
-    pcm24_encode_frames<true>(a, n, Pcm24Rescaled{g, g != 1.0f}, v);
+    encode_frames<true>(T(), a, n, Rescaled{g, g != 1.0f}, v);
     const uint32_t total = levels_block_reduce<4, 0>(v, red);
     if (threadIdx.x < 4 && total != 0)
         atomicAdd(&acc->clipped[threadIdx.x], (unsigned long long)total);
@@ -234,7 +174,7 @@ __global__ __launch_bounds__(LEVELS_THREADS) void stem_rescale_kernel(RescaleBuf
             if (a.p[b])
             {
                 const float2 x = a.p[b][i];
-                a.p[b][i] = make_float2(levels_rescaled(x.x, g), levels_rescaled(x.y, g));
+                a.p[b][i] = make_float2(sample_rescaled(x.x, g), sample_rescaled(x.y, g));
             }
 }
 
@@ -247,44 +187,32 @@ inline void launch_stem_levels(int nb, const float2 *const *src, int n, long lon
 {
     if (n < 1 || nb < 1)
         return;
-    LevelsArgs a = {};
-    for (int b = 0; b < nb && b < 4; ++b)
-    {
-        a.src[b] = src[b];
-        a.key[b][0] = pcm16_dither_key(seed, b, 0);
-        a.key[b][1] = pcm16_dither_key(seed, b, 1);
-    }
-    a.first_frame = first_frame;
-    a.dither = dither ? 1 : 0;
-    a.clip_format = clip_format;
-    hipLaunchKernelGGL(stem_levels_kernel, dim3(levels_blocks(n)), dim3(LEVELS_THREADS), 0, st, a, n, acc);
+    hipLaunchKernelGGL(stem_levels_kernel, dim3(levels_blocks(n)), dim3(LEVELS_THREADS), 0, st,
+                       encode_args(nb, src, nullptr, first_frame, dither, seed), clip_format, n, acc);
 }
 
-inline void launch_pcm16_encode_rescaled(int nb, const float2 *const *src, uint32_t *const *dst, int n, long long first_frame, bool dither,
-                                         uint32_t seed, umx_levels_acc *acc, hipStream_t st)
+// the same buffers into dst (byte addresses) as `format` encodes them; acc: over the divisor of that record, counting into it
+// (nullptr: the plain encode).  An fp32 format: nothing.
+inline void launch_encode(int format, int nb, const float2 *const *src, uint8_t *const *dst, int n, long long first_frame, bool dither,
+                          uint32_t seed, umx_levels_acc *acc, hipStream_t st)
 {
     if (n < 1 || nb < 1)
         return;
-    Pcm16EncodeArgs a = {};
-    for (int b = 0; b < nb && b < 4; ++b)
-    {
-        a.src[b] = src[b];
-        a.dst[b] = dst[b];
-        a.key[b][0] = pcm16_dither_key(seed, b, 0);
-        a.key[b][1] = pcm16_dither_key(seed, b, 1);
-    }
-    a.first_frame = first_frame;
-    a.dither = dither ? 1 : 0;
-    hipLaunchKernelGGL(pcm16_encode_rescaled_kernel, dim3(pcm16_blocks(n)), dim3(LEVELS_THREADS), 0, st, a, n, acc);
+    const EncodeArgs a = encode_args(nb, src, dst, first_frame, dither, seed);
+    with_sample_format(format, [&](auto t) {
+        using T = decltype(t);
+        if (acc)
+            hipLaunchKernelGGL(encode_rescaled_kernel<T>, dim3(encode_blocks(t, n)), dim3(LEVELS_THREADS), 0, st, a, n, acc);
+        else
+            hipLaunchKernelGGL(encode_kernel<T>, dim3(encode_blocks(t, n)), dim3(LEVELS_THREADS), 0, st, a, n);
+    });
 }
 
-inline void launch_pcm24_encode_rescaled(int nb, const float2 *const *src, uint8_t *const *dst, int n, long long first_frame, bool dither,
-                                         uint32_t seed, umx_levels_acc *acc, hipStream_t st)
+// n frames of `format` at `in` -> out[0 .. n)
+inline void launch_decode(int format, const void *in, float2 *out, int n, hipStream_t st)
 {
-    if (n < 1 || nb < 1)
-        return;
-    hipLaunchKernelGGL(pcm24_encode_rescaled_kernel, dim3(pcm24_blocks(n)), dim3(LEVELS_THREADS), 0, st,
-                       pcm24_encode_args(nb, src, dst, first_frame, dither, seed), n, acc);
+    if (n >= 1)
+        with_sample_format(format, [&](auto t) { launch_decode_as(t, in, out, n, st); });
 }
 
 inline void launch_stem_rescale(int nb, float2 *const *bufs, int n, const umx_levels_acc *acc, hipStream_t st)
@@ -301,7 +229,7 @@ inline void launch_stem_rescale(int nb, float2 *const *bufs, int n, const umx_le
 inline void levels_host(const float *x, int n_frames, int buffer, long long first_frame, int clip_format, bool dither, uint32_t seed,
                         float divisor, umx_levels_acc &acc)
 {
-    const uint32_t key[2] = {pcm16_dither_key(seed, buffer, 0), pcm16_dither_key(seed, buffer, 1)};
+    const uint32_t key[2] = {sample_dither_key(seed, buffer, 0), sample_dither_key(seed, buffer, 1)};
     for (int i = 0; i < n_frames; ++i)
         for (int ch = 0; ch < 2; ++ch)
         {
@@ -310,7 +238,7 @@ inline void levels_host(const float *x, int n_frames, int buffer, long long firs
             acc.peak_bits[buffer] = p > acc.peak_bits[buffer] ? p : acc.peak_bits[buffer];
             acc.over_unity[buffer] += levels_is_over_unity(u) ? 1 : 0;
             acc.nonfinite[buffer] += levels_is_nonfinite(u) ? 1 : 0;
-            acc.clipped[buffer] += levels_clips(divisor != 1.0f ? levels_rescaled(s, divisor) : s, clip_format, dither, key[ch], first_frame + i) ? 1 : 0;
+            acc.clipped[buffer] += sample_clips(divisor != 1.0f ? sample_rescaled(s, divisor) : s, clip_format, dither, key[ch], first_frame + i) ? 1 : 0;
         }
 }
 

@@ -1,13 +1,14 @@
 // pcm24.h -- packed 24-bit PCM at the edges of the whole-track drivers: 6 B per stereo frame cross PCIe, as a WAV data
-// chunk holds them (3 bytes per sample, little-endian, two's complement, L then R).  One statement of each rule, for the host entry
-// points (umx_hip_pcm24_decode_host / _encode_host, umx_hip_levels_host) and for the kernels below and in levels.h:
+// chunk holds them (3 bytes per sample, little-endian, two's complement, L then R).  One statement of each rule (sample_format.h:
+// SampleS24 and the dither), for the host entry points (umx_hip_pcm24_decode_host / _encode_host, umx_hip_levels_host) and for the
+// kernels below and in levels.h:
 //   decode   x = (float)q * 2^-23: exact, and the float WAV loader's q / 8388608.f (host/wav.cpp), so a packed upload gives the
 //            bits the float loader gives
 //   encode   v = x * 8388608.0f (exact short of overflow); r = rint((double)v + (dither ? (double)d : 0.0)), the sum formed in double
 //            and rounded once (an fp32 v + d falls on a 0.5 grid at |v| >= 2^22, before the rounding); q = NaN ? 0 :
 //            clamp(r, -8388608, 8388607).  +1.0f encodes to 8388607 and counts as clipped: the loader's scale is 2^23.
-//   dither   pcm16.h's d, with its keys (seed, m, ch) and the frame k of the CALLER's track: in (-1, 1) LSB of the 24-bit grid
-// A frame is 6 bytes, so a frame per thread would mean byte-wide or misaligned stores.  The smallest unit that is word-aligned on
+//   dither   sample_format.h's d, with its keys (seed, m, ch) and the frame k of the CALLER's track: in (-1, 1) LSB of the 24-bit grid
+// This file is the format's MEMORY SHAPE.  A frame is 6 bytes, so a frame per thread would mean byte-wide or misaligned stores.  The smallest unit that is word-aligned on
 // both sides is a PAIR of frames: 16 B of fp32, 12 B packed (3 dwords).  The body of every kernel runs on such pairs, one per lane,
 // lane-contiguous (a wave moves 1 KiB of fp32 and 768 B packed per instruction); a packed address that is 2 mod 4 -- every region
 // that starts at an odd frame of its track -- has one head frame before the first pair, and one tail frame may follow the last.
@@ -16,32 +17,12 @@
 // fp32 pointer its frame's 8 (the 16-byte fp32 accesses are issued on 8-byte aligned addresses, which global memory takes).
 #pragma once
 #include "common.h"
-#include "pcm16.h"
+#include "sample_format.h"
 
 namespace umx
 {
 
-__host__ __device__ inline float pcm24_decode(int32_t q) { return (float)q * (1.0f / 8388608.0f); }
-
-// the encode rule up to and including its rounding: r, before the NaN test and the clamp (levels.h counts the clamped samples from it)
-__host__ __device__ inline double pcm24_round(float x, bool dither, uint32_t key, long long k)
-{
-    const float v = x * 8388608.0f;
-    double s = (double)v;
-    if (dither)
-        s = s + (double)pcm16_dither(pcm16_dither_word(key, k));
-    return rint(s);
-}
-// did the clamp of the encode rule change the rounded value r (a NaN r: no)
-__host__ __device__ inline bool pcm24_is_clipped(double r) { return r > 8388607.0 || r < -8388608.0; }
-
-__host__ __device__ inline int32_t pcm24_clamp(double r)
-{
-    if (r != r)
-        return 0;
-    return (int32_t)(r < -8388608.0 ? -8388608.0 : r > 8388607.0 ? 8388607.0 : r);
-}
-__host__ __device__ inline int32_t pcm24_encode(float x, bool dither, uint32_t key, long long k) { return pcm24_clamp(pcm24_round(x, dither, key, k)); }
+__host__ __device__ inline float pcm24_decode(int32_t q) { return SampleS24::decode(q); }
 
 // one sample <-> its 3 bytes (the host entry points; the kernels move whole pairs of frames and 16-bit pieces)
 __host__ __device__ inline int32_t pcm24_load(const uint8_t *p)
@@ -54,6 +35,9 @@ __host__ __device__ inline void pcm24_store(uint8_t *p, int32_t q)
     p[1] = (uint8_t)((uint32_t)q >> 8);
     p[2] = (uint8_t)((uint32_t)q >> 16);
 }
+// sample i of a host buffer of the format (the host entry points)
+inline float load_sample(SampleS24, const void *q, size_t i) { return SampleS24::decode(pcm24_load(static_cast<const uint8_t *>(q) + 3 * i)); }
+inline void store_sample(SampleS24, void *q, size_t i, int32_t v) { pcm24_store(static_cast<uint8_t *>(q) + 3 * i, v); }
 
 // two frames as the three words that hold them, and one frame as its three 16-bit pieces
 struct Pcm24Pair
@@ -114,33 +98,13 @@ __global__ void pcm24_decode_kernel(const uint8_t *__restrict__ in, float2 *__re
         out[n - 1] = pcm24_load_frame(reinterpret_cast<const uint16_t *>(in + 6 * (size_t)(n - 1)));
 }
 
-// src[b] / dst[b] from the first frame on; b = the output's index in the call's `out` list (the m of the dither), nullptr: none
-struct Pcm24EncodeArgs
-{
-    const float2 *src[4];
-    uint8_t *dst[4];
-    uint32_t key[4][2]; // pcm16_dither_key of (seed, b, channel)
-    long long first_frame;
-    int dither;
-};
-
-struct Pcm24Plain // what a sample goes through before the encode rule: nothing (levels.h: the track's divisor)
-{
-    __device__ float operator()(float x) const { return x; }
-};
-
 // n frames of up to four buffers: frame i of buffer b is frame first_frame + i of the caller's track, `pre` is applied to every sample
 // first.  COUNT: clip[b] += the samples of buffer b that the clamp changed.  Every buffer has its own head (its own address).
-template <bool COUNT, class Pre> __device__ inline void pcm24_encode_frames(const Pcm24EncodeArgs &a, int n, const Pre &pre, uint32_t (&clip)[4])
+template <bool COUNT, class Pre> __device__ inline void encode_frames(SampleS24, const EncodeArgs &a, int n, const Pre &pre, uint32_t (&clip)[4])
 {
     const bool dither = a.dither != 0;
     const size_t step = (size_t)gridDim.x * blockDim.x, first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    auto code = [&](float x, int b, int ch, long long k) {
-        const double r = pcm24_round(pre(x), dither, a.key[b][ch], k);
-        if (COUNT)
-            clip[b] += pcm24_is_clipped(r) ? 1u : 0u;
-        return pcm24_clamp(r);
-    };
+    auto code = [&](float x, int b, int ch, long long k) { return encode_sample<SampleS24, COUNT>(x, pre, dither, a.key[b][ch], k, clip[b]); };
 #pragma unroll
     for (int b = 0; b < 4; ++b)
         if (a.dst[b])
@@ -166,59 +130,13 @@ template <bool COUNT, class Pre> __device__ inline void pcm24_encode_frames(cons
         }
 }
 
-__global__ __launch_bounds__(256) void pcm24_encode_kernel(Pcm24EncodeArgs a, int n)
-{
-    uint32_t unused[4] = {};
-    pcm24_encode_frames<false>(a, n, Pcm24Plain(), unused);
-}
-
 // (a thread per pair of frames; at least two threads: the head's and the tail's)
 inline int pcm24_blocks(int n) { return std::max(1, std::min((n / 2 + 255) / 256, 2048)); }
+inline int encode_blocks(SampleS24, int n) { return pcm24_blocks(n); }
 
-inline void launch_pcm24_decode(const uint8_t *in, float2 *out, int n, hipStream_t st)
+inline void launch_decode_as(SampleS24, const void *in, float2 *out, int n, hipStream_t st)
 {
-    if (n >= 1)
-        hipLaunchKernelGGL(pcm24_decode_kernel, dim3(pcm24_blocks(n)), dim3(256), 0, st, in, out, n);
-}
-
-inline Pcm24EncodeArgs pcm24_encode_args(int nb, const float2 *const *src, uint8_t *const *dst, long long first_frame, bool dither, uint32_t seed)
-{
-    Pcm24EncodeArgs a = {};
-    for (int b = 0; b < nb && b < 4; ++b)
-    {
-        a.src[b] = src[b];
-        a.dst[b] = dst[b];
-        a.key[b][0] = pcm16_dither_key(seed, b, 0);
-        a.key[b][1] = pcm16_dither_key(seed, b, 1);
-    }
-    a.first_frame = first_frame;
-    a.dither = dither ? 1 : 0;
-    return a;
-}
-
-// buffers 0 .. nb-1 of a call's `out` list, n frames from frame first_frame of the caller's track on
-inline void launch_pcm24_encode(int nb, const float2 *const *src, uint8_t *const *dst, int n, long long first_frame, bool dither,
-                                uint32_t seed, hipStream_t st)
-{
-    if (n < 1 || nb < 1)
-        return;
-    hipLaunchKernelGGL(pcm24_encode_kernel, dim3(pcm24_blocks(n)), dim3(256), 0, st, pcm24_encode_args(nb, src, dst, first_frame, dither, seed), n);
-}
-
-// bytes of a stereo frame of a host or integer-side buffer in a format
-inline size_t sample_frame_bytes(int format) { return format == UMX_SAMPLE_S24 ? 6 : format == UMX_SAMPLE_S16 ? 4 : 8; }
-inline bool sample_format_known(int f) { return f == UMX_SAMPLE_F32 || f == UMX_SAMPLE_S16 || f == UMX_SAMPLE_S24; }
-
-// what an entry point refuses (nullptr: fine): io == nullptr is the fp32 call
-inline const char *sample_io_refusal(const umx_sample_io *io)
-{
-    if (!io)
-        return nullptr;
-    if (!sample_format_known(io->in_format) || !sample_format_known(io->out_format))
-        return "sample io: unknown sample format (UMX_SAMPLE_F32, UMX_SAMPLE_S16 or UMX_SAMPLE_S24)";
-    if (io->dither && io->out_format == UMX_SAMPLE_F32)
-        return "sample io: dither goes with a UMX_SAMPLE_S16 or UMX_SAMPLE_S24 output only";
-    return nullptr;
+    hipLaunchKernelGGL(pcm24_decode_kernel, dim3(pcm24_blocks(n)), dim3(256), 0, st, static_cast<const uint8_t *>(in), out, n);
 }
 
 } // namespace umx

@@ -23,6 +23,7 @@
 #include "../../include/umx_host.h"
 #include "clip_env.h"
 #include "mix_env.h"
+#include "pcm_env.h"
 #include "shifts_env.h"
 #include "targets_env.h"
 
@@ -42,19 +43,6 @@ static int env_int(const char *name, int dflt)
 {
     const char *v = getenv(name);
     return v && *v ? atoi(v) : dflt;
-}
-
-// int16 units of an integer output frame (4 bytes of int16, 6 bytes of packed 24-bit PCM); 0 for fp32
-static size_t int_units(int format) { return format == UMX_SAMPLE_S24 ? 3 : format == UMX_SAMPLE_S16 ? 2 : 0; }
-// a file of the run's integer input format as it is, behind an int16 pointer (free: umx_wav_free_pcm16)
-static int load_int(int format, const char *path, int16_t **audio, int *n, int *ch, int *rate, char *err)
-{
-    if (format != UMX_SAMPLE_S24)
-        return umx_wav_load_pcm16(path, audio, n, ch, rate, err);
-    unsigned char *p = nullptr;
-    const int rc = umx_wav_load_pcm24(path, &p, n, ch, rate, err);
-    *audio = reinterpret_cast<int16_t *>(p);
-    return rc;
 }
 
 // The track queue's two ends.  A decoded file waits in `decoded` until a lane takes it (next); its stems wait in `unwritten` from the
@@ -183,51 +171,31 @@ int main(int argc, const char **argv)
         return 1;
     }
     const int per_file = mixed ? mixc.n_out : 4; // buffers of a file
-    const bool pcm16 = env_int("UMX_PCM16", 0) != 0;
-    if (!pcm16 && getenv("UMX_PCM16_DITHER"))
-    {
-        fprintf(stderr, "UMX_PCM16_DITHER: needs UMX_PCM16=1\n");
+    umx_pcm_choice pcmc;
+    if (!umx_pcm_from_env(pcmc, nullptr))
         return 1;
-    }
-    const bool pcm24 = env_int("UMX_PCM24", 0) != 0;
-    if (pcm24 && pcm16)
-    {
-        fprintf(stderr, "UMX_PCM24: does not go with UMX_PCM16=1 (one output format per run)\n");
-        return 1;
-    }
-    if (!pcm24 && getenv("UMX_PCM24_DITHER"))
-    {
-        fprintf(stderr, "UMX_PCM24_DITHER: needs UMX_PCM24=1\n");
-        return 1;
-    }
     umx_clip_choice clipc;
     if (!umx_clip_from_env(clipc, nullptr))
         return 1;
     const bool resample = env_int("UMX_RESAMPLE", 0) != 0;
-    umx_sample_io io = {UMX_SAMPLE_F32, pcm24 ? UMX_SAMPLE_S24 : pcm16 ? UMX_SAMPLE_S16 : UMX_SAMPLE_F32, 0, 0};
-    if (const char *seed = getenv(pcm24 ? "UMX_PCM24_DITHER" : "UMX_PCM16_DITHER"))
-    {
-        io.dither = 1;
-        io.dither_seed = (unsigned)strtoul(seed, nullptr, 0);
-    }
+    umx_sample_io io = pcmc.io;
     // one input format per run: packed 24-bit when every file's head says 24-bit PCM (UMX_PCM24 only), else int16 when every file's head
     // says 16-bit PCM, else fp32 (whatever is wrong with a file, the float loader reports it)
     auto every_file_is = [&](int bits) {
         for (int f = 0; f < nfiles; ++f)
         {
             int n = 0, ch = 0, rate = 0;
-            if (bits == 24 ? umx_wav_load_pcm24(argv[3 + f], nullptr, &n, &ch, resample ? &rate : nullptr, err)
-                           : umx_wav_load_pcm16(argv[3 + f], nullptr, &n, &ch, resample ? &rate : nullptr, err))
+            if (load_int(bits == 24 ? UMX_SAMPLE_S24 : UMX_SAMPLE_S16, argv[3 + f], nullptr, &n, &ch, resample ? &rate : nullptr, err))
                 return false;
         }
         return true;
     };
-    if (pcm24 && every_file_is(24))
+    if (pcmc.pcm24 && every_file_is(24))
         io.in_format = UMX_SAMPLE_S24;
-    else if ((pcm16 || pcm24) && every_file_is(16))
+    else if (pcmc.active() && every_file_is(16))
         io.in_format = UMX_SAMPLE_S16;
     const bool in16 = io.in_format != UMX_SAMPLE_F32; // (the files go up as they are: int16, or packed 24-bit)
-    const bool int_out = pcm16 || pcm24;
+    const bool int_out = pcmc.active();
     umx_model *model = nullptr;
     if (umx_model_load(model_file.c_str(), &model, err)) // umx.cpp:63-70
     {
@@ -278,8 +246,7 @@ int main(int argc, const char **argv)
             if (!mixed && !choice.write[t]) // a target that did not run (UMX_TARGETS): a silent slot
                 continue;
             const std::string p = (dir / (mixed ? mixc.name[t] + ".wav" : choice.file[t])).string();
-            if (pcm24   ? umx_wav_write_pcm24_rate(p.c_str(), reinterpret_cast<const unsigned char *>(bufs16[t]), n, rate_, err_)
-                : pcm16 ? umx_wav_write_pcm16_rate(p.c_str(), bufs16[t], n, rate_, err_)
+            if (int_out    ? write_int(io.out_format, p.c_str(), bufs16[t], n, rate_, err_)
                 : resample ? umx_wav_write_f32_rate(p.c_str(), bufs[t], n, rate_, err_)
                            : umx_wav_write_f32(p.c_str(), bufs[t], n, err_))
                 return false;

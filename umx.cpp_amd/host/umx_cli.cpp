@@ -36,6 +36,7 @@
 #include "../../include/umx_host.h"
 #include "clip_env.h"
 #include "mix_env.h"
+#include "pcm_env.h"
 #include "shifts_env.h"
 #include "targets_env.h"
 
@@ -109,33 +110,11 @@ int main(int argc, const char **argv)
         fprintf(stderr, "UMX_MIX: source \"%s\" does not run (UMX_TARGETS) and is not the residual's slot\n", umx_mix_silent_source(mixc, choice.write));
         return 1;
     }
-    const bool pcm16 = env_int("UMX_PCM16", 0) != 0;
-    if (pcm16 && (shifts > 1 || env_int("UMX_CLI_PER_SEGMENT", 0)))
-    {
-        fprintf(stderr, "UMX_PCM16: the shift ensemble (UMX_SHIFTS > 1) and UMX_CLI_PER_SEGMENT=1 do not offer 16-bit PCM transfers\n");
+    umx_pcm_choice pcmc;
+    if (!umx_pcm_from_env(pcmc, shifts > 1 || env_int("UMX_CLI_PER_SEGMENT", 0)
+                                    ? "the shift ensemble (UMX_SHIFTS > 1) and UMX_CLI_PER_SEGMENT=1 do not offer"
+                                    : nullptr))
         return 1;
-    }
-    if (!pcm16 && getenv("UMX_PCM16_DITHER"))
-    {
-        fprintf(stderr, "UMX_PCM16_DITHER: needs UMX_PCM16=1\n");
-        return 1;
-    }
-    const bool pcm24 = env_int("UMX_PCM24", 0) != 0;
-    if (pcm24 && pcm16)
-    {
-        fprintf(stderr, "UMX_PCM24: does not go with UMX_PCM16=1 (one output format per run)\n");
-        return 1;
-    }
-    if (pcm24 && (shifts > 1 || env_int("UMX_CLI_PER_SEGMENT", 0)))
-    {
-        fprintf(stderr, "UMX_PCM24: the shift ensemble (UMX_SHIFTS > 1) and UMX_CLI_PER_SEGMENT=1 do not offer 24-bit PCM transfers\n");
-        return 1;
-    }
-    if (!pcm24 && getenv("UMX_PCM24_DITHER"))
-    {
-        fprintf(stderr, "UMX_PCM24_DITHER: needs UMX_PCM24=1\n");
-        return 1;
-    }
     umx_clip_choice clipc;
     if (!umx_clip_from_env(clipc, shifts > 1 || env_int("UMX_CLI_PER_SEGMENT", 0)
                                       ? "the shift ensemble (UMX_SHIFTS > 1) and UMX_CLI_PER_SEGMENT=1 do not offer levels or rescale"
@@ -143,22 +122,16 @@ int main(int argc, const char **argv)
         return 1;
     umx_levels levels = {};
     umx_loudness loudness = {};
-    umx_sample_io io = {UMX_SAMPLE_F32, pcm24 ? UMX_SAMPLE_S24 : pcm16 ? UMX_SAMPLE_S16 : UMX_SAMPLE_F32, 0, 0};
-    if (const char *seed = getenv(pcm24 ? "UMX_PCM24_DITHER" : "UMX_PCM16_DITHER"))
-    {
-        io.dither = 1;
-        io.dither_seed = (unsigned)strtoul(seed, nullptr, 0);
-    }
+    umx_sample_io io = pcmc.io;
     printf("umx-cli (MI355X / gfx950) main driver program\n");
 
     float *audio = nullptr;
-    int16_t *audio16 = nullptr;
-    unsigned char *audio24 = nullptr;
+    int16_t *audio_int = nullptr; // the file's samples as they are, in io.in_format (load_int)
     int n = 0, ch = 0, rate = UMX_SAMPLE_RATE;
     const bool resample = env_int("UMX_RESAMPLE", 0) != 0;
-    if (pcm24 && umx_wav_load_pcm24(wav_file.c_str(), &audio24, &n, &ch, resample ? &rate : nullptr, err) == UMX_OK)
+    if (pcmc.pcm24 && load_int(UMX_SAMPLE_S24, wav_file.c_str(), &audio_int, &n, &ch, resample ? &rate : nullptr, err) == UMX_OK)
         io.in_format = UMX_SAMPLE_S24;
-    else if ((pcm16 || pcm24) && umx_wav_load_pcm16(wav_file.c_str(), &audio16, &n, &ch, resample ? &rate : nullptr, err) == UMX_OK)
+    else if (pcmc.active() && load_int(UMX_SAMPLE_S16, wav_file.c_str(), &audio_int, &n, &ch, resample ? &rate : nullptr, err) == UMX_OK)
         io.in_format = UMX_SAMPLE_S16; // (any other encoding, and every other failure, is the float loader's to take or to report)
     else if (resample ? umx_wav_load_rate(wav_file.c_str(), &audio, &n, &ch, &rate, err) : umx_wav_load(wav_file.c_str(), &audio, &n, &ch, err)) // umx.cpp:56
     {
@@ -206,15 +179,12 @@ int main(int argc, const char **argv)
         hb.flags |= UMX_FLAG_LSTM_STEPWISE;
     umx_backend be{hip_segment, hip_reset, &hb};
     std::vector<float> stems[4];
-    std::vector<int16_t> stems16[4];
-    std::vector<unsigned char> stems24[4];
+    std::vector<int16_t> stems_int[4]; // the outputs as they are written, in io.out_format (int_units a frame)
     float *out[4];
     for (int t = 0; t < (mixed ? mixc.n_out : 4); ++t)
     {
-        if (pcm24)
-            stems24[t].resize((size_t)6 * n);
-        else if (pcm16)
-            stems16[t].resize((size_t)2 * n);
+        if (pcmc.active())
+            stems_int[t].resize(int_units(io.out_format) * n);
         else
             stems[t].resize((size_t)2 * n);
         out[t] = stems[t].data();
@@ -250,12 +220,10 @@ int main(int argc, const char **argv)
         // umx.cpp:72-73.  One call for every run: what a run does not ask for at its neutral value (NULL rate, gains, records, fp32
         // formats, clamp) is the narrower entry point's request (include/umx_hip.h)
         const int offset = env_int("UMX_SHIFT_OFFSET", -1) < 0 ? UMX_REFERENCE_SHIFT : env_int("UMX_SHIFT_OFFSET", -1);
-        const void *in = io.in_format == UMX_SAMPLE_S24   ? (const void *)audio24
-                         : io.in_format == UMX_SAMPLE_S16 ? (const void *)audio16
-                                                          : (const void *)audio;
+        const void *in = audio_int ? (const void *)audio_int : (const void *)audio;
         void *out_io[4]; // (read as the formats say)
         for (int t = 0; t < 4; ++t)
-            out_io[t] = pcm24 ? (void *)stems24[t].data() : pcm16 ? (void *)stems16[t].data() : (void *)stems[t].data();
+            out_io[t] = pcmc.active() ? (void *)stems_int[t].data() : (void *)stems[t].data();
         if (umx_hip_separate_tracks_loudness(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out_io,
                                              hb.flags, &io, clipc.clip_mode, clipc.levels ? &levels : nullptr,
                                              clipc.loudness ? &loudness : nullptr, nullptr, print_progress, nullptr))
@@ -279,10 +247,9 @@ int main(int argc, const char **argv)
             continue;
         const std::string p = (std::filesystem::path(out_dir) / (mixed ? mixc.name[t] + ".wav" : choice.file[t])).string();
         printf("Writing wav file %s\n", p.c_str());
-        if (pcm24   ? umx_wav_write_pcm24_rate(p.c_str(), stems24[t].data(), n, rate, err)
-            : pcm16 ? umx_wav_write_pcm16_rate(p.c_str(), stems16[t].data(), n, rate, err)
-            : resample ? umx_wav_write_f32_rate(p.c_str(), out[t], n, rate, err)
-                       : umx_wav_write_f32(p.c_str(), out[t], n, err))
+        if (pcmc.active() ? write_int(io.out_format, p.c_str(), stems_int[t].data(), n, rate, err)
+            : resample    ? umx_wav_write_f32_rate(p.c_str(), out[t], n, rate, err)
+                          : umx_wav_write_f32(p.c_str(), out[t], n, err))
         {
             fprintf(stderr, "%s\n", err);
             return 1;
@@ -293,8 +260,7 @@ int main(int argc, const char **argv)
             umx_loudness_print(p.c_str(), loudness, t);
     }
     umx_wav_free(audio);
-    umx_wav_free_pcm16(audio16);
-    umx_wav_free_pcm24(audio24);
+    umx_wav_free_pcm16(audio_int);
     umx_hip_destroy(ctx);
     return 0;
 }
