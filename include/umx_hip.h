@@ -624,6 +624,64 @@ int umx_hip_kweight_coeffs(int rate, double pb[3], double pa[3], double rb[3], d
 int umx_hip_kweight_hops_host(const float *x, int n, int rate, long long first_hop, long long n_hops, double *E);
 int umx_hip_loudness_gate(const double *E, long long hops, int hop, double *integrated, double *momentary_max, long long *blocks,
                           long long *gated);
+/* True peak of every output: the peak of the reconstructed waveform (dBTP = 20 log10), not of its samples, measured on
+ * the device where every output frame is final.  A separated stem is not bounded by its mixture, and a track rescaled on its sample
+ * peak can still overshoot between the samples: a tone at fs/4 with 45 degrees of phase reads 3.1 dB higher here than in peak[m].
+ * The rules, to the bit; the inputs are the fp32 samples umx_levels measures (at the caller's rate, behind the mix, before any
+ * rescale and before any encode), both channels of the `length` frames of output buffer m:
+ *   factor     F = 4 for rate < 96000, 2 for 96000 <= rate < 192000, 1 for rate == 192000 (libebur128's factors); rates outside
+ *              8000 .. 192000 are refused
+ *   taps       49-tap Hann-windowed sinc (libebur128's interpolator restated), formed on the host in double: for i = 0 .. 48,
+ *              m = i - 24: h[i] = (m == 0 ? 1 : sin(pi m / F) / (pi m / F)) * 0.5 (1 - cos(2 pi i / 48)), each rounded once to fp32.
+ *              h[24] is exactly 1, h[0] = h[48] = 0 and every other tap of phase 0 is below 1e-15: phase 0 is the sample itself.
+ *   y          frame k in [0, length), channel ch, phase f = 1 .. F-1: y = 0; for t = 0 .. 48/F - 1:
+ *              y = fmaf(h[f + F t], x[k + 24/F - t], y) -- fp32, in that order, fused multiply-adds; frames outside [0, length)
+ *              read as +0.  Frame k's values read frames k - (24/F - 1) .. k + 24/F: 12 frames at F = 4, 24 at F = 2.
+ *   true_peak[m]  the largest of |x| over the samples (peak[m]'s rule: the unsigned maximum of the bit patterns, NaN contributes
+ *              nothing, +inf counts) and of |y| over all interpolated values under the same rule.  true_peak[m] >= peak[m] always;
+ *              at F = 1 they are equal.  A maximum of values that depend on fixed frames only: regions, lanes, the queue, reset
+ *              mode and a rerun give the same bits.
+ *   true-peak rescale (UMX_TRUE_PEAK_RESCALE, with UMX_CLIP_RESCALE): P of the rescale rule above is the maximum of true_peak[m]
+ *              instead of peak[m]; everything else of that rule is unchanged (g = 1.01f * P; divisor 1 when P is not finite or
+ *              !(g > 1.0f); x / g, then the unchanged encode).  Since true_peak >= peak nothing clamps afterwards, as before;
+ *              umx_levels.gain reports that divisor.
+ * The shift ensemble, the multi-GPU driver (umx_mgpu.h) and the per-segment umx_hip_infer_* calls do not offer it. */
+#define UMX_TRUE_PEAK_OFF 0
+#define UMX_TRUE_PEAK_MEASURE 1
+#define UMX_TRUE_PEAK_RESCALE 2
+typedef struct umx_true_peak /* what a whole-track call reports per track */
+{
+    float true_peak[4];
+    int n_out;
+    int factor;
+} umx_true_peak;
+/* umx_hip_separate_tracks_loudness with a true-peak mode: n_tracks records, or NULL (a mode other than OFF still measures).
+ * UMX_TRUE_PEAK_OFF with true_peak == NULL IS the _loudness call: the same launches, nothing allocated.  Otherwise one launch per
+ * finished region measures the frames whose window has become final -- all but the last 24/F of the region, and everything on a
+ * track's last region; a track that leaves whole (rescaled, or both): one launch, before the divisor is formed.  UMX_ERR_ARG, naming
+ * the reason and leaving the context usable, for an unknown mode, for UMX_TRUE_PEAK_RESCALE without UMX_CLIP_RESCALE (both checked
+ * behind formats, clip mode and gains), for the shift ensemble and for everything the _loudness call refuses. */
+int umx_hip_separate_tracks_true_peak(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                                      const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                                      const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,
+                                      double *const *hop_energy, int true_peak_mode, umx_true_peak *true_peak,
+                                      void (*progress)(float, void *), void *progress_user);
+/* umx_hip_separate_queue_loudness with a true-peak mode; the done callback also receives the job's true-peak record (all zero with
+ * factor 0 under UMX_TRUE_PEAK_OFF); everything it receives is valid during the callback only. */
+typedef void (*umx_queue_true_peak_fn)(void *user, const umx_queue_job *job, const umx_levels *levels, const umx_loudness *loudness,
+                                       const double *hop_energy, const umx_true_peak *true_peak);
+int umx_hip_separate_queue_true_peak(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_true_peak_fn done, void *user, int n_out,
+                                     const float *gains, unsigned flags, const umx_sample_io *io, int clip_mode, int true_peak_mode);
+/* the kernel on the caller's device buffers, queued on hip_stream: 1 .. 4 buffers of (2,n) interleaved fp32 (8-byte aligned) that
+ * hold a track from frame 0; frames [first_frame, first_frame + n_frames) of buffer b accumulate (unsigned maximum) into
+ * bits_dev[b], four words that the caller has zeroed; exactly those four words are written and nothing outside [0, n) of a buffer is
+ * read.  UMX_ERR_ARG for a rate outside 8000 .. 192000, n > 2^30 - 1 and frames beyond n. */
+int umx_hip_true_peak_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, int rate, long long first_frame,
+                             long long n_frames, unsigned *bits_dev, void *hip_stream);
+/* the same rules on the host (no GPU, no context).  taps: the 49 fp32 taps and the factor of a rate.  host: one buffer of n
+ * interleaved stereo frames, frames [first_frame, first_frame + n_frames) accumulating into *bits. */
+int umx_hip_true_peak_taps(int rate, float taps[49], int *factor);
+int umx_hip_true_peak_host(const float *x, int n, int rate, long long first_frame, long long n_frames, unsigned *bits);
 /* testing, host only: the fp32 tap table of a rate pair (taps[phase * K + d + D]; cap floats at most), its phase count L, taps
  * per phase K and first offset -D.  UMX_ERR_ARG for a bad rate or a too small cap (the sizes are still reported). */
 int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase,

@@ -143,6 +143,21 @@ _dp = C.POINTER(C.c_double)
 QUEUE_LOUDNESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJobRate), C.POINTER(Levels), C.POINTER(Loudness), _dp)
 
 
+TRUE_PEAK_OFF, TRUE_PEAK_MEASURE, TRUE_PEAK_RESCALE = 0, 1, 2  # UMX_TRUE_PEAK_*: whether the true peak of what leaves is measured
+_up = C.POINTER(C.c_uint)
+
+
+class TruePeak(C.Structure):
+    """include/umx_hip.h: umx_true_peak, the true peak (linear; dBTP = 20 log10) of a track's outputs"""
+    _fields_ = [("true_peak", C.c_float * 4), ("n_out", C.c_int), ("factor", C.c_int)]
+
+    def as_dict(self):
+        return {"true_peak": np.array(self.true_peak[:self.n_out], np.float32), "factor": int(self.factor)}
+
+
+QUEUE_TRUE_PEAK_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJobRate), C.POINTER(Levels), C.POINTER(Loudness), _dp, C.POINTER(TruePeak))
+
+
 class TensorView(C.Structure):
     """include/umx_hip.h: umx_tensor_view"""
     _fields_ = [("name", C.c_char_p), ("target", C.c_int), ("dtype", C.c_int), ("n_dims", C.c_int),
@@ -308,6 +323,10 @@ def hip_lib():
     lib.umx_hip_kweight_coeffs.argtypes = [C.c_int, _dp, _dp, _dp, _dp]
     lib.umx_hip_kweight_hops_host.argtypes = [_fp, C.c_int, C.c_int, C.c_longlong, C.c_longlong, _dp]
     lib.umx_hip_loudness_gate.argtypes = [_dp, C.c_longlong, C.c_int, _dp, _dp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    lib.umx_hip_true_peak_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_longlong, C.c_longlong,
+                                             C.c_void_p, C.c_void_p]
+    lib.umx_hip_true_peak_taps.argtypes = [C.c_int, _fp, C.POINTER(C.c_int)]
+    lib.umx_hip_true_peak_host.argtypes = [_fp, C.c_int, C.c_int, C.c_longlong, C.c_longlong, _up]
     # The whole-track ladder, from one prefix: context, n_tracks, audio, lengths[, rates], shift offsets[, n_out, gains], outputs,
     # flags -- then what a rung adds -- then progress and its user pointer.  The queue entry points likewise.
     def tracks_args(ptr, rate=True, mix=True):
@@ -322,6 +341,8 @@ def hip_lib():
     lib.umx_hip_separate_tracks_io.argtypes = wide + progress
     lib.umx_hip_separate_tracks_levels.argtypes = wide + [C.c_int, C.POINTER(Levels)] + progress
     lib.umx_hip_separate_tracks_loudness.argtypes = wide + [C.c_int, C.POINTER(Levels), C.POINTER(Loudness), C.POINTER(C.c_void_p)] + progress
+    lib.umx_hip_separate_tracks_true_peak.argtypes = (wide + [C.c_int, C.POINTER(Levels), C.POINTER(Loudness), C.POINTER(C.c_void_p), C.c_int,
+                                                              C.POINTER(TruePeak)] + progress)
 
     def queue_args(done_fn):
         return [C.c_void_p, QUEUE_NEXT_FN, done_fn, C.c_void_p, C.c_int, _fp, C.c_uint]
@@ -330,6 +351,7 @@ def hip_lib():
     lib.umx_hip_separate_queue_io.argtypes = queue_args(QUEUE_DONE_FN) + [C.POINTER(SampleIO)]
     lib.umx_hip_separate_queue_levels.argtypes = queue_args(QUEUE_LEVELS_FN) + [C.POINTER(SampleIO), C.c_int]
     lib.umx_hip_separate_queue_loudness.argtypes = queue_args(QUEUE_LOUDNESS_FN) + [C.POINTER(SampleIO), C.c_int]
+    lib.umx_hip_separate_queue_true_peak.argtypes = queue_args(QUEUE_TRUE_PEAK_FN) + [C.POINTER(SampleIO), C.c_int, C.c_int]
     _hip = lib
     return lib
 
@@ -375,7 +397,9 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_kweight_coeffs", "umx_hip_kweight_hops_host", "umx_hip_loudness_gate",
                "umx_hip_resample_needs", "umx_hip_resample_ready", "umx_hip_resample_range_device", "umx_hip_debug_resample_launches",
                "umx_hip_pcm24_decode_device", "umx_hip_pcm24_encode_device", "umx_hip_pcm24_encode_rescaled_device",
-               "umx_hip_pcm24_decode_host", "umx_hip_pcm24_encode_host"]
+               "umx_hip_pcm24_decode_host", "umx_hip_pcm24_encode_host",
+               "umx_hip_separate_tracks_true_peak", "umx_hip_separate_queue_true_peak", "umx_hip_true_peak_device",
+               "umx_hip_true_peak_taps", "umx_hip_true_peak_host"]
 
 
 def sample_io(in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None):
@@ -506,6 +530,32 @@ def loudness_gate(E, hop):
     if rc != UMX_OK:
         raise UmxError(rc, "umx_hip_loudness_gate")
     return i.value, m.value, b.value, g.value
+
+
+def true_peak_taps(rate):
+    """umx_hip_true_peak_taps: the 49 float32 taps of the true-peak interpolator at `rate` and its oversampling factor (no GPU)."""
+    h, f = np.empty(49, np.float32), C.c_int()
+    rc = hip_lib().umx_hip_true_peak_taps(int(rate), h.ctypes.data_as(_fp), C.byref(f))
+    if rc != UMX_OK:
+        raise UmxError(rc, "umx_hip_true_peak_taps")
+    return h, f.value
+
+
+def true_peak_host(x, rate, first_frame=0, n_frames=None, bits=0):
+    """umx_hip_true_peak_host: the true peak of frames [first_frame, first_frame + n_frames) of a (2,n) float32 array by the rule of
+    DESIGN 26, as the maximum with the bit pattern `bits` -> the bit pattern (np.uint32; its float: true_peak_float) (no GPU)."""
+    a = np.ascontiguousarray(np.asarray(x, np.float32).T)
+    n_frames = a.shape[0] - first_frame if n_frames is None else n_frames
+    b = C.c_uint(int(bits))
+    rc = hip_lib().umx_hip_true_peak_host(a.ctypes.data_as(_fp), a.shape[0], int(rate), int(first_frame), int(n_frames), C.byref(b))
+    if rc != UMX_OK:
+        raise UmxError(rc, "umx_hip_true_peak_host")
+    return np.uint32(b.value)
+
+
+def true_peak_float(bits):
+    """The float32 whose bit pattern a true-peak word holds."""
+    return np.array([bits], np.uint32).view(np.float32)[0]
 
 
 def resampled_length(n, rate_in, rate_out):
@@ -948,6 +998,34 @@ class Engine:
                                                               ld, ep, None, None))
         return m.result(), (list(lv) if levels else None), (list(ld) if loudness else None), env
 
+    # --- true peak of every output: the oversampled peak of what leaves, measured on the device; a rescale on it ---
+    def separate_many_true_peak(self, waves, true_peak=TRUE_PEAK_MEASURE, clip=CLIP_CLAMP, io=None, flags=0, shift_offsets=None, rates=None,
+                                gains=None, levels=True, loudness=False, envelopes=False, records=True):
+        """umx_hip_separate_tracks_true_peak: separate_many_loudness() with a true-peak mode -> (outputs, [Levels], [Loudness], [hop
+        energies], [TruePeak per track]); levels / loudness / envelopes / records = False pass NULL and return None for them."""
+        nt = len(waves)
+        io = sample_io() if io is None else io
+        n_out, g = (4, None) if gains is None else _mix_gains(gains)
+        m = _TrackArgs(waves, io, n_out, shift_offsets, rates)
+        lv = (Levels * nt)() if levels else None
+        ld = (Loudness * nt)() if loudness else None
+        tp = (TruePeak * nt)() if records else None
+        env = ep = None
+        if envelopes:  # (a rate the call will refuse: any size does)
+            env = [np.full((m.n_host, 2, kweight_hop_count(L, r)), np.nan) for L, r in zip(m.Ls, rates or [MODEL_RATE] * nt)]
+            ep = (C.c_void_p * nt)(*[e.ctypes.data if e.size else None for e in env])
+        self._check(self.lib.umx_hip_separate_tracks_true_peak(self.h, nt, m.a, m.n, m.rt, m.sh, n_out,
+                                                               None if g is None else g.ctypes.data_as(_fp), m.o, flags, C.byref(io), int(clip), lv,
+                                                               ld, ep, int(true_peak), tp, None, None))
+        return m.result(), (list(lv) if levels else None), (list(ld) if loudness else None), env, (list(tp) if records else None)
+
+    def true_peak_device(self, in_ptrs, n, rate, bits_ptr, first_frame=0, n_frames=None, hip_stream=None):
+        """umx_hip_true_peak_device: frames [first_frame, first_frame + n_frames) of 1 .. 4 device buffers (2,n) interleaved fp32 into the
+        four words at device address bits_ptr (unsigned maxima of bit patterns; the caller zeroes them)."""
+        nb = len(in_ptrs)
+        self._check(self.lib.umx_hip_true_peak_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(rate), int(first_frame),
+                                                      int(n - first_frame if n_frames is None else n_frames), C.c_void_p(bits_ptr), hip_stream))
+
     def kweight_hops_device(self, in_ptrs, n, rate, E_ptr, first_hop=0, n_hops=None, hip_stream=None):
         """umx_hip_kweight_hops_device: hops [first_hop, first_hop + n_hops) of 1 .. 4 device buffers (2,n) interleaved fp32 into the
         float64 array [buffer][channel][n // hop] at device address E_ptr."""
@@ -1008,13 +1086,15 @@ class Engine:
         self._encode_device(16, in_ptrs, n, out_ptrs, first_frame, dither_seed, hip_stream)
 
     # --- the track queue: more tracks than lanes, a lane refilled with the next track the moment one ends ---
-    def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None, io=None, clip=None, levels=False, loudness=False, rates=None):
+    def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None, io=None, clip=None, levels=False, loudness=False, rates=None,
+                       true_peak=None):
         """umx_hip_separate_queue: list of (2,L_i) -> list of [4 x (2,L_i)] (mix: an (n_out, 5) gain matrix -> n_out x (2,L_i)), every
         job bit for bit what separate() / separate_mix() returns for it alone on this engine; the jobs are handed out in list order.
         rates: one sample rate per job (None: all 44.1 kHz), as separate_many() takes them.
         io: a SampleIO (sample_io()) -> umx_hip_separate_queue_io, int16 arrays in and / or out as it says.
         clip (CLIP_CLAMP / CLIP_RESCALE) or levels=True -> umx_hip_separate_queue_levels: returns (outputs, [Levels per job]).
-        loudness=True -> umx_hip_separate_queue_loudness: returns (outputs, [Levels], [Loudness], [(n_out, 2, hops) float64])."""
+        loudness=True -> umx_hip_separate_queue_loudness: returns (outputs, [Levels], [Loudness], [(n_out, 2, hops) float64]).
+        true_peak (a TRUE_PEAK_* mode) -> umx_hip_separate_queue_true_peak: returns those four and [TruePeak per job]."""
         nj = len(waves)
         n_out, g = (4, None) if mix is None else _mix_gains(mix)
         m = _TrackArgs(waves, io, n_out, shift_offsets)
@@ -1038,6 +1118,21 @@ class Engine:
         def _done(_user, job):
             state["done"].append(int(job[0].tag) - 1)
 
+        if true_peak is not None:
+            got, loud, env, tps = [None] * nj, [None] * nj, [None] * nj, [None] * nj
+
+            def _done_true_peak(_user, job, lv, ld, e, tp):
+                _done(_user, job)
+                j = int(job[0].tag) - 1
+                got[j], loud[j], tps[j] = Levels.from_buffer_copy(lv[0]), Loudness.from_buffer_copy(ld[0]), TruePeak.from_buffer_copy(tp[0])
+                h = int(loud[j].hops)
+                env[j] = (np.ctypeslib.as_array(e, shape=(n_out * 2 * h,)).copy() if h else np.zeros(0)).reshape(n_out, 2, h)
+
+            self._check(self.lib.umx_hip_separate_queue_true_peak(self.h, QUEUE_NEXT_FN(_next), QUEUE_TRUE_PEAK_FN(_done_true_peak), None, n_out,
+                                                                  None if g is None else g.ctypes.data_as(_fp), flags,
+                                                                  None if io is None else C.byref(io), int(clip or CLIP_CLAMP), int(true_peak)))
+            assert sorted(state["done"]) == list(range(nj)), state
+            return m.result(), got, loud, env, tps
         if loudness:
             got, loud, env = [None] * nj, [None] * nj, [None] * nj
 

@@ -46,6 +46,7 @@
 #include "pcm24.h"
 #include "levels.h"
 #include "loudness.h"
+#include "true_peak.h"
 #include "gate_debug.h"
 
 using namespace umx;
@@ -592,9 +593,11 @@ struct umx_hip_ctx
         int clip_mode = UMX_CLIP_CLAMP; // levels.h, DESIGN 20: UMX_CLIP_RESCALE: every track leaves whole, over its common divisor
         bool levels = false;            // the caller wants the record of what left
         bool loudness = false;          // loudness.h, DESIGN 21: the hop energies of what leaves are measured
+        int true_peak = UMX_TRUE_PEAK_OFF; // true_peak.h, DESIGN 26: MEASURE: the true peak of what leaves is measured; RESCALE: and the divisor comes from it
         int n_host() const { return mix ? mix->n_out : 4; } // host buffers per track
         bool rescale() const { return clip_mode == UMX_CLIP_RESCALE; }
         bool measures() const { return levels || rescale(); } // a rescaled track measures for its divisor whether or not the caller wants the record
+        bool true_peak_rescale() const { return true_peak == UMX_TRUE_PEAK_RESCALE && rescale(); }
     };
     struct TrackRequest // what tracks() is asked for: n_tracks tracks, one per track lane
     {
@@ -612,6 +615,7 @@ struct umx_hip_ctx
         umx_levels *levels = nullptr; // n_tracks records of what left, or nullptr: not wanted
         umx_loudness *loudness = nullptr; // loudness.h, DESIGN 21: n_tracks records, or nullptr
         double *const *hop_energy = nullptr; // per track nullptr or room for its hop energies; either of the two: the tracks are measured
+        umx_true_peak *true_peak = nullptr; // true_peak.h, DESIGN 26: n_tracks records, or nullptr (opt.true_peak says whether the tracks are measured)
     };
     int tracks(const TrackRequest &rq);
     int tracks_once(const TrackRequest &rq);
@@ -638,6 +642,7 @@ struct umx_hip_ctx
         umx_levels_acc *lev = nullptr; // DESIGN 20, only once a job measures: the record of what leaves, zeroed with the accumulators
         double *hopE = nullptr;        // DESIGN 21, only once a job measures loudness: its hop energies [output][channel][hop], grow-only,
         size_t cap_hopE = 0;           // zeroed with the accumulators (cap: doubles)
+        unsigned *tp = nullptr;        // DESIGN 26, only once a job measures its true peak: four words, the bit patterns, zeroed with the levels record
     };
     std::vector<TrackBufs> trk;
     hipEvent_t trk_acc_ev[kMaxSlots] = {}; // per slot: behind the overlap-add of the last call that ran in it
@@ -669,6 +674,10 @@ struct umx_hip_ctx
         int loud_rate = 0;            // the caller's rate: hop = kweight_hop(loud_rate) frames
         long long loud_hops = 0;      // hops of the caller's track (its length at that rate / hop)
         long long hops_done = 0;      // hops already launched (a restart begins again at 0)
+        // DESIGN 26 (opt.true_peak): the true peak of what leaves goes to acc->tp
+        int tp_rate = 0;              // the caller's rate: factor and reach of the interpolator
+        long long tp_length = 0;      // frames of the caller's track at that rate
+        long long tp_done = 0;        // frames already launched (a restart begins again at 0)
     };
     struct TrackLane // a lane of one call: its job (nullptr: idle) and the padded frame at which its segment starts
     {
@@ -714,13 +723,15 @@ struct umx_hip_ctx
     int track_bufs_grow(TrackBufs &tb_, size_t frames);
     int track_int_grow(TrackBufs &tb_, const umx_sample_io &io, size_t frames, int n_host);
     void track_encode(const TrackBufs &tb_, const umx_sample_io &io, int n_host, float *const src[4], size_t src_start, int count,
-                      long long first_frame, umx_levels_acc *acc, hipStream_t st);
+                      long long first_frame, umx_levels_acc *acc, hipStream_t st, const uint32_t *words = nullptr);
     int track_levels_grow(TrackBufs &tb_);
     int admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt, const float *audio, int rate, int length_at_rate, bool leaves_whole);
     void track_leave(TrackJob &j, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st);
     hipError_t track_levels_report(const TrackJob &j, int n_host, umx_levels &lv);
     int track_loudness_grow(TrackBufs &tb_, TrackJob &j, int rate, int length_at_rate, int n_host);
     hipError_t track_loudness_report(const TrackJob &j, int n_host, std::vector<double> &E, umx_loudness &ld);
+    int track_true_peak_grow(TrackBufs &tb_, TrackJob &j, int rate, int length_at_rate);
+    hipError_t track_true_peak_report(const TrackJob &j, int n_host, umx_true_peak &tp);
     hipError_t track_upload_until(TrackJob &j, long long padded_end, hipStream_t st);
     void track_mix(const MixSpec &mix, float *const stems[4], size_t stem_start, const float *in, size_t in_start, int count, hipStream_t st);
     hipError_t track_region_download(const TrackRegion &r, float *const *out_host);
@@ -733,6 +744,7 @@ struct umx_hip_ctx
         umx_queue_done_fn plain = nullptr;
         umx_queue_levels_fn with_levels = nullptr;
         umx_queue_loudness_fn with_loudness = nullptr;
+        umx_queue_true_peak_fn with_true_peak = nullptr; // (levels, loudness, hop energies and the true-peak record)
     };
     int queue(umx_queue_next_fn next, const QueueDone &done, void *user, const TrackOptions &opt, unsigned flags);
     int queue_run(umx_queue_next_fn next, const QueueDone &done, void *user, const TrackOptions &opt, unsigned flags);

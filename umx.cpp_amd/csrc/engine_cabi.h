@@ -329,10 +329,10 @@ int umx_hip_stream_set_layer(umx_hip_ctx *ctx, int layer, const float *host_src)
 }
 
 // ---------------------------------------------------------------- the whole-track entry points
-// The ladder umx_hip_separate_tracks, _rate, _mix, _io, _levels, _loudness and the one-track forms are ONE path: the options of the
+// The ladder umx_hip_separate_tracks, _rate, _mix, _io, _levels, _loudness, _true_peak and the one-track forms are ONE path: the options of the
 // call are checked and recorded once (track_options_checked -> umx_hip_ctx::TrackOptions), the request is filled once (track_request;
 // its checks are tracks_once's), and separate_tracks does both.  A rung is its own preconditions, then that path with the arguments it
-// does not have at their neutral values -- NULL rate, gains, io, records, UMX_CLIP_CLAMP -- so a wider rung with neutral arguments IS
+// does not have at their neutral values -- NULL rate, gains, io, records, UMX_CLIP_CLAMP, UMX_TRUE_PEAK_OFF -- so a wider rung with neutral arguments IS
 // the rung below, field for field, by construction.  The queue entry points share queue_entry the same way.
 static const char *mix_refusal(int n_out, const float *gains, MixSpec &spec) // (NULL gains are refused: who takes "no mix" asks before)
 {
@@ -348,21 +348,24 @@ static bool mix_checked(umx_hip_ctx *ctx, int n_out, const float *gains, MixSpec
 }
 
 // The options of a call, checked in this order: the sample formats (pcm16.h; io == NULL or fp32 both ways: the fp32 call itself), the
-// clip mode (levels.h), the gains (stem_mix.h; NULL: no mix).  true: `opt` holds them, `spec` the matrix behind opt.mix; false: the
+// clip mode (levels.h), the gains (stem_mix.h; NULL: no mix), the true-peak mode (true_peak.h).  true: `opt` holds them, `spec` the matrix behind opt.mix; false: the
 // refusal is the context's error.
 static bool track_options_checked(umx_hip_ctx *ctx, const umx_sample_io *io, int clip_mode, int n_out, const float *gains, MixSpec &spec,
-                                  umx_hip_ctx::TrackOptions &opt)
+                                  umx_hip_ctx::TrackOptions &opt, int true_peak_mode = UMX_TRUE_PEAK_OFF)
 {
     const char *why = sample_io_refusal(io);
     if (!why)
         why = clip_mode_refusal(clip_mode);
     if (!why && gains)
         why = mix_refusal(n_out, gains, spec);
+    if (!why)
+        why = true_peak_mode_refusal(true_peak_mode, clip_mode);
     if (why)
     {
         ctx->set_error(why);
         return false;
     }
+    opt.true_peak = true_peak_mode;
     opt.mix = gains ? &spec : nullptr;
     if (io)
         opt.io = *io;
@@ -374,7 +377,8 @@ static bool track_options_checked(umx_hip_ctx *ctx, const umx_sample_io *io, int
 static umx_hip_ctx::TrackRequest track_request(int n_tracks, const void *const *audio_host, const int *length, const int *rate,
                                                const int *shift_offset, void *const *out_host, unsigned flags, void (*progress)(float, void *),
                                                void *progress_user, const umx_hip_ctx::TrackOptions &opt, umx_levels *levels = nullptr,
-                                               umx_loudness *loudness = nullptr, double *const *hop_energy = nullptr)
+                                               umx_loudness *loudness = nullptr, double *const *hop_energy = nullptr,
+                                               umx_true_peak *true_peak = nullptr)
 {
     umx_hip_ctx::TrackRequest rq = {n_tracks, reinterpret_cast<const float *const *>(audio_host), length, rate, shift_offset,
                                     reinterpret_cast<float *const *>(out_host), flags, progress, progress_user};
@@ -384,22 +388,24 @@ static umx_hip_ctx::TrackRequest track_request(int n_tracks, const void *const *
     rq.levels = levels;
     rq.loudness = loudness;
     rq.hop_energy = hop_energy;
+    rq.true_peak = true_peak; // DESIGN 26 (whether the tracks are measured: opt.true_peak, the mode)
     return rq;
 }
 
 static int separate_tracks(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
                            const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
                            const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness, double *const *hop_energy,
-                           void (*progress)(float, void *), void *progress_user)
+                           void (*progress)(float, void *), void *progress_user, int true_peak_mode = UMX_TRUE_PEAK_OFF,
+                           umx_true_peak *true_peak = nullptr)
 {
     if (!ctx)
         return UMX_ERR_ARG;
     MixSpec spec;
     umx_hip_ctx::TrackOptions opt;
-    if (!track_options_checked(ctx, io, clip_mode, n_out, gains, spec, opt))
+    if (!track_options_checked(ctx, io, clip_mode, n_out, gains, spec, opt, true_peak_mode))
         return UMX_ERR_ARG;
     return ctx->tracks(track_request(n_tracks, audio_host, length, rate, shift_offset, out_host, flags, progress, progress_user, opt, levels,
-                                     loudness, hop_energy));
+                                     loudness, hop_energy, true_peak));
 }
 // the rungs without sample formats: fp32 buffers, no clip handling, nothing measured
 static int separate_tracks_f32(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *rate,
@@ -605,19 +611,19 @@ int umx_hip_shift_ensemble_mix(umx_hip_ctx *ctx, const float *audio_host, int le
 }
 
 // ---------------------------------------------------------------- track queue (engine_queue.h)
-// The four queue entry points differ in their done callback, and with it in what every job measures: a levels or loudness callback
+// The five queue entry points differ in their done callback, and with it in what every job measures: a levels or loudness callback
 // makes every job measure.  Their options are checked as a track call's.
 static int queue_entry(umx_hip_ctx *ctx, umx_queue_next_fn next, const umx_hip_ctx::QueueDone &done, void *user, int n_out, const float *gains,
-                       unsigned flags, const umx_sample_io *io, int clip_mode)
+                       unsigned flags, const umx_sample_io *io, int clip_mode, int true_peak_mode = UMX_TRUE_PEAK_OFF)
 {
     if (!ctx)
         return UMX_ERR_ARG;
     MixSpec spec;
     umx_hip_ctx::TrackOptions opt;
-    if (!track_options_checked(ctx, io, clip_mode, n_out, gains, spec, opt))
+    if (!track_options_checked(ctx, io, clip_mode, n_out, gains, spec, opt, true_peak_mode))
         return UMX_ERR_ARG;
-    opt.levels = done.with_levels || done.with_loudness;
-    opt.loudness = done.with_loudness != nullptr;
+    opt.levels = done.with_levels || done.with_loudness || done.with_true_peak;
+    opt.loudness = done.with_loudness || done.with_true_peak;
     return ctx->queue(next, done, user, opt, flags);
 }
 int umx_hip_separate_queue(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_done_fn done, void *user, int n_out, const float *gains,
@@ -739,7 +745,7 @@ int umx_hip_rescale_device(umx_hip_ctx *ctx, int n_buffers, float *const *bufs_d
         return UMX_ERR_ARG;
     }
     UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
-    launch_stem_rescale(n_buffers, p, n, acc_dev, (hipStream_t)hip_stream);
+    launch_stem_rescale(n_buffers, p, n, levels_peak_words(acc_dev), (hipStream_t)hip_stream);
     UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
     return UMX_OK;
 }
@@ -777,6 +783,66 @@ int umx_hip_separate_queue_loudness(umx_hip_ctx *ctx, umx_queue_next_fn next, um
                                     const float *gains, unsigned flags, const umx_sample_io *io, int clip_mode)
 {
     return queue_entry(ctx, next, {nullptr, nullptr, done}, user, n_out, gains, flags, io, clip_mode);
+}
+
+// ---------------------------------------------------------------- true peak of every output (true_peak.h)
+// UMX_TRUE_PEAK_OFF and true_peak == NULL: the request of umx_hip_separate_tracks_loudness, field for field
+int umx_hip_separate_tracks_true_peak(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                                      const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                                      const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,
+                                      double *const *hop_energy, int true_peak_mode, umx_true_peak *true_peak,
+                                      void (*progress)(float, void *), void *progress_user)
+{
+    return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, clip_mode, levels, loudness,
+                           hop_energy, progress, progress_user, true_peak_mode, true_peak);
+}
+
+int umx_hip_separate_queue_true_peak(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_true_peak_fn done, void *user, int n_out,
+                                     const float *gains, unsigned flags, const umx_sample_io *io, int clip_mode, int true_peak_mode)
+{
+    return queue_entry(ctx, next, {nullptr, nullptr, nullptr, done}, user, n_out, gains, flags, io, clip_mode, true_peak_mode);
+}
+
+int umx_hip_true_peak_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, int rate, long long first_frame,
+                             long long n_frames, unsigned *bits_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!true_peak_rate_ok(rate))
+    {
+        ctx->set_error("true peak: sample rate outside 8000 .. 192000 Hz");
+        return UMX_ERR_ARG;
+    }
+    const float2 *src[4] = {};
+    if (!device_buffers(ctx, "true peak", n_buffers, in_dev, n, first_frame, src))
+        return UMX_ERR_ARG;
+    if (!bits_dev || n > 0x7fffffff / 2 || n_frames < 0 || first_frame > n || n_frames > n - first_frame)
+    {
+        ctx->set_error("true peak: need the record, n <= 2^30 - 1 and 0 <= first_frame, first_frame + n_frames <= n");
+        return UMX_ERR_ARG;
+    }
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    launch_true_peak(n_buffers, src, n, rate, first_frame, n_frames, bits_dev, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+
+int umx_hip_true_peak_taps(int rate, float taps[49], int *factor)
+{
+    if (!true_peak_rate_ok(rate) || !taps || !factor)
+        return UMX_ERR_ARG;
+    *factor = true_peak_factor(rate);
+    const TruePeakTaps tp = true_peak_taps(*factor);
+    std::copy(tp.h, tp.h + TP_TAPS, taps);
+    return UMX_OK;
+}
+
+int umx_hip_true_peak_host(const float *x, int n, int rate, long long first_frame, long long n_frames, unsigned *bits)
+{
+    if (!x || !bits || n < 1 || !true_peak_rate_ok(rate) || first_frame < 0 || n_frames < 0 || first_frame > n || n_frames > n - first_frame)
+        return UMX_ERR_ARG;
+    *bits = true_peak_host(x, n, rate, first_frame, n_frames, *bits);
+    return UMX_OK;
 }
 
 int umx_hip_kweight_hops_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, int rate, long long first_hop,

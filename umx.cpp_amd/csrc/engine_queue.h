@@ -70,7 +70,7 @@ int queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_out, int
 
 int umx_hip_ctx::queue(umx_queue_next_fn next, const QueueDone &done, void *user, const TrackOptions &opt, unsigned flags)
 {
-    if (!next || (!done.plain && !done.with_levels && !done.with_loudness))
+    if (!next || (!done.plain && !done.with_levels && !done.with_loudness && !done.with_true_peak))
     {
         set_error("queue: need the next and the done callback");
         return UMX_ERR_ARG;
@@ -152,6 +152,7 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
         {
             jb->uploaded = jb->done44 = jb->out_done = 0; // (a resampled job goes through the resampler again, from its host copy)
             jb->hops_done = 0; // (its hop energies are zeroed with its accumulators and measured again)
+            jb->tp_done = 0;   // (likewise its true-peak words)
             jb->regions_left = jb->by_region ? jb->segs : 1;
         }
         for (int ln = 0; ln < B; ++ln)
@@ -214,15 +215,20 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
             {
                 umx_levels lv;
                 umx_loudness ld;
+                umx_true_peak tp = {};
                 std::vector<double> hopE;
-                if ((e = track_levels_report(*jb, n_host, lv)) == hipSuccess && done.with_loudness)
+                if ((e = track_levels_report(*jb, n_host, lv)) == hipSuccess && opt.loudness)
                     e = track_loudness_report(*jb, n_host, hopE, ld);
+                if (e == hipSuccess && opt.true_peak != UMX_TRUE_PEAK_OFF)
+                    e = track_true_peak_report(*jb, n_host, tp);
                 if (e != hipSuccess)
                 {
                     set_error(std::string("queue: reading a job's levels failed: ") + hipGetErrorString(e));
                     return UMX_ERR_HIP;
                 }
-                if (done.with_loudness)
+                if (done.with_true_peak)
+                    done.with_true_peak(user, &jb->job, &lv, &ld, hopE.data(), &tp);
+                else if (done.with_loudness)
                     done.with_loudness(user, &jb->job, &lv, &ld, hopE.data());
                 else
                     done.with_levels(user, &jb->job, &lv);
@@ -374,6 +380,8 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
                     (void)hipMemsetAsync(tb_.lev, 0, sizeof(umx_levels_acc), st);
                 if (jb->opt.loudness) // ... and its hop energies
                     (void)hipMemsetAsync(tb_.hopE, 0, sizeof(double) * std::max<size_t>(1, (size_t)n_host * 2 * (size_t)jb->loud_hops), st);
+                if (jb->opt.true_peak != UMX_TRUE_PEAK_OFF) // ... and its true-peak words
+                    (void)hipMemsetAsync(tb_.tp, 0, 4 * sizeof(unsigned), st);
             }
             nl = ln + 1;
         }

@@ -94,9 +94,10 @@ int umx_hip_ctx::track_int_grow(TrackBufs &tb_, const umx_sample_io &io, size_t 
 
 // `count` frames of the first n_host of `src` from frame src_start on -> the set's integer outputs from frame first_frame on, which is
 // their frame number in the caller's track (the k of the dither), at byte frame_bytes x first_frame; the kernel is the output
-// format's (launch_encode).  acc: over the divisor of that record, counting what clamps into it (nullptr: the plain encode).
+// format's (launch_encode).  acc: over the divisor of `words` (nullptr: of that record's peak words), counting what clamps into it
+// (acc nullptr: the plain encode).
 void umx_hip_ctx::track_encode(const TrackBufs &tb_, const umx_sample_io &io, int n_host, float *const src[4], size_t src_start, int count,
-                               long long first_frame, umx_levels_acc *acc, hipStream_t st)
+                               long long first_frame, umx_levels_acc *acc, hipStream_t st, const uint32_t *words)
 {
     const float2 *s[4] = {};
     uint8_t *d[4] = {};
@@ -105,7 +106,7 @@ void umx_hip_ctx::track_encode(const TrackBufs &tb_, const umx_sample_io &io, in
         s[t] = reinterpret_cast<const float2 *>(src[t]) + src_start;
         d[t] = reinterpret_cast<uint8_t *>(tb_.out_int[t]) + sample_frame_bytes(io.out_format) * (size_t)first_frame;
     }
-    launch_encode(io.out_format, n_host, s, d, count, first_frame, io.dither != 0, io.dither_seed, acc, st);
+    launch_encode(io.out_format, n_host, s, d, count, first_frame, io.dither != 0, io.dither_seed, acc, st, words);
 }
 
 // the set's record of what leaves (112 bytes, allocated once a job measures; the driver zeroes it with the accumulators)
@@ -140,6 +141,22 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
             j.hops_done = final_hops;
         }
     }
+    // A job with a true peak: next, and before any divisor, the frames whose window these frames complete -- frame k once
+    // frame k + 24/F is final, every frame on the job's last span (what lies behind the track reads as +0).  The window reaches back
+    // into the spans before this one, which are still in `src` as above; the launch is told that the buffers end where this span does.
+    if (j.opt.true_peak != UMX_TRUE_PEAK_OFF)
+    {
+        const long long end = first_frame + count;
+        const long long fin = end >= j.tp_length ? j.tp_length : std::max<long long>(end - true_peak_reach(true_peak_factor(j.tp_rate)), 0);
+        if (fin > j.tp_done)
+        {
+            const float2 *s0[4] = {};
+            for (int t = 0; t < n_host; ++t)
+                s0[t] = reinterpret_cast<const float2 *>(src[t]) + src_start - first_frame;
+            launch_true_peak(n_host, s0, (int)std::min(end, j.tp_length), j.tp_rate, j.tp_done, fin - j.tp_done, tb_.tp, st);
+            j.tp_done = fin;
+        }
+    }
     if (!j.opt.measures())
     {
         if (integer)
@@ -152,19 +169,54 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
         s[t] = sw[t] = reinterpret_cast<float2 *>(src[t]) + src_start;
     // (a rescaled integer track: its encode counts what it clamps itself, with the divisor it forms)
     launch_stem_levels(n_host, s, count, first_frame, rescale ? UMX_SAMPLE_F32 : io.out_format, io.dither != 0, io.dither_seed, tb_.lev, st);
+    // the words the divisor comes from: the record's peak words, or (UMX_TRUE_PEAK_RESCALE) the true-peak record, final by now
+    const uint32_t *words = j.opt.true_peak_rescale() ? tb_.tp : levels_peak_words(tb_.lev);
     if (integer)
-        track_encode(tb_, io, n_host, src, src_start, count, first_frame, rescale ? tb_.lev : nullptr, st);
+        track_encode(tb_, io, n_host, src, src_start, count, first_frame, rescale ? tb_.lev : nullptr, st, words);
     else if (rescale)
-        launch_stem_rescale(n_host, sw, count, tb_.lev, st);
+        launch_stem_rescale(n_host, sw, count, words, st);
 }
 
 // the job's record to the host (its last launch has finished: the caller has waited for the job's last region), as the call reports it
 hipError_t umx_hip_ctx::track_levels_report(const TrackJob &j, int n_host, umx_levels &lv)
 {
     umx_levels_acc acc;
-    const hipError_t e = hipMemcpy(&acc, j.acc->lev, sizeof acc, hipMemcpyDeviceToHost);
+    uint32_t words[4];
+    hipError_t e = hipMemcpy(&acc, j.acc->lev, sizeof acc, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && j.opt.true_peak_rescale()) // (the gain is the divisor of the true-peak words)
+        e = hipMemcpy(words, j.acc->tp, sizeof words, hipMemcpyDeviceToHost);
     if (e == hipSuccess)
-        levels_report(acc, n_host, j.opt.rescale(), lv);
+        levels_report(acc, n_host, j.opt.rescale(), j.opt.true_peak_rescale() ? words : acc.peak_bits, lv);
+    return e;
+}
+
+// the job measures its true peak at the caller's `rate`, over its length_at_rate frames there; the set's four words
+// (allocated once a job asks; the driver zeroes them with the levels record)
+int umx_hip_ctx::track_true_peak_grow(TrackBufs &tb_, TrackJob &j, int rate, int length_at_rate)
+{
+    if (!true_peak_rate_ok(rate))
+    {
+        set_error("true peak: sample rate outside 8000 .. 192000 Hz");
+        return UMX_ERR_ARG;
+    }
+    if (length_at_rate > 0x7fffffff / 2) // (the kernel counts frames in an int, with room for a tile and its halo beyond the last)
+    {
+        set_error("true peak: track too long");
+        return UMX_ERR_ARG;
+    }
+    j.tp_rate = rate;
+    j.tp_length = length_at_rate;
+    j.tp_done = 0;
+    return tb_.tp ? UMX_OK : dalloc(&tb_.tp, 4, true);
+}
+
+// the job's true-peak words to the host (its last launch has finished, as for track_levels_report), as the call reports them
+hipError_t umx_hip_ctx::track_true_peak_report(const TrackJob &j, int n_host, umx_true_peak &tp)
+{
+    uint32_t words[4] = {};
+    const hipError_t e = hipMemcpy(words, j.acc->tp, sizeof words, hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+        true_peak_report(words, n_host, true_peak_factor(j.tp_rate), tp);
     return e;
 }
 
@@ -210,7 +262,7 @@ int umx_hip_ctx::track_rate_plan(int rate, int length_at_rate, const char *too_l
 // another rate, its j.rs (track_rate_plan); `acc` is the accumulator set it will write, `audio` its host audio of length_at_rate
 // frames at `rate` -- the rate and length the caller sees --, leaves_whole: it is an ensemble lane.  The set grows by what the job
 // needs, in this order (a failed allocation returns at once): accumulators, native-rate staging (a job with j.rs), int16 side, levels
-// record, hop energies; then the job is filled.  What the driver zeroes, and on which stream, is the driver's.
+// record, hop energies, true-peak words; then the job is filled.  What the driver zeroes, and on which stream, is the driver's.
 int umx_hip_ctx::admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt, const float *audio, int rate, int length_at_rate, bool leaves_whole)
 {
     j.opt = opt;
@@ -227,6 +279,9 @@ int umx_hip_ctx::admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt,
             return rc;
     if (opt.loudness)
         if (int rc = track_loudness_grow(acc, j, rate, length_at_rate, opt.n_host()))
+            return rc;
+    if (opt.true_peak != UMX_TRUE_PEAK_OFF)
+        if (int rc = track_true_peak_grow(acc, j, rate, length_at_rate))
             return rc;
     j.audio = audio;
     j.acc = &acc;
@@ -455,7 +510,7 @@ int umx_hip_ctx::track_call(const TrackLane *lanes, int nl, unsigned flags, int 
                 j->out_done = r;
             }
         }
-        else if (opt.io.out_format != UMX_SAMPLE_F32 || opt.measures() || opt.loudness) // the region's frames of the caller's track, as they will
+        else if (opt.io.out_format != UMX_SAMPLE_F32 || opt.measures() || opt.loudness || opt.true_peak != UMX_TRUE_PEAK_OFF) // the region's frames of the caller's track, as they will
         {                                                    // leave (an int16 copy is not written over the accumulators: the next
                                                              // segment's overlap-add still reads its neighbours)
             const long long lo = std::max<long long>(rg.start, j->lead), hi = std::min<long long>((long long)rg.start + rg.count, (long long)j->lead + j->length);
@@ -505,6 +560,12 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     if (loud && ensemble)
     {
         set_error("track: the shift ensemble does not offer loudness");
+        return UMX_ERR_ARG;
+    }
+    const bool tpeak = opt.true_peak != UMX_TRUE_PEAK_OFF;
+    if (tpeak && ensemble)
+    {
+        set_error("track: the shift ensemble does not offer the true peak");
         return UMX_ERR_ARG;
     }
     for (int ln = 0; ln < nt; ++ln)
@@ -582,6 +643,8 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         UMX_HIP_CHECK(hipMemset(tb_.sumw, 0, sizeof(float) * frames));
         if (measure)
             UMX_HIP_CHECK(hipMemset(tb_.lev, 0, sizeof(umx_levels_acc)));
+        if (tpeak)
+            UMX_HIP_CHECK(hipMemset(tb_.tp, 0, 4 * sizeof(unsigned)));
         if (loud)
             UMX_HIP_CHECK(hipMemset(tb_.hopE, 0, sizeof(double) * std::max<size_t>(1, (size_t)n_host * 2 * (size_t)job[ln].loud_hops)));
     }
@@ -721,6 +784,10 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     std::vector<double> hopE[LSTMB_MAX_TRACKS];
     for (int ln = 0; ln < nt && loud && cerr == hipSuccess; ++ln)
         cerr = track_loudness_report(job[ln], n_host, hopE[ln], loud_reports[ln]);
+    // and its true-peak words
+    umx_true_peak tp_reports[LSTMB_MAX_TRACKS];
+    for (int ln = 0; ln < nt && tpeak && rq.true_peak && cerr == hipSuccess; ++ln)
+        cerr = track_true_peak_report(job[ln], n_host, tp_reports[ln]);
     if (cerr != hipSuccess)
     {
         set_error(hipGetErrorString(cerr));
@@ -733,6 +800,8 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         std::copy(reports, reports + nt, rq.levels);
     if (rq.loudness)
         std::copy(loud_reports, loud_reports + nt, rq.loudness);
+    if (rq.true_peak && tpeak)
+        std::copy(tp_reports, tp_reports + nt, rq.true_peak);
     for (int ln = 0; ln < nt && rq.hop_energy; ++ln)
         if (rq.hop_energy[ln])
             std::copy(hopE[ln].begin(), hopE[ln].end(), rq.hop_energy[ln]);

@@ -57,13 +57,15 @@ __host__ __device__ inline float levels_divisor(uint32_t peak_bits)
     const float g = 1.01f * levels_float(peak_bits);
     return g > 1.0f ? g : 1.0f;
 }
-__host__ __device__ inline float levels_divisor(const umx_levels_acc &acc)
+// ... of the four words the divisor comes from: the record's peak words, or a true-peak record's (true_peak.h)
+__host__ __device__ inline float levels_divisor(const uint32_t *words)
 {
-    uint32_t p = acc.peak_bits[0];
+    uint32_t p = words[0];
     for (int m = 1; m < 4; ++m)
-        p = acc.peak_bits[m] > p ? acc.peak_bits[m] : p;
+        p = words[m] > p ? words[m] : p;
     return levels_divisor(p);
 }
+__host__ __device__ inline float levels_divisor(const umx_levels_acc &acc) { return levels_divisor(acc.peak_bits); }
 // (x over that divisor: sample_rescaled; whether a format's clamp changes a sample: sample_clips -- both in sample_format.h)
 
 #define LEVELS_THREADS 256
@@ -142,13 +144,14 @@ template <class T> __global__ __launch_bounds__(LEVELS_THREADS) void encode_kern
     uint32_t unused[4] = {};
     encode_frames<false>(T(), a, n, Plain(), unused);
 }
-// ... and on x / g, g formed here from the record's peak words (final in stream order: the measuring launches precede this one).
+// ... and on x / g, g formed here from `words`, the record's peak words or a true-peak record's (final in stream order: the measuring
+// launches precede this one).
 // Where the divisor is 1 these are the plain encode's bits, and only there a sample can clamp: those are counted into the record's
 // `clipped`, which the measuring launches of a rescaled track leave alone.
-template <class T> __global__ __launch_bounds__(LEVELS_THREADS) void encode_rescaled_kernel(EncodeArgs a, int n, umx_levels_acc *acc)
+template <class T> __global__ __launch_bounds__(LEVELS_THREADS) void encode_rescaled_kernel(EncodeArgs a, int n, umx_levels_acc *acc, const uint32_t *__restrict__ words)
 {
     __shared__ uint32_t red[LEVELS_WAVES * 4];
-    const float g = levels_divisor(*acc);
+    const float g = levels_divisor(words);
     uint32_t v[4] = {};
     encode_frames<true>(T(), a, n, Rescaled{g, g != 1.0f}, v);
     const uint32_t total = levels_block_reduce<4, 0>(v, red);
@@ -162,9 +165,9 @@ struct RescaleBufs
 };
 
 // x / g in place over n frames of up to four buffers; divisor 1: nothing is written
-__global__ __launch_bounds__(LEVELS_THREADS) void stem_rescale_kernel(RescaleBufs a, int n, const umx_levels_acc *__restrict__ acc)
+__global__ __launch_bounds__(LEVELS_THREADS) void stem_rescale_kernel(RescaleBufs a, int n, const uint32_t *__restrict__ words)
 {
-    const float g = levels_divisor(*acc);
+    const float g = levels_divisor(words);
     if (g == 1.0f)
         return;
     const size_t step = (size_t)gridDim.x * blockDim.x;
@@ -191,10 +194,14 @@ inline void launch_stem_levels(int nb, const float2 *const *src, int n, long lon
                        encode_args(nb, src, nullptr, first_frame, dither, seed), clip_format, n, acc);
 }
 
-// the same buffers into dst (byte addresses) as `format` encodes them; acc: over the divisor of that record, counting into it
-// (nullptr: the plain encode).  An fp32 format: nothing.
+// the device address of a device record's peak words (no access: the record's first member)
+inline const uint32_t *levels_peak_words(const umx_levels_acc *acc_dev) { return reinterpret_cast<const uint32_t *>(acc_dev); }
+static_assert(offsetof(umx_levels_acc, peak_bits) == 0, "the peak words lead the record");
+
+// the same buffers into dst (byte addresses) as `format` encodes them; acc: over the divisor of `words` (nullptr: that record's peak
+// words), counting into the record (acc nullptr: the plain encode).  An fp32 format: nothing.
 inline void launch_encode(int format, int nb, const float2 *const *src, uint8_t *const *dst, int n, long long first_frame, bool dither,
-                          uint32_t seed, umx_levels_acc *acc, hipStream_t st)
+                          uint32_t seed, umx_levels_acc *acc, hipStream_t st, const uint32_t *words = nullptr)
 {
     if (n < 1 || nb < 1)
         return;
@@ -202,7 +209,8 @@ inline void launch_encode(int format, int nb, const float2 *const *src, uint8_t 
     with_sample_format(format, [&](auto t) {
         using T = decltype(t);
         if (acc)
-            hipLaunchKernelGGL(encode_rescaled_kernel<T>, dim3(encode_blocks(t, n)), dim3(LEVELS_THREADS), 0, st, a, n, acc);
+            hipLaunchKernelGGL(encode_rescaled_kernel<T>, dim3(encode_blocks(t, n)), dim3(LEVELS_THREADS), 0, st, a, n, acc,
+                               words ? words : levels_peak_words(acc));
         else
             hipLaunchKernelGGL(encode_kernel<T>, dim3(encode_blocks(t, n)), dim3(LEVELS_THREADS), 0, st, a, n);
     });
@@ -215,14 +223,14 @@ inline void launch_decode(int format, const void *in, float2 *out, int n, hipStr
         with_sample_format(format, [&](auto t) { launch_decode_as(t, in, out, n, st); });
 }
 
-inline void launch_stem_rescale(int nb, float2 *const *bufs, int n, const umx_levels_acc *acc, hipStream_t st)
+inline void launch_stem_rescale(int nb, float2 *const *bufs, int n, const uint32_t *words, hipStream_t st)
 {
     if (n < 1 || nb < 1)
         return;
     RescaleBufs a = {};
     for (int b = 0; b < nb && b < 4; ++b)
         a.p[b] = bufs[b];
-    hipLaunchKernelGGL(stem_rescale_kernel, dim3(pcm16_blocks(n)), dim3(LEVELS_THREADS), 0, st, a, n, acc);
+    hipLaunchKernelGGL(stem_rescale_kernel, dim3(pcm16_blocks(n)), dim3(LEVELS_THREADS), 0, st, a, n, words);
 }
 
 // the rules over n_frames interleaved stereo frames of output buffer `buffer`, into a host record (umx_hip_levels_host)
@@ -242,8 +250,8 @@ inline void levels_host(const float *x, int n_frames, int buffer, long long firs
         }
 }
 
-// what a whole-track call reports from a job's record
-inline void levels_report(const umx_levels_acc &acc, int n_out, bool rescaled, umx_levels &lv)
+// what a whole-track call reports from a job's record; `words`: what its divisor came from
+inline void levels_report(const umx_levels_acc &acc, int n_out, bool rescaled, const uint32_t *words, umx_levels &lv)
 {
     lv = umx_levels{};
     lv.n_out = n_out;
@@ -254,7 +262,7 @@ inline void levels_report(const umx_levels_acc &acc, int n_out, bool rescaled, u
         lv.clipped[m] = acc.clipped[m];
         lv.nonfinite[m] = acc.nonfinite[m];
     }
-    lv.gain = rescaled ? levels_divisor(acc) : 1.0f;
+    lv.gain = rescaled ? levels_divisor(words) : 1.0f;
 }
 
 inline const char *clip_mode_refusal(int clip_mode)

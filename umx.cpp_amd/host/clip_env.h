@@ -8,6 +8,10 @@
 //   UMX_LOUDNESS=1           one more line per output file, its ITU-R BS.1770-4 / EBU R128 loudness measured on the device:
 //                            loudness <file> integrated=<LUFS> momentary_max=<LUFS> blocks=<n> gated=<n>      (-inf is printed as -inf)
 //                            UMX_MIX="m=mix" gives the loudness of the input itself.
+//   UMX_TRUE_PEAK=1|rescale  one more line per output file, its true peak measured on the device:
+//                            true_peak <file> dbtp=<dBTP> linear=<%.9g> factor=<F>                            (-inf is printed as -inf)
+//                            rescale: also, UMX_CLIP=rescale divides by 1.01 * the largest TRUE peak of the file's outputs instead of
+//                            their sample peak; refused without UMX_CLIP=rescale.
 // All go with UMX_PCM16, UMX_MIX, UMX_TARGETS / UMX_RESIDUAL and UMX_RESAMPLE, through umx-batch's queue and its pass-by-pass loop;
 // not with UMX_SHIFTS > 1 or UMX_CLI_PER_SEGMENT (the shift ensemble and the per-segment calls do not offer them).
 #pragma once
@@ -24,7 +28,8 @@ struct umx_clip_choice
     int clip_mode = UMX_CLIP_CLAMP;
     bool levels = false;
     bool loudness = false;
-    bool active() const { return clip_mode != UMX_CLIP_CLAMP || levels || loudness; } // false: the calls and the files of a run without the three
+    int true_peak = UMX_TRUE_PEAK_OFF;
+    bool active() const { return clip_mode != UMX_CLIP_CLAMP || levels || loudness || true_peak != UMX_TRUE_PEAK_OFF; } // false: the calls and the files of a run without the four
 };
 
 // false, with a message that names the variable, for a value outside the grammar above (nullptr: unset)
@@ -82,6 +87,26 @@ inline bool umx_clip_from_env(umx_clip_choice &c, const char *not_offered)
                 return false;
             }
         }
+    if (const char *tp = getenv("UMX_TRUE_PEAK"))
+        if (*tp)
+        {
+            if (strcmp(tp, "0") && strcmp(tp, "1") && strcmp(tp, "rescale"))
+            {
+                fprintf(stderr, "UMX_TRUE_PEAK: need 0, 1 or rescale, got \"%s\"\n", tp);
+                return false;
+            }
+            c.true_peak = !strcmp(tp, "rescale") ? UMX_TRUE_PEAK_RESCALE : tp[0] == '1' ? UMX_TRUE_PEAK_MEASURE : UMX_TRUE_PEAK_OFF;
+            if (c.true_peak != UMX_TRUE_PEAK_OFF && not_offered)
+            {
+                fprintf(stderr, "UMX_TRUE_PEAK: %s (nor the true peak)\n", not_offered);
+                return false;
+            }
+            if (c.true_peak == UMX_TRUE_PEAK_RESCALE && c.clip_mode != UMX_CLIP_RESCALE)
+            {
+                fprintf(stderr, "UMX_TRUE_PEAK=rescale: needs UMX_CLIP=rescale (it says which peak the divisor comes from)\n");
+                return false;
+            }
+        }
     return true;
 }
 
@@ -105,4 +130,16 @@ inline void umx_loudness_print(const char *file, const umx_loudness &ld, int m)
     lufs(ld.integrated[m], a, sizeof a);
     lufs(ld.momentary_max[m], b, sizeof b);
     printf("loudness %s integrated=%s momentary_max=%s blocks=%lld gated=%lld\n", file, a, b, ld.blocks[m], ld.gated[m]);
+}
+
+// the true-peak line of output m of a track, written to `file`
+inline void umx_true_peak_print(const char *file, const umx_true_peak &tp, int m)
+{
+    const double v = tp.true_peak[m];
+    char a[40];
+    if (v == 0 || std::isinf(v)) // (-inf by name, as the loudness line)
+        snprintf(a, sizeof a, "%s", v == 0 ? "-inf" : "inf");
+    else
+        snprintf(a, sizeof a, "%.6f", 20.0 * std::log10(v));
+    printf("true_peak %s dbtp=%s linear=%.9g factor=%d\n", file, a, v, tp.factor);
 }

@@ -20,6 +20,8 @@
 // file written, through the queue (umx_hip_separate_queue_levels) and the pass-by-pass loop (umx_hip_separate_tracks_levels) alike.
 // UMX_LOUDNESS (as umx-cli): one `loudness <file> ...` line per file written, through the queue
 // (umx_hip_separate_queue_loudness) and the pass-by-pass loop (umx_hip_separate_tracks_loudness) alike.
+// UMX_TRUE_PEAK (as umx-cli): one `true_peak <file> ...` line per file written, through the queue
+// (umx_hip_separate_queue_true_peak) and the pass-by-pass loop (umx_hip_separate_tracks_true_peak) alike; rescale needs UMX_CLIP=rescale.
 #include "../../include/umx_host.h"
 #include "clip_env.h"
 #include "mix_env.h"
@@ -59,6 +61,7 @@ struct FileJob
     std::vector<std::vector<int16_t>> stems16; // UMX_PCM16 / UMX_PCM24: the outputs as they are written (2 or 3 int16 units a frame)
     umx_levels levels = {};                    // UMX_CLIP / UMX_LEVELS: what the queue measured
     umx_loudness loudness = {};                // UMX_LOUDNESS: likewise
+    umx_true_peak true_peak = {};              // UMX_TRUE_PEAK: likewise
 };
 struct BatchQueue
 {
@@ -130,6 +133,12 @@ struct BatchQueue
     {
         static_cast<FileJob *>(job->tag)->loudness = *loudness;
         done_levels(user, job, levels);
+    }
+    static void done_true_peak(void *user, const umx_queue_job *job, const umx_levels *levels, const umx_loudness *loudness, const double *e,
+                               const umx_true_peak *true_peak)
+    {
+        static_cast<FileJob *>(job->tag)->true_peak = *true_peak;
+        done_loudness(user, job, levels, loudness, e);
     }
 };
 
@@ -237,7 +246,7 @@ int main(int argc, const char **argv)
     }
     // umx.cpp:75-96: the buffers of file f to its directory
     auto write_file = [&](int f, float *const *bufs, int16_t *const *bufs16, int n, int rate_, const umx_levels &lv, const umx_loudness &ld,
-                          char *err_) -> bool {
+                          const umx_true_peak &tp, char *err_) -> bool {
         const std::filesystem::path dir = std::filesystem::path(out_dir) / names[f];
         std::error_code ec;
         std::filesystem::create_directories(dir, ec);
@@ -254,6 +263,8 @@ int main(int argc, const char **argv)
                 umx_levels_print(p.c_str(), lv, t);
             if (clipc.loudness)
                 umx_loudness_print(p.c_str(), ld, t);
+            if (clipc.true_peak != UMX_TRUE_PEAK_OFF)
+                umx_true_peak_print(p.c_str(), tp, t);
         }
         return true;
     };
@@ -319,7 +330,7 @@ int main(int argc, const char **argv)
                     bufs[t] = fj->stems[t].data();
                     bufs16[t] = fj->stems16[t].data();
                 }
-                const bool ok = write_file(fj->index, bufs, bufs16, fj->n, fj->rate, fj->levels, fj->loudness, werr);
+                const bool ok = write_file(fj->index, bufs, bufs16, fj->n, fj->rate, fj->levels, fj->loudness, fj->true_peak, werr);
                 std::lock_guard<std::mutex> lock(q.m);
                 q.unwritten.pop_front(); // (counted until it is written: the stems are in memory until then)
                 if (!ok && q.error.empty())
@@ -329,7 +340,10 @@ int main(int argc, const char **argv)
             }
         });
         const auto t0 = std::chrono::steady_clock::now();
-        const int qrc = clipc.loudness ? umx_hip_separate_queue_loudness(ctx, BatchQueue::next, BatchQueue::done_loudness, &q, mixc.n_out,
+        const int qrc = clipc.true_peak != UMX_TRUE_PEAK_OFF
+                            ? umx_hip_separate_queue_true_peak(ctx, BatchQueue::next, BatchQueue::done_true_peak, &q, mixc.n_out,
+                                                               mixed ? mixc.gains : nullptr, flags, &io, clipc.clip_mode, clipc.true_peak)
+                        : clipc.loudness ? umx_hip_separate_queue_loudness(ctx, BatchQueue::next, BatchQueue::done_loudness, &q, mixc.n_out,
                                                                          mixed ? mixc.gains : nullptr, flags, &io, clipc.clip_mode)
                         : clipc.active() ? umx_hip_separate_queue_levels(ctx, BatchQueue::next, BatchQueue::done_levels, &q, mixc.n_out,
                                                                        mixed ? mixc.gains : nullptr, flags, &io, clipc.clip_mode)
@@ -375,6 +389,7 @@ int main(int argc, const char **argv)
         std::vector<int> rate(nb, UMX_SAMPLE_RATE);
         std::vector<umx_levels> levels(nb);
         std::vector<umx_loudness> loudness(nb);
+        std::vector<umx_true_peak> true_peak(nb);
         std::vector<void *> out_io(per_file * nb); // (read as the formats say)
         for (int i = 0; i < nb; ++i)
         {
@@ -402,10 +417,10 @@ int main(int argc, const char **argv)
         const auto t0 = std::chrono::steady_clock::now();
         // one call for every run: what a run does not ask for at its neutral value (NULL rates, gains, records, fp32 formats, clamp) is the
         // narrower entry point's request (include/umx_hip.h)
-        if (umx_hip_separate_tracks_loudness(ctx, nb, in_io.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out,
-                                             mixed ? mixc.gains : nullptr, out_io.data(), flags, &io, clipc.clip_mode,
-                                             clipc.levels ? levels.data() : nullptr, clipc.loudness ? loudness.data() : nullptr, nullptr, nullptr,
-                                             nullptr))
+        if (umx_hip_separate_tracks_true_peak(ctx, nb, in_io.data(), n.data(), resample ? rate.data() : nullptr, shift.data(), mixc.n_out,
+                                              mixed ? mixc.gains : nullptr, out_io.data(), flags, &io, clipc.clip_mode,
+                                              clipc.levels ? levels.data() : nullptr, clipc.loudness ? loudness.data() : nullptr, nullptr,
+                                              clipc.true_peak, clipc.true_peak != UMX_TRUE_PEAK_OFF ? true_peak.data() : nullptr, nullptr, nullptr))
         {
             fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
             return 1;
@@ -413,7 +428,7 @@ int main(int argc, const char **argv)
         wall += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         for (int i = 0; i < nb; ++i)
         {
-            if (!write_file(f0 + i, &out[per_file * i], &out16[per_file * i], n[i], rate[i], levels[i], loudness[i], err))
+            if (!write_file(f0 + i, &out[per_file * i], &out16[per_file * i], n[i], rate[i], levels[i], loudness[i], true_peak[i], err))
             {
                 fprintf(stderr, "%s\n", err);
                 return 1;

@@ -33,6 +33,9 @@
 //   UMX_LOUDNESS=1   one `loudness <file> integrated=<LUFS> momentary_max=<LUFS> blocks=<n> gated=<n>` line per file written, BS.1770-4 /
 //                    R128 loudness measured on the device (umx_hip_separate_tracks_loudness; host/clip_env.h); goes where
 //                    UMX_LEVELS goes.  Unset or 0: today's output
+//   UMX_TRUE_PEAK=1|rescale   one `true_peak <file> dbtp=<dBTP> linear=<x> factor=<F>` line per file written, the oversampled peak
+//                    measured on the device (umx_hip_separate_tracks_true_peak; host/clip_env.h); rescale: UMX_CLIP=rescale
+//                    (required) divides by the true peak instead of the sample peak.  Goes where UMX_LOUDNESS goes.  Unset or 0: today's output
 #include "../../include/umx_host.h"
 #include "clip_env.h"
 #include "mix_env.h"
@@ -122,6 +125,7 @@ int main(int argc, const char **argv)
         return 1;
     umx_levels levels = {};
     umx_loudness loudness = {};
+    umx_true_peak true_peak = {};
     umx_sample_io io = pcmc.io;
     printf("umx-cli (MI355X / gfx950) main driver program\n");
 
@@ -224,9 +228,10 @@ int main(int argc, const char **argv)
         void *out_io[4]; // (read as the formats say)
         for (int t = 0; t < 4; ++t)
             out_io[t] = pcmc.active() ? (void *)stems_int[t].data() : (void *)stems[t].data();
-        if (umx_hip_separate_tracks_loudness(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out_io,
-                                             hb.flags, &io, clipc.clip_mode, clipc.levels ? &levels : nullptr,
-                                             clipc.loudness ? &loudness : nullptr, nullptr, print_progress, nullptr))
+        if (umx_hip_separate_tracks_true_peak(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out_io,
+                                              hb.flags, &io, clipc.clip_mode, clipc.levels ? &levels : nullptr,
+                                              clipc.loudness ? &loudness : nullptr, nullptr, clipc.true_peak,
+                                              clipc.true_peak != UMX_TRUE_PEAK_OFF ? &true_peak : nullptr, print_progress, nullptr))
         {
             fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
             return 1;
@@ -258,6 +263,8 @@ int main(int argc, const char **argv)
             umx_levels_print(p.c_str(), levels, t);
         if (clipc.loudness)
             umx_loudness_print(p.c_str(), loudness, t);
+        if (clipc.true_peak != UMX_TRUE_PEAK_OFF)
+            umx_true_peak_print(p.c_str(), true_peak, t);
     }
     umx_wav_free(audio);
     umx_wav_free_pcm16(audio_int);
