@@ -38,6 +38,61 @@ def test_whole_track_entry_points_refuse_a_null_context(pkg):
         assert fn(None, *args) == pkg.ERR_ARG, name
 
 
+class _RecordingLib:
+    """stands in for the loaded library behind an Engine: every entry point records its name and arguments and returns UMX_OK"""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        return lambda *args: self.calls.append((name, args)) or 0
+
+
+def _plain(pkg, args):
+    """the values behind a C argument tuple of the whole-track ladder: arrays of lengths, shifts and rates as lists, the pointer arrays
+    by their length (the buffers are each call's own), the gains and the SampleIO by what they point at"""
+    out = []
+    for i, a in enumerate(args):
+        if isinstance(a, ctypes.Array):
+            out.append(len(a) if a._type_ is ctypes.c_void_p else list(a))
+        elif i == 7 and a is not None:  # gains: n_out rows of five
+            out.append([a[k] for k in range(args[6] * pkg.MIX_COLUMNS)])
+        elif hasattr(a, "_obj"):  # byref(io)
+            out.append(bytes(a._obj))
+        else:
+            out.append(a)
+    return out
+
+
+def test_widest_wrapper_with_neutral_measure_arguments_builds_the_io_call(pkg):
+    """A rung of the whole-track ladder is the rung above it with neutral values in the fields it does not have: what
+    separate_many_true_peak with nothing asked hands to umx_hip_separate_tracks_true_peak is what separate_many_io hands to
+    umx_hip_separate_tracks_io, then UMX_CLIP_CLAMP, three NULLs, UMX_TRUE_PEAK_OFF and a NULL, argument by argument; and each rung
+    between is a prefix of that tail.  No GPU: the library behind the engine only records."""
+    eng = object.__new__(pkg.Engine)
+    eng.h, eng.lib = None, _RecordingLib()
+    waves = [pkg.ggml.synth_audio(700, 3), pkg.ggml.synth_audio(90, 4)]
+    io = pkg.sample_io(pkg.SAMPLE_F32, pkg.SAMPLE_S16, 7)
+    gains = np.array([[0, 0, 0, 0, 3], [0, 0, 0, 1, 0]], np.float32)
+    kw = dict(io=io, flags=pkg.FLAG_NO_WIENER, shift_offsets=[4033, None], rates=[48000, 44100], gains=gains)
+    eng.separate_many_io(waves, **kw)
+    eng.separate_many_levels(waves, levels=False, **kw)
+    eng.separate_many_loudness(waves, levels=False, loudness=False, envelopes=False, **kw)
+    eng.separate_many_true_peak(waves, pkg.TRUE_PEAK_OFF, levels=False, records=False, **kw)
+    (n0, a_io), (n1, a_lv), (n2, a_ld), (n3, a_tp) = eng.lib.calls
+    assert (n0, n1, n2, n3) == tuple("umx_hip_separate_tracks_" + r for r in ("io", "levels", "loudness", "true_peak"))
+    base, progress = _plain(pkg, a_io)[:-2], [None, None]
+    assert base[1:] == [2, 2, [700, 90], [48000, 44100], [4033, -1], 2, list(gains.ravel()), 4, pkg.FLAG_NO_WIENER, bytes(io)]
+    neutral = [pkg.CLIP_CLAMP, None, None, None, pkg.TRUE_PEAK_OFF, None]
+    assert _plain(pkg, a_tp) == base + neutral + progress
+    assert _plain(pkg, a_ld) == base + neutral[:4] + progress and _plain(pkg, a_lv) == base + neutral[:2] + progress
+    # and a field that is asked for lands in its own place, the others staying neutral
+    eng.separate_many_true_peak(waves, pkg.TRUE_PEAK_MEASURE, pkg.CLIP_RESCALE, levels=False, records=True, **kw)
+    tail = eng.lib.calls[-1][1][11:]
+    assert tail[0] == pkg.CLIP_RESCALE and tail[1:4] == (None, None, None) and tail[4] == pkg.TRUE_PEAK_MEASURE
+    assert isinstance(tail[5], ctypes.Array) and tail[5]._type_ is pkg.TruePeak and len(tail[5]) == 2 and tail[6:] == (None, None)
+
+
 def test_cu_reservations_are_requests_per_device_not_one_global_value(pkg):
     """umx_hip_gate_reserve (include/umx_hip.h): two multi-GPU drivers on one device each file a request; destroying
     one gives back ITS request only; giving back a request that was never filed is an error.  Pure host state: runs without a GPU."""

@@ -644,6 +644,43 @@ class _TrackArgs:
         return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(self.outs, self.Ls)]
 
 
+# What a rung of the whole-track ladder adds behind its SampleIO, in the C signature's order: a narrower rung is the
+# wider one with the fields it does not have at their neutral values.
+_MEASURE_TAIL = {"umx_hip_separate_tracks_io": (),
+                 "umx_hip_separate_tracks_levels": ("clip", "levels"),
+                 "umx_hip_separate_tracks_loudness": ("clip", "levels", "loudness", "hop_energy"),
+                 "umx_hip_separate_tracks_true_peak": ("clip", "levels", "loudness", "hop_energy", "true_peak_mode", "true_peak")}
+
+
+class _MeasuredCall:
+    """One call of a rung of _MEASURE_TAIL, marshalled once: the _TrackArgs `m`, the record arrays lv / ld / tp and the hop-energy
+    arrays env (None: not asked for, NULL in the call), and `args`, the C argument tuple with the tail that rung has.  results(): the
+    tuple the rung's wrapper returns -- outputs, then one entry per record field of its tail."""
+
+    def __init__(self, entry_name, handle, waves, io, flags, shift_offsets, rates, gains, clip=CLIP_CLAMP, levels=False, loudness=False,
+                 envelopes=False, true_peak=TRUE_PEAK_OFF, records=False):
+        nt = len(waves)
+        self.io = io = sample_io() if io is None else io
+        n_out, self.g = (4, None) if gains is None else _mix_gains(gains)
+        self.m = m = _TrackArgs(waves, io, n_out, shift_offsets, rates)
+        self.lv = (Levels * nt)() if levels else None
+        self.ld = (Loudness * nt)() if loudness else None
+        self.tp = (TruePeak * nt)() if records else None
+        self.env = ep = None
+        if envelopes:  # (a rate the call will refuse: any size does)
+            self.env = [np.full((m.n_host, 2, kweight_hop_count(L, r)), np.nan) for L, r in zip(m.Ls, rates or [MODEL_RATE] * nt)]
+            ep = (C.c_void_p * nt)(*[e.ctypes.data if e.size else None for e in self.env])
+        tail = {"clip": int(clip), "levels": self.lv, "loudness": self.ld, "hop_energy": ep, "true_peak_mode": int(true_peak), "true_peak": self.tp}
+        self.tail = _MEASURE_TAIL[entry_name]
+        self.args = ((handle, nt, m.a, m.n, m.rt, m.sh, n_out, None if self.g is None else self.g.ctypes.data_as(_fp), m.o, flags, C.byref(io))
+                     + tuple(tail[f] for f in self.tail) + (None, None))
+
+    def results(self):
+        got = {"levels": self.lv, "loudness": self.ld, "true_peak": self.tp}
+        return (self.m.result(),) + tuple(self.env if f == "hop_energy" else (None if got[f] is None else list(got[f]))
+                                          for f in self.tail if f not in ("clip", "true_peak_mode"))
+
+
 def mix_columns(gains):
     """umx_hip_mix_columns: the bitmask of the columns of an (n_out, 5) gain matrix with any nonzero gain (bit 4: the mixture).
     Host arithmetic."""
@@ -958,66 +995,37 @@ class Engine:
         SAMPLE_S16 in takes (2,L_i) int16 arrays, SAMPLE_S16 out returns int16 arrays, dithered with dither_seed unless it is None.
         io: a SampleIO passed as it is instead (tests of the refusals)."""
         io = sample_io(in_format, out_format, dither_seed) if io is None else io
-        n_out, g = (4, None) if gains is None else _mix_gains(gains)
-        m = _TrackArgs(waves, io, n_out, shift_offsets, rates)
-        self._check(self.lib.umx_hip_separate_tracks_io(self.h, len(waves), m.a, m.n, m.rt, m.sh, n_out,
-                                                        None if g is None else g.ctypes.data_as(_fp), m.o, flags, C.byref(io), None, None))
-        return m.result()
+        return self._separate_many_measured("umx_hip_separate_tracks_io", waves, io, flags, shift_offsets, rates, gains).m.result()
+
+    def _separate_many_measured(self, entry_name, waves, io, flags, shift_offsets, rates, gains, **asked):
+        """One whole-track call through the rung `entry_name` of the ladder (_MeasuredCall: everything marshalled once, the tail
+        that rung has) -> the call, with its outputs and whatever records it asked for."""
+        call = _MeasuredCall(entry_name, self.h, waves, io, flags, shift_offsets, rates, gains, **asked)
+        self._check(getattr(self.lib, entry_name)(*call.args))
+        return call
 
     # --- output levels and clip handling (DESIGN 20): what leaves is measured on the device; rescale divides a track by one divisor ---
     def separate_many_levels(self, waves, clip=CLIP_CLAMP, io=None, flags=0, shift_offsets=None, rates=None, gains=None, levels=True):
         """umx_hip_separate_tracks_levels: separate_many_io() (io: a SampleIO, None = fp32 both ways) with a clip mode -> (outputs,
         [Levels per track]); levels=False passes NULL for the records and returns None for them."""
-        nt = len(waves)
-        io = sample_io() if io is None else io
-        n_out, g = (4, None) if gains is None else _mix_gains(gains)
-        m = _TrackArgs(waves, io, n_out, shift_offsets, rates)
-        lv = (Levels * nt)() if levels else None
-        self._check(self.lib.umx_hip_separate_tracks_levels(self.h, nt, m.a, m.n, m.rt, m.sh, n_out,
-                                                            None if g is None else g.ctypes.data_as(_fp), m.o, flags, C.byref(io), int(clip), lv,
-                                                            None, None))
-        return m.result(), (list(lv) if levels else None)
+        return self._separate_many_measured("umx_hip_separate_tracks_levels", waves, io, flags, shift_offsets, rates, gains, clip=clip,
+                                            levels=levels).results()
 
     # --- loudness of every output (DESIGN 21): K-weighted hop energies measured on the device, blocks and gates formed on the host ---
     def separate_many_loudness(self, waves, clip=CLIP_CLAMP, io=None, flags=0, shift_offsets=None, rates=None, gains=None, levels=True,
                                loudness=True, envelopes=True):
         """umx_hip_separate_tracks_loudness: separate_many_levels() -> (outputs, [Levels per track], [Loudness per track], [(n_out, 2,
         hops) float64 hop energies per track]); levels / loudness / envelopes = False pass NULL and return None for them."""
-        nt = len(waves)
-        io = sample_io() if io is None else io
-        n_out, g = (4, None) if gains is None else _mix_gains(gains)
-        m = _TrackArgs(waves, io, n_out, shift_offsets, rates)
-        lv = (Levels * nt)() if levels else None
-        ld = (Loudness * nt)() if loudness else None
-        env = ep = None
-        if envelopes:  # (a rate the call will refuse: any size does)
-            env = [np.full((m.n_host, 2, kweight_hop_count(L, r)), np.nan) for L, r in zip(m.Ls, rates or [MODEL_RATE] * nt)]
-            ep = (C.c_void_p * nt)(*[e.ctypes.data if e.size else None for e in env])
-        self._check(self.lib.umx_hip_separate_tracks_loudness(self.h, nt, m.a, m.n, m.rt, m.sh, n_out,
-                                                              None if g is None else g.ctypes.data_as(_fp), m.o, flags, C.byref(io), int(clip), lv,
-                                                              ld, ep, None, None))
-        return m.result(), (list(lv) if levels else None), (list(ld) if loudness else None), env
+        return self._separate_many_measured("umx_hip_separate_tracks_loudness", waves, io, flags, shift_offsets, rates, gains, clip=clip,
+                                            levels=levels, loudness=loudness, envelopes=envelopes).results()
 
     # --- true peak of every output (DESIGN 26): the oversampled peak of what leaves, measured on the device; a rescale on it ---
     def separate_many_true_peak(self, waves, true_peak=TRUE_PEAK_MEASURE, clip=CLIP_CLAMP, io=None, flags=0, shift_offsets=None, rates=None,
                                 gains=None, levels=True, loudness=False, envelopes=False, records=True):
         """umx_hip_separate_tracks_true_peak: separate_many_loudness() with a true-peak mode -> (outputs, [Levels], [Loudness], [hop
         energies], [TruePeak per track]); levels / loudness / envelopes / records = False pass NULL and return None for them."""
-        nt = len(waves)
-        io = sample_io() if io is None else io
-        n_out, g = (4, None) if gains is None else _mix_gains(gains)
-        m = _TrackArgs(waves, io, n_out, shift_offsets, rates)
-        lv = (Levels * nt)() if levels else None
-        ld = (Loudness * nt)() if loudness else None
-        tp = (TruePeak * nt)() if records else None
-        env = ep = None
-        if envelopes:  # (a rate the call will refuse: any size does)
-            env = [np.full((m.n_host, 2, kweight_hop_count(L, r)), np.nan) for L, r in zip(m.Ls, rates or [MODEL_RATE] * nt)]
-            ep = (C.c_void_p * nt)(*[e.ctypes.data if e.size else None for e in env])
-        self._check(self.lib.umx_hip_separate_tracks_true_peak(self.h, nt, m.a, m.n, m.rt, m.sh, n_out,
-                                                               None if g is None else g.ctypes.data_as(_fp), m.o, flags, C.byref(io), int(clip), lv,
-                                                               ld, ep, int(true_peak), tp, None, None))
-        return m.result(), (list(lv) if levels else None), (list(ld) if loudness else None), env, (list(tp) if records else None)
+        return self._separate_many_measured("umx_hip_separate_tracks_true_peak", waves, io, flags, shift_offsets, rates, gains, clip=clip,
+                                            levels=levels, loudness=loudness, envelopes=envelopes, true_peak=true_peak, records=records).results()
 
     def true_peak_device(self, in_ptrs, n, rate, bits_ptr, first_frame=0, n_frames=None, hip_stream=None):
         """umx_hip_true_peak_device: frames [first_frame, first_frame + n_frames) of 1 .. 4 device buffers (2,n) interleaved fp32 into the
@@ -1115,59 +1123,36 @@ class Engine:
                 job[0].rate = int(rates[j])
             return 1
 
-        def _done(_user, job):
-            state["done"].append(int(job[0].tag) - 1)
+        got, loud, env, tps = [None] * nj, [None] * nj, [None] * nj, [None] * nj
 
+        def _done(_user, job, lv=None, ld=None, e=None, tp=None):  # fills whatever its entry point hands it (valid during the callback only)
+            j = int(job[0].tag) - 1
+            state["done"].append(j)
+            if lv is not None:
+                got[j] = Levels.from_buffer_copy(lv[0])
+            if ld is not None:
+                loud[j] = Loudness.from_buffer_copy(ld[0])
+                h = int(loud[j].hops)
+                env[j] = (np.ctypeslib.as_array(e, shape=(n_out * 2 * h,)).copy() if h else np.zeros(0)).reshape(n_out, 2, h)
+            if tp is not None:
+                tps[j] = TruePeak.from_buffer_copy(tp[0])
+
+        # the entry point a combination chooses: its done type, what follows `flags`, and what is returned beside the outputs
+        io_ref, clip_mode = None if io is None else C.byref(io), int(clip or CLIP_CLAMP)
         if true_peak is not None:
-            got, loud, env, tps = [None] * nj, [None] * nj, [None] * nj, [None] * nj
-
-            def _done_true_peak(_user, job, lv, ld, e, tp):
-                _done(_user, job)
-                j = int(job[0].tag) - 1
-                got[j], loud[j], tps[j] = Levels.from_buffer_copy(lv[0]), Loudness.from_buffer_copy(ld[0]), TruePeak.from_buffer_copy(tp[0])
-                h = int(loud[j].hops)
-                env[j] = (np.ctypeslib.as_array(e, shape=(n_out * 2 * h,)).copy() if h else np.zeros(0)).reshape(n_out, 2, h)
-
-            self._check(self.lib.umx_hip_separate_queue_true_peak(self.h, QUEUE_NEXT_FN(_next), QUEUE_TRUE_PEAK_FN(_done_true_peak), None, n_out,
-                                                                  None if g is None else g.ctypes.data_as(_fp), flags,
-                                                                  None if io is None else C.byref(io), int(clip or CLIP_CLAMP), int(true_peak)))
-            assert sorted(state["done"]) == list(range(nj)), state
-            return m.result(), got, loud, env, tps
-        if loudness:
-            got, loud, env = [None] * nj, [None] * nj, [None] * nj
-
-            def _done_loudness(_user, job, lv, ld, e):
-                _done(_user, job)
-                j = int(job[0].tag) - 1
-                got[j], loud[j] = Levels.from_buffer_copy(lv[0]), Loudness.from_buffer_copy(ld[0])  # (valid during the callback only)
-                h = int(loud[j].hops)
-                env[j] = (np.ctypeslib.as_array(e, shape=(n_out * 2 * h,)).copy() if h else np.zeros(0)).reshape(n_out, 2, h)
-
-            self._check(self.lib.umx_hip_separate_queue_loudness(self.h, QUEUE_NEXT_FN(_next), QUEUE_LOUDNESS_FN(_done_loudness), None, n_out,
-                                                                 None if g is None else g.ctypes.data_as(_fp), flags,
-                                                                 None if io is None else C.byref(io), int(clip or CLIP_CLAMP)))
-            assert sorted(state["done"]) == list(range(nj)), state
-            return m.result(), got, loud, env
-        if clip is not None or levels:
-            got = [None] * nj
-
-            def _done_levels(_user, job, lv):
-                _done(_user, job)
-                got[int(job[0].tag) - 1] = Levels.from_buffer_copy(lv[0])  # (valid during the callback only)
-
-            self._check(self.lib.umx_hip_separate_queue_levels(self.h, QUEUE_NEXT_FN(_next), QUEUE_LEVELS_FN(_done_levels), None, n_out,
-                                                               None if g is None else g.ctypes.data_as(_fp), flags,
-                                                               None if io is None else C.byref(io), int(clip or CLIP_CLAMP)))
-            assert sorted(state["done"]) == list(range(nj)), state
-            return m.result(), got
-        if io is None:
-            self._check(self.lib.umx_hip_separate_queue(self.h, QUEUE_NEXT_FN(_next), QUEUE_DONE_FN(_done), None, n_out,
-                                                        None if g is None else g.ctypes.data_as(_fp), flags))
+            entry, fn, tail, recs = "umx_hip_separate_queue_true_peak", QUEUE_TRUE_PEAK_FN, (io_ref, clip_mode, int(true_peak)), (got, loud, env, tps)
+        elif loudness:
+            entry, fn, tail, recs = "umx_hip_separate_queue_loudness", QUEUE_LOUDNESS_FN, (io_ref, clip_mode), (got, loud, env)
+        elif clip is not None or levels:
+            entry, fn, tail, recs = "umx_hip_separate_queue_levels", QUEUE_LEVELS_FN, (io_ref, clip_mode), (got,)
+        elif io is not None:
+            entry, fn, tail, recs = "umx_hip_separate_queue_io", QUEUE_DONE_FN, (io_ref,), ()
         else:
-            self._check(self.lib.umx_hip_separate_queue_io(self.h, QUEUE_NEXT_FN(_next), QUEUE_DONE_FN(_done), None, n_out,
-                                                           None if g is None else g.ctypes.data_as(_fp), flags, C.byref(io)))
+            entry, fn, tail, recs = "umx_hip_separate_queue", QUEUE_DONE_FN, (), ()
+        self._check(getattr(self.lib, entry)(self.h, QUEUE_NEXT_FN(_next), fn(_done), None, n_out, None if g is None else g.ctypes.data_as(_fp),
+                                             flags, *tail))
         assert sorted(state["done"]) == list(range(nj)), state
-        return m.result()
+        return (m.result(),) + recs if recs else m.result()
 
     def queue_calls(self):
         """Calls of the segment loop the engine's last separate_queue made (umx_hip_debug_queue_calls); None: there has been none."""

@@ -594,10 +594,14 @@ struct umx_hip_ctx
         bool levels = false;            // the caller wants the record of what left
         bool loudness = false;          // loudness.h, DESIGN 21: the hop energies of what leaves are measured
         int true_peak = UMX_TRUE_PEAK_OFF; // true_peak.h, DESIGN 26: MEASURE: the true peak of what leaves is measured; RESCALE: and the divisor comes from it
+        bool true_peak_record = false;  // the caller wants the true-peak record
         int n_host() const { return mix ? mix->n_out : 4; } // host buffers per track
         bool rescale() const { return clip_mode == UMX_CLIP_RESCALE; }
         bool measures() const { return levels || rescale(); } // a rescaled track measures for its divisor whether or not the caller wants the record
         bool true_peak_rescale() const { return true_peak == UMX_TRUE_PEAK_RESCALE && rescale(); }
+        bool measures_true_peak() const { return true_peak != UMX_TRUE_PEAK_OFF; }
+        // a finished span goes through track_leave: something is measured or encoded on its way out
+        bool leaves_measured() const { return io.out_format != UMX_SAMPLE_F32 || measures() || loudness || measures_true_peak(); }
     };
     struct TrackRequest // what tracks() is asked for: n_tracks tracks, one per track lane
     {
@@ -611,7 +615,7 @@ struct umx_hip_ctx
         void (*progress)(float, void *) = nullptr;
         void *progress_user = nullptr;
         bool ensemble = false;       // the lanes are ONE track at n_tracks shift offsets, `out` the buffers of their mean
-        TrackOptions opt;            // (opt.levels, opt.loudness: whether the results below are wanted -- track_request, engine_cabi.h)
+        TrackOptions opt;            // (opt.levels, opt.loudness, opt.true_peak_record: whether the results below are wanted -- track_request, engine_cabi.h)
         umx_levels *levels = nullptr; // n_tracks records of what left, or nullptr: not wanted
         umx_loudness *loudness = nullptr; // loudness.h, DESIGN 21: n_tracks records, or nullptr
         double *const *hop_energy = nullptr; // per track nullptr or room for its hop energies; either of the two: the tracks are measured
@@ -654,6 +658,25 @@ struct umx_hip_ctx
         const float *fwd_taps = nullptr, *back_taps = nullptr;
     };
     int track_rate_plan(int rate, int length_at_rate, const char *too_long, TrackResample &rs, int &n44);
+    // The measuring state of a job: the K-weighted hop energies of what leaves go to acc->hopE (opt.loudness), its
+    // true peak to acc->tp (opt.true_peak), both over the caller's track as the caller sees it.
+    struct TrackMeasure
+    {
+        int rate = 0;            // the caller's rate: hop = kweight_hop(rate) frames; factor and reach of the interpolator
+        long long length = 0;    // frames of the caller's track at that rate
+        long long hops = 0;      // whole hops of it
+        long long hops_done = 0; // hops already launched
+        long long tp_done = 0;   // frames whose true peak is already launched
+        void begin(int rate_, long long length_at_rate)
+        {
+            rate = rate_;
+            length = length_at_rate;
+            hops = length / kweight_hop(rate);
+            restart();
+        }
+        void restart() { hops_done = tp_done = 0; } // admission, and the queue's restart: what was measured is zeroed and measured again
+        size_t hop_doubles(int n_host) const { return std::max<size_t>(1, (size_t)n_host * 2 * (size_t)hops); } // of acc->hopE
+    };
     struct TrackJob // a track resident on the device
     {
         const float *audio = nullptr; // on the host (opt.io.in_format UMX_SAMPLE_S16: int16 frames)
@@ -670,14 +693,7 @@ struct umx_hip_ctx
                                       // rescaled track -- mixed and downloaded whole behind the last segment)
         bool whole_region = false;    // not by_region, and track_call itself finishes it behind its last segment as ONE region: the
                                       // frames [lead, lead + length) (a rescaled track)
-        // DESIGN 21 (opt.loudness): the K-weighted hop energies of what leaves go to acc->hopE
-        int loud_rate = 0;            // the caller's rate: hop = kweight_hop(loud_rate) frames
-        long long loud_hops = 0;      // hops of the caller's track (its length at that rate / hop)
-        long long hops_done = 0;      // hops already launched (a restart begins again at 0)
-        // DESIGN 26 (opt.true_peak): the true peak of what leaves goes to acc->tp
-        int tp_rate = 0;              // the caller's rate: factor and reach of the interpolator
-        long long tp_length = 0;      // frames of the caller's track at that rate
-        long long tp_done = 0;        // frames already launched (a restart begins again at 0)
+        TrackMeasure m;               // where its loudness and true-peak launches stand (track_measure_grow)
     };
     struct TrackLane // a lane of one call: its job (nullptr: idle) and the padded frame at which its segment starts
     {
@@ -724,14 +740,23 @@ struct umx_hip_ctx
     int track_int_grow(TrackBufs &tb_, const umx_sample_io &io, size_t frames, int n_host);
     void track_encode(const TrackBufs &tb_, const umx_sample_io &io, int n_host, float *const src[4], size_t src_start, int count,
                       long long first_frame, umx_levels_acc *acc, hipStream_t st, const uint32_t *words = nullptr);
-    int track_levels_grow(TrackBufs &tb_);
+    int track_measure_grow(TrackBufs &tb_, TrackJob &j, int rate, int length_at_rate);
+    struct ZeroSpan
+    {
+        void *p;
+        size_t bytes;
+    };
+    static int track_measure_spans(const TrackJob &j, ZeroSpan spans[3]);
     int admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt, const float *audio, int rate, int length_at_rate, bool leaves_whole);
     void track_leave(TrackJob &j, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st);
-    hipError_t track_levels_report(const TrackJob &j, int n_host, umx_levels &lv);
-    int track_loudness_grow(TrackBufs &tb_, TrackJob &j, int rate, int length_at_rate, int n_host);
-    hipError_t track_loudness_report(const TrackJob &j, int n_host, std::vector<double> &E, umx_loudness &ld);
-    int track_true_peak_grow(TrackBufs &tb_, TrackJob &j, int rate, int length_at_rate);
-    hipError_t track_true_peak_report(const TrackJob &j, int n_host, umx_true_peak &tp);
+    struct TrackReport // what a job measured, on the host (track_report); only what its options asked for is filled
+    {
+        umx_levels lv = {};
+        umx_loudness ld = {};
+        std::vector<double> hopE;
+        umx_true_peak tp = {};
+    };
+    hipError_t track_report(const TrackJob &j, int n_host, TrackReport &r);
     hipError_t track_upload_until(TrackJob &j, long long padded_end, hipStream_t st);
     void track_mix(const MixSpec &mix, float *const stems[4], size_t stem_start, const float *in, size_t in_start, int count, hipStream_t st);
     hipError_t track_region_download(const TrackRegion &r, float *const *out_host);
@@ -739,12 +764,27 @@ struct umx_hip_ctx
     // track queue (engine_queue.h): B + 2 accumulator sets (in, out, sumw of TrackBufs; grow-only) lent to the jobs in flight
     std::vector<TrackBufs> qpool;
     int queue_calls = -1; // infer_batch calls of the last queue run
-    struct QueueDone // the done callback of a run: the plain one, or the one that receives every job's levels
-    {               // (opt.levels of the run), or (opt.loudness) the one that also receives the loudness record and the hop energies
+    struct QueueDone // the done callback of a run: the plain one, or the one that receives every job's levels, or (DESIGN
+    {               // 21) the one that also receives the loudness record and the hop energies, or the true-peak record as well
         umx_queue_done_fn plain = nullptr;
         umx_queue_levels_fn with_levels = nullptr;
         umx_queue_loudness_fn with_loudness = nullptr;
-        umx_queue_true_peak_fn with_true_peak = nullptr; // (levels, loudness, hop energies and the true-peak record)
+        umx_queue_true_peak_fn with_true_peak = nullptr;
+        explicit operator bool() const { return plain || with_levels || with_loudness || with_true_peak; }
+        // what the callback implies for every job of the run (opt.levels, opt.loudness): a wider callback receives the narrower records too
+        bool measures() const { return with_levels || loudness(); }
+        bool loudness() const { return with_loudness || with_true_peak; }
+        void call(void *user, const umx_queue_job *job, const TrackReport &r) const
+        {
+            if (with_true_peak)
+                with_true_peak(user, job, &r.lv, &r.ld, r.hopE.data(), &r.tp);
+            else if (with_loudness)
+                with_loudness(user, job, &r.lv, &r.ld, r.hopE.data());
+            else if (with_levels)
+                with_levels(user, job, &r.lv);
+            else
+                plain(user, job);
+        }
     };
     int queue(umx_queue_next_fn next, const QueueDone &done, void *user, const TrackOptions &opt, unsigned flags);
     int queue_run(umx_queue_next_fn next, const QueueDone &done, void *user, const TrackOptions &opt, unsigned flags);

@@ -332,8 +332,18 @@ int umx_hip_stream_set_layer(umx_hip_ctx *ctx, int layer, const float *host_src)
 // The ladder umx_hip_separate_tracks, _rate, _mix, _io, _levels, _loudness, _true_peak and the one-track forms are ONE path: the options of the
 // call are checked and recorded once (track_options_checked -> umx_hip_ctx::TrackOptions), the request is filled once (track_request;
 // its checks are tracks_once's), and separate_tracks does both.  A rung is its own preconditions, then that path with the arguments it
-// does not have at their neutral values -- NULL rate, gains, io, records, UMX_CLIP_CLAMP, UMX_TRUE_PEAK_OFF -- so a wider rung with neutral arguments IS
-// the rung below, field for field, by construction.  The queue entry points share queue_entry the same way.
+// does not have at their neutral values -- NULL rate, gains and io, and of what is measured (MeasureArgs) only the fields
+// the rung has, the others at the record's defaults -- so a wider rung with neutral arguments IS the rung below, field for field, by
+// construction.  The queue entry points share queue_entry the same way.
+struct MeasureArgs // what a whole-track call measures and where the results go: the defaults are the call that measures nothing
+{
+    int clip_mode = UMX_CLIP_CLAMP;       // levels.h, DESIGN 20
+    umx_levels *levels = nullptr;         // n_tracks records, or NULL
+    umx_loudness *loudness = nullptr;     // loudness.h, DESIGN 21: n_tracks records, or NULL
+    double *const *hop_energy = nullptr;  // per track NULL or room for its hop energies
+    int true_peak_mode = UMX_TRUE_PEAK_OFF; // true_peak.h, DESIGN 26
+    umx_true_peak *true_peak = nullptr;   // n_tracks records, or NULL
+};
 static const char *mix_refusal(int n_out, const float *gains, MixSpec &spec) // (NULL gains are refused: who takes "no mix" asks before)
 {
     return mix_spec_from(n_out, gains, &spec) >= 0 ? nullptr
@@ -350,62 +360,58 @@ static bool mix_checked(umx_hip_ctx *ctx, int n_out, const float *gains, MixSpec
 // The options of a call, checked in this order: the sample formats (pcm16.h; io == NULL or fp32 both ways: the fp32 call itself), the
 // clip mode (levels.h), the gains (stem_mix.h; NULL: no mix), the true-peak mode (true_peak.h).  true: `opt` holds them, `spec` the matrix behind opt.mix; false: the
 // refusal is the context's error.
-static bool track_options_checked(umx_hip_ctx *ctx, const umx_sample_io *io, int clip_mode, int n_out, const float *gains, MixSpec &spec,
-                                  umx_hip_ctx::TrackOptions &opt, int true_peak_mode = UMX_TRUE_PEAK_OFF)
+static bool track_options_checked(umx_hip_ctx *ctx, const umx_sample_io *io, const MeasureArgs &ma, int n_out, const float *gains, MixSpec &spec,
+                                  umx_hip_ctx::TrackOptions &opt)
 {
     const char *why = sample_io_refusal(io);
     if (!why)
-        why = clip_mode_refusal(clip_mode);
+        why = clip_mode_refusal(ma.clip_mode);
     if (!why && gains)
         why = mix_refusal(n_out, gains, spec);
     if (!why)
-        why = true_peak_mode_refusal(true_peak_mode, clip_mode);
+        why = true_peak_mode_refusal(ma.true_peak_mode, ma.clip_mode);
     if (why)
     {
         ctx->set_error(why);
         return false;
     }
-    opt.true_peak = true_peak_mode;
+    opt.true_peak = ma.true_peak_mode;
     opt.mix = gains ? &spec : nullptr;
     if (io)
         opt.io = *io;
-    opt.clip_mode = clip_mode;
+    opt.clip_mode = ma.clip_mode;
     return true;
 }
 
 // (the request keeps its float pointers: the formats say how the driver reads them; a wanted record makes the tracks measure)
 static umx_hip_ctx::TrackRequest track_request(int n_tracks, const void *const *audio_host, const int *length, const int *rate,
                                                const int *shift_offset, void *const *out_host, unsigned flags, void (*progress)(float, void *),
-                                               void *progress_user, const umx_hip_ctx::TrackOptions &opt, umx_levels *levels = nullptr,
-                                               umx_loudness *loudness = nullptr, double *const *hop_energy = nullptr,
-                                               umx_true_peak *true_peak = nullptr)
+                                               void *progress_user, const umx_hip_ctx::TrackOptions &opt, const MeasureArgs &ma)
 {
     umx_hip_ctx::TrackRequest rq = {n_tracks, reinterpret_cast<const float *const *>(audio_host), length, rate, shift_offset,
                                     reinterpret_cast<float *const *>(out_host), flags, progress, progress_user};
     rq.opt = opt;
-    rq.opt.levels = levels != nullptr;
-    rq.opt.loudness = loudness || hop_energy; // the records or the energies themselves
-    rq.levels = levels;
-    rq.loudness = loudness;
-    rq.hop_energy = hop_energy;
-    rq.true_peak = true_peak; // DESIGN 26 (whether the tracks are measured: opt.true_peak, the mode)
+    rq.opt.levels = ma.levels != nullptr;
+    rq.opt.loudness = ma.loudness || ma.hop_energy; // the records or the energies themselves
+    rq.opt.true_peak_record = ma.true_peak != nullptr; // DESIGN 26 (whether the tracks are measured: opt.true_peak, the mode)
+    rq.levels = ma.levels;
+    rq.loudness = ma.loudness;
+    rq.hop_energy = ma.hop_energy;
+    rq.true_peak = ma.true_peak;
     return rq;
 }
 
 static int separate_tracks(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
                            const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
-                           const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness, double *const *hop_energy,
-                           void (*progress)(float, void *), void *progress_user, int true_peak_mode = UMX_TRUE_PEAK_OFF,
-                           umx_true_peak *true_peak = nullptr)
+                           const umx_sample_io *io, const MeasureArgs &ma, void (*progress)(float, void *), void *progress_user)
 {
     if (!ctx)
         return UMX_ERR_ARG;
     MixSpec spec;
     umx_hip_ctx::TrackOptions opt;
-    if (!track_options_checked(ctx, io, clip_mode, n_out, gains, spec, opt, true_peak_mode))
+    if (!track_options_checked(ctx, io, ma, n_out, gains, spec, opt))
         return UMX_ERR_ARG;
-    return ctx->tracks(track_request(n_tracks, audio_host, length, rate, shift_offset, out_host, flags, progress, progress_user, opt, levels,
-                                     loudness, hop_energy, true_peak));
+    return ctx->tracks(track_request(n_tracks, audio_host, length, rate, shift_offset, out_host, flags, progress, progress_user, opt, ma));
 }
 // the rungs without sample formats: fp32 buffers, no clip handling, nothing measured
 static int separate_tracks_f32(umx_hip_ctx *ctx, int n_tracks, const float *const *audio_host, const int *length, const int *rate,
@@ -413,8 +419,7 @@ static int separate_tracks_f32(umx_hip_ctx *ctx, int n_tracks, const float *cons
                                void (*progress)(float, void *), void *progress_user)
 {
     return separate_tracks(ctx, n_tracks, reinterpret_cast<const void *const *>(audio_host), length, rate, shift_offset, n_out, gains,
-                           reinterpret_cast<void *const *>(out_host), flags, nullptr, UMX_CLIP_CLAMP, nullptr, nullptr, nullptr, progress,
-                           progress_user);
+                           reinterpret_cast<void *const *>(out_host), flags, nullptr, MeasureArgs(), progress, progress_user);
 }
 
 // A one-track entry point passes the addresses of its own arguments; shift offset < 0: no shift buffer (plain split_inference).
@@ -537,7 +542,7 @@ static int shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length,
 {
     MixSpec spec;
     umx_hip_ctx::TrackOptions opt;
-    if (!track_options_checked(ctx, nullptr, UMX_CLIP_CLAMP, n_out, gains, spec, opt))
+    if (!track_options_checked(ctx, nullptr, MeasureArgs(), n_out, gains, spec, opt))
         return UMX_ERR_ARG;
     if (!umx_hip_ctx::track_job_ok(audio_host, length, 0, out_host, opt.n_host()))
     {
@@ -576,7 +581,7 @@ static int shift_ensemble(umx_hip_ctx *ctx, const float *audio_host, int length,
         rates[k] = rate;
     }
     umx_hip_ctx::TrackRequest rq = track_request(n_shifts, audio, lengths, rates, off, reinterpret_cast<void *const *>(out_host), flags, progress,
-                                                 progress_user, opt);
+                                                 progress_user, opt, MeasureArgs());
     rq.ensemble = n_shifts > 1;
     return ctx->tracks(rq);
 }
@@ -611,25 +616,30 @@ int umx_hip_shift_ensemble_mix(umx_hip_ctx *ctx, const float *audio_host, int le
 }
 
 // ---------------------------------------------------------------- track queue (engine_queue.h)
-// The five queue entry points differ in their done callback, and with it in what every job measures: a levels or loudness callback
-// makes every job measure.  Their options are checked as a track call's.
+// The five queue entry points differ in their done callback, and with it in what every job measures: a levels, loudness or true-peak
+// callback makes every job measure what it receives (QueueDone::measures, ::loudness).  Their options are checked
+// as a track call's.
 static int queue_entry(umx_hip_ctx *ctx, umx_queue_next_fn next, const umx_hip_ctx::QueueDone &done, void *user, int n_out, const float *gains,
-                       unsigned flags, const umx_sample_io *io, int clip_mode, int true_peak_mode = UMX_TRUE_PEAK_OFF)
+                       unsigned flags, const umx_sample_io *io, int clip_mode, int true_peak_mode)
 {
     if (!ctx)
         return UMX_ERR_ARG;
+    MeasureArgs ma;
+    ma.clip_mode = clip_mode;
+    ma.true_peak_mode = true_peak_mode;
     MixSpec spec;
     umx_hip_ctx::TrackOptions opt;
-    if (!track_options_checked(ctx, io, clip_mode, n_out, gains, spec, opt, true_peak_mode))
+    if (!track_options_checked(ctx, io, ma, n_out, gains, spec, opt))
         return UMX_ERR_ARG;
-    opt.levels = done.with_levels || done.with_loudness || done.with_true_peak;
-    opt.loudness = done.with_loudness || done.with_true_peak;
+    opt.levels = done.measures();
+    opt.loudness = done.loudness();
+    opt.true_peak_record = done.with_true_peak != nullptr;
     return ctx->queue(next, done, user, opt, flags);
 }
 int umx_hip_separate_queue(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_done_fn done, void *user, int n_out, const float *gains,
                            unsigned flags)
 {
-    return queue_entry(ctx, next, {done, nullptr, nullptr}, user, n_out, gains, flags, nullptr, UMX_CLIP_CLAMP);
+    return queue_entry(ctx, next, {done}, user, n_out, gains, flags, nullptr, UMX_CLIP_CLAMP, UMX_TRUE_PEAK_OFF);
 }
 
 // ---------------------------------------------------------------- 16-bit PCM in and out (pcm16.h)
@@ -638,14 +648,14 @@ int umx_hip_separate_tracks_io(umx_hip_ctx *ctx, int n_tracks, const void *const
                                const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
                                const umx_sample_io *io, void (*progress)(float, void *), void *progress_user)
 {
-    return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, UMX_CLIP_CLAMP, nullptr, nullptr,
-                           nullptr, progress, progress_user);
+    return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, MeasureArgs(), progress,
+                           progress_user);
 }
 
 int umx_hip_separate_queue_io(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_done_fn done, void *user, int n_out, const float *gains,
                               unsigned flags, const umx_sample_io *io)
 {
-    return queue_entry(ctx, next, {done, nullptr, nullptr}, user, n_out, gains, flags, io, UMX_CLIP_CLAMP);
+    return queue_entry(ctx, next, {done}, user, n_out, gains, flags, io, UMX_CLIP_CLAMP, UMX_TRUE_PEAK_OFF);
 }
 
 int umx_hip_pcm16_decode_device(umx_hip_ctx *ctx, const int16_t *in_dev, int n, float *out_dev, void *hip_stream)
@@ -695,14 +705,14 @@ int umx_hip_separate_tracks_levels(umx_hip_ctx *ctx, int n_tracks, const void *c
                                    const umx_sample_io *io, int clip_mode, umx_levels *levels, void (*progress)(float, void *),
                                    void *progress_user)
 {
-    return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, clip_mode, levels, nullptr, nullptr,
-                           progress, progress_user);
+    const MeasureArgs ma = {clip_mode, levels};
+    return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, ma, progress, progress_user);
 }
 
 int umx_hip_separate_queue_levels(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_levels_fn done, void *user, int n_out,
                                   const float *gains, unsigned flags, const umx_sample_io *io, int clip_mode)
 {
-    return queue_entry(ctx, next, {nullptr, done, nullptr}, user, n_out, gains, flags, io, clip_mode);
+    return queue_entry(ctx, next, {nullptr, done}, user, n_out, gains, flags, io, clip_mode, UMX_TRUE_PEAK_OFF);
 }
 
 int umx_hip_levels_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, long long first_frame,
@@ -775,14 +785,14 @@ int umx_hip_separate_tracks_loudness(umx_hip_ctx *ctx, int n_tracks, const void 
                                      const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,
                                      double *const *hop_energy, void (*progress)(float, void *), void *progress_user)
 {
-    return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, clip_mode, levels, loudness,
-                           hop_energy, progress, progress_user);
+    const MeasureArgs ma = {clip_mode, levels, loudness, hop_energy};
+    return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, ma, progress, progress_user);
 }
 
 int umx_hip_separate_queue_loudness(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_loudness_fn done, void *user, int n_out,
                                     const float *gains, unsigned flags, const umx_sample_io *io, int clip_mode)
 {
-    return queue_entry(ctx, next, {nullptr, nullptr, done}, user, n_out, gains, flags, io, clip_mode);
+    return queue_entry(ctx, next, {nullptr, nullptr, done}, user, n_out, gains, flags, io, clip_mode, UMX_TRUE_PEAK_OFF);
 }
 
 // ---------------------------------------------------------------- true peak of every output (true_peak.h)
@@ -793,8 +803,8 @@ int umx_hip_separate_tracks_true_peak(umx_hip_ctx *ctx, int n_tracks, const void
                                       double *const *hop_energy, int true_peak_mode, umx_true_peak *true_peak,
                                       void (*progress)(float, void *), void *progress_user)
 {
-    return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, clip_mode, levels, loudness,
-                           hop_energy, progress, progress_user, true_peak_mode, true_peak);
+    const MeasureArgs ma = {clip_mode, levels, loudness, hop_energy, true_peak_mode, true_peak};
+    return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, ma, progress, progress_user);
 }
 
 int umx_hip_separate_queue_true_peak(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_true_peak_fn done, void *user, int n_out,

@@ -3,8 +3,10 @@
 // This file holds what only a queue has: the schedule (QueueSchedule, umx_hip_queue_plan), the pool of accumulator sets lent to the
 // jobs in flight, the in-stream zeroing of a refilled lane, the download of the previous call's regions behind every call, and the
 // restart after a timeout.  A job's checks, geometry and admission, the body of a call and the region list are those of engine_tracks.h
-// (track_job_ok, track_geometry, admit_job, track_call, TrackRegions); the options of a run are the TrackOptions record of engine.hip,
-// which every job keeps.  Included by engine.hip behind engine_tracks.h; not a stand-alone header.
+// (track_job_ok, track_geometry, admit_job, track_call, TrackRegions), and so is what a job measures: what is zeroed in
+// stream order (track_measure_spans), what a restart resets (TrackMeasure::restart) and what is read back (track_report) are stated
+// there; what the run's done callback implies and receives is QueueDone's (engine.hip).  The options of a run are the TrackOptions
+// record of engine.hip, which every job keeps.  Included by engine.hip behind engine_tracks.h; not a stand-alone header.
 // ---------------------------------------------------------------- track queue
 namespace
 {
@@ -70,7 +72,7 @@ int queue_plan(int n_lanes, int n_jobs, const int *seg_count, int *lane_out, int
 
 int umx_hip_ctx::queue(umx_queue_next_fn next, const QueueDone &done, void *user, const TrackOptions &opt, unsigned flags)
 {
-    if (!next || (!done.plain && !done.with_levels && !done.with_loudness && !done.with_true_peak))
+    if (!next || !done)
     {
         set_error("queue: need the next and the done callback");
         return UMX_ERR_ARG;
@@ -151,8 +153,7 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
         for (Job *jb : redo)
         {
             jb->uploaded = jb->done44 = jb->out_done = 0; // (a resampled job goes through the resampler again, from its host copy)
-            jb->hops_done = 0; // (its hop energies are zeroed with its accumulators and measured again)
-            jb->tp_done = 0;   // (likewise its true-peak words)
+            jb->m.restart(); // (what it measured is zeroed with its accumulators and measured again)
             jb->regions_left = jb->by_region ? jb->segs : 1;
         }
         for (int ln = 0; ln < B; ++ln)
@@ -211,30 +212,13 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
         }
         for (Job *jb : finished)
         {
-            if (opt.levels) // the job's records, behind its last region
+            TrackReport report; // what the job measured, behind its last region
+            if ((e = track_report(*jb, n_host, report)) != hipSuccess)
             {
-                umx_levels lv;
-                umx_loudness ld;
-                umx_true_peak tp = {};
-                std::vector<double> hopE;
-                if ((e = track_levels_report(*jb, n_host, lv)) == hipSuccess && opt.loudness)
-                    e = track_loudness_report(*jb, n_host, hopE, ld);
-                if (e == hipSuccess && opt.true_peak != UMX_TRUE_PEAK_OFF)
-                    e = track_true_peak_report(*jb, n_host, tp);
-                if (e != hipSuccess)
-                {
-                    set_error(std::string("queue: reading a job's levels failed: ") + hipGetErrorString(e));
-                    return UMX_ERR_HIP;
-                }
-                if (done.with_true_peak)
-                    done.with_true_peak(user, &jb->job, &lv, &ld, hopE.data(), &tp);
-                else if (done.with_loudness)
-                    done.with_loudness(user, &jb->job, &lv, &ld, hopE.data());
-                else
-                    done.with_levels(user, &jb->job, &lv);
+                set_error(std::string("queue: reading a job's levels failed: ") + hipGetErrorString(e));
+                return UMX_ERR_HIP;
             }
-            else
-                done.plain(user, &jb->job);
+            done.call(user, &jb->job, report);
             jb->live = false;
         }
         return 0;
@@ -376,12 +360,9 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
                 sp.n[7] = state_floats();
                 sp.count = TRACK_BEGIN_SPANS;
                 launch_track_begin(sp, st);
-                if (jb->opt.measures()) // ... and the set's record of what leaves (also on a restart: the job measures from zero again)
-                    (void)hipMemsetAsync(tb_.lev, 0, sizeof(umx_levels_acc), st);
-                if (jb->opt.loudness) // ... and its hop energies
-                    (void)hipMemsetAsync(tb_.hopE, 0, sizeof(double) * std::max<size_t>(1, (size_t)n_host * 2 * (size_t)jb->loud_hops), st);
-                if (jb->opt.true_peak != UMX_TRUE_PEAK_OFF) // ... and its true-peak words
-                    (void)hipMemsetAsync(tb_.tp, 0, 4 * sizeof(unsigned), st);
+                ZeroSpan spans[3]; // ... and what the job measures into (also on a restart: it measures from zero again)
+                for (int k = 0, n = track_measure_spans(*jb, spans); k < n; ++k)
+                    (void)hipMemsetAsync(spans[k].p, 0, spans[k].bytes, st);
             }
             nl = ln + 1;
         }

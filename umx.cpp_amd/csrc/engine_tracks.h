@@ -1,10 +1,12 @@
 // engine_tracks.h -- part of engine.hip (one translation unit: the kernels inline into their launchers): whole tracks on the device.
 // What every whole-track driver shares, stated once each -- the checks of a job (track_job_ok), its padded geometry (track_geometry),
 // the grow-only buffers (grow_only, on dfree, the one release beside dalloc), the admission of a job with the options of its call
-// (admit_job: what grows, in which order, and the by_region / whole_region rules; TrackOptions, engine.hip), what a finished span goes
-// through on its way out (track_leave), the body of one segment call (track_call) and the list of finished regions that owns its
-// events (TrackRegions, engine.hip) -- and the driver of umx_hip_split_inference / umx_hip_shift_inference / umx_hip_separate_tracks* /
-// umx_hip_shift_ensemble* (tracks, tracks_once): one track per lane, or the segments of one track as the lanes (reset mode).
+// (admit_job: what grows, in which order, and the by_region / whole_region rules; TrackOptions, engine.hip), the measuring side of a job
+// (its state TrackMeasure, engine.hip; track_measure_grow, what it checks and allocates; track_measure_spans, what it zeroes;
+// track_report, what comes back), what a finished span goes through on its way out (track_leave), the body of one segment call
+// (track_call) and the list of finished regions that owns its events (TrackRegions, engine.hip) -- and the driver of
+// umx_hip_split_inference / umx_hip_shift_inference / umx_hip_separate_tracks* / umx_hip_shift_ensemble* (tracks, tracks_once): one
+// track per lane, or the segments of one track as the lanes (reset mode).
 // The track queue is the other driver (engine_queue.h).  Included by engine.hip behind the definition of umx_hip_ctx; not a
 // stand-alone header.
 // ---------------------------------------------------------------- whole track
@@ -109,12 +111,6 @@ void umx_hip_ctx::track_encode(const TrackBufs &tb_, const umx_sample_io &io, in
     launch_encode(io.out_format, n_host, s, d, count, first_frame, io.dither != 0, io.dither_seed, acc, st, words);
 }
 
-// the set's record of what leaves (112 bytes, allocated once a job measures; the driver zeroes it with the accumulators)
-int umx_hip_ctx::track_levels_grow(TrackBufs &tb_)
-{
-    return tb_.lev ? UMX_OK : dalloc(&tb_.lev, 1, true);
-}
-
 // What every finished span of a job goes through behind its mix, on its way out: `count` frames of the first n_host of `src` from
 // frame src_start on, which are the frames from first_frame on of the caller's track.  They are measured (a job with levels), then
 // encoded into the set's int16 outputs (track_encode), or -- a rescaled job, whose span is the whole track, so that the record's
@@ -128,33 +124,31 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
     const umx_sample_io &io = j.opt.io;
     const int n_host = j.opt.n_host();
     const bool integer = io.out_format != UMX_SAMPLE_F32, rescale = j.opt.rescale();
+    TrackMeasure &m = j.m;
+    const long long end = first_frame + count;
+    const float2 *s0[4] = {}; // frame 0 of the caller's track
+    for (int t = 0; t < n_host; ++t)
+        s0[t] = reinterpret_cast<const float2 *>(src[t]) + src_start - first_frame;
     if (j.opt.loudness)
     {
-        const int hop = kweight_hop(j.loud_rate);
-        const long long final_hops = std::min<long long>((first_frame + count) / hop, j.loud_hops);
-        if (final_hops > j.hops_done)
+        const int hop = kweight_hop(m.rate);
+        const long long final_hops = std::min<long long>(end / hop, m.hops);
+        if (final_hops > m.hops_done)
         {
-            const float2 *s0[4] = {};
-            for (int t = 0; t < n_host; ++t)
-                s0[t] = reinterpret_cast<const float2 *>(src[t]) + src_start - first_frame;
-            launch_kweight_hops(n_host, s0, kweight_coeffs(j.loud_rate), hop, j.loud_hops, j.hops_done, final_hops - j.hops_done, tb_.hopE, st);
-            j.hops_done = final_hops;
+            launch_kweight_hops(n_host, s0, kweight_coeffs(m.rate), hop, m.hops, m.hops_done, final_hops - m.hops_done, tb_.hopE, st);
+            m.hops_done = final_hops;
         }
     }
     // A job with a true peak: next, and before any divisor, the frames whose window these frames complete -- frame k once
     // frame k + 24/F is final, every frame on the job's last span (what lies behind the track reads as +0).  The window reaches back
     // into the spans before this one, which are still in `src` as above; the launch is told that the buffers end where this span does.
-    if (j.opt.true_peak != UMX_TRUE_PEAK_OFF)
+    if (j.opt.measures_true_peak())
     {
-        const long long end = first_frame + count;
-        const long long fin = end >= j.tp_length ? j.tp_length : std::max<long long>(end - true_peak_reach(true_peak_factor(j.tp_rate)), 0);
-        if (fin > j.tp_done)
+        const long long fin = end >= m.length ? m.length : std::max<long long>(end - true_peak_reach(true_peak_factor(m.rate)), 0);
+        if (fin > m.tp_done)
         {
-            const float2 *s0[4] = {};
-            for (int t = 0; t < n_host; ++t)
-                s0[t] = reinterpret_cast<const float2 *>(src[t]) + src_start - first_frame;
-            launch_true_peak(n_host, s0, (int)std::min(end, j.tp_length), j.tp_rate, j.tp_done, fin - j.tp_done, tb_.tp, st);
-            j.tp_done = fin;
+            launch_true_peak(n_host, s0, (int)std::min(end, m.length), m.rate, m.tp_done, fin - m.tp_done, tb_.tp, st);
+            m.tp_done = fin;
         }
     }
     if (!j.opt.measures())
@@ -177,67 +171,89 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
         launch_stem_rescale(n_host, sw, count, words, st);
 }
 
-// the job's record to the host (its last launch has finished: the caller has waited for the job's last region), as the call reports it
-hipError_t umx_hip_ctx::track_levels_report(const TrackJob &j, int n_host, umx_levels &lv)
+// What a job measured, to the host (its last launch has finished: the caller has waited for the job's last region), as the call
+// reports it -- whatever j.opt says was measured, in this order: the levels record (under UMX_TRUE_PEAK_RESCALE the gain
+// is the divisor of the true-peak words), the hop energies and the loudness record formed from them, the
+// true-peak words (where the record is wanted).
+hipError_t umx_hip_ctx::track_report(const TrackJob &j, int n_host, TrackReport &r)
 {
-    umx_levels_acc acc;
-    uint32_t words[4];
-    hipError_t e = hipMemcpy(&acc, j.acc->lev, sizeof acc, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && j.opt.true_peak_rescale()) // (the gain is the divisor of the true-peak words)
-        e = hipMemcpy(words, j.acc->tp, sizeof words, hipMemcpyDeviceToHost);
-    if (e == hipSuccess)
-        levels_report(acc, n_host, j.opt.rescale(), j.opt.true_peak_rescale() ? words : acc.peak_bits, lv);
-    return e;
-}
-
-// the job measures its true peak at the caller's `rate`, over its length_at_rate frames there; the set's four words
-// (allocated once a job asks; the driver zeroes them with the levels record)
-int umx_hip_ctx::track_true_peak_grow(TrackBufs &tb_, TrackJob &j, int rate, int length_at_rate)
-{
-    if (!true_peak_rate_ok(rate))
-    {
-        set_error("true peak: sample rate outside 8000 .. 192000 Hz");
-        return UMX_ERR_ARG;
-    }
-    if (length_at_rate > 0x7fffffff / 2) // (the kernel counts frames in an int, with room for a tile and its halo beyond the last)
-    {
-        set_error("true peak: track too long");
-        return UMX_ERR_ARG;
-    }
-    j.tp_rate = rate;
-    j.tp_length = length_at_rate;
-    j.tp_done = 0;
-    return tb_.tp ? UMX_OK : dalloc(&tb_.tp, 4, true);
-}
-
-// the job's true-peak words to the host (its last launch has finished, as for track_levels_report), as the call reports them
-hipError_t umx_hip_ctx::track_true_peak_report(const TrackJob &j, int n_host, umx_true_peak &tp)
-{
+    const TrackOptions &opt = j.opt;
     uint32_t words[4] = {};
-    const hipError_t e = hipMemcpy(words, j.acc->tp, sizeof words, hipMemcpyDeviceToHost);
-    if (e == hipSuccess)
-        true_peak_report(words, n_host, true_peak_factor(j.tp_rate), tp);
+    hipError_t e = hipSuccess;
+    if (opt.levels)
+    {
+        umx_levels_acc acc;
+        e = hipMemcpy(&acc, j.acc->lev, sizeof acc, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && opt.true_peak_rescale())
+            e = hipMemcpy(words, j.acc->tp, sizeof words, hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            levels_report(acc, n_host, opt.rescale(), opt.true_peak_rescale() ? words : acc.peak_bits, r.lv);
+    }
+    if (e == hipSuccess && opt.loudness)
+    {
+        r.hopE.assign((size_t)n_host * 2 * (size_t)j.m.hops, 0.0);
+        if (!r.hopE.empty())
+            e = hipMemcpy(r.hopE.data(), j.acc->hopE, sizeof(double) * r.hopE.size(), hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            loudness_report(r.hopE.data(), j.m.hops, kweight_hop(j.m.rate), n_host, r.ld);
+    }
+    if (e == hipSuccess && opt.measures_true_peak() && opt.true_peak_record)
+    {
+        e = hipMemcpy(words, j.acc->tp, sizeof words, hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            true_peak_report(words, n_host, true_peak_factor(j.m.rate), r.tp);
+    }
     return e;
 }
 
-// the job measures loudness at the caller's `rate`, over its length_at_rate frames there; the set's hop energies
-// (n_host x 2 x hops doubles, grow-only, allocated once a job asks; the driver zeroes them with the accumulators)
-int umx_hip_ctx::track_loudness_grow(TrackBufs &tb_, TrackJob &j, int rate, int length_at_rate, int n_host)
+// The measuring side of an accumulator set for a job at the caller's `rate`, over its length_at_rate frames there (DESIGN 20, 21,
+// 26), checked and grown in this order: the record of what leaves (112 bytes, once a job measures), the hop energies (n_host x 2 x
+// hops doubles, grow-only, once a job measures loudness), the four true-peak words (once a job measures its true peak).  The driver
+// zeroes them with the accumulators (track_measure_spans).
+int umx_hip_ctx::track_measure_grow(TrackBufs &tb_, TrackJob &j, int rate, int length_at_rate)
 {
-    if (!kweight_rate_ok(rate))
+    const TrackOptions &opt = j.opt;
+    // (the kernels count frames in an int, with room for a workgroup's rows or a tile and its halo beyond the last)
+    auto refused = [&](const char *what, bool rate_ok) {
+        if (rate_ok && length_at_rate <= 0x7fffffff / 2)
+            return false;
+        set_error(std::string(what) + (rate_ok ? ": track too long" : ": sample rate outside 8000 .. 192000 Hz"));
+        return true;
+    };
+    if (opt.measures() && !tb_.lev)
+        if (int rc = dalloc(&tb_.lev, 1, true))
+            return rc;
+    if (opt.loudness)
     {
-        set_error("loudness: sample rate outside 8000 .. 192000 Hz");
-        return UMX_ERR_ARG;
+        if (refused("loudness", kweight_rate_ok(rate)))
+            return UMX_ERR_ARG;
+        j.m.begin(rate, length_at_rate);
+        if (int rc = grow_only<double>({{&tb_.hopE, 1}}, tb_.cap_hopE, j.m.hop_doubles(opt.n_host())))
+            return rc;
     }
-    if (length_at_rate > 0x7fffffff / 2) // (the kernel counts frames in an int, with room for a workgroup's rows beyond the last hop)
+    if (opt.measures_true_peak())
     {
-        set_error("loudness: track too long");
-        return UMX_ERR_ARG;
+        if (refused("true peak", true_peak_rate_ok(rate)))
+            return UMX_ERR_ARG;
+        j.m.begin(rate, length_at_rate);
+        if (!tb_.tp)
+            return dalloc(&tb_.tp, 4, true);
     }
-    j.loud_rate = rate;
-    j.loud_hops = length_at_rate / kweight_hop(rate);
-    j.hops_done = 0;
-    return grow_only<double>({{&tb_.hopE, 1}}, tb_.cap_hopE, std::max<size_t>(1, (size_t)n_host * 2 * (size_t)j.loud_hops));
+    return UMX_OK;
+}
+
+// What a measuring job zeroes before its first segment, in this order: the levels record, the hop energies, the true-peak words.
+// Returns how many of `spans` are filled.  tracks_once zeroes them with the accumulators, the queue on the stream of the job's first call.
+int umx_hip_ctx::track_measure_spans(const TrackJob &j, ZeroSpan spans[3])
+{
+    int n = 0;
+    if (j.opt.measures())
+        spans[n++] = {j.acc->lev, sizeof(umx_levels_acc)};
+    if (j.opt.loudness)
+        spans[n++] = {j.acc->hopE, sizeof(double) * j.m.hop_doubles(j.opt.n_host())};
+    if (j.opt.measures_true_peak())
+        spans[n++] = {j.acc->tp, 4 * sizeof(unsigned)};
+    return n;
 }
 
 // A job at `rate` != 44.1 kHz: n44, the length of its 44.1 kHz version, which the segments see, and the record that
@@ -261,8 +277,9 @@ int umx_hip_ctx::track_rate_plan(int rate, int length_at_rate, const char *too_l
 // The admission of a job, for both drivers (tracks_once; the queue, engine_queue.h): `j` has its geometry (track_geometry) and, at
 // another rate, its j.rs (track_rate_plan); `acc` is the accumulator set it will write, `audio` its host audio of length_at_rate
 // frames at `rate` -- the rate and length the caller sees --, leaves_whole: it is an ensemble lane.  The set grows by what the job
-// needs, in this order (a failed allocation returns at once): accumulators, native-rate staging (a job with j.rs), int16 side, levels
-// record, hop energies, true-peak words; then the job is filled.  What the driver zeroes, and on which stream, is the driver's.
+// needs, in this order (a failed allocation returns at once): accumulators, native-rate staging (a job with j.rs), int16 side, the
+// measuring side (track_measure_grow: levels record, hop energies, true-peak words); then the job is filled.  When the driver zeroes
+// what, and on which stream, is the driver's; what a measuring job zeroes is track_measure_spans.
 int umx_hip_ctx::admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt, const float *audio, int rate, int length_at_rate, bool leaves_whole)
 {
     j.opt = opt;
@@ -274,15 +291,8 @@ int umx_hip_ctx::admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt,
             return rc;
     if (int rc = track_int_grow(acc, opt.io, (size_t)length_at_rate, opt.n_host())) // (nothing for an fp32 call)
         return rc;
-    if (opt.measures())
-        if (int rc = track_levels_grow(acc))
-            return rc;
-    if (opt.loudness)
-        if (int rc = track_loudness_grow(acc, j, rate, length_at_rate, opt.n_host()))
-            return rc;
-    if (opt.true_peak != UMX_TRUE_PEAK_OFF)
-        if (int rc = track_true_peak_grow(acc, j, rate, length_at_rate))
-            return rc;
+    if (int rc = track_measure_grow(acc, j, rate, length_at_rate)) // (nothing for a call that measures nothing)
+        return rc;
     j.audio = audio;
     j.acc = &acc;
     // Its final regions are mixed in place and leave region by region (a resampled job's through the way back, range by range: DESIGN
@@ -291,16 +301,6 @@ int umx_hip_ctx::admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt,
     j.by_region = !leaves_whole && !opt.rescale();
     j.whole_region = opt.rescale() && !leaves_whole;
     return UMX_OK;
-}
-
-// the job's hop energies to the host (its last launch has finished, as for track_levels_report) and the record formed from them
-hipError_t umx_hip_ctx::track_loudness_report(const TrackJob &j, int n_host, std::vector<double> &E, umx_loudness &ld)
-{
-    E.assign((size_t)n_host * 2 * (size_t)j.loud_hops, 0.0);
-    const hipError_t e = E.empty() ? hipSuccess : hipMemcpy(E.data(), j.acc->hopE, sizeof(double) * E.size(), hipMemcpyDeviceToHost);
-    if (e == hipSuccess)
-        loudness_report(E.data(), j.loud_hops, kweight_hop(j.loud_rate), n_host, ld);
-    return e;
 }
 
 // The track goes up segment by segment (round 6): a call needs the samples up to the end of its last segment, and the rest of a
@@ -510,9 +510,8 @@ int umx_hip_ctx::track_call(const TrackLane *lanes, int nl, unsigned flags, int 
                 j->out_done = r;
             }
         }
-        else if (opt.io.out_format != UMX_SAMPLE_F32 || opt.measures() || opt.loudness || opt.true_peak != UMX_TRUE_PEAK_OFF) // the region's frames of the caller's track, as they will
-        {                                                    // leave (an int16 copy is not written over the accumulators: the next
-                                                             // segment's overlap-add still reads its neighbours)
+        else if (opt.leaves_measured()) // the region's frames of the caller's track, as they will leave (an int16 copy
+        {                               // is not written over the accumulators: the next segment's overlap-add still reads its neighbours)
             const long long lo = std::max<long long>(rg.start, j->lead), hi = std::min<long long>((long long)rg.start + rg.count, (long long)j->lead + j->length);
             if (hi > lo)
                 track_leave(*j, tb_.out, (size_t)lo, (int)(hi - lo), lo - j->lead, st);
@@ -551,23 +550,16 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     }
     if (int rc = check_flags(rq.flags))
         return rc;
-    const bool measure = opt.measures(), loud = opt.loudness;
-    if (measure && ensemble)
-    {
-        set_error("track: the shift ensemble does not offer levels or rescale");
-        return UMX_ERR_ARG;
-    }
-    if (loud && ensemble)
-    {
-        set_error("track: the shift ensemble does not offer loudness");
-        return UMX_ERR_ARG;
-    }
-    const bool tpeak = opt.true_peak != UMX_TRUE_PEAK_OFF;
-    if (tpeak && ensemble)
-    {
-        set_error("track: the shift ensemble does not offer the true peak");
-        return UMX_ERR_ARG;
-    }
+    const std::pair<bool, const char *> not_in_ensemble[] = {// DESIGN 20, 21, 26
+                                                             {opt.measures(), "track: the shift ensemble does not offer levels or rescale"},
+                                                             {opt.loudness, "track: the shift ensemble does not offer loudness"},
+                                                             {opt.measures_true_peak(), "track: the shift ensemble does not offer the true peak"}};
+    for (const auto &asked : not_in_ensemble)
+        if (asked.first && ensemble)
+        {
+            set_error(asked.second);
+            return UMX_ERR_ARG;
+        }
     for (int ln = 0; ln < nt; ++ln)
         if (!track_job_ok(rq.audio[ln], length_in[ln], rq.shift_offset[ln], rq.out && !ensemble ? rq.out + n_host * ln : rq.out, n_host))
         {
@@ -641,12 +633,9 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         for (int t = 0; t < 4; ++t)
             UMX_HIP_CHECK(hipMemset(tb_.out[t], 0, sizeof(float) * 2 * frames));
         UMX_HIP_CHECK(hipMemset(tb_.sumw, 0, sizeof(float) * frames));
-        if (measure)
-            UMX_HIP_CHECK(hipMemset(tb_.lev, 0, sizeof(umx_levels_acc)));
-        if (tpeak)
-            UMX_HIP_CHECK(hipMemset(tb_.tp, 0, 4 * sizeof(unsigned)));
-        if (loud)
-            UMX_HIP_CHECK(hipMemset(tb_.hopE, 0, sizeof(double) * std::max<size_t>(1, (size_t)n_host * 2 * (size_t)job[ln].loud_hops)));
+        ZeroSpan spans[3];
+        for (int k = 0, n = track_measure_spans(job[ln], spans); k < n; ++k)
+            UMX_HIP_CHECK(hipMemset(spans[k].p, 0, spans[k].bytes));
     }
     // A resampled track goes up and through the resampler range by range, with the call that needs the frames (track_upload_until) --
     // but an ensemble's: whole, now, in one launch, on the null stream.
@@ -775,19 +764,10 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         for (int t = 0; t < n_host && whole[ln][0] && cerr == hipSuccess; ++t) // (an ensemble's one result: lane 0)
             cerr = hipMemcpy(rq.out[n_host * ln + t], whole[ln][t], sample_frame_bytes(opt.io.out_format) * (size_t)length_in[ln],
                              hipMemcpyDeviceToHost);
-    // every job's record, once: its last measuring launch is behind its last region, which the host has
-    umx_levels reports[LSTMB_MAX_TRACKS];
-    for (int ln = 0; ln < nt && rq.levels && cerr == hipSuccess; ++ln)
-        cerr = track_levels_report(job[ln], n_host, reports[ln]);
-    // and its hop energies, once, from which the host forms the loudness record
-    umx_loudness loud_reports[LSTMB_MAX_TRACKS];
-    std::vector<double> hopE[LSTMB_MAX_TRACKS];
-    for (int ln = 0; ln < nt && loud && cerr == hipSuccess; ++ln)
-        cerr = track_loudness_report(job[ln], n_host, hopE[ln], loud_reports[ln]);
-    // and its true-peak words
-    umx_true_peak tp_reports[LSTMB_MAX_TRACKS];
-    for (int ln = 0; ln < nt && tpeak && rq.true_peak && cerr == hipSuccess; ++ln)
-        cerr = track_true_peak_report(job[ln], n_host, tp_reports[ln]);
+    // what every job measured, once: its last measuring launch is behind its last region, which the host has
+    std::vector<TrackReport> reports(nt);
+    for (int ln = 0; ln < nt && cerr == hipSuccess; ++ln)
+        cerr = track_report(job[ln], n_host, reports[ln]);
     if (cerr != hipSuccess)
     {
         set_error(hipGetErrorString(cerr));
@@ -796,15 +776,18 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     UMX_HIP_CHECK(hipGetLastError());
     if (int rc = umx_hip_sync(this)) // surfaces a persistent-kernel timeout
         return rc;
-    if (rq.levels) // (only what a run without a timeout measured is reported)
-        std::copy(reports, reports + nt, rq.levels);
-    if (rq.loudness)
-        std::copy(loud_reports, loud_reports + nt, rq.loudness);
-    if (rq.true_peak && tpeak)
-        std::copy(tp_reports, tp_reports + nt, rq.true_peak);
-    for (int ln = 0; ln < nt && rq.hop_energy; ++ln)
-        if (rq.hop_energy[ln])
-            std::copy(hopE[ln].begin(), hopE[ln].end(), rq.hop_energy[ln]);
+    for (int ln = 0; ln < nt; ++ln) // (only what a run without a timeout measured is handed out)
+    {
+        const TrackReport &r = reports[ln];
+        if (rq.levels)
+            rq.levels[ln] = r.lv;
+        if (rq.loudness)
+            rq.loudness[ln] = r.ld;
+        if (rq.hop_energy && rq.hop_energy[ln])
+            std::copy(r.hopE.begin(), r.hopE.end(), rq.hop_energy[ln]);
+        if (rq.true_peak && opt.measures_true_peak())
+            rq.true_peak[ln] = r.tp;
+    }
     return UMX_OK;
 }
 

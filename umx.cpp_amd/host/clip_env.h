@@ -32,6 +32,21 @@ struct umx_clip_choice
     bool active() const { return clip_mode != UMX_CLIP_CLAMP || levels || loudness || true_peak != UMX_TRUE_PEAK_OFF; } // false: the calls and the files of a run without the four
 };
 
+// One of the switches above: unset or empty leaves `value` alone, "0" / "1" (and, where `third` names one, that word) set it to 0 / 1
+// / 2; false, with a message that names the variable, for anything else
+inline bool umx_switch_parse(const char *name, const char *text, const char *third, int &value, std::string &err)
+{
+    if (!text || !*text)
+        return true;
+    if (strcmp(text, "0") && strcmp(text, "1") && !(third && !strcmp(text, third)))
+    {
+        err = std::string(name) + ": need 0" + (third ? std::string(", 1 or ") + third : std::string(" or 1")) + ", got \"" + text + "\"";
+        return false;
+    }
+    value = text[0] == '0' ? 0 : text[0] == '1' ? 1 : 2;
+    return true;
+}
+
 // false, with a message that names the variable, for a value outside the grammar above (nullptr: unset)
 inline bool umx_clip_parse(const char *clip, const char *levels, umx_clip_choice &c, std::string &err)
 {
@@ -46,100 +61,78 @@ inline bool umx_clip_parse(const char *clip, const char *levels, umx_clip_choice
             return false;
         }
     }
-    if (levels && *levels)
-    {
-        if (strcmp(levels, "0") && strcmp(levels, "1"))
-        {
-            err = std::string("UMX_LEVELS: need 0 or 1, got \"") + levels + "\"";
-            return false;
-        }
-        c.levels = levels[0] == '1';
-    }
+    int on = 0;
+    if (!umx_switch_parse("UMX_LEVELS", levels, nullptr, on, err))
+        return false;
+    c.levels = on != 0;
     return true;
 }
 
-// false: refused, message on stderr.  not_offered: the reason this run cannot take the two (nullptr: it can)
+// false: refused, message on stderr.  not_offered: the reason this run cannot take the two (nullptr: it can).  The variables are read
+// in this order, each parsed and then refused where the run cannot offer it: UMX_CLIP and UMX_LEVELS, UMX_LOUDNESS, UMX_TRUE_PEAK.
 inline bool umx_clip_from_env(umx_clip_choice &c, const char *not_offered)
 {
+    auto refuse = [](const std::string &why) {
+        fprintf(stderr, "%s\n", why.c_str());
+        return false;
+    };
+    const std::string no = not_offered ? not_offered : "";
     std::string err;
+    int loud = 0, tp = 0;
     if (!umx_clip_parse(getenv("UMX_CLIP"), getenv("UMX_LEVELS"), c, err))
-    {
-        fprintf(stderr, "%s\n", err.c_str());
-        return false;
-    }
+        return refuse(err);
     if (c.active() && not_offered)
-    {
-        fprintf(stderr, "UMX_CLIP / UMX_LEVELS: %s\n", not_offered);
-        return false;
-    }
-    if (const char *loud = getenv("UMX_LOUDNESS"))
-        if (*loud)
-        {
-            if (strcmp(loud, "0") && strcmp(loud, "1"))
-            {
-                fprintf(stderr, "UMX_LOUDNESS: need 0 or 1, got \"%s\"\n", loud);
-                return false;
-            }
-            c.loudness = loud[0] == '1';
-            if (c.loudness && not_offered)
-            {
-                fprintf(stderr, "UMX_LOUDNESS: %s (nor loudness)\n", not_offered);
-                return false;
-            }
-        }
-    if (const char *tp = getenv("UMX_TRUE_PEAK"))
-        if (*tp)
-        {
-            if (strcmp(tp, "0") && strcmp(tp, "1") && strcmp(tp, "rescale"))
-            {
-                fprintf(stderr, "UMX_TRUE_PEAK: need 0, 1 or rescale, got \"%s\"\n", tp);
-                return false;
-            }
-            c.true_peak = !strcmp(tp, "rescale") ? UMX_TRUE_PEAK_RESCALE : tp[0] == '1' ? UMX_TRUE_PEAK_MEASURE : UMX_TRUE_PEAK_OFF;
-            if (c.true_peak != UMX_TRUE_PEAK_OFF && not_offered)
-            {
-                fprintf(stderr, "UMX_TRUE_PEAK: %s (nor the true peak)\n", not_offered);
-                return false;
-            }
-            if (c.true_peak == UMX_TRUE_PEAK_RESCALE && c.clip_mode != UMX_CLIP_RESCALE)
-            {
-                fprintf(stderr, "UMX_TRUE_PEAK=rescale: needs UMX_CLIP=rescale (it says which peak the divisor comes from)\n");
-                return false;
-            }
-        }
+        return refuse("UMX_CLIP / UMX_LEVELS: " + no);
+    if (!umx_switch_parse("UMX_LOUDNESS", getenv("UMX_LOUDNESS"), nullptr, loud, err))
+        return refuse(err);
+    c.loudness = loud != 0;
+    if (c.loudness && not_offered)
+        return refuse("UMX_LOUDNESS: " + no + " (nor loudness)");
+    if (!umx_switch_parse("UMX_TRUE_PEAK", getenv("UMX_TRUE_PEAK"), "rescale", tp, err))
+        return refuse(err);
+    c.true_peak = tp == 2 ? UMX_TRUE_PEAK_RESCALE : tp == 1 ? UMX_TRUE_PEAK_MEASURE : UMX_TRUE_PEAK_OFF;
+    if (c.true_peak != UMX_TRUE_PEAK_OFF && not_offered)
+        return refuse("UMX_TRUE_PEAK: " + no + " (nor the true peak)");
+    if (c.true_peak == UMX_TRUE_PEAK_RESCALE && c.clip_mode != UMX_CLIP_RESCALE)
+        return refuse("UMX_TRUE_PEAK=rescale: needs UMX_CLIP=rescale (it says which peak the divisor comes from)");
     return true;
 }
 
-// the line of output m of a track, written to `file`
-inline void umx_levels_print(const char *file, const umx_levels &lv, int m)
+// what a run measured of one track: the records its choice asked for are filled
+struct umx_measured
 {
-    printf("levels %s peak=%.9g over_unity=%llu clipped=%llu nonfinite=%llu gain=%.9g\n", file, (double)lv.peak[m], lv.over_unity[m], lv.clipped[m],
-           lv.nonfinite[m], (double)lv.gain);
-}
+    umx_levels levels = {};
+    umx_loudness loudness = {};
+    umx_true_peak true_peak = {};
+};
 
-// the loudness line of output m of a track, written to `file`
-inline void umx_loudness_print(const char *file, const umx_loudness &ld, int m)
+// the lines of output m of a track, written to `file`, that the run asked for: levels, loudness, true peak
+inline void umx_measured_print(const char *file, const umx_clip_choice &c, const umx_measured &rec, int m)
 {
-    auto lufs = [](double v, char *buf, size_t cap) { // (-inf by name: printf's spelling of it is the C library's)
-        if (std::isinf(v))
-            snprintf(buf, cap, v < 0 ? "-inf" : "inf");
+    auto named = [](double v, bool none, char *buf, size_t cap) { // (-inf by name: printf's spelling of it is the C library's)
+        if (none || std::isinf(v))
+            snprintf(buf, cap, "%s", none || v < 0 ? "-inf" : "inf");
         else
             snprintf(buf, cap, "%.6f", v);
     };
     char a[40], b[40];
-    lufs(ld.integrated[m], a, sizeof a);
-    lufs(ld.momentary_max[m], b, sizeof b);
-    printf("loudness %s integrated=%s momentary_max=%s blocks=%lld gated=%lld\n", file, a, b, ld.blocks[m], ld.gated[m]);
-}
-
-// the true-peak line of output m of a track, written to `file`
-inline void umx_true_peak_print(const char *file, const umx_true_peak &tp, int m)
-{
-    const double v = tp.true_peak[m];
-    char a[40];
-    if (v == 0 || std::isinf(v)) // (-inf by name, as the loudness line)
-        snprintf(a, sizeof a, "%s", v == 0 ? "-inf" : "inf");
-    else
-        snprintf(a, sizeof a, "%.6f", 20.0 * std::log10(v));
-    printf("true_peak %s dbtp=%s linear=%.9g factor=%d\n", file, a, v, tp.factor);
+    if (c.levels)
+    {
+        const umx_levels &lv = rec.levels;
+        printf("levels %s peak=%.9g over_unity=%llu clipped=%llu nonfinite=%llu gain=%.9g\n", file, (double)lv.peak[m], lv.over_unity[m], lv.clipped[m],
+               lv.nonfinite[m], (double)lv.gain);
+    }
+    if (c.loudness)
+    {
+        const umx_loudness &ld = rec.loudness;
+        named(ld.integrated[m], false, a, sizeof a);
+        named(ld.momentary_max[m], false, b, sizeof b);
+        printf("loudness %s integrated=%s momentary_max=%s blocks=%lld gated=%lld\n", file, a, b, ld.blocks[m], ld.gated[m]);
+    }
+    if (c.true_peak != UMX_TRUE_PEAK_OFF)
+    {
+        const double v = rec.true_peak.true_peak[m];
+        named(20.0 * std::log10(v), v == 0, a, sizeof a); // (a true peak of 0: -inf dBTP)
+        printf("true_peak %s dbtp=%s linear=%.9g factor=%d\n", file, a, v, rec.true_peak.factor);
+    }
 }

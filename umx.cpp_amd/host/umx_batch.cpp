@@ -59,9 +59,7 @@ struct FileJob
                                 // 24-bit frames of 6 bytes behind this pointer: load_int below)
     std::vector<std::vector<float>> stems;
     std::vector<std::vector<int16_t>> stems16; // UMX_PCM16 / UMX_PCM24: the outputs as they are written (2 or 3 int16 units a frame)
-    umx_levels levels = {};                    // UMX_CLIP / UMX_LEVELS: what the queue measured
-    umx_loudness loudness = {};                // UMX_LOUDNESS: likewise
-    umx_true_peak true_peak = {};              // UMX_TRUE_PEAK: likewise
+    umx_measured measured;                     // UMX_CLIP / UMX_LEVELS, UMX_LOUDNESS, UMX_TRUE_PEAK: what the queue measured
 };
 struct BatchQueue
 {
@@ -124,21 +122,27 @@ struct BatchQueue
         q.unwritten.push_back(fj);
         q.cv.notify_all();
     }
-    static void done_levels(void *user, const umx_queue_job *job, const umx_levels *levels) // (valid during the callback only)
+    // the measuring queues' callbacks: the records they are given (valid during the callback only) are kept with the file
+    static void done_measured(void *user, const umx_queue_job *job, const umx_levels *levels, const umx_loudness *loudness,
+                              const umx_true_peak *true_peak)
     {
-        static_cast<FileJob *>(job->tag)->levels = *levels;
+        umx_measured &m = static_cast<FileJob *>(job->tag)->measured;
+        m.levels = *levels;
+        if (loudness)
+            m.loudness = *loudness;
+        if (true_peak)
+            m.true_peak = *true_peak;
         done(user, job);
     }
+    static void done_levels(void *user, const umx_queue_job *job, const umx_levels *levels) { done_measured(user, job, levels, nullptr, nullptr); }
     static void done_loudness(void *user, const umx_queue_job *job, const umx_levels *levels, const umx_loudness *loudness, const double *)
     {
-        static_cast<FileJob *>(job->tag)->loudness = *loudness;
-        done_levels(user, job, levels);
+        done_measured(user, job, levels, loudness, nullptr);
     }
-    static void done_true_peak(void *user, const umx_queue_job *job, const umx_levels *levels, const umx_loudness *loudness, const double *e,
+    static void done_true_peak(void *user, const umx_queue_job *job, const umx_levels *levels, const umx_loudness *loudness, const double *,
                                const umx_true_peak *true_peak)
     {
-        static_cast<FileJob *>(job->tag)->true_peak = *true_peak;
-        done_loudness(user, job, levels, loudness, e);
+        done_measured(user, job, levels, loudness, true_peak);
     }
 };
 
@@ -245,8 +249,7 @@ int main(int argc, const char **argv)
             names[f] = std::filesystem::path(argv[3 + f]).stem().string() + "_" + std::to_string(k);
     }
     // umx.cpp:75-96: the buffers of file f to its directory
-    auto write_file = [&](int f, float *const *bufs, int16_t *const *bufs16, int n, int rate_, const umx_levels &lv, const umx_loudness &ld,
-                          const umx_true_peak &tp, char *err_) -> bool {
+    auto write_file = [&](int f, float *const *bufs, int16_t *const *bufs16, int n, int rate_, const umx_measured &measured, char *err_) -> bool {
         const std::filesystem::path dir = std::filesystem::path(out_dir) / names[f];
         std::error_code ec;
         std::filesystem::create_directories(dir, ec);
@@ -259,12 +262,7 @@ int main(int argc, const char **argv)
                 : resample ? umx_wav_write_f32_rate(p.c_str(), bufs[t], n, rate_, err_)
                            : umx_wav_write_f32(p.c_str(), bufs[t], n, err_))
                 return false;
-            if (clipc.levels)
-                umx_levels_print(p.c_str(), lv, t);
-            if (clipc.loudness)
-                umx_loudness_print(p.c_str(), ld, t);
-            if (clipc.true_peak != UMX_TRUE_PEAK_OFF)
-                umx_true_peak_print(p.c_str(), tp, t);
+            umx_measured_print(p.c_str(), clipc, measured, t);
         }
         return true;
     };
@@ -330,7 +328,7 @@ int main(int argc, const char **argv)
                     bufs[t] = fj->stems[t].data();
                     bufs16[t] = fj->stems16[t].data();
                 }
-                const bool ok = write_file(fj->index, bufs, bufs16, fj->n, fj->rate, fj->levels, fj->loudness, fj->true_peak, werr);
+                const bool ok = write_file(fj->index, bufs, bufs16, fj->n, fj->rate, fj->measured, werr);
                 std::lock_guard<std::mutex> lock(q.m);
                 q.unwritten.pop_front(); // (counted until it is written: the stems are in memory until then)
                 if (!ok && q.error.empty())
@@ -428,7 +426,7 @@ int main(int argc, const char **argv)
         wall += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         for (int i = 0; i < nb; ++i)
         {
-            if (!write_file(f0 + i, &out[per_file * i], &out16[per_file * i], n[i], rate[i], levels[i], loudness[i], true_peak[i], err))
+            if (!write_file(f0 + i, &out[per_file * i], &out16[per_file * i], n[i], rate[i], {levels[i], loudness[i], true_peak[i]}, err))
             {
                 fprintf(stderr, "%s\n", err);
                 return 1;

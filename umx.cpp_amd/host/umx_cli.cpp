@@ -123,9 +123,7 @@ int main(int argc, const char **argv)
                                       ? "the shift ensemble (UMX_SHIFTS > 1) and UMX_CLI_PER_SEGMENT=1 do not offer levels or rescale"
                                       : nullptr))
         return 1;
-    umx_levels levels = {};
-    umx_loudness loudness = {};
-    umx_true_peak true_peak = {};
+    umx_measured measured;
     umx_sample_io io = pcmc.io;
     printf("umx-cli (MI355X / gfx950) main driver program\n");
 
@@ -229,9 +227,9 @@ int main(int argc, const char **argv)
         for (int t = 0; t < 4; ++t)
             out_io[t] = pcmc.active() ? (void *)stems_int[t].data() : (void *)stems[t].data();
         if (umx_hip_separate_tracks_true_peak(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out_io,
-                                              hb.flags, &io, clipc.clip_mode, clipc.levels ? &levels : nullptr,
-                                              clipc.loudness ? &loudness : nullptr, nullptr, clipc.true_peak,
-                                              clipc.true_peak != UMX_TRUE_PEAK_OFF ? &true_peak : nullptr, print_progress, nullptr))
+                                              hb.flags, &io, clipc.clip_mode, clipc.levels ? &measured.levels : nullptr,
+                                              clipc.loudness ? &measured.loudness : nullptr, nullptr, clipc.true_peak,
+                                              clipc.true_peak != UMX_TRUE_PEAK_OFF ? &measured.true_peak : nullptr, print_progress, nullptr))
         {
             fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
             return 1;
@@ -259,12 +257,7 @@ int main(int argc, const char **argv)
             fprintf(stderr, "%s\n", err);
             return 1;
         }
-        if (clipc.levels)
-            umx_levels_print(p.c_str(), levels, t);
-        if (clipc.loudness)
-            umx_loudness_print(p.c_str(), loudness, t);
-        if (clipc.true_peak != UMX_TRUE_PEAK_OFF)
-            umx_true_peak_print(p.c_str(), true_peak, t);
+        umx_measured_print(p.c_str(), clipc, measured, t);
     }
     umx_wav_free(audio);
     umx_wav_free_pcm16(audio_int);
