@@ -184,6 +184,23 @@ int umx_hip_track_stream_reset(umx_hip_ctx *ctx, int track);
 int umx_hip_track_stream_get(umx_hip_ctx *ctx, int track, float *host_dst);
 int umx_hip_track_stream_set(umx_hip_ctx *ctx, int track, const float *host_src);
 
+/* NON-FINITE INPUT.  Audio is data: a NaN, a +-inf, or finite samples so large that they overflow inside the engine (3e38 does, in
+ * the STFT) are no error.  What they may touch is the lane, the call and the track they came in with, and nothing else, bit for bit
+ * (tests/test_gpu_poisoned_lanes.py):
+ *   1. CONTAINMENT.  In any call, a lane whose audio holds such samples changes no bit of any other lane's outputs or of any other
+ *      lane's carried LSTM state.  The call returns UMX_OK and launches what the call without those samples launches: the same
+ *      recurrence (umx_hip_lstm_kernel_name, _lstm_was_persistent, _lstm_mode), the same GEMMs (umx_hip_gemm_kernel_name); the
+ *      hand-off of the persistent recurrences goes by tags, never by values, so no timeout recovery is triggered.
+ *   2. RECOVERY.  That lane's own outputs and its own LSTM state behind the call are UNSPECIFIED (they need not even be non-finite:
+ *      the clamps of the gate functions and the ReLUs may swallow a NaN).  Once umx_hip_track_stream_reset(ctx, lane) -- on a
+ *      one-track context umx_hip_stream_reset -- has cleared that lane's state, every later call on the context gives every lane,
+ *      that one included, the bits it would have had if the call had never run: whatever n, lane set, target set, Wiener
+ *      iteration count or filter the later calls use, and in whichever pipeline slot they land.  The track queue's admission of a
+ *      job performs that reset.
+ *   3. WHOLE TRACKS.  In umx_hip_separate_tracks* and umx_hip_separate_queue* a track with such samples changes no bit of any other
+ *      track's outputs or measurement records (levels, loudness, hop energies, true peak) -- not of the tracks beside it, not of
+ *      the job that takes its lane next, at any sample rate.  Its own record's `nonfinite` counts what its outputs hold. */
+
 /* umx_inference (inference.cpp:12-207): one segment -> 4 stems.
  * audio: n interleaved stereo frames (2,n), 1 <= n <= segment_samples.  out[t]: (2,n) each.
  * Host-pointer form: H2D + kernels + D2H, synchronous (umx_inference returns its outputs). */
