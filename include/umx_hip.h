@@ -699,6 +699,55 @@ int umx_hip_true_peak_device(umx_hip_ctx *ctx, int n_buffers, const float *const
  * interleaved stereo frames, frames [first_frame, first_frame + n_frames) accumulating into *bits. */
 int umx_hip_true_peak_taps(int rate, float taps[49], int *factor);
 int umx_hip_true_peak_host(const float *x, int n, int rate, long long first_frame, long long n_frames, unsigned *bits);
+/* FLAC out of the whole-track driver: what a catalogue stores is FLAC, so the stems are encoded on the device and an
+ * output buffer comes down as a complete .flac file -- typically half the bytes of the PCM it decodes to.  Lossless has an exact
+ * meaning: the stream decodes to the codes the UMX_SAMPLE_S16 / UMX_SAMPLE_S24 encode above writes for the same fp32 output (the same
+ * dither keys, frame index k of the caller's track, rescale divisor, NaN -> 0 and clamp).  The stream, to the bit:
+ *   file       "fLaC"; one STREAMINFO block flagged last (min = max block size 4096, min and max frame size as measured, the caller's
+ *              rate, 2 channels, 16 or 24 bits, the total sample count, an all-zero MD5: "not computed"); the frames.  42 bytes + frames.
+ *   frame      fixed-blocksize stream, 4096 frames per block, the last block with its length in the 8-bit (<= 256) or 16-bit field;
+ *              sample-rate code 0000 (from STREAMINFO); frame number UTF-8 coded; CRC-8 on the header, CRC-16 on the frame
+ *   channels   per frame independent, left/side, right/side or mid/side (M = (L + R) >> 1, S = L - R): the smallest exact bit count,
+ *              ties to the first in that order
+ *   subframe   CONSTANT when all samples are equal; else FIXED of the order 0 .. min(4, bs - 1) with the smallest sum of |residual|
+ *              over the samples from min(4, bs - 1) on (ties: the lower order), unless VERBATIM is strictly smaller; no wasted bits
+ *   residual   partitioned Rice: partition orders 0 .. 8 tried in a full block, 0 alone in a shorter last block; per partition the
+ *              parameter with the smallest exact cost n (k + 1) + min(sum of u >> k, 2^31 - 1), u the zigzag residual, the lowest on a tie, over 0 .. 14
+ *              (RICE) and 0 .. 30 (RICE2); no escape code; the cheapest (method, order) with 4 or 5 bits per partition, walking the
+ *              orders upwards and RICE first, the first on a tie
+ * Every choice is a function of the block's integer samples alone, so regions, lanes, reset mode and a rerun give the same bytes, and
+ * umx_hip_flac_encode_host produces the same file without a GPU.
+ * umx_hip_flac_bound: host arithmetic, the capacity that always suffices for n_frames at `bits` (0 for bits other than 16 and 24).
+ * umx_hip_flac_encode_device: on the caller's device buffers, queued on hip_stream: n frames (from frame 0 of the track) of 1 .. 4
+ *   buffers of (2,n) interleaved fp32 (8-byte aligned), buffer b being output first_buffer + b of the dither rule (of io only dither
+ *   and dither_seed are read; NULL: none); acc_dev as in umx_hip_pcm24_encode_rescaled_device: NULL for the plain encode, else the
+ *   samples are divided by the divisor of that record's peak words and what clamps is added to its clipped.  out_dev[b]: cap[b] >= the
+ *   bound bytes of device memory; bytes_dev: n_buffers 64-bit words in device memory that receive each stream's length.  Three
+ *   launches (encode into worst-case slots of a grow-only scratch buffer of the context, scan, compaction); no byte at or beyond
+ *   bytes_dev[b] is written.  The context has ONE such scratch set: the caller orders the FLAC work of a context -- a call on another
+ *   stream, or a whole-track FLAC call, starts only after the previous call's launches have finished (a stream or event wait); the
+ *   launches of one call, and calls queued on one stream, are ordered already.  Growing the scratch synchronises the device.  UMX_ERR_ARG for bits other than 16 / 24, a rate outside 1 .. 655350, n < 1 and a capacity below the bound.
+ * umx_hip_flac_encode_host: the same rules with no GPU and no context, for output buffer `buffer`; byte-identical output.
+ * umx_hip_separate_tracks_flac: umx_hip_separate_tracks_true_peak with flac_bits (0, 16 or 24), out_cap and out_bytes (one per output
+ *   buffer: out_cap[n_host * track + m], NULL allowed when flac_bits == 0).  flac_bits == 0 IS the _true_peak call: the same launches,
+ *   nothing allocated.  Otherwise io->out_format (or io == NULL) must be UMX_SAMPLE_F32 and every capacity >= the bound: anything else
+ *   is UMX_ERR_ARG, names its reason and leaves the context usable.  Dither is allowed then, indexed as for the PCM formats with
+ *   flac_bits as the format's LSB; clipped[m] counts as for the PCM format of that width.  A FLAC track leaves whole behind its last
+ *   segment, as a rescaled one does: mix, measurements, divisor, the three launches, one 8-byte read per output, one download of
+ *   exactly that many bytes.  Reset mode, other rates, the mix, levels, loudness and true peak work as before.  The queue, the shift
+ *   ensemble, the multi-GPU driver (umx_mgpu.h) and the per-segment umx_hip_infer_* calls do not offer it. */
+#define UMX_FLAC_BLOCK 4096
+size_t umx_hip_flac_bound(long long n_frames, int bits);
+int umx_hip_flac_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, int rate, int bits, int first_buffer,
+                               const umx_sample_io *io, umx_levels_acc *acc_dev, void *const *out_dev, const size_t *cap,
+                               unsigned long long *bytes_dev, void *hip_stream);
+int umx_hip_flac_encode_host(const float *x, long long n, int rate, int bits, int buffer, const umx_sample_io *io, void *out, size_t cap,
+                             size_t *bytes);
+int umx_hip_separate_tracks_flac(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                                 const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                                 const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,
+                                 double *const *hop_energy, int true_peak_mode, umx_true_peak *true_peak, int flac_bits,
+                                 const size_t *out_cap, size_t *out_bytes, void (*progress)(float, void *), void *progress_user);
 /* testing, host only: the fp32 tap table of a rate pair (taps[phase * K + d + D]; cap floats at most), its phase count L, taps
  * per phase K and first offset -D.  UMX_ERR_ARG for a bad rate or a too small cap (the sizes are still reported). */
 int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase,

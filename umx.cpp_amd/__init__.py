@@ -344,6 +344,17 @@ def hip_lib():
     lib.umx_hip_separate_tracks_true_peak.argtypes = (wide + [C.c_int, C.POINTER(Levels), C.POINTER(Loudness), C.POINTER(C.c_void_p), C.c_int,
                                                               C.POINTER(TruePeak)] + progress)
 
+    # FLAC out: the true-peak rung plus flac_bits, the capacities and the lengths of the streams
+    lib.umx_hip_separate_tracks_flac.argtypes = (lib.umx_hip_separate_tracks_true_peak.argtypes[:-2]
+                                                 + [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)] + progress)
+    lib.umx_hip_flac_bound.argtypes = [C.c_longlong, C.c_int]
+    lib.umx_hip_flac_bound.restype = C.c_size_t
+    lib.umx_hip_flac_encode_host.argtypes = [_fp, C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(SampleIO), _u8p, C.c_size_t,
+                                             C.POINTER(C.c_size_t)]
+    lib.umx_hip_flac_encode_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.POINTER(SampleIO), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p,
+                                               C.c_void_p]
+
     def queue_args(done_fn):
         return [C.c_void_p, QUEUE_NEXT_FN, done_fn, C.c_void_p, C.c_int, _fp, C.c_uint]
 
@@ -399,7 +410,8 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_pcm24_decode_device", "umx_hip_pcm24_encode_device", "umx_hip_pcm24_encode_rescaled_device",
                "umx_hip_pcm24_decode_host", "umx_hip_pcm24_encode_host",
                "umx_hip_separate_tracks_true_peak", "umx_hip_separate_queue_true_peak", "umx_hip_true_peak_device",
-               "umx_hip_true_peak_taps", "umx_hip_true_peak_host"]
+               "umx_hip_true_peak_taps", "umx_hip_true_peak_host",
+               "umx_hip_flac_bound", "umx_hip_flac_encode_device", "umx_hip_flac_encode_host", "umx_hip_separate_tracks_flac"]
 
 
 def sample_io(in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None):
@@ -553,6 +565,29 @@ def true_peak_host(x, rate, first_frame=0, n_frames=None, bits=0):
     return np.uint32(b.value)
 
 
+FLAC_BLOCK = 4096
+
+
+def flac_bound(n_frames, bits):
+    """umx_hip_flac_bound: the bytes that always suffice for a FLAC stream of n_frames stereo frames at 16 or 24 bits (0: bad bits)."""
+    return int(hip_lib().umx_hip_flac_bound(int(n_frames), int(bits)))
+
+
+def flac_encode_host(x, rate, bits, buffer=0, dither_seed=None, cap=None):
+    """umx_hip_flac_encode_host: (2,n) float32 -> the complete .flac file (uint8 array) of output buffer `buffer` of a call, the codes
+    being those of pcm16_encode_host / pcm24_encode_host (no GPU)."""
+    a = np.ascontiguousarray(np.asarray(x, np.float32).T)
+    cap = flac_bound(a.shape[0], bits) if cap is None else int(cap)
+    out = np.zeros(max(1, cap), np.uint8)
+    io = sample_io(SAMPLE_F32, SAMPLE_F32, dither_seed)
+    got = C.c_size_t(0)
+    rc = hip_lib().umx_hip_flac_encode_host(a.ctypes.data_as(_fp), a.shape[0], int(rate), int(bits), int(buffer), C.byref(io),
+                                            out.ctypes.data_as(_u8p), cap, C.byref(got))
+    if rc != UMX_OK:
+        raise UmxError(rc, "umx_hip_flac_encode_host")
+    return out[:got.value].copy()
+
+
 def true_peak_float(bits):
     """The float32 whose bit pattern a true-peak word holds."""
     return np.array([bits], np.uint32).view(np.float32)[0]
@@ -615,7 +650,7 @@ class _TrackArgs:
     arrays of audio, outputs, lengths, shift offsets (None = -1: no shift) and rates (None: all 44.1 kHz); result(): the outputs as a
     list of [n_out x (2, L_i)]."""
 
-    def __init__(self, waves, io=None, n_out=4, shift_offsets=None, rates=None, ptr=C.c_void_p):
+    def __init__(self, waves, io=None, n_out=4, shift_offsets=None, rates=None, ptr=C.c_void_p, out_bytes=None):
         nt = len(waves)
         fin = SAMPLE_F32 if io is None else io.in_format
         self.fout = SAMPLE_F32 if io is None else io.out_format
@@ -627,7 +662,9 @@ class _TrackArgs:
             self.ins = [np.ascontiguousarray(np.asarray(w, tin).T).ravel() for w in waves]
         self.Ls = [np.asarray(w).shape[1] for w in waves]
         self.n_host = min(max(n_out, 0), MAX_MIX_OUTPUTS)
-        if self.fout == SAMPLE_S24:
+        if out_bytes is not None:  # FLAC: every output a byte buffer of out_bytes(L) bytes, handed back as it is
+            self.outs = [[np.zeros(max(1, out_bytes(L)), np.uint8) for _ in range(self.n_host)] for L in self.Ls]
+        elif self.fout == SAMPLE_S24:
             self.outs = [[np.empty(6 * L, np.uint8) for _ in range(self.n_host)] for L in self.Ls]
         else:
             self.outs = [[np.empty(2 * L, tout) for _ in range(self.n_host)] for L in self.Ls]
@@ -637,8 +674,11 @@ class _TrackArgs:
         self.shifts = [(-1 if s is None else int(s)) for s in (shift_offsets or [None] * nt)]
         self.sh = (C.c_int * nt)(*self.shifts)
         self.rt = None if rates is None else (C.c_int * nt)(*[int(r) for r in rates])
+        self.raw = out_bytes is not None
 
     def result(self):
+        if self.raw:
+            return self.outs
         if self.fout == SAMPLE_S24:
             return [[pcm24_unpack(x) for x in t] for t in self.outs]
         return [[np.ascontiguousarray(x.reshape(L, 2).T) for x in t] for t, L in zip(self.outs, self.Ls)]
@@ -649,7 +689,9 @@ class _TrackArgs:
 _MEASURE_TAIL = {"umx_hip_separate_tracks_io": (),
                  "umx_hip_separate_tracks_levels": ("clip", "levels"),
                  "umx_hip_separate_tracks_loudness": ("clip", "levels", "loudness", "hop_energy"),
-                 "umx_hip_separate_tracks_true_peak": ("clip", "levels", "loudness", "hop_energy", "true_peak_mode", "true_peak")}
+                 "umx_hip_separate_tracks_true_peak": ("clip", "levels", "loudness", "hop_energy", "true_peak_mode", "true_peak"),
+                 "umx_hip_separate_tracks_flac": ("clip", "levels", "loudness", "hop_energy", "true_peak_mode", "true_peak", "flac_bits", "out_cap",
+                                                  "out_bytes")}
 
 
 class _MeasuredCall:
@@ -658,11 +700,16 @@ class _MeasuredCall:
     tuple the rung's wrapper returns -- outputs, then one entry per record field of its tail."""
 
     def __init__(self, entry_name, handle, waves, io, flags, shift_offsets, rates, gains, clip=CLIP_CLAMP, levels=False, loudness=False,
-                 envelopes=False, true_peak=TRUE_PEAK_OFF, records=False):
+                 envelopes=False, true_peak=TRUE_PEAK_OFF, records=False, flac_bits=0, caps=None):
         nt = len(waves)
         self.io = io = sample_io() if io is None else io
         n_out, self.g = (4, None) if gains is None else _mix_gains(gains)
-        self.m = m = _TrackArgs(waves, io, n_out, shift_offsets, rates)
+        # flac_bits != 0 (DESIGN 29): the outputs are byte buffers of flac_bound bytes (caps: of that many instead, for the refusal)
+        room = None if not flac_bits else (lambda L: flac_bound(L, flac_bits) if caps is None else int(caps))
+        self.m = m = _TrackArgs(waves, io, n_out, shift_offsets, rates, out_bytes=room)
+        nb = max(1, nt * m.n_host)
+        self.cap = (C.c_size_t * nb)(*[x.size for t in m.outs for x in t]) if flac_bits else None
+        self.got = (C.c_size_t * nb)()
         self.lv = (Levels * nt)() if levels else None
         self.ld = (Loudness * nt)() if loudness else None
         self.tp = (TruePeak * nt)() if records else None
@@ -670,15 +717,19 @@ class _MeasuredCall:
         if envelopes:  # (a rate the call will refuse: any size does)
             self.env = [np.full((m.n_host, 2, kweight_hop_count(L, r)), np.nan) for L, r in zip(m.Ls, rates or [MODEL_RATE] * nt)]
             ep = (C.c_void_p * nt)(*[e.ctypes.data if e.size else None for e in self.env])
-        tail = {"clip": int(clip), "levels": self.lv, "loudness": self.ld, "hop_energy": ep, "true_peak_mode": int(true_peak), "true_peak": self.tp}
+        tail = {"clip": int(clip), "levels": self.lv, "loudness": self.ld, "hop_energy": ep, "true_peak_mode": int(true_peak), "true_peak": self.tp,
+                "flac_bits": int(flac_bits), "out_cap": self.cap, "out_bytes": self.got}
         self.tail = _MEASURE_TAIL[entry_name]
         self.args = ((handle, nt, m.a, m.n, m.rt, m.sh, n_out, None if self.g is None else self.g.ctypes.data_as(_fp), m.o, flags, C.byref(io))
                      + tuple(tail[f] for f in self.tail) + (None, None))
 
     def results(self):
         got = {"levels": self.lv, "loudness": self.ld, "true_peak": self.tp}
-        return (self.m.result(),) + tuple(self.env if f == "hop_energy" else (None if got[f] is None else list(got[f]))
-                                          for f in self.tail if f not in ("clip", "true_peak_mode"))
+        outs = self.m.result()
+        if self.m.raw:  # the streams: the bytes the call reported, of every buffer
+            outs = [[x[:self.got[i * self.m.n_host + t]] for t, x in enumerate(tr)] for i, tr in enumerate(outs)]
+        return (outs,) + tuple(self.env if f == "hop_energy" else (None if got[f] is None else list(got[f]))
+                               for f in self.tail if f in ("levels", "loudness", "hop_energy", "true_peak"))
 
 
 def mix_columns(gains):
@@ -1027,6 +1078,28 @@ class Engine:
         return self._separate_many_measured("umx_hip_separate_tracks_true_peak", waves, io, flags, shift_offsets, rates, gains, clip=clip,
                                             levels=levels, loudness=loudness, envelopes=envelopes, true_peak=true_peak, records=records).results()
 
+    # --- FLAC out: the stems encoded on the device, every output buffer a complete .flac file ---
+    def separate_many_flac(self, waves, flac_bits, true_peak=TRUE_PEAK_OFF, clip=CLIP_CLAMP, io=None, flags=0, shift_offsets=None, rates=None,
+                           gains=None, levels=True, loudness=False, envelopes=False, records=False, caps=None):
+        """umx_hip_separate_tracks_flac: separate_many_true_peak() whose outputs are FLAC streams of flac_bits (16 or 24) bits -> ([n_out
+        uint8 arrays per track], [Levels], [Loudness], [hop energies], [TruePeak]); flac_bits 0 is that call, with its outputs.
+        io: fp32 out (its dither seed dithers the codes); caps: a capacity for every buffer instead of flac_bound (tests)."""
+        return self._separate_many_measured("umx_hip_separate_tracks_flac", waves, io, flags, shift_offsets, rates, gains, clip=clip,
+                                            levels=levels, loudness=loudness, envelopes=envelopes, true_peak=true_peak, records=records,
+                                            flac_bits=flac_bits, caps=caps).results()
+
+    def flac_encode_device(self, in_ptrs, n, rate, bits, out_ptrs, caps, bytes_ptr, first_buffer=0, dither_seed=None, acc_ptr=None,
+                           hip_stream=None):
+        """umx_hip_flac_encode_device: 1 .. 4 device buffers (2,n) interleaved fp32 -> a complete FLAC stream each at out_ptrs[b] (caps[b]
+        bytes of device memory), its length in the 64-bit word bytes_ptr[b]; buffer b is output first_buffer + b; acc_ptr: the record
+        whose divisor the samples go over (None: the plain encode)."""
+        nb = len(in_ptrs)
+        io = sample_io(SAMPLE_F32, SAMPLE_F32, dither_seed)
+        self._check(self.lib.umx_hip_flac_encode_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(rate), int(bits),
+                                                        int(first_buffer), C.byref(io), None if acc_ptr is None else C.c_void_p(acc_ptr),
+                                                        (C.c_void_p * max(1, nb))(*out_ptrs), (C.c_size_t * max(1, nb))(*caps),
+                                                        C.c_void_p(bytes_ptr), hip_stream))
+
     def true_peak_device(self, in_ptrs, n, rate, bits_ptr, first_frame=0, n_frames=None, hip_stream=None):
         """umx_hip_true_peak_device: frames [first_frame, first_frame + n_frames) of 1 .. 4 device buffers (2,n) interleaved fp32 into the
         four words at device address bits_ptr (unsigned maxima of bit patterns; the caller zeroes them)."""
@@ -1095,14 +1168,18 @@ class Engine:
 
     # --- the track queue: more tracks than lanes, a lane refilled with the next track the moment one ends ---
     def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None, io=None, clip=None, levels=False, loudness=False, rates=None,
-                       true_peak=None):
+                       true_peak=None, flac_bits=0):
         """umx_hip_separate_queue: list of (2,L_i) -> list of [4 x (2,L_i)] (mix: an (n_out, 5) gain matrix -> n_out x (2,L_i)), every
         job bit for bit what separate() / separate_mix() returns for it alone on this engine; the jobs are handed out in list order.
         rates: one sample rate per job (None: all 44.1 kHz), as separate_many() takes them.
         io: a SampleIO (sample_io()) -> umx_hip_separate_queue_io, int16 arrays in and / or out as it says.
         clip (CLIP_CLAMP / CLIP_RESCALE) or levels=True -> umx_hip_separate_queue_levels: returns (outputs, [Levels per job]).
         loudness=True -> umx_hip_separate_queue_loudness: returns (outputs, [Levels], [Loudness], [(n_out, 2, hops) float64]).
-        true_peak (a TRUE_PEAK_* mode) -> umx_hip_separate_queue_true_peak: returns those four and [TruePeak per job]."""
+        true_peak (a TRUE_PEAK_* mode) -> umx_hip_separate_queue_true_peak: returns those four and [TruePeak per job].
+        flac_bits: the queue does not offer FLAC and its C entry points have no such argument, so a nonzero value is
+        refused HERE, in Python, with ERR_ARG, before the library is called -- the parameter exists only to say so."""
+        if flac_bits:  # DESIGN 29: a FLAC track leaves whole; the queue's C entry points have no such argument
+            raise UmxError(ERR_ARG, "queue: the track queue does not offer FLAC (separate_many_flac)")
         nj = len(waves)
         n_out, g = (4, None) if mix is None else _mix_gains(mix)
         m = _TrackArgs(waves, io, n_out, shift_offsets)

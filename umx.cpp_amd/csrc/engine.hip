@@ -47,6 +47,7 @@
 #include "levels.h"
 #include "loudness.h"
 #include "true_peak.h"
+#include "flac.h"
 #include "gate_debug.h"
 
 using namespace umx;
@@ -595,13 +596,17 @@ struct umx_hip_ctx
         bool loudness = false;          // loudness.h, DESIGN 21: the hop energies of what leaves are measured
         int true_peak = UMX_TRUE_PEAK_OFF; // true_peak.h, DESIGN 26: MEASURE: the true peak of what leaves is measured; RESCALE: and the divisor comes from it
         bool true_peak_record = false;  // the caller wants the true-peak record
+        int flac_bits = 0;              // flac.h, DESIGN 29: 16 or 24: every track leaves whole, as a FLAC stream of that width's codes
         int n_host() const { return mix ? mix->n_out : 4; } // host buffers per track
         bool rescale() const { return clip_mode == UMX_CLIP_RESCALE; }
         bool measures() const { return levels || rescale(); } // a rescaled track measures for its divisor whether or not the caller wants the record
         bool true_peak_rescale() const { return true_peak == UMX_TRUE_PEAK_RESCALE && rescale(); }
         bool measures_true_peak() const { return true_peak != UMX_TRUE_PEAK_OFF; }
         // a finished span goes through track_leave: something is measured or encoded on its way out
-        bool leaves_measured() const { return io.out_format != UMX_SAMPLE_F32 || measures() || loudness || measures_true_peak(); }
+        bool leaves_measured() const { return io.out_format != UMX_SAMPLE_F32 || measures() || loudness || measures_true_peak() || flac_bits; }
+        bool leaves_whole() const { return rescale() || flac_bits; } // behind its last segment, as ONE region
+        // the integer format whose clamp `clipped` counts: the output's, or the PCM format of a FLAC stream's width
+        int clip_format() const { return flac_bits == 16 ? UMX_SAMPLE_S16 : flac_bits == 24 ? UMX_SAMPLE_S24 : io.out_format; }
     };
     struct TrackRequest // what tracks() is asked for: n_tracks tracks, one per track lane
     {
@@ -620,6 +625,8 @@ struct umx_hip_ctx
         umx_loudness *loudness = nullptr; // loudness.h, DESIGN 21: n_tracks records, or nullptr
         double *const *hop_energy = nullptr; // per track nullptr or room for its hop energies; either of the two: the tracks are measured
         umx_true_peak *true_peak = nullptr; // true_peak.h, DESIGN 26: n_tracks records, or nullptr (opt.true_peak says whether the tracks are measured)
+        const size_t *out_cap = nullptr;    // flac.h, DESIGN 29 (opt.flac_bits): the bytes behind every host buffer, and
+        size_t *out_bytes = nullptr;        // the bytes of the stream that went there, both [n_host * track + m]
     };
     int tracks(const TrackRequest &rq);
     int tracks_once(const TrackRequest &rq);
@@ -647,8 +654,19 @@ struct umx_hip_ctx
         double *hopE = nullptr;        // DESIGN 21, only once a job measures loudness: its hop energies [output][channel][hop], grow-only,
         size_t cap_hopE = 0;           // zeroed with the accumulators (cap: doubles)
         unsigned *tp = nullptr;        // DESIGN 26, only once a job measures its true peak: four words, the bit patterns, zeroed with the levels record
+        // DESIGN 29, only once a job asks for FLAC: its streams as they leave (bytes, each grow-only on its own) and their lengths
+        uint8_t *flac_out[4] = {};
+        size_t cap_flac_out[4] = {};
+        unsigned long long *flac_bytes = nullptr;
     };
     std::vector<TrackBufs> trk;
+    // the scratch of the FLAC launches, grow-only, one for the context (every job's launches are ordered behind each other:
+    // trk_acc_ev chains the calls): the frames in their worst-case slots, their sizes and their byte offsets
+    uint8_t *flac_slots = nullptr;
+    uint32_t *flac_sizes = nullptr;
+    unsigned long long *flac_offsets = nullptr;
+    size_t cap_flac_slots = 0, cap_flac_sizes = 0, cap_flac_offsets = 0; // bytes; frames; frames
+    int flac_scratch_grow(int nb, long long n, int bps);
     hipEvent_t trk_acc_ev[kMaxSlots] = {}; // per slot: behind the overlap-add of the last call that ran in it
     // ---- what tracks_once and the track queue share (engine_tracks.h)
     struct TrackResample // a job at another rate (track_rate_plan): the caller's rate and length, the two rate pairs' geometry and taps
@@ -694,6 +712,8 @@ struct umx_hip_ctx
         bool whole_region = false;    // not by_region, and track_call itself finishes it behind its last segment as ONE region: the
                                       // frames [lead, lead + length) (a rescaled track)
         TrackMeasure m;               // where its loudness and true-peak launches stand (track_measure_grow)
+        int flac_rate = 0;            // the caller's rate, for STREAMINFO
+        unsigned long long flac_len[4] = {}; // ... and the bytes of its streams, once they are on the host
     };
     struct TrackLane // a lane of one call: its job (nullptr: idle) and the padded frame at which its segment starts
     {
@@ -741,6 +761,7 @@ struct umx_hip_ctx
     void track_encode(const TrackBufs &tb_, const umx_sample_io &io, int n_host, float *const src[4], size_t src_start, int count,
                       long long first_frame, umx_levels_acc *acc, hipStream_t st, const uint32_t *words = nullptr);
     int track_measure_grow(TrackBufs &tb_, TrackJob &j, int rate, int length_at_rate);
+    int track_flac_grow(TrackBufs &tb_, int bits, size_t frames, int n_host);
     struct ZeroSpan
     {
         void *p;

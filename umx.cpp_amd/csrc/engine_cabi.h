@@ -343,7 +343,26 @@ struct MeasureArgs // what a whole-track call measures and where the results go:
     double *const *hop_energy = nullptr;  // per track NULL or room for its hop energies
     int true_peak_mode = UMX_TRUE_PEAK_OFF; // true_peak.h, DESIGN 26
     umx_true_peak *true_peak = nullptr;   // n_tracks records, or NULL
+    int flac_bits = 0;                    // flac.h, DESIGN 29: 0, 16 or 24
+    const size_t *out_cap = nullptr;      // per output buffer: its bytes, and
+    size_t *out_bytes = nullptr;          // the bytes of the stream written there
 };
+// what a FLAC call is refused for, behind the sample formats' own checks: a width that is none, a PCM output format.
+// Dither goes with it (the stream's width is the format's LSB), so the formats are checked as if the output were that PCM format.
+static const char *flac_refusal(int flac_bits, const umx_sample_io *io)
+{
+    if (flac_bits == 0)
+        return sample_io_refusal(io);
+    if (!flac_bits_ok(flac_bits))
+        return "flac: flac_bits must be 0, 16 or 24";
+    if (io && io->out_format != UMX_SAMPLE_F32)
+        return "flac: the FLAC stream is the output format; io->out_format must be UMX_SAMPLE_F32";
+    if (!io)
+        return nullptr;
+    umx_sample_io as_pcm = *io;
+    as_pcm.out_format = flac_bits == 16 ? UMX_SAMPLE_S16 : UMX_SAMPLE_S24;
+    return sample_io_refusal(&as_pcm);
+}
 static const char *mix_refusal(int n_out, const float *gains, MixSpec &spec) // (NULL gains are refused: who takes "no mix" asks before)
 {
     return mix_spec_from(n_out, gains, &spec) >= 0 ? nullptr
@@ -363,7 +382,7 @@ static bool mix_checked(umx_hip_ctx *ctx, int n_out, const float *gains, MixSpec
 static bool track_options_checked(umx_hip_ctx *ctx, const umx_sample_io *io, const MeasureArgs &ma, int n_out, const float *gains, MixSpec &spec,
                                   umx_hip_ctx::TrackOptions &opt)
 {
-    const char *why = sample_io_refusal(io);
+    const char *why = flac_refusal(ma.flac_bits, io);
     if (!why)
         why = clip_mode_refusal(ma.clip_mode);
     if (!why && gains)
@@ -376,6 +395,7 @@ static bool track_options_checked(umx_hip_ctx *ctx, const umx_sample_io *io, con
         return false;
     }
     opt.true_peak = ma.true_peak_mode;
+    opt.flac_bits = ma.flac_bits;
     opt.mix = gains ? &spec : nullptr;
     if (io)
         opt.io = *io;
@@ -398,6 +418,8 @@ static umx_hip_ctx::TrackRequest track_request(int n_tracks, const void *const *
     rq.loudness = ma.loudness;
     rq.hop_energy = ma.hop_energy;
     rq.true_peak = ma.true_peak;
+    rq.out_cap = ma.out_cap;
+    rq.out_bytes = ma.out_bytes;
     return rq;
 }
 
@@ -805,6 +827,68 @@ int umx_hip_separate_tracks_true_peak(umx_hip_ctx *ctx, int n_tracks, const void
 {
     const MeasureArgs ma = {clip_mode, levels, loudness, hop_energy, true_peak_mode, true_peak};
     return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, ma, progress, progress_user);
+}
+
+// ---------------------------------------------------------------- FLAC out (flac.h)
+// flac_bits == 0: the request of umx_hip_separate_tracks_true_peak, field for field
+int umx_hip_separate_tracks_flac(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                                 const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                                 const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,
+                                 double *const *hop_energy, int true_peak_mode, umx_true_peak *true_peak, int flac_bits,
+                                 const size_t *out_cap, size_t *out_bytes, void (*progress)(float, void *), void *progress_user)
+{
+    MeasureArgs ma = {clip_mode, levels, loudness, hop_energy, true_peak_mode, true_peak};
+    if (flac_bits != 0)
+    {
+        ma.flac_bits = flac_bits;
+        ma.out_cap = out_cap;
+        ma.out_bytes = out_bytes;
+    }
+    return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, ma, progress, progress_user);
+}
+size_t umx_hip_flac_bound(long long n_frames, int bits) { return flac_bits_ok(bits) && n_frames >= 0 ? flac_bound(n_frames, bits) : 0; }
+int umx_hip_flac_encode_host(const float *x, long long n, int rate, int bits, int buffer, const umx_sample_io *io, void *out, size_t cap,
+                             size_t *bytes)
+{
+    if (!x || !out || !bytes || n < 1 || !flac_bits_ok(bits) || !flac_rate_ok(rate) || buffer < 0 || buffer >= UMX_MAX_MIX_OUTPUTS ||
+        cap < flac_bound(n, bits))
+        return UMX_ERR_ARG;
+    const DitherArg d = dither_of(io);
+    uint8_t *o = static_cast<uint8_t *>(out);
+    *bytes = bits == 16 ? flac_encode_host<SampleS16>(x, n, rate, buffer, d.on, d.seed, o) : flac_encode_host<SampleS24>(x, n, rate, buffer, d.on, d.seed, o);
+    return UMX_OK;
+}
+int umx_hip_flac_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, int rate, int bits, int first_buffer,
+                               const umx_sample_io *io, umx_levels_acc *acc_dev, void *const *out_dev, const size_t *cap,
+                               unsigned long long *bytes_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    const float2 *src[4] = {};
+    uint8_t *dst[4] = {};
+    if (!device_buffers(ctx, "flac encode", n_buffers, in_dev, n, 0, src) || !device_buffers(ctx, "flac encode", n_buffers, out_dev, n, 0, dst))
+        return UMX_ERR_ARG;
+    const char *why = !flac_bits_ok(bits)                                                        ? "flac encode: bits must be 16 or 24"
+                      : !flac_rate_ok(rate)                                                      ? "flac encode: sample rate outside 1 .. 655350 Hz"
+                      : first_buffer < 0 || first_buffer + n_buffers > UMX_MAX_MIX_OUTPUTS       ? "flac encode: first_buffer + n_buffers must stay within 4 outputs"
+                      : !cap || !bytes_dev                                                       ? "flac encode: need the capacities and the length words"
+                                                                                                 : nullptr;
+    for (int b = 0; !why && b < n_buffers; ++b)
+        if (cap[b] < flac_bound(n, bits))
+            why = "flac encode: a capacity below umx_hip_flac_bound(n, bits)";
+    if (why)
+    {
+        ctx->set_error(why);
+        return UMX_ERR_ARG;
+    }
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    if (int rc = ctx->flac_scratch_grow(n_buffers, n, bits))
+        return rc;
+    const DitherArg d = dither_of(io);
+    launch_flac(bits, n_buffers, src, n, rate, first_buffer, d.on, d.seed, acc_dev ? levels_peak_words(acc_dev) : nullptr, acc_dev, ctx->flac_slots,
+                ctx->flac_sizes, ctx->flac_offsets, dst, bytes_dev, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
 }
 
 int umx_hip_separate_queue_true_peak(umx_hip_ctx *ctx, umx_queue_next_fn next, umx_queue_true_peak_fn done, void *user, int n_out,

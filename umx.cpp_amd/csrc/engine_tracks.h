@@ -94,6 +94,28 @@ int umx_hip_ctx::track_int_grow(TrackBufs &tb_, const umx_sample_io &io, size_t 
     return UMX_OK;
 }
 
+// the FLAC side of an accumulator set for a job of `frames` frames at the caller's rate: n_host streams of the bound's
+// bytes, each grow-only on its own, the words their lengths go to, and the context's scratch for one job's launches
+int umx_hip_ctx::track_flac_grow(TrackBufs &tb_, int bits, size_t frames, int n_host)
+{
+    for (int t = 0; t < n_host; ++t)
+        if (int rc = grow_only<uint8_t>({{&tb_.flac_out[t], 1}}, tb_.cap_flac_out[t], flac_bound((long long)frames, bits)))
+            return rc;
+    if (!tb_.flac_bytes)
+        if (int rc = dalloc(&tb_.flac_bytes, 4, true))
+            return rc;
+    return flac_scratch_grow(n_host, (long long)frames, bits);
+}
+int umx_hip_ctx::flac_scratch_grow(int nb, long long n, int bps)
+{
+    const size_t frames = (size_t)nb * (size_t)flac_blocks(n);
+    if (int rc = grow_only<uint8_t>({{&flac_slots, 1}}, cap_flac_slots, flac_scratch_slots(nb, n, bps)))
+        return rc;
+    if (int rc = grow_only<uint32_t>({{&flac_sizes, 1}}, cap_flac_sizes, frames))
+        return rc;
+    return grow_only<unsigned long long>({{&flac_offsets, 1}}, cap_flac_offsets, frames);
+}
+
 // `count` frames of the first n_host of `src` from frame src_start on -> the set's integer outputs from frame first_frame on, which is
 // their frame number in the caller's track (the k of the dither), at byte frame_bytes x first_frame; the kernel is the output
 // format's (launch_encode).  acc: over the divisor of `words` (nullptr: of that record's peak words), counting what clamps into it
@@ -151,22 +173,32 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
             m.tp_done = fin;
         }
     }
-    if (!j.opt.measures())
-    {
-        if (integer)
-            track_encode(tb_, io, n_host, src, src_start, count, first_frame, nullptr, st);
-        return;
-    }
     const float2 *s[4] = {};
     float2 *sw[4] = {};
     for (int t = 0; t < n_host; ++t)
         s[t] = sw[t] = reinterpret_cast<float2 *>(src[t]) + src_start;
-    // (a rescaled integer track: its encode counts what it clamps itself, with the divisor it forms)
-    launch_stem_levels(n_host, s, count, first_frame, rescale ? UMX_SAMPLE_F32 : io.out_format, io.dither != 0, io.dither_seed, tb_.lev, st);
+    // A FLAC job (its span is the whole track): the three launches, last of all -- over the divisor of `words` when the
+    // track is rescaled (the fp32 frames stay as they are), counting what clamps as a rescaled integer encode does
+    auto flac = [&](const uint32_t *words) {
+        launch_flac(j.opt.flac_bits, n_host, s, count, j.flac_rate, 0, io.dither != 0, io.dither_seed, words, words ? tb_.lev : nullptr, flac_slots,
+                    flac_sizes, flac_offsets, tb_.flac_out, tb_.flac_bytes, st);
+    };
+    if (!j.opt.measures())
+    {
+        if (integer)
+            track_encode(tb_, io, n_host, src, src_start, count, first_frame, nullptr, st);
+        else if (j.opt.flac_bits)
+            flac(nullptr);
+        return;
+    }
+    // (a rescaled integer or FLAC track: its encode counts what it clamps itself, with the divisor it forms)
+    launch_stem_levels(n_host, s, count, first_frame, rescale ? UMX_SAMPLE_F32 : j.opt.clip_format(), io.dither != 0, io.dither_seed, tb_.lev, st);
     // the words the divisor comes from: the record's peak words, or (UMX_TRUE_PEAK_RESCALE) the true-peak record, final by now
     const uint32_t *words = j.opt.true_peak_rescale() ? tb_.tp : levels_peak_words(tb_.lev);
     if (integer)
         track_encode(tb_, io, n_host, src, src_start, count, first_frame, rescale ? tb_.lev : nullptr, st, words);
+    else if (j.opt.flac_bits)
+        flac(rescale ? words : nullptr);
     else if (rescale)
         launch_stem_rescale(n_host, sw, count, words, st);
 }
@@ -293,13 +325,17 @@ int umx_hip_ctx::admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt,
         return rc;
     if (int rc = track_measure_grow(acc, j, rate, length_at_rate)) // (nothing for a call that measures nothing)
         return rc;
+    if (opt.flac_bits)
+        if (int rc = track_flac_grow(acc, opt.flac_bits, (size_t)length_at_rate, opt.n_host()))
+            return rc;
+    j.flac_rate = rate;
     j.audio = audio;
     j.acc = &acc;
     // Its final regions are mixed in place and leave region by region (a resampled job's through the way back, range by range: DESIGN
     // 23) -- unless it leaves whole behind its last segment: an ensemble lane (its mean leaves: leaves_whole of tracks_once), a rescaled
     // track (its divisor needs every peak).  The last is finished by track_call itself as ONE region.
-    j.by_region = !leaves_whole && !opt.rescale();
-    j.whole_region = opt.rescale() && !leaves_whole;
+    j.by_region = !leaves_whole && !opt.leaves_whole();
+    j.whole_region = opt.leaves_whole() && !leaves_whole;
     return UMX_OK;
 }
 
@@ -400,7 +436,13 @@ hipError_t umx_hip_ctx::track_region_download(const TrackRegion &r, float *const
     hipError_t cerr = hipEventSynchronize(r.ready);
     const size_t count = (size_t)n;
     for (int t = 0; t < n_host && cerr == hipSuccess; ++t)
-        if (j.opt.io.out_format != UMX_SAMPLE_F32) // (encoded behind the region's normalisation and mix, at its frame number: track_call)
+        if (j.opt.flac_bits) // the stream's length, then exactly that many bytes
+        {
+            cerr = hipMemcpy(&r.job->flac_len[t], j.acc->flac_bytes + t, sizeof(unsigned long long), hipMemcpyDeviceToHost);
+            if (cerr == hipSuccess)
+                cerr = hipMemcpy(out_host[t], j.acc->flac_out[t], (size_t)r.job->flac_len[t], hipMemcpyDeviceToHost);
+        }
+        else if (j.opt.io.out_format != UMX_SAMPLE_F32) // (encoded behind the region's normalisation and mix, at its frame number: track_call)
         {
             const size_t fb = sample_frame_bytes(j.opt.io.out_format); // 4 or 6 x frame on both sides
             cerr = hipMemcpy(reinterpret_cast<uint8_t *>(out_host[t]) + fb * first, reinterpret_cast<const uint8_t *>(j.acc->out_int[t]) + fb * first,
@@ -553,7 +595,8 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
     const std::pair<bool, const char *> not_in_ensemble[] = {// DESIGN 20, 21, 26
                                                              {opt.measures(), "track: the shift ensemble does not offer levels or rescale"},
                                                              {opt.loudness, "track: the shift ensemble does not offer loudness"},
-                                                             {opt.measures_true_peak(), "track: the shift ensemble does not offer the true peak"}};
+                                                             {opt.measures_true_peak(), "track: the shift ensemble does not offer the true peak"},
+                                                             {opt.flac_bits != 0, "track: the shift ensemble does not offer FLAC"}};
     for (const auto &asked : not_in_ensemble)
         if (asked.first && ensemble)
         {
@@ -566,6 +609,13 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
             set_error("track: need audio, outputs, length >= 1 and shift offset < 22050");
             return UMX_ERR_ARG;
         }
+    for (int ln = 0; ln < nt && opt.flac_bits; ++ln)
+        for (int t = 0; t < n_host; ++t)
+            if (!rq.out_cap || !rq.out_bytes || rq.out_cap[n_host * ln + t] < flac_bound(length_in[ln], opt.flac_bits))
+            {
+                set_error("flac: every output buffer needs a capacity of at least umx_hip_flac_bound(length, flac_bits) bytes, and out_bytes");
+                return UMX_ERR_ARG;
+            }
     // A track at another rate runs as the n44 = ceil(length L / M) frames of its 44.1 kHz version: `length` below is
     // that length, length_in the caller's.
     int length[LSTMB_MAX_TRACKS];
@@ -787,6 +837,8 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
             std::copy(r.hopE.begin(), r.hopE.end(), rq.hop_energy[ln]);
         if (rq.true_peak && opt.measures_true_peak())
             rq.true_peak[ln] = r.tp;
+        for (int t = 0; t < n_host && opt.flac_bits; ++t)
+            rq.out_bytes[n_host * ln + t] = (size_t)job[ln].flac_len[t];
     }
     return UMX_OK;
 }

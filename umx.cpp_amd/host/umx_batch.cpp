@@ -187,6 +187,11 @@ int main(int argc, const char **argv)
     umx_pcm_choice pcmc;
     if (!umx_pcm_from_env(pcmc, nullptr))
         return 1;
+    if (getenv("UMX_FLAC")) // a FLAC track leaves whole behind its last segment; the track queue does not offer it
+    {
+        fprintf(stderr, "UMX_FLAC: umx-batch runs the track queue, which does not offer FLAC (umx-cli does)\n");
+        return 1;
+    }
     umx_clip_choice clipc;
     if (!umx_clip_from_env(clipc, nullptr))
         return 1;

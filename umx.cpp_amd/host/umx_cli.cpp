@@ -23,6 +23,10 @@
 //                    16-bit PCM WAVs under the same names, quantised on the device, and a 16-bit PCM input goes up as int16 (any other
 //                    encoding as fp32); UMX_PCM16_DITHER=<seed> adds TPDF dither with that seed.  Goes with UMX_RESAMPLE, UMX_TARGETS /
 //                    UMX_RESIDUAL, UMX_MIX and the other knobs; not with UMX_SHIFTS > 1 or UMX_CLI_PER_SEGMENT.  Unset: today's files
+//   UMX_FLAC=16|24   FLAC out (umx_hip_separate_tracks_flac): every output is encoded on the device and written as
+//                    <name>.flac instead of .wav, the codes being those UMX_PCM16=1 / UMX_PCM24=1 would have written.  Goes with UMX_MIX,
+//                    UMX_TARGETS / UMX_RESIDUAL, UMX_RESAMPLE, UMX_CLIP, UMX_LEVELS, UMX_LOUDNESS and UMX_TRUE_PEAK; not with UMX_PCM16,
+//                    UMX_PCM24, UMX_SHIFTS > 1 and UMX_CLI_PER_SEGMENT=1
 //   UMX_PCM24=1      packed 24-bit PCM across PCIe (UMX_SAMPLE_S24): the outputs are written as 24-bit PCM WAVs under the same
 //                    names, quantised on the device; a 24-bit PCM input goes up packed, a 16-bit one as int16, any other encoding as
 //                    fp32; UMX_PCM24_DITHER=<seed> adds TPDF dither with that seed.  Goes where UMX_PCM16 goes, not together with it.
@@ -123,6 +127,20 @@ int main(int argc, const char **argv)
                                       ? "the shift ensemble (UMX_SHIFTS > 1) and UMX_CLI_PER_SEGMENT=1 do not offer levels or rescale"
                                       : nullptr))
         return 1;
+    const int flac_bits = getenv("UMX_FLAC") ? env_int("UMX_FLAC", -1) : 0; // (unset: today's files byte for byte)
+    if (getenv("UMX_FLAC"))
+    {
+        const char *why = flac_bits != 16 && flac_bits != 24       ? "need 16 or 24"
+                          : pcmc.active()                          ? "does not go with UMX_PCM16=1 or UMX_PCM24=1 (one output format per run)"
+                          : shifts > 1                             ? "the shift ensemble (UMX_SHIFTS > 1) does not offer FLAC"
+                          : env_int("UMX_CLI_PER_SEGMENT", 0) != 0 ? "UMX_CLI_PER_SEGMENT=1 does not offer FLAC"
+                                                                   : nullptr;
+        if (why)
+        {
+            fprintf(stderr, "UMX_FLAC: %s\n", why);
+            return 1;
+        }
+    }
     umx_measured measured;
     umx_sample_io io = pcmc.io;
     printf("umx-cli (MI355X / gfx950) main driver program\n");
@@ -182,10 +200,14 @@ int main(int argc, const char **argv)
     umx_backend be{hip_segment, hip_reset, &hb};
     std::vector<float> stems[4];
     std::vector<int16_t> stems_int[4]; // the outputs as they are written, in io.out_format (int_units a frame)
+    std::vector<unsigned char> stems_flac[4]; // UMX_FLAC: the streams, flac_cap bytes of room and flac_bytes of stream each
+    size_t flac_cap[4] = {}, flac_bytes[4] = {};
     float *out[4];
     for (int t = 0; t < (mixed ? mixc.n_out : 4); ++t)
     {
-        if (pcmc.active())
+        if (flac_bits)
+            stems_flac[t].resize(flac_cap[t] = umx_hip_flac_bound(n, flac_bits));
+        else if (pcmc.active())
             stems_int[t].resize(int_units(io.out_format) * n);
         else
             stems[t].resize((size_t)2 * n);
@@ -225,11 +247,12 @@ int main(int argc, const char **argv)
         const void *in = audio_int ? (const void *)audio_int : (const void *)audio;
         void *out_io[4]; // (read as the formats say)
         for (int t = 0; t < 4; ++t)
-            out_io[t] = pcmc.active() ? (void *)stems_int[t].data() : (void *)stems[t].data();
-        if (umx_hip_separate_tracks_true_peak(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out_io,
+            out_io[t] = flac_bits ? (void *)stems_flac[t].data() : pcmc.active() ? (void *)stems_int[t].data() : (void *)stems[t].data();
+        if (umx_hip_separate_tracks_flac(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out_io,
                                               hb.flags, &io, clipc.clip_mode, clipc.levels ? &measured.levels : nullptr,
                                               clipc.loudness ? &measured.loudness : nullptr, nullptr, clipc.true_peak,
-                                              clipc.true_peak != UMX_TRUE_PEAK_OFF ? &measured.true_peak : nullptr, print_progress, nullptr))
+                                              clipc.true_peak != UMX_TRUE_PEAK_OFF ? &measured.true_peak : nullptr, flac_bits, flac_cap, flac_bytes, print_progress,
+                                         nullptr))
         {
             fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
             return 1;
@@ -248,9 +271,22 @@ int main(int argc, const char **argv)
     {
         if (!mixed && !choice.write[t]) // a target that did not run (UMX_TARGETS): a silent slot
             continue;
-        const std::string p = (std::filesystem::path(out_dir) / (mixed ? mixc.name[t] + ".wav" : choice.file[t])).string();
-        printf("Writing wav file %s\n", p.c_str());
-        if (pcmc.active() ? write_int(io.out_format, p.c_str(), stems_int[t].data(), n, rate, err)
+        std::filesystem::path file = std::filesystem::path(out_dir) / (mixed ? mixc.name[t] + ".wav" : choice.file[t]);
+        if (flac_bits)
+            file.replace_extension(".flac");
+        const std::string p = file.string();
+        printf("Writing %s file %s\n", flac_bits ? "flac" : "wav", p.c_str());
+        if (flac_bits)
+        {
+            FILE *f = fopen(p.c_str(), "wb");
+            const bool ok = f && fwrite(stems_flac[t].data(), 1, flac_bytes[t], f) == flac_bytes[t];
+            if ((f && fclose(f) != 0) || !ok)
+            {
+                fprintf(stderr, "%s: cannot write\n", p.c_str());
+                return 1;
+            }
+        }
+        else if (pcmc.active() ? write_int(io.out_format, p.c_str(), stems_int[t].data(), n, rate, err)
             : resample    ? umx_wav_write_f32_rate(p.c_str(), out[t], n, rate, err)
                           : umx_wav_write_f32(p.c_str(), out[t], n, err))
         {
