@@ -748,6 +748,25 @@ int umx_hip_separate_tracks_flac(umx_hip_ctx *ctx, int n_tracks, const void *con
                                  const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,
                                  double *const *hop_energy, int true_peak_mode, umx_true_peak *true_peak, int flac_bits,
                                  const size_t *out_cap, size_t *out_bytes, void (*progress)(float, void *), void *progress_user);
+/* FLAC with LPC subframes: the three calls above with flac_lpc, and each of them IS its _lpc form with flac_lpc == 0, byte
+ * for byte and launch for launch.  flac_lpc in 1 .. 12: in every full block a channel that is not CONSTANT also gets one LPC candidate of
+ * an order up to flac_lpc -- an integer window ((2 i + 1) (8191 - 2 i)) >> 10, exact 64-bit autocorrelation, Levinson-Durbin in double
+ * without fused operations, 14-bit coefficients with error feedback, the order with the smallest estimate of its bits -- whose exact
+ * Rice-coded bits are compared with the FIXED subframe's: the smaller wins, FIXED on a tie, so no subframe, frame or file is larger than
+ * with 0; it decodes to the same codes.  12 keeps the streams in the streamable subset up to 48 kHz.  The host and the device still
+ * produce the same bytes.  umx_hip_flac_bound is unchanged.  UMX_ERR_ARG with a reason (umx_hip_last_error; of a NULL context for the
+ * host call) for a flac_lpc outside 0 .. 12, and in the whole-track call for a nonzero flac_lpc with flac_bits == 0. */
+int umx_hip_flac_encode_device_lpc(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, int rate, int bits, int first_buffer,
+                                   const umx_sample_io *io, umx_levels_acc *acc_dev, void *const *out_dev, const size_t *cap,
+                                   unsigned long long *bytes_dev, void *hip_stream, int flac_lpc);
+int umx_hip_flac_encode_host_lpc(const float *x, long long n, int rate, int bits, int buffer, const umx_sample_io *io, void *out, size_t cap,
+                                 size_t *bytes, int flac_lpc);
+int umx_hip_separate_tracks_flac_lpc(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                                     const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                                     const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,
+                                     double *const *hop_energy, int true_peak_mode, umx_true_peak *true_peak, int flac_bits,
+                                     const size_t *out_cap, size_t *out_bytes, int flac_lpc, void (*progress)(float, void *),
+                                     void *progress_user);
 /* testing, host only: the fp32 tap table of a rate pair (taps[phase * K + d + D]; cap floats at most), its phase count L, taps
  * per phase K and first offset -D.  UMX_ERR_ARG for a bad rate or a too small cap (the sizes are still reported). */
 int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase,

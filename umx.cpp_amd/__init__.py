@@ -347,6 +347,8 @@ def hip_lib():
     # FLAC out: the true-peak rung plus flac_bits, the capacities and the lengths of the streams
     lib.umx_hip_separate_tracks_flac.argtypes = (lib.umx_hip_separate_tracks_true_peak.argtypes[:-2]
                                                  + [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)] + progress)
+    # ... with LPC subframes: the same three calls and flac_lpc
+    lib.umx_hip_separate_tracks_flac_lpc.argtypes = lib.umx_hip_separate_tracks_flac.argtypes[:-2] + [C.c_int] + progress
     lib.umx_hip_flac_bound.argtypes = [C.c_longlong, C.c_int]
     lib.umx_hip_flac_bound.restype = C.c_size_t
     lib.umx_hip_flac_encode_host.argtypes = [_fp, C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(SampleIO), _u8p, C.c_size_t,
@@ -354,6 +356,8 @@ def hip_lib():
     lib.umx_hip_flac_encode_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int,
                                                C.POINTER(SampleIO), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p,
                                                C.c_void_p]
+    lib.umx_hip_flac_encode_host_lpc.argtypes = lib.umx_hip_flac_encode_host.argtypes + [C.c_int]
+    lib.umx_hip_flac_encode_device_lpc.argtypes = lib.umx_hip_flac_encode_device.argtypes + [C.c_int]
 
     def queue_args(done_fn):
         return [C.c_void_p, QUEUE_NEXT_FN, done_fn, C.c_void_p, C.c_int, _fp, C.c_uint]
@@ -411,7 +415,8 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_pcm24_decode_host", "umx_hip_pcm24_encode_host",
                "umx_hip_separate_tracks_true_peak", "umx_hip_separate_queue_true_peak", "umx_hip_true_peak_device",
                "umx_hip_true_peak_taps", "umx_hip_true_peak_host",
-               "umx_hip_flac_bound", "umx_hip_flac_encode_device", "umx_hip_flac_encode_host", "umx_hip_separate_tracks_flac"]
+               "umx_hip_flac_bound", "umx_hip_flac_encode_device", "umx_hip_flac_encode_host", "umx_hip_separate_tracks_flac",
+               "umx_hip_flac_encode_device_lpc", "umx_hip_flac_encode_host_lpc", "umx_hip_separate_tracks_flac_lpc"]
 
 
 def sample_io(in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None):
@@ -573,18 +578,19 @@ def flac_bound(n_frames, bits):
     return int(hip_lib().umx_hip_flac_bound(int(n_frames), int(bits)))
 
 
-def flac_encode_host(x, rate, bits, buffer=0, dither_seed=None, cap=None):
+def flac_encode_host(x, rate, bits, buffer=0, dither_seed=None, cap=None, lpc=0):
     """umx_hip_flac_encode_host: (2,n) float32 -> the complete .flac file (uint8 array) of output buffer `buffer` of a call, the codes
-    being those of pcm16_encode_host / pcm24_encode_host (no GPU)."""
+    being those of pcm16_encode_host / pcm24_encode_host (no GPU).  lpc: umx_hip_flac_encode_host_lpc with LPC subframes of up to
+    that order as candidates (0: none); None: the entry point without the argument, the same bytes as 0."""
     a = np.ascontiguousarray(np.asarray(x, np.float32).T)
     cap = flac_bound(a.shape[0], bits) if cap is None else int(cap)
     out = np.zeros(max(1, cap), np.uint8)
     io = sample_io(SAMPLE_F32, SAMPLE_F32, dither_seed)
     got = C.c_size_t(0)
-    rc = hip_lib().umx_hip_flac_encode_host(a.ctypes.data_as(_fp), a.shape[0], int(rate), int(bits), int(buffer), C.byref(io),
-                                            out.ctypes.data_as(_u8p), cap, C.byref(got))
+    args = (a.ctypes.data_as(_fp), a.shape[0], int(rate), int(bits), int(buffer), C.byref(io), out.ctypes.data_as(_u8p), cap, C.byref(got))
+    rc = hip_lib().umx_hip_flac_encode_host(*args) if lpc is None else hip_lib().umx_hip_flac_encode_host_lpc(*args, int(lpc))
     if rc != UMX_OK:
-        raise UmxError(rc, "umx_hip_flac_encode_host")
+        raise UmxError(rc, "umx_hip_flac_encode_host" if lpc is None else "umx_hip_flac_encode_host_lpc: " + hip_lib().umx_hip_last_error(None).decode())
     return out[:got.value].copy()
 
 
@@ -691,7 +697,9 @@ _MEASURE_TAIL = {"umx_hip_separate_tracks_io": (),
                  "umx_hip_separate_tracks_loudness": ("clip", "levels", "loudness", "hop_energy"),
                  "umx_hip_separate_tracks_true_peak": ("clip", "levels", "loudness", "hop_energy", "true_peak_mode", "true_peak"),
                  "umx_hip_separate_tracks_flac": ("clip", "levels", "loudness", "hop_energy", "true_peak_mode", "true_peak", "flac_bits", "out_cap",
-                                                  "out_bytes")}
+                                                  "out_bytes"),
+                 "umx_hip_separate_tracks_flac_lpc": ("clip", "levels", "loudness", "hop_energy", "true_peak_mode", "true_peak", "flac_bits",
+                                                      "out_cap", "out_bytes", "flac_lpc")}
 
 
 class _MeasuredCall:
@@ -700,7 +708,7 @@ class _MeasuredCall:
     tuple the rung's wrapper returns -- outputs, then one entry per record field of its tail."""
 
     def __init__(self, entry_name, handle, waves, io, flags, shift_offsets, rates, gains, clip=CLIP_CLAMP, levels=False, loudness=False,
-                 envelopes=False, true_peak=TRUE_PEAK_OFF, records=False, flac_bits=0, caps=None):
+                 envelopes=False, true_peak=TRUE_PEAK_OFF, records=False, flac_bits=0, caps=None, flac_lpc=0):
         nt = len(waves)
         self.io = io = sample_io() if io is None else io
         n_out, self.g = (4, None) if gains is None else _mix_gains(gains)
@@ -718,7 +726,7 @@ class _MeasuredCall:
             self.env = [np.full((m.n_host, 2, kweight_hop_count(L, r)), np.nan) for L, r in zip(m.Ls, rates or [MODEL_RATE] * nt)]
             ep = (C.c_void_p * nt)(*[e.ctypes.data if e.size else None for e in self.env])
         tail = {"clip": int(clip), "levels": self.lv, "loudness": self.ld, "hop_energy": ep, "true_peak_mode": int(true_peak), "true_peak": self.tp,
-                "flac_bits": int(flac_bits), "out_cap": self.cap, "out_bytes": self.got}
+                "flac_bits": int(flac_bits), "out_cap": self.cap, "out_bytes": self.got, "flac_lpc": int(flac_lpc)}
         self.tail = _MEASURE_TAIL[entry_name]
         self.args = ((handle, nt, m.a, m.n, m.rt, m.sh, n_out, None if self.g is None else self.g.ctypes.data_as(_fp), m.o, flags, C.byref(io))
                      + tuple(tail[f] for f in self.tail) + (None, None))
@@ -1080,25 +1088,29 @@ class Engine:
 
     # --- FLAC out: the stems encoded on the device, every output buffer a complete .flac file ---
     def separate_many_flac(self, waves, flac_bits, true_peak=TRUE_PEAK_OFF, clip=CLIP_CLAMP, io=None, flags=0, shift_offsets=None, rates=None,
-                           gains=None, levels=True, loudness=False, envelopes=False, records=False, caps=None):
+                           gains=None, levels=True, loudness=False, envelopes=False, records=False, caps=None, lpc=0):
         """umx_hip_separate_tracks_flac: separate_many_true_peak() whose outputs are FLAC streams of flac_bits (16 or 24) bits -> ([n_out
         uint8 arrays per track], [Levels], [Loudness], [hop energies], [TruePeak]); flac_bits 0 is that call, with its outputs.
-        io: fp32 out (its dither seed dithers the codes); caps: a capacity for every buffer instead of flac_bound (tests)."""
-        return self._separate_many_measured("umx_hip_separate_tracks_flac", waves, io, flags, shift_offsets, rates, gains, clip=clip,
+        io: fp32 out (its dither seed dithers the codes); caps: a capacity for every buffer instead of flac_bound (tests).
+        lpc: umx_hip_separate_tracks_flac_lpc with LPC subframes of up to that order as candidates (0: none); None: the entry
+        point without the argument, the same call as 0."""
+        entry, more = ("umx_hip_separate_tracks_flac", {}) if lpc is None else ("umx_hip_separate_tracks_flac_lpc", {"flac_lpc": lpc})
+        return self._separate_many_measured(entry, waves, io, flags, shift_offsets, rates, gains, clip=clip,
                                             levels=levels, loudness=loudness, envelopes=envelopes, true_peak=true_peak, records=records,
-                                            flac_bits=flac_bits, caps=caps).results()
+                                            flac_bits=flac_bits, caps=caps, **more).results()
 
     def flac_encode_device(self, in_ptrs, n, rate, bits, out_ptrs, caps, bytes_ptr, first_buffer=0, dither_seed=None, acc_ptr=None,
-                           hip_stream=None):
+                           hip_stream=None, lpc=0):
         """umx_hip_flac_encode_device: 1 .. 4 device buffers (2,n) interleaved fp32 -> a complete FLAC stream each at out_ptrs[b] (caps[b]
         bytes of device memory), its length in the 64-bit word bytes_ptr[b]; buffer b is output first_buffer + b; acc_ptr: the record
         whose divisor the samples go over (None: the plain encode)."""
         nb = len(in_ptrs)
         io = sample_io(SAMPLE_F32, SAMPLE_F32, dither_seed)
-        self._check(self.lib.umx_hip_flac_encode_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(rate), int(bits),
-                                                        int(first_buffer), C.byref(io), None if acc_ptr is None else C.c_void_p(acc_ptr),
-                                                        (C.c_void_p * max(1, nb))(*out_ptrs), (C.c_size_t * max(1, nb))(*caps),
-                                                        C.c_void_p(bytes_ptr), hip_stream))
+        args = (self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(rate), int(bits), int(first_buffer), C.byref(io),
+                None if acc_ptr is None else C.c_void_p(acc_ptr), (C.c_void_p * max(1, nb))(*out_ptrs), (C.c_size_t * max(1, nb))(*caps),
+                C.c_void_p(bytes_ptr), hip_stream)
+        # lpc: umx_hip_flac_encode_device_lpc (DESIGN 30); None: the entry point without the argument
+        self._check(self.lib.umx_hip_flac_encode_device(*args) if lpc is None else self.lib.umx_hip_flac_encode_device_lpc(*args, int(lpc)))
 
     def true_peak_device(self, in_ptrs, n, rate, bits_ptr, first_frame=0, n_frames=None, hip_stream=None):
         """umx_hip_true_peak_device: frames [first_frame, first_frame + n_frames) of 1 .. 4 device buffers (2,n) interleaved fp32 into the

@@ -597,6 +597,7 @@ struct umx_hip_ctx
         int true_peak = UMX_TRUE_PEAK_OFF; // true_peak.h, DESIGN 26: MEASURE: the true peak of what leaves is measured; RESCALE: and the divisor comes from it
         bool true_peak_record = false;  // the caller wants the true-peak record
         int flac_bits = 0;              // flac.h, DESIGN 29: 16 or 24: every track leaves whole, as a FLAC stream of that width's codes
+        int flac_lpc = 0;               // 1 .. 12: LPC subframes of up to that order are candidates in every full block
         int n_host() const { return mix ? mix->n_out : 4; } // host buffers per track
         bool rescale() const { return clip_mode == UMX_CLIP_RESCALE; }
         bool measures() const { return levels || rescale(); } // a rescaled track measures for its divisor whether or not the caller wants the record

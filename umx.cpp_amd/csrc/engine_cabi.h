@@ -344,13 +344,18 @@ struct MeasureArgs // what a whole-track call measures and where the results go:
     int true_peak_mode = UMX_TRUE_PEAK_OFF; // true_peak.h, DESIGN 26
     umx_true_peak *true_peak = nullptr;   // n_tracks records, or NULL
     int flac_bits = 0;                    // flac.h, DESIGN 29: 0, 16 or 24
+    int flac_lpc = 0;                     // 0 .. 12, nonzero only with flac_bits
     const size_t *out_cap = nullptr;      // per output buffer: its bytes, and
     size_t *out_bytes = nullptr;          // the bytes of the stream written there
 };
 // what a FLAC call is refused for, behind the sample formats' own checks: a width that is none, a PCM output format.
 // Dither goes with it (the stream's width is the format's LSB), so the formats are checked as if the output were that PCM format.
-static const char *flac_refusal(int flac_bits, const umx_sample_io *io)
+static const char *flac_refusal(int flac_bits, int flac_lpc, const umx_sample_io *io)
 {
+    if (!flac_lpc_ok(flac_lpc))
+        return "flac: flac_lpc must be 0 .. 12";
+    if (flac_lpc != 0 && flac_bits == 0)
+        return "flac: flac_lpc needs flac_bits (16 or 24)";
     if (flac_bits == 0)
         return sample_io_refusal(io);
     if (!flac_bits_ok(flac_bits))
@@ -382,7 +387,7 @@ static bool mix_checked(umx_hip_ctx *ctx, int n_out, const float *gains, MixSpec
 static bool track_options_checked(umx_hip_ctx *ctx, const umx_sample_io *io, const MeasureArgs &ma, int n_out, const float *gains, MixSpec &spec,
                                   umx_hip_ctx::TrackOptions &opt)
 {
-    const char *why = flac_refusal(ma.flac_bits, io);
+    const char *why = flac_refusal(ma.flac_bits, ma.flac_lpc, io);
     if (!why)
         why = clip_mode_refusal(ma.clip_mode);
     if (!why && gains)
@@ -396,6 +401,7 @@ static bool track_options_checked(umx_hip_ctx *ctx, const umx_sample_io *io, con
     }
     opt.true_peak = ma.true_peak_mode;
     opt.flac_bits = ma.flac_bits;
+    opt.flac_lpc = ma.flac_lpc;
     opt.mix = gains ? &spec : nullptr;
     if (io)
         opt.io = *io;
@@ -837,7 +843,19 @@ int umx_hip_separate_tracks_flac(umx_hip_ctx *ctx, int n_tracks, const void *con
                                  double *const *hop_energy, int true_peak_mode, umx_true_peak *true_peak, int flac_bits,
                                  const size_t *out_cap, size_t *out_bytes, void (*progress)(float, void *), void *progress_user)
 {
+    return umx_hip_separate_tracks_flac_lpc(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, clip_mode, levels,
+                                            loudness, hop_energy, true_peak_mode, true_peak, flac_bits, out_cap, out_bytes, 0, progress, progress_user);
+}
+// flac_lpc == 0 is the call above, field for field
+int umx_hip_separate_tracks_flac_lpc(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                                     const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                                     const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,
+                                     double *const *hop_energy, int true_peak_mode, umx_true_peak *true_peak, int flac_bits,
+                                     const size_t *out_cap, size_t *out_bytes, int flac_lpc, void (*progress)(float, void *),
+                                     void *progress_user)
+{
     MeasureArgs ma = {clip_mode, levels, loudness, hop_energy, true_peak_mode, true_peak};
+    ma.flac_lpc = flac_lpc; // (refused when nonzero without flac_bits)
     if (flac_bits != 0)
     {
         ma.flac_bits = flac_bits;
@@ -850,17 +868,37 @@ size_t umx_hip_flac_bound(long long n_frames, int bits) { return flac_bits_ok(bi
 int umx_hip_flac_encode_host(const float *x, long long n, int rate, int bits, int buffer, const umx_sample_io *io, void *out, size_t cap,
                              size_t *bytes)
 {
+    return umx_hip_flac_encode_host_lpc(x, n, rate, bits, buffer, io, out, cap, bytes, 0);
+}
+int umx_hip_flac_encode_host_lpc(const float *x, long long n, int rate, int bits, int buffer, const umx_sample_io *io, void *out, size_t cap,
+                                 size_t *bytes, int flac_lpc)
+{
+    // (no context: the reason of a flac_lpc refusal goes where umx_hip_last_error(NULL) reads)
+    if (const char *why = !flac_lpc_ok(flac_lpc)       ? "flac encode: flac_lpc must be 0 .. 12"
+                          : flac_lpc != 0 && bits == 0 ? "flac encode: flac_lpc needs bits (16 or 24)"
+                                                       : nullptr)
+    {
+        g_create_error = why;
+        return UMX_ERR_ARG;
+    }
     if (!x || !out || !bytes || n < 1 || !flac_bits_ok(bits) || !flac_rate_ok(rate) || buffer < 0 || buffer >= UMX_MAX_MIX_OUTPUTS ||
         cap < flac_bound(n, bits))
         return UMX_ERR_ARG;
     const DitherArg d = dither_of(io);
     uint8_t *o = static_cast<uint8_t *>(out);
-    *bytes = bits == 16 ? flac_encode_host<SampleS16>(x, n, rate, buffer, d.on, d.seed, o) : flac_encode_host<SampleS24>(x, n, rate, buffer, d.on, d.seed, o);
+    *bytes = bits == 16 ? flac_encode_host<SampleS16>(x, n, rate, buffer, d.on, d.seed, flac_lpc, o)
+                        : flac_encode_host<SampleS24>(x, n, rate, buffer, d.on, d.seed, flac_lpc, o);
     return UMX_OK;
 }
 int umx_hip_flac_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, int rate, int bits, int first_buffer,
                                const umx_sample_io *io, umx_levels_acc *acc_dev, void *const *out_dev, const size_t *cap,
                                unsigned long long *bytes_dev, void *hip_stream)
+{
+    return umx_hip_flac_encode_device_lpc(ctx, n_buffers, in_dev, n, rate, bits, first_buffer, io, acc_dev, out_dev, cap, bytes_dev, hip_stream, 0);
+}
+int umx_hip_flac_encode_device_lpc(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, int n, int rate, int bits, int first_buffer,
+                                   const umx_sample_io *io, umx_levels_acc *acc_dev, void *const *out_dev, const size_t *cap,
+                                   unsigned long long *bytes_dev, void *hip_stream, int flac_lpc)
 {
     if (!ctx)
         return UMX_ERR_ARG;
@@ -869,6 +907,7 @@ int umx_hip_flac_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *con
     if (!device_buffers(ctx, "flac encode", n_buffers, in_dev, n, 0, src) || !device_buffers(ctx, "flac encode", n_buffers, out_dev, n, 0, dst))
         return UMX_ERR_ARG;
     const char *why = !flac_bits_ok(bits)                                                        ? "flac encode: bits must be 16 or 24"
+                      : !flac_lpc_ok(flac_lpc)                                                   ? "flac encode: flac_lpc must be 0 .. 12"
                       : !flac_rate_ok(rate)                                                      ? "flac encode: sample rate outside 1 .. 655350 Hz"
                       : first_buffer < 0 || first_buffer + n_buffers > UMX_MAX_MIX_OUTPUTS       ? "flac encode: first_buffer + n_buffers must stay within 4 outputs"
                       : !cap || !bytes_dev                                                       ? "flac encode: need the capacities and the length words"
@@ -885,7 +924,7 @@ int umx_hip_flac_encode_device(umx_hip_ctx *ctx, int n_buffers, const float *con
     if (int rc = ctx->flac_scratch_grow(n_buffers, n, bits))
         return rc;
     const DitherArg d = dither_of(io);
-    launch_flac(bits, n_buffers, src, n, rate, first_buffer, d.on, d.seed, acc_dev ? levels_peak_words(acc_dev) : nullptr, acc_dev, ctx->flac_slots,
+    launch_flac(bits, flac_lpc, n_buffers, src, n, rate, first_buffer, d.on, d.seed, acc_dev ? levels_peak_words(acc_dev) : nullptr, acc_dev, ctx->flac_slots,
                 ctx->flac_sizes, ctx->flac_offsets, dst, bytes_dev, (hipStream_t)hip_stream);
     UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
     return UMX_OK;

@@ -180,7 +180,7 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
     // A FLAC job (its span is the whole track): the three launches, last of all -- over the divisor of `words` when the
     // track is rescaled (the fp32 frames stay as they are), counting what clamps as a rescaled integer encode does
     auto flac = [&](const uint32_t *words) {
-        launch_flac(j.opt.flac_bits, n_host, s, count, j.flac_rate, 0, io.dither != 0, io.dither_seed, words, words ? tb_.lev : nullptr, flac_slots,
+        launch_flac(j.opt.flac_bits, j.opt.flac_lpc, n_host, s, count, j.flac_rate, 0, io.dither != 0, io.dither_seed, words, words ? tb_.lev : nullptr, flac_slots,
                     flac_sizes, flac_offsets, tb_.flac_out, tb_.flac_bytes, st);
     };
     if (!j.opt.measures())

@@ -41,6 +41,38 @@
 // buffer) turns sizes into byte offsets, finds the smallest and largest frame and writes the 42 header bytes and the buffer's total;
 // the compaction kernel (a workgroup per frame) moves every frame to its byte offset: 16-byte loads and stores, the destination
 // rounded up to 16 bytes by head bytes, the source shifted across dword pairs (alignbyte).  No byte beyond the total is written.
+//
+// LPC subframes (flac_lpc in 1 .. 12, 0: everything above and nothing else).  In a full block every channel that is not
+// CONSTANT also gets ONE linear-prediction candidate, by the rules stated once further down (flac_lpc_window .. flac_pick):
+//   window     w[i] = ((2 i + 1) (8191 - 2 i)) >> 10; xw[i] = (x[i] w[i] + 8192) >> 14
+//   lags       r[l] = sum of xw[i] xw[i - l], l = 0 .. flac_lpc, exact in 64 bits; r[0] == 0: no candidate
+//   solve      Levinson-Durbin in double, one order of operations, no fused operations; it stops at the first order whose reflection
+//              coefficient is not inside (-1, 1) or whose error is not > 0: the orders below it are the candidates
+//   quantise   per candidate order: 14-bit coefficients, shift = clamp(13 - (exponent of max |a_j| + 1), 0, 15), error feedback
+//   residual   e[i] = x[i] - ((sum of c_j x[i - j]) >> shift) in 64 bits; an order with any |e[i]| >= 2^29 is no candidate
+//   order      the smallest min over k of (4084 (k + 1) + ((2 S_o) >> k)) + o (w + 14) + 9, S_o = sum of |e_o| over [12, 4096); ties: the lower
+//   subframe   that order's residual gets the same exhaustive Rice search; its exact bits (8 + o w + 4 + 5 + 14 o + the coded residual)
+//              against the FIXED (or VERBATIM) subframe's: the smaller wins, a tie stays; type 1(o-1), o warm-up samples, precision - 1,
+//              shift, o coefficients, the residual.  So no subframe, frame or file is larger than with flac_lpc = 0.
+// The kernel's LPC variant is a template parameter of the encode kernel, ONE kernel: the analysis needs the block's samples in LDS, which
+// are there, and a table in global memory between two kernels would load and convert every block twice.  The FIXED-only instantiations
+// are compiled from the same text to the same registers as before (212 / 236 VGPRs, 54 080 / 62 272 B of LDS, no scratch).  The variant:
+//   reach      channels lie behind 12 zero predecessors; a thread reads its run and the 12 samples before it (seven 16-byte LDS loads a side).
+//              Lags are formed against PREDECESSORS (r[l] = sum over i >= l of xw[i] xw[i - l]), so no successors are needed.
+//   lags       every thread windows its 28 samples and forms 13 x 16 products with v_mad_i64_i32 (the operands are 25-bit); all four
+//              waves work on one channel at a time; a lag's 64-bit sum crosses the wave by shuffles and the four waves through LDS
+//   solve      lane 0 of wave c runs Levinson-Durbin and quantises every order for channel c, its arrays in LDS (no indexed registers)
+//   residuals  a thread keeps a channel's 28 samples in registers for ALL candidate orders: each order reads its 12 zero-padded
+//              coefficients from LDS (one address a wave) and costs 16 x 12 v_mad_i64_i32 -- two 32-bit halves do not work: a 14-bit
+//              coefficient times a 17-bit sample over 12 taps passes 32 bits already; |e| sums and the limit flag go through shuffles
+//              and one 64-bit LDS add per wave
+//   choice     lane 0 of wave c prices its channel's orders and leaves 12 coefficients, shift and order in 256 B of LDS outside the image
+//   Rice       the search loop runs over 8 residuals instead of 4 (FIXED, then LPC where a channel has a candidate): a second 4 KB heap
+//              of parameters, second level totals and wave sums; wave c then decides channel c: FIXED, and LPC against it
+//   pack       an LPC subframe differs in thread 0's header (warm-up samples from LDS, 9 + 14 o more bits) and in where the residual comes from
+// LDS: 32 864 B of samples, the image, 8 192 B of parameters, 512 + 256 + 256 B: 58 496 B / 66 688 B, still two workgroups a CU by LDS.
+// Registers: 256 VGPRs and 120 AGPRs (no matrix instruction: values the allocator parks there, a spill to registers), no scratch, no
+// call: with 376 registers a SIMD holds one wave, so one workgroup runs per CU (DESIGN 30 names the two ways back under 256).  The analysis' exchange (10 720 B with the Rice sums in front) lies in the image like the rest.
 #pragma once
 #include "common.h"
 #include "levels.h"
@@ -58,10 +90,14 @@ enum
 {
     FLAC_CONSTANT = 0,
     FLAC_VERBATIM = 1,
-    FLAC_FIXED = 2
+    FLAC_FIXED = 2,
+    FLAC_LPC = 3
 };
+constexpr int FLAC_LPC_MAX = 12, FLAC_LPC_PRECISION = 14; // the largest order (the streamable subset up to 48 kHz), the coefficients' bits
+constexpr long long FLAC_LPC_LIMIT = 1ll << 29;           // an LPC residual stays below it in magnitude, or its order is no candidate
 
 inline bool flac_bits_ok(int bits) { return bits == 16 || bits == 24; }
+inline bool flac_lpc_ok(int lpc) { return lpc >= 0 && lpc <= FLAC_LPC_MAX; }
 inline bool flac_rate_ok(int rate) { return rate >= 1 && rate <= 655350; } // STREAMINFO's 20 bits
 // the largest frame of a block of bs frames: header (at most 16), two VERBATIM subframes, CRC-16
 __host__ __device__ constexpr int flac_frame_max(int bs, int bps) { return 16 + (2 * 8 + 2 * bs * bps + 7) / 8 + 2; }
@@ -204,12 +240,9 @@ template <int K> __host__ __device__ inline FlacBest flac_best(uint32_t n, const
     }
     return b;
 }
-// (method, p) from the per-level totals of the partitions' bits, and the subframe that follows
-__host__ __device__ inline FlacChannel flac_decide(const uint32_t *lvl /* [2][9] */, int pmax, int order, bool nonconst, int bs, int width)
+// (method, p) from the per-level totals of the partitions' bits: the coded residual's bits, its 6 header bits included
+__host__ __device__ inline uint32_t flac_coding(const uint32_t *lvl /* [2][9] */, int pmax, FlacChannel &ch)
 {
-    FlacChannel ch = {FLAC_CONSTANT, 0, 0, 0, 8u + (uint32_t)width};
-    if (!nonconst)
-        return ch;
     uint32_t best = 0xffffffffu;
     for (int p = 0; p <= pmax; ++p)
         for (int m = 0; m < 2; ++m)
@@ -222,7 +255,15 @@ __host__ __device__ inline FlacChannel flac_decide(const uint32_t *lvl /* [2][9]
                 ch.porder = p;
             }
         }
-    const uint32_t fixed = 8u + (uint32_t)(order * width) + 6u + best, verbatim = 8u + (uint32_t)(bs * width);
+    return 6u + best;
+}
+// ... and the subframe that follows
+__host__ __device__ inline FlacChannel flac_decide(const uint32_t *lvl /* [2][9] */, int pmax, int order, bool nonconst, int bs, int width)
+{
+    FlacChannel ch = {FLAC_CONSTANT, 0, 0, 0, 8u + (uint32_t)width};
+    if (!nonconst)
+        return ch;
+    const uint32_t fixed = 8u + (uint32_t)(order * width) + flac_coding(lvl, pmax, ch), verbatim = 8u + (uint32_t)(bs * width);
     ch.type = verbatim < fixed ? FLAC_VERBATIM : FLAC_FIXED;
     ch.order = order;
     ch.bits = verbatim < fixed ? verbatim : fixed;
@@ -241,7 +282,126 @@ __host__ __device__ inline int flac_assign(const uint32_t bits[4], int &c0, int 
     return a == 0 ? 1 : 7 + a;
 }
 // a subframe's first byte: a zero bit, the type (CONSTANT 000000, VERBATIM 000001, FIXED 001ooo), no wasted bits
-__host__ __device__ inline uint32_t flac_subframe_byte(int type, int order) { return type == FLAC_CONSTANT ? 0x00u : type == FLAC_VERBATIM ? 0x02u : (uint32_t)(8 | order) << 1; }
+__host__ __device__ inline uint32_t flac_subframe_byte(int type, int order)
+{
+    return type == FLAC_CONSTANT ? 0x00u : type == FLAC_VERBATIM ? 0x02u : type == FLAC_FIXED ? (uint32_t)(8 | order) << 1 : (uint32_t)(32 | (order - 1)) << 1;
+}
+
+// ---------------------------------------------------------------- the LPC rules, each stated once for the host and the kernel
+// 1. the window, an integer parabola without a table: 7 .. 16384 over a full block; the windowed sample fits 25 bits as the sample does
+__host__ __device__ inline int32_t flac_lpc_window(int i) { return ((2 * i + 1) * (2 * FLAC_BLOCK - 1 - 2 * i)) >> 10; }
+__host__ __device__ inline int32_t flac_lpc_windowed(int32_t x, int i) { return (int32_t)(((long long)x * flac_lpc_window(i) + 8192) >> 14); }
+// 2. the autocorrelation is the exact integer sum r[l] = sum of xw[i] xw[i - l] (products below 2^48, sums below 2^60: any grouping)
+// 3, 4. Levinson-Durbin in double on (double)r[l] -- one order of operations, + - * / and comparisons only, built with -ffp-contract=off
+// on both sides -- and, after every order i, that order's coefficients quantised to 14 bits with error feedback into row i - 1 of
+// coef[12][12] (c_1 first, zeros behind c_i) and shift[i - 1].  a: 13 doubles of scratch.  Returns how many orders 1 .. n are candidates:
+// it stops at the first reflection coefficient that is not inside (-1, 1) (a NaN fails the comparison) or error that is not > 0.
+__host__ __device__ inline int flac_lpc_solve(const long long *r, int P, double *a, int32_t *coef, int32_t *shift)
+{
+    if (r[0] == 0)
+        return 0;
+    double err = (double)r[0];
+    for (int i = 1; i <= P; ++i)
+    {
+        double acc = (double)r[i];
+        for (int j = 1; j < i; ++j)
+            acc = acc - a[j] * (double)r[i - j];
+        const double k = acc / err;
+        if (!(k > -1.0 && k < 1.0))
+            return i - 1;
+        for (int j = 1; 2 * j < i; ++j) // a_j and a_{i-j} from each other's old values
+        {
+            const double lo = a[j], hi = a[i - j];
+            a[j] = lo - k * hi;
+            a[i - j] = hi - k * lo;
+        }
+        if (i % 2 == 0)
+            a[i / 2] = a[i / 2] - k * a[i / 2];
+        a[i] = k;
+        err = err * (1.0 - k * k);
+        if (!(err > 0.0))
+            return i - 1;
+        double m = 0.0;
+        for (int j = 1; j <= i; ++j)
+        {
+            const double v = a[j] < 0.0 ? -a[j] : a[j];
+            m = v > m ? v : m;
+        }
+        long long mbits;
+        __builtin_memcpy(&mbits, &m, 8); // floor(log2(m)) is the exponent field (zero and subnormals: -1023, so the shift clamps to 15)
+        int sh = 13 - ((int)((mbits >> 52) & 0x7ff) - 1023 + 1);
+        sh = sh < 0 ? 0 : sh > 15 ? 15 : sh;
+        const double scale = (double)(1 << sh);
+        double fb = 0.0;
+        for (int j = 1; j <= FLAC_LPC_MAX; ++j)
+        {
+            int32_t c = 0;
+            if (j <= i)
+            {
+                fb = fb + a[j] * scale;
+                const double v = fb + 0.5; // c = clamp(floor(v), -8192, 8191), the floor through a truncating conversion
+                if (v >= 8192.0)
+                    c = 8191;
+                else if (v < -8192.0)
+                    c = -8192;
+                else
+                {
+                    c = (int32_t)v;
+                    c -= (double)c > v ? 1 : 0;
+                }
+                fb = fb - (double)c;
+            }
+            coef[(i - 1) * FLAC_LPC_MAX + j - 1] = c;
+        }
+        shift[i - 1] = sh;
+    }
+    return P;
+}
+// 5. the residual of one sample: x(0) is the sample, x(j) its j-th predecessor (anything where c[j - 1] is zero); 64-bit sum and shift.
+// An order whose residual reaches 2^29 in magnitude anywhere in [o, bs) is no candidate: below it the zigzag code stays below 2^30, inside
+// what the 32-bit fold, the saturating Rice sums (operands <= 2^31 - 1) and the 64-bit order sums (16 magnitudes below 2^30) assume.
+template <class X> __host__ __device__ inline long long flac_lpc_error(const X &x, const int32_t (&c)[FLAC_LPC_MAX], int shift)
+{
+    long long s = 0;
+#pragma unroll
+    for (int j = 0; j < FLAC_LPC_MAX; ++j)
+        s += (long long)c[j] * x(j + 1); // (v_mad_i64_i32: a 14-bit coefficient times a 17-bit sample already passes 32 bits over 12 taps)
+    return (long long)x(0) - (s >> shift);
+}
+// 6. the order: the candidate with the smallest proxy of S[o - 1] = sum of |e_o[i]| over [12, bs) -- every order over the same samples --
+// the lower order on a tie; 0: none.  bad: bit o - 1 set where order o broke rule 5.
+__host__ __device__ inline int flac_lpc_choose(int candidates, uint32_t bad, const unsigned long long *S, int width)
+{
+    int best = 0;
+    unsigned long long least = ~0ull;
+    for (int o = 1; o <= candidates; ++o)
+    {
+        if ((bad >> (o - 1)) & 1)
+            continue;
+        unsigned long long p = ~0ull;
+        for (int k = 0; k <= 30; ++k)
+        {
+            const unsigned long long c = (unsigned long long)(FLAC_BLOCK - FLAC_LPC_MAX) * (unsigned)(k + 1) + ((2 * S[o - 1]) >> k);
+            p = c < p ? c : p;
+        }
+        p += (unsigned long long)(o * (width + FLAC_LPC_PRECISION) + 9);
+        if (p < least)
+        {
+            least = p;
+            best = o;
+        }
+    }
+    return best;
+}
+// 7, 8. the LPC subframe of order o from its residual's level totals (the byte, o warm-up samples, 4 bits of precision - 1, 5 bits of shift,
+// o coefficients, the coded residual), and FIXED against LPC: the smaller exact bit count, FIXED (or VERBATIM, or CONSTANT) on a tie
+__host__ __device__ inline FlacChannel flac_decide_lpc(const uint32_t *lvl /* [2][9] */, int order, int width)
+{
+    FlacChannel ch = {FLAC_LPC, order, 0, 0, 0};
+    ch.bits = 8u + (uint32_t)(order * width) + 9u + (uint32_t)(order * FLAC_LPC_PRECISION) + flac_coding(lvl, FLAC_MAX_PORDER, ch);
+    return ch;
+}
+__host__ __device__ inline FlacChannel flac_pick(const FlacChannel &fixed, const FlacChannel &lpc) { return fixed.type != FLAC_CONSTANT && lpc.bits < fixed.bits ? lpc : fixed; }
 
 // ---------------------------------------------------------------- the host restatement
 struct FlacBitWriter // big-endian, into bytes that are zero
@@ -256,8 +416,44 @@ struct FlacBitWriter // big-endian, into bytes that are zero
     }
 };
 
-// one channel of a block analysed: its subframe and kpart[heap index] of the chosen method
-template <int K> inline FlacChannel flac_channel_host(const int32_t *x, int bs, int width, std::vector<uint32_t> &u, uint8_t *kpart)
+// the exhaustive Rice search of a residual u[order .. bs): the per-level totals and every partition's parameter under both methods
+template <int K> inline void flac_rice_host(const std::vector<uint32_t> &u, int bs, int order, uint32_t (&lvl)[2][9], uint8_t (&kall)[2][FLAC_HEAP])
+{
+    const int pmax = bs == FLAC_BLOCK ? FLAC_MAX_PORDER : 0;
+    // exact sums of the finest partitions, merged pairwise down the orders (a saturated sum is min(exact sum, cap) in any grouping)
+    std::vector<unsigned long long> sums((size_t)K << pmax, 0);
+    for (int i = 0; i < bs; ++i)
+        for (int k = 0; k < K; ++k)
+            sums[(size_t)(i / (bs >> pmax)) * K + k] += u[i] >> k;
+    for (int p = pmax; p >= 0; --p)
+    {
+        for (int j = 0; j < (1 << p); ++j)
+        {
+            uint32_t c[K];
+            for (int k = 0; k < K; ++k)
+                c[k] = (uint32_t)std::min<unsigned long long>(sums[(size_t)j * K + k], FLAC_SUM_CAP);
+            const FlacBest b = flac_best<K>((uint32_t)((bs >> p) - (j == 0 ? order : 0)), c);
+            for (int m = 0; m < 2; ++m)
+            {
+                lvl[m][p] += b.bits[m];
+                kall[m][(1 << p) + j] = (uint8_t)b.k[m];
+            }
+        }
+        for (int j = 0; p > 0 && j < (1 << (p - 1)); ++j)
+            for (int k = 0; k < K; ++k)
+                sums[(size_t)j * K + k] = sums[(size_t)(2 * j) * K + k] + sums[(size_t)(2 * j + 1) * K + k];
+    }
+}
+
+struct FlacLpcChoice // the predictor of a channel whose subframe is FLAC_LPC
+{
+    int32_t coef[FLAC_LPC_MAX];
+    int shift;
+};
+
+// one channel of a block analysed: its subframe, kpart[heap index] of the chosen method and, for FLAC_LPC, its predictor.  lpc: 0, or the
+// largest LPC order that is a candidate (a full block only)
+template <int K> inline FlacChannel flac_channel_host(const int32_t *x, int bs, int width, int lpc, std::vector<uint32_t> &u, uint8_t *kpart, FlacLpcChoice &lp)
 {
     const int maxo = std::min(4, bs - 1);
     std::vector<int32_t> e(x, x + bs);
@@ -285,35 +481,54 @@ template <int K> inline FlacChannel flac_channel_host(const int32_t *x, int bs, 
     const int pmax = bs == FLAC_BLOCK ? FLAC_MAX_PORDER : 0;
     uint32_t lvl[2][9] = {};
     uint8_t kall[2][FLAC_HEAP] = {};
-    // exact sums of the finest partitions, merged pairwise down the orders (a saturated sum is min(exact sum, cap) in any grouping)
-    std::vector<unsigned long long> sums((size_t)K << pmax, 0);
-    for (int i = 0; i < bs; ++i)
-        for (int k = 0; k < K; ++k)
-            sums[(size_t)(i / (bs >> pmax)) * K + k] += u[i] >> k;
-    for (int p = pmax; p >= 0; --p)
-    {
-        for (int j = 0; j < (1 << p); ++j)
-        {
-            uint32_t c[K];
-            for (int k = 0; k < K; ++k)
-                c[k] = (uint32_t)std::min<unsigned long long>(sums[(size_t)j * K + k], FLAC_SUM_CAP);
-            const FlacBest b = flac_best<K>((uint32_t)((bs >> p) - (j == 0 ? order : 0)), c);
-            for (int m = 0; m < 2; ++m)
-            {
-                lvl[m][p] += b.bits[m];
-                kall[m][(1 << p) + j] = (uint8_t)b.k[m];
-            }
-        }
-        for (int j = 0; p > 0 && j < (1 << (p - 1)); ++j)
-            for (int k = 0; k < K; ++k)
-                sums[(size_t)j * K + k] = sums[(size_t)(2 * j) * K + k] + sums[(size_t)(2 * j + 1) * K + k];
-    }
-    const FlacChannel ch = flac_decide(&lvl[0][0], pmax, order, nonconst, bs, width);
+    flac_rice_host<K>(u, bs, order, lvl, kall);
+    FlacChannel ch = flac_decide(&lvl[0][0], pmax, order, nonconst, bs, width);
     std::copy(kall[ch.method], kall[ch.method] + FLAC_HEAP, kpart);
+    if (lpc < 1 || bs != FLAC_BLOCK || !nonconst)
+        return ch;
+    // the LPC candidate (rules 1 - 6), then its exact bits against the FIXED ones (rule 7)
+    std::vector<long long> xw(bs);
+    for (int i = 0; i < bs; ++i)
+        xw[i] = flac_lpc_windowed(x[i], i);
+    long long r[FLAC_LPC_MAX + 1] = {};
+    for (int l = 0; l <= lpc; ++l)
+        for (int i = l; i < bs; ++i)
+            r[l] += xw[i] * xw[i - l];
+    double a[FLAC_LPC_MAX + 1];
+    int32_t coef[FLAC_LPC_MAX][FLAC_LPC_MAX], shift[FLAC_LPC_MAX];
+    const int candidates = flac_lpc_solve(r, lpc, a, &coef[0][0], shift);
+    unsigned long long S[FLAC_LPC_MAX] = {};
+    uint32_t bad = 0;
+    auto error_at = [&](int o, int i) { return flac_lpc_error([&](int j) { return i - j >= 0 ? x[i - j] : 0; }, coef[o - 1], shift[o - 1]); };
+    for (int o = 1; o <= candidates; ++o)
+        for (int i = o; i < bs; ++i)
+        {
+            const long long ei = error_at(o, i), mag = ei < 0 ? -ei : ei;
+            bad |= mag >= FLAC_LPC_LIMIT ? 1u << (o - 1) : 0u;
+            S[o - 1] += i >= FLAC_LPC_MAX ? (unsigned long long)mag : 0ull;
+        }
+    const int o = flac_lpc_choose(candidates, bad, S, width);
+    if (!o)
+        return ch;
+    std::vector<uint32_t> ul(bs, 0);
+    for (int i = o; i < bs; ++i)
+        ul[i] = flac_fold((int32_t)error_at(o, i));
+    uint32_t lvll[2][9] = {};
+    uint8_t kalll[2][FLAC_HEAP] = {};
+    flac_rice_host<K>(ul, bs, o, lvll, kalll);
+    ch = flac_pick(ch, flac_decide_lpc(&lvll[0][0], o, width));
+    if (ch.type == FLAC_LPC)
+    {
+        u = ul;
+        std::copy(kalll[ch.method], kalll[ch.method] + FLAC_HEAP, kpart);
+        std::copy(coef[o - 1], coef[o - 1] + FLAC_LPC_MAX, lp.coef);
+        lp.shift = shift[o - 1];
+    }
     return ch;
 }
 
-inline void flac_subframe_host(FlacBitWriter &w, const FlacChannel &ch, const int32_t *x, int bs, int width, const std::vector<uint32_t> &u, const uint8_t *kpart)
+inline void flac_subframe_host(FlacBitWriter &w, const FlacChannel &ch, const int32_t *x, int bs, int width, const std::vector<uint32_t> &u, const uint8_t *kpart,
+                               const FlacLpcChoice &lp)
 {
     const uint32_t mask = width == 32 ? 0xffffffffu : (1u << width) - 1;
     w.put(flac_subframe_byte(ch.type, ch.order), 8);
@@ -326,6 +541,13 @@ inline void flac_subframe_host(FlacBitWriter &w, const FlacChannel &ch, const in
     {
         for (int i = 0; i < ch.order; ++i)
             w.put((uint32_t)x[i] & mask, width);
+        if (ch.type == FLAC_LPC)
+        {
+            w.put(FLAC_LPC_PRECISION - 1, 4);
+            w.put((uint32_t)lp.shift, 5);
+            for (int j = 0; j < ch.order; ++j)
+                w.put((uint32_t)lp.coef[j] & ((1u << FLAC_LPC_PRECISION) - 1), FLAC_LPC_PRECISION);
+        }
         w.put((uint32_t)ch.method, 2);
         w.put((uint32_t)ch.porder, 4);
         const int psize = bs >> ch.porder;
@@ -343,7 +565,7 @@ inline void flac_subframe_host(FlacBitWriter &w, const FlacChannel &ch, const in
 }
 
 // n frames of output buffer `buffer` -> a complete stream at out (capacity >= flac_bound(n, bps), checked by the caller); returns its bytes
-template <class T> inline size_t flac_encode_host(const float *x, long long n, int rate, int buffer, bool dither, uint32_t seed, uint8_t *out)
+template <class T> inline size_t flac_encode_host(const float *x, long long n, int rate, int buffer, bool dither, uint32_t seed, int lpc, uint8_t *out)
 {
     constexpr int BPS = T::frame_bytes * 4, K = flac_params(BPS);
     const uint32_t key[2] = {sample_dither_key(seed, buffer, 0), sample_dither_key(seed, buffer, 1)};
@@ -368,11 +590,12 @@ template <class T> inline size_t flac_encode_host(const float *x, long long n, i
             ch[3][i] = l - r;
         }
         FlacChannel fc[4];
+        FlacLpcChoice lp[4];
         uint8_t kpart[4][FLAC_HEAP];
         uint32_t bits[4];
         for (int c = 0; c < 4; ++c)
         {
-            fc[c] = flac_channel_host<K>(ch[c].data(), bs, BPS + (c == 3), u[c], kpart[c]);
+            fc[c] = flac_channel_host<K>(ch[c].data(), bs, BPS + (c == 3), lpc, u[c], kpart[c], lp[c]);
             bits[c] = fc[c].bits;
         }
         int c0, c1;
@@ -380,8 +603,8 @@ template <class T> inline size_t flac_encode_host(const float *x, long long n, i
         frame.assign((size_t)flac_frame_max(bs, BPS) + 8, 0);
         const int hb = flac_frame_header(frame.data(), bs, BPS, code, (uint32_t)blk);
         FlacBitWriter w{frame.data(), (size_t)hb * 8};
-        flac_subframe_host(w, fc[c0], ch[c0].data(), bs, BPS + (c0 == 3), u[c0], kpart[c0]);
-        flac_subframe_host(w, fc[c1], ch[c1].data(), bs, BPS + (c1 == 3), u[c1], kpart[c1]);
+        flac_subframe_host(w, fc[c0], ch[c0].data(), bs, BPS + (c0 == 3), u[c0], kpart[c0], lp[c0]);
+        flac_subframe_host(w, fc[c1], ch[c1].data(), bs, BPS + (c1 == 3), u[c1], kpart[c1], lp[c1]);
         const size_t body = (w.pos + 7) / 8;
         uint32_t crc = 0;
         for (size_t i = 0; i < body; ++i)
@@ -415,7 +638,20 @@ struct FlacArgs
     const uint32_t *words; // nullptr, or the four words the divisor comes from (levels.h)
     umx_levels_acc *acc;   // nullptr, or the record whose clipped[first_buffer + b] counts what clamps
     int n, nblocks, dither, first_buffer;
+    int lpc;               // the LPC variant alone: 1 .. 12, the largest candidate order
 };
+
+// the sum of a 64-bit value over the wave, in every lane
+__device__ inline unsigned long long flac_wave_sum64(unsigned long long s)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+    {
+        const uint32_t ol = (uint32_t)__shfl_xor((int)(uint32_t)s, d, 64), oh = (uint32_t)__shfl_xor((int)(uint32_t)(s >> 32), d, 64);
+        s += ((unsigned long long)oh << 32) | ol;
+    }
+    return s;
+}
 
 // a thread's bit string: a big-endian word in registers, whole words stored, the first one it touches ORed (it may hold a neighbour's bits)
 struct FlacPacker
@@ -423,7 +659,7 @@ struct FlacPacker
     uint32_t *image;
     uint32_t pos, cw;
     bool first;
-    __device__ void flush()
+    __device__ __forceinline__ void flush()
     {
         if (cw)
         {
@@ -436,7 +672,7 @@ struct FlacPacker
         first = false;
         cw = 0;
     }
-    __device__ void put(uint32_t v, uint32_t n) // v < 2^n, 1 <= n <= 32
+    __device__ __forceinline__ void put(uint32_t v, uint32_t n) // v < 2^n, 1 <= n <= 32
     {
         const uint32_t room = 32 - (pos & 31);
         if (n < room)
@@ -453,30 +689,43 @@ struct FlacPacker
                 cw = v << (32 - (n - room));
         }
     }
-    __device__ void skip(uint32_t q) // q zero bits
+    __device__ __forceinline__ void skip(uint32_t q) // q zero bits
     {
         if (((pos + q) >> 5) != (pos >> 5))
             flush();
         pos += q;
     }
-    __device__ void finish() // the last word, which a neighbour may share
+    __device__ __forceinline__ void finish() // the last word, which a neighbour may share
     {
         first = true;
         flush();
     }
 };
 
-template <class T> FLAC_KERNEL void flac_encode_kernel(FlacArgs a)
+template <class T, bool LPC> FLAC_KERNEL void flac_encode_kernel(FlacArgs a)
 {
     constexpr int BPS = T::frame_bytes * 4, K = flac_params(BPS), IMG = flac_slot_bytes(BPS);
-    __shared__ __attribute__((aligned(16))) int32_t samp[2][FLAC_BLOCK + 4];
+    // PRE zero predecessors in front of a channel; RESIDUALS a channel has searched: FIXED, or FIXED (0 .. 3) and LPC (4 .. 7)
+    constexpr int PRE = LPC ? FLAC_LPC_MAX : 4, RESIDUALS = LPC ? 8 : 4, WIDE = FLAC_RUN + FLAC_LPC_MAX;
+    __shared__ __attribute__((aligned(16))) int32_t samp[2][FLAC_BLOCK + PRE];
     __shared__ __attribute__((aligned(16))) uint32_t image[IMG / 4];
-    __shared__ uint8_t kbest[4][2][FLAC_HEAP];
+    __shared__ uint8_t kbest[RESIDUALS][2][FLAC_HEAP];
     __shared__ uint16_t crctab[256];
     __shared__ uint32_t note[64]; // [0..20): the four channels' decisions; [32]: clipped; [40..44): wave totals; [48..52): wave CRCs
+    __shared__ int32_t lpcsel[LPC ? 4 : 1][16]; // a channel's LPC candidate: 12 coefficients, [12] the shift, [13] the order (0: none)
     // the analysis' exchange, in the image: order sums [wave][channel][6] as 64-bit, Rice sums [channel][wave][K], level totals [channel][2][9]
     unsigned long long *const osum = reinterpret_cast<unsigned long long *>(image);
-    uint32_t *const wsum = image + 192, *const lvl = image + 192 + 4 * 4 * 31;
+    uint32_t *const wsum = image + 192, *const lvl = image + 192 + RESIDUALS * 4 * 31;
+    // ... and behind them the LPC analysis': autocorrelation sums [wave][channel][13] and their totals [channel][13] (64-bit), Levinson's
+    // scratch [channel][13] (double), the order sums [channel][12] (64-bit), every order's coefficients [channel][12][12] and shift
+    // [channel][12], the candidates and the refused orders [channel]: 10 720 B with what lies in front
+    unsigned long long *const rpart = reinterpret_cast<unsigned long long *>(lvl + RESIDUALS * 18);
+    long long *const rsum = reinterpret_cast<long long *>(rpart + 16 * 13);
+    double *const lev = reinterpret_cast<double *>(rsum + 4 * 13);
+    unsigned long long *const ssum = reinterpret_cast<unsigned long long *>(lev + 4 * 13);
+    int32_t *const qcoef = reinterpret_cast<int32_t *>(ssum + 4 * FLAC_LPC_MAX), *const qshift = qcoef + 4 * FLAC_LPC_MAX * FLAC_LPC_MAX;
+    int32_t *const cands = qshift + 4 * FLAC_LPC_MAX;
+    uint32_t *const refused = reinterpret_cast<uint32_t *>(cands + 4);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, blk = blockIdx.x, b = blockIdx.y;
     const int bs = min(FLAC_BLOCK, a.n - blk * FLAC_BLOCK), maxo = min(4, bs - 1);
     const bool full = bs == FLAC_BLOCK;
@@ -500,15 +749,18 @@ template <class T> FLAC_KERNEL void flac_encode_kernel(FlacArgs a)
                 l = encode_sample<T, true>(x.x, pre, a.dither != 0, key0, k, clip);
                 r = encode_sample<T, true>(x.y, pre, a.dither != 0, key1, k, clip);
             }
-            samp[0][4 + i] = l;
-            samp[1][4 + i] = r;
+            samp[0][PRE + i] = l;
+            samp[1][PRE + i] = r;
         }
-        if (t < 4)
+        if (t < PRE)
             samp[0][t] = samp[1][t] = 0;
-        if (t < 72)
+        if (t < RESIDUALS * 18)
             lvl[t] = 0;
         if (t == 0)
             note[32] = 0;
+        if constexpr (LPC)
+            if (t < 64)
+                lpcsel[t >> 4][t & 15] = 0;
         {
             uint32_t c = (uint32_t)t << 8;
 #pragma unroll
@@ -523,7 +775,7 @@ template <class T> FLAC_KERNEL void flac_encode_kernel(FlacArgs a)
 
     // a thread's run of channel c with its four predecessors: v[j] is sample 16 t + j - 4
     auto load_run = [&](int c, int32_t (&v)[FLAC_RUN + 4]) {
-        const int4 *pl = reinterpret_cast<const int4 *>(&samp[0][FLAC_RUN * t]), *pr = reinterpret_cast<const int4 *>(&samp[1][FLAC_RUN * t]);
+        const int4 *pl = reinterpret_cast<const int4 *>(&samp[0][PRE - 4 + FLAC_RUN * t]), *pr = reinterpret_cast<const int4 *>(&samp[1][PRE - 4 + FLAC_RUN * t]);
 #pragma unroll
         for (int q = 0; q < (FLAC_RUN + 4) / 4; ++q)
         {
@@ -533,6 +785,40 @@ template <class T> FLAC_KERNEL void flac_encode_kernel(FlacArgs a)
             for (int i = 0; i < 4; ++i)
                 v[4 * q + i] = c == 0 ? ls[i] : c == 1 ? rs[i] : c == 2 ? (ls[i] + rs[i]) >> 1 : ls[i] - rs[i];
         }
+    };
+    // the LPC variant's reach, twelve predecessors: v[j] is sample 16 t + j - 12 (seven 16-byte loads a side; PRE = 12 there)
+    auto load_wide = [&](int c, int32_t (&v)[WIDE]) {
+        const int4 *pl = reinterpret_cast<const int4 *>(&samp[0][FLAC_RUN * t]), *pr = reinterpret_cast<const int4 *>(&samp[1][FLAC_RUN * t]);
+#pragma unroll
+        for (int q = 0; q < WIDE / 4; ++q)
+        {
+            const int4 l = pl[q], r = pr[q];
+            const int ls[4] = {l.x, l.y, l.z, l.w}, rs[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                v[4 * q + i] = c == 0 ? ls[i] : c == 1 ? rs[i] : c == 2 ? (ls[i] + rs[i]) >> 1 : ls[i] - rs[i];
+        }
+    };
+    // the thread's 16 residuals of channel c under cf and sh (rule 5), and whether one of those in [from, bs) reaches the limit
+    auto lpc_errors = [&](const int32_t (&v)[WIDE], const int32_t (&cf)[FLAC_LPC_MAX], int sh, int from, int32_t (&e)[FLAC_RUN]) {
+        bool over = false;
+#pragma unroll
+        for (int i = 0; i < FLAC_RUN; ++i)
+        {
+            const long long ei = flac_lpc_error([&](int j) { return v[FLAC_LPC_MAX + i - j]; }, cf, sh);
+            over |= FLAC_RUN * t + i >= from && (ei >= FLAC_LPC_LIMIT || ei <= -FLAC_LPC_LIMIT);
+            e[i] = (int32_t)ei;
+        }
+        return over;
+    };
+    // ... under the channel's chosen candidate
+    auto lpc_run = [&](int c, int32_t (&e)[FLAC_RUN]) {
+        int32_t v[WIDE], cf[FLAC_LPC_MAX];
+        load_wide(c, v);
+#pragma unroll
+        for (int j = 0; j < FLAC_LPC_MAX; ++j)
+            cf[j] = lpcsel[c][j];
+        lpc_errors(v, cf, lpcsel[c][12], 0, e);
     };
     auto difference = [&](int32_t (&v)[FLAC_RUN + 4], int o) { // e_{o-1} -> e_o in place, valid from v[o] on
 #pragma unroll
@@ -608,15 +894,117 @@ template <class T> FLAC_KERNEL void flac_encode_kernel(FlacArgs a)
         nonconst[c] = s[5] != 0;
     }
 
-    // ---- Rice: per channel the sums of u >> k of the thread's run, folded up the partition orders
+    // ---- LPC (rules 1 - 6) in a full block: every channel's candidate into lpcsel
+    if constexpr (LPC)
+        if (full)
+        {
+            // autocorrelation: a thread windows its run and the twelve samples before it and forms the 13 lags' products of its 16 samples
+            // in 64 bits (v_mad_i64_i32); wave sums by shuffles, the four waves' through LDS
 #pragma unroll 1
-    for (int c = 0; c < 4; ++c)
+            for (int c = 0; c < 4; ++c)
+            {
+                int32_t v[WIDE];
+                load_wide(c, v);
+#pragma unroll
+                for (int j = 0; j < WIDE; ++j)
+                    v[j] = flac_lpc_windowed(v[j], FLAC_RUN * t + j - FLAC_LPC_MAX); // (in front of the block: zero samples)
+#pragma unroll
+                for (int l = 0; l <= FLAC_LPC_MAX; ++l)
+                {
+                    long long r = 0;
+#pragma unroll
+                    for (int i = 0; i < FLAC_RUN; ++i)
+                        r += (long long)v[FLAC_LPC_MAX + i] * v[FLAC_LPC_MAX + i - l];
+                    const unsigned long long all = flac_wave_sum64((unsigned long long)r);
+                    if (lane == 0)
+                        rpart[(wave * 4 + c) * 13 + l] = all;
+                }
+            }
+            __syncthreads();
+            // Levinson-Durbin and the quantisation of every order: serial and tiny, lane 0 of wave c for channel c, its arrays in LDS
+            if (lane == 0)
+            {
+                const int c = wave;
+                for (int l = 0; l <= FLAC_LPC_MAX; ++l)
+                    rsum[c * 13 + l] = (long long)(rpart[(0 * 4 + c) * 13 + l] + rpart[(1 * 4 + c) * 13 + l] + rpart[(2 * 4 + c) * 13 + l] + rpart[(3 * 4 + c) * 13 + l]);
+                const bool moves = c == 0 ? nonconst[0] : c == 1 ? nonconst[1] : c == 2 ? nonconst[2] : nonconst[3];
+                cands[c] = moves ? flac_lpc_solve(rsum + c * 13, a.lpc, lev + c * 13, qcoef + c * FLAC_LPC_MAX * FLAC_LPC_MAX, qshift + c * FLAC_LPC_MAX) : 0;
+                for (int o = 0; o < FLAC_LPC_MAX; ++o)
+                    ssum[c * FLAC_LPC_MAX + o] = 0;
+                refused[c] = 0;
+            }
+            __syncthreads();
+            // the candidates' residuals: a channel's 28 samples are loaded once for all its orders, an order's zero-padded coefficients come
+            // from LDS (one address for the wave); |e| sums over [12, bs) and the limit of rule 5
+#pragma unroll 1
+            for (int c = 0; c < 4; ++c)
+            {
+                const int nc = cands[c];
+                if (nc == 0)
+                    continue;
+                int32_t v[WIDE];
+                load_wide(c, v);
+#pragma unroll 1
+                for (int o = 1; o <= nc; ++o)
+                {
+                    int32_t cf[FLAC_LPC_MAX], e[FLAC_RUN];
+#pragma unroll
+                    for (int j = 0; j < FLAC_LPC_MAX; ++j)
+                        cf[j] = qcoef[(c * FLAC_LPC_MAX + o - 1) * FLAC_LPC_MAX + j];
+                    const bool over = lpc_errors(v, cf, qshift[c * FLAC_LPC_MAX + o - 1], o, e);
+                    unsigned long long s = 0;
+#pragma unroll
+                    for (int i = 0; i < FLAC_RUN; ++i)
+                        s += FLAC_RUN * t + i >= FLAC_LPC_MAX ? (unsigned long long)(e[i] < 0 ? -(long long)e[i] : (long long)e[i]) : 0ull;
+                    s = flac_wave_sum64(s);
+                    const bool any = __any(over);
+                    if (lane == 0)
+                    {
+                        atomicAdd(&ssum[c * FLAC_LPC_MAX + o - 1], s);
+                        if (any)
+                            atomicOr(&refused[c], 1u << (o - 1));
+                    }
+                }
+            }
+            __syncthreads();
+            if (lane == 0)
+            {
+                const int c = wave, o = flac_lpc_choose(cands[c], refused[c], ssum + c * FLAC_LPC_MAX, BPS + (c == 3));
+                if (o)
+                {
+                    for (int j = 0; j < FLAC_LPC_MAX; ++j)
+                        lpcsel[c][j] = qcoef[(c * FLAC_LPC_MAX + o - 1) * FLAC_LPC_MAX + j];
+                    lpcsel[c][12] = qshift[c * FLAC_LPC_MAX + o - 1];
+                    lpcsel[c][13] = o;
+                }
+            }
+            __syncthreads();
+        }
+
+    // ---- Rice: per searched residual the sums of u >> k of the thread's run, folded up the partition orders
+#pragma unroll 1
+    for (int rs = 0; rs < RESIDUALS; ++rs)
     {
-        const int o = c == 0 ? order[0] : c == 1 ? order[1] : c == 2 ? order[2] : order[3];
+        const int c = rs & 3;
+        int o = c == 0 ? order[0] : c == 1 ? order[1] : c == 2 ? order[2] : order[3];
         int32_t v[FLAC_RUN + 4];
-        load_run(c, v);
-        for (int p = 1; p <= o; ++p)
-            difference(v, p);
+        if (!LPC || rs < 4)
+        {
+            load_run(c, v);
+            for (int p = 1; p <= o; ++p)
+                difference(v, p);
+        }
+        else
+        {
+            o = lpcsel[c][13];
+            if (o == 0)
+                continue;
+            int32_t e[FLAC_RUN];
+            lpc_run(c, e);
+#pragma unroll
+            for (int i = 0; i < FLAC_RUN; ++i)
+                v[4 + i] = e[i];
+        }
         uint32_t ck[K];
 #pragma unroll
         for (int k = 0; k < K; ++k)
@@ -643,26 +1031,32 @@ template <class T> FLAC_KERNEL void flac_encode_kernel(FlacArgs a)
             {
                 const int j = t >> s, p = FLAC_MAX_PORDER - s;
                 const FlacBest bb = flac_best<K>((uint32_t)((FLAC_RUN << s) - (j == 0 ? o : 0)), ck);
-                kbest[c][0][(1 << p) + j] = (uint8_t)bb.k[0];
-                kbest[c][1][(1 << p) + j] = (uint8_t)bb.k[1];
-                atomicAdd(&lvl[c * 18 + p], bb.bits[0]);
-                atomicAdd(&lvl[c * 18 + 9 + p], bb.bits[1]);
+                kbest[rs][0][(1 << p) + j] = (uint8_t)bb.k[0];
+                kbest[rs][1][(1 << p) + j] = (uint8_t)bb.k[1];
+                atomicAdd(&lvl[rs * 18 + p], bb.bits[0]);
+                atomicAdd(&lvl[rs * 18 + 9 + p], bb.bits[1]);
             }
         }
         if (lane == 0)
 #pragma unroll
             for (int k = 0; k < K; ++k)
-                wsum[(c * 4 + wave) * 31 + k] = ck[k];
+                wsum[(rs * 4 + wave) * 31 + k] = ck[k];
     }
     __syncthreads();
-    // wave c finishes channel c: lane k prices parameter k for the two partitions of order 1 and the one of order 0
+    // wave c finishes channel c: lane k prices parameter k for the two partitions of order 1 and the one of order 0 -- of its FIXED residual
+    // and then, where it has an LPC candidate, of that (rule 7)
+    FlacChannel fixed = {};
+#pragma unroll 1
+    for (int rs = wave; rs < RESIDUALS; rs += 4)
     {
-        const int c = wave, o = c == 0 ? order[0] : c == 1 ? order[1] : c == 2 ? order[2] : order[3];
+        const int c = wave, o = LPC && rs >= 4 ? lpcsel[c][13] : c == 0 ? order[0] : c == 1 ? order[1] : c == 2 ? order[2] : order[3];
+        if (LPC && rs >= 4 && o == 0)
+            break;
         uint32_t w4[4] = {0, 0, 0, 0};
         if (lane < K)
 #pragma unroll
             for (int w = 0; w < 4; ++w)
-                w4[w] = wsum[(c * 4 + w) * 31 + lane];
+                w4[w] = wsum[(rs * 4 + w) * 31 + lane];
         const uint32_t part[3] = {flac_sat_add(flac_sat_add(w4[0], w4[1]), flac_sat_add(w4[2], w4[3])), flac_sat_add(w4[0], w4[1]), flac_sat_add(w4[2], w4[3])};
         const uint32_t n[3] = {(uint32_t)(bs - o), (uint32_t)(FLAC_BLOCK / 2 - o), (uint32_t)(FLAC_BLOCK / 2)};
 #pragma unroll
@@ -681,13 +1075,17 @@ template <class T> FLAC_KERNEL void flac_encode_kernel(FlacArgs a)
                 }
                 if (lane == 0 && (q == 0 || full))
                 {
-                    kbest[c][m][1 + q] = (uint8_t)(key & 0xff);
-                    lvl[c * 18 + m * 9 + (q ? 1 : 0)] += (uint32_t)(key >> 8); // (this wave alone writes orders 0 and 1)
+                    kbest[rs][m][1 + q] = (uint8_t)(key & 0xff);
+                    lvl[rs * 18 + m * 9 + (q ? 1 : 0)] += (uint32_t)(key >> 8); // (this wave alone writes orders 0 and 1)
                 }
             }
         if (lane == 0)
         {
-            const FlacChannel ch = flac_decide(&lvl[c * 18], full ? FLAC_MAX_PORDER : 0, o, c == 0 ? nonconst[0] : c == 1 ? nonconst[1] : c == 2 ? nonconst[2] : nonconst[3], bs, BPS + (c == 3));
+            FlacChannel ch;
+            if (!LPC || rs < 4)
+                ch = fixed = flac_decide(&lvl[rs * 18], full ? FLAC_MAX_PORDER : 0, o, c == 0 ? nonconst[0] : c == 1 ? nonconst[1] : c == 2 ? nonconst[2] : nonconst[3], bs, BPS + (c == 3));
+            else
+                ch = flac_pick(fixed, flac_decide_lpc(&lvl[rs * 18], o, BPS + (c == 3)));
             note[c * 5 + 0] = (uint32_t)ch.type;
             note[c * 5 + 1] = (uint32_t)ch.order;
             note[c * 5 + 2] = (uint32_t)ch.method;
@@ -720,7 +1118,8 @@ template <class T> FLAC_KERNEL void flac_encode_kernel(FlacArgs a)
         int32_t v[FLAC_RUN + 4];
         load_run(c, v);
         const uint32_t sfbyte = flac_subframe_byte((int)type, (int)o);
-        if (type != FLAC_FIXED)
+        const bool lp = LPC && type == FLAC_LPC;
+        if (type != FLAC_FIXED && !lp)
         {
             FlacPacker pk = {image, base + (t == 0 ? 0u : 8u + (uint32_t)first * (uint32_t)width), 0u, true};
             if (t == 0)
@@ -738,13 +1137,22 @@ template <class T> FLAC_KERNEL void flac_encode_kernel(FlacArgs a)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 warm[i] = (uint32_t)v[4 + i] & mask;
-            for (uint32_t p = 1; p <= o; ++p)
-                difference(v, (int)p);
+            if (!lp)
+                for (uint32_t p = 1; p <= o; ++p)
+                    difference(v, (int)p);
+            else if constexpr (LPC)
+            {
+                int32_t e[FLAC_RUN];
+                lpc_run(c, e);
+#pragma unroll
+                for (int i = 0; i < FLAC_RUN; ++i)
+                    v[4 + i] = e[i];
+            }
             const uint32_t shift = 12 - porder; // log2 of the partition's samples (a short block: one partition, never indexed by it)
             const uint32_t part = full ? (uint32_t)first >> shift : 0u;
-            const uint32_t k = kbest[c][method][(1u << porder) + part];
+            const uint32_t k = kbest[lp ? 4 + c : c][method][(1u << porder) + part];
             const bool opens = count > 0 && (full ? ((uint32_t)first & ((1u << shift) - 1)) == 0 : t == 0);
-            uint32_t mybits = (t == 0 ? 8u + o * (uint32_t)width + 6u : 0u) + (opens ? 4u + method : 0u);
+            uint32_t mybits = (t == 0 ? 8u + o * (uint32_t)width + 6u + (lp ? 9u + o * FLAC_LPC_PRECISION : 0u) : 0u) + (opens ? 4u + method : 0u);
 #pragma unroll
             for (int i = 0; i < FLAC_RUN; ++i)
                 if (i < count && first + i >= (int)o)
@@ -768,10 +1176,25 @@ template <class T> FLAC_KERNEL void flac_encode_kernel(FlacArgs a)
             if (t == 0)
             {
                 pk.put(sfbyte, 8);
+                if (!lp)
+                {
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (i < (int)o)
-                        pk.put(warm[i], (uint32_t)width);
+                    for (int i = 0; i < 4; ++i)
+                        if (i < (int)o)
+                            pk.put(warm[i], (uint32_t)width);
+                }
+                else if constexpr (LPC) // rule 8: the warm-up samples from LDS, the precision, the shift, the coefficients
+                {
+                    for (int i = 0; i < (int)o; ++i)
+                    {
+                        const int32_t l = samp[0][PRE + i], r = samp[1][PRE + i];
+                        pk.put((uint32_t)(c == 0 ? l : c == 1 ? r : c == 2 ? (l + r) >> 1 : l - r) & mask, (uint32_t)width);
+                    }
+                    pk.put(FLAC_LPC_PRECISION - 1, 4);
+                    pk.put((uint32_t)lpcsel[c][12], 5);
+                    for (int j = 0; j < (int)o; ++j)
+                        pk.put((uint32_t)lpcsel[c][j] & ((1u << FLAC_LPC_PRECISION) - 1), FLAC_LPC_PRECISION);
+                }
                 pk.put(method, 2);
                 pk.put(porder, 4);
             }
@@ -813,8 +1236,9 @@ template <class T> FLAC_KERNEL void flac_encode_kernel(FlacArgs a)
         __syncthreads();
         if (t == 0)
         {
-            const uint32_t c01 = flac_crc16_mul(note[48], flac_crc16_advance(6)) ^ note[49], c23 = flac_crc16_mul(note[50], flac_crc16_advance(6)) ^ note[51];
-            const uint32_t all = flac_crc16_mul(c01, flac_crc16_advance(7)) ^ c23;
+            constexpr uint32_t adv6 = flac_crc16_advance(6), adv7 = flac_crc16_advance(7);
+            const uint32_t c01 = flac_crc16_mul(note[48], adv6) ^ note[49], c23 = flac_crc16_mul(note[50], adv6) ^ note[51];
+            const uint32_t all = flac_crc16_mul(c01, adv7) ^ c23;
             uint8_t *w8 = reinterpret_cast<uint8_t *>(image);
             w8[body] = (uint8_t)(all >> 8);
             w8[body + 1] = (uint8_t)all;
@@ -935,8 +1359,8 @@ FLAC_KERNEL void flac_compact_kernel(FlacCompactArgs a)
 inline size_t flac_scratch_slots(int nb, long long n, int bps) { return (size_t)nb * (size_t)flac_blocks(n) * (size_t)flac_slot_bytes(bps) + 64; }
 
 // n frames of buffers 0 .. nb-1 (output first_buffer + b of the call) -> complete streams at out[b], their bytes at bytes[b].  The caller
-// has checked n, rate, bps, the capacities and the scratch (slots, sizes, offsets: flac_scratch_slots bytes, nb x blocks words and doublewords).
-inline void launch_flac(int bps, int nb, const float2 *const *src, int n, int rate, int first_buffer, bool dither, uint32_t seed, const uint32_t *words,
+// has checked n, rate, bps, lpc (0: the kernel without the LPC stages; 1 .. 12: its LPC variant), the capacities and the scratch (slots, sizes, offsets: flac_scratch_slots bytes, nb x blocks words and doublewords).
+inline void launch_flac(int bps, int lpc, int nb, const float2 *const *src, int n, int rate, int first_buffer, bool dither, uint32_t seed, const uint32_t *words,
                         umx_levels_acc *acc, uint8_t *slots, uint32_t *sizes, unsigned long long *offsets, uint8_t *const *out,
                         unsigned long long *bytes, hipStream_t st)
 {
@@ -959,6 +1383,7 @@ inline void launch_flac(int bps, int nb, const float2 *const *src, int n, int ra
     a.nblocks = nblocks;
     a.dither = dither ? 1 : 0;
     a.first_buffer = first_buffer;
+    a.lpc = lpc;
     sa.sizes = ca.sizes = sizes;
     sa.offsets = offsets;
     ca.offsets = offsets;
@@ -970,10 +1395,14 @@ inline void launch_flac(int bps, int nb, const float2 *const *src, int n, int ra
     ca.slots = slots;
     ca.slot_bytes = flac_slot_bytes(bps);
     const dim3 grid((unsigned)nblocks, (unsigned)nb);
-    if (bps == 16)
-        hipLaunchKernelGGL(flac_encode_kernel<SampleS16>, grid, dim3(FLAC_THREADS), 0, st, a);
+    if (bps == 16 && !lpc)
+        hipLaunchKernelGGL((flac_encode_kernel<SampleS16, false>), grid, dim3(FLAC_THREADS), 0, st, a);
+    else if (bps == 16)
+        hipLaunchKernelGGL((flac_encode_kernel<SampleS16, true>), grid, dim3(FLAC_THREADS), 0, st, a);
+    else if (!lpc)
+        hipLaunchKernelGGL((flac_encode_kernel<SampleS24, false>), grid, dim3(FLAC_THREADS), 0, st, a);
     else
-        hipLaunchKernelGGL(flac_encode_kernel<SampleS24>, grid, dim3(FLAC_THREADS), 0, st, a);
+        hipLaunchKernelGGL((flac_encode_kernel<SampleS24, true>), grid, dim3(FLAC_THREADS), 0, st, a);
     hipLaunchKernelGGL(flac_scan_kernel, dim3(nb), dim3(FLAC_THREADS), 0, st, sa);
     hipLaunchKernelGGL(flac_compact_kernel, grid, dim3(FLAC_THREADS), 0, st, ca);
 }

@@ -27,6 +27,9 @@
 //                    <name>.flac instead of .wav, the codes being those UMX_PCM16=1 / UMX_PCM24=1 would have written.  Goes with UMX_MIX,
 //                    UMX_TARGETS / UMX_RESIDUAL, UMX_RESAMPLE, UMX_CLIP, UMX_LEVELS, UMX_LOUDNESS and UMX_TRUE_PEAK; not with UMX_PCM16,
 //                    UMX_PCM24, UMX_SHIFTS > 1 and UMX_CLI_PER_SEGMENT=1
+//   UMX_FLAC_LPC=<0..12>  with UMX_FLAC: LPC subframes of up to that order are candidates in every full block
+//                    (umx_hip_separate_tracks_flac_lpc): smaller files of the same codes, never larger ones.  Refused without
+//                    UMX_FLAC.  Unset or 0: the FIXED-only streams
 //   UMX_PCM24=1      packed 24-bit PCM across PCIe (UMX_SAMPLE_S24): the outputs are written as 24-bit PCM WAVs under the same
 //                    names, quantised on the device; a 24-bit PCM input goes up packed, a 16-bit one as int16, any other encoding as
 //                    fp32; UMX_PCM24_DITHER=<seed> adds TPDF dither with that seed.  Goes where UMX_PCM16 goes, not together with it.
@@ -141,6 +144,12 @@ int main(int argc, const char **argv)
             return 1;
         }
     }
+    const int flac_lpc = getenv("UMX_FLAC_LPC") ? env_int("UMX_FLAC_LPC", -1) : 0; // (unset or 0: the FIXED-only streams byte for byte)
+    if (getenv("UMX_FLAC_LPC") && (flac_lpc < 0 || flac_lpc > 12 || !flac_bits))
+    {
+        fprintf(stderr, "UMX_FLAC_LPC: %s\n", flac_bits ? "need 0 .. 12" : "needs UMX_FLAC=16|24");
+        return 1;
+    }
     umx_measured measured;
     umx_sample_io io = pcmc.io;
     printf("umx-cli (MI355X / gfx950) main driver program\n");
@@ -248,11 +257,11 @@ int main(int argc, const char **argv)
         void *out_io[4]; // (read as the formats say)
         for (int t = 0; t < 4; ++t)
             out_io[t] = flac_bits ? (void *)stems_flac[t].data() : pcmc.active() ? (void *)stems_int[t].data() : (void *)stems[t].data();
-        if (umx_hip_separate_tracks_flac(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out_io,
-                                              hb.flags, &io, clipc.clip_mode, clipc.levels ? &measured.levels : nullptr,
-                                              clipc.loudness ? &measured.loudness : nullptr, nullptr, clipc.true_peak,
-                                              clipc.true_peak != UMX_TRUE_PEAK_OFF ? &measured.true_peak : nullptr, flac_bits, flac_cap, flac_bytes, print_progress,
-                                         nullptr))
+        if (umx_hip_separate_tracks_flac_lpc(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out_io,
+                                             hb.flags, &io, clipc.clip_mode, clipc.levels ? &measured.levels : nullptr,
+                                             clipc.loudness ? &measured.loudness : nullptr, nullptr, clipc.true_peak,
+                                             clipc.true_peak != UMX_TRUE_PEAK_OFF ? &measured.true_peak : nullptr, flac_bits, flac_cap, flac_bytes,
+                                             flac_lpc, print_progress, nullptr))
         {
             fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
             return 1;
