@@ -767,6 +767,43 @@ int umx_hip_separate_tracks_flac_lpc(umx_hip_ctx *ctx, int n_tracks, const void 
                                      double *const *hop_energy, int true_peak_mode, umx_true_peak *true_peak, int flac_bits,
                                      const size_t *out_cap, size_t *out_bytes, int flac_lpc, void (*progress)(float, void *),
                                      void *progress_user);
+/* FLAC in: UMX_SAMPLE_FLAC as io->in_format of the whole-track calls above (every rung that takes a sample io record).
+ * audio_host[i] then points at a record of the bytes of a complete .flac file; length[i] must equal the stream's total sample count
+ * and rate[i] (44100 when rate == NULL) its rate: anything else is UMX_ERR_ARG with a reason.  The bytes go up whole and are decoded
+ * on the device into exactly the floats that the UMX_SAMPLE_S16 / UMX_SAMPLE_S24 upload of the same codes produces (q / 32767.0f,
+ * q * 2^-23), so the call is that call bit for bit.  A stream that does not decode -- a frame that is missing, ambiguous or fails
+ * a CRC -- ends the call with UMX_ERR_ARG naming track and frame; the context stays usable.  As out_format the value is refused (FLAC
+ * out is flac_bits); the track queue, the shift ensemble, the multi-GPU driver and the per-segment calls do not take it.
+ * Accepted: fixed-blocksize streams (sync 0xFFF8) of 2 channels and 16 or 24 bits, block sizes 16 .. 16384 and sample rates in every
+ * header encoding, a known total, all four channel assignments, CONSTANT / VERBATIM / FIXED 0-4 / LPC 1-32 subframes, wasted bits,
+ * RICE and RICE2 with the escape code; an ID3v2 tag in front and any metadata behind STREAMINFO are skipped.  STREAMINFO's MD5 is
+ * not verified: the CRC-8 and CRC-16 of every frame are.  One limit of this decoder's own: a frame longer than twice the bytes of
+ * its two VERBATIM subframes (no encoder that falls back to VERBATIM writes one) fails like a damaged frame -- the bound keeps what a
+ * false sync candidate can make a lane read finite.
+ * umx_hip_flac_probe_host: host only, no context: fills *info from the stream's head (audio_offset: the first frame's byte).
+ * umx_hip_flac_decode_host: the host restatement, (2, n_frames) interleaved fp32 at x; n_frames must be the stream's total.
+ * umx_hip_flac_decode_device: queued on hip_stream, does not wait.  bytes_dev: the n_bytes of the file in device memory (any
+ *   alignment), info: what the probe returned.  *status_dev becomes 0 for a valid stream, else 1 + the first frame number that is
+ *   missing, ambiguous or failed (1 + the number of frames: more sync candidates than the scratch holds); exactly info->n_frames frames
+ *   of out_dev are written, and none for a stream that is not valid.  The scratch is the context's, grow-only: calls on one context
+ *   are ordered by the caller.
+ * The reasons of the two host calls are read with umx_hip_last_error(NULL); a failing frame is named in it ("frame 12: ..."). */
+#define UMX_SAMPLE_FLAC 4
+typedef struct umx_flac_in
+{
+    const void *bytes;
+    size_t n_bytes;
+} umx_flac_in;
+typedef struct umx_flac_info
+{
+    long long n_frames;
+    int rate, bits, channels, max_block;
+    long long audio_offset;
+} umx_flac_info;
+int umx_hip_flac_probe_host(const void *bytes, size_t n_bytes, umx_flac_info *info);
+int umx_hip_flac_decode_host(const void *bytes, size_t n_bytes, float *x, long long n_frames);
+int umx_hip_flac_decode_device(umx_hip_ctx *ctx, const void *bytes_dev, size_t n_bytes, const umx_flac_info *info, float *out_dev,
+                               unsigned *status_dev, void *hip_stream);
 /* testing, host only: the fp32 tap table of a rate pair (taps[phase * K + d + D]; cap floats at most), its phase count L, taps
  * per phase K and first offset -D.  UMX_ERR_ARG for a bad rate or a too small cap (the sizes are still reported). */
 int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase,

@@ -358,6 +358,10 @@ def hip_lib():
                                                C.c_void_p]
     lib.umx_hip_flac_encode_host_lpc.argtypes = lib.umx_hip_flac_encode_host.argtypes + [C.c_int]
     lib.umx_hip_flac_encode_device_lpc.argtypes = lib.umx_hip_flac_encode_device.argtypes + [C.c_int]
+    # FLAC in
+    lib.umx_hip_flac_probe_host.argtypes = [_u8p, C.c_size_t, C.POINTER(FlacInfo)]
+    lib.umx_hip_flac_decode_host.argtypes = [_u8p, C.c_size_t, _fp, C.c_longlong]
+    lib.umx_hip_flac_decode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(FlacInfo), C.c_void_p, C.c_void_p, C.c_void_p]
 
     def queue_args(done_fn):
         return [C.c_void_p, QUEUE_NEXT_FN, done_fn, C.c_void_p, C.c_int, _fp, C.c_uint]
@@ -416,7 +420,8 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_separate_tracks_true_peak", "umx_hip_separate_queue_true_peak", "umx_hip_true_peak_device",
                "umx_hip_true_peak_taps", "umx_hip_true_peak_host",
                "umx_hip_flac_bound", "umx_hip_flac_encode_device", "umx_hip_flac_encode_host", "umx_hip_separate_tracks_flac",
-               "umx_hip_flac_encode_device_lpc", "umx_hip_flac_encode_host_lpc", "umx_hip_separate_tracks_flac_lpc"]
+               "umx_hip_flac_encode_device_lpc", "umx_hip_flac_encode_host_lpc", "umx_hip_separate_tracks_flac_lpc",
+               "umx_hip_flac_probe_host", "umx_hip_flac_decode_host", "umx_hip_flac_decode_device"]
 
 
 def sample_io(in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None):
@@ -594,6 +599,43 @@ def flac_encode_host(x, rate, bits, buffer=0, dither_seed=None, cap=None, lpc=0)
     return out[:got.value].copy()
 
 
+# --- FLAC in ---
+SAMPLE_FLAC = 4  # UMX_SAMPLE_FLAC: an input format only; the "audio" of a track is a FlacIn record of a .flac file's bytes
+
+
+class FlacIn(C.Structure):
+    """umx_flac_in"""
+    _fields_ = [("bytes", C.c_void_p), ("n_bytes", C.c_size_t)]
+
+
+class FlacInfo(C.Structure):
+    """umx_flac_info"""
+    _fields_ = [("n_frames", C.c_longlong), ("rate", C.c_int), ("bits", C.c_int), ("channels", C.c_int), ("max_block", C.c_int),
+                ("audio_offset", C.c_longlong)]
+
+
+def flac_probe(data):
+    """umx_hip_flac_probe_host: the bytes of a .flac file (uint8 array or bytes) -> FlacInfo; UmxError with the reason (no GPU)."""
+    b = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.asarray(data, np.uint8))
+    info = FlacInfo()
+    rc = hip_lib().umx_hip_flac_probe_host(b.ctypes.data_as(_u8p), b.size, C.byref(info))
+    if rc != UMX_OK:
+        raise UmxError(rc, hip_lib().umx_hip_last_error(None).decode())
+    return info
+
+
+def flac_decode_host(data, n_frames=None):
+    """umx_hip_flac_decode_host: the bytes of a .flac file -> (2,n) float32, the floats pcm16_decode_host / pcm24_decode_host give for
+    the stream's codes (no GPU).  n_frames: what the caller believes the total is (None: the probe's); UmxError names a failing frame."""
+    b = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.asarray(data, np.uint8))
+    n = flac_probe(b).n_frames if n_frames is None else int(n_frames)
+    x = np.zeros((max(n, 1), 2), np.float32)
+    rc = hip_lib().umx_hip_flac_decode_host(b.ctypes.data_as(_u8p), b.size, x.ctypes.data_as(_fp), n)
+    if rc != UMX_OK:
+        raise UmxError(rc, hip_lib().umx_hip_last_error(None).decode())
+    return np.ascontiguousarray(x[:n].T)
+
+
 def true_peak_float(bits):
     """The float32 whose bit pattern a true-peak word holds."""
     return np.array([bits], np.uint32).view(np.float32)[0]
@@ -662,11 +704,16 @@ class _TrackArgs:
         self.fout = SAMPLE_F32 if io is None else io.out_format
         tin = np.int16 if fin == SAMPLE_S16 else np.float32
         tout = np.int16 if self.fout == SAMPLE_S16 else np.float32
-        if fin == SAMPLE_S24:
+        if fin == SAMPLE_FLAC:  # uint8 arrays, the bytes of .flac files; the call gets a record of each
+            self.ins = [np.ascontiguousarray(np.asarray(w, np.uint8)).ravel() for w in waves]
+            self.recs = [FlacIn(x.ctypes.data, x.size) for x in self.ins]
+            self.Ls = [flac_probe(x).n_frames for x in self.ins]
+        elif fin == SAMPLE_S24:
             self.ins = [pcm24_pack(w) for w in waves]
         else:
             self.ins = [np.ascontiguousarray(np.asarray(w, tin).T).ravel() for w in waves]
-        self.Ls = [np.asarray(w).shape[1] for w in waves]
+        if fin != SAMPLE_FLAC:
+            self.Ls = [np.asarray(w).shape[1] for w in waves]
         self.n_host = min(max(n_out, 0), MAX_MIX_OUTPUTS)
         if out_bytes is not None:  # FLAC: every output a byte buffer of out_bytes(L) bytes, handed back as it is
             self.outs = [[np.zeros(max(1, out_bytes(L)), np.uint8) for _ in range(self.n_host)] for L in self.Ls]
@@ -674,7 +721,8 @@ class _TrackArgs:
             self.outs = [[np.empty(6 * L, np.uint8) for _ in range(self.n_host)] for L in self.Ls]
         else:
             self.outs = [[np.empty(2 * L, tout) for _ in range(self.n_host)] for L in self.Ls]
-        self.a = (ptr * nt)(*[C.cast(x.ctypes.data, ptr) for x in self.ins])
+        self.a = (ptr * nt)(*[C.cast(C.addressof(r) if fin == SAMPLE_FLAC else r.ctypes.data, ptr)
+                              for r in (self.recs if fin == SAMPLE_FLAC else self.ins)])
         self.o = (ptr * max(1, nt * self.n_host))(*[C.cast(x.ctypes.data, ptr) for t in self.outs for x in t])
         self.n = (C.c_int * nt)(*self.Ls)
         self.shifts = [(-1 if s is None else int(s)) for s in (shift_offsets or [None] * nt)]
@@ -1112,6 +1160,13 @@ class Engine:
         # lpc: umx_hip_flac_encode_device_lpc; None: the entry point without the argument
         self._check(self.lib.umx_hip_flac_encode_device(*args) if lpc is None else self.lib.umx_hip_flac_encode_device_lpc(*args, int(lpc)))
 
+    def flac_decode_device(self, bytes_ptr, n_bytes, info, out_ptr, status_ptr, hip_stream=None):
+        """umx_hip_flac_decode_device: the n_bytes of a .flac file at device address bytes_ptr (any alignment), info = flac_probe() of
+        them -> (2, info.n_frames) interleaved fp32 at out_ptr and the 32-bit status word at status_ptr (0: valid, else 1 + the first
+        frame that is missing, ambiguous or failed; nothing of out_ptr is written then).  Queued on hip_stream."""
+        self._check(self.lib.umx_hip_flac_decode_device(self.h, C.c_void_p(bytes_ptr), int(n_bytes), C.byref(info), C.c_void_p(out_ptr),
+                                                        C.c_void_p(status_ptr), hip_stream))
+
     def true_peak_device(self, in_ptrs, n, rate, bits_ptr, first_frame=0, n_frames=None, hip_stream=None):
         """umx_hip_true_peak_device: frames [first_frame, first_frame + n_frames) of 1 .. 4 device buffers (2,n) interleaved fp32 into the
         four words at device address bits_ptr (unsigned maxima of bit patterns; the caller zeroes them)."""
@@ -1192,6 +1247,8 @@ class Engine:
         refused HERE, in Python, with ERR_ARG, before the library is called -- the parameter exists only to say so."""
         if flac_bits:  # DESIGN 29: a FLAC track leaves whole; the queue's C entry points have no such argument
             raise UmxError(ERR_ARG, "queue: the track queue does not offer FLAC (separate_many_flac)")
+        if io is not None and io.in_format == SAMPLE_FLAC:  # DESIGN 31: a FLAC track goes up whole; the whole-track calls take it
+            raise UmxError(ERR_ARG, "queue: the track queue does not take SAMPLE_FLAC (separate_many_io and the rungs above it)")
         nj = len(waves)
         n_out, g = (4, None) if mix is None else _mix_gains(mix)
         m = _TrackArgs(waves, io, n_out, shift_offsets)

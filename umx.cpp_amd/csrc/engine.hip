@@ -48,6 +48,7 @@
 #include "loudness.h"
 #include "true_peak.h"
 #include "flac.h"
+#include "flac_decode.h"
 #include "gate_debug.h"
 
 using namespace umx;
@@ -659,8 +660,17 @@ struct umx_hip_ctx
         uint8_t *flac_out[4] = {};
         size_t cap_flac_out[4] = {};
         unsigned long long *flac_bytes = nullptr;
+        // DESIGN 31, only once a job asks for UMX_SAMPLE_FLAC: the file's bytes as uploaded (grow-only) and the decode's status word
+        uint8_t *flac_in = nullptr;
+        size_t cap_flac_in = 0;
+        unsigned *flac_in_status = nullptr;
     };
     std::vector<TrackBufs> trk;
+    // the scratch of a FLAC decode (candidates, per-frame words, the samples as coded), grow-only, one for the context:
+    // the decodes of a call are queued behind each other on one stream
+    unsigned *flac_in_scratch = nullptr;
+    size_t cap_flac_in_scratch = 0; // words
+    int flac_in_scratch_grow(const umx_flac_info &info);
     // the scratch of the FLAC launches, grow-only, one for the context (every job's launches are ordered behind each other:
     // trk_acc_ev chains the calls): the frames in their worst-case slots, their sizes and their byte offsets
     uint8_t *flac_slots = nullptr;

@@ -659,6 +659,11 @@ static int queue_entry(umx_hip_ctx *ctx, umx_queue_next_fn next, const umx_hip_c
     umx_hip_ctx::TrackOptions opt;
     if (!track_options_checked(ctx, io, ma, n_out, gains, spec, opt))
         return UMX_ERR_ARG;
+    if (opt.io.in_format == UMX_SAMPLE_FLAC) // a FLAC track goes up whole, in front of its first segment
+    {
+        ctx->set_error("queue: the track queue does not take UMX_SAMPLE_FLAC (the whole-track calls do)");
+        return UMX_ERR_ARG;
+    }
     opt.levels = done.measures();
     opt.loudness = done.loudness();
     opt.true_peak_record = done.with_true_peak != nullptr;
@@ -864,6 +869,60 @@ int umx_hip_separate_tracks_flac_lpc(umx_hip_ctx *ctx, int n_tracks, const void 
     }
     return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, ma, progress, progress_user);
 }
+// ---------------------------------------------------------------- FLAC in (flac_decode.h)
+// (no context: the reasons of the two host calls go where umx_hip_last_error(NULL) reads)
+int umx_hip_flac_probe_host(const void *bytes, size_t n_bytes, umx_flac_info *info)
+{
+    if (!bytes || !info)
+    {
+        g_create_error = "flac probe: need the bytes and an info record";
+        return UMX_ERR_ARG;
+    }
+    *info = umx_flac_info{};
+    if (int why = flac_probe(static_cast<const uint8_t *>(bytes), n_bytes, *info))
+    {
+        g_create_error = std::string("flac probe: ") + flac_reason(why);
+        return UMX_ERR_ARG;
+    }
+    return UMX_OK;
+}
+int umx_hip_flac_decode_host(const void *bytes, size_t n_bytes, float *x, long long n_frames)
+{
+    umx_flac_info info;
+    if (int rc = umx_hip_flac_probe_host(bytes, n_bytes, &info))
+        return rc;
+    if (!x || n_frames != info.n_frames)
+    {
+        g_create_error = "flac decode: need x, and n_frames equal to the stream's total sample count (" + std::to_string(info.n_frames) + ")";
+        return UMX_ERR_ARG;
+    }
+    long long frame = 0;
+    if (int why = flac_decode_host(static_cast<const uint8_t *>(bytes), n_bytes, info, x, &frame))
+    {
+        g_create_error = "flac decode: frame " + std::to_string(frame) + ": " + flac_reason(why);
+        return UMX_ERR_ARG;
+    }
+    return UMX_OK;
+}
+int umx_hip_flac_decode_device(umx_hip_ctx *ctx, const void *bytes_dev, size_t n_bytes, const umx_flac_info *info, float *out_dev,
+                               unsigned *status_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    if (!bytes_dev || !info || !out_dev || !status_dev || !flac_info_ok(*info, n_bytes))
+    {
+        ctx->set_error("flac decode: need the bytes, an info record as umx_hip_flac_probe_host fills it, out_dev and status_dev");
+        return UMX_ERR_ARG;
+    }
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    if (int rc = ctx->flac_in_scratch_grow(*info))
+        return rc;
+    launch_flac_decode(static_cast<const uint8_t *>(bytes_dev), n_bytes, *info, ctx->flac_in_scratch, reinterpret_cast<float2 *>(out_dev), status_dev,
+                       (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+
 size_t umx_hip_flac_bound(long long n_frames, int bits) { return flac_bits_ok(bits) && n_frames >= 0 ? flac_bound(n_frames, bits) : 0; }
 int umx_hip_flac_encode_host(const float *x, long long n, int rate, int bits, int buffer, const umx_sample_io *io, void *out, size_t cap,
                              size_t *bytes)

@@ -85,7 +85,7 @@ int umx_hip_ctx::track_bufs_grow(TrackBufs &tb_, size_t frames)
 int umx_hip_ctx::track_int_grow(TrackBufs &tb_, const umx_sample_io &io, size_t frames, int n_host)
 {
     auto words = [&](int format) { return (sample_frame_bytes(format) * frames + 3) / 4; };
-    if (io.in_format != UMX_SAMPLE_F32)
+    if (io.in_format != UMX_SAMPLE_F32 && io.in_format != UMX_SAMPLE_FLAC) // (a FLAC job's bytes: tracks_once)
         if (int rc = grow_only<uint32_t>({{&tb_.in_int, 1}}, tb_.cap_in_int, words(io.in_format)))
             return rc;
     for (int t = 0; t < n_host && io.out_format != UMX_SAMPLE_F32; ++t)
@@ -105,6 +105,11 @@ int umx_hip_ctx::track_flac_grow(TrackBufs &tb_, int bits, size_t frames, int n_
         if (int rc = dalloc(&tb_.flac_bytes, 4, true))
             return rc;
     return flac_scratch_grow(n_host, (long long)frames, bits);
+}
+// the context's scratch of a FLAC decode, for a stream of that many frames and that block size
+int umx_hip_ctx::flac_in_scratch_grow(const umx_flac_info &info)
+{
+    return grow_only<unsigned>({{&flac_in_scratch, 1}}, cap_flac_in_scratch, flac_in_scratch_words(info.n_frames, info.max_block));
 }
 int umx_hip_ctx::flac_scratch_grow(int nb, long long n, int bps)
 {
@@ -609,6 +614,27 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
             set_error("track: need audio, outputs, length >= 1 and shift offset < 22050");
             return UMX_ERR_ARG;
         }
+    // a FLAC input is a record of a file's bytes; its head is read here, and its length and rate must be the caller's
+    const bool flac_in = opt.io.in_format == UMX_SAMPLE_FLAC;
+    umx_flac_info flac_info[LSTMB_MAX_TRACKS] = {};
+    for (int ln = 0; ln < nt && flac_in; ++ln)
+    {
+        const umx_flac_in *rec = reinterpret_cast<const umx_flac_in *>(rq.audio[ln]);
+        std::string why;
+        if (!rec->bytes || rec->n_bytes > 0x7fffffffu) // (the shift ensemble has no sample io argument: the format cannot reach it)
+            why = "need the file's bytes (fewer than 2 GiB)";
+        else if (int r = flac_probe(static_cast<const uint8_t *>(rec->bytes), rec->n_bytes, flac_info[ln]))
+            why = flac_reason(r);
+        else if (flac_info[ln].n_frames != length_in[ln])
+            why = "length disagrees with the stream's total sample count (" + std::to_string(flac_info[ln].n_frames) + ")";
+        else if (flac_info[ln].rate != (rq.rate ? rq.rate[ln] : RS_MODEL_RATE))
+            why = "rate disagrees with the stream's sample rate (" + std::to_string(flac_info[ln].rate) + ")";
+        if (!why.empty())
+        {
+            set_error("flac in: track " + std::to_string(ln) + ": " + why);
+            return UMX_ERR_ARG;
+        }
+    }
     for (int ln = 0; ln < nt && opt.flac_bits; ++ln)
         for (int t = 0; t < n_host; ++t)
             if (!rq.out_cap || !rq.out_bytes || rq.out_cap[n_host * ln + t] < flac_bound(length_in[ln], opt.flac_bits))
@@ -706,7 +732,36 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         for (int ln = 1; ln < nt; ++ln)
             UMX_HIP_CHECK(hipMemcpy(trk[ln].in + 2 * (size_t)job[ln].lead, first, bytes, hipMemcpyDeviceToDevice));
     }
+    // a FLAC job's bytes go up whole, in front of its first segment (which bytes a segment needs is not known before the
+    // stream is indexed), and the decode is queued behind them on the same stream, into the buffer the other formats decode into
+    for (int ln = 0; ln < nt && flac_in; ++ln)
+    {
+        TrackBufs &tb_ = trk[ln];
+        const umx_flac_in *rec = reinterpret_cast<const umx_flac_in *>(rq.audio[ln]);
+        if (int rc = grow_only<uint8_t>({{&tb_.flac_in, 1}}, tb_.cap_flac_in, rec->n_bytes))
+            return rc;
+        if (!tb_.flac_in_status)
+            if (int rc = dalloc(&tb_.flac_in_status, 1, true))
+                return rc;
+        if (int rc = flac_in_scratch_grow(flac_info[ln]))
+            return rc;
+        UMX_HIP_CHECK(hipMemcpy(tb_.flac_in, rec->bytes, rec->n_bytes, hipMemcpyHostToDevice));
+        float *const dst = job[ln].rs.rate ? tb_.rs.in : tb_.in + 2 * (size_t)job[ln].lead;
+        launch_flac_decode(tb_.flac_in, rec->n_bytes, flac_info[ln], flac_in_scratch, reinterpret_cast<float2 *>(dst), tb_.flac_in_status, nullptr);
+    }
     UMX_HIP_CHECK(hipDeviceSynchronize());
+    for (int ln = 0; ln < nt && flac_in; ++ln) // the status words, behind the synchronisation the call has anyway
+    {
+        unsigned status = 0;
+        UMX_HIP_CHECK(hipMemcpy(&status, trk[ln].flac_in_status, sizeof status, hipMemcpyDeviceToHost));
+        if (status)
+        {
+            set_error("flac in: track " + std::to_string(ln) + ": frame " + std::to_string(status - 1) +
+                      " is missing, ambiguous or fails its CRC (or the stream holds more frame syncs than frames allow)");
+            return UMX_ERR_ARG;
+        }
+        job[ln].uploaded = length_in[ln];
+    }
     for (int ln = 0; ln < nt && ensemble; ++ln) // (on the device whole already)
         if (!job[ln].rs.rate)
             job[ln].uploaded = length[ln];

@@ -115,7 +115,9 @@ inline const char *sample_io_refusal(const umx_sample_io *io)
 {
     if (!io)
         return nullptr;
-    if (!sample_format_known(io->in_format) || !sample_format_known(io->out_format))
+    if (io->out_format == UMX_SAMPLE_FLAC)
+        return "sample io: UMX_SAMPLE_FLAC is an input format (FLAC out is flac_bits)";
+    if ((!sample_format_known(io->in_format) && io->in_format != UMX_SAMPLE_FLAC) || !sample_format_known(io->out_format))
         return "sample io: unknown sample format (UMX_SAMPLE_F32, UMX_SAMPLE_S16 or UMX_SAMPLE_S24)";
     if (io->dither && io->out_format == UMX_SAMPLE_F32)
         return "sample io: dither goes with a UMX_SAMPLE_S16 or UMX_SAMPLE_S24 output only";

@@ -192,6 +192,22 @@ int main(int argc, const char **argv)
         fprintf(stderr, "UMX_FLAC: umx-batch runs the track queue, which does not offer FLAC (umx-cli does)\n");
         return 1;
     }
+    for (int f = 0; f < nfiles; ++f) // a FLAC track goes up whole in front of its first segment; the track queue does not take it
+    {
+        unsigned char head[4] = {};
+        FILE *fp = fopen(argv[3 + f], "rb");
+        const bool marker = fp && fread(head, 1, 4, fp) == 4 && head[0] == 'f' && head[1] == 'L' && head[2] == 'a' && head[3] == 'C';
+        if (fp)
+            fclose(fp);
+        std::string ext = std::filesystem::path(argv[3 + f]).extension().string();
+        for (char &c : ext)
+            c = (char)tolower((unsigned char)c);
+        if (marker || ext == ".flac")
+        {
+            fprintf(stderr, "%s: a FLAC input: umx-batch runs the track queue, which does not take FLAC in (umx-cli does)\n", argv[3 + f]);
+            return 1;
+        }
+    }
     umx_clip_choice clipc;
     if (!umx_clip_from_env(clipc, nullptr))
         return 1;

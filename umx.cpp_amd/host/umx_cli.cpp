@@ -30,6 +30,10 @@
 //   UMX_FLAC_LPC=<0..12>  with UMX_FLAC: LPC subframes of up to that order are candidates in every full block
 //                    (umx_hip_separate_tracks_flac_lpc): smaller files of the same codes, never larger ones.  Refused without
 //                    UMX_FLAC.  Unset or 0: the FIXED-only streams
+//   a .flac input    FLAC in (UMX_SAMPLE_FLAC): an input file that is a FLAC stream by its content (2 channels, 16 or 24 bits)
+//                    goes up as its bytes and is decoded on the device to what the int16 / 24-bit upload of its codes gives; every
+//                    output switch works as with a WAV input; another rate needs UMX_RESAMPLE=1; not with UMX_SHIFTS > 1 or
+//                    UMX_CLI_PER_SEGMENT=1
 //   UMX_PCM24=1      packed 24-bit PCM across PCIe (UMX_SAMPLE_S24): the outputs are written as 24-bit PCM WAVs under the same
 //                    names, quantised on the device; a 24-bit PCM input goes up packed, a 16-bit one as int16, any other encoding as
 //                    fp32; UMX_PCM24_DITHER=<seed> adds TPDF dither with that seed.  Goes where UMX_PCM16 goes, not together with it.
@@ -78,6 +82,31 @@ int env_int(const char *name, int dflt)
 {
     const char *v = getenv(name);
     return v && *v ? atoi(v) : dflt;
+}
+// Is the file a FLAC stream by its content: "fLaC" at its start, or behind an ID3v2 tag?  Then `bytes` holds the whole file.
+bool is_flac_file(const char *path, std::vector<unsigned char> &bytes)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f)
+        return false;
+    unsigned char head[10] = {};
+    const size_t got = fread(head, 1, sizeof head, f);
+    size_t marker = 0;
+    if (got == sizeof head && head[0] == 'I' && head[1] == 'D' && head[2] == '3')
+        marker = 10 + (((size_t)(head[6] & 127) << 21) | ((size_t)(head[7] & 127) << 14) | ((size_t)(head[8] & 127) << 7) | (size_t)(head[9] & 127)) +
+                 ((head[5] & 0x10) ? 10 : 0);
+    unsigned char m[4] = {};
+    const bool flac = fseek(f, (long)marker, SEEK_SET) == 0 && fread(m, 1, 4, f) == 4 && m[0] == 'f' && m[1] == 'L' && m[2] == 'a' && m[3] == 'C';
+    if (flac && fseek(f, 0, SEEK_END) == 0)
+    {
+        const long size = ftell(f);
+        bytes.resize(size > 0 ? (size_t)size : 0);
+        rewind(f);
+        if (fread(bytes.data(), 1, bytes.size(), f) != bytes.size())
+            bytes.clear();
+    }
+    fclose(f);
+    return flac && !bytes.empty();
 }
 } // namespace
 
@@ -158,7 +187,35 @@ int main(int argc, const char **argv)
     int16_t *audio_int = nullptr; // the file's samples as they are, in io.in_format (load_int)
     int n = 0, ch = 0, rate = UMX_SAMPLE_RATE;
     const bool resample = env_int("UMX_RESAMPLE", 0) != 0;
-    if (pcmc.pcm24 && load_int(UMX_SAMPLE_S24, wav_file.c_str(), &audio_int, &n, &ch, resample ? &rate : nullptr, err) == UMX_OK)
+    // FLAC in: a file that IS a FLAC stream, by its content ("fLaC", or an ID3v2 tag in front of one; the probe decides),
+    // goes up as its bytes and is decoded on the device, with whatever output switches are set
+    std::vector<unsigned char> flac_file;
+    umx_flac_in flac_rec = {};
+    if (is_flac_file(wav_file.c_str(), flac_file))
+    {
+        umx_flac_info info;
+        const char *why = nullptr;
+        if (umx_hip_flac_probe_host(flac_file.data(), flac_file.size(), &info))
+            why = umx_hip_last_error(nullptr);
+        else if (shifts > 1 || env_int("UMX_CLI_PER_SEGMENT", 0))
+            why = "flac in: the shift ensemble (UMX_SHIFTS > 1) and UMX_CLI_PER_SEGMENT=1 do not take a .flac input";
+        else if (info.rate != UMX_SAMPLE_RATE && !resample)
+            why = "flac in: the stream is not at 44100 Hz: set UMX_RESAMPLE=1 to resample on the device";
+        else if (info.n_frames > 0x7fffffff / 2)
+            why = "flac in: track too long";
+        if (why)
+        {
+            fprintf(stderr, "%s: %s\n", wav_file.c_str(), why);
+            return 1;
+        }
+        n = (int)info.n_frames;
+        ch = info.channels;
+        rate = info.rate;
+        flac_rec.bytes = flac_file.data();
+        flac_rec.n_bytes = flac_file.size();
+        io.in_format = UMX_SAMPLE_FLAC;
+    }
+    else if (pcmc.pcm24 && load_int(UMX_SAMPLE_S24, wav_file.c_str(), &audio_int, &n, &ch, resample ? &rate : nullptr, err) == UMX_OK)
         io.in_format = UMX_SAMPLE_S24;
     else if (pcmc.active() && load_int(UMX_SAMPLE_S16, wav_file.c_str(), &audio_int, &n, &ch, resample ? &rate : nullptr, err) == UMX_OK)
         io.in_format = UMX_SAMPLE_S16; // (any other encoding, and every other failure, is the float loader's to take or to report)
@@ -253,7 +310,7 @@ int main(int argc, const char **argv)
         // umx.cpp:72-73.  One call for every run: what a run does not ask for at its neutral value (NULL rate, gains, records, fp32
         // formats, clamp) is the narrower entry point's request (include/umx_hip.h)
         const int offset = env_int("UMX_SHIFT_OFFSET", -1) < 0 ? UMX_REFERENCE_SHIFT : env_int("UMX_SHIFT_OFFSET", -1);
-        const void *in = audio_int ? (const void *)audio_int : (const void *)audio;
+        const void *in = flac_rec.bytes ? (const void *)&flac_rec : audio_int ? (const void *)audio_int : (const void *)audio;
         void *out_io[4]; // (read as the formats say)
         for (int t = 0; t < 4; ++t)
             out_io[t] = flac_bits ? (void *)stems_flac[t].data() : pcmc.active() ? (void *)stems_int[t].data() : (void *)stems[t].data();
