@@ -446,6 +446,26 @@ int umx_hip_debug_queue_calls(umx_hip_ctx *ctx);
  *                a = h(seed + 0x9e3779b9 * (2 m + ch + 1)),  w = h(a ^ (uint32) k),
  *                d = (((float)(w & 0xffff) + (float)(w >> 16)) - 65535.0f) * (1.0f / 65536.0f), in (-1, 1), every step exact.
  * encode(decode(q)) == q for every code without dither, within 1 LSB with it.
+ *   shaped   dither == UMX_DITHER_SHAPED: noise-shaped dither, the usual way to make a 44.1 kHz / 16-bit deliverable.  The
+ *            quantisation error is fed back through five taps so that its power leaves the 2 - 6 kHz band for the top octave.  Defined
+ *            per output buffer m, channel ch and BLOCK j of 4096 frames anchored at frame 0 of the caller's track at the caller's rate
+ *            (the anchor of UMX_FLAC_BLOCK and of k).  At the first frame of every block e1 = ... = e5 = 0.  For frame k = 4096 j + n,
+ *            in fp32, one rounding per line, no fused multiply-add:
+ *                v  = pre(x) * 32767.0f                              pre: the rescale divisor, as above
+ *                s  = ((((c1*e1 + c2*e2) + c3*e3) + c4*e4) + c5*e5)  c = 2.033f, -2.165f, 1.959f, -1.590f, 0.6149f
+ *                y  = v - s
+ *                r  = rintf(y + d(seed, m, ch, k))                   the d of the TPDF rule, same keys
+ *                e  = r - y;  if e is not finite: e = 0              the error BEFORE the clamp; NaN / inf do not outlive their sample
+ *                q  = r is NaN ? 0 : (int16) min(max(r, -32768.f), 32767.f);   clipped counts r outside that range
+ *                e5..e2 = e4..e1; e1 = e
+ *            c: Lipshitz-Vanderkooy-Wannamaker, five taps, E-weighted, 44.1 kHz; the noise transfer function is 1 - sum c_i z^-i.
+ *            A frame's code depends on the samples of its own block alone, from the block's start: regions, lanes, reset mode, the
+ *            queue and a rerun give the same bits; the price is at most five frames of unshaped error every 93 ms.
+ *            UMX_SAMPLE_S16 outputs of tracks at 44100 or 48000 Hz only.  Refused with UMX_ERR_ARG and a reason, the context staying
+ *            usable: UMX_SAMPLE_S24 and fp32 outputs, flac_bits != 0 and the FLAC encoders, the levels launches (the stateless clip
+ *            count cannot know y: the shaped encode counts what it clamps itself), any other rate, any other mode value, and the
+ *            two encode kernels' entry points below with first_frame % 4096 != 0 (they cannot promise that the frames in front of
+ *            their pointer are readable; umx_hip_pcm16_encode_host likewise).
  * The _io forms below are the calls they are named after with the formats of the host buffers chosen per call; io == NULL, or
  * UMX_SAMPLE_F32 both ways, IS that call: the same launches, nothing allocated.  UMX_SAMPLE_S16 in: audio[i] points at length[i]
  * interleaved int16 stereo frames; out: every output buffer receives exactly length[i] such frames.  On the device a format costs 4 B
@@ -456,10 +476,13 @@ int umx_hip_debug_queue_calls(umx_hip_ctx *ctx);
  * per-segment infer calls do not offer the formats. */
 #define UMX_SAMPLE_F32 0
 #define UMX_SAMPLE_S16 1
+#define UMX_DITHER_TPDF 1
+#define UMX_DITHER_SHAPED 2
 typedef struct umx_sample_io
 {
     int in_format, out_format; /* UMX_SAMPLE_* of the audio and of the output buffers */
-    int dither;                /* != 0: TPDF dither before the rounding (UMX_SAMPLE_S16 and UMX_SAMPLE_S24 outputs only) */
+    int dither;                /* 0: none; UMX_DITHER_TPDF: TPDF dither before the rounding (UMX_SAMPLE_S16 and UMX_SAMPLE_S24 outputs
+                                  only); UMX_DITHER_SHAPED: noise-shaped (UMX_SAMPLE_S16 outputs only); anything else is refused */
     unsigned dither_seed;
 } umx_sample_io;
 /* umx_hip_separate_tracks_mix (rate == NULL: 44100 for all; gains == NULL: umx_hip_separate_tracks_rate) with the formats */

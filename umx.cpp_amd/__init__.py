@@ -98,6 +98,7 @@ class SampleIO(C.Structure):
 
 
 SAMPLE_F32, SAMPLE_S16 = 0, 1  # UMX_SAMPLE_*: the formats of the host buffers of the whole-track calls
+DITHER_TPDF, DITHER_SHAPED = 1, 2  # UMX_DITHER_*: the modes of SampleIO.dither (0: none); shaped: noise-shaped, 16-bit outputs only
 SAMPLE_S24 = 3  # packed 24-bit PCM, 6 bytes per stereo frame; 2 stays an unknown format
 _i16p = C.POINTER(C.c_int16)
 _u8p = C.POINTER(C.c_uint8)
@@ -424,9 +425,11 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_flac_probe_host", "umx_hip_flac_decode_host", "umx_hip_flac_decode_device"]
 
 
-def sample_io(in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None):
-    """A umx_sample_io: dither_seed None = no dither, else TPDF dither with that seed."""
-    return SampleIO(int(in_format), int(out_format), 0 if dither_seed is None else 1, 0 if dither_seed is None else int(dither_seed) & 0xFFFFFFFF)
+def sample_io(in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None, shaped=False):
+    """A umx_sample_io: dither_seed None = no dither, else TPDF dither with that seed; shaped: noise-shaped dither with that seed
+    (DITHER_SHAPED; seed 0 when dither_seed is None)."""
+    mode = DITHER_SHAPED if shaped else 0 if dither_seed is None else DITHER_TPDF
+    return SampleIO(int(in_format), int(out_format), mode, 0 if dither_seed is None else int(dither_seed) & 0xFFFFFFFF)
 
 
 def pcm16_decode_host(q):
@@ -439,22 +442,22 @@ def pcm16_decode_host(q):
     return x
 
 
-def _encode_host(fmt, x, buffer, first_frame, dither_seed):
+def _encode_host(fmt, x, buffer, first_frame, dither_seed, shaped=False):
     """umx_hip_pcm<fmt>_encode_host (fmt: 16 or 24) of a (2,n) float32 x -> the n frames as the format holds them: (n,2) int16, or 6 n bytes."""
     a = np.ascontiguousarray(np.asarray(x, np.float32).T)
     q, qp, out_format = {16: (np.empty(a.shape, np.int16), _i16p, SAMPLE_S16), 24: (np.empty(6 * a.shape[0], np.uint8), _u8p, SAMPLE_S24)}[fmt]
-    io = sample_io(SAMPLE_F32, out_format, dither_seed)
+    io = sample_io(SAMPLE_F32, out_format, dither_seed, shaped)
     name = f"umx_hip_pcm{fmt}_encode_host"
     rc = getattr(hip_lib(), name)(a.ctypes.data_as(_fp), a.shape[0], int(buffer), int(first_frame), C.byref(io), q.ctypes.data_as(qp))
     if rc != UMX_OK:
-        raise UmxError(rc, name)
+        raise UmxError(rc, name + ": " + hip_lib().umx_hip_last_error(None).decode())
     return q
 
 
-def pcm16_encode_host(x, buffer=0, first_frame=0, dither_seed=None):
+def pcm16_encode_host(x, buffer=0, first_frame=0, dither_seed=None, shaped=False):
     """umx_hip_pcm16_encode_host: (2,n) float32 -> (2,n) int16 as output buffer `buffer` of a call, frame 0 of x being frame
-    first_frame of the track (no GPU)."""
-    return np.ascontiguousarray(_encode_host(16, x, buffer, first_frame, dither_seed).T)
+    first_frame of the track (no GPU).  shaped: noise-shaped dither; first_frame must then be a multiple of 4096."""
+    return np.ascontiguousarray(_encode_host(16, x, buffer, first_frame, dither_seed, shaped).T)
 
 
 def pcm24_pack(q):
@@ -1097,11 +1100,12 @@ class Engine:
 
     # --- 16-bit PCM in and out: int16 frames across PCIe, converted on the device ---
     def separate_many_io(self, waves, in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None, flags=0, shift_offsets=None,
-                         rates=None, gains=None, io=None):
+                         rates=None, gains=None, io=None, shaped=False):
         """umx_hip_separate_tracks_io: separate_many() / separate_many_mix() (gains) with the formats of the host buffers chosen:
         SAMPLE_S16 in takes (2,L_i) int16 arrays, SAMPLE_S16 out returns int16 arrays, dithered with dither_seed unless it is None.
+        shaped: the dither is noise-shaped (SAMPLE_S16 out, tracks at 44.1 or 48 kHz).
         io: a SampleIO passed as it is instead (tests of the refusals)."""
-        io = sample_io(in_format, out_format, dither_seed) if io is None else io
+        io = sample_io(in_format, out_format, dither_seed, shaped) if io is None else io
         return self._separate_many_measured("umx_hip_separate_tracks_io", waves, io, flags, shift_offsets, rates, gains).m.result()
 
     def _separate_many_measured(self, entry_name, waves, io, flags, shift_offsets, rates, gains, **asked):
@@ -1188,11 +1192,11 @@ class Engine:
         self._check(self.lib.umx_hip_levels_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(first_frame),
                                                    None if io is None else C.byref(io), C.c_void_p(acc_ptr), hip_stream))
 
-    def _encode_device(self, fmt, in_ptrs, n, out_ptrs, first_frame, dither_seed, hip_stream, acc_ptr=None):
+    def _encode_device(self, fmt, in_ptrs, n, out_ptrs, first_frame, dither_seed, hip_stream, acc_ptr=None, shaped=False):
         """umx_hip_pcm<fmt>_encode_device, or with acc_ptr umx_hip_pcm<fmt>_encode_rescaled_device (fmt: 16 or 24)."""
         nb = len(in_ptrs)
         assert len(out_ptrs) == nb
-        io = sample_io(SAMPLE_F32, {16: SAMPLE_S16, 24: SAMPLE_S24}[fmt], dither_seed)
+        io = sample_io(SAMPLE_F32, {16: SAMPLE_S16, 24: SAMPLE_S24}[fmt], dither_seed, shaped)
         fn = getattr(self.lib, f"umx_hip_pcm{fmt}_encode_device" if acc_ptr is None else f"umx_hip_pcm{fmt}_encode_rescaled_device")
         tail = (hip_stream,) if acc_ptr is None else (C.c_void_p(acc_ptr), hip_stream)
         self._check(fn(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n), int(first_frame), C.byref(io), (C.c_void_p * max(1, nb))(*out_ptrs),
@@ -1202,9 +1206,9 @@ class Engine:
         """umx_hip_pcm<fmt>_decode_device (fmt: 16 or 24)."""
         self._check(getattr(self.lib, f"umx_hip_pcm{fmt}_decode_device")(self.h, C.c_void_p(in_ptr), int(n), C.c_void_p(out_ptr), hip_stream))
 
-    def pcm16_encode_rescaled_device(self, in_ptrs, n, out_ptrs, acc_ptr, first_frame=0, dither_seed=None, hip_stream=None):
+    def pcm16_encode_rescaled_device(self, in_ptrs, n, out_ptrs, acc_ptr, first_frame=0, dither_seed=None, hip_stream=None, shaped=False):
         """umx_hip_pcm16_encode_rescaled_device: pcm16_encode_device() on x / g, g formed on the device from the record at acc_ptr."""
-        self._encode_device(16, in_ptrs, n, out_ptrs, first_frame, dither_seed, hip_stream, acc_ptr)
+        self._encode_device(16, in_ptrs, n, out_ptrs, first_frame, dither_seed, hip_stream, acc_ptr, shaped)
 
     def pcm24_encode_rescaled_device(self, in_ptrs, n, out_ptrs, acc_ptr, first_frame=0, dither_seed=None, hip_stream=None):
         """umx_hip_pcm24_encode_rescaled_device: pcm24_encode_device() on x / g, g formed on the device from the record at acc_ptr."""
@@ -1229,17 +1233,19 @@ class Engine:
         """umx_hip_pcm16_decode_device: n int16 stereo frames at device address in_ptr -> (2,n) interleaved fp32 at out_ptr."""
         self._decode_device(16, in_ptr, n, out_ptr, hip_stream)
 
-    def pcm16_encode_device(self, in_ptrs, n, out_ptrs, first_frame=0, dither_seed=None, hip_stream=None):
-        """umx_hip_pcm16_encode_device: 1 .. 4 device buffers (2,n) interleaved fp32 -> n int16 stereo frames each, buffer b as output b."""
-        self._encode_device(16, in_ptrs, n, out_ptrs, first_frame, dither_seed, hip_stream)
+    def pcm16_encode_device(self, in_ptrs, n, out_ptrs, first_frame=0, dither_seed=None, hip_stream=None, shaped=False):
+        """umx_hip_pcm16_encode_device: 1 .. 4 device buffers (2,n) interleaved fp32 -> n int16 stereo frames each, buffer b as output b.
+        shaped: noise-shaped dither (first_frame a multiple of 4096)."""
+        self._encode_device(16, in_ptrs, n, out_ptrs, first_frame, dither_seed, hip_stream, shaped=shaped)
 
     # --- the track queue (DESIGN 18): more tracks than lanes, a lane refilled with the next track the moment one ends ---
     def separate_queue(self, waves, shift_offsets=None, flags=0, mix=None, io=None, clip=None, levels=False, loudness=False, rates=None,
-                       true_peak=None, flac_bits=0):
+                       true_peak=None, flac_bits=0, shaped=False):
         """umx_hip_separate_queue: list of (2,L_i) -> list of [4 x (2,L_i)] (mix: an (n_out, 5) gain matrix -> n_out x (2,L_i)), every
         job bit for bit what separate() / separate_mix() returns for it alone on this engine; the jobs are handed out in list order.
         rates: one sample rate per job (None: all 44.1 kHz), as separate_many() takes them.
         io: a SampleIO (sample_io()) -> umx_hip_separate_queue_io, int16 arrays in and / or out as it says.
+        shaped: io's dither is noise-shaped -- the same SampleIO with dither = DITHER_SHAPED.
         clip (CLIP_CLAMP / CLIP_RESCALE) or levels=True -> umx_hip_separate_queue_levels: returns (outputs, [Levels per job]).
         loudness=True -> umx_hip_separate_queue_loudness: returns (outputs, [Levels], [Loudness], [(n_out, 2, hops) float64]).
         true_peak (a TRUE_PEAK_* mode) -> umx_hip_separate_queue_true_peak: returns those four and [TruePeak per job].
@@ -1249,6 +1255,8 @@ class Engine:
             raise UmxError(ERR_ARG, "queue: the track queue does not offer FLAC (separate_many_flac)")
         if io is not None and io.in_format == SAMPLE_FLAC:  # a FLAC track goes up whole; the whole-track calls take it
             raise UmxError(ERR_ARG, "queue: the track queue does not take SAMPLE_FLAC (separate_many_io and the rungs above it)")
+        if shaped and io is not None:
+            io = SampleIO(io.in_format, io.out_format, DITHER_SHAPED, io.dither_seed)
         nj = len(waves)
         n_out, g = (4, None) if mix is None else _mix_gains(mix)
         m = _TrackArgs(waves, io, n_out, shift_offsets)

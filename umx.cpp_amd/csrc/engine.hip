@@ -45,6 +45,7 @@
 #include "pcm16.h"
 #include "pcm24.h"
 #include "levels.h"
+#include "pcm16_shaped.h"
 #include "loudness.h"
 #include "true_peak.h"
 #include "flac.h"

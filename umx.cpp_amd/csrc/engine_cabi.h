@@ -80,9 +80,23 @@ static int encode_device(umx_hip_ctx *ctx, const char *what, int format, int n_b
         ctx->set_error(std::string(what) + ": null record");
         return UMX_ERR_ARG;
     }
+    // the dither mode; a shaped encode starts at the first frame of a block (what lies in front of in_dev is not the caller's promise)
+    const char *why = dither_mode_refusal(io, format == UMX_SAMPLE_S16);
+    const bool shaped = !why && io && io->dither == UMX_DITHER_SHAPED;
+    if (shaped && first_frame % SHAPED_BLOCK != 0)
+        why = "sample io: a shaped encode starts at a block: first_frame must be a multiple of 4096";
+    if (why)
+    {
+        ctx->set_error(std::string(what) + ": " + why);
+        return UMX_ERR_ARG;
+    }
     UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
     const DitherArg d = dither_of(io);
-    launch_encode(format, n_buffers, src, dst, n, first_frame, d.on, d.seed, rescaled ? acc_dev : nullptr, (hipStream_t)hip_stream);
+    if (shaped)
+        launch_shaped_encode(n_buffers, src, dst, n, first_frame, d.seed, rescaled ? acc_dev : nullptr, rescaled ? levels_peak_words(acc_dev) : nullptr,
+                             (hipStream_t)hip_stream);
+    else
+        launch_encode(format, n_buffers, src, dst, n, first_frame, d.on, d.seed, rescaled ? acc_dev : nullptr, (hipStream_t)hip_stream);
     UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
     return UMX_OK;
 }
@@ -98,10 +112,37 @@ template <class T> static int decode_host(T t, const void *q, long long n_values
 }
 template <class T> static int encode_host(T t, const float *x, int n_frames, int buffer, long long first_frame, const umx_sample_io *io, void *q)
 {
+    // (no context: the reason of a refusal goes where umx_hip_last_error(NULL) reads)
     if (!x || !q || n_frames < 0 || buffer < 0 || buffer >= UMX_MAX_MIX_OUTPUTS || first_frame < 0)
+    {
+        g_create_error = "sample encode: need x, q, n_frames >= 0, buffer 0 .. 3 and first_frame >= 0";
         return UMX_ERR_ARG;
+    }
+    const char *why = dither_mode_refusal(io, T::format == UMX_SAMPLE_S16);
+    const bool shaped = !why && io && io->dither == UMX_DITHER_SHAPED;
+    if (shaped && first_frame % SHAPED_BLOCK != 0)
+        why = "sample io: a shaped encode starts at a block: first_frame must be a multiple of 4096";
+    if (why)
+    {
+        g_create_error = why;
+        return UMX_ERR_ARG;
+    }
     const DitherArg d = dither_of(io);
     const uint32_t key[2] = {sample_dither_key(d.seed, buffer, 0), sample_dither_key(d.seed, buffer, 1)};
+    if constexpr (T::format == UMX_SAMPLE_S16)
+        if (shaped) // the rule of sample_format.h, frame by frame, the history zero at every block's first frame
+        {
+            ShapedHistory h[2] = {};
+            for (int i = 0; i < n_frames; ++i)
+                for (int ch = 0; ch < 2; ++ch)
+                {
+                    if ((first_frame + i) % SHAPED_BLOCK == 0)
+                        h[ch] = ShapedHistory{};
+                    const float dd = sample_dither_value(sample_dither_word(key[ch], first_frame + i));
+                    store_sample(t, q, 2 * (size_t)i + ch, T::clamp(shaped_round(h[ch], x[2 * (size_t)i + ch] * 32767.0f, dd)));
+                }
+            return UMX_OK;
+        }
     for (int i = 0; i < n_frames; ++i)
         for (int ch = 0; ch < 2; ++ch)
             store_sample(t, q, 2 * (size_t)i + ch, T::clamp(T::round(x[2 * (size_t)i + ch], d.on, key[ch], first_frame + i)));
@@ -366,7 +407,9 @@ static const char *flac_refusal(int flac_bits, int flac_lpc, const umx_sample_io
         return nullptr;
     umx_sample_io as_pcm = *io;
     as_pcm.out_format = flac_bits == 16 ? UMX_SAMPLE_S16 : UMX_SAMPLE_S24;
-    return sample_io_refusal(&as_pcm);
+    if (const char *why = sample_io_refusal(&as_pcm))
+        return why;
+    return dither_mode_refusal(io, false); // shaped dither does not go into a FLAC stream
 }
 static const char *mix_refusal(int n_out, const float *gains, MixSpec &spec) // (NULL gains are refused: who takes "no mix" asks before)
 {
@@ -761,6 +804,11 @@ int umx_hip_levels_device(umx_hip_ctx *ctx, int n_buffers, const float *const *i
         ctx->set_error("levels: null record");
         return UMX_ERR_ARG;
     }
+    if (const char *why = dither_mode_refusal(io, false))
+    {
+        ctx->set_error(std::string("levels: ") + why);
+        return UMX_ERR_ARG;
+    }
     UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
     const DitherArg d = dither_of(io);
     launch_stem_levels(n_buffers, src, n, first_frame, clip_format_of(io), d.on, d.seed, acc_dev, (hipStream_t)hip_stream);
@@ -798,6 +846,11 @@ int umx_hip_levels_host(const float *x, int n_frames, int buffer, long long firs
 {
     if (!x || !acc || n_frames < 0 || buffer < 0 || buffer >= UMX_MAX_MIX_OUTPUTS || first_frame < 0)
         return UMX_ERR_ARG;
+    if (const char *why = dither_mode_refusal(io, false)) // DESIGN 32 (no context: the reason goes where umx_hip_last_error(NULL) reads)
+    {
+        g_create_error = std::string("levels: ") + why;
+        return UMX_ERR_ARG;
+    }
     const DitherArg d = dither_of(io);
     levels_host(x, n_frames, buffer, first_frame, clip_format_of(io), d.on, d.seed, clip_divisor, *acc);
     return UMX_OK;
@@ -935,7 +988,7 @@ int umx_hip_flac_encode_host_lpc(const float *x, long long n, int rate, int bits
     // (no context: the reason of a flac_lpc refusal goes where umx_hip_last_error(NULL) reads)
     if (const char *why = !flac_lpc_ok(flac_lpc)       ? "flac encode: flac_lpc must be 0 .. 12"
                           : flac_lpc != 0 && bits == 0 ? "flac encode: flac_lpc needs bits (16 or 24)"
-                                                       : nullptr)
+                                                       : dither_mode_refusal(io, false))
     {
         g_create_error = why;
         return UMX_ERR_ARG;
@@ -970,7 +1023,7 @@ int umx_hip_flac_encode_device_lpc(umx_hip_ctx *ctx, int n_buffers, const float 
                       : !flac_rate_ok(rate)                                                      ? "flac encode: sample rate outside 1 .. 655350 Hz"
                       : first_buffer < 0 || first_buffer + n_buffers > UMX_MAX_MIX_OUTPUTS       ? "flac encode: first_buffer + n_buffers must stay within 4 outputs"
                       : !cap || !bytes_dev                                                       ? "flac encode: need the capacities and the length words"
-                                                                                                 : nullptr;
+                                                                                                 : dither_mode_refusal(io, false);
     for (int b = 0; !why && b < n_buffers; ++b)
         if (cap[b] < flac_bound(n, bits))
             why = "flac encode: a capacity below umx_hip_flac_bound(n, bits)";

@@ -125,6 +125,10 @@ int umx_hip_ctx::flac_scratch_grow(int nb, long long n, int bps)
 // their frame number in the caller's track (the k of the dither), at byte frame_bytes x first_frame; the kernel is the output
 // format's (launch_encode).  acc: over the divisor of `words` (nullptr: of that record's peak words), counting what clamps into it
 // (acc nullptr: the plain encode).
+// Shaped dither: the span is encoded by the lanes of the blocks of 4096 frames it touches, each from its block's first
+// frame on -- the frames in front of first_frame are read where the loudness and true-peak launches read them, at their frame numbers
+// in `src` ("the spans before this one are still in src": track_leave), computed through and not stored.  So a span needs no state,
+// and any partition of a track gives the whole-track bits.  There acc counts what clamps, and `words` alone says whether a divisor applies.
 void umx_hip_ctx::track_encode(const TrackBufs &tb_, const umx_sample_io &io, int n_host, float *const src[4], size_t src_start, int count,
                                long long first_frame, umx_levels_acc *acc, hipStream_t st, const uint32_t *words)
 {
@@ -135,6 +139,8 @@ void umx_hip_ctx::track_encode(const TrackBufs &tb_, const umx_sample_io &io, in
         s[t] = reinterpret_cast<const float2 *>(src[t]) + src_start;
         d[t] = reinterpret_cast<uint8_t *>(tb_.out_int[t]) + sample_frame_bytes(io.out_format) * (size_t)first_frame;
     }
+    if (io.dither == UMX_DITHER_SHAPED) // (a UMX_SAMPLE_S16 output: sample_io_refusal)
+        return launch_shaped_encode(n_host, s, d, count, first_frame, io.dither_seed, acc, words, st);
     launch_encode(io.out_format, n_host, s, d, count, first_frame, io.dither != 0, io.dither_seed, acc, st, words);
 }
 
@@ -196,12 +202,14 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
             flac(nullptr);
         return;
     }
-    // (a rescaled integer or FLAC track: its encode counts what it clamps itself, with the divisor it forms)
-    launch_stem_levels(n_host, s, count, first_frame, rescale ? UMX_SAMPLE_F32 : j.opt.clip_format(), io.dither != 0, io.dither_seed, tb_.lev, st);
+    // (a rescaled integer or FLAC track: its encode counts what it clamps itself, with the divisor it forms; so does a shaped encode,
+    // DESIGN 32, rescaled or not: the stateless sample_clips cannot know the error that was fed back)
+    const bool shaped = io.dither == UMX_DITHER_SHAPED;
+    launch_stem_levels(n_host, s, count, first_frame, rescale || shaped ? UMX_SAMPLE_F32 : j.opt.clip_format(), io.dither != 0, io.dither_seed, tb_.lev, st);
     // the words the divisor comes from: the record's peak words, or (UMX_TRUE_PEAK_RESCALE) the true-peak record, final by now
     const uint32_t *words = j.opt.true_peak_rescale() ? tb_.tp : levels_peak_words(tb_.lev);
     if (integer)
-        track_encode(tb_, io, n_host, src, src_start, count, first_frame, rescale ? tb_.lev : nullptr, st, words);
+        track_encode(tb_, io, n_host, src, src_start, count, first_frame, rescale || shaped ? tb_.lev : nullptr, st, rescale || !shaped ? words : nullptr);
     else if (j.opt.flac_bits)
         flac(rescale ? words : nullptr);
     else if (rescale)
@@ -320,6 +328,11 @@ int umx_hip_ctx::track_rate_plan(int rate, int length_at_rate, const char *too_l
 int umx_hip_ctx::admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt, const float *audio, int rate, int length_at_rate, bool leaves_whole)
 {
     j.opt = opt;
+    if (const char *why = shaped_rate_refusal(opt.io, rate)) // DESIGN 32 (before anything grows or is launched)
+    {
+        set_error(why);
+        return UMX_ERR_ARG;
+    }
     if (int rc = track_bufs_grow(acc, (size_t)j.L2))
         return rc;
     if (j.rs.rate)

@@ -4,6 +4,8 @@
 //               lanes and a rerun after a timeout give the same bits.  h = the 32-bit mixer below,
 //               a = h(seed + 0x9e3779b9 (2 m + ch + 1)), w = h(a ^ (uint32)k), d = ((w & 0xffff) + (w >> 16) - 65535) / 65536: the sum
 //               of two uniform 16-bit integers, in (-1, 1), every step exact in fp32.  Both integer formats add it in their own LSB.
+//   shaped      UMX_DITHER_SHAPED: the 16-bit encode with five taps of error feedback, restarted every SHAPED_BLOCK frames of
+//               the caller's track: shaped_round, one step of it, and dither_mode_refusal / shaped_rate_refusal, who may ask for it
 //   a format    a compile-time trait per integer format (SampleS16, SampleS24) with the SAMPLE rule only: round, is_clipped, clamp,
 //               the frame's bytes and the alignment an entry point asks of a buffer.  How frames move through memory is not part of
 //               it: that is encode_frames / launch_decode_as of pcm16.h (a frame per thread) and pcm24.h (a pair of frames per lane).
@@ -62,6 +64,32 @@ struct SampleS16
     }
 };
 
+// Noise-shaped dither of a 16-bit output (UMX_DITHER_SHAPED): the quantisation error of the last five frames is fed back
+// through c (Lipshitz-Vanderkooy-Wannamaker, five taps, E-weighted, 44.1 kHz), the history being ZERO at the first frame of every
+// block of SHAPED_BLOCK frames of the caller's track.  One step, for the host rule and the kernel (pcm16_shaped.h): v = pre(x) *
+// 32767.0f and d = the TPDF dither of the frame go in, r comes out (then SampleS16::is_clipped / ::clamp, as for the other modes).
+// One fp32 rounding per operation, in this order; the error is taken before the clamp, and one that is not finite is dropped.
+constexpr int SHAPED_BLOCK = 4096;
+struct ShapedHistory
+{
+    float e1, e2, e3, e4, e5;
+};
+__host__ __device__ inline float shaped_round(ShapedHistory &h, float v, float d)
+{
+    const float s = ((((2.033f * h.e1 + -2.165f * h.e2) + 1.959f * h.e3) + -1.590f * h.e4) + 0.6149f * h.e5);
+    const float y = v - s;
+    const float r = rintf(y + d);
+    float e = r - y;
+    if (!(fabsf(e) < INFINITY))
+        e = 0.0f;
+    h.e5 = h.e4;
+    h.e4 = h.e3;
+    h.e3 = h.e2;
+    h.e2 = h.e1;
+    h.e1 = e;
+    return r;
+}
+
 // packed 24-bit PCM.  decode x = (float)q * 2^-23, exact; encode v = x * 8388608.0f (exact short of overflow);
 // r = rint((double)v + (dither ? (double)d : 0.0)), the sum formed in double and rounded once (an fp32 v + d falls on a 0.5 grid at
 // |v| >= 2^22, before the rounding); q = NaN ? 0 : clamp(r, -8388608, 8388607).  +1.0f encodes to 8388607 and counts as clipped.
@@ -110,6 +138,17 @@ inline size_t sample_frame_bytes(int format)
 }
 inline bool sample_format_known(int f) { return f == UMX_SAMPLE_F32 || with_sample_format(f, [](auto) { return true; }); }
 
+// io's dither mode where `shaped_goes` says whether UMX_DITHER_SHAPED can be served: the 16-bit PCM encode alone (a 24-bit or fp32
+// output, a FLAC stream and the stateless clip count of the levels launches cannot: DESIGN 32)
+inline const char *dither_mode_refusal(const umx_sample_io *io, bool shaped_goes)
+{
+    if (!io || io->dither == 0 || io->dither == UMX_DITHER_TPDF)
+        return nullptr;
+    if (io->dither != UMX_DITHER_SHAPED)
+        return "sample io: unknown dither mode (0, UMX_DITHER_TPDF or UMX_DITHER_SHAPED)";
+    return shaped_goes ? nullptr : "sample io: shaped dither is for 16-bit outputs (the UMX_SAMPLE_S16 encode, not FLAC, not a levels launch)";
+}
+
 // what an entry point refuses (nullptr: fine): io == nullptr is the fp32 call
 inline const char *sample_io_refusal(const umx_sample_io *io)
 {
@@ -119,9 +158,17 @@ inline const char *sample_io_refusal(const umx_sample_io *io)
         return "sample io: UMX_SAMPLE_FLAC is an input format (FLAC out is flac_bits)";
     if ((!sample_format_known(io->in_format) && io->in_format != UMX_SAMPLE_FLAC) || !sample_format_known(io->out_format))
         return "sample io: unknown sample format (UMX_SAMPLE_F32, UMX_SAMPLE_S16 or UMX_SAMPLE_S24)";
+    if (const char *why = dither_mode_refusal(io, io->out_format == UMX_SAMPLE_S16))
+        return why;
     if (io->dither && io->out_format == UMX_SAMPLE_F32)
         return "sample io: dither goes with a UMX_SAMPLE_S16 or UMX_SAMPLE_S24 output only";
     return nullptr;
+}
+
+// the rates the shaping filter is designed for; a whole-track job at another rate is refused (admit_job)
+inline const char *shaped_rate_refusal(const umx_sample_io &io, int rate)
+{
+    return io.dither == UMX_DITHER_SHAPED && rate != 44100 && rate != 48000 ? "sample io: shaped dither needs a track at 44100 or 48000 Hz" : nullptr;
 }
 
 // would sample x, as it leaves in clip_format, be changed by that format's clamp (an fp32 output: never)

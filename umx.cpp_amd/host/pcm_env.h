@@ -2,6 +2,8 @@
 // (include/umx_hip.h), and the integer buffers of both programs behind one int16 pointer plus the format.
 //   UMX_PCM16=1 / UMX_PCM24=1     every output a 16-bit / 24-bit PCM WAV quantised on the device; not both in one run
 //   UMX_PCM16_DITHER=<seed> / UMX_PCM24_DITHER=<seed>   TPDF dither with that seed; needs its format
+//   UMX_PCM16_SHAPE=1             the 16-bit dither noise-shaped (UMX_DITHER_SHAPED); needs UMX_PCM16=1 and UMX_PCM16_DITHER,
+//                                 and files at 44.1 or 48 kHz (the library refuses another rate)
 #pragma once
 #include "../../include/umx_host.h"
 
@@ -53,8 +55,22 @@ inline bool umx_pcm_from_env(umx_pcm_choice &c, const char *not_offered)
     c.io.out_format = c.pcm24 ? UMX_SAMPLE_S24 : c.pcm16 ? UMX_SAMPLE_S16 : UMX_SAMPLE_F32;
     if (const char *seed = getenv(c.pcm24 ? "UMX_PCM24_DITHER" : "UMX_PCM16_DITHER"))
     {
-        c.io.dither = 1;
+        c.io.dither = UMX_DITHER_TPDF;
         c.io.dither_seed = (unsigned)strtoul(seed, nullptr, 0);
+    }
+    if (on("UMX_PCM16_SHAPE"))
+    {
+        if (!c.pcm16)
+        {
+            fprintf(stderr, "UMX_PCM16_SHAPE: needs UMX_PCM16=1\n");
+            return false;
+        }
+        if (c.io.dither == 0)
+        {
+            fprintf(stderr, "UMX_PCM16_SHAPE: needs UMX_PCM16_DITHER=<seed>\n");
+            return false;
+        }
+        c.io.dither = UMX_DITHER_SHAPED;
     }
     return true;
 }
