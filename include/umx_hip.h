@@ -827,6 +827,64 @@ int umx_hip_flac_probe_host(const void *bytes, size_t n_bytes, umx_flac_info *in
 int umx_hip_flac_decode_host(const void *bytes, size_t n_bytes, float *x, long long n_frames);
 int umx_hip_flac_decode_device(umx_hip_ctx *ctx, const void *bytes_dev, size_t n_bytes, const umx_flac_info *info, float *out_dev,
                                unsigned *status_dev, void *hip_stream);
+/* Look-ahead peak limiter: the third answer to outputs beyond full scale, beside the clamp of the integer encodes and
+ * UMX_CLIP_RESCALE.  Gain dips only around the frames that exceed a ceiling and ramps down before a peak arrives; everything else
+ * leaves bit for bit.  The rule, for one track of N frames whose B = 1 .. 4 outputs x_b[n][ch] leave, and a ceiling c, 0 < c <= 1:
+ *   peak      p[n] = the maximum of |x_b[n][ch]| over all b and both channels, exact (an unsigned maximum of bit patterns); NaN and
+ *             +-inf samples are ignored, and p[n] = 0 if none remain
+ *   required  r[n] = 2^21 if p[n] <= c, else max(1, floor(((double)c / (double)p[n]) * 2097152.0)) with an IEEE double quotient;
+ *             r[n] = 2^21 for n < 0 and n >= N
+ *   window    W = 256 frames for a rate <= 50000 Hz, 512 for <= 100000 Hz, 1024 above (about 5.8 ms at 44.1 kHz)
+ *   minimum   m[k] = min(r[k .. k + W - 1])
+ *   sum       S[n] = m[n - W + 1] + ... + m[n], at most 1024 * 2^21 = 2^31: exact in 32 bits
+ *   gain      q[n] = S[n] / W (a shift), g[n] = (float)q[n] * 2^-21, exactly representable
+ *   output    y_b[n][ch] = x_b[n][ch] * g[n], one fp32 product; one gain for all outputs and channels of the track, so the stems
+ *             still add up to the limited mixture
+ * So g[n] <= r[n] * 2^-21 and |y| <= nextafterf(c, inf) wherever p[n] < 2^20; if no frame within +-(W - 1) exceeds c then g[n] == 1.0f
+ * and y == x bit for bit (a track that never exceeds c leaves exactly as the call without a limiter writes it); NaN stays NaN and inf
+ * stays inf (g > 0) and neither pulls the gain down (the containment contract of DESIGN 28); g[n] depends on the frames n - W + 1 ..
+ * n + W - 1 only, through integers, so tiles, ranges, lanes, reset mode and reruns give the same bits, on the host and on the device.
+ * The report of a track: min_gain, the smallest g, and limited_frames, the number of frames with g < 1.
+ * umx_hip_limit_window: W of a rate; 0 outside 1 .. 655350 Hz.
+ * umx_hip_limit_gain_device: queued on hip_stream, does not wait.  in_dev[b]: frame 0 of output b of a track of n_track frames,
+ *   interleaved stereo fp32, 8-byte aligned, all buffers at the same address modulo 16.  The gains of the frames [first, first + n)
+ *   go to gain_dev[0 .. n); nothing else of gain_dev is written.  report_dev: two 32-bit words that the caller zeroes and that
+ *   calls add to: word 0 becomes the largest 2^21 - q (min_gain = (2^21 - word 0) * 2^-21), word 1 counts the frames with q < 2^21.
+ *   A track cut into ranges gives the gains and the report of one call.  n_track <= 2^30.
+ * umx_hip_limit_apply_device: y = x * gain in place over n frames of 1 .. 4 device buffers (aligned as above), gain_dev[i] the gain of
+ *   frame i.  Nothing is written where the gain is 1.0f.
+ * umx_hip_limit_host: the host restatement, no context and no GPU: gain (n floats) and y (n_buffers buffers, may be x itself) may be
+ *   NULL; *report is always filled.  Reasons are read with umx_hip_last_error(NULL).
+ * umx_hip_separate_tracks_limit: umx_hip_separate_tracks_flac_lpc with a limiter; limit == NULL IS that call, launch for launch, and
+ *   nothing is allocated.  With a limiter a track leaves whole behind its last segment, as a rescaled or a FLAC track does.  On the
+ *   way out: the mix; levels (peak, over_unity, nonfinite), loudness and true peak, which stay measurements of what the separation
+ *   produced, as they are under UMX_CLIP_RESCALE; the gain and the product; then the unchanged encode (fp32, int16, 24-bit or FLAC,
+ *   with its dither).  clipped[m] counts what is encoded, that is, behind the limiter.  report: n_tracks records, or NULL.
+ *   UMX_ERR_ARG with a reason, the context staying usable, for everything umx_hip_separate_tracks_flac_lpc refuses (in its order and
+ *   words), then for a ceiling outside (0, 1] or NaN, then for a limiter together with UMX_CLIP_RESCALE (they answer the same question).
+ * The track queue (umx_hip_separate_queue_*), the shift ensemble, the multi-GPU driver (umx_mgpu.h) and the per-segment
+ * umx_hip_infer_* calls do not offer the limiter. */
+typedef struct umx_limit
+{
+    float ceiling; /* 0 < ceiling <= 1 */
+} umx_limit;
+typedef struct umx_limit_report
+{
+    float min_gain;
+    unsigned long long limited_frames;
+} umx_limit_report;
+int umx_hip_limit_window(int rate);
+int umx_hip_limit_gain_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, long long n_track, long long first, int n, int rate,
+                              float ceiling, float *gain_dev, unsigned *report_dev, void *hip_stream);
+int umx_hip_limit_apply_device(umx_hip_ctx *ctx, int n_buffers, float *const *bufs_dev, int n, const float *gain_dev, void *hip_stream);
+int umx_hip_limit_host(int n_buffers, const float *const *x, long long n, int rate, float ceiling, float *gain, float *const *y,
+                       umx_limit_report *report);
+int umx_hip_separate_tracks_limit(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                                  const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                                  const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,
+                                  double *const *hop_energy, int true_peak_mode, umx_true_peak *true_peak, int flac_bits,
+                                  const size_t *out_cap, size_t *out_bytes, int flac_lpc, const umx_limit *limit, umx_limit_report *report,
+                                  void (*progress)(float, void *), void *progress_user);
 /* testing, host only: the fp32 tap table of a rate pair (taps[phase * K + d + D]; cap floats at most), its phase count L, taps
  * per phase K and first offset -D.  UMX_ERR_ARG for a bad rate or a too small cap (the sizes are still reported). */
 int umx_hip_debug_resample_taps(int rate_in, int rate_out, float *taps, size_t cap, int *phases, int *taps_per_phase,

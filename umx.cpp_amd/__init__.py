@@ -159,6 +159,19 @@ class TruePeak(C.Structure):
 QUEUE_TRUE_PEAK_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJobRate), C.POINTER(Levels), C.POINTER(Loudness), _dp, C.POINTER(TruePeak))
 
 
+class Limit(C.Structure):
+    """umx_limit: the look-ahead peak limiter of a whole-track call; 0 < ceiling <= 1"""
+    _fields_ = [("ceiling", C.c_float)]
+
+
+class LimitReport(C.Structure):
+    """umx_limit_report: the smallest gain of a track and the number of its frames whose gain is below 1"""
+    _fields_ = [("min_gain", C.c_float), ("limited_frames", C.c_ulonglong)]
+
+    def as_tuple(self):
+        return (float(self.min_gain), int(self.limited_frames))
+
+
 class TensorView(C.Structure):
     """include/umx_hip.h: umx_tensor_view"""
     _fields_ = [("name", C.c_char_p), ("target", C.c_int), ("dtype", C.c_int), ("n_dims", C.c_int),
@@ -359,6 +372,15 @@ def hip_lib():
                                                C.c_void_p]
     lib.umx_hip_flac_encode_host_lpc.argtypes = lib.umx_hip_flac_encode_host.argtypes + [C.c_int]
     lib.umx_hip_flac_encode_device_lpc.argtypes = lib.umx_hip_flac_encode_device.argtypes + [C.c_int]
+    # look-ahead peak limiter: the LPC rung plus the limiter and its reports
+    lib.umx_hip_separate_tracks_limit.argtypes = (lib.umx_hip_separate_tracks_flac_lpc.argtypes[:-2]
+                                                  + [C.POINTER(Limit), C.POINTER(LimitReport)] + progress)
+    lib.umx_hip_limit_window.argtypes = [C.c_int]
+    lib.umx_hip_limit_host.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.c_longlong, C.c_int, C.c_float, _fp, C.POINTER(C.c_void_p),
+                                       C.POINTER(LimitReport)]
+    lib.umx_hip_limit_gain_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_float,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.umx_hip_limit_apply_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
     # FLAC in
     lib.umx_hip_flac_probe_host.argtypes = [_u8p, C.c_size_t, C.POINTER(FlacInfo)]
     lib.umx_hip_flac_decode_host.argtypes = [_u8p, C.c_size_t, _fp, C.c_longlong]
@@ -422,7 +444,9 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_true_peak_taps", "umx_hip_true_peak_host",
                "umx_hip_flac_bound", "umx_hip_flac_encode_device", "umx_hip_flac_encode_host", "umx_hip_separate_tracks_flac",
                "umx_hip_flac_encode_device_lpc", "umx_hip_flac_encode_host_lpc", "umx_hip_separate_tracks_flac_lpc",
-               "umx_hip_flac_probe_host", "umx_hip_flac_decode_host", "umx_hip_flac_decode_device"]
+               "umx_hip_flac_probe_host", "umx_hip_flac_decode_host", "umx_hip_flac_decode_device",
+               "umx_hip_limit_window", "umx_hip_limit_gain_device", "umx_hip_limit_apply_device", "umx_hip_limit_host",
+               "umx_hip_separate_tracks_limit"]
 
 
 def sample_io(in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None, shaped=False):
@@ -639,6 +663,27 @@ def flac_decode_host(data, n_frames=None):
     return np.ascontiguousarray(x[:n].T)
 
 
+# --- look-ahead peak limiter ---
+def limit_window(rate):
+    """umx_hip_limit_window: the limiter's window W in frames at `rate` (256 / 512 / 1024; 0 outside 1 .. 655350 Hz)."""
+    return int(hip_lib().umx_hip_limit_window(int(rate)))
+
+
+def limit_host(xs, rate, ceiling):
+    """umx_hip_limit_host: a list of 1 .. 4 (2,n) float32 arrays, the outputs of one track -> (gain (n,) float32, [limited (2,n)
+    arrays], (min_gain, limited_frames)) by the rule of DESIGN 33 (no GPU); UmxError with the reason."""
+    a = [np.ascontiguousarray(np.asarray(x, np.float32).T) for x in xs]
+    n = a[0].shape[0] if a else 0
+    y = [np.empty_like(x) for x in a]
+    gain, rep = np.empty(max(n, 1), np.float32), LimitReport()
+    nb = max(1, len(a))
+    rc = hip_lib().umx_hip_limit_host(len(a), (C.c_void_p * nb)(*[x.ctypes.data for x in a]), n, int(rate), float(ceiling),
+                                      gain.ctypes.data_as(_fp), (C.c_void_p * nb)(*[x.ctypes.data for x in y]), C.byref(rep))
+    if rc != UMX_OK:
+        raise UmxError(rc, hip_lib().umx_hip_last_error(None).decode())
+    return gain[:n], [np.ascontiguousarray(x.T) for x in y], rep.as_tuple()
+
+
 def true_peak_float(bits):
     """The float32 whose bit pattern a true-peak word holds."""
     return np.array([bits], np.uint32).view(np.float32)[0]
@@ -750,7 +795,9 @@ _MEASURE_TAIL = {"umx_hip_separate_tracks_io": (),
                  "umx_hip_separate_tracks_flac": ("clip", "levels", "loudness", "hop_energy", "true_peak_mode", "true_peak", "flac_bits", "out_cap",
                                                   "out_bytes"),
                  "umx_hip_separate_tracks_flac_lpc": ("clip", "levels", "loudness", "hop_energy", "true_peak_mode", "true_peak", "flac_bits",
-                                                      "out_cap", "out_bytes", "flac_lpc")}
+                                                      "out_cap", "out_bytes", "flac_lpc"),
+                 "umx_hip_separate_tracks_limit": ("clip", "levels", "loudness", "hop_energy", "true_peak_mode", "true_peak", "flac_bits", "out_cap",
+                                                   "out_bytes", "flac_lpc", "limit", "limit_report")}
 
 
 class _MeasuredCall:
@@ -759,7 +806,7 @@ class _MeasuredCall:
     tuple the rung's wrapper returns -- outputs, then one entry per record field of its tail."""
 
     def __init__(self, entry_name, handle, waves, io, flags, shift_offsets, rates, gains, clip=CLIP_CLAMP, levels=False, loudness=False,
-                 envelopes=False, true_peak=TRUE_PEAK_OFF, records=False, flac_bits=0, caps=None, flac_lpc=0):
+                 envelopes=False, true_peak=TRUE_PEAK_OFF, records=False, flac_bits=0, caps=None, flac_lpc=0, ceiling=None):
         nt = len(waves)
         self.io = io = sample_io() if io is None else io
         n_out, self.g = (4, None) if gains is None else _mix_gains(gains)
@@ -772,23 +819,26 @@ class _MeasuredCall:
         self.lv = (Levels * nt)() if levels else None
         self.ld = (Loudness * nt)() if loudness else None
         self.tp = (TruePeak * nt)() if records else None
+        self.lim = None if ceiling is None else Limit(float(ceiling))  # None: NULL, the call without a limiter
+        self.lr = None if ceiling is None else (LimitReport * nt)()
         self.env = ep = None
         if envelopes:  # (a rate the call will refuse: any size does)
             self.env = [np.full((m.n_host, 2, kweight_hop_count(L, r)), np.nan) for L, r in zip(m.Ls, rates or [MODEL_RATE] * nt)]
             ep = (C.c_void_p * nt)(*[e.ctypes.data if e.size else None for e in self.env])
         tail = {"clip": int(clip), "levels": self.lv, "loudness": self.ld, "hop_energy": ep, "true_peak_mode": int(true_peak), "true_peak": self.tp,
-                "flac_bits": int(flac_bits), "out_cap": self.cap, "out_bytes": self.got, "flac_lpc": int(flac_lpc)}
+                "flac_bits": int(flac_bits), "out_cap": self.cap, "out_bytes": self.got, "flac_lpc": int(flac_lpc),
+                "limit": None if self.lim is None else C.byref(self.lim), "limit_report": self.lr}
         self.tail = _MEASURE_TAIL[entry_name]
         self.args = ((handle, nt, m.a, m.n, m.rt, m.sh, n_out, None if self.g is None else self.g.ctypes.data_as(_fp), m.o, flags, C.byref(io))
                      + tuple(tail[f] for f in self.tail) + (None, None))
 
     def results(self):
-        got = {"levels": self.lv, "loudness": self.ld, "true_peak": self.tp}
+        got = {"levels": self.lv, "loudness": self.ld, "true_peak": self.tp, "limit_report": self.lr}
         outs = self.m.result()
         if self.m.raw:  # the streams: the bytes the call reported, of every buffer
             outs = [[x[:self.got[i * self.m.n_host + t]] for t, x in enumerate(tr)] for i, tr in enumerate(outs)]
         return (outs,) + tuple(self.env if f == "hop_energy" else (None if got[f] is None else list(got[f]))
-                               for f in self.tail if f in ("levels", "loudness", "hop_energy", "true_peak"))
+                               for f in self.tail if f in ("levels", "loudness", "hop_energy", "true_peak", "limit_report"))
 
 
 def mix_columns(gains):
@@ -1150,6 +1200,29 @@ class Engine:
         return self._separate_many_measured(entry, waves, io, flags, shift_offsets, rates, gains, clip=clip,
                                             levels=levels, loudness=loudness, envelopes=envelopes, true_peak=true_peak, records=records,
                                             flac_bits=flac_bits, caps=caps, **more).results()
+
+    # --- look-ahead peak limiter: gain dips around the overs only, formed and applied on the device ---
+    def separate_many_limit(self, waves, ceiling, flac_bits=0, true_peak=TRUE_PEAK_OFF, clip=CLIP_CLAMP, io=None, flags=0, shift_offsets=None,
+                            rates=None, gains=None, levels=True, loudness=False, envelopes=False, records=False, caps=None, lpc=0):
+        """umx_hip_separate_tracks_limit: separate_many_flac() behind a look-ahead limiter with that ceiling (0 < ceiling <= 1) ->
+        (outputs, [Levels], [Loudness], [hop energies], [TruePeak], [LimitReport per track]); ceiling None passes NULL: the FLAC
+        wrapper's call, and None for the reports."""
+        return self._separate_many_measured("umx_hip_separate_tracks_limit", waves, io, flags, shift_offsets, rates, gains, clip=clip,
+                                            levels=levels, loudness=loudness, envelopes=envelopes, true_peak=true_peak, records=records,
+                                            flac_bits=flac_bits, caps=caps, flac_lpc=lpc, ceiling=ceiling).results()
+
+    def limit_gain_device(self, in_ptrs, n_track, rate, ceiling, gain_ptr, report_ptr, first=0, n=None, hip_stream=None):
+        """umx_hip_limit_gain_device: the gains of frames [first, first + n) of a track of n_track frames (1 .. 4 device buffers (2,n_track)
+        interleaved fp32, frame 0 at in_ptrs[b]) into the n floats at gain_ptr; the two report words at report_ptr are added to."""
+        nb = len(in_ptrs)
+        self._check(self.lib.umx_hip_limit_gain_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n_track), int(first),
+                                                       int(n_track - first if n is None else n), int(rate), float(ceiling), C.c_void_p(gain_ptr),
+                                                       C.c_void_p(report_ptr), hip_stream))
+
+    def limit_apply_device(self, ptrs, n, gain_ptr, hip_stream=None):
+        """umx_hip_limit_apply_device: x *= gain in place over n frames of 1 .. 4 device buffers; nothing is written where the gain is 1."""
+        nb = len(ptrs)
+        self._check(self.lib.umx_hip_limit_apply_device(self.h, nb, (C.c_void_p * max(1, nb))(*ptrs), int(n), C.c_void_p(gain_ptr), hip_stream))
 
     def flac_encode_device(self, in_ptrs, n, rate, bits, out_ptrs, caps, bytes_ptr, first_buffer=0, dither_seed=None, acc_ptr=None,
                            hip_stream=None, lpc=0):

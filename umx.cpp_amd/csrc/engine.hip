@@ -50,6 +50,7 @@
 #include "true_peak.h"
 #include "flac.h"
 #include "flac_decode.h"
+#include "limiter.h"
 #include "gate_debug.h"
 
 using namespace umx;
@@ -600,14 +601,15 @@ struct umx_hip_ctx
         bool true_peak_record = false;  // the caller wants the true-peak record
         int flac_bits = 0;              // flac.h, DESIGN 29: 16 or 24: every track leaves whole, as a FLAC stream of that width's codes
         int flac_lpc = 0;               // 1 .. 12: LPC subframes of up to that order are candidates in every full block
+        float limit = 0.0f;             // limiter.h, DESIGN 33: a ceiling in (0, 1]: every track leaves whole, behind its look-ahead limiter (0: none)
         int n_host() const { return mix ? mix->n_out : 4; } // host buffers per track
         bool rescale() const { return clip_mode == UMX_CLIP_RESCALE; }
         bool measures() const { return levels || rescale(); } // a rescaled track measures for its divisor whether or not the caller wants the record
         bool true_peak_rescale() const { return true_peak == UMX_TRUE_PEAK_RESCALE && rescale(); }
         bool measures_true_peak() const { return true_peak != UMX_TRUE_PEAK_OFF; }
         // a finished span goes through track_leave: something is measured or encoded on its way out
-        bool leaves_measured() const { return io.out_format != UMX_SAMPLE_F32 || measures() || loudness || measures_true_peak() || flac_bits; }
-        bool leaves_whole() const { return rescale() || flac_bits; } // behind its last segment, as ONE region
+        bool leaves_measured() const { return io.out_format != UMX_SAMPLE_F32 || measures() || loudness || measures_true_peak() || flac_bits || limit != 0.0f; }
+        bool leaves_whole() const { return rescale() || flac_bits || limit != 0.0f; } // behind its last segment, as ONE region
         // the integer format whose clamp `clipped` counts: the output's, or the PCM format of a FLAC stream's width
         int clip_format() const { return flac_bits == 16 ? UMX_SAMPLE_S16 : flac_bits == 24 ? UMX_SAMPLE_S24 : io.out_format; }
     };
@@ -630,6 +632,7 @@ struct umx_hip_ctx
         umx_true_peak *true_peak = nullptr; // true_peak.h, DESIGN 26: n_tracks records, or nullptr (opt.true_peak says whether the tracks are measured)
         const size_t *out_cap = nullptr;    // flac.h, DESIGN 29 (opt.flac_bits): the bytes behind every host buffer, and
         size_t *out_bytes = nullptr;        // the bytes of the stream that went there, both [n_host * track + m]
+        umx_limit_report *limit_report = nullptr; // limiter.h, DESIGN 33 (opt.limit): n_tracks records, or nullptr
     };
     int tracks(const TrackRequest &rq);
     int tracks_once(const TrackRequest &rq);
@@ -665,6 +668,12 @@ struct umx_hip_ctx
         uint8_t *flac_in = nullptr;
         size_t cap_flac_in = 0;
         unsigned *flac_in_status = nullptr;
+        // DESIGN 33, only once a job asks for a limiter: a gain per frame of the caller's track (grow-only; cap: frames), and eight words,
+        // zeroed with the levels record: the two report words, and (words 4 .. 7, which nothing writes) the peak words of "no divisor"
+        // for the encode that counts what it clamps
+        float *limit_gain = nullptr;
+        size_t cap_limit_gain = 0;
+        unsigned *limit_words = nullptr;
     };
     std::vector<TrackBufs> trk;
     // the scratch of a FLAC decode (candidates, per-frame words, the samples as coded), grow-only, one for the context:
@@ -724,7 +733,7 @@ struct umx_hip_ctx
         bool whole_region = false;    // not by_region, and track_call itself finishes it behind its last segment as ONE region: the
                                       // frames [lead, lead + length) (a rescaled track)
         TrackMeasure m;               // where its loudness and true-peak launches stand (track_measure_grow)
-        int flac_rate = 0;            // the caller's rate, for STREAMINFO
+        int flac_rate = 0;            // the caller's rate, for STREAMINFO (and, DESIGN 33, for the limiter's window)
         unsigned long long flac_len[4] = {}; // ... and the bytes of its streams, once they are on the host
     };
     struct TrackLane // a lane of one call: its job (nullptr: idle) and the padded frame at which its segment starts
@@ -779,7 +788,7 @@ struct umx_hip_ctx
         void *p;
         size_t bytes;
     };
-    static int track_measure_spans(const TrackJob &j, ZeroSpan spans[3]);
+    static int track_measure_spans(const TrackJob &j, ZeroSpan spans[4]);
     int admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt, const float *audio, int rate, int length_at_rate, bool leaves_whole);
     void track_leave(TrackJob &j, float *const src[4], size_t src_start, int count, long long first_frame, hipStream_t st);
     struct TrackReport // what a job measured, on the host (track_report); only what its options asked for is filled
@@ -788,6 +797,7 @@ struct umx_hip_ctx
         umx_loudness ld = {};
         std::vector<double> hopE;
         umx_true_peak tp = {};
+        umx_limit_report lim = {1.0f, 0};
     };
     hipError_t track_report(const TrackJob &j, int n_host, TrackReport &r);
     hipError_t track_upload_until(TrackJob &j, long long padded_end, hipStream_t st);

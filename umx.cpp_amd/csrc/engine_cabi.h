@@ -388,7 +388,18 @@ struct MeasureArgs // what a whole-track call measures and where the results go:
     int flac_lpc = 0;                     // 0 .. 12, nonzero only with flac_bits
     const size_t *out_cap = nullptr;      // per output buffer: its bytes, and
     size_t *out_bytes = nullptr;          // the bytes of the stream written there
+    const umx_limit *limit = nullptr;     // limiter.h, DESIGN 33: NULL: none
+    umx_limit_report *limit_report = nullptr; // n_tracks records, or NULL
 };
+// what a call with a limiter is refused for, behind everything else: a ceiling that is none, a rescale beside it
+static const char *limit_refusal(const umx_limit *limit, int clip_mode)
+{
+    if (!limit)
+        return nullptr;
+    if (!limit_ceiling_ok(limit->ceiling))
+        return "limiter: the ceiling must lie in (0, 1]";
+    return clip_mode == UMX_CLIP_RESCALE ? "limiter: not with UMX_CLIP_RESCALE (they answer the same question)" : nullptr;
+}
 // what a FLAC call is refused for, behind the sample formats' own checks: a width that is none, a PCM output format.
 // Dither goes with it (the stream's width is the format's LSB), so the formats are checked as if the output were that PCM format.
 static const char *flac_refusal(int flac_bits, int flac_lpc, const umx_sample_io *io)
@@ -437,6 +448,8 @@ static bool track_options_checked(umx_hip_ctx *ctx, const umx_sample_io *io, con
         why = mix_refusal(n_out, gains, spec);
     if (!why)
         why = true_peak_mode_refusal(ma.true_peak_mode, ma.clip_mode);
+    if (!why)
+        why = limit_refusal(ma.limit, ma.clip_mode);
     if (why)
     {
         ctx->set_error(why);
@@ -445,6 +458,7 @@ static bool track_options_checked(umx_hip_ctx *ctx, const umx_sample_io *io, con
     opt.true_peak = ma.true_peak_mode;
     opt.flac_bits = ma.flac_bits;
     opt.flac_lpc = ma.flac_lpc;
+    opt.limit = ma.limit ? ma.limit->ceiling : 0.0f;
     opt.mix = gains ? &spec : nullptr;
     if (io)
         opt.io = *io;
@@ -469,6 +483,7 @@ static umx_hip_ctx::TrackRequest track_request(int n_tracks, const void *const *
     rq.true_peak = ma.true_peak;
     rq.out_cap = ma.out_cap;
     rq.out_bytes = ma.out_bytes;
+    rq.limit_report = ma.limit_report;
     return rq;
 }
 
@@ -912,6 +927,19 @@ int umx_hip_separate_tracks_flac_lpc(umx_hip_ctx *ctx, int n_tracks, const void 
                                      const size_t *out_cap, size_t *out_bytes, int flac_lpc, void (*progress)(float, void *),
                                      void *progress_user)
 {
+    return umx_hip_separate_tracks_limit(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, clip_mode, levels,
+                                         loudness, hop_energy, true_peak_mode, true_peak, flac_bits, out_cap, out_bytes, flac_lpc, nullptr, nullptr,
+                                         progress, progress_user);
+}
+// ---------------------------------------------------------------- look-ahead peak limiter (limiter.h)
+// limit == NULL: the request of umx_hip_separate_tracks_flac_lpc, field for field
+int umx_hip_separate_tracks_limit(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
+                                  const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
+                                  const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,
+                                  double *const *hop_energy, int true_peak_mode, umx_true_peak *true_peak, int flac_bits,
+                                  const size_t *out_cap, size_t *out_bytes, int flac_lpc, const umx_limit *limit, umx_limit_report *report,
+                                  void (*progress)(float, void *), void *progress_user)
+{
     MeasureArgs ma = {clip_mode, levels, loudness, hop_energy, true_peak_mode, true_peak};
     ma.flac_lpc = flac_lpc; // (refused when nonzero without flac_bits)
     if (flac_bits != 0)
@@ -920,7 +948,83 @@ int umx_hip_separate_tracks_flac_lpc(umx_hip_ctx *ctx, int n_tracks, const void 
         ma.out_cap = out_cap;
         ma.out_bytes = out_bytes;
     }
+    if (limit)
+    {
+        ma.limit = limit;
+        ma.limit_report = report;
+    }
     return separate_tracks(ctx, n_tracks, audio_host, length, rate, shift_offset, n_out, gains, out_host, flags, io, ma, progress, progress_user);
+}
+
+int umx_hip_limit_window(int rate) { return limit_window(rate); }
+// (no context: the reason goes where umx_hip_last_error(NULL) reads)
+int umx_hip_limit_host(int n_buffers, const float *const *x, long long n, int rate, float ceiling, float *gain, float *const *y,
+                       umx_limit_report *report)
+{
+    const char *why = n_buffers < 1 || n_buffers > 4 || !x || n < 1 || !report ? "limiter: need 1 .. 4 buffers, n >= 1 and a report"
+                      : !limit_window(rate)                                     ? "limiter: sample rate outside 1 .. 655350 Hz"
+                      : !limit_ceiling_ok(ceiling)                              ? "limiter: the ceiling must lie in (0, 1]"
+                                                                                : nullptr;
+    for (int b = 0; !why && b < n_buffers; ++b)
+        if (!x[b] || (y && !y[b]))
+            why = "limiter: null buffer";
+    if (why)
+    {
+        g_create_error = why;
+        return UMX_ERR_ARG;
+    }
+    limit_host(n_buffers, x, n, limit_window(rate), ceiling, gain, y, *report);
+    return UMX_OK;
+}
+// 1 .. 4 device buffers of interleaved stereo frames as the limiter's kernels read them: 16 bytes a lane
+static bool limit_buffers(umx_hip_ctx *ctx, int n_buffers, const float *const *bufs, int n, const float *p[4])
+{
+    if (!device_buffers(ctx, "limiter", n_buffers, bufs, n, 0, p))
+        return false;
+    if (limit_phase(n_buffers, p) < 0)
+        ctx->set_error("limiter: the buffers must be 8-byte aligned and share their address modulo 16");
+    return limit_phase(n_buffers, p) >= 0;
+}
+int umx_hip_limit_gain_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, long long n_track, long long first, int n, int rate,
+                              float ceiling, float *gain_dev, unsigned *report_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    const float *src[4] = {};
+    if (!limit_buffers(ctx, n_buffers, in_dev, n, src))
+        return UMX_ERR_ARG;
+    const char *why = !limit_window(rate)                                                 ? "limiter: sample rate outside 1 .. 655350 Hz"
+                      : !limit_ceiling_ok(ceiling)                                        ? "limiter: the ceiling must lie in (0, 1]"
+                      : !gain_dev || !report_dev                                          ? "limiter: need the gains and the report words"
+                      : n_track > 0x7fffffff / 2 || first < 0 || first > n_track - n      ? "limiter: need n_track <= 2^30 - 1 and 0 <= first, first + n <= n_track"
+                                                                                          : nullptr;
+    if (why)
+    {
+        ctx->set_error(why);
+        return UMX_ERR_ARG;
+    }
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    launch_limit_gain(n_buffers, reinterpret_cast<const float2 *const *>(src), n_track, first, n, limit_window(rate), ceiling, gain_dev, report_dev,
+                      (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
+}
+int umx_hip_limit_apply_device(umx_hip_ctx *ctx, int n_buffers, float *const *bufs_dev, int n, const float *gain_dev, void *hip_stream)
+{
+    if (!ctx)
+        return UMX_ERR_ARG;
+    const float *bufs[4] = {};
+    if (!limit_buffers(ctx, n_buffers, bufs_dev, n, bufs))
+        return UMX_ERR_ARG;
+    if (!gain_dev)
+    {
+        ctx->set_error("limiter: need the gains");
+        return UMX_ERR_ARG;
+    }
+    UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
+    launch_limit_apply(n_buffers, reinterpret_cast<float2 *const *>(bufs_dev), n, gain_dev, (hipStream_t)hip_stream);
+    UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
+    return UMX_OK;
 }
 // ---------------------------------------------------------------- FLAC in (flac_decode.h)
 // (no context: the reasons of the two host calls go where umx_hip_last_error(NULL) reads)

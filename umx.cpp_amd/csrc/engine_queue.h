@@ -360,7 +360,7 @@ int umx_hip_ctx::queue_run(umx_queue_next_fn next, const QueueDone &done, void *
                 sp.n[7] = state_floats();
                 sp.count = TRACK_BEGIN_SPANS;
                 launch_track_begin(sp, st);
-                ZeroSpan spans[3]; // ... and what the job measures into (also on a restart: it measures from zero again)
+                ZeroSpan spans[4]; // ... and what the job measures into (also on a restart: it measures from zero again)
                 for (int k = 0, n = track_measure_spans(*jb, spans); k < n; ++k)
                     (void)hipMemsetAsync(spans[k].p, 0, spans[k].bytes, st);
             }

@@ -194,8 +194,19 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
         launch_flac(j.opt.flac_bits, j.opt.flac_lpc, n_host, s, count, j.flac_rate, 0, io.dither != 0, io.dither_seed, words, words ? tb_.lev : nullptr, flac_slots,
                     flac_sizes, flac_offsets, tb_.flac_out, tb_.flac_bytes, st);
     };
+    // A limited job (its span is the whole track): behind everything that measures what the separation produced, in front
+    // of the encode -- the gains of these frames from the track's frames (limit_gain_kernel reads a window to both sides), then the
+    // product in place.  Its encode counts what it still clamps itself, over "no divisor": the zero words behind the report's.
+    const bool limited = j.opt.limit != 0.0f;
+    auto limit = [&]() {
+        launch_limit_gain(n_host, s0, end, first_frame, count, limit_window(j.flac_rate), j.opt.limit, tb_.limit_gain + first_frame, tb_.limit_words, st);
+        launch_limit_apply(n_host, sw, count, tb_.limit_gain + first_frame, st);
+    };
+    const uint32_t *const no_divisor = limited ? tb_.limit_words + 4 : nullptr;
     if (!j.opt.measures())
     {
+        if (limited)
+            limit();
         if (integer)
             track_encode(tb_, io, n_host, src, src_start, count, first_frame, nullptr, st);
         else if (j.opt.flac_bits)
@@ -205,7 +216,17 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
     // (a rescaled integer or FLAC track: its encode counts what it clamps itself, with the divisor it forms; so does a shaped encode,
     // DESIGN 32, rescaled or not: the stateless sample_clips cannot know the error that was fed back)
     const bool shaped = io.dither == UMX_DITHER_SHAPED;
-    launch_stem_levels(n_host, s, count, first_frame, rescale || shaped ? UMX_SAMPLE_F32 : j.opt.clip_format(), io.dither != 0, io.dither_seed, tb_.lev, st);
+    launch_stem_levels(n_host, s, count, first_frame, rescale || shaped || limited ? UMX_SAMPLE_F32 : j.opt.clip_format(), io.dither != 0, io.dither_seed,
+                       tb_.lev, st);
+    if (limited) // (never rescaled: refused)
+    {
+        limit();
+        if (integer)
+            track_encode(tb_, io, n_host, src, src_start, count, first_frame, tb_.lev, st, shaped ? nullptr : no_divisor);
+        else if (j.opt.flac_bits)
+            flac(no_divisor);
+        return;
+    }
     // the words the divisor comes from: the record's peak words, or (UMX_TRUE_PEAK_RESCALE) the true-peak record, final by now
     const uint32_t *words = j.opt.true_peak_rescale() ? tb_.tp : levels_peak_words(tb_.lev);
     if (integer)
@@ -248,6 +269,12 @@ hipError_t umx_hip_ctx::track_report(const TrackJob &j, int n_host, TrackReport 
         if (e == hipSuccess)
             true_peak_report(words, n_host, true_peak_factor(j.m.rate), r.tp);
     }
+    if (e == hipSuccess && opt.limit != 0.0f)
+    {
+        e = hipMemcpy(words, j.acc->limit_words, 2 * sizeof(unsigned), hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            limit_report_of(words, r.lim);
+    }
     return e;
 }
 
@@ -282,14 +309,25 @@ int umx_hip_ctx::track_measure_grow(TrackBufs &tb_, TrackJob &j, int rate, int l
             return UMX_ERR_ARG;
         j.m.begin(rate, length_at_rate);
         if (!tb_.tp)
-            return dalloc(&tb_.tp, 4, true);
+            if (int rc = dalloc(&tb_.tp, 4, true))
+                return rc;
+    }
+    if (opt.limit != 0.0f) // the gains of the caller's track, the report words and the zero words behind them
+    {
+        if (refused("limiter", true))
+            return UMX_ERR_ARG;
+        if (int rc = grow_only<float>({{&tb_.limit_gain, 1}}, tb_.cap_limit_gain, (size_t)length_at_rate))
+            return rc;
+        if (!tb_.limit_words)
+            return dalloc(&tb_.limit_words, 8, true);
     }
     return UMX_OK;
 }
 
-// What a measuring job zeroes before its first segment, in this order: the levels record, the hop energies, the true-peak words.
+// What a measuring job zeroes before its first segment, in this order: the levels record, the hop energies, the true-peak words, the
+// limiter's words.
 // Returns how many of `spans` are filled.  tracks_once zeroes them with the accumulators, the queue on the stream of the job's first call.
-int umx_hip_ctx::track_measure_spans(const TrackJob &j, ZeroSpan spans[3])
+int umx_hip_ctx::track_measure_spans(const TrackJob &j, ZeroSpan spans[4])
 {
     int n = 0;
     if (j.opt.measures())
@@ -298,6 +336,8 @@ int umx_hip_ctx::track_measure_spans(const TrackJob &j, ZeroSpan spans[3])
         spans[n++] = {j.acc->hopE, sizeof(double) * j.m.hop_doubles(j.opt.n_host())};
     if (j.opt.measures_true_peak())
         spans[n++] = {j.acc->tp, 4 * sizeof(unsigned)};
+    if (j.opt.limit != 0.0f)
+        spans[n++] = {j.acc->limit_words, 8 * sizeof(unsigned)};
     return n;
 }
 
@@ -323,7 +363,7 @@ int umx_hip_ctx::track_rate_plan(int rate, int length_at_rate, const char *too_l
 // another rate, its j.rs (track_rate_plan); `acc` is the accumulator set it will write, `audio` its host audio of length_at_rate
 // frames at `rate` -- the rate and length the caller sees --, leaves_whole: it is an ensemble lane.  The set grows by what the job
 // needs, in this order (a failed allocation returns at once): accumulators, native-rate staging (a job with j.rs), int16 side, the
-// measuring side (track_measure_grow: levels record, hop energies, true-peak words); then the job is filled.  When the driver zeroes
+// measuring side (track_measure_grow: levels record, hop energies, true-peak words, the limiter's gains and words); then the job is filled.  When the driver zeroes
 // what, and on which stream, is the driver's; what a measuring job zeroes is track_measure_spans.
 int umx_hip_ctx::admit_job(TrackJob &j, TrackBufs &acc, const TrackOptions &opt, const float *audio, int rate, int length_at_rate, bool leaves_whole)
 {
@@ -722,7 +762,7 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
         for (int t = 0; t < 4; ++t)
             UMX_HIP_CHECK(hipMemset(tb_.out[t], 0, sizeof(float) * 2 * frames));
         UMX_HIP_CHECK(hipMemset(tb_.sumw, 0, sizeof(float) * frames));
-        ZeroSpan spans[3];
+        ZeroSpan spans[4];
         for (int k = 0, n = track_measure_spans(job[ln], spans); k < n; ++k)
             UMX_HIP_CHECK(hipMemset(spans[k].p, 0, spans[k].bytes));
     }
@@ -907,6 +947,8 @@ int umx_hip_ctx::tracks_once(const TrackRequest &rq)
             rq.true_peak[ln] = r.tp;
         for (int t = 0; t < n_host && opt.flac_bits; ++t)
             rq.out_bytes[n_host * ln + t] = (size_t)job[ln].flac_len[t];
+        if (rq.limit_report && opt.limit != 0.0f)
+            rq.limit_report[ln] = r.lim;
     }
     return UMX_OK;
 }

@@ -12,6 +12,11 @@
 //                            true_peak <file> dbtp=<dBTP> linear=<%.9g> factor=<F>                            (-inf is printed as -inf)
 //                            rescale: also, UMX_CLIP=rescale divides by 1.01 * the largest TRUE peak of the file's outputs instead of
 //                            their sample peak; refused without UMX_CLIP=rescale.
+//   UMX_LIMIT=<dB, <= 0>     (umx-cli) a look-ahead peak limiter in front of every encode: ceiling = (float)pow(10, dB / 20),
+//                            for example UMX_LIMIT=-1; gain dips only around the overs, the rest of the track leaves as it was; one line
+//                            per output file: limit <file> min_gain_db=<dB> limited_frames=<n>
+//                            Not with UMX_CLIP=rescale (they answer the same question); umx-batch refuses it (the track queue does not
+//                            offer the limiter).
 // All go with UMX_PCM16, UMX_MIX, UMX_TARGETS / UMX_RESIDUAL and UMX_RESAMPLE, through umx-batch's queue and its pass-by-pass loop;
 // not with UMX_SHIFTS > 1 or UMX_CLI_PER_SEGMENT (the shift ensemble and the per-segment calls do not offer them).
 #pragma once
@@ -96,6 +101,34 @@ inline bool umx_clip_from_env(umx_clip_choice &c, const char *not_offered)
     if (c.true_peak == UMX_TRUE_PEAK_RESCALE && c.clip_mode != UMX_CLIP_RESCALE)
         return refuse("UMX_TRUE_PEAK=rescale: needs UMX_CLIP=rescale (it says which peak the divisor comes from)");
     return true;
+}
+
+// UMX_LIMIT: unset or empty leaves `on` false.  false: refused, message on stderr -- a value that is no number <= 0, then
+// not_offered (the reason this run cannot take it; nullptr: it can), then UMX_CLIP=rescale beside it.
+inline bool umx_limit_from_env(umx_limit &limit, bool &on, int clip_mode, const char *not_offered)
+{
+    on = false;
+    const char *text = getenv("UMX_LIMIT");
+    if (!text || !*text)
+        return true;
+    char *end = nullptr;
+    const double db = strtod(text, &end);
+    const char *why = end == text || *end || !(db <= 0.0) || !((float)std::pow(10.0, db / 20.0) > 0.0f) ? "need a ceiling in dB, a number <= 0 (for example -1)"
+                      : not_offered                                                                      ? not_offered
+                      : clip_mode == UMX_CLIP_RESCALE ? "does not go with UMX_CLIP=rescale (they answer the same question)"
+                                                      : nullptr;
+    if (why)
+    {
+        fprintf(stderr, "UMX_LIMIT: %s\n", why);
+        return false;
+    }
+    limit.ceiling = (float)std::pow(10.0, db / 20.0);
+    on = true;
+    return true;
+}
+inline void umx_limit_print(const char *file, const umx_limit_report &r)
+{
+    printf("limit %s min_gain_db=%.6f limited_frames=%llu\n", file, 20.0 * std::log10((double)r.min_gain), r.limited_frames);
 }
 
 // what a run measured of one track: the records its choice asked for are filled

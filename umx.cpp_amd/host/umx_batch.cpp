@@ -211,6 +211,10 @@ int main(int argc, const char **argv)
     umx_clip_choice clipc;
     if (!umx_clip_from_env(clipc, nullptr))
         return 1;
+    umx_limit limit = {};
+    bool limited = false; // (never true: the track queue does not offer the limiter)
+    if (!umx_limit_from_env(limit, limited, clipc.clip_mode, "umx-batch runs the track queue, which does not offer the limiter (umx-cli does)"))
+        return 1;
     const bool resample = env_int("UMX_RESAMPLE", 0) != 0;
     umx_sample_io io = pcmc.io;
     // one input format per run: packed 24-bit when every file's head says 24-bit PCM (UMX_PCM24 only), else int16 when every file's head

@@ -47,6 +47,10 @@
 //   UMX_TRUE_PEAK=1|rescale   one `true_peak <file> dbtp=<dBTP> linear=<x> factor=<F>` line per file written, the oversampled peak
 //                    measured on the device (umx_hip_separate_tracks_true_peak; host/clip_env.h); rescale: UMX_CLIP=rescale
 //                    (required) divides by the true peak instead of the sample peak.  Goes where UMX_LOUDNESS goes.  Unset or 0: today's output
+//   UMX_LIMIT=<dB, <= 0>   a look-ahead peak limiter in front of every encode (umx_hip_separate_tracks_limit; host/clip_env.h):
+//                    ceiling 10^(dB/20), gain dips only around the overs; one `limit <file> min_gain_db=<dB> limited_frames=<n>` line per file
+//                    written.  Goes where UMX_LEVELS goes and with every output format; not with UMX_CLIP=rescale, UMX_SHIFTS > 1 or
+//                    UMX_CLI_PER_SEGMENT=1.  Unset: today's files and output
 #include "../../include/umx_host.h"
 #include "clip_env.h"
 #include "mix_env.h"
@@ -179,6 +183,14 @@ int main(int argc, const char **argv)
         fprintf(stderr, "UMX_FLAC_LPC: %s\n", flac_bits ? "need 0 .. 12" : "needs UMX_FLAC=16|24");
         return 1;
     }
+    umx_limit limit = {};
+    umx_limit_report limit_report = {1.0f, 0};
+    bool limited = false;
+    if (!umx_limit_from_env(limit, limited, clipc.clip_mode,
+                            shifts > 1                               ? "the shift ensemble (UMX_SHIFTS > 1) does not offer the limiter"
+                            : env_int("UMX_CLI_PER_SEGMENT", 0) != 0 ? "UMX_CLI_PER_SEGMENT=1 does not offer the limiter"
+                                                                     : nullptr))
+        return 1;
     umx_measured measured;
     umx_sample_io io = pcmc.io;
     printf("umx-cli (MI355X / gfx950) main driver program\n");
@@ -314,11 +326,11 @@ int main(int argc, const char **argv)
         void *out_io[4]; // (read as the formats say)
         for (int t = 0; t < 4; ++t)
             out_io[t] = flac_bits ? (void *)stems_flac[t].data() : pcmc.active() ? (void *)stems_int[t].data() : (void *)stems[t].data();
-        if (umx_hip_separate_tracks_flac_lpc(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out_io,
-                                             hb.flags, &io, clipc.clip_mode, clipc.levels ? &measured.levels : nullptr,
-                                             clipc.loudness ? &measured.loudness : nullptr, nullptr, clipc.true_peak,
-                                             clipc.true_peak != UMX_TRUE_PEAK_OFF ? &measured.true_peak : nullptr, flac_bits, flac_cap, flac_bytes,
-                                             flac_lpc, print_progress, nullptr))
+        if (umx_hip_separate_tracks_limit(ctx, 1, &in, &n, resample ? &rate : nullptr, &offset, mixc.n_out, mixed ? mixc.gains : nullptr, out_io,
+                                          hb.flags, &io, clipc.clip_mode, clipc.levels ? &measured.levels : nullptr,
+                                          clipc.loudness ? &measured.loudness : nullptr, nullptr, clipc.true_peak,
+                                          clipc.true_peak != UMX_TRUE_PEAK_OFF ? &measured.true_peak : nullptr, flac_bits, flac_cap, flac_bytes,
+                                          flac_lpc, limited ? &limit : nullptr, &limit_report, print_progress, nullptr))
         {
             fprintf(stderr, "inference failed: %s\n", umx_hip_last_error(ctx));
             return 1;
@@ -360,6 +372,8 @@ int main(int argc, const char **argv)
             return 1;
         }
         umx_measured_print(p.c_str(), clipc, measured, t);
+        if (limited)
+            umx_limit_print(p.c_str(), limit_report);
     }
     umx_wav_free(audio);
     umx_wav_free_pcm16(audio_int);
