@@ -863,15 +863,46 @@ int umx_hip_flac_decode_device(umx_hip_ctx *ctx, const void *bytes_dev, size_t n
  *   UMX_ERR_ARG with a reason, the context staying usable, for everything umx_hip_separate_tracks_flac_lpc refuses (in its order and
  *   words), then for a ceiling outside (0, 1] or NaN, then for a limiter together with UMX_CLIP_RESCALE (they answer the same question).
  * The track queue (umx_hip_separate_queue_*), the shift ensemble, the multi-GPU driver (umx_mgpu.h) and the per-segment
- * umx_hip_infer_* calls do not offer the limiter. */
+ * umx_hip_infer_* calls do not offer the limiter.
+ *
+ * The true-peak detector (detector = UMX_LIMIT_TRUE_PEAK): a ceiling worded in dBTP.  A tone at fs/4 with 45 degrees of
+ * phase reads 3 dB higher between the samples than at them, and the sample detector lets it through untouched.  For a track of N
+ * frames at `rate`, F, the taps h and the values y_b(k, f)[ch] are exactly those of the true-peak rule above: phases f = 1 .. F-1,
+ * fp32 fused multiply-adds in the stated order, frames outside [0, N) read as +0.  y(k, f) lies at time k + f/F, between the frames k
+ * and k + 1.
+ *   between   e[n] = the unsigned maximum of the bit patterns of |y_b(n, f)[ch]| over b, ch and f; a NaN or +-inf value contributes
+ *             nothing; e[n] = 0 if nothing remains, and 0 at F = 1; e[-1] = 0
+ *   peak      p[n] = max(s[n], e[n], e[n-1]), s[n] the sample peak of the rule above (NaN and inf ignored): a point between two
+ *             frames binds the gain of both
+ *   r, W, m, S, q, g and y = x g: the rule above with this p; nothing behind p changes
+ * So g[n] <= r[n] * 2^-21, as before; if no frame within +-(W - 1) has p > c then y == x bit for bit; at 192 kHz (F = 1) the gains are
+ * the sample detector's, bit for bit; g[n] depends on the frames n - W + 1 - 24/F .. n + W - 1 + 24/F only, through fixed-order fp32
+ * chains and integers, so tiles, ranges, lanes, reset mode, reruns, host and device all give the same bits.  NaN and inf pass and do
+ * not pull the gain down; within 24/F frames of a sample that is not finite the interpolated values are not finite either and are
+ * ignored, so only the sample peaks detect there.
+ * The true peak of the LIMITED output is not bounded to the bit: the interpolator reads up to 24 frames (24/F before and after a
+ * point) and the gain moves across them.  Where the gain is constant over that reach, TP(y) <= c (1 + 1e-5): g p <= c, one product
+ * rounding per sample, 48/F fma roundings of 2^-24 each, a per-phase sum of |h| below 2.5.  Everywhere else the report says what
+ * happened: true_peak_after, the largest true peak (the rule above) over the track's outputs as they leave the limiter, measured on
+ * the limited fp32 buffers behind the product and in front of the encode; filled only under UMX_LIMIT_TRUE_PEAK, else 0.
+ * The true-peak detector takes 8000 .. 192000 Hz, the range the interpolator is defined on; the sample detector keeps its range.
+ * umx_hip_limit_gain_tp_device: umx_hip_limit_gain_device under the true-peak detector, argument for argument; the words of r between
+ *   its two launches are the context's (grow-only), so calls on one context are queued on one stream or ordered by the caller.
+ * umx_hip_limit_tp_host: umx_hip_limit_host under the true-peak detector; with y it fills report->true_peak_after from y.
+ * umx_hip_separate_tracks_limit refuses, behind everything above, a detector that is neither of the two, and the true-peak detector
+ * for a track at a rate outside 8000 .. 192000 Hz.  A zero-initialised umx_limit beside its ceiling is the sample detector. */
+#define UMX_LIMIT_SAMPLE_PEAK 0
+#define UMX_LIMIT_TRUE_PEAK 1
 typedef struct umx_limit
 {
     float ceiling; /* 0 < ceiling <= 1 */
+    int detector;  /* UMX_LIMIT_SAMPLE_PEAK or UMX_LIMIT_TRUE_PEAK */
 } umx_limit;
 typedef struct umx_limit_report
 {
     float min_gain;
     unsigned long long limited_frames;
+    float true_peak_after; /* UMX_LIMIT_TRUE_PEAK only (else 0) */
 } umx_limit_report;
 int umx_hip_limit_window(int rate);
 int umx_hip_limit_gain_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, long long n_track, long long first, int n, int rate,
@@ -879,6 +910,10 @@ int umx_hip_limit_gain_device(umx_hip_ctx *ctx, int n_buffers, const float *cons
 int umx_hip_limit_apply_device(umx_hip_ctx *ctx, int n_buffers, float *const *bufs_dev, int n, const float *gain_dev, void *hip_stream);
 int umx_hip_limit_host(int n_buffers, const float *const *x, long long n, int rate, float ceiling, float *gain, float *const *y,
                        umx_limit_report *report);
+int umx_hip_limit_gain_tp_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, long long n_track, long long first, int n, int rate,
+                                 float ceiling, float *gain_dev, unsigned *report_dev, void *hip_stream);
+int umx_hip_limit_tp_host(int n_buffers, const float *const *x, long long n, int rate, float ceiling, float *gain, float *const *y,
+                          umx_limit_report *report);
 int umx_hip_separate_tracks_limit(umx_hip_ctx *ctx, int n_tracks, const void *const *audio_host, const int *length, const int *rate,
                                   const int *shift_offset, int n_out, const float *gains, void *const *out_host, unsigned flags,
                                   const umx_sample_io *io, int clip_mode, umx_levels *levels, umx_loudness *loudness,

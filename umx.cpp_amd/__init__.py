@@ -159,14 +159,19 @@ class TruePeak(C.Structure):
 QUEUE_TRUE_PEAK_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(QueueJobRate), C.POINTER(Levels), C.POINTER(Loudness), _dp, C.POINTER(TruePeak))
 
 
+LIMIT_SAMPLE_PEAK, LIMIT_TRUE_PEAK = 0, 1  # UMX_LIMIT_*: what the limiter detects on
+
+
 class Limit(C.Structure):
-    """umx_limit: the look-ahead peak limiter of a whole-track call; 0 < ceiling <= 1"""
-    _fields_ = [("ceiling", C.c_float)]
+    """umx_limit: the look-ahead peak limiter of a whole-track call; 0 < ceiling <= 1; detector: LIMIT_SAMPLE_PEAK or
+    LIMIT_TRUE_PEAK"""
+    _fields_ = [("ceiling", C.c_float), ("detector", C.c_int)]
 
 
 class LimitReport(C.Structure):
-    """umx_limit_report: the smallest gain of a track and the number of its frames whose gain is below 1"""
-    _fields_ = [("min_gain", C.c_float), ("limited_frames", C.c_ulonglong)]
+    """umx_limit_report: the smallest gain of a track, the number of its frames whose gain is below 1 and (LIMIT_TRUE_PEAK only, else
+    0) true_peak_after, the largest true peak of the limited outputs"""
+    _fields_ = [("min_gain", C.c_float), ("limited_frames", C.c_ulonglong), ("true_peak_after", C.c_float)]
 
     def as_tuple(self):
         return (float(self.min_gain), int(self.limited_frames))
@@ -378,8 +383,10 @@ def hip_lib():
     lib.umx_hip_limit_window.argtypes = [C.c_int]
     lib.umx_hip_limit_host.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.c_longlong, C.c_int, C.c_float, _fp, C.POINTER(C.c_void_p),
                                        C.POINTER(LimitReport)]
+    lib.umx_hip_limit_tp_host.argtypes = lib.umx_hip_limit_host.argtypes
     lib.umx_hip_limit_gain_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_float,
                                               C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.umx_hip_limit_gain_tp_device.argtypes = lib.umx_hip_limit_gain_device.argtypes
     lib.umx_hip_limit_apply_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
     # FLAC in
     lib.umx_hip_flac_probe_host.argtypes = [_u8p, C.c_size_t, C.POINTER(FlacInfo)]
@@ -446,7 +453,7 @@ HIP_SYMBOLS = ["umx_hip_create", "umx_hip_create_ex", "umx_hip_create_tracks", "
                "umx_hip_flac_encode_device_lpc", "umx_hip_flac_encode_host_lpc", "umx_hip_separate_tracks_flac_lpc",
                "umx_hip_flac_probe_host", "umx_hip_flac_decode_host", "umx_hip_flac_decode_device",
                "umx_hip_limit_window", "umx_hip_limit_gain_device", "umx_hip_limit_apply_device", "umx_hip_limit_host",
-               "umx_hip_separate_tracks_limit"]
+               "umx_hip_separate_tracks_limit", "umx_hip_limit_gain_tp_device", "umx_hip_limit_tp_host"]
 
 
 def sample_io(in_format=SAMPLE_F32, out_format=SAMPLE_F32, dither_seed=None, shaped=False):
@@ -669,16 +676,18 @@ def limit_window(rate):
     return int(hip_lib().umx_hip_limit_window(int(rate)))
 
 
-def limit_host(xs, rate, ceiling):
+def limit_host(xs, rate, ceiling, detector=LIMIT_SAMPLE_PEAK):
     """umx_hip_limit_host: a list of 1 .. 4 (2,n) float32 arrays, the outputs of one track -> (gain (n,) float32, [limited (2,n)
-    arrays], (min_gain, limited_frames)) by the rule of DESIGN 33 (no GPU); UmxError with the reason."""
+    arrays], (min_gain, limited_frames)) by the rule of DESIGN 33 (no GPU); UmxError with the reason.  detector LIMIT_TRUE_PEAK:
+    umx_hip_limit_tp_host."""
+    call = hip_lib().umx_hip_limit_tp_host if detector == LIMIT_TRUE_PEAK else hip_lib().umx_hip_limit_host
     a = [np.ascontiguousarray(np.asarray(x, np.float32).T) for x in xs]
     n = a[0].shape[0] if a else 0
     y = [np.empty_like(x) for x in a]
     gain, rep = np.empty(max(n, 1), np.float32), LimitReport()
     nb = max(1, len(a))
-    rc = hip_lib().umx_hip_limit_host(len(a), (C.c_void_p * nb)(*[x.ctypes.data for x in a]), n, int(rate), float(ceiling),
-                                      gain.ctypes.data_as(_fp), (C.c_void_p * nb)(*[x.ctypes.data for x in y]), C.byref(rep))
+    rc = call(len(a), (C.c_void_p * nb)(*[x.ctypes.data for x in a]), n, int(rate), float(ceiling),
+              gain.ctypes.data_as(_fp), (C.c_void_p * nb)(*[x.ctypes.data for x in y]), C.byref(rep))
     if rc != UMX_OK:
         raise UmxError(rc, hip_lib().umx_hip_last_error(None).decode())
     return gain[:n], [np.ascontiguousarray(x.T) for x in y], rep.as_tuple()
@@ -806,7 +815,8 @@ class _MeasuredCall:
     tuple the rung's wrapper returns -- outputs, then one entry per record field of its tail."""
 
     def __init__(self, entry_name, handle, waves, io, flags, shift_offsets, rates, gains, clip=CLIP_CLAMP, levels=False, loudness=False,
-                 envelopes=False, true_peak=TRUE_PEAK_OFF, records=False, flac_bits=0, caps=None, flac_lpc=0, ceiling=None):
+                 envelopes=False, true_peak=TRUE_PEAK_OFF, records=False, flac_bits=0, caps=None, flac_lpc=0, ceiling=None,
+                 detector=LIMIT_SAMPLE_PEAK):
         nt = len(waves)
         self.io = io = sample_io() if io is None else io
         n_out, self.g = (4, None) if gains is None else _mix_gains(gains)
@@ -819,7 +829,7 @@ class _MeasuredCall:
         self.lv = (Levels * nt)() if levels else None
         self.ld = (Loudness * nt)() if loudness else None
         self.tp = (TruePeak * nt)() if records else None
-        self.lim = None if ceiling is None else Limit(float(ceiling))  # None: NULL, the call without a limiter
+        self.lim = None if ceiling is None else Limit(float(ceiling), int(detector))  # None: NULL, the call without a limiter
         self.lr = None if ceiling is None else (LimitReport * nt)()
         self.env = ep = None
         if envelopes:  # (a rate the call will refuse: any size does)
@@ -1203,21 +1213,25 @@ class Engine:
 
     # --- look-ahead peak limiter: gain dips around the overs only, formed and applied on the device ---
     def separate_many_limit(self, waves, ceiling, flac_bits=0, true_peak=TRUE_PEAK_OFF, clip=CLIP_CLAMP, io=None, flags=0, shift_offsets=None,
-                            rates=None, gains=None, levels=True, loudness=False, envelopes=False, records=False, caps=None, lpc=0):
+                            rates=None, gains=None, levels=True, loudness=False, envelopes=False, records=False, caps=None, lpc=0,
+                            detector=LIMIT_SAMPLE_PEAK):
         """umx_hip_separate_tracks_limit: separate_many_flac() behind a look-ahead limiter with that ceiling (0 < ceiling <= 1) ->
         (outputs, [Levels], [Loudness], [hop energies], [TruePeak], [LimitReport per track]); ceiling None passes NULL: the FLAC
-        wrapper's call, and None for the reports."""
+        wrapper's call, and None for the reports.  detector LIMIT_TRUE_PEAK: the limiter detects on the interpolated
+        waveform, and the reports carry true_peak_after."""
         return self._separate_many_measured("umx_hip_separate_tracks_limit", waves, io, flags, shift_offsets, rates, gains, clip=clip,
                                             levels=levels, loudness=loudness, envelopes=envelopes, true_peak=true_peak, records=records,
-                                            flac_bits=flac_bits, caps=caps, flac_lpc=lpc, ceiling=ceiling).results()
+                                            flac_bits=flac_bits, caps=caps, flac_lpc=lpc, ceiling=ceiling, detector=detector).results()
 
-    def limit_gain_device(self, in_ptrs, n_track, rate, ceiling, gain_ptr, report_ptr, first=0, n=None, hip_stream=None):
+    def limit_gain_device(self, in_ptrs, n_track, rate, ceiling, gain_ptr, report_ptr, first=0, n=None, hip_stream=None,
+                          detector=LIMIT_SAMPLE_PEAK):
         """umx_hip_limit_gain_device: the gains of frames [first, first + n) of a track of n_track frames (1 .. 4 device buffers (2,n_track)
-        interleaved fp32, frame 0 at in_ptrs[b]) into the n floats at gain_ptr; the two report words at report_ptr are added to."""
+        interleaved fp32, frame 0 at in_ptrs[b]) into the n floats at gain_ptr; the two report words at report_ptr are added to.
+        detector LIMIT_TRUE_PEAK: umx_hip_limit_gain_tp_device."""
         nb = len(in_ptrs)
-        self._check(self.lib.umx_hip_limit_gain_device(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n_track), int(first),
-                                                       int(n_track - first if n is None else n), int(rate), float(ceiling), C.c_void_p(gain_ptr),
-                                                       C.c_void_p(report_ptr), hip_stream))
+        call = self.lib.umx_hip_limit_gain_tp_device if detector == LIMIT_TRUE_PEAK else self.lib.umx_hip_limit_gain_device
+        self._check(call(self.h, nb, (C.c_void_p * max(1, nb))(*in_ptrs), int(n_track), int(first), int(n_track - first if n is None else n),
+                         int(rate), float(ceiling), C.c_void_p(gain_ptr), C.c_void_p(report_ptr), hip_stream))
 
     def limit_apply_device(self, ptrs, n, gain_ptr, hip_stream=None):
         """umx_hip_limit_apply_device: x *= gain in place over n frames of 1 .. 4 device buffers; nothing is written where the gain is 1."""

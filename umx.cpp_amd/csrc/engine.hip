@@ -602,6 +602,8 @@ struct umx_hip_ctx
         int flac_bits = 0;              // flac.h, DESIGN 29: 16 or 24: every track leaves whole, as a FLAC stream of that width's codes
         int flac_lpc = 0;               // 1 .. 12: LPC subframes of up to that order are candidates in every full block
         float limit = 0.0f;             // limiter.h, DESIGN 33: a ceiling in (0, 1]: every track leaves whole, behind its look-ahead limiter (0: none)
+        int limit_detector = UMX_LIMIT_SAMPLE_PEAK; // UMX_LIMIT_TRUE_PEAK: the limiter detects on the interpolated waveform
+        bool limit_true_peak() const { return limit != 0.0f && limit_detector == UMX_LIMIT_TRUE_PEAK; }
         int n_host() const { return mix ? mix->n_out : 4; } // host buffers per track
         bool rescale() const { return clip_mode == UMX_CLIP_RESCALE; }
         bool measures() const { return levels || rescale(); } // a rescaled track measures for its divisor whether or not the caller wants the record
@@ -668,14 +670,21 @@ struct umx_hip_ctx
         uint8_t *flac_in = nullptr;
         size_t cap_flac_in = 0;
         unsigned *flac_in_status = nullptr;
-        // DESIGN 33, only once a job asks for a limiter: a gain per frame of the caller's track (grow-only; cap: frames), and eight words,
-        // zeroed with the levels record: the two report words, and (words 4 .. 7, which nothing writes) the peak words of "no divisor"
-        // for the encode that counts what it clamps
+        // DESIGN 33, only once a job asks for a limiter: a gain per frame of the caller's track (grow-only; cap: frames), and twelve words,
+        // the first eight zeroed with the levels record: the two report words, and (words 4 .. 7, which nothing writes) the peak words of
+        // "no divisor" for the encode that counts what it clamps.  Words 8 .. 11 (zeroed and written under the true-peak
+        // detector only): the true-peak words of the limited outputs
         float *limit_gain = nullptr;
         size_t cap_limit_gain = 0;
         unsigned *limit_words = nullptr;
+        // DESIGN 34, only once a job asks for the true-peak detector: r of every frame of the caller's track (grow-only; cap: frames)
+        uint32_t *limit_r = nullptr;
+        size_t cap_limit_r = 0;
     };
     std::vector<TrackBufs> trk;
+    // the words of r between the two launches of umx_hip_limit_gain_tp_device, grow-only, one for the context
+    uint32_t *limit_r = nullptr;
+    size_t cap_limit_r = 0; // words
     // the scratch of a FLAC decode (candidates, per-frame words, the samples as coded), grow-only, one for the context:
     // the decodes of a call are queued behind each other on one stream
     unsigned *flac_in_scratch = nullptr;

@@ -398,7 +398,9 @@ static const char *limit_refusal(const umx_limit *limit, int clip_mode)
         return nullptr;
     if (!limit_ceiling_ok(limit->ceiling))
         return "limiter: the ceiling must lie in (0, 1]";
-    return clip_mode == UMX_CLIP_RESCALE ? "limiter: not with UMX_CLIP_RESCALE (they answer the same question)" : nullptr;
+    if (clip_mode == UMX_CLIP_RESCALE)
+        return "limiter: not with UMX_CLIP_RESCALE (they answer the same question)";
+    return limit_detector_ok(limit->detector) ? nullptr : "limiter: unknown detector (UMX_LIMIT_SAMPLE_PEAK or UMX_LIMIT_TRUE_PEAK)";
 }
 // what a FLAC call is refused for, behind the sample formats' own checks: a width that is none, a PCM output format.
 // Dither goes with it (the stream's width is the format's LSB), so the formats are checked as if the output were that PCM format.
@@ -459,6 +461,7 @@ static bool track_options_checked(umx_hip_ctx *ctx, const umx_sample_io *io, con
     opt.flac_bits = ma.flac_bits;
     opt.flac_lpc = ma.flac_lpc;
     opt.limit = ma.limit ? ma.limit->ceiling : 0.0f;
+    opt.limit_detector = ma.limit ? ma.limit->detector : UMX_LIMIT_SAMPLE_PEAK;
     opt.mix = gains ? &spec : nullptr;
     if (io)
         opt.io = *io;
@@ -958,12 +961,14 @@ int umx_hip_separate_tracks_limit(umx_hip_ctx *ctx, int n_tracks, const void *co
 
 int umx_hip_limit_window(int rate) { return limit_window(rate); }
 // (no context: the reason goes where umx_hip_last_error(NULL) reads)
-int umx_hip_limit_host(int n_buffers, const float *const *x, long long n, int rate, float ceiling, float *gain, float *const *y,
-                       umx_limit_report *report)
+// both detectors' host calls; tp: the true-peak detector's
+static int limit_host_call(bool tp, int n_buffers, const float *const *x, long long n, int rate, float ceiling, float *gain, float *const *y,
+                           umx_limit_report *report)
 {
     const char *why = n_buffers < 1 || n_buffers > 4 || !x || n < 1 || !report ? "limiter: need 1 .. 4 buffers, n >= 1 and a report"
                       : !limit_window(rate)                                     ? "limiter: sample rate outside 1 .. 655350 Hz"
                       : !limit_ceiling_ok(ceiling)                              ? "limiter: the ceiling must lie in (0, 1]"
+                      : tp && !true_peak_rate_ok(rate)                          ? limit_tp_rate_refusal
                                                                                 : nullptr;
     for (int b = 0; !why && b < n_buffers; ++b)
         if (!x[b] || (y && !y[b]))
@@ -973,8 +978,23 @@ int umx_hip_limit_host(int n_buffers, const float *const *x, long long n, int ra
         g_create_error = why;
         return UMX_ERR_ARG;
     }
-    limit_host(n_buffers, x, n, limit_window(rate), ceiling, gain, y, *report);
+    *report = umx_limit_report{};
+    limit_host(n_buffers, x, n, limit_window(rate), ceiling, gain, y, *report, tp ? true_peak_factor(rate) : 1);
+    uint32_t after = 0; // (a limited track's true peak: what the whole-track call measures on the device)
+    for (int b = 0; tp && y && b < n_buffers; ++b)
+        after = true_peak_host(y[b], n, rate, 0, n, after);
+    report->true_peak_after = levels_float(after);
     return UMX_OK;
+}
+int umx_hip_limit_host(int n_buffers, const float *const *x, long long n, int rate, float ceiling, float *gain, float *const *y,
+                       umx_limit_report *report)
+{
+    return limit_host_call(false, n_buffers, x, n, rate, ceiling, gain, y, report);
+}
+int umx_hip_limit_tp_host(int n_buffers, const float *const *x, long long n, int rate, float ceiling, float *gain, float *const *y,
+                          umx_limit_report *report)
+{
+    return limit_host_call(true, n_buffers, x, n, rate, ceiling, gain, y, report);
 }
 // 1 .. 4 device buffers of interleaved stereo frames as the limiter's kernels read them: 16 bytes a lane
 static bool limit_buffers(umx_hip_ctx *ctx, int n_buffers, const float *const *bufs, int n, const float *p[4])
@@ -985,8 +1005,9 @@ static bool limit_buffers(umx_hip_ctx *ctx, int n_buffers, const float *const *b
         ctx->set_error("limiter: the buffers must be 8-byte aligned and share their address modulo 16");
     return limit_phase(n_buffers, p) >= 0;
 }
-int umx_hip_limit_gain_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, long long n_track, long long first, int n, int rate,
-                              float ceiling, float *gain_dev, unsigned *report_dev, void *hip_stream)
+// both detectors' gain calls; tp: the true-peak detector's, its words of r in the context's scratch
+static int limit_gain_call(bool tp, umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, long long n_track, long long first, int n, int rate,
+                           float ceiling, float *gain_dev, unsigned *report_dev, void *hip_stream)
 {
     if (!ctx)
         return UMX_ERR_ARG;
@@ -997,6 +1018,7 @@ int umx_hip_limit_gain_device(umx_hip_ctx *ctx, int n_buffers, const float *cons
                       : !limit_ceiling_ok(ceiling)                                        ? "limiter: the ceiling must lie in (0, 1]"
                       : !gain_dev || !report_dev                                          ? "limiter: need the gains and the report words"
                       : n_track > 0x7fffffff / 2 || first < 0 || first > n_track - n      ? "limiter: need n_track <= 2^30 - 1 and 0 <= first, first + n <= n_track"
+                      : tp && !true_peak_rate_ok(rate)                                    ? limit_tp_rate_refusal
                                                                                           : nullptr;
     if (why)
     {
@@ -1004,10 +1026,28 @@ int umx_hip_limit_gain_device(umx_hip_ctx *ctx, int n_buffers, const float *cons
         return UMX_ERR_ARG;
     }
     UMX_HIP_CHECK_CTX(ctx, hipSetDevice(ctx->device));
-    launch_limit_gain(n_buffers, reinterpret_cast<const float2 *const *>(src), n_track, first, n, limit_window(rate), ceiling, gain_dev, report_dev,
-                      (hipStream_t)hip_stream);
+    if (tp)
+    {
+        if (int rc = ctx->grow_only<uint32_t>({{&ctx->limit_r, 1}}, ctx->cap_limit_r, limit_tp_scratch_words(n, limit_window(rate))))
+            return rc;
+        launch_limit_gain_tp(n_buffers, reinterpret_cast<const float2 *const *>(src), n_track, first, n, rate, ceiling, ctx->limit_r, gain_dev, report_dev,
+                             (hipStream_t)hip_stream);
+    }
+    else
+        launch_limit_gain(n_buffers, reinterpret_cast<const float2 *const *>(src), n_track, first, n, limit_window(rate), ceiling, gain_dev, report_dev,
+                          (hipStream_t)hip_stream);
     UMX_HIP_CHECK_CTX(ctx, hipGetLastError());
     return UMX_OK;
+}
+int umx_hip_limit_gain_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, long long n_track, long long first, int n, int rate,
+                              float ceiling, float *gain_dev, unsigned *report_dev, void *hip_stream)
+{
+    return limit_gain_call(false, ctx, n_buffers, in_dev, n_track, first, n, rate, ceiling, gain_dev, report_dev, hip_stream);
+}
+int umx_hip_limit_gain_tp_device(umx_hip_ctx *ctx, int n_buffers, const float *const *in_dev, long long n_track, long long first, int n, int rate,
+                                 float ceiling, float *gain_dev, unsigned *report_dev, void *hip_stream)
+{
+    return limit_gain_call(true, ctx, n_buffers, in_dev, n_track, first, n, rate, ceiling, gain_dev, report_dev, hip_stream);
 }
 int umx_hip_limit_apply_device(umx_hip_ctx *ctx, int n_buffers, float *const *bufs_dev, int n, const float *gain_dev, void *hip_stream)
 {

@@ -198,9 +198,16 @@ void umx_hip_ctx::track_leave(TrackJob &j, float *const src[4], size_t src_start
     // of the encode -- the gains of these frames from the track's frames (limit_gain_kernel reads a window to both sides), then the
     // product in place.  Its encode counts what it still clamps itself, over "no divisor": the zero words behind the report's.
     const bool limited = j.opt.limit != 0.0f;
+    // Under the true-peak detector: the detector launch in front of the gain launch, which then loads r instead of forming
+    // it, and behind the product the true peak of what the limiter leaves, into words 8 .. 11 (the report's true_peak_after).
     auto limit = [&]() {
-        launch_limit_gain(n_host, s0, end, first_frame, count, limit_window(j.flac_rate), j.opt.limit, tb_.limit_gain + first_frame, tb_.limit_words, st);
+        if (j.opt.limit_true_peak())
+            launch_limit_gain_tp(n_host, s0, end, first_frame, count, j.flac_rate, j.opt.limit, tb_.limit_r, tb_.limit_gain + first_frame, tb_.limit_words, st);
+        else
+            launch_limit_gain(n_host, s0, end, first_frame, count, limit_window(j.flac_rate), j.opt.limit, tb_.limit_gain + first_frame, tb_.limit_words, st);
         launch_limit_apply(n_host, sw, count, tb_.limit_gain + first_frame, st);
+        if (j.opt.limit_true_peak())
+            launch_true_peak(n_host, s0, (int)end, j.flac_rate, first_frame, count, tb_.limit_words + 8, st);
     };
     const uint32_t *const no_divisor = limited ? tb_.limit_words + 4 : nullptr;
     if (!j.opt.measures())
@@ -274,6 +281,11 @@ hipError_t umx_hip_ctx::track_report(const TrackJob &j, int n_host, TrackReport 
         e = hipMemcpy(words, j.acc->limit_words, 2 * sizeof(unsigned), hipMemcpyDeviceToHost);
         if (e == hipSuccess)
             limit_report_of(words, r.lim);
+        if (e == hipSuccess && opt.limit_true_peak()) // the largest true peak of the limited outputs
+        {
+            e = hipMemcpy(words, j.acc->limit_words + 8, sizeof words, hipMemcpyDeviceToHost);
+            r.lim.true_peak_after = levels_float(*std::max_element(words, words + 4));
+        }
     }
     return e;
 }
@@ -316,10 +328,18 @@ int umx_hip_ctx::track_measure_grow(TrackBufs &tb_, TrackJob &j, int rate, int l
     {
         if (refused("limiter", true))
             return UMX_ERR_ARG;
+        if (opt.limit_true_peak() && !true_peak_rate_ok(rate)) // behind every other refusal, before its words of r grow
+        {
+            set_error(limit_tp_rate_refusal);
+            return UMX_ERR_ARG;
+        }
         if (int rc = grow_only<float>({{&tb_.limit_gain, 1}}, tb_.cap_limit_gain, (size_t)length_at_rate))
             return rc;
+        if (opt.limit_true_peak())
+            if (int rc = grow_only<uint32_t>({{&tb_.limit_r, 1}}, tb_.cap_limit_r, limit_tp_scratch_words(length_at_rate, limit_window(rate))))
+                return rc;
         if (!tb_.limit_words)
-            return dalloc(&tb_.limit_words, 8, true);
+            return dalloc(&tb_.limit_words, 12, true);
     }
     return UMX_OK;
 }
@@ -337,7 +357,7 @@ int umx_hip_ctx::track_measure_spans(const TrackJob &j, ZeroSpan spans[4])
     if (j.opt.measures_true_peak())
         spans[n++] = {j.acc->tp, 4 * sizeof(unsigned)};
     if (j.opt.limit != 0.0f)
-        spans[n++] = {j.acc->limit_words, 8 * sizeof(unsigned)};
+        spans[n++] = {j.acc->limit_words, (j.opt.limit_true_peak() ? 12 : 8) * sizeof(unsigned)};
     return n;
 }
 

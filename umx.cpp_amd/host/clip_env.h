@@ -17,6 +17,10 @@
 //                            per output file: limit <file> min_gain_db=<dB> limited_frames=<n>
 //                            Not with UMX_CLIP=rescale (they answer the same question); umx-batch refuses it (the track queue does not
 //                            offer the limiter).
+//   UMX_LIMIT_DETECTOR=sample|true_peak   what UMX_LIMIT detects on: sample (the default, and unset or empty: today's files
+//                            byte for byte) or true_peak, the waveform between the samples too -- a ceiling in dBTP; the line gains
+//                            true_peak_after_db=<dBTP>, the largest true peak of the file's track behind the limiter (-inf for silence).
+//                            Refused without UMX_LIMIT.
 // All go with UMX_PCM16, UMX_MIX, UMX_TARGETS / UMX_RESIDUAL and UMX_RESAMPLE, through umx-batch's queue and its pass-by-pass loop;
 // not with UMX_SHIFTS > 1 or UMX_CLI_PER_SEGMENT (the shift ensemble and the per-segment calls do not offer them).
 #pragma once
@@ -126,9 +130,28 @@ inline bool umx_limit_from_env(umx_limit &limit, bool &on, int clip_mode, const 
     on = true;
     return true;
 }
-inline void umx_limit_print(const char *file, const umx_limit_report &r)
+// UMX_LIMIT_DETECTOR, read behind UMX_LIMIT (`on`: what umx_limit_from_env left): unset or empty leaves the sample detector.  false:
+// refused, message on stderr -- a word that is neither sample nor true_peak, then a detector without UMX_LIMIT.
+inline bool umx_limit_detector_from_env(umx_limit &limit, bool on)
 {
-    printf("limit %s min_gain_db=%.6f limited_frames=%llu\n", file, 20.0 * std::log10((double)r.min_gain), r.limited_frames);
+    const char *text = getenv("UMX_LIMIT_DETECTOR");
+    if (!text || !*text)
+        return true;
+    const bool sample = !strcmp(text, "sample"), tp = !strcmp(text, "true_peak");
+    if ((sample || tp) && on)
+    {
+        limit.detector = tp ? UMX_LIMIT_TRUE_PEAK : UMX_LIMIT_SAMPLE_PEAK;
+        return true;
+    }
+    fprintf(stderr, "UMX_LIMIT_DETECTOR: %s\n", sample || tp ? "needs UMX_LIMIT (it says what the limiter detects on)" : "need sample or true_peak");
+    return false;
+}
+inline void umx_limit_print(const char *file, const umx_limit &limit, const umx_limit_report &r)
+{
+    printf("limit %s min_gain_db=%.6f limited_frames=%llu", file, 20.0 * std::log10((double)r.min_gain), r.limited_frames);
+    if (limit.detector == UMX_LIMIT_TRUE_PEAK)
+        printf(" true_peak_after_db=%.6f", 20.0 * std::log10((double)r.true_peak_after));
+    printf("\n");
 }
 
 // what a run measured of one track: the records its choice asked for are filled

@@ -51,6 +51,8 @@
 //                    ceiling 10^(dB/20), gain dips only around the overs; one `limit <file> min_gain_db=<dB> limited_frames=<n>` line per file
 //                    written.  Goes where UMX_LEVELS goes and with every output format; not with UMX_CLIP=rescale, UMX_SHIFTS > 1 or
 //                    UMX_CLI_PER_SEGMENT=1.  Unset: today's files and output
+//   UMX_LIMIT_DETECTOR=sample|true_peak   what UMX_LIMIT detects on (host/clip_env.h): true_peak reads the waveform between
+//                    the samples too and adds ` true_peak_after_db=<dBTP>` to the line.  Needs UMX_LIMIT.  Unset or sample: today's files
 #include "../../include/umx_host.h"
 #include "clip_env.h"
 #include "mix_env.h"
@@ -190,6 +192,8 @@ int main(int argc, const char **argv)
                             shifts > 1                               ? "the shift ensemble (UMX_SHIFTS > 1) does not offer the limiter"
                             : env_int("UMX_CLI_PER_SEGMENT", 0) != 0 ? "UMX_CLI_PER_SEGMENT=1 does not offer the limiter"
                                                                      : nullptr))
+        return 1;
+    if (!umx_limit_detector_from_env(limit, limited))
         return 1;
     umx_measured measured;
     umx_sample_io io = pcmc.io;
@@ -373,7 +377,7 @@ int main(int argc, const char **argv)
         }
         umx_measured_print(p.c_str(), clipc, measured, t);
         if (limited)
-            umx_limit_print(p.c_str(), limit_report);
+            umx_limit_print(p.c_str(), limit, limit_report);
     }
     umx_wav_free(audio);
     umx_wav_free_pcm16(audio_int);
